@@ -5,7 +5,16 @@
 machinery - workloads, seeded corpora, timed runners, CPU legs, roofline pricing - is bench_common.py, the `also.*` sub-results and the other
 workloads are bench_extras.py.  `python bench.py` is the only entry point.)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--workload c1|c2|c3|c5|c3b|c5h|c5f|c5q|c5l|stage|sql] [--no-also]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--workload c1|c2|c3|c5|c3b|c5h|c5f|c5q|c5l|stage|sql] [--full [--no-also]]
+                    [--dump-outputs DIR]
+
+A plain run (no --full) does what the headline needs and nothing else: set up, W untimed steps, K timed steps, the line.  --full adds
+everything else this file measures or checks - the CPU baselines, the `filter_scan` / `also.*` sub-results and `caller_view` below, the
+N-rank self check, a batch's `against_single_scans`.  --dump-outputs DIR writes what the timed path handed its caller in the last timed
+step as DIR/<name>.npy (float64): `rowids` and `distances` (one list; [queries, k] for the batched workloads, NaN past a query's count);
+the inputs are seeded, so two builds given the same arguments can be compared output for output.  It covers the scan workloads (c2, c3
+and the batched ones); c1, stage, sql and --inprocess refuse it.  --steps K is the number of timed steps of every scan workload; the
+--full sub-results keep their own counts (batched ones: at most 10 after at most 2 warm-up batches).
 
 Default line (BASELINE.json configs[1]): 10M x 384 f32, L2, top-20, single query, corpus resident in HBM, answered by
 the PLAIN f32 scan kernel (vg_scan_kernel; the shadow-copy filter is switched off for this corpus), so that
@@ -15,7 +24,7 @@ PMC FETCH_SIZE figure of profiles/pmc_traffic.json - emitted only while that fil
 A "step" is ONE complete query: upload the query, scan the whole shard, reduce to k candidates, bring the k keys back
 and decode them - what vector_full_scan's xFilter costs once the corpus is staged.
 
-The same run appends (N = 1, default workload only; --no-also skips them, --also filter,c3,c5,matrix,c4,long,clustered,c1 picks):
+--full appends (N = 1, default workload only; --no-also skips them, --also filter,c3,c5,matrix,c4,long,clustered,c1 picks):
   filter_scan  the SAME queries over the SAME corpus through the product's default path for a corpus of this size: the lower-bound
                filter over an int8 shadow copy + exact f32 re-evaluation of the candidates (vg_scan_filter.h).  It answers the
                f32 question with the f32 scan's rowids and distance bits but STREAMS int8: its rate is priced on the bytes it
@@ -41,8 +50,8 @@ non-zero and without printing a line, when fewer than N devices are visible or w
 (VG_BENCH_SHARE_DEVICES=1: the ranks share the visible devices and exchange over gloo - a functional check of the N-rank path on a
 smaller box; --selftest-launch: the launch + exchange + merge plumbing with fabricated keys, no device - tests/test_bench_launch.py.)
 
-cpu_baseline (rank 0, every N) = the reference's own kernel + top-k loop (oracle/_ref/libref_avx2.so, built from /root/reference
-by oracle/Makefile) on ONE host core - the reference is single-threaded - over a bounded sample, timed in this run; all_cores =
+cpu_baseline (--full; rank 0, every N) = the reference's own kernel + top-k loop (oracle/_ref/libref_avx2.so, built from the reference's
+sources by oracle/Makefile) on ONE host core - the reference is single-threaded - over a bounded sample, timed in this run; all_cores =
 a row-split of ONE matrix over every logical core of the host - thread i runs that loop over its range, a query's answer is the merge of
 the per-range lists (checked against the unsplit scan).
 """
@@ -70,6 +79,10 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-rows", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=1024, help="queries per batch (workload c5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baselines, the sub-results (--also), the N-rank self check, caller views")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's rowids and distances as DIR/<name>.npy (float64)")
     ap.add_argument("--no-also", action="store_true", help="default workload: skip the filter_scan / c3 / c5 sub-results")
     ap.add_argument("--also", default="filter,c3,c5,matrix,c4,long,clustered,c1", help="default workload: which sub-results to append (filter,c3,c5,matrix,c4,long,clustered,c1)")
     ap.add_argument("--inprocess", action="store_true",
@@ -78,7 +91,19 @@ def parse():
     ap.add_argument("--selftest-launch", action="store_true",
                     help="no GPU work: every rank fabricates its candidate keys and runs the N-rank exchange + merge + timing plumbing "
                          "over gloo (what tests/test_bench_launch.py drives on a CPU-only box)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and (args.inprocess or args.workload in ("c1", "stage", "sql")):
+        ap.error("--dump-outputs: the scan workloads only (c2, c3 and the batched ones), without --inprocess")
+    if not args.full:                    # a plain run: the headline only
+        args.no_cpu_baseline = args.no_also = True
+    return args
+
+
+def dump_outputs(path, rowids, distances):
+    """--dump-outputs: the last timed step's answer as DIR/rowids.npy and DIR/distances.npy (float64 holds every rowid exactly)"""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rowids.npy"), np.asarray(rowids, dtype=np.float64))
+    np.save(os.path.join(path, "distances.npy"), np.asarray(distances, dtype=np.float64))
 
 
 C4_EXPECTED = os.path.join(ROOT, "tests", "golden", "bench_c4_expected.json")
@@ -274,11 +299,18 @@ def main():
         if args.workload == "c5":
             corpus.set_scan_filter(0)                                 # the f32 matrix-core kernel (the filters are the default for a corpus of this size)
         out = run_batched(args, pkg, torch, corpus, args.workload, n_rows, dim, metric, k, desc, the_dist, shard, n_gpus, rank,
-                          share=share)
+                          share=share, exact_steps=True)
         rccl = rccl_record(torch, dist, share, n_dev) if use_dist else None      # (a collective: every rank)
         if out is not None:
             if rccl is not None:
                 out["rccl"] = rccl
+            if args.dump_outputs:
+                ids, d, cnt = run_batched.last_result
+                ids = np.asarray(ids + 1 if use_dist else ids, dtype=np.float64)      # (merged global positions -> rowids)
+                d = np.array(d, dtype=np.float64)
+                past = np.arange(ids.shape[1])[None, :] >= np.asarray(cnt)[:, None]  # slots past a query's count hold no result
+                ids[past] = d[past] = np.nan
+                dump_outputs(args.dump_outputs, ids, d)
             if not args.no_cpu_baseline:
                 out["cpu_baseline"] = batch_cpu_baseline(args, vt, np_dtype, dim, metric, k, sample=(pkg, torch, n_rows, 42 + rank))
             print(json.dumps(out))
@@ -298,7 +330,7 @@ def main():
     corpus.set_scan_filter(0)
     runner = SingleQueryRunner(pkg, torch, the_dist, shard, corpus, vt, dim, metric, k, n_rows, n_gpus, queries, share=share)
     check = None
-    if args.workload == "c2":
+    if args.workload == "c2" and args.full:
         # The N-rank answer checked against an answer that was NOT computed by N ranks: query 0 over the same seeded shards, scanned
         # one after the other on ONE device and merged on the host (tools/make_bench_c4_expected.py -> tests/golden/bench_c4_expected.json).
         # A wrong merged top-20 ends the run without a line.
@@ -325,6 +357,8 @@ def main():
         if share:
             out["config"]["note"] = "VG_BENCH_SHARE_DEVICES=1: %d ranks share %d device(s), exchange over gloo - a functional check, not a measurement" % (n_gpus, n_dev)
     plain_last = dict(runner.last)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, np.asarray(plain_last["pos"]) + 1, plain_last["dist"])     # (rowid base 1 + rank * rows)
     if rank == 0 and not args.no_cpu_baseline:
         try:
             want = max(args.cpu_sample_rows, min(4_000_000, (os.cpu_count() or 1) * 8192))

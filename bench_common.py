@@ -245,15 +245,18 @@ def cpu_baseline(vt, np_dtype, dim, metric, k, sample_rows, seconds=10.0, all_co
     return out
 
 
-def run_batched(args, pkg, torch, corpus, workload, n_rows, dim, metric, k, desc, dist=None, shard=None, n_gpus=1, rank=0, share=False):
+def run_batched(args, pkg, torch, corpus, workload, n_rows, dim, metric, k, desc, dist=None, shard=None, n_gpus=1, rank=0, share=False,
+                exact_steps=False):
     """config #5: each step = one batch of queries through the batched scan (host queries in, host (position,
     distance) lists out).  The dominant kernel is MFMA-bound: flops = 2 * Q * N * D per launch.
+    exact_steps: time exactly --steps batches after --warmup (the run's own workload); otherwise (the --full sub-results) at most 10
+    after at most 2.
     N > 1: every rank scans its own row-range shard with the same batch, ONE all_gather of nq x k keys per rank
     (160 KB at 1024 x 20), rank 0 merges every query (shard.gather_and_merge_batch) - SURVEY 8e.
     Returns the result line (a dict) on rank 0, None elsewhere."""
     nq = args.batch
     rng = np.random.default_rng(44)
-    steps, warmup = min(args.steps, 10), min(args.warmup, 2)
+    steps, warmup = (args.steps, args.warmup) if exact_steps else (min(args.steps, 10), min(args.warmup, 2))
     quantized = corpus.vtype in (pkg.U8, pkg.I8)
     half = corpus.vtype == pkg.F16
     filt = workload in ("c5f", "c5l")
@@ -303,7 +306,7 @@ def run_batched(args, pkg, torch, corpus, workload, n_rows, dim, metric, k, desc
     q8 = q8 or corpus.last_batch_path() == 7
     peak = I8_MFMA_PEAK_TOPS if (quantized or q8) else (F16_MFMA_PEAK_TF if (half or filt) else F32_MFMA_PEAK_TF)
     single = None
-    if workload == "c5l" and not use_dist:               # what the batch replaces: one scan per query (the plain kernel; HBM-bound)
+    if workload == "c5l" and not use_dist and args.full:  # what the batch replaces: one scan per query (the plain kernel; HBM-bound)
         path = corpus.last_batch_path()
         corpus.set_profiling(False)
         for i in range(3):                               # (the first scans make the corpus' shadow copy for the filter scan)
@@ -550,7 +553,7 @@ def single_query_line(args, pkg, runner, corpus, workload, vt, dim, metric, k, n
     }
     if source:
         out["roofline"]["traffic_source"] = source
-    if n_gpus == 1:
+    if n_gpus == 1 and args.full:
         out["caller_view"] = caller_view(args, corpus, runner, metric, scan_ms)
     return out, prepass_ms
 

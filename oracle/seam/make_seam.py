@@ -6,7 +6,7 @@
 Reads /root/reference/src/sqlite-vector.c where it lies, applies the anchored edits below (each anchor is a few tokens of the reference's
 text - a function name, a struct's closing line - never a copy of its code), writes the result OUT OF TREE (oracle/_ref/ is git-ignored,
 travels to the GPU box) and compiles it with the reference's other sources against include/vectorgpu.h, linked to
-sqlite-vector_amd/libvectorgpu.so.  Test infrastructure: tests/test_seam_binding.py loads the result; the product never does."""
+sqlite-vector_amd/libvectorgpu.so by a path relative to itself (the tree may be moved after the build).  Test infrastructure: tests/test_seam_binding.py loads the result; the product never does."""
 import os
 import re
 import subprocess
@@ -55,7 +55,7 @@ def main():
     lib_dir = os.path.join(ROOT, "sqlite-vector_amd")
     srcs = [spliced] + [os.path.join(REF, "src", f) for f in ("distance-cpu.c", "distance-avx2.c", "distance-sse2.c", "distance-neon.c")]
     cmd = ["gcc", "-O3", "-fPIC", "-w", "-mavx2", "-shared", "-I" + os.path.join(REF, "src"), "-I" + os.path.join(REF, "libs"), "-I" + os.path.join(ROOT, "include"),
-           "-I" + HERE, "-o", os.path.join(OUT, "vector.so")] + srcs + ["-L" + lib_dir, "-lvectorgpu", "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/root/repo/sqlite-vector_amd", "-lm"]
+           "-I" + HERE, "-o", os.path.join(OUT, "vector.so")] + srcs + ["-L" + lib_dir, "-lvectorgpu", "-Wl,-rpath,$ORIGIN/../../../sqlite-vector_amd", "-lm"]
     if not os.path.exists(os.path.join(lib_dir, "libvectorgpu.so")):
         print("make_seam: sqlite-vector_amd/libvectorgpu.so is not built yet - nothing built")
         return 0

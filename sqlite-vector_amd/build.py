@@ -3,9 +3,8 @@
     libvectorgpu.so : hipcc --offload-arch=gfx950 over csrc/*.hip     (HIP kernels + C-ABI)
     vector.so       : gcc over ext/vector_ext.c                       (SQLite loadable extension, plain C)
 
-hipcc cross-compiles without a GPU.  The extension needs SQLite's public headers (sqlite3ext.h): they are taken
-from a system include dir or from the reference tree's vendored, unmodified copy (/root/reference/libs) at build
-time only - never copied into this repository.
+hipcc cross-compiles without a GPU.  The extension needs no SQLite development headers: ext/vext_sqlite.h declares the
+part of SQLite's public interface it uses, and it reaches SQLite through the routines table its host hands it.
 """
 import os
 import shutil
@@ -81,27 +80,15 @@ def build_gpu_library(force=False, verbose=False):
     return LIB
 
 
-def sqlite_include_dir():
-    for d in ("/usr/include", "/usr/local/include", "/root/reference/libs"):
-        if os.path.exists(os.path.join(d, "sqlite3ext.h")) and os.path.exists(os.path.join(d, "sqlite3.h")):
-            return d
-    return None
-
-
 def build_extension(force=False, verbose=False):
     src = os.path.join(EXT, "vector_ext.c")
     if not os.path.exists(src):
         return None
-    deps = [src, os.path.join(ROOT, "include", "vectorgpu.h")] + [os.path.join(EXT, f) for f in os.listdir(EXT) if f.endswith(".inc")]
+    deps = [src, os.path.join(ROOT, "include", "vectorgpu.h")] + [os.path.join(EXT, f) for f in os.listdir(EXT) if f.endswith((".inc", ".h"))]
     if not force and not _newer(VEC, deps):
         return VEC
-    inc = sqlite_include_dir()
-    if inc is None:
-        if os.path.exists(VEC):
-            return VEC            # prebuilt artefact travelled here (GPU box): keep it
-        raise RuntimeError("sqlite3ext.h not found: cannot build the SQLite extension host")
     cmd = ["gcc", "-O2", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wno-unused-parameter", "-Wno-missing-field-initializers",
-           "-I" + inc, "-I" + os.path.join(ROOT, "include"), "-I" + EXT, "-o", VEC, src, "-ldl", "-lm", "-lpthread"]
+           "-I" + os.path.join(ROOT, "include"), "-I" + EXT, "-o", VEC, src, "-ldl", "-lm", "-lpthread"]
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)

@@ -10,7 +10,8 @@
  * computed in this file; if libvectorgpu.so or a GPU is missing the scan functions raise an SQL error.
  *
  * The C-ABI library is dlopen()ed from the directory this extension was loaded from (or $VECTORGPU_LIB), so the
- * extension itself links only against libc/libdl and talks to SQLite through sqlite3_api_routines.
+ * extension itself links only against libc/libdl and talks to SQLite through sqlite3_api_routines (vext_sqlite.h declares
+ * the part of SQLite's public interface it uses).
  *
  * Deliberate deviations from the reference (documented in DESIGN.md):
  *   - result order among EQUAL distances: the reference's own slot-history dependent result, rowid for rowid, for integer
@@ -26,7 +27,7 @@
  * text - in this repository's own structure; a differential test against the reference extension pins that contract.
  */
 #define _GNU_SOURCE            /* dladdr, strcasestr */
-#include "sqlite3ext.h"
+#include "vext_sqlite.h"
 SQLITE_EXTENSION_INIT1
 
 #include <ctype.h>

@@ -64,7 +64,7 @@ def test_eight_ranks_on_the_visible_devices_pass_the_self_check():
     full = free > 200 * (1 << 30)
     env = _env()
     env["VG_BENCH_SHARE_DEVICES"] = "1"
-    cmd = [sys.executable, BENCH, "--gpus", "8", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
+    cmd = [sys.executable, BENCH, "--gpus", "8", "--full", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
     if not full:                                                                  # (another process holds the device's memory: a smaller shard,
         cmd += ["--rows", "1000000"]                                              #  for which no recorded answer exists)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env)

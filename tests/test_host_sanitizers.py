@@ -21,8 +21,6 @@ def _lib(name):
 def test_extension_host_code_is_clean_under_asan_ubsan_and_tsan():
     if not (_lib("libasan.so") and _lib("libubsan.so") and _lib("libtsan.so")):
         pytest.skip("sanitizer runtimes not installed")
-    if not (os.path.exists("/usr/include/sqlite3ext.h") or os.path.exists("/root/reference/libs/sqlite3ext.h")):
-        pytest.skip("no sqlite3ext.h to build the extension against")
     p = subprocess.run(["bash", os.path.join(ROOT, "tools", "asan_host_check.sh")], capture_output=True, text=True, timeout=600, cwd=ROOT)
     out = p.stdout + p.stderr
     for bad in ("ERROR: AddressSanitizer", "runtime error", "WARNING: ThreadSanitizer", "Traceback"):

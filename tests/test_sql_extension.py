@@ -55,6 +55,15 @@ def test_only_the_entry_point_is_exported(ext_path):
     assert syms == ["sqlite3_vector_init"], syms            # sqlite-vector.h:29 is the reference's only export
 
 
+def test_sqlite_is_reached_only_through_the_hosts_routines_table(ext_path):
+    """a loadable extension must use the SQLite of its host (shared or compiled in): no SQLite library of its own, no SQLite symbol
+    resolved by the loader - every call goes through the sqlite3_api_routines table the entry point receives"""
+    dyn = subprocess.run(["readelf", "-d", ext_path + ".so"], capture_output=True, text=True).stdout
+    assert "sqlite" not in " ".join(l for l in dyn.splitlines() if "NEEDED" in l).lower(), dyn
+    undef = subprocess.run(["nm", "-D", "--undefined-only", ext_path + ".so"], capture_output=True, text=True).stdout
+    assert not [l for l in undef.splitlines() if "sqlite3" in l], undef
+
+
 def test_surface_matches_reference(ext_path, orc):
     """same function names / arities and the same four eponymous table-valued functions (sqlite-vector.c:2574-2634)"""
     db = connect(ext_path)

@@ -1,5 +1,6 @@
 import os, sys, sqlite3, numpy as np
-sys.path.insert(0, "/root/repo/tests"); sys.path.insert(0, "/root/repo/tests/golden")
+TESTS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+sys.path.insert(0, TESTS); sys.path.insert(0, os.path.join(TESTS, "golden"))
 import datagen as dg, make_golden as mg
 ext = sys.argv[1]
 def connect():

@@ -24,4 +24,4 @@ cp profiles/pmc_traffic.json "$OUT/pmc_traffic.json"
 rm -rf "$OUT"/pmc_c5/p* "$OUT"/pmc_long/p* "$OUT"/pmc_c3b/p*
 tail -12 "$OUT/c5_default_path_int8_filter_pmc.txt"
 # the bench once more, now that the traffic entries carry this build's hash
-python bench.py > "$OUT/bench_default_with_traffic.json" 2> /dev/null; cut -c1-900 "$OUT/bench_default_with_traffic.json"
+python bench.py --full > "$OUT/bench_default_with_traffic.json" 2> /dev/null; cut -c1-900 "$OUT/bench_default_with_traffic.json"
