@@ -147,6 +147,25 @@ int vg_scan_distances_device(vg_corpus *c, int metric, const void *dev_query, fl
 /* rowid of a scan position (host map) */
 int64_t vg_corpus_rowid_at(const vg_corpus *c, int64_t position);
 
+/* ---- range scans: every row within a distance of the query (no reference entry point; the reference's form is
+ * "SELECT ... FROM vector_full_scan_stream(...) WHERE distance <= r": N rows stepped to keep a handful) ----
+ * A row matches when its distance d - the float vg_scan_distances reports for it, bit for bit - satisfies (double)d <= radius.
+ * NaN and +Inf distances never match, whatever the radius (the top-k contract: they never enter a list); radius = +Inf means
+ * "every row with a finite distance"; a NaN radius is VG_ERR_INVALID.  The host turns the radius into the largest float not above
+ * it, so the device compares floats and decides what SQLite's comparison of the stream function's output would decide.
+ * Order: ascending (distance, scan position), whatever the handle's tie_order (membership does not depend on history).
+ * limit > 0: the first `limit` matches in that order are held, *out_matches still counts all of them; limit <= 0: all are held.
+ * The compare-and-compact runs inside the streaming scan kernel (nothing is written for a row that does not match); the caller
+ * never guesses a buffer size and the corpus is never scanned twice to learn one - only a result larger than the device buffer
+ * (2^20 keys to start with) costs ONE more launch into a buffer of the counted size.
+ * The result stays on the handle, in host memory, until the next call that scans or changes the handle; vg_scan_within_fetch copies
+ * rows [first, first + n) of it as (rowid, distance widened to double), vg_scan_within_keys as packed keys with positions local to
+ * this corpus - the form a multi-shard caller merges.  out_rowids / out_dist may be NULL (not wanted). */
+int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, int64_t limit,
+                   int64_t *out_matches, int64_t *out_held);
+int vg_scan_within_fetch(const vg_corpus *c, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
+int vg_scan_within_keys(const vg_corpus *c, int64_t first, int64_t n, uint64_t *out_keys);
+
 /* nq queries at once (row-major nq x dim, host).  out_rowids / out_dist are nq x k, out_counts nq.
  * f32 corpora, k <= 32, rows <= 512 floats, metric DOT / COSINE / L2 / SQUARED_L2: one pass over the corpus on the
  * matrix cores (Q x C^T tiles feed per-query candidate lists; L2 survivors are re-evaluated with the direct formula);
@@ -213,6 +232,11 @@ int     vg_shards_scan_topk(vg_shards *s, int metric, const void *query, int k, 
 int     vg_shards_scan_topk_batch(vg_shards *s, int metric, const void *queries, int nq, int k,
                                   int64_t *out_rowids, double *out_dist, int *out_counts);
 int     vg_shards_scan_distances(vg_shards *s, int metric, const void *query, float *out_dist_host);
+/* vg_scan_within over every shard, merged by (distance, GLOBAL scan position): the rows, order and distance bits of one corpus holding
+ * all rows.  Same contract; the merged result stays on the shards handle until its next scan. */
+int     vg_shards_scan_within(vg_shards *s, int metric, const void *query, double radius, int64_t limit,
+                              int64_t *out_matches, int64_t *out_held);
+int     vg_shards_scan_within_fetch(const vg_shards *s, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
 int     vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative);
 int     vg_shards_quantize_rows(vg_shards *s, float scale, float offset, int qtype, int64_t row0, int64_t n_rows, uint8_t *out_host);
 

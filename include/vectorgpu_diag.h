@@ -82,6 +82,14 @@ int vg_scan_distances_resident(vg_corpus *c, int metric, const void *query);
 int vg_resident_distances_fetch(vg_corpus *c, int64_t pos0, int64_t n, float *out_host);
 int vg_resident_distances_below(vg_corpus *c, int64_t pos0, float bound, uint64_t *out_pairs, int64_t cap, int64_t *out_count);
 
+/* range scans (vg_scan_within): keys the device buffer of the next scans starts with (<= 0: the default, 2^20) - tests lower it so that
+ * small corpora overflow it - and the kernel launches the last scan took: 1, or 2 when the buffer overflowed and the scan ran once more
+ * into a buffer of the counted size (shards: the setting goes to every shard, the count is the largest over the shards) */
+int vg_within_set_initial_capacity(vg_corpus *c, int64_t keys);
+int vg_within_last_launches(const vg_corpus *c);
+int vg_shards_within_set_initial_capacity(vg_shards *s, int64_t keys);
+int vg_shards_within_last_launches(const vg_shards *s);
+
 /* host-only: the same replay over n distances the caller holds (scan order); returns the count (<= k) or -1.
  * below_cap <= 0: the device path's candidate capacity. */
 int vg_reference_topk_replay(const float *dist, int64_t n, int k, int64_t below_cap, int64_t *out_pos, double *out_dist);

@@ -167,6 +167,15 @@ def _load():
         "vg_scan_distances_resident": (i32, [vp, i32, vp]),
         "vg_resident_distances_fetch": (i32, [vp, i64, i64, vp]),
         "vg_resident_distances_below": (i32, [vp, i64, C.c_float, vp, i64, C.POINTER(i64)]),
+        "vg_scan_within": (i32, [vp, i32, vp, C.c_double, i64, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_scan_within_fetch": (i32, [vp, i64, i64, vp, vp]),
+        "vg_scan_within_keys": (i32, [vp, i64, i64, vp]),
+        "vg_shards_scan_within": (i32, [vp, i32, vp, C.c_double, i64, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_shards_scan_within_fetch": (i32, [vp, i64, i64, vp, vp]),
+        "vg_within_set_initial_capacity": (i32, [vp, i64]),
+        "vg_within_last_launches": (i32, [vp]),
+        "vg_shards_within_set_initial_capacity": (i32, [vp, i64]),
+        "vg_shards_within_last_launches": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -268,6 +277,32 @@ class Corpus:
         out = np.empty(self.rows, dtype=np.float32)
         _check(lib().vg_scan_distances(self.h, metric, _ptr(query), _ptr(out)))
         return out
+
+    def scan_within(self, metric, query, radius, limit=None):
+        """every row with distance <= radius (finite), ordered by (distance, scan position): (rowids, distances, matches); with a
+        limit the first `limit` of them, `matches` still counting all"""
+        query = np.ascontiguousarray(query)
+        m, held = C.c_int64(0), C.c_int64(0)
+        _check(lib().vg_scan_within(self.h, metric, _ptr(query), float(radius), 0 if limit is None else max(int(limit), 0), C.byref(m), C.byref(held)))
+        n = 0 if (limit is not None and limit <= 0) else held.value
+        ids, dist = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64)
+        if n:
+            _check(lib().vg_scan_within_fetch(self.h, 0, n, _ptr(ids), _ptr(dist)))
+        return ids, dist, m.value
+
+    def within_keys(self, n):
+        """the first n keys the last scan_within holds (positions local to this corpus): what a multi-shard caller merges"""
+        keys = np.zeros(n, dtype=np.uint64)
+        if n:
+            _check(lib().vg_scan_within_keys(self.h, 0, n, _ptr(keys)))
+        return keys
+
+    def set_within_initial_capacity(self, keys):
+        """keys the device buffer of the next range scans starts with (0: the default) - vectorgpu_diag.h"""
+        _check(lib().vg_within_set_initial_capacity(self.h, keys))
+
+    def within_last_launches(self):
+        return int(lib().vg_within_last_launches(self.h))
 
     def scan_topk_batch(self, metric, queries, k):
         queries = np.ascontiguousarray(queries)
@@ -523,6 +558,23 @@ class Shards:
         cnt = np.zeros(nq, dtype=np.int32)
         _check(lib().vg_shards_scan_topk_batch(self.h, metric, _ptr(queries), nq, k, _ptr(ids), _ptr(dist), _ptr(cnt)))
         return ids, dist, cnt
+
+    def scan_within(self, metric, query, radius, limit=None):
+        """Corpus.scan_within over all shards, merged by (distance, global scan position): (rowids, distances, matches)"""
+        query = np.ascontiguousarray(query)
+        m, held = C.c_int64(0), C.c_int64(0)
+        _check(lib().vg_shards_scan_within(self.h, metric, _ptr(query), float(radius), 0 if limit is None else max(int(limit), 0), C.byref(m), C.byref(held)))
+        n = 0 if (limit is not None and limit <= 0) else held.value
+        ids, dist = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64)
+        if n:
+            _check(lib().vg_shards_scan_within_fetch(self.h, 0, n, _ptr(ids), _ptr(dist)))
+        return ids, dist, m.value
+
+    def set_within_initial_capacity(self, keys):
+        _check(lib().vg_shards_within_set_initial_capacity(self.h, keys))
+
+    def within_last_launches(self):
+        return int(lib().vg_shards_within_last_launches(self.h))
 
     def scan_distances(self, metric, query):
         query = np.ascontiguousarray(query)

@@ -44,6 +44,11 @@ struct ScanArgs {
     unsigned long long *emit_reset;   // zeroed by this launch's first thread (the prefix pass resets the counter of the pass behind it)
     int order;                 // top-k mode: 0 = grid-stride batches (the whole chip sweeps one contiguous window), 1 = every workgroup owns a
                                //   contiguous run of batches, its 16 wavefronts striding inside it (one CU stays on one page for many iterations)
+    // ---- "within" mode (the WITHIN = true instantiations, vg_scan_within.hip): every row whose distance is <= within_r and finite is
+    // appended as a key to `emit` = [count | within_cap keys]; the count keeps counting past the capacity (the host grows the buffer and
+    // launches once more), the per-wavefront queues live at store_lds_off.  Fields the other kernels never read.
+    float within_r;
+    unsigned long long within_cap;
 };
 
 // ------------------------------------------------------------------------------------------ keys

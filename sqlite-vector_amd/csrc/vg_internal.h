@@ -149,6 +149,17 @@ struct vg_corpus {
     int last_batch_path = 0;       // vg_batch_last_path (vectorgpu_diag.h)
     bool last_batch_half = false;  // (the last matrix-core batch went through vg_batch_h.hip)
     int blong_cooldown = 0;        // ... of the long-row kernel (vg_batch_hl.hip): the next batches over this corpus take the multi-query scan
+    // range scans (vg_scan_within.hip): the device buffer the kernel appends to, the sort's buffers, and the last result - kept on the host
+    unsigned long long *d_within = nullptr;   // [count | within_cap keys]
+    int64_t within_cap = 0;
+    int64_t within_cap_init = 0;              // vg_within_set_initial_capacity (0: VG_WITHIN_INITIAL_CAP)
+    uint64_t *d_within_sorted = nullptr;
+    void *d_within_temp = nullptr;
+    size_t within_temp_bytes = 0;
+    int64_t within_sort_cap = 0;
+    std::vector<uint64_t> within_keys;        // the held keys of the last vg_scan_within, ascending = (distance, scan position)
+    int64_t within_matches = 0;
+    int within_launches = 0;                  // kernel launches the last vg_scan_within took (2: the buffer overflowed once)
     int max_blocks = 0;
     int cu_count = 0;
 
@@ -187,6 +198,8 @@ struct ScanPlan {
     // (anything in front that reads dev_out_keys on the device - a pre-pass' threshold keys - still finds them in device memory)
     uint64_t *final_out = nullptr;
 };
+#define VG_WITHIN_INITIAL_CAP (1 << 20) // keys the within scans' device buffer starts with (8 MB); more matches: one more launch into a buffer of the counted size
+#define VG_WITHIN_HOST_SORT 4096      // up to this many matches are sorted on the host behind the copy, more by the device radix sort
 #define VG_BELOW_CAP (1 << 17)        // candidate pairs the device buffer holds (more: the store-mode replay takes over)
 #define VG_REF_EMIT_MIN_ROWS (1 << 17) // below this a reference-order scan with a tie simply replays a store-mode scan (cheap at that size)
 #define VG_REF_PREFIX_MAX (1 << 20)   // rows of the prefix pass whose distances travel to the host on a tie (4 MB of pinned memory)

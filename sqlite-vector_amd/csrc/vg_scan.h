@@ -81,11 +81,36 @@ __device__ inline void vg_load_batch(uint4 (&dst)[U], const uint8_t *rows, long 
 #endif
 #define VG_STORE_FLOATS 1024          // store mode: distances parked in LDS per wavefront between bursts of stores
 
+// ---- "within" mode (WITHIN = true, instantiated in vg_scan_within.hip): the keys of the rows within the radius are parked in a
+// per-wavefront LDS queue and leave in bursts - one atomicAdd of the burst size by one lane, then coalesced 8-byte-per-lane stores.
+// A store (and the atomic's return) shares vmcnt with the batch prefetch, see the store-mode note in vg_scan_kernel: a burst of 64+
+// keys makes that drain rare, and a batch without a match - nearly every batch - costs one ballot.
+#define VG_WITHIN_QUEUE 128           // keys per wavefront: flushed once a further batch (<= 64 rows) might not fit
+#define VG_WITHIN_LDS_BYTES (VG_WAVES_PER_BLOCK * VG_WITHIN_QUEUE * 8)
+__device__ inline void vg_within_flush(const uint64_t *queue, int &queued, unsigned long long *out, unsigned long long cap, int lane) {
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(out, (unsigned long long)queued);      // keeps counting past cap: the host learns the size it needs
+    base = vg_readlane64(base, 0);
+    for (int i = lane; i < queued; i += VG_WAVE)
+        if (base + (unsigned long long)i < cap) out[1 + base + i] = queue[i];
+    queued = 0;
+}
+// `queued` is wave-uniform; lanes of one wavefront write and read the queue in program order (LDS operations of a wavefront are ordered)
+__device__ inline void vg_within_offer(uint64_t key, bool match, uint64_t *queue, int &queued, unsigned long long *out,
+                                       unsigned long long cap, int lane) {
+    const unsigned long long m = __ballot(match);
+    if (m == 0ull) return;
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (match) queue[queued + rank] = key;
+    queued += __popcll(m);
+    if (queued > VG_WITHIN_QUEUE - VG_WAVE) vg_within_flush(queue, queued, out, cap, lane);
+}
+
 // EX = true: the variants tie_order = reference needs (vg_reforder.hip) - a start threshold from a pass over the rows in front
 // (init_keys), the candidate stream (emit) and "top-k + store" (out_dist != nullptr with k > 0: the replay's prefix pass).  They are
 // instantiations of their own (vg_scan_ex.hip) because the plain kernels sit AT the 128-VGPR / 106-SGPR limit of 16 wavefronts per
 // CU: the few registers the extras take spilled f32 U = 8 and f16 U = 6, shapes the plain scans use.
-template <int VT, int ACC, int U, bool NT, bool EX = false>
+template <int VT, int ACC, int U, bool NT, bool EX = false, bool WITHIN = false>
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ VgListExtras ex;
@@ -117,7 +142,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
         q[u] = (c < a.nch) ? qs[c] : make_uint4(0u, 0u, 0u, 0u);
     }
     const typename Accum<VT, ACC>::QStat qstat = Accum<VT, ACC>::template query_stat<U>(q, lpr_log2);
-    const bool store_mode = EX ? ((a.out_dist != nullptr) && k == 0) : (a.out_dist != nullptr);
+    const bool store_mode = WITHIN ? false : EX ? ((a.out_dist != nullptr) && k == 0) : (a.out_dist != nullptr);
     const bool store_too = EX && (a.out_dist != nullptr) && k != 0; // the reference replay's prefix pass: top-k + every distance
 
     // ---- loop over row batches, one batch prefetched.  Top-k mode: grid-stride (batch b, b + W, ...).  Store mode:
@@ -144,6 +169,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
     float *line = reinterpret_cast<float *>(smem + a.store_lds_off) + wave * VG_STORE_FLOATS;    // store mode only
     int in_line = 0;
     long long line_row0 = b * rpb;                                    // a multiple of VG_STORE_FLOATS: 16-byte aligned
+    uint64_t *wqueue = reinterpret_cast<uint64_t *>(smem + a.store_lds_off) + wave * VG_WITHIN_QUEUE;   // within mode only
+    int wqueued = 0;
     // Short uint8 / int8 rows (U <= 2) use a prefetch ring: NB buffers of U chunks, the loop unrolled NB times so that
     // every buffer keeps its registers (no copies); while buffer j is reduced the NB-1 others are in flight.  With
     // plain double buffering such rows have 1-2 KB per wavefront in flight and sit in s_waitcnt (dim-64 uint8 rows:
@@ -192,7 +219,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
                                               reinterpret_cast<const uint16_t *>(a.rows + row * a.stride), a.dim, a.root);
         }
         d = vg_clamp(d);
-        if (store_mode) {
+        if constexpr (WITHIN) {
+            // d <= r is false for NaN; +Inf never matches, whatever the radius (the top-k contract: such rows never enter a list)
+            vg_within_offer(vg_make_key(d, (uint32_t)row), owner && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
+        } else if (store_mode) {
             if (sub == 0) line[in_line * rpb + rib] = d;          // rows of consecutive batches are consecutive
             if (++in_line == flush_every) {
                 // same wavefront wrote the lines: LDS ops are ordered, no barrier needed
@@ -238,6 +268,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
             b = bn;
         }
     }
+    if constexpr (WITHIN) {
+        if (wqueued > 0) vg_within_flush(wqueue, wqueued, a.emit, a.within_cap, lane);
+        return;
+    }
     if (store_mode) {
         // the run's last, partly filled staging area
         for (int j = lane; j < in_line * rpb && line_row0 + j < a.n_rows; j += VG_WAVE) a.out_dist[line_row0 + j] = line[j];
@@ -253,7 +287,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 // the row is consumed in `S` slices of 64 x VG_LONG_U chunks with the accumulator carried across slices and the
 // query slice read from LDS (ds_read_b128) instead of living in VGPRs.  Same epilogue / top-k tail as above.
 #define VG_LONG_U 2
-template <int VT, int ACC, bool NT>
+template <int VT, int ACC, bool NT, bool WITHIN = false>
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
@@ -285,7 +319,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
 
     uint64_t mine = VG_EMPTY_KEY, thr = VG_EMPTY_KEY;
     const int k = a.k;
-    const bool store_mode = (a.out_dist != nullptr);
+    const bool store_mode = WITHIN ? false : (a.out_dist != nullptr);
+    uint64_t *wqueue = reinterpret_cast<uint64_t *>(smem + a.store_lds_off) + wave * VG_WITHIN_QUEUE;   // within mode only (vg_within_offer)
+    int wqueued = 0;
     const long long wstride = (long long)gridDim.x * VG_WAVES_PER_BLOCK;
     const long long gw = (long long)blockIdx.x * VG_WAVES_PER_BLOCK + wave;
 
@@ -325,7 +361,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
                                                   reinterpret_cast<const uint16_t *>(a.rows + row * a.stride), a.dim, a.root);
             }
             d = vg_clamp(d);
-            if (store_mode) {
+            if constexpr (WITHIN) {
+                vg_within_offer(vg_make_key(d, (uint32_t)row), (lane == 0) && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
+            } else if (store_mode) {
                 if (lane == 0) a.out_dist[row] = d;
             } else {
                 vg_list_offer(vg_make_key(d, (uint32_t)row), (lane == 0) && (d < INFINITY), mine, thr, lane, k);
@@ -336,6 +374,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
         row = nrow;
         s = ns;
+    }
+    if constexpr (WITHIN) {
+        if (wqueued > 0) vg_within_flush(wqueue, wqueued, a.emit, a.within_cap, lane);
+        return;
     }
     if (store_mode) return;
 

@@ -53,6 +53,13 @@ extern "C" int vg_select_sorted_keys(const float *dist, long long n, uint64_t *k
     return (int)hipGetLastError();
 }
 
+// keys[n] -> keys_sorted[n] (ascending): the within scans' matches (vg_scan_within.hip), whose unsigned order is the contract order
+extern "C" int vg_select_sort_keys(const uint64_t *keys, long long n, uint64_t *keys_sorted, void *temp, size_t temp_bytes, hipStream_t stream) {
+    hipError_t e = rocprim::radix_sort_keys(temp, temp_bytes, keys, keys_sorted, (size_t)n, 0, 64, stream, false);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipGetLastError();
+}
+
 
 // ------------------------------------------------------------------------------------------------ radix select
 

@@ -59,6 +59,9 @@ struct vg_shards {
     int ref_hot = 0;
     unsigned long long ref_stats[4] = {0, 0, 0, 0};   // reference-order scans | with a tie among the k+1 best | fused replays | store-mode replays
     struct ShardPool *pool = nullptr;          // persistent host threads, one per shard behind the first (see pool_run)
+    // the last vg_shards_scan_within (S > 1): the shards' matches merged by (distance image, GLOBAL position), kept for the fetch
+    struct WithinHit { uint64_t key; int64_t gpos; int shard; };   // key: the shard's own (image << 32 | local position)
+    std::vector<WithinHit> within_hits;
     int threaded = 0;                          // per-query issue + collect of the shards on those threads
 };
 
@@ -867,6 +870,64 @@ extern "C" int vg_shards_scan_distances(vg_shards *s, int metric, const void *qu
         }
         return (int)VG_OK;
     });
+}
+
+// ---- range scans: every shard runs vg_scan_within (same radius, same limit - the first `limit` of the whole are among the first `limit`
+// of every shard); local order is monotone in global order, so sorting the held keys by (distance image, global position) is the order
+// of one corpus holding all rows
+extern "C" int vg_shards_scan_within(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
+                                     int64_t *out_held) {
+    if (!s || !query) return fail(VG_ERR_INVALID, "vg_shards_scan_within: NULL argument");
+    if (s->S == 1) return vg_scan_within(s->sh[0], metric, query, radius, limit, out_matches, out_held);
+    if (out_matches) *out_matches = 0;
+    if (out_held) *out_held = 0;
+    s->within_hits.clear();
+    std::vector<int64_t> matches((size_t)s->S, 0), held((size_t)s->S, 0);
+    int rc = for_each_shard(s, [&](int i) { return vg_scan_within(s->sh[(size_t)i], metric, query, radius, limit, &matches[(size_t)i], &held[(size_t)i]); });
+    if (rc != VG_OK) return rc;
+    int64_t total = 0, all_held = 0;
+    for (int i = 0; i < s->S; ++i) { total += matches[(size_t)i]; all_held += held[(size_t)i]; }
+    s->within_hits.reserve((size_t)all_held);
+    std::vector<uint64_t> keys;
+    for (int i = 0; i < s->S; ++i) {
+        keys.resize((size_t)held[(size_t)i]);
+        if ((rc = vg_scan_within_keys(s->sh[(size_t)i], 0, held[(size_t)i], keys.data())) != VG_OK) return rc;
+        for (uint64_t key : keys) s->within_hits.push_back(vg_shards::WithinHit{key, global_of(s, i, (int64_t)vg_key_position(key)), i});
+    }
+    std::sort(s->within_hits.begin(), s->within_hits.end(), [](const vg_shards::WithinHit &a, const vg_shards::WithinHit &b) {
+        const uint32_t ia = (uint32_t)(a.key >> 32), ib = (uint32_t)(b.key >> 32);
+        return ia != ib ? ia < ib : a.gpos < b.gpos;
+    });
+    const int64_t keep = (limit > 0) ? std::min<int64_t>(limit, total) : total;
+    if ((int64_t)s->within_hits.size() > keep) s->within_hits.resize((size_t)keep);
+    if (out_matches) *out_matches = total;
+    if (out_held) *out_held = (int64_t)s->within_hits.size();
+    return VG_OK;
+}
+
+extern "C" int vg_shards_scan_within_fetch(const vg_shards *s, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
+    if (!s) return fail(VG_ERR_INVALID, "vg_shards_scan_within_fetch: NULL argument");
+    if (s->S == 1) return vg_scan_within_fetch(s->sh[0], first, n, out_rowids, out_dist);
+    if (n <= 0) return VG_OK;
+    if (first < 0 || first + n > (int64_t)s->within_hits.size()) return fail(VG_ERR_INVALID, "vg_shards_scan_within_fetch: rows outside the held result");
+    for (int64_t i = 0; i < n; ++i) {
+        const vg_shards::WithinHit &h = s->within_hits[(size_t)(first + i)];
+        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)h.shard], (int64_t)vg_key_position(h.key));
+        if (out_dist) out_dist[i] = (double)vg_key_distance(h.key);
+    }
+    return VG_OK;
+}
+
+extern "C" int vg_shards_within_set_initial_capacity(vg_shards *s, int64_t keys) {
+    if (!s) return fail(VG_ERR_INVALID, "vg_shards_within_set_initial_capacity: NULL argument");
+    for (auto *c : s->sh) { int rc = vg_within_set_initial_capacity(c, keys); if (rc != VG_OK) return rc; }
+    return VG_OK;
+}
+
+extern "C" int vg_shards_within_last_launches(const vg_shards *s) {
+    int most = 0;
+    if (s) for (auto *c : s->sh) most = std::max(most, vg_within_last_launches(c));
+    return most;
 }
 
 extern "C" int vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative) {

@@ -180,7 +180,9 @@ int sqlite3_column_type(sqlite3_stmt *, int iCol);
 /* SQL functions: arguments and results */
 const void *sqlite3_value_blob(sqlite3_value *);
 int sqlite3_value_bytes(sqlite3_value *);
+double sqlite3_value_double(sqlite3_value *);
 int sqlite3_value_int(sqlite3_value *);
+sqlite3_int64 sqlite3_value_int64(sqlite3_value *);
 const unsigned char *sqlite3_value_text(sqlite3_value *);
 int sqlite3_value_type(sqlite3_value *);
 void *sqlite3_user_data(sqlite3_context *);
@@ -274,9 +276,11 @@ struct sqlite3_api_routines {
     __typeof__(sqlite3_user_data) *sqlite3_user_data;
     __typeof__(sqlite3_value_blob) *sqlite3_value_blob;
     __typeof__(sqlite3_value_bytes) *sqlite3_value_bytes;
-    void *unused_104[2];
+    void *unused_104[1];
+    __typeof__(sqlite3_value_double) *sqlite3_value_double;
     __typeof__(sqlite3_value_int) *sqlite3_value_int;
-    void *unused_107[2];
+    __typeof__(sqlite3_value_int64) *sqlite3_value_int64;
+    void *unused_108[1];
     __typeof__(sqlite3_value_text) *sqlite3_value_text;
     void *unused_110[3];
     __typeof__(sqlite3_value_type) *sqlite3_value_type;
@@ -369,7 +373,9 @@ struct sqlite3_api_routines {
 #define sqlite3_user_data            sqlite3_api->sqlite3_user_data
 #define sqlite3_value_blob           sqlite3_api->sqlite3_value_blob
 #define sqlite3_value_bytes          sqlite3_api->sqlite3_value_bytes
+#define sqlite3_value_double         sqlite3_api->sqlite3_value_double
 #define sqlite3_value_int            sqlite3_api->sqlite3_value_int
+#define sqlite3_value_int64          sqlite3_api->sqlite3_value_int64
 #define sqlite3_value_text           sqlite3_api->sqlite3_value_text
 #define sqlite3_value_type           sqlite3_api->sqlite3_value_type
 #define sqlite3_vmprintf             sqlite3_api->sqlite3_vmprintf
