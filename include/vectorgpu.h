@@ -166,6 +166,30 @@ int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, i
 int vg_scan_within_fetch(const vg_corpus *c, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
 int vg_scan_within_keys(const vg_corpus *c, int64_t first, int64_t n, uint64_t *out_keys);
 
+/* ---- masked scans: the k nearest rows among an allowed set ("... of this tenant / this category"; no reference entry point) ----
+ * A row mask is a bitmap over scan positions kept on the handle, in device memory (rows / 8 bytes): bit (p & 63) of 64-bit word
+ * (p >> 6) set = the row at scan position p may be returned.  Setting it and scanning are two calls: one filter serves many queries.
+ * vg_corpus_set_mask_bits: n_bits <= rows, the rows behind n_bits are not allowed.  vg_corpus_set_mask_rowids: the rowids are
+ * mapped to positions on the host (implicit rowids: rowid - base; an ascending map: the search behind vg_corpus_find_rowid; a map
+ * that is not ascending: VG_ERR_UNSUPPORTED); rowids the corpus does not hold are ignored, duplicates are harmless, *out_set (may
+ * be NULL) = rows allowed.  vg_corpus_mask_count: rows allowed, -1 without a mask.
+ * ONLY vg_scan_topk_masked reads the mask: every other call behaves the same with and without one.  A call that changes the
+ * number of rows or which row sits at which position (append*, delete_rows, clear) drops the mask; patch_rows, reserve and trim
+ * keep it; vg_corpus_clone copies it.
+ * vg_scan_topk_masked: the contract of vg_scan_topk restricted to the allowed rows - NaN / +Inf never enter, fewer than k rows
+ * when fewer allowed rows qualify, every distance the float vg_scan_distances reports for that row, bit for bit - in ascending
+ * (distance, scan position) order whatever the handle's tie_order.  The plain streaming kernel with one scalar load of mask bits
+ * per batch of rows: a batch without an allowed row is not read (by construction; timings not measured yet).  1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below);
+ * no mask set: VG_ERR_INVALID; an empty mask: *out_count = 0 without a launch.  vg_scan_topk_masked_keys: the same as packed keys
+ * with positions local to this corpus (out_keys[k]) - the form a multi-shard caller merges. */
+int     vg_corpus_set_mask_bits(vg_corpus *c, const uint64_t *words, int64_t n_bits);
+int     vg_corpus_set_mask_rowids(vg_corpus *c, const int64_t *rowids, int64_t n, int64_t *out_set);
+int     vg_corpus_clear_mask(vg_corpus *c);
+int64_t vg_corpus_mask_count(const vg_corpus *c);
+int     vg_scan_topk_masked(vg_corpus *c, int metric, const void *query, int k,
+                            int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, int *out_count);
+
 /* nq queries at once (row-major nq x dim, host).  out_rowids / out_dist are nq x k, out_counts nq.
  * f32 corpora, k <= 32, rows <= 512 floats, metric DOT / COSINE / L2 / SQUARED_L2: one pass over the corpus on the
  * matrix cores (Q x C^T tiles feed per-query candidate lists; L2 survivors are re-evaluated with the direct formula);
@@ -237,6 +261,14 @@ int     vg_shards_scan_distances(vg_shards *s, int metric, const void *query, fl
 int     vg_shards_scan_within(vg_shards *s, int metric, const void *query, double radius, int64_t limit,
                               int64_t *out_matches, int64_t *out_held);
 int     vg_shards_scan_within_fetch(const vg_shards *s, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
+/* the row mask over GLOBAL scan positions (vg_corpus_set_mask_*): the bits are dealt out to the shards by the block-cyclic map of the
+ * rows; vg_shards_scan_topk_masked = vg_scan_topk_masked of one corpus holding all rows (rowids, order and distance bits). */
+int     vg_shards_set_mask_bits(vg_shards *s, const uint64_t *words, int64_t n_bits);
+int     vg_shards_set_mask_rowids(vg_shards *s, const int64_t *rowids, int64_t n, int64_t *out_set);
+int     vg_shards_clear_mask(vg_shards *s);
+int64_t vg_shards_mask_count(const vg_shards *s);
+int     vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *query, int k,
+                                   int64_t *out_rowids, double *out_dist, int *out_count);
 int     vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative);
 int     vg_shards_quantize_rows(vg_shards *s, float scale, float offset, int qtype, int64_t row0, int64_t n_rows, uint8_t *out_host);
 

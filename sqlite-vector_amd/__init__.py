@@ -176,6 +176,17 @@ def _load():
         "vg_within_last_launches": (i32, [vp]),
         "vg_shards_within_set_initial_capacity": (i32, [vp, i64]),
         "vg_shards_within_last_launches": (i32, [vp]),
+        "vg_corpus_set_mask_bits": (i32, [vp, vp, i64]),
+        "vg_corpus_set_mask_rowids": (i32, [vp, vp, i64, C.POINTER(i64)]),
+        "vg_corpus_clear_mask": (i32, [vp]),
+        "vg_corpus_mask_count": (i64, [vp]),
+        "vg_scan_topk_masked": (i32, [vp, i32, vp, i32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_masked_keys": (i32, [vp, i32, vp, i32, vp, C.POINTER(i32)]),
+        "vg_shards_set_mask_bits": (i32, [vp, vp, i64]),
+        "vg_shards_set_mask_rowids": (i32, [vp, vp, i64, C.POINTER(i64)]),
+        "vg_shards_clear_mask": (i32, [vp]),
+        "vg_shards_mask_count": (i64, [vp]),
+        "vg_shards_scan_topk_masked": (i32, [vp, i32, vp, i32, vp, vp, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -217,6 +228,32 @@ def plan_scan_shape(vtype, dim, metric):
     lpr, u, lng = C.c_int(0), C.c_int(0), C.c_int(0)
     _check(lib().vg_plan_scan_shape(vtype, dim, metric, C.byref(lpr), C.byref(u), C.byref(lng)))
     return lpr.value, u.value, bool(lng.value)
+
+
+def _set_mask(obj, prefix, rows, bits, positions, rowids):
+    """Corpus.set_mask / Shards.set_mask: bits | positions | rowids -> the handle's row mask; returns the rows allowed"""
+    if (bits is not None) + (positions is not None) + (rowids is not None) != 1:
+        raise ValueError("set_mask takes exactly one of bits, positions, rowids")
+    L = lib()
+    if rowids is not None:
+        ids = np.ascontiguousarray(rowids, dtype=np.int64).ravel()
+        n_set = C.c_int64(0)
+        _check(getattr(L, prefix + "_set_mask_rowids")(obj.h, _ptr(ids), ids.size, C.byref(n_set)))
+        return n_set.value
+    if positions is not None:
+        flags = np.zeros(rows, dtype=bool)
+        flags[np.asarray(positions, dtype=np.int64).ravel()] = True
+        bits = flags
+    bits = np.asarray(bits)
+    if bits.dtype == np.uint64:                              # packed words: every bit they hold, up to the rows held
+        words, n_bits = np.ascontiguousarray(bits).ravel(), min(int(bits.size) * 64, int(rows))
+    else:
+        flags = np.ascontiguousarray(bits, dtype=bool).ravel()
+        n_bits = int(flags.size)
+        words = np.zeros((n_bits + 63) // 64, dtype=np.uint64)
+        words.view(np.uint8)[:(n_bits + 7) // 8] = np.packbits(flags, bitorder="little")
+    _check(getattr(L, prefix + "_set_mask_bits")(obj.h, _ptr(words), n_bits))
+    return int(getattr(L, prefix + "_mask_count")(obj.h))
 
 
 class Corpus:
@@ -289,6 +326,36 @@ class Corpus:
         if n:
             _check(lib().vg_scan_within_fetch(self.h, 0, n, _ptr(ids), _ptr(dist)))
         return ids, dist, m.value
+
+    # masked scans: a row mask on the handle (a bitmap over scan positions), read by scan_topk_masked only
+    def set_mask(self, bits=None, positions=None, rowids=None):
+        """the rows a masked scan may return - exactly one of: `bits` (bool per scan position, or packed uint64 words: bit p & 63 of
+        word p >> 6), `positions` (scan positions), `rowids` (those not held are ignored).  Returns the number of rows allowed."""
+        return _set_mask(self, "vg_corpus", self.rows, bits, positions, rowids)
+
+    def clear_mask(self):
+        _check(lib().vg_corpus_clear_mask(self.h))
+
+    def mask_count(self):
+        """rows the mask allows, -1 without a mask"""
+        return int(lib().vg_corpus_mask_count(self.h))
+
+    def scan_topk_masked(self, metric, query, k):
+        """the k nearest ALLOWED rows, ascending (distance, scan position): (rowids, distances)"""
+        query = np.ascontiguousarray(query)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        cnt = C.c_int(0)
+        _check(lib().vg_scan_topk_masked(self.h, metric, _ptr(query), k, _ptr(ids), _ptr(dist), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value]
+
+    def clone(self):
+        """a second corpus with the same rows, rowids, switches and row mask (vg_corpus_clone)"""
+        other = Corpus.__new__(Corpus)
+        other.h = C.c_void_p()
+        other.vtype, other.dim = self.vtype, self.dim
+        _check(lib().vg_corpus_clone(self.h, C.byref(other.h)))
+        return other
 
     def within_keys(self, n):
         """the first n keys the last scan_within holds (positions local to this corpus): what a multi-shard caller merges"""
@@ -558,6 +625,25 @@ class Shards:
         cnt = np.zeros(nq, dtype=np.int32)
         _check(lib().vg_shards_scan_topk_batch(self.h, metric, _ptr(queries), nq, k, _ptr(ids), _ptr(dist), _ptr(cnt)))
         return ids, dist, cnt
+
+    def set_mask(self, bits=None, positions=None, rowids=None):
+        """Corpus.set_mask over GLOBAL scan positions: the bits are dealt out to the shards like the rows"""
+        return _set_mask(self, "vg_shards", self.rows, bits, positions, rowids)
+
+    def clear_mask(self):
+        _check(lib().vg_shards_clear_mask(self.h))
+
+    def mask_count(self):
+        return int(lib().vg_shards_mask_count(self.h))
+
+    def scan_topk_masked(self, metric, query, k):
+        """Corpus.scan_topk_masked over all shards, merged by (distance, global scan position)"""
+        query = np.ascontiguousarray(query)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        cnt = C.c_int(0)
+        _check(lib().vg_shards_scan_topk_masked(self.h, metric, _ptr(query), k, _ptr(ids), _ptr(dist), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value]
 
     def scan_within(self, metric, query, radius, limit=None):
         """Corpus.scan_within over all shards, merged by (distance, global scan position): (rowids, distances, matches)"""

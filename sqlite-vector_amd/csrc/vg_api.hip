@@ -274,6 +274,20 @@ int vg_plain_scan_shape(const vg_corpus *c, int metric, VgShape *out) {
     choose_shape(c->nch, c->vtype, vg_metric_to_acc(metric), out);
     return 0;
 }
+// workgroups of a top-k launch of the plain kernel over n_rows rows (shared with the masked scan, vg_scan_masked.hip)
+long long vg_plain_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s) {
+    const int rpb = VG_WAVE >> s.lpr_log2;
+    const long long nbatch = (n_rows + rpb - 1) / rpb;
+    // 16-wave workgroups: one per CU is what ~96 VGPRs admit (5 waves/SIMD); a second one only queues behind it
+    const int bpc = std::max(1, std::min(8, vg_sw(SW_VG_BLOCKS_PER_CU, 1)));
+    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
+    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count * bpc));
+    blocks = std::min<long long>(blocks, VG_SEL_MAX_HEADS);          // the final rank-select handles <= 256 lists
+    // small corpora: at least two batches per wavefront - the merge kernel's time grows with the number of per-CU lists (6.6 us for
+    // 32, 14 us for 256) and is most of a 10k-row query; round 3's wider shapes halved the rows per batch, i.e. doubled the lists
+    blocks = std::min<long long>(blocks, std::max<long long>(32, nbatch / (2 * VG_WAVES_PER_BLOCK)));
+    return blocks;
+}
 
 // Launch the scan (+ merge in top-k mode) on `stream`.  dev_query holds nch*16 zero-padded bytes.
 static int launch_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int k, uint64_t *dev_out_keys,
@@ -321,16 +335,7 @@ static int launch_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int k
     scan_fn_t fn = (emitting || prefix_pass) ? vg_pick_scan_kernel_ex(c->vtype, acc, s.U) : pick_kernel(c->vtype, acc, s, use_nt_loads(c, n_rows));
     if (!fn) return vg_fail(VG_ERR_UNSUPPORTED, "no scan kernel for type %s", type_tag(c->vtype));
 
-    const int rpb = VG_WAVE >> s.lpr_log2;
-    const long long nbatch = (n_rows + rpb - 1) / rpb;
-    // 16-wave workgroups: one per CU is what ~96 VGPRs admit (5 waves/SIMD); a second one only queues behind it
-    const int bpc = std::max(1, std::min(8, vg_sw(SW_VG_BLOCKS_PER_CU, 1)));
-    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
-    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count * bpc));
-    blocks = std::min<long long>(blocks, VG_SEL_MAX_HEADS);          // the final rank-select handles <= 256 lists
-    // small corpora: at least two batches per wavefront - the merge kernel's time grows with the number of per-CU lists (6.6 us for
-    // 32, 14 us for 256) and is most of a 10k-row query; round 3's wider shapes halved the rows per batch, i.e. doubled the lists
-    blocks = std::min<long long>(blocks, std::max<long long>(32, nbatch / (2 * VG_WAVES_PER_BLOCK)));
+    const long long blocks = vg_plain_scan_blocks(c, n_rows, s);
 
     ScanArgs a{};
     a.rows = c->d_rows;

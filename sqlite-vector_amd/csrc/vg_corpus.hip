@@ -211,6 +211,7 @@ extern "C" void vg_corpus_destroy(vg_corpus *c) {
     if (c->d_within) hipFree(c->d_within);
     if (c->d_within_sorted) hipFree(c->d_within_sorted);
     if (c->d_within_temp) hipFree(c->d_within_temp);
+    if (c->d_mask) hipFree(c->d_mask);
     if (c->d_ref_prefix) hipFree(c->d_ref_prefix);
     if (c->h_ref) hipHostFree(c->h_ref);
     if (c->norm_ev) hipEventDestroy(c->norm_ev);
@@ -229,6 +230,7 @@ extern "C" int vg_corpus_clear(vg_corpus *c) {
     c->dist_valid_rows = 0;
     c->within_keys.clear();
     c->within_matches = 0;
+    vg_drop_mask(c);
     c->xnorm_rows = 0;
     c->i8_rows = 0;
     c->tm_rows = 0;
@@ -262,7 +264,7 @@ extern "C" int vg_corpus_device_bytes(const vg_corpus *c, long long *out3) {
     out3[0] = size_of(c->d_rows);
     const void *derived[] = {c->d_rows_s8, c->d_sx, c->d_rows_tm, c->d_rows_bf, c->d_rows_q8, c->d_q8stat, c->d_rows_q8tm, c->d_q8tm_stat, c->d_rows_n4, c->d_n4stat, c->d_xnorm};
     const void *working[] = {c->d_query, c->d_cand, c->d_cand_pre, c->d_keys, c->d_dist, c->d_below, c->d_ref_prefix, c->d_sel_keys, c->d_sel_sorted,
-                             c->d_sel_temp, c->d_sel_state, c->d_within, c->d_within_sorted, c->d_within_temp, c->d_stage, c->d_filter_evals, c->d_bq, c->d_bcand, c->d_bkeys, c->d_bpairs, c->d_bpcounts};
+                             c->d_sel_temp, c->d_sel_state, c->d_within, c->d_within_sorted, c->d_within_temp, c->d_mask, c->d_stage, c->d_filter_evals, c->d_bq, c->d_bcand, c->d_bkeys, c->d_bpairs, c->d_bpcounts};
     out3[1] = 0; out3[2] = 0;
     for (const void *p : derived) out3[1] += size_of(p);
     for (const void *p : working) out3[2] += size_of(p);
@@ -319,6 +321,11 @@ extern "C" int vg_corpus_clone(const vg_corpus *src, vg_corpus **out) {
     c->rowid_base = src->rowid_base;
     c->tie_order = src->tie_order;
     c->scan_filter_mode = src->scan_filter_mode;
+    if (src->mask_count >= 0) {                              // the row mask travels with the rows it names
+        c->mask_host = src->mask_host;
+        c->mask_count = src->mask_count;
+        if ((rc = vg_mask_upload(c)) != VG_OK) { vg_corpus_destroy(c); return rc; }
+    }
     *out = c;
     return VG_OK;
 }
@@ -480,6 +487,7 @@ static int append_impl(vg_corpus *c, const void *src, bool src_on_device, int64_
     HIP_TRY(hipSetDevice(c->device));
     int rc = corpus_reserve(c, c->n_rows + n_rows);
     if (rc != VG_OK) return rc;
+    vg_drop_mask(c);                                         // (a row mask covers the rows as they were)
     uint8_t *dst = c->d_rows + c->n_rows * c->stride;
     // a plain copy is only valid when source rows have no padding of their own: padding bytes must be ZERO in HBM
     // (they are summed like data), so any row whose size is not a 16-byte multiple goes through the repack kernel
@@ -719,6 +727,7 @@ extern "C" int vg_corpus_delete_rows(vg_corpus *c, const int64_t *positions, int
         c->rowids.swap(ids);
     }
     c->n_rows -= n;
+    vg_drop_mask(c);
     invalidate_derived_from(c, positions[0]);
     return VG_OK;
 }

@@ -49,6 +49,9 @@ struct ScanArgs {
     // launches once more), the per-wavefront queues live at store_lds_off.  Fields the other kernels never read.
     float within_r;
     unsigned long long within_cap;
+    // ---- "masked" mode (the MASKED = true instantiations, vg_scan_masked.hip): bit (p & 63) of word (p >> 6) set = the row at scan
+    // position p may enter a list; ceil(n_rows / 64) words, bits behind the last row zero.  A field the other kernels never read.
+    const uint64_t *mask;
 };
 
 // ------------------------------------------------------------------------------------------ keys

@@ -160,6 +160,12 @@ struct vg_corpus {
     std::vector<uint64_t> within_keys;        // the held keys of the last vg_scan_within, ascending = (distance, scan position)
     int64_t within_matches = 0;
     int within_launches = 0;                  // kernel launches the last vg_scan_within took (2: the buffer overflowed once)
+    // masked scans (vg_scan_masked.hip): the row mask - bit (p & 63) of word (p >> 6) = the row at scan position p may be returned.  Read
+    // by vg_scan_topk_masked only; dropped (vg_drop_mask) by every call that changes the number of rows or which row sits where
+    uint64_t *d_mask = nullptr;               // ceil(n_rows / 64) words while a mask is set (mask_cap_words allocated)
+    int64_t mask_cap_words = 0;
+    std::vector<uint64_t> mask_host;          // the same words on the host (vg_corpus_clone copies them)
+    int64_t mask_count = -1;                  // rows allowed; -1: no mask
     int max_blocks = 0;
     int cu_count = 0;
 
@@ -220,6 +226,9 @@ struct VgRefSlots;
 void vg_ref_offer_run(VgRefSlots &slots, const float *d, int64_t n, int64_t g0);   // a run of consecutive rows offered to the slots
 int vg_ref_replay_slab(vg_corpus *c, int metric, const void *query, int k, VgRefSlots &slots, int64_t gbase, bool fresh);   // vg_reforder.hip
 
+static inline void vg_drop_mask(vg_corpus *c) { c->mask_count = -1; c->mask_host.clear(); }   // (the device words stay allocated for the next mask)
+int vg_mask_upload(vg_corpus *c);             // vg_scan_masked.hip: mask_host -> d_mask
+
 // next slot of the profiling ring (nullptr when profiling is off)
 static inline hipEvent_t *vg_prof_slot(vg_corpus *c, uint8_t flags) {
     if (!c->profiling) return nullptr;
@@ -243,6 +252,7 @@ int vg_launch_plain_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int
 int vg_launch_merge_one(const uint64_t *dev_cand, int nlists, int k, uint64_t *dev_out_keys, hipStream_t stream,
                         const unsigned long long *mirror_src = nullptr, unsigned long long *mirror_dst = nullptr);
 int vg_plain_scan_shape(const vg_corpus *c, int metric, VgShape *out);   // vg_api.hip: launch shape of the plain kernel
+long long vg_plain_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s);   // vg_api.hip: workgroups of its top-k launch
 int vg_launch_scan_filter(vg_corpus *c, int metric, const uint8_t *dev_query, int k, uint64_t *dev_out_keys, hipStream_t stream,
                           bool ref_emit = false, uint64_t *final_out = nullptr);   // vg_filter.hip; -1: not served
 int vg_scan_topk_enqueue_plan(vg_corpus *c, int metric, const void *query, int k, bool ref_emit);   // vg_api.hip: vg_scan_topk_enqueue with the reference-order extras

@@ -106,11 +106,25 @@ __device__ inline void vg_within_offer(uint64_t key, bool match, uint64_t *queue
     if (queued > VG_WITHIN_QUEUE - VG_WAVE) vg_within_flush(queue, queued, out, cap, lane);
 }
 
+// ---- "masked" mode (MASKED = true, instantiated in vg_scan_masked.hip): top-k among the rows whose bit is set in ScanArgs.mask.
+// vg_mask_bits: the bits of the `n` rows from `row0` on (n a power of two <= 64 and row0 a multiple of it: adjacent bits of ONE word),
+// bit i = row0 + i, zero when the rows are out of range.  Every lane of the wavefront asks for the same rows, but the compiler cannot
+// know that of a value derived from threadIdx: the start row goes through readfirstlane (0xFFFFFFFF = out of range: a shard holds at
+// most 2^32 - 1 rows), and from there on index, word, shift and result are wave-uniform - one scalar load (s_load_dwordx2) per call on
+// the scalar cache's counter (lgkmcnt), nothing on the vector memory path the row prefetch lives on, and `bits != 0` is a scalar branch.
+__device__ inline uint64_t vg_mask_bits(const uint64_t *mask, long long row0, int n, bool in_range) {
+    const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(in_range ? (uint32_t)row0 : 0xFFFFFFFFu));
+    const bool ok = r != 0xFFFFFFFFu;
+    const uint64_t bits = mask[ok ? (r >> 6) : 0u] >> (r & 63u);
+    const uint64_t keep = (n >= VG_WAVE) ? ~0ull : ((1ull << (n & 63)) - 1ull);
+    return ok ? (bits & keep) : 0ull;
+}
+
 // EX = true: the variants tie_order = reference needs (vg_reforder.hip) - a start threshold from a pass over the rows in front
 // (init_keys), the candidate stream (emit) and "top-k + store" (out_dist != nullptr with k > 0: the replay's prefix pass).  They are
 // instantiations of their own (vg_scan_ex.hip) because the plain kernels sit AT the 128-VGPR / 106-SGPR limit of 16 wavefronts per
 // CU: the few registers the extras take spilled f32 U = 8 and f16 U = 6, shapes the plain scans use.
-template <int VT, int ACC, int U, bool NT, bool EX = false, bool WITHIN = false>
+template <int VT, int ACC, int U, bool NT, bool EX = false, bool WITHIN = false, bool MASKED = false>
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ VgListExtras ex;
@@ -142,7 +156,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
         q[u] = (c < a.nch) ? qs[c] : make_uint4(0u, 0u, 0u, 0u);
     }
     const typename Accum<VT, ACC>::QStat qstat = Accum<VT, ACC>::template query_stat<U>(q, lpr_log2);
-    const bool store_mode = WITHIN ? false : EX ? ((a.out_dist != nullptr) && k == 0) : (a.out_dist != nullptr);
+    const bool store_mode = (WITHIN || MASKED) ? false : EX ? ((a.out_dist != nullptr) && k == 0) : (a.out_dist != nullptr);
     const bool store_too = EX && (a.out_dist != nullptr) && k != 0; // the reference replay's prefix pass: top-k + every distance
 
     // ---- loop over row batches, one batch prefetched.  Top-k mode: grid-stride (batch b, b + W, ...).  Store mode:
@@ -186,13 +200,16 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
     float nn[NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) nn[j] = 0.0f;
-    auto load = [&](uint4 (&dst)[U], float &nn_dst, long long batch) {
-        vg_load_batch<U, NT>(dst, a.rows, batch * rpb + rib, (batch < b_end) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
+    // (masked mode: `live` = the batch has an allowed row; a batch without one points every load at vg_zero_chunk - no row is read)
+    auto load = [&](uint4 (&dst)[U], float &nn_dst, long long batch, bool live = true) {
+        vg_load_batch<U, NT>(dst, a.rows, batch * rpb + rib, (batch < b_end && live) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
         // A_COSN: the row's squared norm rides along with the batch prefetch (one dword per row from the cached vector)
         // (unconditional for the same reason as the chunk loads: row 0's norm stands in, the row's result is never used)
-        if constexpr (ACC == A_COSN) { const long long r0 = batch * rpb + rib; nn_dst = a.row_nn[(batch < b_end && r0 < a.n_rows) ? r0 : 0]; }
+        if constexpr (ACC == A_COSN) { const long long r0 = batch * rpb + rib; nn_dst = a.row_nn[(batch < b_end && live && r0 < a.n_rows) ? r0 : 0]; }
     };
-    auto process = [&](uint4 (&cur)[U], float nn_cur, long long bcur) {
+    // masked mode: the mask bits of a batch (wave-uniform; 0 behind the wavefront's last batch)
+    auto mask_of = [&](long long batch) -> uint64_t { return vg_mask_bits(a.mask, batch * rpb, rpb, batch < b_end); };
+    auto process = [&](uint4 (&cur)[U], float nn_cur, long long bcur, uint64_t mbits = 0ull) {
         Accum<VT, ACC> acc;
         acc.init();
         if constexpr (VT == T_F16 || VT == T_BF16) {
@@ -236,6 +253,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
                 in_line = 0;
                 line_row0 = (bcur + wstride) * rpb;
             }
+        } else if constexpr (MASKED) {
+            // a row whose bit is clear was computed with its batch and is simply not offered
+            vg_list_offer(vg_make_key(d, (uint32_t)row), owner && ((mbits >> rib) & 1ull) && (d < INFINITY), mine, thr, lane, k);
         } else if constexpr (EX) {
             if (store_too && owner) a.out_dist[row] = d;
             vg_list_offer_ex(vg_make_key(d, (uint32_t)row), owner && (d < INFINITY), mine, thr, lane, k, &ex);
@@ -244,7 +264,48 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
             vg_list_offer(vg_make_key(d, (uint32_t)row), owner && (d < INFINITY), mine, thr, lane, k);
         }
     };
-    if constexpr (RING) {
+    if constexpr (MASKED) {
+        // The mask fetch runs ONE step ahead of the row prefetch: the bits of a batch decide the ADDRESSES of its loads, so they must be
+        // in registers when those are issued - `mnext` is asked for one loop step before the batch it describes is prefetched and has a
+        // whole step (the current batch's arithmetic) to arrive.  mb[j] = the bits of the batch in buffer j.  In the ring form the row
+        // prefetch is NB - 1 batches ahead of the arithmetic, the mask fetch therefore NB: still one scalar load in flight per
+        // wavefront, NB + 1 words of bits held (scalar registers).  A batch without an allowed row costs its U loads of the zero chunk
+        // (one cache line, always a hit) and no arithmetic.  These two loops are the plain ring / double-buffer loops below with the
+        // mask threaded through; they are copies so that the plain instantiations stay byte-identical - keep the four in step by hand.
+        uint64_t mb[NB];
+        if constexpr (RING) {
+#pragma unroll
+            for (int j = 0; j < NB - 1; ++j) { mb[j] = mask_of(b + j * wstride); load(buf[j], nn[j], b + j * wstride, mb[j] != 0ull); }
+            uint64_t mnext = mask_of(b + (NB - 1) * wstride);
+            while (b < b_end) {
+#pragma unroll
+                for (int j = 0; j < NB; ++j) {
+                    const long long bj = b + j * wstride;             // the batch in buffer j
+                    mb[(j + NB - 1) % NB] = mnext;
+                    mnext = mask_of(bj + NB * wstride);
+                    load(buf[(j + NB - 1) % NB], nn[(j + NB - 1) % NB], bj + (NB - 1) * wstride, mb[(j + NB - 1) % NB] != 0ull);
+                    if (mb[j] != 0ull) process(buf[j], nn[j], bj, mb[j]);       // (0 behind b_end)
+                }
+                b += NB * wstride;
+            }
+        } else {
+            mb[0] = mask_of(b);
+            uint64_t mnext = mask_of(b + wstride);
+            load(buf[0], nn[0], b, mb[0] != 0ull);
+            while (b < b_end) {
+                const long long bn = b + wstride;
+                mb[1] = mnext;
+                mnext = mask_of(bn + wstride);
+                load(buf[1], nn[1], bn, mb[1] != 0ull);
+                if (mb[0] != 0ull) process(buf[0], nn[0], b, mb[0]);
+#pragma unroll
+                for (int u = 0; u < U; ++u) buf[0][u] = buf[1][u];
+                nn[0] = nn[1];
+                mb[0] = mb[1];
+                b = bn;
+            }
+        }
+    } else if constexpr (RING) {
 #pragma unroll
         for (int j = 0; j < NB - 1; ++j) load(buf[j], nn[j], b + j * wstride);
         while (b < b_end) {
@@ -287,7 +348,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 // the row is consumed in `S` slices of 64 x VG_LONG_U chunks with the accumulator carried across slices and the
 // query slice read from LDS (ds_read_b128) instead of living in VGPRs.  Same epilogue / top-k tail as above.
 #define VG_LONG_U 2
-template <int VT, int ACC, bool NT, bool WITHIN = false>
+template <int VT, int ACC, bool NT, bool WITHIN = false, bool MASKED = false>
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
@@ -319,41 +380,53 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
 
     uint64_t mine = VG_EMPTY_KEY, thr = VG_EMPTY_KEY;
     const int k = a.k;
-    const bool store_mode = WITHIN ? false : (a.out_dist != nullptr);
+    const bool store_mode = (WITHIN || MASKED) ? false : (a.out_dist != nullptr);
     uint64_t *wqueue = reinterpret_cast<uint64_t *>(smem + a.store_lds_off) + wave * VG_WITHIN_QUEUE;   // within mode only (vg_within_offer)
     int wqueued = 0;
     const long long wstride = (long long)gridDim.x * VG_WAVES_PER_BLOCK;
     const long long gw = (long long)blockIdx.x * VG_WAVES_PER_BLOCK + wave;
 
     // flattened (row, slice) stream per wavefront, one slice prefetched
-    auto load_slice = [&](uint4 (&dst)[U], long long row, int s) {
+    // (masked mode: `live` = the row's bit is set; a row whose bit is clear issues no slice loads - the same address selection)
+    auto load_slice = [&](uint4 (&dst)[U], long long row, int s, bool live = true) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int c = s * slice + u * VG_WAVE + lane;
             if (VG_LOAD_PREDICATED) {
                 uint4 v = make_uint4(0u, 0u, 0u, 0u);
-                if (row < a.n_rows && c < a.nch) v = vg_load16<NT>(a.rows + row * a.stride + (long long)c * 16);
+                if (row < a.n_rows && live && c < a.nch) v = vg_load16<NT>(a.rows + row * a.stride + (long long)c * 16);
                 dst[u] = v;
             } else {                                                // (unconditional, address selected: see vg_load_batch)
-                dst[u] = vg_load16<NT>((row < a.n_rows && c < a.nch) ? a.rows + row * a.stride + (long long)c * 16
-                                                                     : reinterpret_cast<const uint8_t *>(vg_zero_chunk));
+                dst[u] = vg_load16<NT>((row < a.n_rows && live && c < a.nch) ? a.rows + row * a.stride + (long long)c * 16
+                                                                             : reinterpret_cast<const uint8_t *>(vg_zero_chunk));
             }
         }
     };
     uint4 cur[U], nxt[U];
     long long row = gw;
-    load_slice(cur, row, 0);
+    // masked mode: the bit of the current row and of the wavefront's next one (wave-uniform, vg_mask_bits).  The next row's first slice is
+    // prefetched during the current row's last step, so its bit is fetched when the current row STARTS: one step ahead of that prefetch
+    // at least.  A row whose bit is clear takes one step (no loads, no arithmetic) instead of S.
+    bool m_cur = true, m_nxt = true;
+    if constexpr (MASKED) {
+        m_cur = vg_mask_bits(a.mask, row, 1, row < a.n_rows) != 0ull;
+        m_nxt = vg_mask_bits(a.mask, row + wstride, 1, row + wstride < a.n_rows) != 0ull;
+    }
+    load_slice(cur, row, 0, m_cur);
     Accum<VT, ACC> acc;
     acc.init();
     int s = 0;
     while (row < a.n_rows) {
         long long nrow = row;
         int ns = s + 1;
-        if (ns == S) { ns = 0; nrow = row + wstride; }
-        load_slice(nxt, nrow, ns);
+        bool m_load = m_cur;
+        if (ns == S || (MASKED && !m_cur)) { ns = 0; nrow = row + wstride; m_load = m_nxt; }
+        load_slice(nxt, nrow, ns, m_load);
+        if (!MASKED || m_cur) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc.chunk(qs[s * slice + u * VG_WAVE + lane], cur[u]);
-        if (ns == 0) {                                              // row complete
+            for (int u = 0; u < U; ++u) acc.chunk(qs[s * slice + u * VG_WAVE + lane], cur[u]);
+        }
+        if (ns == 0 && (!MASKED || m_cur)) {                        // row complete (masked mode: nothing to finish for a row that was not read)
             float d = acc.finish(qstat, 6, a.root);
             if constexpr (VT == T_F16 || VT == T_BF16) {
                 if (acc.special(qstat, 6) && lane == 0)
@@ -369,6 +442,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
                 vg_list_offer(vg_make_key(d, (uint32_t)row), (lane == 0) && (d < INFINITY), mine, thr, lane, k);
             }
             acc.init();
+        }
+        if constexpr (MASKED) {
+            if (ns == 0) { m_cur = m_nxt; m_nxt = vg_mask_bits(a.mask, nrow + wstride, 1, nrow + wstride < a.n_rows) != 0ull; }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];

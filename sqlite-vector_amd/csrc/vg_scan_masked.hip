@@ -1,0 +1,219 @@
+// vg_scan_masked.hip - masked scans: the k nearest rows among an allowed set (vg_scan_topk_masked, include/vectorgpu.h).
+//
+// The row mask is a bitmap over scan positions on the corpus handle (bit p & 63 of word p >> 6 = the row at position p may be returned;
+// bits behind the last row are zero), set once and read by any number of masked scans.  The kernels are the MASKED = true
+// instantiations of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h): the plain top-k scan's launch shape, loads, arithmetic, candidate
+// lists and merge - plus one scalar load of mask bits per batch, fetched one step ahead of the row prefetch, so that a batch without an
+// allowed row reads no rows and a row whose bit is clear is never offered to a list.  A translation unit of their own, like
+// vg_scan_ex.hip and vg_scan_within.hip: the plain kernels keep their register budget.  One load policy (non-temporal).
+//
+// Only vg_scan_topk_masked reads the mask.  Order: ascending (distance, scan position) whatever the handle's tie_order.
+#include "vg_internal.h"
+
+#include "vg_scan.h"
+
+typedef void (*scan_fn_t)(ScanArgs);
+
+template <int VT, int ACC>
+static scan_fn_t pick_u(int U) {
+    switch (U) {
+        case 1: return vg_scan_kernel<VT, ACC, 1, true, false, false, true>;
+        case 2: return vg_scan_kernel<VT, ACC, 2, true, false, false, true>;
+        case 3: return vg_scan_kernel<VT, ACC, 3, true, false, false, true>;
+        case 4: return vg_scan_kernel<VT, ACC, 4, true, false, false, true>;
+        case 6: return vg_scan_kernel<VT, ACC, 6, true, false, false, true>;
+        case 8: return vg_scan_kernel<VT, ACC, 8, true, false, false, true>;
+    }
+    return nullptr;
+}
+
+template <int VT>
+static scan_fn_t pick_acc(int acc, int U, bool long_rows) {
+    if (long_rows) {
+        switch (acc) {
+            case A_L2: return vg_scan_long_kernel<VT, A_L2, true, false, true>;
+            case A_COS: return vg_scan_long_kernel<VT, A_COS, true, false, true>;
+            case A_DOT: return vg_scan_long_kernel<VT, A_DOT, true, false, true>;
+            case A_L1: return vg_scan_long_kernel<VT, A_L1, true, false, true>;
+        }
+        return nullptr;
+    }
+    switch (acc) {
+        case A_L2: return pick_u<VT, A_L2>(U);
+        case A_COS: return pick_u<VT, A_COS>(U);
+        case A_DOT: return pick_u<VT, A_DOT>(U);
+        case A_L1: return pick_u<VT, A_L1>(U);
+        case A_COSN:
+            if constexpr (VT == T_F16 || VT == T_BF16) return pick_u<VT, A_COSN>(U);
+            return nullptr;
+    }
+    return nullptr;
+}
+
+static scan_fn_t pick_masked_kernel(int vtype, int acc, const VgShape &s) {
+    switch (vtype) {
+        case VG_TYPE_F32: return pick_acc<T_F32>(acc, s.U, s.long_rows);
+        case VG_TYPE_U8: return pick_acc<T_U8>(acc, s.U, s.long_rows);
+        case VG_TYPE_I8: return pick_acc<T_I8>(acc, s.U, s.long_rows);
+        case VG_TYPE_F16: return pick_acc<T_F16>(acc, s.U, s.long_rows);
+        case VG_TYPE_BF16: return pick_acc<T_BF16>(acc, s.U, s.long_rows);
+    }
+    return nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------ the mask on the handle
+
+// mask_host (ceil(n_rows / 64) words, tail bits clear) -> d_mask; the scan that follows runs on the same stream
+int vg_mask_upload(vg_corpus *c) {
+    HIP_TRY(hipSetDevice(c->device));
+    const int64_t words = (int64_t)c->mask_host.size();
+    if (words == 0) return VG_OK;
+    if (c->mask_cap_words < words) {
+        if (c->d_mask) { hipFree(c->d_mask); c->d_mask = nullptr; c->mask_cap_words = 0; }
+        HIP_TRY(hipMalloc(&c->d_mask, (size_t)words * sizeof(uint64_t)));
+        c->mask_cap_words = words;
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_mask, c->mask_host.data(), (size_t)words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                // (the host words may change right behind this call)
+    return VG_OK;
+}
+
+// the handle's mask becomes `words` (already sized and tail-cleared); a failed upload leaves no mask
+static int install_mask(vg_corpus *c, std::vector<uint64_t> &words) {
+    int64_t count = 0;
+    for (uint64_t w : words) count += __builtin_popcountll(w);
+    c->mask_host.swap(words);
+    c->mask_count = count;
+    int rc = vg_mask_upload(c);
+    if (rc != VG_OK) vg_drop_mask(c);
+    return rc;
+}
+
+extern "C" int vg_corpus_set_mask_bits(vg_corpus *c, const uint64_t *words, int64_t n_bits) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    if (n_bits < 0 || (n_bits > 0 && !words)) return vg_fail(VG_ERR_INVALID, "vg_corpus_set_mask_bits: bad words pointer / bit count");
+    if (n_bits > c->n_rows) return vg_fail(VG_ERR_INVALID, "vg_corpus_set_mask_bits: %lld bits for %lld rows", (long long)n_bits, (long long)c->n_rows);
+    std::vector<uint64_t> w((size_t)((c->n_rows + 63) / 64), 0ull);
+    const int64_t full = n_bits / 64;
+    if (full > 0) memcpy(w.data(), words, (size_t)full * sizeof(uint64_t));
+    if (n_bits % 64) w[(size_t)full] = words[full] & ((1ull << (n_bits % 64)) - 1ull);      // bits behind n_bits: zero
+    return install_mask(c, w);
+}
+
+extern "C" int vg_corpus_set_mask_rowids(vg_corpus *c, const int64_t *rowids, int64_t n, int64_t *out_set) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    if (out_set) *out_set = 0;
+    if (n < 0 || (n > 0 && !rowids)) return vg_fail(VG_ERR_INVALID, "vg_corpus_set_mask_rowids: bad rowids pointer / count");
+    if (!c->rowids.empty() && !c->rowids_ascending)
+        return vg_fail(VG_ERR_UNSUPPORTED, "vg_corpus_set_mask_rowids: the corpus' rowids are not ascending (no rowid lookup); set the mask by scan position");
+    std::vector<uint64_t> w((size_t)((c->n_rows + 63) / 64), 0ull);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t p = vg_corpus_find_rowid(c, rowids[i]);              // (rowids not held are ignored, duplicates set a set bit)
+        if (p >= 0) w[(size_t)(p >> 6)] |= 1ull << (p & 63);
+    }
+    int rc = install_mask(c, w);
+    if (rc == VG_OK && out_set) *out_set = c->mask_count;
+    return rc;
+}
+
+extern "C" int vg_corpus_clear_mask(vg_corpus *c) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    vg_drop_mask(c);
+    return VG_OK;
+}
+
+extern "C" int64_t vg_corpus_mask_count(const vg_corpus *c) { return c ? c->mask_count : -1; }
+
+// ------------------------------------------------------------------------------------------------ the scan
+
+// the masked kernel + the plain scan's merge; the k winners land in the pinned c->h_keys (copied behind the merge)
+static int launch_masked(vg_corpus *c, int metric, int k) {
+    int acc = vg_metric_to_acc(metric);
+    VgShape s;
+    vg_plain_scan_shape(c, metric, &s);
+    if (acc == A_COS && (c->vtype == VG_TYPE_F16 || c->vtype == VG_TYPE_BF16) && !s.long_rows && vg_sw(SW_VG_HALF_COSN, 1)) {
+        int rcn = vg_ensure_row_norms(c);                    // the plain scan's cached-norm cosine: the same floats
+        if (rcn != VG_OK) return rcn;
+        acc = A_COSN;
+    }
+    scan_fn_t fn = pick_masked_kernel(c->vtype, acc, s);
+    if (!fn) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_masked: no kernel for this type / metric");
+
+    // the launch shape of the plain top-k scan (vg_api.hip: launch_scan)
+    const long long blocks = vg_plain_scan_blocks(c, c->n_rows, s);
+
+    ScanArgs a{};
+    a.rows = c->d_rows;
+    a.query = c->d_query;
+    a.cand = c->d_cand;
+    a.n_rows = c->n_rows;
+    a.stride = c->stride;
+    a.nch = c->nch;
+    a.lpr_log2 = s.lpr_log2;
+    a.k = k;
+    a.root = (metric == VG_DIST_L2) ? 1 : 0;
+    a.dim = c->dim;
+    a.row_nn = (acc == A_COSN) ? c->d_xnorm : nullptr;
+    a.mask = c->d_mask;
+    size_t qbytes = (size_t)c->nch * 16;
+    if (s.long_rows) {
+        const size_t slice = (size_t)VG_WAVE * VG_LONG_U;
+        qbytes = ((c->nch + slice - 1) / slice) * slice * 16;
+    }
+    const size_t smem = std::max<size_t>(qbytes, (size_t)VG_PUBLISH_LDS_BYTES);
+
+    hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);
+    if (evs) hipEventRecord(evs[0], c->stream);
+    if (smem > 64 * 1024)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, c->stream, a);
+    if (evs) hipEventRecord(evs[2], c->stream);
+    int rcm = vg_launch_merge_one(c->d_cand, (int)blocks, k, c->d_keys, c->stream);
+    if (evs) hipEventRecord(evs[3], c->stream);
+    if (rcm != 0) return vg_fail(VG_ERR_HIP, "vg_scan_topk_masked: merge launch failed: %s", hipGetErrorString((hipError_t)rcm));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_keys, c->d_keys, VG_WAVE * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return VG_OK;
+}
+
+// packed keys (distance image << 32 | position local to this corpus), ascending: the form a multi-shard caller merges
+extern "C" int vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, int *out_count) {
+    if (!c || !query || !out_count) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: NULL argument");
+    *out_count = 0;
+    if (k < 1) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: k must be at least 1");
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_masked: k must be in 1..%d (masked scans use the fused list only)", VG_MAX_FUSED_K);
+    if (!out_keys) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: NULL output");
+    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: no row mask set");
+    if (c->mask_count == 0 || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
+    HIP_TRY(hipSetDevice(c->device));
+    c->enqueued = false;                                     // (the pinned key buffer is this scan's landing zone now)
+    memset(c->h_query, 0, (size_t)c->stride);
+    memcpy(c->h_query, query, (size_t)c->dim * c->es);
+    HIP_TRY(hipMemcpyAsync(c->d_query, c->h_query, (size_t)c->stride, hipMemcpyHostToDevice, c->stream));
+    int rc = launch_masked(c, metric, k);
+    if (rc != VG_OK) return rc;
+    vg_collect_timing(c);
+    int cnt = 0;
+    while (cnt < k && c->h_keys[cnt] != VG_EMPTY_KEY) { out_keys[cnt] = c->h_keys[cnt]; ++cnt; }
+    *out_count = cnt;
+    return VG_OK;
+}
+
+extern "C" int vg_scan_topk_masked(vg_corpus *c, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
+                                   int *out_count) {
+    if (!c || !query || !out_count) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: NULL argument");
+    *out_count = 0;
+    if (k >= 1 && k <= VG_MAX_FUSED_K && (!out_rowids || !out_dist)) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: NULL output");
+    uint64_t keys[VG_WAVE];
+    int cnt = 0;
+    int rc = vg_scan_topk_masked_keys(c, metric, query, k, keys, &cnt);
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < cnt; ++i) {
+        out_dist[i] = (double)vg_key_distance(keys[i]);
+        out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(keys[i]));
+    }
+    *out_count = cnt;
+    return VG_OK;
+}

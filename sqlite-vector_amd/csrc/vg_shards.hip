@@ -930,6 +930,110 @@ extern "C" int vg_shards_within_last_launches(const vg_shards *s) {
     return most;
 }
 
+// ---- masked scans: the mask is given over GLOBAL scan positions and dealt out by the block-cyclic map of the rows (block b of B rows
+// -> shard b % S, local rows (b / S) * B ...); every shard runs vg_scan_topk_masked over its own bits and the lists merge like the plain
+// scan's, by (distance image, global position)
+static inline uint64_t bits_at(const uint64_t *w, int64_t n_bits, int64_t pos, int n) {       // n <= 64 bits from `pos` on, 0 behind n_bits
+    if (pos >= n_bits) return 0ull;
+    const int64_t i = pos >> 6;
+    const int sh = (int)(pos & 63);
+    uint64_t v = w[i] >> sh;
+    if (sh && ((i + 1) << 6) < n_bits) v |= w[i + 1] << (64 - sh);
+    const int64_t have = std::min<int64_t>(n, n_bits - pos);
+    return have >= 64 ? v : (v & ((1ull << have) - 1ull));
+}
+static inline void bits_put(uint64_t *w, int64_t pos, int n, uint64_t v) {                     // into zeroed words
+    const int64_t i = pos >> 6;
+    const int sh = (int)(pos & 63);
+    w[i] |= v << sh;
+    if (sh && sh + n > 64) w[i + 1] |= v >> (64 - sh);
+}
+
+// every shard's local words become its mask; a failure on the way leaves NO shard with a mask (never a mix of the new and the old one)
+static int install_shard_masks(vg_shards *s, std::vector<std::vector<uint64_t>> &local, int64_t *out_set) {
+    int64_t total = 0;
+    for (int i = 0; i < s->S; ++i) {
+        int rc = vg_corpus_set_mask_bits(s->sh[(size_t)i], local[(size_t)i].data(), vg_corpus_rows(s->sh[(size_t)i]));
+        if (rc != VG_OK) {
+            const std::string msg = vg_last_error();
+            for (auto *c : s->sh) vg_corpus_clear_mask(c);
+            return fail(rc, msg.c_str());
+        }
+        total += vg_corpus_mask_count(s->sh[(size_t)i]);
+    }
+    if (out_set) *out_set = total;
+    return VG_OK;
+}
+
+extern "C" int vg_shards_set_mask_bits(vg_shards *s, const uint64_t *words, int64_t n_bits) {
+    if (!s) return fail(VG_ERR_INVALID, "shards handle is NULL");
+    if (s->S == 1) return vg_corpus_set_mask_bits(s->sh[0], words, n_bits);
+    if (n_bits < 0 || (n_bits > 0 && !words) || n_bits > s->n_rows) return fail(VG_ERR_INVALID, "vg_shards_set_mask_bits: bad words pointer / bit count");
+    std::vector<std::vector<uint64_t>> local((size_t)s->S);
+    for (int i = 0; i < s->S; ++i) local[(size_t)i].assign((size_t)((vg_corpus_rows(s->sh[(size_t)i]) + 63) / 64) + 1, 0ull);
+    for (int64_t g = 0; g < n_bits; g += s->B) {                               // block by block: one shard, consecutive local positions
+        int shard;
+        int64_t l0;
+        locate(s, g, &shard, &l0);
+        const int64_t len = std::min<int64_t>(s->B, n_bits - g);
+        for (int64_t o = 0; o < len; o += 64) {
+            const int n = (int)std::min<int64_t>(64, len - o);
+            const uint64_t v = bits_at(words, n_bits, g + o, n);
+            if (v) bits_put(local[(size_t)shard].data(), l0 + o, n, v);
+        }
+    }
+    return install_shard_masks(s, local, nullptr);
+}
+
+extern "C" int vg_shards_set_mask_rowids(vg_shards *s, const int64_t *rowids, int64_t n, int64_t *out_set) {
+    if (!s) return fail(VG_ERR_INVALID, "shards handle is NULL");
+    if (s->S == 1) return vg_corpus_set_mask_rowids(s->sh[0], rowids, n, out_set);
+    if (out_set) *out_set = 0;
+    if (n < 0 || (n > 0 && !rowids)) return fail(VG_ERR_INVALID, "vg_shards_set_mask_rowids: bad rowids pointer / count");
+    std::vector<std::vector<uint64_t>> local((size_t)s->S);
+    for (int i = 0; i < s->S; ++i) local[(size_t)i].assign((size_t)((vg_corpus_rows(s->sh[(size_t)i]) + 63) / 64) + 1, 0ull);
+    for (int i = 0; i < s->S; ++i)                                             // (decided before any rowid is looked at, like one corpus does)
+        if (vg_corpus_find_rowid(s->sh[(size_t)i], 0) == -2)
+            return fail(VG_ERR_UNSUPPORTED, "vg_shards_set_mask_rowids: the rowids are not ascending (no rowid lookup); set the mask by scan position");
+    for (int64_t j = 0; j < n; ++j)
+        for (int i = 0; i < s->S; ++i) {                                       // (every shard keeps its own rowid map: S bisections per rowid)
+            const int64_t p = vg_corpus_find_rowid(s->sh[(size_t)i], rowids[j]);
+            if (p >= 0) { local[(size_t)i][(size_t)(p >> 6)] |= 1ull << (p & 63); break; }
+        }
+    return install_shard_masks(s, local, out_set);
+}
+
+extern "C" int vg_shards_clear_mask(vg_shards *s) {
+    if (!s) return fail(VG_ERR_INVALID, "shards handle is NULL");
+    for (auto *c : s->sh) { int rc = vg_corpus_clear_mask(c); if (rc != VG_OK) return rc; }
+    return VG_OK;
+}
+
+// rows allowed over all shards; -1 when a shard has no mask (an append drops the mask of the shards it reaches)
+extern "C" int64_t vg_shards_mask_count(const vg_shards *s) {
+    if (!s) return -1;
+    int64_t total = 0;
+    for (auto *c : s->sh) { const int64_t n = vg_corpus_mask_count(c); if (n < 0) return -1; total += n; }
+    return total;
+}
+
+extern "C" int vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
+                                          int *out_count) {
+    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_masked: NULL argument");
+    if (s->S == 1) return vg_scan_topk_masked(s->sh[0], metric, query, k, out_rowids, out_dist, out_count);
+    *out_count = 0;
+    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_masked: k must be at least 1");
+    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_masked: k must be in 1..64 (masked scans use the fused list only)");
+    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_masked: NULL output");
+    if (vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_topk_masked: no row mask set");
+    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
+    std::vector<int> counts((size_t)s->S, 0);
+    int rc = for_each_shard(s, [&](int i) { return vg_scan_topk_masked_keys(s->sh[(size_t)i], metric, query, k, &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]); });
+    if (rc != VG_OK) return rc;
+    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), k, out_rowids, out_dist);
+    return VG_OK;
+}
+
 extern "C" int vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative) {
     if (!s || !out_min || !out_max || !out_any_negative) return fail(VG_ERR_INVALID, "vg_shards_minmax: NULL argument");
     if (s->S == 1) return vg_corpus_minmax(s->sh[0], out_min, out_max, out_any_negative);

@@ -164,6 +164,7 @@ int sqlite3_prepare_v2(sqlite3 *, const char *zSql, int nByte, sqlite3_stmt **pp
 int sqlite3_step(sqlite3_stmt *);
 int sqlite3_reset(sqlite3_stmt *);
 int sqlite3_finalize(sqlite3_stmt *);
+int sqlite3_stmt_readonly(sqlite3_stmt *);
 int sqlite3_bind_blob(sqlite3_stmt *, int, const void *, int n, void (*)(void *));
 int sqlite3_bind_double(sqlite3_stmt *, int, double);
 int sqlite3_bind_int(sqlite3_stmt *, int, int);
@@ -171,6 +172,7 @@ int sqlite3_bind_int64(sqlite3_stmt *, int, sqlite3_int64);
 int sqlite3_bind_text(sqlite3_stmt *, int, const char *, int, void (*)(void *));
 const void *sqlite3_column_blob(sqlite3_stmt *, int iCol);
 int sqlite3_column_bytes(sqlite3_stmt *, int iCol);
+int sqlite3_column_count(sqlite3_stmt *);
 double sqlite3_column_double(sqlite3_stmt *, int iCol);
 int sqlite3_column_int(sqlite3_stmt *, int iCol);
 sqlite3_int64 sqlite3_column_int64(sqlite3_stmt *, int iCol);
@@ -227,7 +229,9 @@ struct sqlite3_api_routines {
     void *unused_17[2];
     __typeof__(sqlite3_column_blob) *sqlite3_column_blob;
     __typeof__(sqlite3_column_bytes) *sqlite3_column_bytes;
-    void *unused_21[6];
+    void *unused_21[1];
+    __typeof__(sqlite3_column_count) *sqlite3_column_count;
+    void *unused_23[4];
     __typeof__(sqlite3_column_double) *sqlite3_column_double;
     __typeof__(sqlite3_column_int) *sqlite3_column_int;
     __typeof__(sqlite3_column_int64) *sqlite3_column_int64;
@@ -307,7 +311,8 @@ struct sqlite3_api_routines {
     __typeof__(sqlite3_create_function_v2) *sqlite3_create_function_v2;
     void *unused_163[17];
     __typeof__(sqlite3_db_filename) *sqlite3_db_filename;
-    void *unused_181[5];
+    void *unused_181[4];
+    __typeof__(sqlite3_stmt_readonly) *sqlite3_stmt_readonly;
     __typeof__(sqlite3_stricmp) *sqlite3_stricmp;
     void *unused_187[10];
     __typeof__(sqlite3_malloc64) *sqlite3_malloc64;
@@ -327,6 +332,7 @@ struct sqlite3_api_routines {
 #define sqlite3_close                sqlite3_api->sqlite3_close
 #define sqlite3_column_blob          sqlite3_api->sqlite3_column_blob
 #define sqlite3_column_bytes         sqlite3_api->sqlite3_column_bytes
+#define sqlite3_column_count         sqlite3_api->sqlite3_column_count
 #define sqlite3_column_double        sqlite3_api->sqlite3_column_double
 #define sqlite3_column_int           sqlite3_api->sqlite3_column_int
 #define sqlite3_column_int64         sqlite3_api->sqlite3_column_int64
@@ -365,6 +371,7 @@ struct sqlite3_api_routines {
 #define sqlite3_result_value         sqlite3_api->sqlite3_result_value
 #define sqlite3_snprintf             sqlite3_api->sqlite3_snprintf
 #define sqlite3_step                 sqlite3_api->sqlite3_step
+#define sqlite3_stmt_readonly        sqlite3_api->sqlite3_stmt_readonly
 #define sqlite3_stricmp              sqlite3_api->sqlite3_stricmp
 #define sqlite3_threadsafe           sqlite3_api->sqlite3_threadsafe
 #define sqlite3_total_changes        sqlite3_api->sqlite3_total_changes
