@@ -480,6 +480,14 @@ class Corpus:
     def clear(self):
         _check(lib().vg_corpus_clear(self.h))
 
+    def reserve(self, n):
+        """room for n rows in all (vg_corpus_reserve): never shrinks"""
+        _check(lib().vg_corpus_reserve(self.h, n))
+
+    def trim(self):
+        """give back what a reservation holds beyond the rows that arrived (vg_corpus_trim)"""
+        _check(lib().vg_corpus_trim(self.h))
+
     def tie_stats(self):
         """reference-order scans so far: {scans, with_a_tie_among_the_k_plus_1_best, fused_replays, store_mode_replays}"""
         out = np.zeros(4, dtype=np.uint64)
@@ -565,6 +573,30 @@ class Shards:
 
     def clear(self):
         _check(lib().vg_shards_clear(self.h))
+
+    def trim(self):
+        _check(lib().vg_shards_trim(self.h))
+
+    def clone(self):
+        """a second shard set with the same rows, rowids and switches (vg_shards_clone)"""
+        other = Shards.__new__(Shards)
+        other.h = C.c_void_p()
+        other.vtype, other.dim = self.vtype, self.dim
+        _check(lib().vg_shards_clone(self.h, C.byref(other.h)))
+        return other
+
+    def find_rowid(self, rowid):
+        """global scan position of `rowid`, -1 not held, -2 no lookup (vg_shards_find_rowid)"""
+        return int(lib().vg_shards_find_rowid(self.h, rowid))
+
+    def patch_rows(self, positions, rows):
+        positions = np.ascontiguousarray(positions, dtype=np.int64)
+        rows = np.ascontiguousarray(rows)
+        _check(lib().vg_shards_patch_rows(self.h, _ptr(positions), positions.shape[0], _ptr(rows), rows.strides[0]))
+
+    def delete_rows(self, positions):
+        positions = np.ascontiguousarray(positions, dtype=np.int64)
+        _check(lib().vg_shards_delete_rows(self.h, _ptr(positions), positions.shape[0]))
 
     def append(self, rows, rowids=None):
         rows = np.ascontiguousarray(rows)
