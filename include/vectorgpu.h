@@ -173,7 +173,7 @@ int vg_scan_within_keys(const vg_corpus *c, int64_t first, int64_t n, uint64_t *
  * mapped to positions on the host (implicit rowids: rowid - base; an ascending map: the search behind vg_corpus_find_rowid; a map
  * that is not ascending: VG_ERR_UNSUPPORTED); rowids the corpus does not hold are ignored, duplicates are harmless, *out_set (may
  * be NULL) = rows allowed.  vg_corpus_mask_count: rows allowed, -1 without a mask.
- * ONLY vg_scan_topk_masked reads the mask: every other call behaves the same with and without one.  A call that changes the
+ * ONLY the masked scans (vg_scan_topk_masked, vg_scan_topk_batch_masked) read the mask: every other call behaves the same with and without one.  A call that changes the
  * number of rows or which row sits at which position (append*, delete_rows, clear) drops the mask; patch_rows, reserve and trim
  * keep it; vg_corpus_clone copies it.
  * vg_scan_topk_masked: the contract of vg_scan_topk restricted to the allowed rows - NaN / +Inf never enter, fewer than k rows
@@ -189,6 +189,28 @@ int64_t vg_corpus_mask_count(const vg_corpus *c);
 int     vg_scan_topk_masked(vg_corpus *c, int metric, const void *query, int k,
                             int64_t *out_rowids, double *out_dist, int *out_count);
 int     vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, int *out_count);
+
+/* ---- masked batch scans: one row mask, nq queries (row-major nq x dim, host) - "the k nearest rows of this tenant, for these 50
+ * queries".  The mask is the one vg_corpus_set_mask_* left on the handle; these three calls and vg_scan_topk_masked[_keys] are the
+ * only ones that read it - vg_scan_topk_batch still ignores it.  out_rowids / out_dist are nq x k, out_counts nq; the slots of
+ * query i behind out_counts[i] are NOT written.
+ * Query i's answer is what vg_scan_topk_masked is contracted to return for it: only allowed rows, ascending (distance, scan
+ * position) whatever the handle's tie_order, NaN / +Inf never enter, fewer than k rows when fewer allowed rows qualify.
+ * f32 / uint8 / int8 rows of a register-resident shape: 4 queries (2 where a lane holds 4 or 6 chunks of the row) share every row
+ * load of a pass, and a pass reads only the batches of rows that hold an allowed row (vg_scan_multi_masked.h; the plan:
+ * vg_batch_masked_plan, vectorgpu_diag.h); nq queries cost ceil(nq / 4) - or ceil(nq / 2) - such passes, enqueued back to back with
+ * one wait at the end.  uint8 / int8: rowids, order and distance bits identical to nq vg_scan_topk_masked calls.  f32: the single
+ * scan's arithmetic per (query, row) pair, possibly under another lane decomposition (the multi-query scans' launch shape) - the
+ * single masked scan's bits where the two shapes agree, its floats up to the summation order elsewhere.  f16 / bf16, long rows and
+ * every other shape without a multi-query form: nq single masked scans - same contract, no sharing.  Timings not measured yet
+ * (DESIGN.md 3.9).
+ * 1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below); nq < 1 or a NULL argument: VG_ERR_INVALID; no mask set:
+ * VG_ERR_INVALID; an empty mask or an empty corpus: every count 0 without a launch.  vg_scan_topk_batch_masked_keys: the same as
+ * packed keys with positions local to this corpus (out_keys nq x k) - the form a multi-shard caller merges. */
+int     vg_scan_topk_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, int k,
+                                  int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k,
+                                       uint64_t *out_keys, int *out_counts);
 
 /* nq queries at once (row-major nq x dim, host).  out_rowids / out_dist are nq x k, out_counts nq.
  * f32 corpora, k <= 32, rows <= 512 floats, metric DOT / COSINE / L2 / SQUARED_L2: one pass over the corpus on the
@@ -269,6 +291,10 @@ int     vg_shards_clear_mask(vg_shards *s);
 int64_t vg_shards_mask_count(const vg_shards *s);
 int     vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *query, int k,
                                    int64_t *out_rowids, double *out_dist, int *out_count);
+/* vg_scan_topk_batch_masked over every shard (each answers all nq queries over its own bits), merged per query by (distance,
+ * GLOBAL scan position): the answer of one corpus holding all rows.  Same contract. */
+int     vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const void *queries, int nq, int k,
+                                         int64_t *out_rowids, double *out_dist, int *out_counts);
 int     vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative);
 int     vg_shards_quantize_rows(vg_shards *s, float scale, float offset, int qtype, int64_t row0, int64_t n_rows, uint8_t *out_host);
 

@@ -51,6 +51,11 @@ int vg_batch_last_path(const vg_corpus *c);
 /* how this corpus' last attempt at the int8 batch filter ended: 0 it answered, 1 no room for the tile-major int8 copy, 2 shape not
  * served, 3 a pair region overflowed (the batch was answered by another path and the next 16 batches skip the int8 filter) */
 int vg_batch_q8_status(const vg_corpus *c);
+/* how vg_scan_topk_batch_masked would serve this corpus under `metric`: queries per pass of the masked multi-query scan (4 or 2; 0 =
+ * the fallback, one single masked scan per query) and the launch shape of the kernel that runs - lanes per row, 16-byte chunks per
+ * lane (the single masked scan's shape for the fallback; 64 / 0 for the long-row kernel).  Pure host logic.  Every pass of a masked
+ * batch takes one slot of the profiling ring (vg_set_profiling / vg_profile_mean_ms: kernel and merge time per pass). */
+int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 
 /* kernel milliseconds (HIP events on the corpus stream) and rows of the corpus' last vg_corpus_minmax (which = 0) /
  * vg_corpus_quantize_rows (1) pass, and - while profiling is on - of the last int8 shadow-copy pass of the filter scans (2) */

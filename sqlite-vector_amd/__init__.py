@@ -187,6 +187,10 @@ def _load():
         "vg_shards_clear_mask": (i32, [vp]),
         "vg_shards_mask_count": (i64, [vp]),
         "vg_shards_scan_topk_masked": (i32, [vp, i32, vp, i32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_batch_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
+        "vg_scan_topk_batch_masked_keys": (i32, [vp, i32, vp, i32, i32, vp, vp]),
+        "vg_shards_scan_topk_batch_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
+        "vg_batch_masked_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -228,6 +232,24 @@ def plan_scan_shape(vtype, dim, metric):
     lpr, u, lng = C.c_int(0), C.c_int(0), C.c_int(0)
     _check(lib().vg_plan_scan_shape(vtype, dim, metric, C.byref(lpr), C.byref(u), C.byref(lng)))
     return lpr.value, u.value, bool(lng.value)
+
+
+def batch_masked_plan(corpus, metric):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_topk_batch_masked serves this corpus with; 0 queries per pass =
+    one single masked scan per query (f16 / bf16, long rows) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().vg_batch_masked_plan(corpus.h, metric, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
+
+
+def _scan_topk_batch_masked(fn, h, metric, queries, k):
+    queries = np.ascontiguousarray(queries)
+    nq = queries.shape[0]
+    ids = np.zeros((nq, max(k, 1)), dtype=np.int64)
+    dist = np.zeros((nq, max(k, 1)), dtype=np.float64)
+    cnt = np.zeros(max(nq, 1), dtype=np.int32)
+    _check(fn(h, metric, _ptr(queries), nq, k, _ptr(ids), _ptr(dist), _ptr(cnt)))
+    return ids, dist, cnt[:nq]
 
 
 def _set_mask(obj, prefix, rows, bits, positions, rowids):
@@ -327,7 +349,7 @@ class Corpus:
             _check(lib().vg_scan_within_fetch(self.h, 0, n, _ptr(ids), _ptr(dist)))
         return ids, dist, m.value
 
-    # masked scans: a row mask on the handle (a bitmap over scan positions), read by scan_topk_masked only
+    # masked scans: a row mask on the handle (a bitmap over scan positions), read by scan_topk_masked / scan_topk_batch_masked only
     def set_mask(self, bits=None, positions=None, rowids=None):
         """the rows a masked scan may return - exactly one of: `bits` (bool per scan position, or packed uint64 words: bit p & 63 of
         word p >> 6), `positions` (scan positions), `rowids` (those not held are ignored).  Returns the number of rows allowed."""
@@ -348,6 +370,11 @@ class Corpus:
         cnt = C.c_int(0)
         _check(lib().vg_scan_topk_masked(self.h, metric, _ptr(query), k, _ptr(ids), _ptr(dist), C.byref(cnt)))
         return ids[:cnt.value], dist[:cnt.value]
+
+    def scan_topk_batch_masked(self, metric, queries, k):
+        """scan_topk_masked for every row of `queries` in shared passes over the allowed rows: (rowids [nq, k], distances [nq, k],
+        counts [nq]) like scan_topk_batch; slots behind a query's count stay zero"""
+        return _scan_topk_batch_masked(lib().vg_scan_topk_batch_masked, self.h, metric, queries, k)
 
     def clone(self):
         """a second corpus with the same rows, rowids, switches and row mask (vg_corpus_clone)"""
@@ -676,6 +703,10 @@ class Shards:
         cnt = C.c_int(0)
         _check(lib().vg_shards_scan_topk_masked(self.h, metric, _ptr(query), k, _ptr(ids), _ptr(dist), C.byref(cnt)))
         return ids[:cnt.value], dist[:cnt.value]
+
+    def scan_topk_batch_masked(self, metric, queries, k):
+        """Corpus.scan_topk_batch_masked over all shards, merged per query by (distance, global scan position)"""
+        return _scan_topk_batch_masked(lib().vg_shards_scan_topk_batch_masked, self.h, metric, queries, k)
 
     def scan_within(self, metric, query, radius, limit=None):
         """Corpus.scan_within over all shards, merged by (distance, global scan position): (rowids, distances, matches)"""

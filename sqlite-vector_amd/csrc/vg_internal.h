@@ -267,3 +267,4 @@ int vg_ensure_q8_shadow(vg_corpus *c);                             // vg_filter.
 int vg_multi_queries_per_pass(const vg_corpus *c, int metric);     // vg_multi.hip: queries per pass of the multi-query scan, 0 = none
 int vg_launch_scan_multi(vg_corpus *c, int metric, const uint8_t *dev_queries, int k, uint64_t *dev_cand,
                          uint64_t *dev_out_keys, hipStream_t stream);   // vg_multi.hip; -1: no multi-query kernel for this shape
+int vg_multi_plan(const vg_corpus *c, int metric, VgShape *s);     // vg_multi.hip: queries per pass + the launch shape they run with

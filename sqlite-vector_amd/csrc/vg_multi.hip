@@ -60,6 +60,9 @@ int vg_multi_queries_per_pass(const vg_corpus *c, int metric) {
     return multi_plan(c, metric, &s);
 }
 
+// the same plan with its launch shape: what the masked multi-query scan (vg_multi_masked.hip) is launched with too
+int vg_multi_plan(const vg_corpus *c, int metric, VgShape *s) { return multi_plan(c, metric, s); }
+
 // NQ = vg_multi_queries_per_pass() queries (zero-padded rows of the corpus stride, back to back at dev_queries) against
 // the corpus in ONE pass; dev_cand: NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on
 // `stream`.  Returns -1 when the shape has no multi-query kernel, VG_OK or an error code otherwise.

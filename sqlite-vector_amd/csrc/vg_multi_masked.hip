@@ -1,0 +1,186 @@
+// vg_multi_masked.hip - masked batch scans: the k nearest ALLOWED rows for many queries (vg_scan_topk_batch_masked, include/vectorgpu.h).
+//
+// Host side of the masked multi-query scan (vg_scan_multi_masked.h): kernel table, launch, and the batch entry points.  The plan is
+// the multi-query scan's (vg_multi_plan: 4 queries per pass with up to 3 chunks per lane, 2 with 4 or 6; f32 / uint8 / int8 rows that
+// fit the register-resident shapes); a pass reads the batches of rows that hold an allowed row, once, for all its queries.  Shapes
+// without a multi-query form (f16 / bf16, long rows) are answered by nq single masked scans (vg_scan_masked.hip): same contract, no
+// sharing.  A translation unit of its own, like vg_multi.hip: its kernel instances compile next to the others, not after them.
+#include "vg_internal.h"
+
+#include "vg_scan_multi_masked.h"
+
+typedef void (*scan_fn_t)(ScanArgs);
+
+template <int VT, int ACC, int NQ>
+static scan_fn_t pick_mm_u(int U) {
+    if constexpr (NQ == 4) {
+        switch (U) {
+            case 1: return vg_scan_multi_masked_kernel<VT, ACC, 1, 4, true>;
+            case 2: return vg_scan_multi_masked_kernel<VT, ACC, 2, 4, true>;
+            case 3: return vg_scan_multi_masked_kernel<VT, ACC, 3, 4, true>;
+        }
+    } else {
+        switch (U) {
+            case 4: return vg_scan_multi_masked_kernel<VT, ACC, 4, 2, true>;
+            case 6: return vg_scan_multi_masked_kernel<VT, ACC, 6, 2, true>;
+        }
+    }
+    return nullptr;
+}
+template <int VT, int NQ>
+static scan_fn_t pick_mm_acc(int acc, int U) {
+    switch (acc) {
+        case A_L2: return pick_mm_u<VT, A_L2, NQ>(U);
+        case A_COS: return pick_mm_u<VT, A_COS, NQ>(U);
+        case A_DOT: return pick_mm_u<VT, A_DOT, NQ>(U);
+        case A_L1: return pick_mm_u<VT, A_L1, NQ>(U);
+    }
+    return nullptr;
+}
+static scan_fn_t pick_mm(int vtype, int acc, int U, int NQ) {
+    switch (vtype) {
+        case VG_TYPE_F32: return NQ == 4 ? pick_mm_acc<T_F32, 4>(acc, U) : pick_mm_acc<T_F32, 2>(acc, U);
+        case VG_TYPE_U8: return NQ == 4 ? pick_mm_acc<T_U8, 4>(acc, U) : pick_mm_acc<T_U8, 2>(acc, U);
+        case VG_TYPE_I8: return NQ == 4 ? pick_mm_acc<T_I8, 4>(acc, U) : pick_mm_acc<T_I8, 2>(acc, U);
+    }
+    return nullptr;
+}
+
+// (queries per pass, launch shape, kernel) of the masked multi-query scan; 0 queries per pass: the fallback serves the shape
+static int mm_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn) {
+    const int NQ = vg_multi_plan(c, metric, s);
+    if (NQ == 0) return 0;
+    scan_fn_t f = pick_mm(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
+    if (fn) *fn = f;
+    return f ? NQ : 0;
+}
+
+extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    VgShape s{};
+    const int NQ = mm_plan(c, metric, &s, nullptr);
+    if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single masked scan's
+    if (out_queries_per_pass) *out_queries_per_pass = NQ;
+    if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
+    if (out_u) *out_u = s.long_rows ? 0 : s.U;
+    return VG_OK;
+}
+
+// NQ queries (zero-padded rows of the corpus stride, back to back at dev_queries) against the allowed rows in ONE pass; dev_cand:
+// NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on the corpus stream.
+static int launch_multi_masked(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_queries, int k,
+                               uint64_t *dev_cand, uint64_t *dev_out_keys) {
+    const int rpb = VG_WAVE >> s.lpr_log2;
+    const long long nbatch = (c->n_rows + rpb - 1) / rpb;
+    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
+    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count));
+    blocks = std::min<long long>(blocks, VG_SEL_MAX_HEADS);
+    ScanArgs a{};
+    a.rows = c->d_rows; a.query = dev_queries; a.cand = dev_cand; a.out_dist = nullptr; a.n_rows = c->n_rows;
+    a.stride = c->stride; a.nch = c->nch; a.lpr_log2 = s.lpr_log2; a.k = k; a.root = (metric == VG_DIST_L2) ? 1 : 0;
+    a.dim = c->dim; a.row_nn = nullptr; a.store_lds_off = 0;
+    a.mask = c->d_mask;
+    const size_t smem = std::max<size_t>((size_t)NQ * c->nch * 16, (size_t)VG_PUBLISH_LDS_BYTES);
+    if (smem > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);          // one slot of the profiling ring per pass
+    if (evs) hipEventRecord(evs[0], c->stream);
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, c->stream, a);
+    if (evs) hipEventRecord(evs[2], c->stream);
+    int rc = vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
+    if (evs) hipEventRecord(evs[3], c->stream);
+    if (rc != 0) return vg_fail(VG_ERR_HIP, "vg_scan_topk_batch_masked: merge launch failed: %s", hipGetErrorString((hipError_t)rc));
+    HIP_TRY(hipGetLastError());
+    return VG_OK;
+}
+
+// queries go up in slices of this many (a multiple of every queries-per-pass): the device staging area does not grow with the batch
+#define VG_BMASK_SLICE 256
+
+// nq queries, NQ per pass; every pass of every slice is enqueued back to back on the corpus stream, one wait at the end
+static int batch_masked_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries, int nq, int k,
+                              uint64_t *out_keys, int *out_counts) {
+    const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
+    const int slice = std::min(nq_pad, VG_BMASK_SLICE);
+    const size_t qbytes = (size_t)slice * c->stride, keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
+    if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
+                                HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
+    if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
+                                     HIP_TRY(hipMalloc(&c->d_bkeys, keybytes)); c->bkeys_bytes = keybytes; }
+    // zero-padded rows of the corpus stride; pad queries are zero.  The whole batch stays on the host until the wait: a slice's copy
+    // is ordered behind the passes of the slice in front of it by the stream, its source must not move before it ran
+    std::vector<uint8_t> hq((size_t)nq_pad * c->stride, 0);
+    const size_t row_bytes = (size_t)c->dim * c->es;
+    for (int i = 0; i < nq; ++i) memcpy(hq.data() + (size_t)i * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
+    int rc = VG_OK;
+    for (int q0 = 0; q0 < nq_pad && rc == VG_OK; q0 += slice) {
+        const int nqs = std::min(slice, nq_pad - q0);
+        hipError_t e = hipMemcpyAsync(c->d_bq, hq.data() + (size_t)q0 * c->stride, (size_t)nqs * c->stride, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { rc = vg_fail(VG_ERR_HIP, "vg_scan_topk_batch_masked: query upload failed: %s", hipGetErrorString(e)); break; }
+        for (int g = 0; g < nqs && rc == VG_OK; g += NQ)
+            rc = launch_multi_masked(c, metric, fn, NQ, s, (const uint8_t *)c->d_bq + (size_t)g * c->stride, k, c->d_cand,
+                                     c->d_bkeys + (size_t)(q0 + g) * 64);
+    }
+    if (rc != VG_OK) { hipStreamSynchronize(c->stream); return rc; }      // (hq must outlive what was enqueued)
+    std::vector<uint64_t> keys((size_t)nq * 64);
+    hipError_t e = hipMemcpyAsync(keys.data(), c->d_bkeys, (size_t)nq * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+    hipError_t e2 = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess || e2 != hipSuccess)
+        return vg_fail(VG_ERR_HIP, "vg_scan_topk_batch_masked: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    vg_collect_timing(c);
+    for (int i = 0; i < nq; ++i) {
+        int cnt = 0;
+        for (int j = 0; j < k; ++j) {
+            const uint64_t key = keys[(size_t)i * 64 + j];
+            if (key == VG_KEY_EMPTY) break;
+            out_keys[(size_t)i * k + cnt] = key;
+            ++cnt;
+        }
+        out_counts[i] = cnt;
+    }
+    return VG_OK;
+}
+
+// packed keys (distance image << 32 | position local to this corpus), ascending, nq x k: the form a multi-shard caller merges.
+// Slots behind out_counts[i] are not written.
+extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
+                                              int *out_counts) {
+    if (!c || !queries || !out_counts) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: NULL argument");
+    if (nq < 1) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: nq must be at least 1");
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k < 1) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: k must be at least 1");
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_batch_masked: k must be in 1..%d (masked scans use the fused list only)", VG_MAX_FUSED_K);
+    if (!out_keys) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: NULL output");
+    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: no row mask set");
+    if (c->mask_count == 0 || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
+    HIP_TRY(hipSetDevice(c->device));
+    VgShape s{};
+    scan_fn_t fn = nullptr;
+    const int NQ = mm_plan(c, metric, &s, &fn);
+    if (NQ == 0) {                                               // no multi-query form: the single masked scans, one by one
+        const size_t row_bytes = (size_t)c->dim * c->es;
+        for (int i = 0; i < nq; ++i) {
+            int rc = vg_scan_topk_masked_keys(c, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, out_keys + (size_t)i * k, &out_counts[i]);
+            if (rc != VG_OK) return rc;
+        }
+        return VG_OK;
+    }
+    return batch_masked_multi(c, metric, fn, NQ, s, queries, nq, k, out_keys, out_counts);
+}
+
+extern "C" int vg_scan_topk_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
+                                         double *out_dist, int *out_counts) {
+    if (!c || !queries || !out_counts) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: NULL argument");
+    if (nq >= 1 && k >= 1 && k <= VG_MAX_FUSED_K && (!out_rowids || !out_dist)) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: NULL output");
+    std::vector<uint64_t> keys((nq >= 1 && k >= 1 && k <= VG_MAX_FUSED_K) ? (size_t)nq * k : 1);
+    int rc = vg_scan_topk_batch_masked_keys(c, metric, queries, nq, k, keys.data(), out_counts);
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < nq; ++i)
+        for (int j = 0; j < out_counts[i]; ++j) {
+            const uint64_t key = keys[(size_t)i * k + j];
+            out_dist[(size_t)i * k + j] = (double)vg_key_distance(key);
+            out_rowids[(size_t)i * k + j] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
+        }
+    return VG_OK;
+}

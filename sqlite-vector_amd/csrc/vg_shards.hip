@@ -1034,6 +1034,35 @@ extern "C" int vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *
     return VG_OK;
 }
 
+// the masked batch: every shard answers all nq queries over its own bits (vg_scan_topk_batch_masked_keys), then one merge per query
+extern "C" int vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
+                                                double *out_dist, int *out_counts) {
+    if (!s || !queries || !out_counts) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_masked: NULL argument");
+    if (s->S == 1) return vg_scan_topk_batch_masked(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_counts);
+    if (nq < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: nq must be at least 1");
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: k must be at least 1");
+    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_batch_masked: k must be in 1..64 (masked scans use the fused list only)");
+    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_masked: NULL output");
+    if (vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: no row mask set");
+    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
+    std::vector<int> counts((size_t)s->S * nq, 0);
+    int rc = for_each_shard(s, [&](int i) {
+        return vg_scan_topk_batch_masked_keys(s->sh[(size_t)i], metric, queries, nq, k, &keys[(size_t)i * nq * k], &counts[(size_t)i * nq]);
+    });
+    if (rc != VG_OK) return rc;
+    std::vector<uint64_t> qkeys((size_t)s->S * k);
+    std::vector<int> qcounts((size_t)s->S);
+    for (int q = 0; q < nq; ++q) {
+        for (int i = 0; i < s->S; ++i) {
+            memcpy(&qkeys[(size_t)i * k], &keys[((size_t)i * nq + q) * k], (size_t)k * sizeof(uint64_t));
+            qcounts[(size_t)i] = counts[(size_t)i * nq + q];
+        }
+        out_counts[q] = merge_lists(s, qkeys.data(), k, qcounts.data(), k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
+    }
+    return VG_OK;
+}
+
 extern "C" int vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative) {
     if (!s || !out_min || !out_max || !out_any_negative) return fail(VG_ERR_INVALID, "vg_shards_minmax: NULL argument");
     if (s->S == 1) return vg_corpus_minmax(s->sh[0], out_min, out_max, out_any_negative);

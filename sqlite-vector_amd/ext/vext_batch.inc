@@ -64,6 +64,59 @@ static void *batch_from_json(sqlite3_vtab *vt, int type, const char *json, int d
     return buf;
 }
 
+/* the `queries` argument of a batch function: a BLOB of nq * dim elements (used in place) or a JSON array of arrays (*owned:
+ * sqlite3_malloc'd).  nq = 0 with SQLITE_OK: an empty JSON array */
+static int batch_queries_arg(scan_vtab *vt, const char *fname, table_ctx *t, sqlite3_value *arg, const uint8_t **queries, void **owned, int *nq) {
+    const int dim = t->opt.v_dim;
+    const int64_t qrow = (int64_t)dim * elem_size(t->opt.v_type);
+    *owned = NULL;
+    *nq = 0;
+    if (sqlite3_value_type(arg) == SQLITE_TEXT) {
+        *owned = batch_from_json(&vt->base, t->opt.v_type, (const char *)sqlite3_value_text(arg), dim, nq);
+        if (!*owned && *nq == 0 && vt->base.zErrMsg) return SQLITE_ERROR;
+        *queries = (const uint8_t *)*owned;
+        return SQLITE_OK;
+    }
+    *queries = (const uint8_t *)sqlite3_value_blob(arg);
+    const int64_t bytes = sqlite3_value_bytes(arg);
+    if (!*queries || bytes == 0 || bytes % qrow != 0)
+        return vtab_error(&vt->base, "%s: the query batch has %lld bytes, expected a multiple of %lld (dimension %d).", fname, (long long)bytes, (long long)qrow, dim);
+    *nq = (int)(bytes / qrow);
+    return SQLITE_OK;
+}
+
+/* nq queries -> the quantized table's element type (*out: sqlite3_malloc'd nq x dim bytes, the caller frees it on every path) */
+static int batch_quantize_queries(scan_vtab *vt, const char *fname, table_ctx *t, const uint8_t *queries, int nq, uint8_t **out) {
+    const int dim = t->opt.v_dim;
+    const int64_t qrow = (int64_t)dim * elem_size(t->opt.v_type);
+    *out = (uint8_t *)sqlite3_malloc64((sqlite3_uint64)nq * dim);
+    if (!*out) return SQLITE_NOMEM;
+    for (int i = 0; i < nq; ++i)
+        if (G.quantize_query(t->opt.v_type, queries + (int64_t)i * qrow, dim, t->scale, t->offset, t->opt.q_type, *out + (int64_t)i * dim) != VG_OK)
+            return vtab_error(&vt->base, "%s: %s", fname, gpu_error());
+    return SQLITE_OK;
+}
+
+/* nq x kk results + counts -> the cursor's (query, id, distance) rows, by query number */
+static int batch_emit(scan_cursor *c, int nq, int kk, const int64_t *ids, const double *dist, const int *counts) {
+    int64_t total = 0;
+    for (int i = 0; i < nq; ++i) total += counts[i];
+    sqlite3_free(c->rowids); sqlite3_free(c->distance); sqlite3_free(c->query_no);
+    c->rowids = (int64_t *)sqlite3_malloc64((sqlite3_uint64)(total ? total : 1) * sizeof(int64_t));
+    c->distance = (double *)sqlite3_malloc64((sqlite3_uint64)(total ? total : 1) * sizeof(double));
+    c->query_no = (int *)sqlite3_malloc64((sqlite3_uint64)(total ? total : 1) * sizeof(int));
+    if (!c->rowids || !c->distance || !c->query_no) return SQLITE_NOMEM;
+    int w = 0;
+    for (int i = 0; i < nq; ++i)
+        for (int j = 0; j < counts[i]; ++j, ++w) {
+            c->rowids[w] = ids[(int64_t)i * kk + j];
+            c->distance[w] = dist[(int64_t)i * kk + j];
+            c->query_no[w] = i;
+        }
+    c->row_count = w;
+    return SQLITE_OK;
+}
+
 static int batch_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized) {
     scan_cursor *c = (scan_cursor *)cur;
     scan_vtab *vt = (scan_vtab *)cur->pVtab;
@@ -92,17 +145,8 @@ static int batch_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value
     int *counts = NULL;
     char *err = NULL;
     int nq = 0, rc = SQLITE_OK;
-    if (sqlite3_value_type(argv[2]) == SQLITE_TEXT) {
-        owned = batch_from_json(&vt->base, t->opt.v_type, (const char *)sqlite3_value_text(argv[2]), dim, &nq);
-        if (!owned && nq == 0 && vt->base.zErrMsg) return SQLITE_ERROR;
-        queries = (const uint8_t *)owned;
-    } else {
-        queries = (const uint8_t *)sqlite3_value_blob(argv[2]);
-        const int64_t bytes = sqlite3_value_bytes(argv[2]);
-        if (!queries || bytes == 0 || bytes % qrow != 0)
-            return vtab_error(&vt->base, "%s: the query batch has %lld bytes, expected a multiple of %lld (dimension %d).", fname, (long long)bytes, (long long)qrow, dim);
-        nq = (int)(bytes / qrow);
-    }
+    rc = batch_queries_arg(vt, fname, t, argv[2], &queries, &owned, &nq);
+    if (rc != SQLITE_OK) return rc;
     const int k = sqlite3_value_int(argv[3]);
     if (k == 0 || nq == 0) { rc = (k == 0) ? SQLITE_DONE : SQLITE_OK; goto out; }
     if (k < 0) { rc = vtab_error(&vt->base, "%s: k must be positive.", fname); goto out; }
@@ -118,14 +162,8 @@ static int batch_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value
         }
         if (!t->quant_preloaded || !t->quant) rc = stage_quant(vt->db, t, 0, &err);
         if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "staging failed"); goto out; }
-        qquant = (uint8_t *)sqlite3_malloc64((sqlite3_uint64)nq * dim);
-        if (!qquant) { rc = SQLITE_NOMEM; goto out; }
-        for (int i = 0; i < nq; ++i) {
-            if (G.quantize_query(t->opt.v_type, queries + (int64_t)i * qrow, dim, t->scale, t->offset, t->opt.q_type, qquant + (int64_t)i * dim) != VG_OK) {
-                rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error());
-                goto out;
-            }
-        }
+        rc = batch_quantize_queries(vt, fname, t, queries, nq, &qquant);
+        if (rc != SQLITE_OK) goto out;
         scan_queries = qquant;
         corpus = t->quant;
     } else {
@@ -157,21 +195,7 @@ static int batch_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value
             if (quantized) quant_unlock(t); else full_unlock(t);
             if (brc != VG_OK) goto out;
         }
-        int64_t total = 0;
-        for (int i = 0; i < nq; ++i) total += counts[i];
-        sqlite3_free(c->rowids); sqlite3_free(c->distance); sqlite3_free(c->query_no);
-        c->rowids = (int64_t *)sqlite3_malloc64((sqlite3_uint64)(total ? total : 1) * sizeof(int64_t));
-        c->distance = (double *)sqlite3_malloc64((sqlite3_uint64)(total ? total : 1) * sizeof(double));
-        c->query_no = (int *)sqlite3_malloc64((sqlite3_uint64)(total ? total : 1) * sizeof(int));
-        if (!c->rowids || !c->distance || !c->query_no) { rc = SQLITE_NOMEM; goto out; }
-        int w = 0;
-        for (int i = 0; i < nq; ++i)
-            for (int j = 0; j < counts[i]; ++j, ++w) {
-                c->rowids[w] = ids[(int64_t)i * kk + j];
-                c->distance[w] = dist[(int64_t)i * kk + j];
-                c->query_no[w] = i;
-            }
-        c->row_count = w;
+        rc = batch_emit(c, nq, kk, ids, dist, counts);
     }
 out:
     sqlite3_free(err);

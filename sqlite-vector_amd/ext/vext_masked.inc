@@ -7,7 +7,8 @@
  * Staging, locks, tracked changes and freshness are vector_full_scan's (stage_full / stage_quant).  The row mask is state of the
  * staged copy, and a copy may be shared by several connections (vext_shared.inc): the mask is set and the scan runs inside ONE hold
  * of full_lock / quant_lock.  An out-of-core table answers through the slab path with k = 0 and a filter + sort here: correct, not
- * fast (INTEGRATION.md).  Cursor, columns and index plan are the within functions' (vext_within.inc).
+ * fast (INTEGRATION.md).  Cursor, columns and index plan are the within functions' (vext_within.inc).  The filter argument and the
+ * out-of-core answer are helpers (masked_filter_arg, masked_ooc_topk) shared with the batch form (vext_batch_masked.inc).
  */
 static int masked_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
     int rc = sqlite3_declare_vtab(db, "CREATE TABLE x(id, distance, tbl hidden, col hidden, vector hidden, k hidden, filter hidden);");
@@ -84,6 +85,63 @@ static int masked_filter_rowids(scan_vtab *vt, const char *fname, const char *sq
     return SQLITE_OK;
 }
 
+/* the filter argument of a masked function -> the rowids it names (sqlite3_malloc'd, NULL when it names none): TEXT is one read-only
+ * SELECT (masked_filter_rowids), a BLOB holds packed little-endian int64 rowids */
+static int masked_filter_arg(scan_vtab *vt, const char *fname, sqlite3_value *arg, int64_t **out_ids, int64_t *out_n) {
+    *out_ids = NULL;
+    *out_n = 0;
+    if (sqlite3_value_type(arg) == SQLITE_TEXT) return masked_filter_rowids(vt, fname, (const char *)sqlite3_value_text(arg), out_ids, out_n);
+    const int fbytes = sqlite3_value_bytes(arg);
+    if (fbytes % 8) return vtab_error(&vt->base, "%s: a BLOB filter holds packed 64-bit rowids, its length (%d bytes) must be a multiple of 8.", fname, fbytes);
+    const int64_t n = fbytes / 8;
+    if (n > 0) {                                                                         /* (copied: alignment, and the host's byte order) */
+        const uint8_t *p = (const uint8_t *)sqlite3_value_blob(arg);
+        int64_t *ids = (int64_t *)sqlite3_malloc64((sqlite3_uint64)n * sizeof(int64_t));
+        if (!ids) return SQLITE_NOMEM;
+        for (int64_t i = 0; i < n; ++i) {
+            uint64_t v = 0;
+            for (int b = 0; b < 8; ++b) v |= (uint64_t)p[i * 8 + b] << (8 * b);
+            ids[i] = (int64_t)v;
+        }
+        *out_ids = ids;
+    }
+    *out_n = n;
+    return SQLITE_OK;
+}
+
+/* one query against a table that does not fit the device: every distance through the slab path (k = 0), filtered against the SORTED
+ * rowids, sorted by (distance, scan position) and cut to k here; out_ids / out_dist hold k slots */
+static int masked_ooc_topk(scan_vtab *vt, const char *fname, table_ctx *t, int quantized, const void *scan_query, int k,
+                           const int64_t *sorted_ids, int64_t filter_n, int64_t *out_ids, double *out_dist, int64_t *out_held) {
+    char *err = NULL;
+    float *all_dist = NULL;
+    int64_t *all_ids = NULL;
+    int got = 0;
+    int64_t n = 0;
+    *out_held = 0;
+    int rc = quantized ? ooc_scan_quant(vt->db, t, scan_query, 0, NULL, NULL, &got, &all_dist, &all_ids, &n, &err)
+                       : ooc_scan_full(vt->db, t, scan_query, 0, NULL, NULL, &got, &all_dist, &all_ids, &n, &err);
+    if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "scan failed"); goto done; }
+    within_hit *hits = (within_hit *)sqlite3_malloc64((sqlite3_uint64)(n > 0 ? n : 1) * sizeof(within_hit));
+    if (!hits) { rc = SQLITE_NOMEM; goto done; }
+    int64_t m = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(all_dist[i] < INFINITY) || filter_n == 0) continue;                        /* NaN / +Inf never enter */
+        if (!bsearch(&all_ids[i], sorted_ids, (size_t)filter_n, sizeof(int64_t), masked_i64_cmp)) continue;
+        hits[m].d = all_dist[i]; hits[m].pos = i; ++m;
+    }
+    qsort(hits, (size_t)m, sizeof(within_hit), within_hit_cmp);
+    const int64_t held = (m < k) ? m : k;
+    for (int64_t i = 0; i < held; ++i) { out_ids[i] = all_ids[hits[i].pos]; out_dist[i] = (double)hits[i].d; }
+    sqlite3_free(hits);
+    *out_held = held;
+done:
+    sqlite3_free(err);
+    sqlite3_free(all_dist);
+    sqlite3_free(all_ids);
+    return rc;
+}
+
 static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized) {
     scan_cursor *c = (scan_cursor *)cur;
     scan_vtab *vt = (scan_vtab *)cur->pVtab;
@@ -118,8 +176,6 @@ static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_valu
     int rc = SQLITE_OK;
     char *err = NULL;
     uint8_t *qquant = NULL;
-    float *all_dist = NULL;
-    int64_t *all_ids = NULL;
     int64_t *filter_owned = NULL;
     const int64_t *filter_ids = NULL;
     int64_t filter_n = 0;
@@ -141,26 +197,9 @@ static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_valu
     if (k > 64) { rc = vtab_error(&vt->base, "%s: k must not exceed 64.", fname); goto out; }
 
     /* the allowed rowids: before anything is staged - a refused filter runs nothing */
-    if (sqlite3_value_type(argv[4]) == SQLITE_TEXT) {
-        rc = masked_filter_rowids(vt, fname, (const char *)sqlite3_value_text(argv[4]), &filter_owned, &filter_n);
-        if (rc != SQLITE_OK) goto out;
-        filter_ids = filter_owned;
-    } else {
-        const int fbytes = sqlite3_value_bytes(argv[4]);
-        if (fbytes % 8) { rc = vtab_error(&vt->base, "%s: a BLOB filter holds packed 64-bit rowids, its length (%d bytes) must be a multiple of 8.", fname, fbytes); goto out; }
-        filter_n = fbytes / 8;
-        if (filter_n > 0) {                                                              /* (copied: alignment, and the host's byte order) */
-            const uint8_t *p = (const uint8_t *)sqlite3_value_blob(argv[4]);
-            filter_owned = (int64_t *)sqlite3_malloc64((sqlite3_uint64)filter_n * sizeof(int64_t));
-            if (!filter_owned) { rc = SQLITE_NOMEM; goto out; }
-            for (int64_t i = 0; i < filter_n; ++i) {
-                uint64_t v = 0;
-                for (int b = 0; b < 8; ++b) v |= (uint64_t)p[i * 8 + b] << (8 * b);
-                filter_owned[i] = (int64_t)v;
-            }
-        }
-        filter_ids = filter_owned;
-    }
+    rc = masked_filter_arg(vt, fname, argv[4], &filter_owned, &filter_n);
+    if (rc != SQLITE_OK) goto out;
+    filter_ids = filter_owned;
 
     masked_set_fn set_mask = NULL;
     masked_scan_fn scan = NULL;
@@ -195,24 +234,10 @@ static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_valu
 
     if (quantized ? t->quant_ooc : t->full_ooc) {
         /* the table does not fit the device: every distance through the slab path (k = 0), filtered, sorted and cut here */
-        int got = 0;
-        int64_t n = 0;
-        rc = quantized ? ooc_scan_quant(vt->db, t, scan_query, 0, NULL, NULL, &got, &all_dist, &all_ids, &n, &err)
-                       : ooc_scan_full(vt->db, t, scan_query, 0, NULL, NULL, &got, &all_dist, &all_ids, &n, &err);
-        if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "scan failed"); goto out; }
+        int64_t held = 0;
         if (filter_n > 1) qsort(filter_owned, (size_t)filter_n, sizeof(int64_t), masked_i64_cmp);
-        within_hit *hits = (within_hit *)sqlite3_malloc64((sqlite3_uint64)(n > 0 ? n : 1) * sizeof(within_hit));
-        if (!hits) { rc = SQLITE_NOMEM; goto out; }
-        int64_t m = 0;
-        for (int64_t i = 0; i < n; ++i) {
-            if (!(all_dist[i] < INFINITY) || filter_n == 0) continue;                    /* NaN / +Inf never enter */
-            if (!bsearch(&all_ids[i], filter_ids, (size_t)filter_n, sizeof(int64_t), masked_i64_cmp)) continue;
-            hits[m].d = all_dist[i]; hits[m].pos = i; ++m;
-        }
-        qsort(hits, (size_t)m, sizeof(within_hit), within_hit_cmp);
-        const int64_t held = (m < k) ? m : k;
-        for (int64_t i = 0; i < held; ++i) { c->rowids[i] = all_ids[hits[i].pos]; c->distance[i] = (double)hits[i].d; }
-        sqlite3_free(hits);
+        rc = masked_ooc_topk(vt, fname, t, quantized, scan_query, k, filter_ids, filter_n, c->rowids, c->distance, &held);
+        if (rc != SQLITE_OK) goto out;
         c->stream_n = held;
         goto out;
     }
@@ -235,8 +260,6 @@ out:
     sqlite3_free(err);
     sqlite3_free(owned);
     sqlite3_free(qquant);
-    sqlite3_free(all_dist);
-    sqlite3_free(all_ids);
     sqlite3_free(filter_owned);
     return rc;
 }
