@@ -166,6 +166,35 @@ int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, i
 int vg_scan_within_fetch(const vg_corpus *c, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
 int vg_scan_within_keys(const vg_corpus *c, int64_t first, int64_t n, uint64_t *out_keys);
 
+/* ---- batch range scans: nq queries (row-major nq x dim, host), a radius each - "for each of these vectors, every row within r":
+ * near-duplicate detection, similarity joins, neighbourhood queries.  out_matches / out_held are nq (either may be NULL).
+ * Query i's answer is what vg_scan_within(c, metric, q_i, radii[i], limit, ..) is contracted to return: the rows with
+ * (double)d <= radii[i]; NaN / +Inf distances never match, whatever the radius; radii[i] = +Inf means every row with a finite
+ * distance; each radius is turned into the largest float not above it; ascending (distance, scan position) whatever the handle's
+ * tie_order; limit > 0 holds the first `limit` matches PER QUERY while out_matches[i] still counts all of them.
+ * f32 / uint8 / int8 rows of a register-resident shape: 4 queries (2 where a lane holds 4 or 6 chunks of the row) share every row
+ * load of a pass (vg_scan_multi_within.h; the plan: vg_within_batch_plan, vectorgpu_diag.h), nq queries cost ceil(nq / 4) - or
+ * ceil(nq / 2) - such passes.  Queries go up in slices; the passes of a slice are enqueued back to back with one copy of the counts
+ * and one wait behind them.  A query's device region starts as a share of one fixed budget of keys (2^20 over the queries of a
+ * slice); a pass in which a query counted past its region runs ONCE more as a whole into regions of the counted sizes - passes that
+ * fit are not launched again, and a partial answer is never returned.
+ * uint8 / int8: rowids, order, distance bits and counts identical to nq vg_scan_within calls.  f32: the single scan's arithmetic per
+ * (query, row) pair, possibly under another lane decomposition (the multi-query scans' launch shape) - the single range scan's
+ * result bit for bit where the two shapes agree; elsewhere its distances up to the summation order, so a row whose distance lies
+ * within that difference of the radius may fall on either side.  f16 / bf16, long rows and every other shape without a multi-query
+ * form: nq single vg_scan_within calls whose results are copied into the per-query storage - same contract, no sharing.  Timings
+ * not measured yet.
+ * nq < 1 or a NULL c / queries / radii: VG_ERR_INVALID; any NaN radius: VG_ERR_INVALID before any launch; unknown metric:
+ * VG_ERR_INVALID - each with the counts zeroed first.  An empty corpus: every count 0 without a launch.
+ * The result stays on the handle, in host memory, per query, until the next call that scans or changes the handle (the single
+ * vg_scan_within keeps its own result apart); vg_scan_within_batch_fetch / _keys copy rows [first, first + n) of query `query` as
+ * (rowid, distance widened to double) / packed keys with positions local to this corpus; a query index or a row range outside what
+ * is held: VG_ERR_INVALID.  The handle's row mask is not read. */
+int vg_scan_within_batch(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                         int64_t *out_matches, int64_t *out_held);
+int vg_scan_within_batch_fetch(const vg_corpus *c, int query, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
+int vg_scan_within_batch_keys(const vg_corpus *c, int query, int64_t first, int64_t n, uint64_t *out_keys);
+
 /* ---- masked scans: the k nearest rows among an allowed set ("... of this tenant / this category"; no reference entry point) ----
  * A row mask is a bitmap over scan positions kept on the handle, in device memory (rows / 8 bytes): bit (p & 63) of 64-bit word
  * (p >> 6) set = the row at scan position p may be returned.  Setting it and scanning are two calls: one filter serves many queries.
@@ -283,6 +312,12 @@ int     vg_shards_scan_distances(vg_shards *s, int metric, const void *query, fl
 int     vg_shards_scan_within(vg_shards *s, int metric, const void *query, double radius, int64_t limit,
                               int64_t *out_matches, int64_t *out_held);
 int     vg_shards_scan_within_fetch(const vg_shards *s, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
+/* vg_scan_within_batch over every shard (each answers all nq queries over its own rows, same radii, same limit), merged per query by
+ * (distance, GLOBAL scan position) and cut to `limit`: the answer of one corpus holding all rows.  Same contract; the merged result
+ * stays on the shards handle until its next batch range scan. */
+int     vg_shards_scan_within_batch(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                    int64_t *out_matches, int64_t *out_held);
+int     vg_shards_scan_within_batch_fetch(const vg_shards *s, int query, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
 /* the row mask over GLOBAL scan positions (vg_corpus_set_mask_*): the bits are dealt out to the shards by the block-cyclic map of the
  * rows; vg_shards_scan_topk_masked = vg_scan_topk_masked of one corpus holding all rows (rowids, order and distance bits). */
 int     vg_shards_set_mask_bits(vg_shards *s, const uint64_t *words, int64_t n_bits);

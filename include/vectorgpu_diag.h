@@ -94,6 +94,20 @@ int vg_within_set_initial_capacity(vg_corpus *c, int64_t keys);
 int vg_within_last_launches(const vg_corpus *c);
 int vg_shards_within_set_initial_capacity(vg_shards *s, int64_t keys);
 int vg_shards_within_last_launches(const vg_shards *s);
+/* batch range scans (vg_scan_within_batch).  vg_within_batch_plan: queries per pass of the multi-query range scan (4 or 2; 0 = the
+ * fallback, one single range scan per query) and the launch shape of the kernel that runs - lanes per row, 16-byte chunks per lane
+ * (the single range scan's shape for the fallback; 64 / 0 for the long-row kernel).  Pure host logic.
+ * vg_within_batch_set_initial_capacity: keys the device region of EACH query of the next batches starts with (<= 0: the default, a
+ * share of 2^20 over the queries of a slice) - tests lower it so that small corpora overflow it.  vg_within_batch_last_launches: scan
+ * kernel launches of the last batch - its passes, plus one for every pass that overflowed and ran once more (the fallback: the sum
+ * over its single scans).  Shards: the plan is shard 0's, the setting goes to every shard, the count is the largest over the shards.
+ * Every pass takes one slot of the profiling ring. */
+int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
+int vg_within_batch_set_initial_capacity(vg_corpus *c, int64_t keys_per_query);
+int vg_within_batch_last_launches(const vg_corpus *c);
+int vg_shards_within_batch_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
+int vg_shards_within_batch_set_initial_capacity(vg_shards *s, int64_t keys_per_query);
+int vg_shards_within_batch_last_launches(const vg_shards *s);
 
 /* host-only: the same replay over n distances the caller holds (scan order); returns the count (<= k) or -1.
  * below_cap <= 0: the device path's candidate capacity. */

@@ -191,6 +191,17 @@ def _load():
         "vg_scan_topk_batch_masked_keys": (i32, [vp, i32, vp, i32, i32, vp, vp]),
         "vg_shards_scan_topk_batch_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
         "vg_batch_masked_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "vg_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
+        "vg_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
+        "vg_scan_within_batch_keys": (i32, [vp, i32, i64, i64, vp]),
+        "vg_shards_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
+        "vg_shards_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
+        "vg_within_batch_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "vg_within_batch_set_initial_capacity": (i32, [vp, i64]),
+        "vg_within_batch_last_launches": (i32, [vp]),
+        "vg_shards_within_batch_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "vg_shards_within_batch_set_initial_capacity": (i32, [vp, i64]),
+        "vg_shards_within_batch_last_launches": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -250,6 +261,48 @@ def _scan_topk_batch_masked(fn, h, metric, queries, k):
     cnt = np.zeros(max(nq, 1), dtype=np.int32)
     _check(fn(h, metric, _ptr(queries), nq, k, _ptr(ids), _ptr(dist), _ptr(cnt)))
     return ids, dist, cnt[:nq]
+
+
+def _wb_prefix(obj):
+    return "vg_shards_within_batch_" if isinstance(obj, Shards) else "vg_within_batch_"
+
+
+def within_batch_plan(corpus, metric):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_within_batch serves this corpus (or shard set) with; 0 queries
+    per pass = one single range scan per query (f16 / bf16, long rows) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(getattr(lib(), _wb_prefix(corpus) + "plan")(corpus.h, metric, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
+
+
+def set_within_batch_initial_capacity(corpus, keys_per_query):
+    """keys the device region of each query of the next scan_within_batch calls starts with (0: the default) - vectorgpu_diag.h"""
+    _check(getattr(lib(), _wb_prefix(corpus) + "set_initial_capacity")(corpus.h, int(keys_per_query)))
+
+
+def within_batch_last_launches(corpus):
+    """scan kernel launches of the last scan_within_batch: its passes, plus one per pass that overflowed and ran once more"""
+    return int(getattr(lib(), _wb_prefix(corpus) + "last_launches")(corpus.h))
+
+
+def _scan_within_batch(scan, fetch, h, metric, queries, radii, limit):
+    queries = np.ascontiguousarray(queries)
+    if queries.ndim != 2:
+        raise ValueError("scan_within_batch takes a 2-d array of queries")
+    nq = queries.shape[0]
+    radii = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, dtype=np.float64), (nq,)) if np.ndim(radii) == 0 else np.asarray(radii, dtype=np.float64).ravel())
+    if radii.size != nq:
+        raise ValueError("scan_within_batch: %d radii for %d queries" % (radii.size, nq))
+    m, held = np.zeros(max(nq, 1), dtype=np.int64), np.zeros(max(nq, 1), dtype=np.int64)
+    _check(scan(h, metric, _ptr(queries), nq, _ptr(radii), 0 if limit is None else max(int(limit), 0), _ptr(m), _ptr(held)))
+    out = []
+    for i in range(nq):
+        n = 0 if (limit is not None and limit <= 0) else int(held[i])
+        ids, dist = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64)
+        if n:
+            _check(fetch(h, i, 0, n, _ptr(ids), _ptr(dist)))
+        out.append((ids, dist, int(m[i])))
+    return out
 
 
 def _set_mask(obj, prefix, rows, bits, positions, rowids):
@@ -397,6 +450,26 @@ class Corpus:
 
     def within_last_launches(self):
         return int(lib().vg_within_last_launches(self.h))
+
+    def scan_within_batch(self, metric, queries, radii, limit=None):
+        """scan_within for every row of `queries` in shared passes over the corpus, a radius each (a scalar is broadcast): a list of
+        (rowids, distances, matches) per query; `limit` is per query"""
+        return _scan_within_batch(lib().vg_scan_within_batch, lib().vg_scan_within_batch_fetch, self.h, metric, queries, radii, limit)
+
+    def within_batch_keys(self, query, n):
+        """the first n keys the last scan_within_batch holds for `query` (positions local to this corpus)"""
+        keys = np.zeros(n, dtype=np.uint64)
+        _check(lib().vg_scan_within_batch_keys(self.h, query, 0, n, _ptr(keys)))
+        return keys
+
+    def within_batch_plan(self, metric):
+        return within_batch_plan(self, metric)
+
+    def set_within_batch_initial_capacity(self, keys_per_query):
+        set_within_batch_initial_capacity(self, keys_per_query)
+
+    def within_batch_last_launches(self):
+        return within_batch_last_launches(self)
 
     def scan_topk_batch(self, metric, queries, k):
         queries = np.ascontiguousarray(queries)
@@ -724,6 +797,19 @@ class Shards:
 
     def within_last_launches(self):
         return int(lib().vg_shards_within_last_launches(self.h))
+
+    def scan_within_batch(self, metric, queries, radii, limit=None):
+        """Corpus.scan_within_batch over all shards, merged per query by (distance, global scan position)"""
+        return _scan_within_batch(lib().vg_shards_scan_within_batch, lib().vg_shards_scan_within_batch_fetch, self.h, metric, queries, radii, limit)
+
+    def within_batch_plan(self, metric):
+        return within_batch_plan(self, metric)
+
+    def set_within_batch_initial_capacity(self, keys_per_query):
+        set_within_batch_initial_capacity(self, keys_per_query)
+
+    def within_batch_last_launches(self):
+        return within_batch_last_launches(self)
 
     def scan_distances(self, metric, query):
         query = np.ascontiguousarray(query)

@@ -211,6 +211,10 @@ extern "C" void vg_corpus_destroy(vg_corpus *c) {
     if (c->d_within) hipFree(c->d_within);
     if (c->d_within_sorted) hipFree(c->d_within_sorted);
     if (c->d_within_temp) hipFree(c->d_within_temp);
+    if (c->d_wb) hipFree(c->d_wb);
+    if (c->d_wb_grow) hipFree(c->d_wb_grow);
+    if (c->d_wb_counts) hipFree(c->d_wb_counts);
+    if (c->h_wb) hipHostFree(c->h_wb);
     if (c->d_mask) hipFree(c->d_mask);
     if (c->d_ref_prefix) hipFree(c->d_ref_prefix);
     if (c->h_ref) hipHostFree(c->h_ref);
@@ -228,8 +232,7 @@ extern "C" int vg_corpus_clear(vg_corpus *c) {
     if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
     c->n_rows = 0;
     c->dist_valid_rows = 0;
-    c->within_keys.clear();
-    c->within_matches = 0;
+    vg_drop_within_results(c);
     vg_drop_mask(c);
     c->xnorm_rows = 0;
     c->i8_rows = 0;
@@ -264,7 +267,7 @@ extern "C" int vg_corpus_device_bytes(const vg_corpus *c, long long *out3) {
     out3[0] = size_of(c->d_rows);
     const void *derived[] = {c->d_rows_s8, c->d_sx, c->d_rows_tm, c->d_rows_bf, c->d_rows_q8, c->d_q8stat, c->d_rows_q8tm, c->d_q8tm_stat, c->d_rows_n4, c->d_n4stat, c->d_xnorm};
     const void *working[] = {c->d_query, c->d_cand, c->d_cand_pre, c->d_keys, c->d_dist, c->d_below, c->d_ref_prefix, c->d_sel_keys, c->d_sel_sorted,
-                             c->d_sel_temp, c->d_sel_state, c->d_within, c->d_within_sorted, c->d_within_temp, c->d_mask, c->d_stage, c->d_filter_evals, c->d_bq, c->d_bcand, c->d_bkeys, c->d_bpairs, c->d_bpcounts};
+                             c->d_sel_temp, c->d_sel_state, c->d_within, c->d_within_sorted, c->d_within_temp, c->d_wb, c->d_wb_grow, c->d_wb_counts, c->d_mask, c->d_stage, c->d_filter_evals, c->d_bq, c->d_bcand, c->d_bkeys, c->d_bpairs, c->d_bpcounts};
     out3[1] = 0; out3[2] = 0;
     for (const void *p : derived) out3[1] += size_of(p);
     for (const void *p : working) out3[2] += size_of(p);
@@ -606,8 +609,7 @@ static void invalidate_derived_from(vg_corpus *c, int64_t pos) {
     c->q8tm_rows = std::min(c->q8tm_rows, pos);
     c->n4_rows = std::min(c->n4_rows, pos);
     c->dist_valid_rows = 0;
-    c->within_keys.clear();                        // (a held range-scan result names positions of the rows as they were)
-    c->within_matches = 0;
+    vg_drop_within_results(c);                     // (a held range-scan result names positions of the rows as they were)
 }
 
 // position of `rowid`, -1 if the corpus does not hold it, -2 if its rowids are not ascending (no lookup: the caller re-stages)

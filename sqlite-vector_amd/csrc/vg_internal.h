@@ -160,6 +160,14 @@ struct vg_corpus {
     std::vector<uint64_t> within_keys;        // the held keys of the last vg_scan_within, ascending = (distance, scan position)
     int64_t within_matches = 0;
     int within_launches = 0;                  // kernel launches the last vg_scan_within took (2: the buffer overflowed once)
+    // batch range scans (vg_multi_within.hip): the key regions of one slice of queries, [count | cap keys] each at one pitch; the
+    // regions of a pass that overflowed and ran once more; the slice's counts gathered (device, then pinned host); the last result
+    unsigned long long *d_wb = nullptr, *d_wb_grow = nullptr, *d_wb_counts = nullptr, *h_wb = nullptr;
+    size_t wb_bytes = 0, wb_grow_bytes = 0;
+    int64_t wb_cap_init = 0;                  // vg_within_batch_set_initial_capacity: keys per query (0: a share of VG_WITHIN_INITIAL_CAP)
+    int wb_launches = 0;                      // scan kernel launches of the last vg_scan_within_batch
+    std::vector<std::vector<uint64_t>> wb_keys;   // per query: the held keys, ascending = (distance, scan position)
+    std::vector<int64_t> wb_matches;
     // masked scans (vg_scan_masked.hip): the row mask - bit (p & 63) of word (p >> 6) = the row at scan position p may be returned.  Read
     // by vg_scan_topk_masked only; dropped (vg_drop_mask) by every call that changes the number of rows or which row sits where
     uint64_t *d_mask = nullptr;               // ceil(n_rows / 64) words while a mask is set (mask_cap_words allocated)
@@ -226,6 +234,9 @@ struct VgRefSlots;
 void vg_ref_offer_run(VgRefSlots &slots, const float *d, int64_t n, int64_t g0);   // a run of consecutive rows offered to the slots
 int vg_ref_replay_slab(vg_corpus *c, int metric, const void *query, int k, VgRefSlots &slots, int64_t gbase, bool fresh);   // vg_reforder.hip
 
+static inline void vg_drop_within_results(vg_corpus *c) {           // (held range-scan results name positions of the rows as they were)
+    c->within_keys.clear(); c->within_matches = 0; c->wb_keys.clear(); c->wb_matches.clear();
+}
 static inline void vg_drop_mask(vg_corpus *c) { c->mask_count = -1; c->mask_host.clear(); }   // (the device words stay allocated for the next mask)
 int vg_mask_upload(vg_corpus *c);             // vg_scan_masked.hip: mask_host -> d_mask
 

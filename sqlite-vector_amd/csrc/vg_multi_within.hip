@@ -1,0 +1,355 @@
+// vg_multi_within.hip - batch range scans: every row within a radius, for many queries with a radius each (vg_scan_within_batch,
+// include/vectorgpu.h).
+//
+// Host side of the multi-query range scan (vg_scan_multi_within.h): kernel table, launch, the overflow protocol and the entry points.
+// The plan is the multi-query scan's (vg_multi_plan: 4 queries per pass with up to 3 chunks per lane, 2 with 4 or 6; f32 / uint8 /
+// int8 rows that fit the register-resident shapes).  Shapes without a multi-query form (f16 / bf16, long rows) are answered by nq
+// single range scans (vg_scan_within.hip): same contract, no sharing.
+//
+// Queries go up in slices; a slice's staging area holds, per pass, [NQ queries | NQ descriptors], and its key regions - [count | cap
+// keys] per query, one pitch - share one fixed budget of keys, so neither grows with nq.  All passes of a slice are enqueued back to
+// back; the counts are gathered by one small kernel and come back in one copy behind one wait.  A count past its capacity IS the size
+// needed: that pass - and only that pass - runs once more as a whole into regions of the counted sizes; a partial answer is never
+// returned.  The unsigned order of the keys is the contract order: up to VG_WITHIN_HOST_SORT keys of a query are sorted on the host,
+// more by the device radix sort (vg_select.hip), so a `limit` below the match count brings only `limit` keys across the host link.
+#include "vg_internal.h"
+
+#include "vg_scan_multi_within.h"
+
+typedef void (*scan_fn_t)(ScanArgs);
+
+template <int VT, int ACC, int NQ>
+static scan_fn_t pick_mw_u(int U) {
+    if constexpr (NQ == 4) {
+        switch (U) {
+            case 1: return vg_scan_multi_within_kernel<VT, ACC, 1, 4, true>;
+            case 2: return vg_scan_multi_within_kernel<VT, ACC, 2, 4, true>;
+            case 3: return vg_scan_multi_within_kernel<VT, ACC, 3, 4, true>;
+        }
+    } else {
+        switch (U) {
+            case 4: return vg_scan_multi_within_kernel<VT, ACC, 4, 2, true>;
+            case 6: return vg_scan_multi_within_kernel<VT, ACC, 6, 2, true>;
+        }
+    }
+    return nullptr;
+}
+template <int VT, int NQ>
+static scan_fn_t pick_mw_acc(int acc, int U) {
+    switch (acc) {
+        case A_L2: return pick_mw_u<VT, A_L2, NQ>(U);
+        case A_COS: return pick_mw_u<VT, A_COS, NQ>(U);
+        case A_DOT: return pick_mw_u<VT, A_DOT, NQ>(U);
+        case A_L1: return pick_mw_u<VT, A_L1, NQ>(U);
+    }
+    return nullptr;
+}
+static scan_fn_t pick_mw(int vtype, int acc, int U, int NQ) {
+    switch (vtype) {
+        case VG_TYPE_F32: return NQ == 4 ? pick_mw_acc<T_F32, 4>(acc, U) : pick_mw_acc<T_F32, 2>(acc, U);
+        case VG_TYPE_U8: return NQ == 4 ? pick_mw_acc<T_U8, 4>(acc, U) : pick_mw_acc<T_U8, 2>(acc, U);
+        case VG_TYPE_I8: return NQ == 4 ? pick_mw_acc<T_I8, 4>(acc, U) : pick_mw_acc<T_I8, 2>(acc, U);
+    }
+    return nullptr;
+}
+
+// (queries per pass, launch shape, kernel) of the multi-query range scan; 0 queries per pass: the fallback serves the shape
+static int mw_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn) {
+    const int NQ = vg_multi_plan(c, metric, s);
+    if (NQ == 0) return 0;
+    scan_fn_t f = pick_mw(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
+    if (fn) *fn = f;
+    return f ? NQ : 0;
+}
+
+extern "C" int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    VgShape s{};
+    const int NQ = mw_plan(c, metric, &s, nullptr);
+    if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single range scan's
+    if (out_queries_per_pass) *out_queries_per_pass = NQ;
+    if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
+    if (out_u) *out_u = s.long_rows ? 0 : s.U;
+    return VG_OK;
+}
+
+extern "C" int vg_select_temp_bytes(long long n, size_t *bytes);                                                  // vg_select.hip
+extern "C" int vg_select_sort_keys(const uint64_t *keys, long long n, uint64_t *keys_sorted, void *temp, size_t temp_bytes, hipStream_t stream);
+
+// the largest float not above the radius (vg_scan_within.hip: the device compares floats, `d <= r` decides what (double)d <= radius decides)
+static float radius_to_float(double radius) {
+    float r = (float)radius;
+    if ((double)r > radius) r = std::nextafterf(r, -INFINITY);
+    return r;
+}
+
+// queries go up in slices of this many (a multiple of every queries-per-pass): staging and key regions do not grow with the batch
+#define VG_WB_SLICE 256
+#define VG_WB_MIN_CAP 1024            // the floor of a query's share of VG_WITHIN_INITIAL_CAP keys
+
+// the first word of n regions `pitch` words apart: zeroed (dst == nullptr) or gathered into dst
+__global__ void vg_wb_counts_kernel(unsigned long long *regions, long long pitch, int n, unsigned long long *dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (dst) dst[i] = regions[(long long)i * pitch];
+    else regions[(long long)i * pitch] = 0ull;
+}
+
+static int ensure_dev(unsigned long long **p, size_t *have, size_t need) {
+    if (*have >= need) return VG_OK;
+    if (*p) hipFree(*p);
+    *p = nullptr; *have = 0;
+    HIP_TRY(hipMalloc(p, need));
+    *have = need;
+    return VG_OK;
+}
+
+// the sort buffers of the single range scan (the corpus' fields; vg_scan_within.hip grows them the same way)
+static int ensure_sort(vg_corpus *c, int64_t n) {
+    if (c->within_sort_cap >= n) return VG_OK;
+    if (c->d_within_sorted) hipFree(c->d_within_sorted);
+    if (c->d_within_temp) hipFree(c->d_within_temp);
+    c->d_within_sorted = nullptr; c->d_within_temp = nullptr; c->within_sort_cap = 0;
+    if (vg_select_temp_bytes(n, &c->within_temp_bytes) != 0) return vg_fail(VG_ERR_HIP, "radix sort temp-size query failed");
+    HIP_TRY(hipMalloc(&c->d_within_sorted, (size_t)n * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc(&c->d_within_temp, c->within_temp_bytes ? c->within_temp_bytes : 16));
+    c->within_sort_cap = n;
+    return VG_OK;
+}
+
+// one pass: NQ queries + their descriptors at dev_block.  Asynchronous on the corpus stream.
+static int launch_multi_within(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_block) {
+    const int rpb = VG_WAVE >> s.lpr_log2;
+    const long long nbatch = (c->n_rows + rpb - 1) / rpb;
+    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
+    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count));      // the multi-query scan's launch shape
+    blocks = std::min<long long>(blocks, VG_SEL_MAX_HEADS);
+    ScanArgs a{};
+    a.rows = c->d_rows; a.query = dev_block; a.n_rows = c->n_rows;
+    a.stride = c->stride; a.nch = c->nch; a.lpr_log2 = s.lpr_log2; a.k = 0; a.root = (metric == VG_DIST_L2) ? 1 : 0;
+    a.dim = c->dim; a.row_nn = nullptr;
+    a.store_lds_off = (int)(((size_t)NQ * c->nch * 16 + 255) / 256 * 256);     // the key queues behind the staged queries
+    const size_t smem = (size_t)a.store_lds_off + (size_t)NQ * VG_WITHIN_LDS_BYTES;
+    if (smem > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipEvent_t *evs = vg_prof_slot(c, 0);                      // one slot of the profiling ring per pass
+    if (evs) hipEventRecord(evs[0], c->stream);
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, c->stream, a);
+    if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
+    HIP_TRY(hipGetLastError());
+    ++c->wb_launches;
+    return VG_OK;
+}
+
+// `count` keys at dev_keys -> the held keys of query qi, sorted and cut to `limit`.  Small results: the copy is enqueued and *pending
+// set - the caller waits once, then sorts (finish_small); large ones are sorted on the device and only `held` keys come back (waits).
+static int collect_keys(vg_corpus *c, int qi, const unsigned long long *dev_keys, int64_t count, int64_t limit, bool *pending) {
+    std::vector<uint64_t> &dst = c->wb_keys[(size_t)qi];
+    c->wb_matches[(size_t)qi] = count;
+    if (count <= 0) { dst.clear(); return VG_OK; }
+    if (count <= VG_WITHIN_HOST_SORT) {
+        dst.resize((size_t)count);
+        HIP_TRY(hipMemcpyAsync(dst.data(), dev_keys, (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        *pending = true;
+        return VG_OK;
+    }
+    const int64_t held = (limit > 0) ? std::min<int64_t>(limit, count) : count;
+    int rc = ensure_sort(c, count);
+    if (rc != VG_OK) return rc;
+    if (vg_select_sort_keys(reinterpret_cast<const uint64_t *>(dev_keys), count, c->d_within_sorted, c->d_within_temp, c->within_temp_bytes, c->stream) != 0)
+        return vg_fail(VG_ERR_HIP, "device key sort failed: %s", hipGetErrorString(hipGetLastError()));
+    dst.resize((size_t)held);
+    HIP_TRY(hipMemcpyAsync(dst.data(), c->d_within_sorted, (size_t)held * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                  // (the sort buffers serve the next query)
+    return VG_OK;
+}
+static void finish_small(vg_corpus *c, int qi, int64_t limit) {
+    std::vector<uint64_t> &dst = c->wb_keys[(size_t)qi];
+    const int64_t count = c->wb_matches[(size_t)qi];
+    if (count <= 0 || count > VG_WITHIN_HOST_SORT) return;
+    std::sort(dst.begin(), dst.end());
+    if (limit > 0 && limit < count) dst.resize((size_t)limit);
+}
+
+// nq queries, NQ per pass
+static int batch_within_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries, int nq,
+                              const double *radii, int64_t limit) {
+    const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
+    const int slice = std::min(nq_pad, VG_WB_SLICE);
+    const size_t block_bytes = (size_t)NQ * c->stride + (size_t)NQ * sizeof(VgWithinQuery);      // one pass: [NQ queries | NQ descriptors]
+    const size_t qbytes = (size_t)(slice / NQ) * block_bytes;
+    if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
+                                HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
+    if (!c->d_wb_counts) HIP_TRY(hipMalloc(&c->d_wb_counts, (size_t)VG_WB_SLICE * sizeof(unsigned long long)));
+    if (!c->h_wb) HIP_TRY(hipHostMalloc(&c->h_wb, (size_t)(VG_WB_SLICE + 8) * sizeof(unsigned long long)));
+    // zero-padded rows of the corpus stride; a pad query is zero with no capacity and a radius nothing is below.  The whole batch stays
+    // on the host until the last wait: a slice's copy is ordered behind the passes of the slice in front of it by the stream
+    std::vector<uint8_t> hq((size_t)ngroups * block_bytes, 0);
+    const size_t row_bytes = (size_t)c->dim * c->es;
+    auto block_of = [&](int q) { return hq.data() + (size_t)(q / NQ) * block_bytes; };
+    auto desc_of = [&](int q) { return reinterpret_cast<VgWithinQuery *>(block_of(q) + (size_t)NQ * c->stride) + (q % NQ); };
+    for (int i = 0; i < nq; ++i) memcpy(block_of(i) + (size_t)(i % NQ) * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
+    uint8_t *d_stage = (uint8_t *)c->d_bq;
+
+    for (int q0 = 0; q0 < nq_pad; q0 += slice) {
+        const int nqs = std::min(slice, nq_pad - q0);
+        // a query's share of the one key budget, never more than the rows there are
+        int64_t cap = c->wb_cap_init > 0 ? c->wb_cap_init : std::max<int64_t>(VG_WB_MIN_CAP, (int64_t)VG_WITHIN_INITIAL_CAP / nqs);
+        cap = std::max<int64_t>(1, std::min<int64_t>(cap, c->n_rows));
+        const long long pitch = (long long)cap + 1;
+        int rc = ensure_dev(&c->d_wb, &c->wb_bytes, (size_t)nqs * (size_t)pitch * sizeof(unsigned long long));
+        if (rc != VG_OK) return rc;
+        for (int j = 0; j < nqs; ++j) {
+            VgWithinQuery *d = desc_of(q0 + j);
+            const bool real = q0 + j < nq;
+            d->out = c->d_wb + (long long)j * pitch;
+            d->cap = real ? (unsigned long long)cap : 0ull;
+            d->r = real ? radius_to_float(radii[q0 + j]) : -INFINITY;
+        }
+        HIP_TRY(hipMemcpyAsync(d_stage, block_of(q0), (size_t)(nqs / NQ) * block_bytes, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(vg_wb_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, c->d_wb, pitch, nqs, (unsigned long long *)nullptr);
+        for (int g = 0; g < nqs; g += NQ)
+            if ((rc = launch_multi_within(c, metric, fn, NQ, s, d_stage + (size_t)(g / NQ) * block_bytes)) != VG_OK) { hipStreamSynchronize(c->stream); return rc; }
+        hipLaunchKernelGGL(vg_wb_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, c->d_wb, pitch, nqs, c->d_wb_counts);
+        hipError_t e = hipMemcpyAsync(c->h_wb, c->d_wb_counts, (size_t)nqs * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+        hipError_t e2 = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess || e2 != hipSuccess) return vg_fail(VG_ERR_HIP, "vg_scan_within_batch: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        std::vector<int64_t> counts((size_t)nqs);
+        for (int j = 0; j < nqs; ++j) counts[(size_t)j] = (q0 + j < nq) ? (int64_t)c->h_wb[j] : 0;
+
+        // the passes that fit: their keys leave first (nothing below touches d_wb)
+        bool pending = false;
+        for (int g = 0; g < nqs; g += NQ) {
+            bool over = false;
+            for (int n = 0; n < NQ; ++n) over = over || counts[(size_t)(g + n)] > cap;
+            if (over) continue;
+            for (int n = 0; n < NQ && q0 + g + n < nq; ++n)
+                if ((rc = collect_keys(c, q0 + g + n, c->d_wb + (long long)(g + n) * pitch + 1, counts[(size_t)(g + n)], limit, &pending)) != VG_OK) return rc;
+        }
+        if (pending) HIP_TRY(hipStreamSynchronize(c->stream));
+        // a pass with a query past its capacity: once more as a whole, counts reset, every region at its counted size
+        for (int g = 0; g < nqs; g += NQ) {
+            bool over = false;
+            for (int n = 0; n < NQ; ++n) over = over || counts[(size_t)(g + n)] > cap;
+            if (!over) continue;
+            size_t words = 0;
+            for (int n = 0; n < NQ; ++n) words += (size_t)counts[(size_t)(g + n)] + 1;
+            if ((rc = ensure_dev(&c->d_wb_grow, &c->wb_grow_bytes, words * sizeof(unsigned long long))) != VG_OK) return rc;
+            size_t at = 0;
+            for (int n = 0; n < NQ; ++n) {
+                VgWithinQuery *d = desc_of(q0 + g + n);
+                d->out = c->d_wb_grow + at;
+                d->cap = (unsigned long long)counts[(size_t)(g + n)];
+                HIP_TRY(hipMemsetAsync(d->out, 0, sizeof(unsigned long long), c->stream));
+                at += (size_t)counts[(size_t)(g + n)] + 1;
+            }
+            uint8_t *d_block = d_stage + (size_t)(g / NQ) * block_bytes;
+            HIP_TRY(hipMemcpyAsync(d_block + (size_t)NQ * c->stride, desc_of(q0 + g), (size_t)NQ * sizeof(VgWithinQuery), hipMemcpyHostToDevice, c->stream));
+            if ((rc = launch_multi_within(c, metric, fn, NQ, s, d_block)) != VG_OK) { hipStreamSynchronize(c->stream); return rc; }
+            for (int n = 0; n < NQ; ++n)
+                HIP_TRY(hipMemcpyAsync(c->h_wb + VG_WB_SLICE + n, desc_of(q0 + g + n)->out, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (int n = 0; n < NQ && q0 + g + n < nq; ++n)
+                if ((int64_t)c->h_wb[VG_WB_SLICE + n] != counts[(size_t)(g + n)])
+                    return vg_fail(VG_ERR_HIP, "vg_scan_within_batch: two launches counted %lld and %lld rows for query %d", (long long)counts[(size_t)(g + n)],
+                                   (long long)c->h_wb[VG_WB_SLICE + n], q0 + g + n);
+            pending = false;
+            for (int n = 0; n < NQ && q0 + g + n < nq; ++n)
+                if ((rc = collect_keys(c, q0 + g + n, desc_of(q0 + g + n)->out + 1, counts[(size_t)(g + n)], limit, &pending)) != VG_OK) return rc;
+            if (pending) HIP_TRY(hipStreamSynchronize(c->stream));          // (d_wb_grow serves the next such pass)
+        }
+        for (int j = 0; j < nqs && q0 + j < nq; ++j) finish_small(c, q0 + j, limit);
+    }
+    vg_collect_timing(c);
+    return VG_OK;
+}
+
+extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                    int64_t *out_matches, int64_t *out_held) {
+    for (int i = 0; i < nq; ++i) { if (out_matches) out_matches[i] = 0; if (out_held) out_held[i] = 0; }      // (every error leaves the counts zeroed)
+    if (!c || !queries || !radii) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch: NULL argument");
+    c->wb_keys.clear();
+    c->wb_matches.clear();
+    c->wb_launches = 0;
+    if (nq < 1) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch: nq must be at least 1");
+    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    for (int i = 0; i < nq; ++i)
+        if (radii[i] != radii[i]) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch: radius %d is NaN", i);
+    c->wb_keys.resize((size_t)nq);
+    c->wb_matches.assign((size_t)nq, 0);
+    if (c->n_rows == 0) return VG_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    VgShape s{};
+    scan_fn_t fn = nullptr;
+    const int NQ = mw_plan(c, metric, &s, &fn);
+    int rc = VG_OK;
+    if (NQ == 0) {                                               // no multi-query form: the single range scans, one by one
+        const size_t row_bytes = (size_t)c->dim * c->es;
+        // (the single range scan keeps its own result apart: what the handle held for it is put back behind the loop)
+        std::vector<uint64_t> single_keys;
+        single_keys.swap(c->within_keys);
+        const int64_t single_matches = c->within_matches;
+        const int single_launches = c->within_launches;
+        for (int i = 0; i < nq && rc == VG_OK; ++i) {
+            int64_t m = 0, h = 0;
+            rc = vg_scan_within(c, metric, (const uint8_t *)queries + (size_t)i * row_bytes, radii[i], limit, &m, &h);
+            if (rc != VG_OK) break;
+            c->wb_keys[(size_t)i] = c->within_keys;
+            c->wb_matches[(size_t)i] = m;
+            c->wb_launches += c->within_launches;
+        }
+        c->within_keys.swap(single_keys);
+        c->within_matches = single_matches;
+        c->within_launches = single_launches;
+    } else {
+        rc = batch_within_multi(c, metric, fn, NQ, s, queries, nq, radii, limit);
+    }
+    if (rc != VG_OK) { c->wb_keys.clear(); c->wb_matches.clear(); return rc; }
+    for (int i = 0; i < nq; ++i) {
+        if (out_matches) out_matches[i] = c->wb_matches[(size_t)i];
+        if (out_held) out_held[i] = (int64_t)c->wb_keys[(size_t)i].size();
+    }
+    return VG_OK;
+}
+
+// the held keys of `query`, or nullptr (with the error set) when the query or the rows are outside what is held
+static const std::vector<uint64_t> *held_of(const vg_corpus *c, const char *who, int query, int64_t first, int64_t n) {
+    if (query < 0 || (size_t)query >= c->wb_keys.size()) {
+        vg_fail(VG_ERR_INVALID, "%s: query %d of %lld held", who, query, (long long)c->wb_keys.size());
+        return nullptr;
+    }
+    const std::vector<uint64_t> &keys = c->wb_keys[(size_t)query];
+    if (first < 0 || first + n > (int64_t)keys.size()) {
+        vg_fail(VG_ERR_INVALID, "%s: rows %lld..%lld of %lld held", who, (long long)first, (long long)(first + n), (long long)keys.size());
+        return nullptr;
+    }
+    return &keys;
+}
+
+extern "C" int vg_scan_within_batch_keys(const vg_corpus *c, int query, int64_t first, int64_t n, uint64_t *out_keys) {
+    if (!c || (n > 0 && !out_keys)) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch_keys: NULL argument");
+    const std::vector<uint64_t> *keys = held_of(c, "vg_scan_within_batch_keys", query, first, n > 0 ? n : 0);
+    if (!keys) return VG_ERR_INVALID;
+    if (n > 0) memcpy(out_keys, keys->data() + first, (size_t)n * sizeof(uint64_t));
+    return VG_OK;
+}
+
+extern "C" int vg_scan_within_batch_fetch(const vg_corpus *c, int query, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch_fetch: NULL argument");
+    const std::vector<uint64_t> *keys = held_of(c, "vg_scan_within_batch_fetch", query, first, n > 0 ? n : 0);
+    if (!keys) return VG_ERR_INVALID;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t key = (*keys)[(size_t)(first + i)];
+        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
+        if (out_dist) out_dist[i] = (double)vg_key_distance(key);
+    }
+    return VG_OK;
+}
+
+extern "C" int vg_within_batch_set_initial_capacity(vg_corpus *c, int64_t keys_per_query) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    c->wb_cap_init = keys_per_query > 0 ? keys_per_query : 0;
+    return VG_OK;
+}
+
+extern "C" int vg_within_batch_last_launches(const vg_corpus *c) { return c ? c->wb_launches : 0; }

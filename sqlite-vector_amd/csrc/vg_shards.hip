@@ -62,6 +62,7 @@ struct vg_shards {
     // the last vg_shards_scan_within (S > 1): the shards' matches merged by (distance image, GLOBAL position), kept for the fetch
     struct WithinHit { uint64_t key; int64_t gpos; int shard; };   // key: the shard's own (image << 32 | local position)
     std::vector<WithinHit> within_hits;
+    std::vector<std::vector<WithinHit>> within_batch_hits;   // the last vg_shards_scan_within_batch (S > 1): the same, per query
     int threaded = 0;                          // per-query issue + collect of the shards on those threads
 };
 
@@ -927,6 +928,76 @@ extern "C" int vg_shards_within_set_initial_capacity(vg_shards *s, int64_t keys)
 extern "C" int vg_shards_within_last_launches(const vg_shards *s) {
     int most = 0;
     if (s) for (auto *c : s->sh) most = std::max(most, vg_within_last_launches(c));
+    return most;
+}
+
+// ---- batch range scans: every shard answers all nq queries (vg_scan_within_batch: same radii, same limit), then the per-query merge
+// of vg_shards_scan_within
+extern "C" int vg_shards_scan_within_batch(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                           int64_t *out_matches, int64_t *out_held) {
+    for (int q = 0; q < nq; ++q) { if (out_matches) out_matches[q] = 0; if (out_held) out_held[q] = 0; }
+    if (!s || !queries || !radii) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch: NULL argument");
+    if (s->S == 1) return vg_scan_within_batch(s->sh[0], metric, queries, nq, radii, limit, out_matches, out_held);
+    s->within_batch_hits.clear();
+    if (nq < 1) return fail(VG_ERR_INVALID, "vg_scan_within_batch: nq must be at least 1");
+    std::vector<int64_t> matches((size_t)s->S * nq, 0), held((size_t)s->S * nq, 0);
+    int rc = for_each_shard(s, [&](int i) {
+        return vg_scan_within_batch(s->sh[(size_t)i], metric, queries, nq, radii, limit, &matches[(size_t)i * nq], &held[(size_t)i * nq]);
+    });
+    if (rc != VG_OK) return rc;
+    s->within_batch_hits.resize((size_t)nq);
+    std::vector<uint64_t> keys;
+    for (int q = 0; q < nq; ++q) {
+        std::vector<vg_shards::WithinHit> &hits = s->within_batch_hits[(size_t)q];
+        int64_t total = 0;
+        for (int i = 0; i < s->S; ++i) {
+            const int64_t h = held[(size_t)i * nq + q];
+            total += matches[(size_t)i * nq + q];
+            keys.resize((size_t)h);
+            if ((rc = vg_scan_within_batch_keys(s->sh[(size_t)i], q, 0, h, keys.data())) != VG_OK) { s->within_batch_hits.clear(); return rc; }
+            for (uint64_t key : keys) hits.push_back(vg_shards::WithinHit{key, global_of(s, i, (int64_t)vg_key_position(key)), i});
+        }
+        std::sort(hits.begin(), hits.end(), [](const vg_shards::WithinHit &a, const vg_shards::WithinHit &b) {
+            const uint32_t ia = (uint32_t)(a.key >> 32), ib = (uint32_t)(b.key >> 32);
+            return ia != ib ? ia < ib : a.gpos < b.gpos;
+        });
+        const int64_t keep = (limit > 0) ? std::min<int64_t>(limit, total) : total;
+        if ((int64_t)hits.size() > keep) hits.resize((size_t)keep);
+        if (out_matches) out_matches[q] = total;
+        if (out_held) out_held[q] = (int64_t)hits.size();
+    }
+    return VG_OK;
+}
+
+extern "C" int vg_shards_scan_within_batch_fetch(const vg_shards *s, int query, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
+    if (!s) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch_fetch: NULL argument");
+    if (s->S == 1) return vg_scan_within_batch_fetch(s->sh[0], query, first, n, out_rowids, out_dist);
+    if (query < 0 || (size_t)query >= s->within_batch_hits.size()) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch_fetch: query outside the held result");
+    const std::vector<vg_shards::WithinHit> &hits = s->within_batch_hits[(size_t)query];
+    if (n <= 0) n = 0;
+    if (first < 0 || first + n > (int64_t)hits.size()) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch_fetch: rows outside the held result");
+    for (int64_t i = 0; i < n; ++i) {
+        const vg_shards::WithinHit &h = hits[(size_t)(first + i)];
+        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)h.shard], (int64_t)vg_key_position(h.key));
+        if (out_dist) out_dist[i] = (double)vg_key_distance(h.key);
+    }
+    return VG_OK;
+}
+
+extern "C" int vg_shards_within_batch_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    if (!s) return fail(VG_ERR_INVALID, "vg_shards_within_batch_plan: NULL argument");
+    return vg_within_batch_plan(s->sh[0], metric, out_queries_per_pass, out_lpr, out_u);
+}
+
+extern "C" int vg_shards_within_batch_set_initial_capacity(vg_shards *s, int64_t keys_per_query) {
+    if (!s) return fail(VG_ERR_INVALID, "vg_shards_within_batch_set_initial_capacity: NULL argument");
+    for (auto *c : s->sh) { int rc = vg_within_batch_set_initial_capacity(c, keys_per_query); if (rc != VG_OK) return rc; }
+    return VG_OK;
+}
+
+extern "C" int vg_shards_within_batch_last_launches(const vg_shards *s) {
+    int most = 0;
+    if (s) for (auto *c : s->sh) most = std::max(most, vg_within_batch_last_launches(c));
     return most;
 }
 

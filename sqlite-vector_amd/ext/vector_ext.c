@@ -22,7 +22,7 @@
  *   - the JSON query vector is freed (the reference leaks it, :1771).
  *
  * Layout: this file holds the includes, the registration and the entry point; the rest lives in vext_*.inc by concern
- * (gpulib, context, tracking, sqlutil, convert, staging, quantize, tvf, batch, cursor, within, masked, batch_masked).  The JSON and option-string parsers
+ * (gpulib, context, tracking, sqlutil, convert, staging, quantize, tvf, batch, cursor, within, masked, batch_masked, batch_within).  The JSON and option-string parsers
  * (vext_convert.inc / vext_sqlutil.inc) implement the reference's user-visible contract - what is accepted, every error
  * text - in this repository's own structure; a differential test against the reference extension pins that contract.
  */
@@ -71,6 +71,7 @@ enum { COL_TBL = 0, COL_VECTOR = 1, COL_K = 2, COL_MEMIDX = 3, COL_ID = 4, COL_D
 #include "vext_within.inc"
 #include "vext_masked.inc"
 #include "vext_batch_masked.inc"
+#include "vext_batch_within.inc"
 
 /* ------------------------------------------------------------------------------------------------ registration */
 
@@ -193,5 +194,8 @@ int sqlite3_vector_init(sqlite3 *db, char **pzErrMsg, const sqlite3_api_routines
     /* ... for a whole batch of queries under one filter (vext_batch_masked.inc) */
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_filtered", &full_bmasked_module, ctx);
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_filtered", &quant_bmasked_module, ctx);
+    /* range scans for a whole batch of queries, a radius each (vext_batch_within.inc) */
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_within", &full_bwithin_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_within", &quant_bwithin_module, ctx);
     return rc;
 }
