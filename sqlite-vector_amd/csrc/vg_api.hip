@@ -6,10 +6,10 @@
 #include "vg_internal.h"
 
 #include "vg_scan.h"
+#include "vg_pick.h"
 
 // ------------------------------------------------------------------------------------------------ kernel selection
 
-typedef void (*scan_fn_t)(ScanArgs);
 scan_fn_t vg_pick_scan_kernel_ex(int vtype, int acc, int U);      // vg_scan_ex.hip
 
 typedef VgShape Shape;
@@ -119,71 +119,16 @@ extern "C" int vg_plan_scan_shape(int vtype, int dim, int metric, int *lanes_per
     return VG_OK;
 }
 
-template <int VT, int ACC, bool NT>
-static scan_fn_t pick_u(int U) {
-    switch (U) {
-        case 1: return vg_scan_kernel<VT, ACC, 1, NT>;
-        case 2: return vg_scan_kernel<VT, ACC, 2, NT>;
-        case 3: return vg_scan_kernel<VT, ACC, 3, NT>;
-        case 4: return vg_scan_kernel<VT, ACC, 4, NT>;
-        case 6: return vg_scan_kernel<VT, ACC, 6, NT>;
-        case 8: return vg_scan_kernel<VT, ACC, 8, NT>;
-    }
-    return nullptr;
-}
-
-template <int VT, bool NT>
-static scan_fn_t pick_acc(int acc, int U) {
-    switch (acc) {
-        case A_L2: return pick_u<VT, A_L2, NT>(U);
-        case A_COS: return pick_u<VT, A_COS, NT>(U);
-        case A_DOT: return pick_u<VT, A_DOT, NT>(U);
-        case A_L1: return pick_u<VT, A_L1, NT>(U);
-        case A_COSN:
-            if constexpr (VT == T_F16 || VT == T_BF16) return pick_u<VT, A_COSN, NT>(U);
-            return nullptr;
-    }
-    return nullptr;
-}
-
+// the plain kernels, one family per load policy (vg_pick.h)
 template <bool NT>
-static scan_fn_t pick_type(int vtype, int acc, int U) {
-    switch (vtype) {
-        case VG_TYPE_F32: return pick_acc<T_F32, NT>(acc, U);
-        case VG_TYPE_U8: return pick_acc<T_U8, NT>(acc, U);
-        case VG_TYPE_I8: return pick_acc<T_I8, NT>(acc, U);
-        case VG_TYPE_F16: return pick_acc<T_F16, NT>(acc, U);
-        case VG_TYPE_BF16: return pick_acc<T_BF16, NT>(acc, U);
-    }
-    return nullptr;
-}
-
-template <int VT, bool NT>
-static scan_fn_t pick_long_acc(int acc) {
-    switch (acc) {
-        case A_L2: return vg_scan_long_kernel<VT, A_L2, NT>;
-        case A_COS: return vg_scan_long_kernel<VT, A_COS, NT>;
-        case A_DOT: return vg_scan_long_kernel<VT, A_DOT, NT>;
-        case A_L1: return vg_scan_long_kernel<VT, A_L1, NT>;
-    }
-    return nullptr;
-}
-
-template <bool NT>
-static scan_fn_t pick_long_type(int vtype, int acc) {
-    switch (vtype) {
-        case VG_TYPE_F32: return pick_long_acc<T_F32, NT>(acc);
-        case VG_TYPE_U8: return pick_long_acc<T_U8, NT>(acc);
-        case VG_TYPE_I8: return pick_long_acc<T_I8, NT>(acc);
-        case VG_TYPE_F16: return pick_long_acc<T_F16, NT>(acc);
-        case VG_TYPE_BF16: return pick_long_acc<T_BF16, NT>(acc);
-    }
-    return nullptr;
-}
+struct PlainFamily {
+    static const bool has_long = true;
+    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, NT>; }
+    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, NT>; }
+};
 
 static scan_fn_t pick_kernel(int vtype, int acc, const Shape &s, bool nt) {
-    if (s.long_rows) return nt ? pick_long_type<true>(vtype, acc) : pick_long_type<false>(vtype, acc);
-    return nt ? pick_type<true>(vtype, acc, s.U) : pick_type<false>(vtype, acc, s.U);
+    return nt ? vg_pick_scan<PlainFamily<true>>(vtype, acc, s.U, s.long_rows) : vg_pick_scan<PlainFamily<false>>(vtype, acc, s.U, s.long_rows);
 }
 
 // stream with non-temporal loads once the corpus cannot live in the 256 MiB Infinity Cache anyway
@@ -222,12 +167,24 @@ static const char *acc_tag(int a) {
 }
 
 
+// f16 / bf16 cosine: the row norms come from a cached vector (computed once per appended row) instead of being re-accumulated
+// in f64 on every scan - the f64 chain is what bounds these kernels, not HBM.  Not for long rows (no A_COSN long-row kernel).
+static bool half_cosine_cached(const vg_corpus *c, int acc, const Shape &s) {
+    return acc == A_COS && (c->vtype == VG_TYPE_F16 || c->vtype == VG_TYPE_BF16) && !s.long_rows && vg_sw(SW_VG_HALF_COSN, 1);
+}
+int vg_half_cosine_acc(vg_corpus *c, const VgShape &s, int *acc) {
+    if (!half_cosine_cached(c, *acc, s)) return VG_OK;
+    int rc = vg_ensure_row_norms(c);
+    if (rc == VG_OK) *acc = A_COSN;
+    return rc;
+}
+
 extern "C" const char *vg_scan_kernel_name(vg_corpus *c, int metric) {
     if (!c) return "";
     Shape s;
     int acc = vg_metric_to_acc(metric);
     if (acc < 0 || !choose_shape(c->nch, c->vtype, acc, &s)) return "";
-    if (acc == A_COS && (c->vtype == VG_TYPE_F16 || c->vtype == VG_TYPE_BF16) && !s.long_rows && vg_sw(SW_VG_HALF_COSN, 1)) acc = A_COSN;
+    if (half_cosine_cached(c, acc, s)) acc = A_COSN;
     if (!s.long_rows && vg_scan_filter_name(c, metric, c->kernel_name, sizeof(c->kernel_name))) return c->kernel_name;
     snprintf(c->kernel_name, sizeof(c->kernel_name), "scan%s_%s_%s_u%d_lpr%d%s", s.long_rows ? "_long" : "",
              type_tag(c->vtype), acc_tag(acc), s.U, 1 << s.lpr_log2, use_nt_loads(c, c->n_rows) ? "_nt" : "");
@@ -274,19 +231,57 @@ int vg_plain_scan_shape(const vg_corpus *c, int metric, VgShape *out) {
     choose_shape(c->nch, c->vtype, vg_metric_to_acc(metric), out);
     return 0;
 }
-// workgroups of a top-k launch of the plain kernel over n_rows rows (shared with the masked scan, vg_scan_masked.hip)
+// ---- workgroups of a scan launch over n_rows rows.  Geometry is behaviour: the three formulas differ on purpose and stay apart.
+// batches of VG_WAVE >> lpr_log2 rows, one per wavefront and step: as many workgroups as have a batch each, at most per_cu on every CU
+static long long blocks_for(const vg_corpus *c, int64_t n_rows, const VgShape &s, int per_cu) {
+    const int rpb = VG_WAVE >> s.lpr_log2;
+    const long long nbatch = (n_rows + rpb - 1) / rpb;
+    const long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
+    return std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count * per_cu));
+}
+// 16-wave workgroups: one per CU is what ~96 VGPRs admit (5 waves/SIMD); a second one only queues behind it
+static int blocks_per_cu() { return std::max(1, std::min(8, vg_sw(SW_VG_BLOCKS_PER_CU, 1))); }
+// top-k launches of the plain, EX and masked kernels: every workgroup leaves a list for the one-workgroup merge
 long long vg_plain_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s) {
     const int rpb = VG_WAVE >> s.lpr_log2;
     const long long nbatch = (n_rows + rpb - 1) / rpb;
-    // 16-wave workgroups: one per CU is what ~96 VGPRs admit (5 waves/SIMD); a second one only queues behind it
-    const int bpc = std::max(1, std::min(8, vg_sw(SW_VG_BLOCKS_PER_CU, 1)));
-    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
-    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count * bpc));
-    blocks = std::min<long long>(blocks, VG_SEL_MAX_HEADS);          // the final rank-select handles <= 256 lists
+    long long blocks = std::min<long long>(blocks_for(c, n_rows, s, blocks_per_cu()), VG_SEL_MAX_HEADS);   // the final rank-select handles <= 256 lists
     // small corpora: at least two batches per wavefront - the merge kernel's time grows with the number of per-CU lists (6.6 us for
     // 32, 14 us for 256) and is most of a 10k-row query; round 3's wider shapes halved the rows per batch, i.e. doubled the lists
-    blocks = std::min<long long>(blocks, std::max<long long>(32, nbatch / (2 * VG_WAVES_PER_BLOCK)));
-    return blocks;
+    return std::min<long long>(blocks, std::max<long long>(32, nbatch / (2 * VG_WAVES_PER_BLOCK)));
+}
+// the single range scan: keys go to one buffer, there are no lists and no merge - neither the cap of 256 nor the small-corpus one
+long long vg_within_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s) { return blocks_for(c, n_rows, s, blocks_per_cu()); }
+// the multi-query scans (top-k, masked, range) and the filter scans: one workgroup per CU whatever SW_VG_BLOCKS_PER_CU says, <= 256 lists
+long long vg_percu_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s) {
+    return std::min<long long>(blocks_for(c, n_rows, s, 1), VG_SEL_MAX_HEADS);
+}
+
+// ---- the rest of the launch preamble the scan variants share
+ScanArgs vg_scan_args(const vg_corpus *c, int metric, int acc, const VgShape &s, const uint8_t *dev_query, int k, int64_t n_rows) {
+    ScanArgs a{};
+    a.rows = c->d_rows;
+    a.query = dev_query;
+    a.n_rows = n_rows >= 0 ? n_rows : c->n_rows;
+    a.stride = c->stride;
+    a.nch = c->nch;
+    a.lpr_log2 = s.lpr_log2;
+    a.k = k;
+    a.root = (metric == VG_DIST_L2) ? 1 : 0;
+    a.dim = c->dim;
+    a.row_nn = (acc == A_COSN) ? c->d_xnorm : nullptr;
+    return a;
+}
+size_t vg_query_lds_bytes(const vg_corpus *c, const VgShape &s) {
+    if (!s.long_rows) return (size_t)c->nch * 16;
+    const size_t slice = (size_t)VG_WAVE * VG_LONG_U;               // the long kernel pads the query to whole slices
+    return ((c->nch + slice - 1) / slice) * slice * 16;
+}
+int vg_launch_scan_kernel(scan_fn_t fn, long long blocks, size_t smem, hipStream_t stream, const ScanArgs &a) {
+    if (smem > 64 * 1024)          // very long rows: the query alone needs more than the default dynamic-LDS window
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, stream, a);
+    return VG_OK;
 }
 
 // Launch the scan (+ merge in top-k mode) on `stream`.  dev_query holds nch*16 zero-padded bytes.
@@ -306,17 +301,12 @@ static int launch_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int k
         int rcf = vg_launch_scan_filter(c, metric, dev_query, k, dev_out_keys, stream, plan.ref_emit, plan.final_out);
         if (rcf != -1) return rcf;
     }
-    // f16 / bf16 cosine: the row norms come from a cached vector (computed once per appended row) instead of being
-    // re-accumulated in f64 on every scan - the f64 chain is what bounds these kernels, not HBM
-    if (acc == A_COS && (c->vtype == VG_TYPE_F16 || c->vtype == VG_TYPE_BF16) && !s.long_rows && vg_sw(SW_VG_HALF_COSN, 1)) {
-        int rcn = vg_ensure_row_norms(c);
-        if (rcn != VG_OK) return rcn;
-        acc = A_COSN;
-        if (stream != c->stream) {                       // the norm pass ran on the corpus stream
-            if (!c->norm_ev) HIP_TRY(hipEventCreateWithFlags(&c->norm_ev, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(c->norm_ev, c->stream));
-            HIP_TRY(hipStreamWaitEvent(stream, c->norm_ev, 0));
-        }
+    int rcn = vg_half_cosine_acc(c, s, &acc);
+    if (rcn != VG_OK) return rcn;
+    if (acc == A_COSN && stream != c->stream) {              // the norm pass ran on the corpus stream
+        if (!c->norm_ev) HIP_TRY(hipEventCreateWithFlags(&c->norm_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->norm_ev, c->stream));
+        HIP_TRY(hipStreamWaitEvent(stream, c->norm_ev, 0));
     }
     // tie_order = reference: the prefix pass (this kernel over the first P rows: top-k + store) runs in front of an emitting scan; its
     // k-th best is every list's start threshold and the line below which an accepted row is emitted.  Both are EX kernels (vg_scan_ex.hip).
@@ -337,33 +327,13 @@ static int launch_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int k
 
     const long long blocks = vg_plain_scan_blocks(c, n_rows, s);
 
-    ScanArgs a{};
-    a.rows = c->d_rows;
-    a.query = dev_query;
+    ScanArgs a = vg_scan_args(c, metric, acc, s, dev_query, k, n_rows);
     a.cand = plan.lists_out ? plan.lists_out : c->d_cand;
     a.out_dist = dev_out_dist;
-    a.n_rows = n_rows;
-    a.stride = c->stride;
-    a.nch = c->nch;
-    a.lpr_log2 = s.lpr_log2;
-    a.k = k;
-    a.root = (metric == VG_DIST_L2) ? 1 : 0;
-    a.dim = c->dim;
-    a.row_nn = (acc == A_COSN) ? c->d_xnorm : nullptr;
-    a.init_keys = nullptr;
-    a.emit = nullptr;
-    a.emit_cap = 0;
-    a.emit_reset = emit_reset;
     a.order = scan_order_for(c, n_rows);
-    if (prefix_pass) a.out_dist = store_prefix;            // top-k + store (EX kernel, k > 0)
-    else a.emit_reset = nullptr;
-    size_t qbytes = (size_t)c->nch * 16;
-    if (s.long_rows) {
-        const size_t slice = (size_t)VG_WAVE * VG_LONG_U;               // the long kernel pads the query to whole slices
-        qbytes = ((c->nch + slice - 1) / slice) * slice * 16;
-    }
+    if (prefix_pass) { a.out_dist = store_prefix; a.emit_reset = emit_reset; }      // top-k + store (EX kernel, k > 0)
+    const size_t qbytes = vg_query_lds_bytes(c, s);
     size_t smem = std::max<size_t>(qbytes, (size_t)VG_PUBLISH_LDS_BYTES);
-    a.store_lds_off = 0;
     if (dev_out_dist && !s.long_rows) {             // store mode: a staging area per wavefront behind the query
         a.store_lds_off = (int)((qbytes + 255) / 256 * 256);
         smem = std::max<size_t>(smem, (size_t)a.store_lds_off + (size_t)VG_WAVES_PER_BLOCK * VG_STORE_FLOATS * sizeof(float));
@@ -392,9 +362,8 @@ static int launch_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int k
         c->ref_prefix_rows = P;
         if (evs) hipEventRecord(evs[1], stream);
     }
-    if (smem > 64 * 1024)          // very long rows: the query alone needs more than the default dynamic-LDS window
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, stream, a);
+    int rcl = vg_launch_scan_kernel(fn, blocks, smem, stream, a);
+    if (rcl != VG_OK) return rcl;
     if (evs) hipEventRecord(evs[2], stream);
     if (plan.lists_out) {                                   // the caller's kernel reads the lists itself: no merge launch
         if (plan.n_lists_out) *plan.n_lists_out = (int)blocks;

@@ -482,11 +482,7 @@ int vg_launch_scan_filter(vg_corpus *c, int metric, const uint8_t *dev_query, in
     filter_fn_t fn = n4 ? (nt ? pick_n4<true>(c->vtype, mode, s.U) : pick_n4<false>(c->vtype, mode, s.U))
                         : (nt ? pick_filter<true>(c->vtype, mode, s.U, q8) : pick_filter<false>(c->vtype, mode, s.U, q8));
     if (!fn) return -1;
-    const int rpb = VG_WAVE >> s.lpr_log2;
-    const long long nbatch = (scan_rows + rpb - 1) / rpb;
-    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
-    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count));
-    blocks = std::min<long long>(blocks, VG_SEL_MAX_HEADS);
+    const long long blocks = vg_percu_scan_blocks(c, scan_rows, s);
     FilterScanArgs a{};
     a.shadow = n4 ? c->d_rows_n4 : (q8 ? c->d_rows_q8 : (f32 ? c->d_rows_bf : c->d_rows));
     a.q8stat = reinterpret_cast<const float2 *>(n4 ? c->d_n4stat : c->d_q8stat); a.rows = c->d_rows; a.query = dev_query; a.row_norm = c->d_xnorm; a.cand = c->d_cand;

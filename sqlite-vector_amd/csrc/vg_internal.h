@@ -234,6 +234,15 @@ struct VgRefSlots;
 void vg_ref_offer_run(VgRefSlots &slots, const float *d, int64_t n, int64_t g0);   // a run of consecutive rows offered to the slots
 int vg_ref_replay_slab(vg_corpus *c, int metric, const void *query, int k, VgRefSlots &slots, int64_t gbase, bool fresh);   // vg_reforder.hip
 
+// a (position << 32 | float bits) pair of the candidate streams (ScanArgs.emit, vg_resident_distances_below)
+static inline float vg_pair_distance(unsigned long long pair) {
+    const uint32_t bits = (uint32_t)pair;
+    float d;
+    memcpy(&d, &bits, 4);
+    return d;
+}
+static inline int64_t vg_pair_position(unsigned long long pair) { return (int64_t)(pair >> 32); }
+
 static inline void vg_drop_within_results(vg_corpus *c) {           // (held range-scan results name positions of the rows as they were)
     c->within_keys.clear(); c->within_matches = 0; c->wb_keys.clear(); c->wb_matches.clear();
 }
@@ -263,7 +272,30 @@ int vg_launch_plain_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int
 int vg_launch_merge_one(const uint64_t *dev_cand, int nlists, int k, uint64_t *dev_out_keys, hipStream_t stream,
                         const unsigned long long *mirror_src = nullptr, unsigned long long *mirror_dst = nullptr);
 int vg_plain_scan_shape(const vg_corpus *c, int metric, VgShape *out);   // vg_api.hip: launch shape of the plain kernel
-long long vg_plain_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s);   // vg_api.hip: workgroups of its top-k launch
+// ---- what the launchers of the scan variants share (vg_api.hip; the kernel tables are vg_pick.h)
+struct ScanArgs;                                                    // vg_device.h
+typedef void (*scan_fn_t)(ScanArgs);
+// workgroups of a launch over n_rows rows: the three formulas, side by side in vg_api.hip
+long long vg_plain_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s);    // top-k scans that end in the one-workgroup merge
+long long vg_within_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s);   // the single range scan: no lists, no merge
+long long vg_percu_scan_blocks(const vg_corpus *c, int64_t n_rows, const VgShape &s);    // multi-query and filter scans: one per CU
+// *acc = A_COSN where the plain scan reads cached row norms (f16 / bf16 cosine), the norms made sure of on the corpus stream
+int vg_half_cosine_acc(vg_corpus *c, const VgShape &s, int *acc);
+// the fields every scan kernel reads, everything else zero; n_rows < 0: the whole corpus
+ScanArgs vg_scan_args(const vg_corpus *c, int metric, int acc, const VgShape &s, const uint8_t *dev_query, int k, int64_t n_rows = -1);
+size_t vg_query_lds_bytes(const vg_corpus *c, const VgShape &s);   // the staged query in LDS (long rows: padded to whole slices)
+// the launch itself (VG_BLOCK threads), behind the dynamic-LDS attribute step a window above 64 KiB needs; enqueue only
+int vg_launch_scan_kernel(scan_fn_t fn, long long blocks, size_t smem, hipStream_t stream, const ScanArgs &a);
+// ---- range-scan results (vg_scan_within.hip), shared by the single and the batch form
+float vg_within_radius(double radius);                              // the largest float not above the radius
+// `count` keys at dev_keys -> *dst, ascending and cut to `limit`.  Up to VG_WITHIN_HOST_SORT keys: the copy is only enqueued and
+// *pending set - the caller waits for the corpus stream once, then calls vg_within_finish; more: sorted on the device, waits itself
+int vg_within_collect(vg_corpus *c, const unsigned long long *dev_keys, int64_t count, int64_t limit, std::vector<uint64_t> *dst, bool *pending);
+void vg_within_finish(std::vector<uint64_t> *dst, int64_t count, int64_t limit);
+// keys / rows [first, first + n) of a held result; outside it: VG_ERR_INVALID in `who`'s name
+int vg_within_held_keys(const char *who, const std::vector<uint64_t> &held, int64_t first, int64_t n, uint64_t *out_keys);
+int vg_within_held_rows(const vg_corpus *c, const char *who, const std::vector<uint64_t> &held, int64_t first, int64_t n, int64_t *out_rowids,
+                        double *out_dist);
 int vg_launch_scan_filter(vg_corpus *c, int metric, const uint8_t *dev_query, int k, uint64_t *dev_out_keys, hipStream_t stream,
                           bool ref_emit = false, uint64_t *final_out = nullptr);   // vg_filter.hip; -1: not served
 int vg_scan_topk_enqueue_plan(vg_corpus *c, int metric, const void *query, int k, bool ref_emit);   // vg_api.hip: vg_scan_topk_enqueue with the reference-order extras

@@ -8,49 +8,17 @@
 #include "vg_internal.h"
 
 #include "vg_scan_multi_masked.h"
+#include "vg_pick.h"
 
-typedef void (*scan_fn_t)(ScanArgs);
-
-template <int VT, int ACC, int NQ>
-static scan_fn_t pick_mm_u(int U) {
-    if constexpr (NQ == 4) {
-        switch (U) {
-            case 1: return vg_scan_multi_masked_kernel<VT, ACC, 1, 4, true>;
-            case 2: return vg_scan_multi_masked_kernel<VT, ACC, 2, 4, true>;
-            case 3: return vg_scan_multi_masked_kernel<VT, ACC, 3, 4, true>;
-        }
-    } else {
-        switch (U) {
-            case 4: return vg_scan_multi_masked_kernel<VT, ACC, 4, 2, true>;
-            case 6: return vg_scan_multi_masked_kernel<VT, ACC, 6, 2, true>;
-        }
-    }
-    return nullptr;
-}
-template <int VT, int NQ>
-static scan_fn_t pick_mm_acc(int acc, int U) {
-    switch (acc) {
-        case A_L2: return pick_mm_u<VT, A_L2, NQ>(U);
-        case A_COS: return pick_mm_u<VT, A_COS, NQ>(U);
-        case A_DOT: return pick_mm_u<VT, A_DOT, NQ>(U);
-        case A_L1: return pick_mm_u<VT, A_L1, NQ>(U);
-    }
-    return nullptr;
-}
-static scan_fn_t pick_mm(int vtype, int acc, int U, int NQ) {
-    switch (vtype) {
-        case VG_TYPE_F32: return NQ == 4 ? pick_mm_acc<T_F32, 4>(acc, U) : pick_mm_acc<T_F32, 2>(acc, U);
-        case VG_TYPE_U8: return NQ == 4 ? pick_mm_acc<T_U8, 4>(acc, U) : pick_mm_acc<T_U8, 2>(acc, U);
-        case VG_TYPE_I8: return NQ == 4 ? pick_mm_acc<T_I8, 4>(acc, U) : pick_mm_acc<T_I8, 2>(acc, U);
-    }
-    return nullptr;
-}
+struct MultiMaskedFamily {
+    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_masked_kernel<VT, ACC, U, NQ, true>; }
+};
 
 // (queries per pass, launch shape, kernel) of the masked multi-query scan; 0 queries per pass: the fallback serves the shape
 static int mm_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn) {
     const int NQ = vg_multi_plan(c, metric, s);
     if (NQ == 0) return 0;
-    scan_fn_t f = pick_mm(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
+    scan_fn_t f = vg_pick_multi<MultiMaskedFamily>(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
     if (fn) *fn = f;
     return f ? NQ : 0;
 }
@@ -71,23 +39,17 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
 // NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on the corpus stream.
 static int launch_multi_masked(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_queries, int k,
                                uint64_t *dev_cand, uint64_t *dev_out_keys) {
-    const int rpb = VG_WAVE >> s.lpr_log2;
-    const long long nbatch = (c->n_rows + rpb - 1) / rpb;
-    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
-    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count));
-    blocks = std::min<long long>(blocks, VG_SEL_MAX_HEADS);
-    ScanArgs a{};
-    a.rows = c->d_rows; a.query = dev_queries; a.cand = dev_cand; a.out_dist = nullptr; a.n_rows = c->n_rows;
-    a.stride = c->stride; a.nch = c->nch; a.lpr_log2 = s.lpr_log2; a.k = k; a.root = (metric == VG_DIST_L2) ? 1 : 0;
-    a.dim = c->dim; a.row_nn = nullptr; a.store_lds_off = 0;
+    const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);
+    ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_queries, k);
+    a.cand = dev_cand;
     a.mask = c->d_mask;
     const size_t smem = std::max<size_t>((size_t)NQ * c->nch * 16, (size_t)VG_PUBLISH_LDS_BYTES);
-    if (smem > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);          // one slot of the profiling ring per pass
     if (evs) hipEventRecord(evs[0], c->stream);
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, c->stream, a);
+    int rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a);
+    if (rc != VG_OK) return rc;
     if (evs) hipEventRecord(evs[2], c->stream);
-    int rc = vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
+    rc = vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
     if (rc != 0) return vg_fail(VG_ERR_HIP, "vg_scan_topk_batch_masked: merge launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipGetLastError());

@@ -10,54 +10,22 @@
 // keys] per query, one pitch - share one fixed budget of keys, so neither grows with nq.  All passes of a slice are enqueued back to
 // back; the counts are gathered by one small kernel and come back in one copy behind one wait.  A count past its capacity IS the size
 // needed: that pass - and only that pass - runs once more as a whole into regions of the counted sizes; a partial answer is never
-// returned.  The unsigned order of the keys is the contract order: up to VG_WITHIN_HOST_SORT keys of a query are sorted on the host,
-// more by the device radix sort (vg_select.hip), so a `limit` below the match count brings only `limit` keys across the host link.
+// returned.  From the counted keys of a query on - sorted, cut to `limit`, held, read - the result path is the single range scan's
+// (vg_scan_within.hip: vg_within_collect / _finish / _held_*); the batch's held results stay apart from the single scan's on a handle.
 #include "vg_internal.h"
 
 #include "vg_scan_multi_within.h"
+#include "vg_pick.h"
 
-typedef void (*scan_fn_t)(ScanArgs);
-
-template <int VT, int ACC, int NQ>
-static scan_fn_t pick_mw_u(int U) {
-    if constexpr (NQ == 4) {
-        switch (U) {
-            case 1: return vg_scan_multi_within_kernel<VT, ACC, 1, 4, true>;
-            case 2: return vg_scan_multi_within_kernel<VT, ACC, 2, 4, true>;
-            case 3: return vg_scan_multi_within_kernel<VT, ACC, 3, 4, true>;
-        }
-    } else {
-        switch (U) {
-            case 4: return vg_scan_multi_within_kernel<VT, ACC, 4, 2, true>;
-            case 6: return vg_scan_multi_within_kernel<VT, ACC, 6, 2, true>;
-        }
-    }
-    return nullptr;
-}
-template <int VT, int NQ>
-static scan_fn_t pick_mw_acc(int acc, int U) {
-    switch (acc) {
-        case A_L2: return pick_mw_u<VT, A_L2, NQ>(U);
-        case A_COS: return pick_mw_u<VT, A_COS, NQ>(U);
-        case A_DOT: return pick_mw_u<VT, A_DOT, NQ>(U);
-        case A_L1: return pick_mw_u<VT, A_L1, NQ>(U);
-    }
-    return nullptr;
-}
-static scan_fn_t pick_mw(int vtype, int acc, int U, int NQ) {
-    switch (vtype) {
-        case VG_TYPE_F32: return NQ == 4 ? pick_mw_acc<T_F32, 4>(acc, U) : pick_mw_acc<T_F32, 2>(acc, U);
-        case VG_TYPE_U8: return NQ == 4 ? pick_mw_acc<T_U8, 4>(acc, U) : pick_mw_acc<T_U8, 2>(acc, U);
-        case VG_TYPE_I8: return NQ == 4 ? pick_mw_acc<T_I8, 4>(acc, U) : pick_mw_acc<T_I8, 2>(acc, U);
-    }
-    return nullptr;
-}
+struct MultiWithinFamily {
+    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_within_kernel<VT, ACC, U, NQ, true>; }
+};
 
 // (queries per pass, launch shape, kernel) of the multi-query range scan; 0 queries per pass: the fallback serves the shape
 static int mw_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn) {
     const int NQ = vg_multi_plan(c, metric, s);
     if (NQ == 0) return 0;
-    scan_fn_t f = pick_mw(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
+    scan_fn_t f = vg_pick_multi<MultiWithinFamily>(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
     if (fn) *fn = f;
     return f ? NQ : 0;
 }
@@ -72,16 +40,6 @@ extern "C" int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_que
     if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
     if (out_u) *out_u = s.long_rows ? 0 : s.U;
     return VG_OK;
-}
-
-extern "C" int vg_select_temp_bytes(long long n, size_t *bytes);                                                  // vg_select.hip
-extern "C" int vg_select_sort_keys(const uint64_t *keys, long long n, uint64_t *keys_sorted, void *temp, size_t temp_bytes, hipStream_t stream);
-
-// the largest float not above the radius (vg_scan_within.hip: the device compares floats, `d <= r` decides what (double)d <= radius decides)
-static float radius_to_float(double radius) {
-    float r = (float)radius;
-    if ((double)r > radius) r = std::nextafterf(r, -INFINITY);
-    return r;
 }
 
 // queries go up in slices of this many (a multiple of every queries-per-pass): staging and key regions do not grow with the batch
@@ -105,70 +63,26 @@ static int ensure_dev(unsigned long long **p, size_t *have, size_t need) {
     return VG_OK;
 }
 
-// the sort buffers of the single range scan (the corpus' fields; vg_scan_within.hip grows them the same way)
-static int ensure_sort(vg_corpus *c, int64_t n) {
-    if (c->within_sort_cap >= n) return VG_OK;
-    if (c->d_within_sorted) hipFree(c->d_within_sorted);
-    if (c->d_within_temp) hipFree(c->d_within_temp);
-    c->d_within_sorted = nullptr; c->d_within_temp = nullptr; c->within_sort_cap = 0;
-    if (vg_select_temp_bytes(n, &c->within_temp_bytes) != 0) return vg_fail(VG_ERR_HIP, "radix sort temp-size query failed");
-    HIP_TRY(hipMalloc(&c->d_within_sorted, (size_t)n * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc(&c->d_within_temp, c->within_temp_bytes ? c->within_temp_bytes : 16));
-    c->within_sort_cap = n;
-    return VG_OK;
-}
-
 // one pass: NQ queries + their descriptors at dev_block.  Asynchronous on the corpus stream.
 static int launch_multi_within(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_block) {
-    const int rpb = VG_WAVE >> s.lpr_log2;
-    const long long nbatch = (c->n_rows + rpb - 1) / rpb;
-    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
-    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count));      // the multi-query scan's launch shape
-    blocks = std::min<long long>(blocks, VG_SEL_MAX_HEADS);
-    ScanArgs a{};
-    a.rows = c->d_rows; a.query = dev_block; a.n_rows = c->n_rows;
-    a.stride = c->stride; a.nch = c->nch; a.lpr_log2 = s.lpr_log2; a.k = 0; a.root = (metric == VG_DIST_L2) ? 1 : 0;
-    a.dim = c->dim; a.row_nn = nullptr;
+    const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);      // the multi-query scan's launch shape
+    ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_block, 0);
     a.store_lds_off = (int)(((size_t)NQ * c->nch * 16 + 255) / 256 * 256);     // the key queues behind the staged queries
     const size_t smem = (size_t)a.store_lds_off + (size_t)NQ * VG_WITHIN_LDS_BYTES;
-    if (smem > 64 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipEvent_t *evs = vg_prof_slot(c, 0);                      // one slot of the profiling ring per pass
     if (evs) hipEventRecord(evs[0], c->stream);
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, c->stream, a);
+    int rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a);
+    if (rc != VG_OK) return rc;
     if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
     HIP_TRY(hipGetLastError());
     ++c->wb_launches;
     return VG_OK;
 }
 
-// `count` keys at dev_keys -> the held keys of query qi, sorted and cut to `limit`.  Small results: the copy is enqueued and *pending
-// set - the caller waits once, then sorts (finish_small); large ones are sorted on the device and only `held` keys come back (waits).
+// `count` keys at dev_keys -> the held keys of query qi (vg_within_collect; the caller waits once for the small results of a slice)
 static int collect_keys(vg_corpus *c, int qi, const unsigned long long *dev_keys, int64_t count, int64_t limit, bool *pending) {
-    std::vector<uint64_t> &dst = c->wb_keys[(size_t)qi];
     c->wb_matches[(size_t)qi] = count;
-    if (count <= 0) { dst.clear(); return VG_OK; }
-    if (count <= VG_WITHIN_HOST_SORT) {
-        dst.resize((size_t)count);
-        HIP_TRY(hipMemcpyAsync(dst.data(), dev_keys, (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        *pending = true;
-        return VG_OK;
-    }
-    const int64_t held = (limit > 0) ? std::min<int64_t>(limit, count) : count;
-    int rc = ensure_sort(c, count);
-    if (rc != VG_OK) return rc;
-    if (vg_select_sort_keys(reinterpret_cast<const uint64_t *>(dev_keys), count, c->d_within_sorted, c->d_within_temp, c->within_temp_bytes, c->stream) != 0)
-        return vg_fail(VG_ERR_HIP, "device key sort failed: %s", hipGetErrorString(hipGetLastError()));
-    dst.resize((size_t)held);
-    HIP_TRY(hipMemcpyAsync(dst.data(), c->d_within_sorted, (size_t)held * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));                  // (the sort buffers serve the next query)
-    return VG_OK;
-}
-static void finish_small(vg_corpus *c, int qi, int64_t limit) {
-    std::vector<uint64_t> &dst = c->wb_keys[(size_t)qi];
-    const int64_t count = c->wb_matches[(size_t)qi];
-    if (count <= 0 || count > VG_WITHIN_HOST_SORT) return;
-    std::sort(dst.begin(), dst.end());
-    if (limit > 0 && limit < count) dst.resize((size_t)limit);
+    return vg_within_collect(c, dev_keys, count, limit, &c->wb_keys[(size_t)qi], pending);
 }
 
 // nq queries, NQ per pass
@@ -204,7 +118,7 @@ static int batch_within_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, co
             const bool real = q0 + j < nq;
             d->out = c->d_wb + (long long)j * pitch;
             d->cap = real ? (unsigned long long)cap : 0ull;
-            d->r = real ? radius_to_float(radii[q0 + j]) : -INFINITY;
+            d->r = real ? vg_within_radius(radii[q0 + j]) : -INFINITY;
         }
         HIP_TRY(hipMemcpyAsync(d_stage, block_of(q0), (size_t)(nqs / NQ) * block_bytes, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(vg_wb_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, c->d_wb, pitch, nqs, (unsigned long long *)nullptr);
@@ -258,7 +172,7 @@ static int batch_within_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, co
                 if ((rc = collect_keys(c, q0 + g + n, desc_of(q0 + g + n)->out + 1, counts[(size_t)(g + n)], limit, &pending)) != VG_OK) return rc;
             if (pending) HIP_TRY(hipStreamSynchronize(c->stream));          // (d_wb_grow serves the next such pass)
         }
-        for (int j = 0; j < nqs && q0 + j < nq; ++j) finish_small(c, q0 + j, limit);
+        for (int j = 0; j < nqs && q0 + j < nq; ++j) vg_within_finish(&c->wb_keys[(size_t)(q0 + j)], c->wb_matches[(size_t)(q0 + j)], limit);
     }
     vg_collect_timing(c);
     return VG_OK;
@@ -312,38 +226,23 @@ extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *querie
     return VG_OK;
 }
 
-// the held keys of `query`, or nullptr (with the error set) when the query or the rows are outside what is held
-static const std::vector<uint64_t> *held_of(const vg_corpus *c, const char *who, int query, int64_t first, int64_t n) {
-    if (query < 0 || (size_t)query >= c->wb_keys.size()) {
-        vg_fail(VG_ERR_INVALID, "%s: query %d of %lld held", who, query, (long long)c->wb_keys.size());
-        return nullptr;
-    }
-    const std::vector<uint64_t> &keys = c->wb_keys[(size_t)query];
-    if (first < 0 || first + n > (int64_t)keys.size()) {
-        vg_fail(VG_ERR_INVALID, "%s: rows %lld..%lld of %lld held", who, (long long)first, (long long)(first + n), (long long)keys.size());
-        return nullptr;
-    }
-    return &keys;
+// the held keys of `query`, or nullptr (with the error set) when there is no such query
+static const std::vector<uint64_t> *held_of(const vg_corpus *c, const char *who, int query) {
+    if (query >= 0 && (size_t)query < c->wb_keys.size()) return &c->wb_keys[(size_t)query];
+    vg_fail(VG_ERR_INVALID, "%s: query %d of %lld held", who, query, (long long)c->wb_keys.size());
+    return nullptr;
 }
 
 extern "C" int vg_scan_within_batch_keys(const vg_corpus *c, int query, int64_t first, int64_t n, uint64_t *out_keys) {
     if (!c || (n > 0 && !out_keys)) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch_keys: NULL argument");
-    const std::vector<uint64_t> *keys = held_of(c, "vg_scan_within_batch_keys", query, first, n > 0 ? n : 0);
-    if (!keys) return VG_ERR_INVALID;
-    if (n > 0) memcpy(out_keys, keys->data() + first, (size_t)n * sizeof(uint64_t));
-    return VG_OK;
+    const std::vector<uint64_t> *keys = held_of(c, "vg_scan_within_batch_keys", query);
+    return keys ? vg_within_held_keys("vg_scan_within_batch_keys", *keys, first, n, out_keys) : VG_ERR_INVALID;
 }
 
 extern "C" int vg_scan_within_batch_fetch(const vg_corpus *c, int query, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
     if (!c) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch_fetch: NULL argument");
-    const std::vector<uint64_t> *keys = held_of(c, "vg_scan_within_batch_fetch", query, first, n > 0 ? n : 0);
-    if (!keys) return VG_ERR_INVALID;
-    for (int64_t i = 0; i < n; ++i) {
-        const uint64_t key = (*keys)[(size_t)(first + i)];
-        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
-        if (out_dist) out_dist[i] = (double)vg_key_distance(key);
-    }
-    return VG_OK;
+    const std::vector<uint64_t> *keys = held_of(c, "vg_scan_within_batch_fetch", query);
+    return keys ? vg_within_held_rows(c, "vg_scan_within_batch_fetch", *keys, first, n, out_rowids, out_dist) : VG_ERR_INVALID;
 }
 
 extern "C" int vg_within_batch_set_initial_capacity(vg_corpus *c, int64_t keys_per_query) {

@@ -117,12 +117,7 @@ struct CorpusSrc {
         int rc = vg_resident_distances_below(c, g0, bound, pairs.data(), VG_BELOW_CAP, &count);
         if (rc != VG_OK) return rc;
         if (count > VG_BELOW_CAP) { *overflow = true; return VG_OK; }
-        for (int64_t i = 0; i < count; ++i) {
-            const uint32_t bits = (uint32_t)pairs[(size_t)i];
-            float d;
-            memcpy(&d, &bits, 4);
-            out.push_back(VgRefCand{(int64_t)(pairs[(size_t)i] >> 32), d});
-        }
+        for (int64_t i = 0; i < count; ++i) out.push_back(VgRefCand{vg_pair_position(pairs[(size_t)i]), vg_pair_distance(pairs[(size_t)i])});
         return VG_OK;
     }
 };
@@ -234,12 +229,8 @@ static int replay_emitted(vg_corpus *c, int k, VgRefSlots &slots, bool *overflow
     // the rows behind it, in scan order (position is the high word of a pair)
     std::sort(pairs, pairs + count);
     for (unsigned long long j = 0; j < count; ++j) {
-        const int64_t pos = (int64_t)(pairs[j] >> 32);
-        if (pos < P) continue;                              // (the main pass covers the prefix rows again)
-        const uint32_t bits = (uint32_t)pairs[j];
-        float d;
-        memcpy(&d, &bits, 4);
-        slots.offer(d, pos);
+        const int64_t pos = vg_pair_position(pairs[j]);
+        if (pos >= P) slots.offer(vg_pair_distance(pairs[j]), pos);      // (the main pass covers the prefix rows again)
     }
     return VG_OK;
 }

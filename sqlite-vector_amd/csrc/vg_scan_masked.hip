@@ -11,55 +11,13 @@
 #include "vg_internal.h"
 
 #include "vg_scan.h"
+#include "vg_pick.h"
 
-typedef void (*scan_fn_t)(ScanArgs);
-
-template <int VT, int ACC>
-static scan_fn_t pick_u(int U) {
-    switch (U) {
-        case 1: return vg_scan_kernel<VT, ACC, 1, true, false, false, true>;
-        case 2: return vg_scan_kernel<VT, ACC, 2, true, false, false, true>;
-        case 3: return vg_scan_kernel<VT, ACC, 3, true, false, false, true>;
-        case 4: return vg_scan_kernel<VT, ACC, 4, true, false, false, true>;
-        case 6: return vg_scan_kernel<VT, ACC, 6, true, false, false, true>;
-        case 8: return vg_scan_kernel<VT, ACC, 8, true, false, false, true>;
-    }
-    return nullptr;
-}
-
-template <int VT>
-static scan_fn_t pick_acc(int acc, int U, bool long_rows) {
-    if (long_rows) {
-        switch (acc) {
-            case A_L2: return vg_scan_long_kernel<VT, A_L2, true, false, true>;
-            case A_COS: return vg_scan_long_kernel<VT, A_COS, true, false, true>;
-            case A_DOT: return vg_scan_long_kernel<VT, A_DOT, true, false, true>;
-            case A_L1: return vg_scan_long_kernel<VT, A_L1, true, false, true>;
-        }
-        return nullptr;
-    }
-    switch (acc) {
-        case A_L2: return pick_u<VT, A_L2>(U);
-        case A_COS: return pick_u<VT, A_COS>(U);
-        case A_DOT: return pick_u<VT, A_DOT>(U);
-        case A_L1: return pick_u<VT, A_L1>(U);
-        case A_COSN:
-            if constexpr (VT == T_F16 || VT == T_BF16) return pick_u<VT, A_COSN>(U);
-            return nullptr;
-    }
-    return nullptr;
-}
-
-static scan_fn_t pick_masked_kernel(int vtype, int acc, const VgShape &s) {
-    switch (vtype) {
-        case VG_TYPE_F32: return pick_acc<T_F32>(acc, s.U, s.long_rows);
-        case VG_TYPE_U8: return pick_acc<T_U8>(acc, s.U, s.long_rows);
-        case VG_TYPE_I8: return pick_acc<T_I8>(acc, s.U, s.long_rows);
-        case VG_TYPE_F16: return pick_acc<T_F16>(acc, s.U, s.long_rows);
-        case VG_TYPE_BF16: return pick_acc<T_BF16>(acc, s.U, s.long_rows);
-    }
-    return nullptr;
-}
+struct MaskedFamily {
+    static const bool has_long = true;
+    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, true, false, false, true>; }
+    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, true, false, true>; }
+};
 
 // ------------------------------------------------------------------------------------------------ the mask on the handle
 
@@ -131,42 +89,20 @@ static int launch_masked(vg_corpus *c, int metric, int k) {
     int acc = vg_metric_to_acc(metric);
     VgShape s;
     vg_plain_scan_shape(c, metric, &s);
-    if (acc == A_COS && (c->vtype == VG_TYPE_F16 || c->vtype == VG_TYPE_BF16) && !s.long_rows && vg_sw(SW_VG_HALF_COSN, 1)) {
-        int rcn = vg_ensure_row_norms(c);                    // the plain scan's cached-norm cosine: the same floats
-        if (rcn != VG_OK) return rcn;
-        acc = A_COSN;
-    }
-    scan_fn_t fn = pick_masked_kernel(c->vtype, acc, s);
+    int rc = vg_half_cosine_acc(c, s, &acc);                 // the plain scan's cached-norm cosine: the same floats
+    if (rc != VG_OK) return rc;
+    scan_fn_t fn = vg_pick_scan<MaskedFamily>(c->vtype, acc, s.U, s.long_rows);
     if (!fn) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_masked: no kernel for this type / metric");
 
-    // the launch shape of the plain top-k scan (vg_api.hip: launch_scan)
-    const long long blocks = vg_plain_scan_blocks(c, c->n_rows, s);
-
-    ScanArgs a{};
-    a.rows = c->d_rows;
-    a.query = c->d_query;
+    const long long blocks = vg_plain_scan_blocks(c, c->n_rows, s);      // the launch shape of the plain top-k scan
+    ScanArgs a = vg_scan_args(c, metric, acc, s, c->d_query, k);
     a.cand = c->d_cand;
-    a.n_rows = c->n_rows;
-    a.stride = c->stride;
-    a.nch = c->nch;
-    a.lpr_log2 = s.lpr_log2;
-    a.k = k;
-    a.root = (metric == VG_DIST_L2) ? 1 : 0;
-    a.dim = c->dim;
-    a.row_nn = (acc == A_COSN) ? c->d_xnorm : nullptr;
     a.mask = c->d_mask;
-    size_t qbytes = (size_t)c->nch * 16;
-    if (s.long_rows) {
-        const size_t slice = (size_t)VG_WAVE * VG_LONG_U;
-        qbytes = ((c->nch + slice - 1) / slice) * slice * 16;
-    }
-    const size_t smem = std::max<size_t>(qbytes, (size_t)VG_PUBLISH_LDS_BYTES);
+    const size_t smem = std::max<size_t>(vg_query_lds_bytes(c, s), (size_t)VG_PUBLISH_LDS_BYTES);
 
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);
     if (evs) hipEventRecord(evs[0], c->stream);
-    if (smem > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, c->stream, a);
+    if ((rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a)) != VG_OK) return rc;
     if (evs) hipEventRecord(evs[2], c->stream);
     int rcm = vg_launch_merge_one(c->d_cand, (int)blocks, k, c->d_keys, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);

@@ -9,117 +9,115 @@
 // the counted size answers an overflow - a partial answer is never returned.  The unsigned order of the keys is the contract order
 // (distance, scan position): up to VG_WITHIN_HOST_SORT keys are sorted on the host behind the copy, more by a device radix sort
 // (vg_select.hip) so that a `limit` below the match count brings only `limit` keys across the host link.
+//
+// The result path - radius rounding, the sort's buffers, "count keys on the device -> held, sorted, cut to limit", the readers of a held
+// result - is here ONCE and serves the batch form (vg_multi_within.hip) too; each form keeps its own held result on the handle.
 #include "vg_internal.h"
 
 #include "vg_scan.h"
+#include "vg_pick.h"
 
-typedef void (*scan_fn_t)(ScanArgs);
+struct WithinFamily {
+    static const bool has_long = true;
+    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, true, false, true>; }
+    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, true, true>; }
+};
 
-template <int VT, int ACC>
-static scan_fn_t pick_u(int U) {
-    switch (U) {
-        case 1: return vg_scan_kernel<VT, ACC, 1, true, false, true>;
-        case 2: return vg_scan_kernel<VT, ACC, 2, true, false, true>;
-        case 3: return vg_scan_kernel<VT, ACC, 3, true, false, true>;
-        case 4: return vg_scan_kernel<VT, ACC, 4, true, false, true>;
-        case 6: return vg_scan_kernel<VT, ACC, 6, true, false, true>;
-        case 8: return vg_scan_kernel<VT, ACC, 8, true, false, true>;
-    }
-    return nullptr;
-}
-
-template <int VT>
-static scan_fn_t pick_acc(int acc, int U, bool long_rows) {
-    if (long_rows) {
-        switch (acc) {
-            case A_L2: return vg_scan_long_kernel<VT, A_L2, true, true>;
-            case A_COS: return vg_scan_long_kernel<VT, A_COS, true, true>;
-            case A_DOT: return vg_scan_long_kernel<VT, A_DOT, true, true>;
-            case A_L1: return vg_scan_long_kernel<VT, A_L1, true, true>;
-        }
-        return nullptr;
-    }
-    switch (acc) {
-        case A_L2: return pick_u<VT, A_L2>(U);
-        case A_COS: return pick_u<VT, A_COS>(U);
-        case A_DOT: return pick_u<VT, A_DOT>(U);
-        case A_L1: return pick_u<VT, A_L1>(U);
-        case A_COSN:
-            if constexpr (VT == T_F16 || VT == T_BF16) return pick_u<VT, A_COSN>(U);
-            return nullptr;
-    }
-    return nullptr;
-}
-
-static scan_fn_t pick_within_kernel(int vtype, int acc, const VgShape &s) {
-    switch (vtype) {
-        case VG_TYPE_F32: return pick_acc<T_F32>(acc, s.U, s.long_rows);
-        case VG_TYPE_U8: return pick_acc<T_U8>(acc, s.U, s.long_rows);
-        case VG_TYPE_I8: return pick_acc<T_I8>(acc, s.U, s.long_rows);
-        case VG_TYPE_F16: return pick_acc<T_F16>(acc, s.U, s.long_rows);
-        case VG_TYPE_BF16: return pick_acc<T_BF16>(acc, s.U, s.long_rows);
-    }
-    return nullptr;
-}
+// ------------------------------------------------------------------------------------------------ the result path
 
 extern "C" int vg_select_temp_bytes(long long n, size_t *bytes);                                                  // vg_select.hip
 extern "C" int vg_select_sort_keys(const uint64_t *keys, long long n, uint64_t *keys_sorted, void *temp, size_t temp_bytes, hipStream_t stream);
 
 // the largest float not above the radius: the device then compares floats and `d <= r` decides what (double)d <= radius decides
-static float radius_to_float(double radius) {
+float vg_within_radius(double radius) {
     float r = (float)radius;
     if ((double)r > radius) r = std::nextafterf(r, -INFINITY);
     return r;
 }
+
+static int ensure_within_sort(vg_corpus *c, int64_t n) {
+    if (c->within_sort_cap >= n) return VG_OK;
+    if (c->d_within_sorted) hipFree(c->d_within_sorted);
+    if (c->d_within_temp) hipFree(c->d_within_temp);
+    c->d_within_sorted = nullptr; c->d_within_temp = nullptr; c->within_sort_cap = 0;
+    if (vg_select_temp_bytes(n, &c->within_temp_bytes) != 0) return vg_fail(VG_ERR_HIP, "radix sort temp-size query failed");
+    HIP_TRY(hipMalloc(&c->d_within_sorted, (size_t)n * sizeof(uint64_t)));
+    HIP_TRY(hipMalloc(&c->d_within_temp, c->within_temp_bytes ? c->within_temp_bytes : 16));
+    c->within_sort_cap = n;
+    return VG_OK;
+}
+
+int vg_within_collect(vg_corpus *c, const unsigned long long *dev_keys, int64_t count, int64_t limit, std::vector<uint64_t> *dst, bool *pending) {
+    if (count <= 0) { dst->clear(); return VG_OK; }
+    if (count <= VG_WITHIN_HOST_SORT) {
+        dst->resize((size_t)count);
+        HIP_TRY(hipMemcpyAsync(dst->data(), dev_keys, (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        *pending = true;
+        return VG_OK;
+    }
+    const int64_t held = (limit > 0) ? std::min<int64_t>(limit, count) : count;
+    int rc = ensure_within_sort(c, count);
+    if (rc != VG_OK) return rc;
+    if (vg_select_sort_keys(reinterpret_cast<const uint64_t *>(dev_keys), count, c->d_within_sorted, c->d_within_temp, c->within_temp_bytes, c->stream) != 0)
+        return vg_fail(VG_ERR_HIP, "device key sort failed: %s", hipGetErrorString(hipGetLastError()));
+    dst->resize((size_t)held);
+    HIP_TRY(hipMemcpyAsync(dst->data(), c->d_within_sorted, (size_t)held * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));                  // (the sort buffers serve the next result)
+    return VG_OK;
+}
+void vg_within_finish(std::vector<uint64_t> *dst, int64_t count, int64_t limit) {
+    if (count <= 0 || count > VG_WITHIN_HOST_SORT) return;
+    std::sort(dst->begin(), dst->end());
+    if (limit > 0 && limit < count) dst->resize((size_t)limit);
+}
+
+static bool held_range(const char *who, const std::vector<uint64_t> &held, int64_t first, int64_t n) {
+    if (first >= 0 && first + n <= (int64_t)held.size()) return true;
+    vg_fail(VG_ERR_INVALID, "%s: rows %lld..%lld of %lld held", who, (long long)first, (long long)(first + n), (long long)held.size());
+    return false;
+}
+int vg_within_held_keys(const char *who, const std::vector<uint64_t> &held, int64_t first, int64_t n, uint64_t *out_keys) {
+    if (n < 0) n = 0;
+    if (!held_range(who, held, first, n)) return VG_ERR_INVALID;
+    if (n > 0) memcpy(out_keys, held.data() + first, (size_t)n * sizeof(uint64_t));
+    return VG_OK;
+}
+int vg_within_held_rows(const vg_corpus *c, const char *who, const std::vector<uint64_t> &held, int64_t first, int64_t n, int64_t *out_rowids,
+                        double *out_dist) {
+    if (n < 0) n = 0;
+    if (!held_range(who, held, first, n)) return VG_ERR_INVALID;
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t key = held[(size_t)(first + i)];
+        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
+        if (out_dist) out_dist[i] = (double)vg_key_distance(key);
+    }
+    return VG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the single range scan
 
 // one launch of the within kernel into c->d_within ([count | cap keys]); the count lands in the pinned c->h_keys[0] behind it
 static int launch_within(vg_corpus *c, int metric, float r, int64_t cap) {
     int acc = vg_metric_to_acc(metric);
     VgShape s;
     vg_plain_scan_shape(c, metric, &s);
-    if (acc == A_COS && (c->vtype == VG_TYPE_F16 || c->vtype == VG_TYPE_BF16) && !s.long_rows && vg_sw(SW_VG_HALF_COSN, 1)) {
-        int rcn = vg_ensure_row_norms(c);                    // the plain scan's cached-norm cosine: the same floats
-        if (rcn != VG_OK) return rcn;
-        acc = A_COSN;
-    }
-    scan_fn_t fn = pick_within_kernel(c->vtype, acc, s);
+    int rc = vg_half_cosine_acc(c, s, &acc);                 // the plain scan's cached-norm cosine: the same floats
+    if (rc != VG_OK) return rc;
+    scan_fn_t fn = vg_pick_scan<WithinFamily>(c->vtype, acc, s.U, s.long_rows);
     if (!fn) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_within: no kernel for this type / metric");
 
-    // the launch shape of the plain top-k scan (vg_api.hip: launch_scan)
-    const int rpb = VG_WAVE >> s.lpr_log2;
-    const long long nbatch = (c->n_rows + rpb - 1) / rpb;
-    const int bpc = std::max(1, std::min(8, vg_sw(SW_VG_BLOCKS_PER_CU, 1)));
-    long long blocks = (nbatch + VG_WAVES_PER_BLOCK - 1) / VG_WAVES_PER_BLOCK;
-    blocks = std::max<long long>(1, std::min<long long>(blocks, (long long)c->cu_count * bpc));
-
-    ScanArgs a{};
-    a.rows = c->d_rows;
-    a.query = c->d_query;
-    a.n_rows = c->n_rows;
-    a.stride = c->stride;
-    a.nch = c->nch;
-    a.lpr_log2 = s.lpr_log2;
-    a.k = 0;
-    a.root = (metric == VG_DIST_L2) ? 1 : 0;
-    a.dim = c->dim;
-    a.row_nn = (acc == A_COSN) ? c->d_xnorm : nullptr;
+    const long long blocks = vg_within_scan_blocks(c, c->n_rows, s);
+    ScanArgs a = vg_scan_args(c, metric, acc, s, c->d_query, 0);
     a.emit = c->d_within;
     a.within_r = r;
     a.within_cap = (unsigned long long)cap;
-    size_t qbytes = (size_t)c->nch * 16;
-    if (s.long_rows) {
-        const size_t slice = (size_t)VG_WAVE * VG_LONG_U;
-        qbytes = ((c->nch + slice - 1) / slice) * slice * 16;
-    }
-    a.store_lds_off = (int)((qbytes + 255) / 256 * 256);     // the wavefronts' key queues behind the query
+    a.store_lds_off = (int)((vg_query_lds_bytes(c, s) + 255) / 256 * 256);     // the wavefronts' key queues behind the query
     const size_t smem = (size_t)a.store_lds_off + VG_WITHIN_LDS_BYTES;
 
     HIP_TRY(hipMemsetAsync(c->d_within, 0, sizeof(unsigned long long), c->stream));
     hipEvent_t *evs = vg_prof_slot(c, 0);
     if (evs) hipEventRecord(evs[0], c->stream);
-    if (smem > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(VG_BLOCK), smem, c->stream, a);
+    if ((rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a)) != VG_OK) return rc;
     if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_keys, c->d_within, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -136,18 +134,6 @@ static int ensure_within_buffer(vg_corpus *c, int64_t cap) {
     return VG_OK;
 }
 
-static int ensure_within_sort(vg_corpus *c, int64_t n) {
-    if (c->within_sort_cap >= n) return VG_OK;
-    if (c->d_within_sorted) hipFree(c->d_within_sorted);
-    if (c->d_within_temp) hipFree(c->d_within_temp);
-    c->d_within_sorted = nullptr; c->d_within_temp = nullptr; c->within_sort_cap = 0;
-    if (vg_select_temp_bytes(n, &c->within_temp_bytes) != 0) return vg_fail(VG_ERR_HIP, "radix sort temp-size query failed");
-    HIP_TRY(hipMalloc(&c->d_within_sorted, (size_t)n * sizeof(uint64_t)));
-    HIP_TRY(hipMalloc(&c->d_within_temp, c->within_temp_bytes ? c->within_temp_bytes : 16));
-    c->within_sort_cap = n;
-    return VG_OK;
-}
-
 extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                               int64_t *out_held) {
     if (!c || !query) return vg_fail(VG_ERR_INVALID, "vg_scan_within: NULL argument");
@@ -161,7 +147,7 @@ extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, doubl
     if (c->n_rows == 0) return VG_OK;
     HIP_TRY(hipSetDevice(c->device));
     c->enqueued = false;                                     // (the pinned key buffer is this scan's landing zone now)
-    const float r = radius_to_float(radius);
+    const float r = vg_within_radius(radius);
     int64_t cap = c->within_cap_init > 0 ? c->within_cap_init : (int64_t)VG_WITHIN_INITIAL_CAP;
     cap = std::max<int64_t>(std::min<int64_t>(cap, c->n_rows), c->within_cap);      // (a buffer an earlier scan grew is kept)
     int rc = ensure_within_buffer(c, cap);
@@ -178,46 +164,26 @@ extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, doubl
         if ((int64_t)c->h_keys[0] != count) return vg_fail(VG_ERR_HIP, "vg_scan_within: two launches counted %lld and %lld rows", (long long)count, (long long)c->h_keys[0]);
     }
     vg_collect_timing(c);
-    const int64_t held = (limit > 0) ? std::min<int64_t>(limit, count) : count;
-    c->within_keys.resize((size_t)held);
-    if (count > 0 && count <= VG_WITHIN_HOST_SORT) {
-        std::vector<uint64_t> all((size_t)count);
-        HIP_TRY(hipMemcpy(all.data(), c->d_within + 1, (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        std::sort(all.begin(), all.end());
-        std::copy(all.begin(), all.begin() + held, c->within_keys.begin());
-    } else if (count > 0) {
-        if ((rc = ensure_within_sort(c, count)) != VG_OK) return rc;
-        if (vg_select_sort_keys(reinterpret_cast<const uint64_t *>(c->d_within + 1), count, c->d_within_sorted, c->d_within_temp, c->within_temp_bytes, c->stream) != 0)
-            return vg_fail(VG_ERR_HIP, "device key sort failed: %s", hipGetErrorString(hipGetLastError()));
-        HIP_TRY(hipMemcpyAsync(c->within_keys.data(), c->d_within_sorted, (size_t)held * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    bool pending = false;
+    if ((rc = vg_within_collect(c, c->d_within + 1, count, limit, &c->within_keys, &pending)) != VG_OK) return rc;
+    if (pending) HIP_TRY(hipStreamSynchronize(c->stream));
+    vg_within_finish(&c->within_keys, count, limit);
     c->within_matches = count;
     if (out_matches) *out_matches = count;
-    if (out_held) *out_held = held;
+    if (out_held) *out_held = (int64_t)c->within_keys.size();
     return VG_OK;
 }
 
 extern "C" int vg_scan_within_keys(const vg_corpus *c, int64_t first, int64_t n, uint64_t *out_keys) {
     if (!c || (n > 0 && !out_keys)) return vg_fail(VG_ERR_INVALID, "vg_scan_within_keys: NULL argument");
     if (n <= 0) return VG_OK;
-    if (first < 0 || first + n > (int64_t)c->within_keys.size())
-        return vg_fail(VG_ERR_INVALID, "vg_scan_within_keys: rows %lld..%lld of %lld held", (long long)first, (long long)(first + n), (long long)c->within_keys.size());
-    memcpy(out_keys, c->within_keys.data() + first, (size_t)n * sizeof(uint64_t));
-    return VG_OK;
+    return vg_within_held_keys("vg_scan_within_keys", c->within_keys, first, n, out_keys);
 }
 
 extern "C" int vg_scan_within_fetch(const vg_corpus *c, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
     if (!c) return vg_fail(VG_ERR_INVALID, "vg_scan_within_fetch: NULL argument");
     if (n <= 0) return VG_OK;
-    if (first < 0 || first + n > (int64_t)c->within_keys.size())
-        return vg_fail(VG_ERR_INVALID, "vg_scan_within_fetch: rows %lld..%lld of %lld held", (long long)first, (long long)(first + n), (long long)c->within_keys.size());
-    for (int64_t i = 0; i < n; ++i) {
-        const uint64_t key = c->within_keys[(size_t)(first + i)];
-        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
-        if (out_dist) out_dist[i] = (double)vg_key_distance(key);
-    }
-    return VG_OK;
+    return vg_within_held_rows(c, "vg_scan_within_fetch", c->within_keys, first, n, out_rowids, out_dist);
 }
 
 extern "C" int vg_within_set_initial_capacity(vg_corpus *c, int64_t keys) {

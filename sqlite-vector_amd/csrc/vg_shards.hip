@@ -501,16 +501,16 @@ struct Cand { uint32_t img; int64_t gpos; int shard; uint32_t local; };
 
 static inline bool cand_less(const Cand &a, const Cand &b) { return a.img != b.img ? a.img < b.img : a.gpos < b.gpos; }
 
-// merge per-shard ascending key lists (list i = shard i, `len` keys each, `counts[i]` valid) into the global top-k.
+// merge per-shard ascending key lists (list i = shard i at keys + i * pitch, counts[i * cpitch] keys valid) into the global top-k.
 // ref_k >= 0: the lists were taken with one more slot than asked for (tie_order = reference, see vg_scan_topk_reference): when the
 // best ref_k + 1 distances are pairwise distinct the reference's own result IS the first ref_k in ascending order and that is what
 // comes back; when they hold a tie nothing is written and -1 comes back (the caller replays the reference's slots).
-static int merge_lists(const vg_shards *s, const uint64_t *keys, int len, const int *counts, int k, int64_t *out_rowids,
+static int merge_lists(const vg_shards *s, const uint64_t *keys, size_t pitch, const int *counts, int cpitch, int k, int64_t *out_rowids,
                        double *out_dist, int ref_k = -1) {
     std::vector<Cand> all;
     for (int i = 0; i < s->S; ++i)
-        for (int j = 0; j < counts[i]; ++j) {
-            const uint64_t key = keys[(size_t)i * len + j];
+        for (int j = 0; j < counts[(size_t)i * cpitch]; ++j) {
+            const uint64_t key = keys[(size_t)i * pitch + j];
             if (key == VG_KEY_EMPTY) break;
             const uint32_t local = vg_key_position(key);
             all.push_back(Cand{(uint32_t)(key >> 32), global_of(s, i, (int64_t)local), i, local});
@@ -526,6 +526,11 @@ static int merge_lists(const vg_shards *s, const uint64_t *keys, int len, const 
         out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)all[i].shard], (int64_t)all[i].local);
     }
     return (int)take;
+}
+// the same for query q of a batch: keys [S][nq][kk], counts [S][nq]
+static int merge_query_lists(const vg_shards *s, const uint64_t *keys, const int *counts, int nq, int q, int kk, int k, int64_t *out_rowids,
+                             double *out_dist, int ref_k = -1) {
+    return merge_lists(s, keys + (size_t)q * kk, (size_t)nq * kk, counts + q, nq, k, out_rowids, out_dist, ref_k);
 }
 
 // ---- tie_order = reference over several shards: the same replay (vg_refslots.h), its stream assembled in GLOBAL scan
@@ -569,12 +574,8 @@ struct ShardsSrc {
             int rc = vg_resident_distances_below(s->sh[(size_t)i], local_from, bound, pairs.data(), kCap, &count);
             if (rc != VG_OK) return rc;
             if (count > kCap) { *overflow = true; return VG_OK; }
-            for (int64_t j = 0; j < count; ++j) {
-                const uint32_t bits = (uint32_t)pairs[(size_t)j];
-                float d;
-                memcpy(&d, &bits, 4);
-                out.push_back(VgRefCand{global_of(s, i, (int64_t)(pairs[(size_t)j] >> 32)), d});
-            }
+            for (int64_t j = 0; j < count; ++j)
+                out.push_back(VgRefCand{global_of(s, i, vg_pair_position(pairs[(size_t)j])), vg_pair_distance(pairs[(size_t)j])});
         }
         return VG_OK;
     }
@@ -636,12 +637,8 @@ static int shards_replay_emitted(vg_shards *s, int k, VgRefSlots &slots, bool *o
     for (int i = 0; i < s->S; ++i) {
         const Part &pt = parts[(size_t)i];
         for (unsigned long long j = 0; j < pt.count; ++j) {
-            const int64_t local = (int64_t)(pt.pairs[j] >> 32);
-            if (local < pt.P) continue;                        // (the main pass covers the prefix rows again)
-            const uint32_t bits = (uint32_t)pt.pairs[j];
-            float d;
-            memcpy(&d, &bits, 4);
-            cand.push_back(GCand{global_of(s, i, local), d});
+            const int64_t local = vg_pair_position(pt.pairs[j]);
+            if (local >= pt.P) cand.push_back(GCand{global_of(s, i, local), vg_pair_distance(pt.pairs[j])});   // (the main pass covers the prefix rows again)
         }
     }
     std::sort(cand.begin(), cand.end(), [](const GCand &x, const GCand &y) { return x.gpos < y.gpos; });
@@ -662,6 +659,31 @@ static int shards_replay_emitted(vg_shards *s, int k, VgRefSlots &slots, bool *o
     return VG_OK;
 }
 
+// Every shard's fused top-k scan (kk <= 64 list slots) and its 64 candidate keys on the host, S x 64.  The RCCL gather where the handle
+// asks for it and it serves (not an emitting scan: that leaves more than 64 keys behind) - a failure there leaves the host gather to
+// this query and the ones after it; host gather: every shard in flight before the first wait, or each on its own pool thread.
+static int scan_shards_topk(vg_shards *s, int metric, const void *query, int kk, bool emit, uint64_t *keys) {
+    if (!emit && s->gather_mode == 1 && rccl_ready(s)) {
+        if (rccl_scan_and_gather(s, metric, query, kk, keys) == VG_OK) return VG_OK;
+        s->rccl_failed = true;
+    }
+    int rc = VG_OK;
+    if (s->threaded) {
+        rc = pool_run(s, [&](int i) {
+            const int r = vg_scan_topk_enqueue_plan(s->sh[(size_t)i], metric, query, kk, emit);
+            return r != VG_OK ? r : vg_scan_topk_collect(s->sh[(size_t)i], &keys[(size_t)i * VG_WAVE_KEYS]);
+        });
+    } else {
+        for (int i = 0; i < s->S && rc == VG_OK; ++i) rc = vg_scan_topk_enqueue_plan(s->sh[(size_t)i], metric, query, kk, emit);
+        for (int i = 0; i < s->S; ++i) {
+            int rc2 = vg_scan_topk_collect(s->sh[(size_t)i], &keys[(size_t)i * VG_WAVE_KEYS]);
+            if (rc == VG_OK) rc = rc2;
+        }
+    }
+    if (rc == VG_OK) ++s->gather_calls[0];
+    return rc;
+}
+
 // tie_order = reference for k <= 64 over several shards, the fused form: every shard's ordinary top-k scan with one more list slot;
 // a tie among the merged k + 1 best -> the replay above.  The policy is one corpus' (vg_scan_topk_reference): scans through a filter
 // kernel always emit, plain-kernel scans only while ties are around (a first tie costs one more scan of every shard, emitting);
@@ -677,30 +699,10 @@ static int shards_scan_topk_fused(vg_shards *s, int metric, const void *query, i
     std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS);
     std::vector<int> counts((size_t)s->S, VG_WAVE_KEYS);
     for (int attempt = 0; attempt < 2; ++attempt) {
-        int rc = -1;
-        if (!emit && s->gather_mode == 1 && rccl_ready(s)) {      // (an emitting scan leaves more than 64 keys behind: host gather)
-            rc = rccl_scan_and_gather(s, metric, query, kk, keys.data());
-            if (rc != VG_OK) s->rccl_failed = true;
-        }
-        if (rc != VG_OK) {
-            rc = VG_OK;
-            if (s->threaded) {
-                rc = pool_run(s, [&](int i) {
-                    const int r = vg_scan_topk_enqueue_plan(s->sh[(size_t)i], metric, query, kk, emit);
-                    return r != VG_OK ? r : vg_scan_topk_collect(s->sh[(size_t)i], &keys[(size_t)i * VG_WAVE_KEYS]);
-                });
-            } else {
-                for (int i = 0; i < s->S && rc == VG_OK; ++i) rc = vg_scan_topk_enqueue_plan(s->sh[(size_t)i], metric, query, kk, emit);
-                for (int i = 0; i < s->S; ++i) {
-                    int rc2 = vg_scan_topk_collect(s->sh[(size_t)i], &keys[(size_t)i * VG_WAVE_KEYS]);
-                    if (rc == VG_OK) rc = rc2;
-                }
-            }
-            if (rc != VG_OK) return rc;
-            ++s->gather_calls[0];
-        }
+        int rc = scan_shards_topk(s, metric, query, kk, emit, keys.data());
+        if (rc != VG_OK) return rc;
         if (!always) {
-            const int got = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), kk, out_rowids, out_dist, k);
+            const int got = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, kk, out_rowids, out_dist, k);
             if (got >= 0) {
                 *out_count = got;
                 if (s->ref_hot > 0) --s->ref_hot;
@@ -762,32 +764,11 @@ extern "C" int vg_shards_scan_topk(vg_shards *s, int metric, const void *query, 
     if (ref && k > VG_WAVE_KEYS) { ++s->ref_stats[0]; return shards_scan_topk_reference(s, metric, query, k, out_rowids, out_dist, out_count); }
     if (ref) return shards_scan_topk_fused(s, metric, query, k, false, out_rowids, out_dist, out_count);
     if (k <= VG_WAVE_KEYS) {
-        // every shard in flight before the first wait: S scans run concurrently, one host thread
         std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS);
         std::vector<int> counts((size_t)s->S, VG_WAVE_KEYS);
-        int rc = -1;
-        if (s->gather_mode == 1 && rccl_ready(s)) {
-            rc = rccl_scan_and_gather(s, metric, query, k, keys.data());
-            if (rc != VG_OK) s->rccl_failed = true;            // (the host gather serves this query and the ones after it)
-        }
-        if (rc != VG_OK) {
-            rc = VG_OK;
-            if (s->threaded) {
-                rc = pool_run(s, [&](int i) {
-                    const int r = vg_scan_topk_enqueue(s->sh[(size_t)i], metric, query, k);
-                    return r != VG_OK ? r : vg_scan_topk_collect(s->sh[(size_t)i], &keys[(size_t)i * VG_WAVE_KEYS]);
-                });
-            } else {
-                for (int i = 0; i < s->S && rc == VG_OK; ++i) rc = vg_scan_topk_enqueue(s->sh[(size_t)i], metric, query, k);
-                for (int i = 0; i < s->S; ++i) {
-                    int rc2 = vg_scan_topk_collect(s->sh[(size_t)i], &keys[(size_t)i * VG_WAVE_KEYS]);
-                    if (rc == VG_OK) rc = rc2;
-                }
-            }
-            if (rc != VG_OK) return rc;
-            ++s->gather_calls[0];
-        }
-        *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), k, out_rowids, out_dist);
+        int rc = scan_shards_topk(s, metric, query, k, false, keys.data());
+        if (rc != VG_OK) return rc;
+        *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids, out_dist);
         return VG_OK;
     }
     const int kk = (int)std::min<int64_t>((int64_t)k, s->n_rows);
@@ -797,7 +778,7 @@ extern "C" int vg_shards_scan_topk(vg_shards *s, int metric, const void *query, 
         return vg_scan_topk_keys(s->sh[(size_t)i], metric, query, kk, &keys[(size_t)i * kk], &counts[(size_t)i]);
     });
     if (rc != VG_OK) return rc;
-    *out_count = merge_lists(s, keys.data(), kk, counts.data(), kk, out_rowids, out_dist);
+    *out_count = merge_lists(s, keys.data(), kk, counts.data(), 1, kk, out_rowids, out_dist);
     return VG_OK;
 }
 
@@ -836,14 +817,8 @@ extern "C" int vg_shards_scan_topk_batch(vg_shards *s, int metric, const void *q
         return vg_scan_topk_batch_keys(s->sh[(size_t)i], metric, queries, nq, kk, &keys[(size_t)i * nq * kk], &counts[(size_t)i * nq]);
     });
     if (rc != VG_OK) return rc;
-    std::vector<uint64_t> qkeys((size_t)s->S * kk);
-    std::vector<int> qcounts((size_t)s->S);
     for (int q = 0; q < nq; ++q) {
-        for (int i = 0; i < s->S; ++i) {
-            memcpy(&qkeys[(size_t)i * kk], &keys[((size_t)i * nq + q) * kk], (size_t)kk * sizeof(uint64_t));
-            qcounts[(size_t)i] = counts[(size_t)i * nq + q];
-        }
-        int got = merge_lists(s, qkeys.data(), kk, qcounts.data(), kk, out_rowids + (size_t)q * k, out_dist + (size_t)q * k, ref ? k : -1);
+        int got = merge_query_lists(s, keys.data(), counts.data(), nq, q, kk, kk, out_rowids + (size_t)q * k, out_dist + (size_t)q * k, ref ? k : -1);
         if (got < 0) {                                       // a tie: this query again through the emitting scans + the replay
             int rc1 = shards_scan_topk_fused(s, metric, (const uint8_t *)queries + (size_t)q * qbytes, k, true, out_rowids + (size_t)q * k,
                                              out_dist + (size_t)q * k, &got);
@@ -875,7 +850,46 @@ extern "C" int vg_shards_scan_distances(vg_shards *s, int metric, const void *qu
 
 // ---- range scans: every shard runs vg_scan_within (same radius, same limit - the first `limit` of the whole are among the first `limit`
 // of every shard); local order is monotone in global order, so sorting the held keys by (distance image, global position) is the order
-// of one corpus holding all rows
+// of one corpus holding all rows.  The single and the batch form share the merge and the fetch.
+
+// the shards' held keys of one query (read_keys(shard, n, out) brings shard's n) -> hits: merged, cut to `limit`.  matches / held: one
+// count per shard, `pitch` apart.  Returns VG_OK with *out_total = the matches of all shards.
+template <typename ReadKeys>
+static int merge_within(const vg_shards *s, const int64_t *matches, const int64_t *held, size_t pitch, int64_t limit, ReadKeys read_keys,
+                        std::vector<vg_shards::WithinHit> *hits, int64_t *out_total) {
+    int64_t total = 0;
+    std::vector<uint64_t> keys;
+    hits->clear();
+    for (int i = 0; i < s->S; ++i) {
+        total += matches[(size_t)i * pitch];
+        keys.resize((size_t)held[(size_t)i * pitch]);
+        int rc = read_keys(i, (int64_t)keys.size(), keys.data());
+        if (rc != VG_OK) return rc;
+        for (uint64_t key : keys) hits->push_back(vg_shards::WithinHit{key, global_of(s, i, (int64_t)vg_key_position(key)), i});
+    }
+    std::sort(hits->begin(), hits->end(), [](const vg_shards::WithinHit &a, const vg_shards::WithinHit &b) {
+        const uint32_t ia = (uint32_t)(a.key >> 32), ib = (uint32_t)(b.key >> 32);
+        return ia != ib ? ia < ib : a.gpos < b.gpos;
+    });
+    const int64_t keep = (limit > 0) ? std::min<int64_t>(limit, total) : total;
+    if ((int64_t)hits->size() > keep) hits->resize((size_t)keep);
+    *out_total = total;
+    return VG_OK;
+}
+
+// rows [first, first + n) of a merged result
+static int fetch_within(const vg_shards *s, const char *who, const std::vector<vg_shards::WithinHit> &hits, int64_t first, int64_t n,
+                        int64_t *out_rowids, double *out_dist) {
+    if (n < 0) n = 0;
+    if (first < 0 || first + n > (int64_t)hits.size()) return fail(VG_ERR_INVALID, (std::string(who) + ": rows outside the held result").c_str());
+    for (int64_t i = 0; i < n; ++i) {
+        const vg_shards::WithinHit &h = hits[(size_t)(first + i)];
+        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)h.shard], (int64_t)vg_key_position(h.key));
+        if (out_dist) out_dist[i] = (double)vg_key_distance(h.key);
+    }
+    return VG_OK;
+}
+
 extern "C" int vg_shards_scan_within(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                                      int64_t *out_held) {
     if (!s || !query) return fail(VG_ERR_INVALID, "vg_shards_scan_within: NULL argument");
@@ -886,21 +900,10 @@ extern "C" int vg_shards_scan_within(vg_shards *s, int metric, const void *query
     std::vector<int64_t> matches((size_t)s->S, 0), held((size_t)s->S, 0);
     int rc = for_each_shard(s, [&](int i) { return vg_scan_within(s->sh[(size_t)i], metric, query, radius, limit, &matches[(size_t)i], &held[(size_t)i]); });
     if (rc != VG_OK) return rc;
-    int64_t total = 0, all_held = 0;
-    for (int i = 0; i < s->S; ++i) { total += matches[(size_t)i]; all_held += held[(size_t)i]; }
-    s->within_hits.reserve((size_t)all_held);
-    std::vector<uint64_t> keys;
-    for (int i = 0; i < s->S; ++i) {
-        keys.resize((size_t)held[(size_t)i]);
-        if ((rc = vg_scan_within_keys(s->sh[(size_t)i], 0, held[(size_t)i], keys.data())) != VG_OK) return rc;
-        for (uint64_t key : keys) s->within_hits.push_back(vg_shards::WithinHit{key, global_of(s, i, (int64_t)vg_key_position(key)), i});
-    }
-    std::sort(s->within_hits.begin(), s->within_hits.end(), [](const vg_shards::WithinHit &a, const vg_shards::WithinHit &b) {
-        const uint32_t ia = (uint32_t)(a.key >> 32), ib = (uint32_t)(b.key >> 32);
-        return ia != ib ? ia < ib : a.gpos < b.gpos;
-    });
-    const int64_t keep = (limit > 0) ? std::min<int64_t>(limit, total) : total;
-    if ((int64_t)s->within_hits.size() > keep) s->within_hits.resize((size_t)keep);
+    int64_t total = 0;
+    rc = merge_within(s, matches.data(), held.data(), 1, limit,
+                      [&](int i, int64_t n, uint64_t *out) { return vg_scan_within_keys(s->sh[(size_t)i], 0, n, out); }, &s->within_hits, &total);
+    if (rc != VG_OK) return rc;
     if (out_matches) *out_matches = total;
     if (out_held) *out_held = (int64_t)s->within_hits.size();
     return VG_OK;
@@ -910,13 +913,7 @@ extern "C" int vg_shards_scan_within_fetch(const vg_shards *s, int64_t first, in
     if (!s) return fail(VG_ERR_INVALID, "vg_shards_scan_within_fetch: NULL argument");
     if (s->S == 1) return vg_scan_within_fetch(s->sh[0], first, n, out_rowids, out_dist);
     if (n <= 0) return VG_OK;
-    if (first < 0 || first + n > (int64_t)s->within_hits.size()) return fail(VG_ERR_INVALID, "vg_shards_scan_within_fetch: rows outside the held result");
-    for (int64_t i = 0; i < n; ++i) {
-        const vg_shards::WithinHit &h = s->within_hits[(size_t)(first + i)];
-        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)h.shard], (int64_t)vg_key_position(h.key));
-        if (out_dist) out_dist[i] = (double)vg_key_distance(h.key);
-    }
-    return VG_OK;
+    return fetch_within(s, "vg_shards_scan_within_fetch", s->within_hits, first, n, out_rowids, out_dist);
 }
 
 extern "C" int vg_shards_within_set_initial_capacity(vg_shards *s, int64_t keys) {
@@ -931,8 +928,7 @@ extern "C" int vg_shards_within_last_launches(const vg_shards *s) {
     return most;
 }
 
-// ---- batch range scans: every shard answers all nq queries (vg_scan_within_batch: same radii, same limit), then the per-query merge
-// of vg_shards_scan_within
+// ---- batch range scans: every shard answers all nq queries (vg_scan_within_batch: same radii, same limit), then merge_within per query
 extern "C" int vg_shards_scan_within_batch(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                            int64_t *out_matches, int64_t *out_held) {
     for (int q = 0; q < nq; ++q) { if (out_matches) out_matches[q] = 0; if (out_held) out_held[q] = 0; }
@@ -946,25 +942,14 @@ extern "C" int vg_shards_scan_within_batch(vg_shards *s, int metric, const void 
     });
     if (rc != VG_OK) return rc;
     s->within_batch_hits.resize((size_t)nq);
-    std::vector<uint64_t> keys;
     for (int q = 0; q < nq; ++q) {
-        std::vector<vg_shards::WithinHit> &hits = s->within_batch_hits[(size_t)q];
         int64_t total = 0;
-        for (int i = 0; i < s->S; ++i) {
-            const int64_t h = held[(size_t)i * nq + q];
-            total += matches[(size_t)i * nq + q];
-            keys.resize((size_t)h);
-            if ((rc = vg_scan_within_batch_keys(s->sh[(size_t)i], q, 0, h, keys.data())) != VG_OK) { s->within_batch_hits.clear(); return rc; }
-            for (uint64_t key : keys) hits.push_back(vg_shards::WithinHit{key, global_of(s, i, (int64_t)vg_key_position(key)), i});
-        }
-        std::sort(hits.begin(), hits.end(), [](const vg_shards::WithinHit &a, const vg_shards::WithinHit &b) {
-            const uint32_t ia = (uint32_t)(a.key >> 32), ib = (uint32_t)(b.key >> 32);
-            return ia != ib ? ia < ib : a.gpos < b.gpos;
-        });
-        const int64_t keep = (limit > 0) ? std::min<int64_t>(limit, total) : total;
-        if ((int64_t)hits.size() > keep) hits.resize((size_t)keep);
+        rc = merge_within(s, &matches[(size_t)q], &held[(size_t)q], (size_t)nq, limit,
+                          [&](int i, int64_t n, uint64_t *out) { return vg_scan_within_batch_keys(s->sh[(size_t)i], q, 0, n, out); },
+                          &s->within_batch_hits[(size_t)q], &total);
+        if (rc != VG_OK) { s->within_batch_hits.clear(); return rc; }
         if (out_matches) out_matches[q] = total;
-        if (out_held) out_held[q] = (int64_t)hits.size();
+        if (out_held) out_held[q] = (int64_t)s->within_batch_hits[(size_t)q].size();
     }
     return VG_OK;
 }
@@ -973,15 +958,7 @@ extern "C" int vg_shards_scan_within_batch_fetch(const vg_shards *s, int query, 
     if (!s) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch_fetch: NULL argument");
     if (s->S == 1) return vg_scan_within_batch_fetch(s->sh[0], query, first, n, out_rowids, out_dist);
     if (query < 0 || (size_t)query >= s->within_batch_hits.size()) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch_fetch: query outside the held result");
-    const std::vector<vg_shards::WithinHit> &hits = s->within_batch_hits[(size_t)query];
-    if (n <= 0) n = 0;
-    if (first < 0 || first + n > (int64_t)hits.size()) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch_fetch: rows outside the held result");
-    for (int64_t i = 0; i < n; ++i) {
-        const vg_shards::WithinHit &h = hits[(size_t)(first + i)];
-        if (out_rowids) out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)h.shard], (int64_t)vg_key_position(h.key));
-        if (out_dist) out_dist[i] = (double)vg_key_distance(h.key);
-    }
-    return VG_OK;
+    return fetch_within(s, "vg_shards_scan_within_batch_fetch", s->within_batch_hits[(size_t)query], first, n, out_rowids, out_dist);
 }
 
 extern "C" int vg_shards_within_batch_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
@@ -1101,7 +1078,7 @@ extern "C" int vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *
     std::vector<int> counts((size_t)s->S, 0);
     int rc = for_each_shard(s, [&](int i) { return vg_scan_topk_masked_keys(s->sh[(size_t)i], metric, query, k, &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]); });
     if (rc != VG_OK) return rc;
-    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), k, out_rowids, out_dist);
+    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids, out_dist);
     return VG_OK;
 }
 
@@ -1122,15 +1099,8 @@ extern "C" int vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const 
         return vg_scan_topk_batch_masked_keys(s->sh[(size_t)i], metric, queries, nq, k, &keys[(size_t)i * nq * k], &counts[(size_t)i * nq]);
     });
     if (rc != VG_OK) return rc;
-    std::vector<uint64_t> qkeys((size_t)s->S * k);
-    std::vector<int> qcounts((size_t)s->S);
-    for (int q = 0; q < nq; ++q) {
-        for (int i = 0; i < s->S; ++i) {
-            memcpy(&qkeys[(size_t)i * k], &keys[((size_t)i * nq + q) * k], (size_t)k * sizeof(uint64_t));
-            qcounts[(size_t)i] = counts[(size_t)i * nq + q];
-        }
-        out_counts[q] = merge_lists(s, qkeys.data(), k, qcounts.data(), k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
-    }
+    for (int q = 0; q < nq; ++q)
+        out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
     return VG_OK;
 }
 

@@ -10,7 +10,8 @@ Contract (include/vectorgpu.h): query i's answer is what scan_within is contract
     multi-query top-k scan's floats where it is not;
   * shapes without a multi-query form (f16 / bf16, long rows): the single range scans, bit for bit;
   * overflow of a query's region: complete answers, one more launch per overflowed pass;
-  * contract, batches larger than a staging slice, logical shards == one corpus.
+  * contract, batches larger than a staging slice, logical shards == one corpus;
+  * the shards' merge, single and batch form, against the oracle's order with equal distances in every shard.
 """
 import numpy as np
 import pytest
@@ -399,3 +400,38 @@ def test_shards_equal_one_corpus(pkg, vt, dim):
         _assert_same(many[i], ids, dist, ctx=("shards, overflow", i))
     sh.close()
     c.close()
+
+
+def test_shards_merge_vs_oracle_with_ties_across_shards(pkg, orc):
+    """The merge of the shards' held keys, single and batch form, against the order computed HERE from the pinned oracle's distances -
+    not against the other entry point: 40 distinct uint8 rows repeated over 3000 positions, so that every distance is held by rows of
+    all 3 shards and the order inside a distance is the global scan position's; 1 query and 5 (two passes at 4 per pass); limits that
+    cut inside a run of equal distances, and above the match count.  uint8 distances are exact: equality, bit for bit."""
+    vt, dim, n, S, B = dg.U8, 64, 3000, 3, 256
+    rows = np.ascontiguousarray(dg.corpus(vt, 40, dim, 9140)[np.random.default_rng(9141).integers(0, 40, n)])
+    qs = _queries(vt, 5, dim, 9142)
+    rowids = np.arange(n, dtype=np.int64) * 3 + 11
+    sh = pkg.Shards(vt, dim, [0] * S, block_rows=B)
+    sh.append(rows, rowids)
+    shard_of = (np.arange(n) // B) % S
+    for metric in (dg.SQUARED_L2, dg.L2):
+        assert sh.within_batch_plan(metric)[0] == 4
+        want = [orc.scan_distances(orc.AVX2, metric, vt, qs[i], rows) for i in range(5)]
+        radii = [float(np.sort(want[i])[n // 3 + 100 * i]) for i in range(5)]
+        exp = [_expected(want[i], radii[i], rowids) for i in range(5)]
+        m0 = len(exp[0][0])
+        tie = next(j for j in range(m0 // 2, m0) if exp[0][1][j - 1] == exp[0][1][j])      # a cut between two rows of one distance ...
+        held_by = shard_of[(exp[0][0] - 11) // 3][exp[0][1] == exp[0][1][tie]]
+        assert len(set(held_by.tolist())) == S, "... that rows of every shard hold"
+        for limit in (None, 7, tie, max(len(e[0]) for e in exp) + 10):
+            cut = n if limit is None else limit
+            ctx = (dg.METRIC_NAMES[metric], limit)
+            _assert_same(sh.scan_within(metric, qs[0], radii[0], limit=limit), exp[0][0][:cut], exp[0][1][:cut], matches=m0, ctx=(ctx, "single"))
+            one = sh.scan_within_batch(metric, qs[:1], radii[:1], limit=limit)
+            assert len(one) == 1
+            _assert_same(one[0], exp[0][0][:cut], exp[0][1][:cut], matches=m0, ctx=(ctx, "batch of 1"))
+            five = sh.scan_within_batch(metric, qs, radii, limit=limit)
+            assert len(five) == 5
+            for i in range(5):
+                _assert_same(five[i], exp[i][0][:cut], exp[i][1][:cut], matches=len(exp[i][0]), ctx=(ctx, "batch of 5", i))
+    sh.close()
