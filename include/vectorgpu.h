@@ -160,7 +160,8 @@ int64_t vg_corpus_rowid_at(const vg_corpus *c, int64_t position);
  * (2^20 keys to start with) costs ONE more launch into a buffer of the counted size.
  * The result stays on the handle, in host memory, until the next call that scans or changes the handle; vg_scan_within_fetch copies
  * rows [first, first + n) of it as (rowid, distance widened to double), vg_scan_within_keys as packed keys with positions local to
- * this corpus - the form a multi-shard caller merges.  out_rowids / out_dist may be NULL (not wanted). */
+ * this corpus - the form a multi-shard caller merges.  out_rowids / out_dist may be NULL (not wanted).  vg_scan_within_masked (below)
+ * leaves its result in the same place: either call overwrites what the other one held.  The handle's row mask is not read. */
 int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, int64_t limit,
                    int64_t *out_matches, int64_t *out_held);
 int vg_scan_within_fetch(const vg_corpus *c, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
@@ -189,7 +190,8 @@ int vg_scan_within_keys(const vg_corpus *c, int64_t first, int64_t n, uint64_t *
  * The result stays on the handle, in host memory, per query, until the next call that scans or changes the handle (the single
  * vg_scan_within keeps its own result apart); vg_scan_within_batch_fetch / _keys copy rows [first, first + n) of query `query` as
  * (rowid, distance widened to double) / packed keys with positions local to this corpus; a query index or a row range outside what
- * is held: VG_ERR_INVALID.  The handle's row mask is not read. */
+ * is held: VG_ERR_INVALID.  vg_scan_within_batch_masked (below) leaves its result in the same place: either call overwrites what the
+ * other one held.  The handle's row mask is not read. */
 int vg_scan_within_batch(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                          int64_t *out_matches, int64_t *out_held);
 int vg_scan_within_batch_fetch(const vg_corpus *c, int query, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist);
@@ -202,7 +204,7 @@ int vg_scan_within_batch_keys(const vg_corpus *c, int query, int64_t first, int6
  * mapped to positions on the host (implicit rowids: rowid - base; an ascending map: the search behind vg_corpus_find_rowid; a map
  * that is not ascending: VG_ERR_UNSUPPORTED); rowids the corpus does not hold are ignored, duplicates are harmless, *out_set (may
  * be NULL) = rows allowed.  vg_corpus_mask_count: rows allowed, -1 without a mask.
- * ONLY the masked scans (vg_scan_topk_masked, vg_scan_topk_batch_masked) read the mask: every other call behaves the same with and without one.  A call that changes the
+ * ONLY the masked scans (vg_scan_topk_masked[_keys], vg_scan_topk_batch_masked[_keys], vg_scan_within_masked, vg_scan_within_batch_masked) read the mask: every other call behaves the same with and without one.  A call that changes the
  * number of rows or which row sits at which position (append*, delete_rows, clear) drops the mask; patch_rows, reserve and trim
  * keep it; vg_corpus_clone copies it.
  * vg_scan_topk_masked: the contract of vg_scan_topk restricted to the allowed rows - NaN / +Inf never enter, fewer than k rows
@@ -220,8 +222,8 @@ int     vg_scan_topk_masked(vg_corpus *c, int metric, const void *query, int k,
 int     vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, int *out_count);
 
 /* ---- masked batch scans: one row mask, nq queries (row-major nq x dim, host) - "the k nearest rows of this tenant, for these 50
- * queries".  The mask is the one vg_corpus_set_mask_* left on the handle; these three calls and vg_scan_topk_masked[_keys] are the
- * only ones that read it - vg_scan_topk_batch still ignores it.  out_rowids / out_dist are nq x k, out_counts nq; the slots of
+ * queries".  The mask is the one vg_corpus_set_mask_* left on the handle; these calls, vg_scan_topk_masked[_keys] and the masked range
+ * scans (vg_scan_within_masked, vg_scan_within_batch_masked) are the only ones that read it - vg_scan_topk_batch still ignores it.  out_rowids / out_dist are nq x k, out_counts nq; the slots of
  * query i behind out_counts[i] are NOT written.
  * Query i's answer is what vg_scan_topk_masked is contracted to return for it: only allowed rows, ascending (distance, scan
  * position) whatever the handle's tie_order, NaN / +Inf never enter, fewer than k rows when fewer allowed rows qualify.
@@ -240,6 +242,35 @@ int     vg_scan_topk_batch_masked(vg_corpus *c, int metric, const void *queries,
                                   int64_t *out_rowids, double *out_dist, int *out_counts);
 int     vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k,
                                        uint64_t *out_keys, int *out_counts);
+
+/* ---- masked range scans: every ALLOWED row within a distance of the query - "every row of this tenant within r", near-duplicate
+ * detection inside one category (no reference entry point; the reference's form is "SELECT ... FROM vector_full_scan_stream(...)
+ * WHERE id IN (...) AND distance <= r": N rows stepped).  The contract is the conjunction of vg_scan_within's and vg_scan_topk_masked's.
+ * The mask is the one vg_corpus_set_mask_* left on the handle.  A row matches when its bit is set AND its distance d - the float
+ * vg_scan_distances reports for it, bit for bit - satisfies (double)d <= radius.  NaN and +Inf distances never match, whatever the
+ * radius; radius = +Inf means "every allowed row with a finite distance"; the radius is turned into the largest float not above it.
+ * Order: ascending (distance, scan position), whatever the handle's tie_order.  limit > 0: the first `limit` matches in that order
+ * are held (per query), *out_matches still counts all of them; limit <= 0: all are held.
+ * The kernels are the masked scans' loops with the range scans' compare-and-compact: a batch of rows without an allowed row is not
+ * read, nothing is written for a row that does not match, and only ALLOWED matches take room in the device buffer - a result larger
+ * than it costs ONE more launch into a buffer of the counted size, as in vg_scan_within (timings not measured yet).
+ * vg_scan_within_masked leaves its result where vg_scan_within leaves its own and overwrites it (and the reverse): read it with
+ * vg_scan_within_fetch / _keys.  vg_scan_within_batch_masked: nq queries (row-major nq x dim, host), a radius each, out_matches /
+ * out_held nq (either may be NULL); it leaves its results where vg_scan_within_batch leaves its own and overwrites them (and the
+ * reverse): read them with vg_scan_within_batch_fetch / _keys.  The single and the batch form keep their results apart.
+ * Batch precision: f32 / uint8 / int8 rows of a register-resident shape share every row load of a pass among 4 (or 2) queries
+ * (vg_scan_multi_within_masked.h; the plan: vg_within_batch_masked_plan, vectorgpu_diag.h), slices, key budget and the "a pass that
+ * overflowed runs once more as a whole" rule as in vg_scan_within_batch.  uint8 / int8: rowids, order, distance bits and counts
+ * identical to nq vg_scan_within_masked calls.  f32: the single scan's arithmetic per (query, row) pair under the multi-query launch
+ * shape - bit for bit the single masked range scan where the two shapes agree, and as in vg_scan_within_batch elsewhere (for an
+ * allowed row, vg_scan_within_batch's float, bit for bit).  f16 / bf16, long rows and every other shape without a multi-query form:
+ * nq single vg_scan_within_masked calls whose results are copied into the per-query storage.
+ * No mask set: VG_ERR_INVALID; a NaN radius: VG_ERR_INVALID before any launch; an unknown metric, a NULL c / query / queries / radii
+ * or nq < 1: VG_ERR_INVALID - each with the counts zeroed first.  An empty mask or an empty corpus: every count 0 without a launch. */
+int     vg_scan_within_masked(vg_corpus *c, int metric, const void *query, double radius, int64_t limit,
+                              int64_t *out_matches, int64_t *out_held);
+int     vg_scan_within_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                    int64_t *out_matches, int64_t *out_held);
 
 /* nq queries at once (row-major nq x dim, host).  out_rowids / out_dist are nq x k, out_counts nq.
  * f32 corpora, k <= 32, rows <= 512 floats, metric DOT / COSINE / L2 / SQUARED_L2: one pass over the corpus on the
@@ -330,6 +361,14 @@ int     vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *query, 
  * GLOBAL scan position): the answer of one corpus holding all rows.  Same contract. */
 int     vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const void *queries, int nq, int k,
                                          int64_t *out_rowids, double *out_dist, int *out_counts);
+/* the masked range scans over every shard: each shard answers over its own bits (a shard whose share of the mask is empty launches
+ * nothing and contributes nothing), merged like vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus
+ * holding all rows.  Same contract; the results are read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and
+ * overwrite what the unmasked forms held there (and the reverse). */
+int     vg_shards_scan_within_masked(vg_shards *s, int metric, const void *query, double radius, int64_t limit,
+                                     int64_t *out_matches, int64_t *out_held);
+int     vg_shards_scan_within_batch_masked(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                           int64_t *out_matches, int64_t *out_held);
 int     vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative);
 int     vg_shards_quantize_rows(vg_shards *s, float scale, float offset, int qtype, int64_t row0, int64_t n_rows, uint8_t *out_host);
 

@@ -108,6 +108,13 @@ int vg_within_batch_last_launches(const vg_corpus *c);
 int vg_shards_within_batch_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 int vg_shards_within_batch_set_initial_capacity(vg_shards *s, int64_t keys_per_query);
 int vg_shards_within_batch_last_launches(const vg_shards *s);
+/* masked range scans (vg_scan_within_masked, vg_scan_within_batch_masked): capacities and launch counts are the unmasked forms'
+ * (vg_within_set_initial_capacity / vg_within_last_launches, vg_within_batch_set_initial_capacity / vg_within_batch_last_launches: a
+ * masked scan starts from the same buffer and counts its launches in the same place; 0 launches for an empty mask).
+ * vg_within_batch_masked_plan: how vg_scan_within_batch_masked would serve this corpus under `metric` - the outputs of
+ * vg_within_batch_plan (0 queries per pass = the fallback, one single masked range scan per query).  Shards: shard 0's plan. */
+int vg_within_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
+int vg_shards_within_batch_masked_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 
 /* host-only: the same replay over n distances the caller holds (scan order); returns the count (<= k) or -1.
  * below_cap <= 0: the device path's candidate capacity. */

@@ -172,6 +172,12 @@ def _load():
         "vg_scan_within_keys": (i32, [vp, i64, i64, vp]),
         "vg_shards_scan_within": (i32, [vp, i32, vp, C.c_double, i64, C.POINTER(i64), C.POINTER(i64)]),
         "vg_shards_scan_within_fetch": (i32, [vp, i64, i64, vp, vp]),
+        "vg_scan_within_masked": (i32, [vp, i32, vp, C.c_double, i64, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_shards_scan_within_masked": (i32, [vp, i32, vp, C.c_double, i64, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_scan_within_batch_masked": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
+        "vg_shards_scan_within_batch_masked": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
+        "vg_within_batch_masked_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "vg_shards_within_batch_masked_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_within_set_initial_capacity": (i32, [vp, i64]),
         "vg_within_last_launches": (i32, [vp]),
         "vg_shards_within_set_initial_capacity": (i32, [vp, i64]),
@@ -275,6 +281,14 @@ def within_batch_plan(corpus, metric):
     return nq.value, lpr.value, u.value
 
 
+def within_batch_masked_plan(corpus, metric):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_within_batch_masked serves this corpus (or shard set) with; 0
+    queries per pass = one single masked range scan per query (f16 / bf16, long rows) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(getattr(lib(), _wb_prefix(corpus) + "masked_plan")(corpus.h, metric, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
+
+
 def set_within_batch_initial_capacity(corpus, keys_per_query):
     """keys the device region of each query of the next scan_within_batch calls starts with (0: the default) - vectorgpu_diag.h"""
     _check(getattr(lib(), _wb_prefix(corpus) + "set_initial_capacity")(corpus.h, int(keys_per_query)))
@@ -283,6 +297,17 @@ def set_within_batch_initial_capacity(corpus, keys_per_query):
 def within_batch_last_launches(corpus):
     """scan kernel launches of the last scan_within_batch: its passes, plus one per pass that overflowed and ran once more"""
     return int(getattr(lib(), _wb_prefix(corpus) + "last_launches")(corpus.h))
+
+
+def _scan_within(scan, fetch, h, metric, query, radius, limit):
+    query = np.ascontiguousarray(query)
+    m, held = C.c_int64(0), C.c_int64(0)
+    _check(scan(h, metric, _ptr(query), float(radius), 0 if limit is None else max(int(limit), 0), C.byref(m), C.byref(held)))
+    n = 0 if (limit is not None and limit <= 0) else held.value
+    ids, dist = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64)
+    if n:
+        _check(fetch(h, 0, n, _ptr(ids), _ptr(dist)))
+    return ids, dist, m.value
 
 
 def _scan_within_batch(scan, fetch, h, metric, queries, radii, limit):
@@ -393,16 +418,9 @@ class Corpus:
     def scan_within(self, metric, query, radius, limit=None):
         """every row with distance <= radius (finite), ordered by (distance, scan position): (rowids, distances, matches); with a
         limit the first `limit` of them, `matches` still counting all"""
-        query = np.ascontiguousarray(query)
-        m, held = C.c_int64(0), C.c_int64(0)
-        _check(lib().vg_scan_within(self.h, metric, _ptr(query), float(radius), 0 if limit is None else max(int(limit), 0), C.byref(m), C.byref(held)))
-        n = 0 if (limit is not None and limit <= 0) else held.value
-        ids, dist = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64)
-        if n:
-            _check(lib().vg_scan_within_fetch(self.h, 0, n, _ptr(ids), _ptr(dist)))
-        return ids, dist, m.value
+        return _scan_within(lib().vg_scan_within, lib().vg_scan_within_fetch, self.h, metric, query, radius, limit)
 
-    # masked scans: a row mask on the handle (a bitmap over scan positions), read by scan_topk_masked / scan_topk_batch_masked only
+    # masked scans: a row mask on the handle (a bitmap over scan positions), read by the four *_masked scans only
     def set_mask(self, bits=None, positions=None, rowids=None):
         """the rows a masked scan may return - exactly one of: `bits` (bool per scan position, or packed uint64 words: bit p & 63 of
         word p >> 6), `positions` (scan positions), `rowids` (those not held are ignored).  Returns the number of rows allowed."""
@@ -428,6 +446,15 @@ class Corpus:
         """scan_topk_masked for every row of `queries` in shared passes over the allowed rows: (rowids [nq, k], distances [nq, k],
         counts [nq]) like scan_topk_batch; slots behind a query's count stay zero"""
         return _scan_topk_batch_masked(lib().vg_scan_topk_batch_masked, self.h, metric, queries, k)
+
+    def scan_within_masked(self, metric, query, radius, limit=None):
+        """scan_within among the ALLOWED rows: (rowids, distances, matches); it holds its result where scan_within does"""
+        return _scan_within(lib().vg_scan_within_masked, lib().vg_scan_within_fetch, self.h, metric, query, radius, limit)
+
+    def scan_within_batch_masked(self, metric, queries, radii, limit=None):
+        """scan_within_masked for every row of `queries` in shared passes over the allowed rows, a radius each (a scalar is
+        broadcast): a list of (rowids, distances, matches) per query; it holds its results where scan_within_batch does"""
+        return _scan_within_batch(lib().vg_scan_within_batch_masked, lib().vg_scan_within_batch_fetch, self.h, metric, queries, radii, limit)
 
     def clone(self):
         """a second corpus with the same rows, rowids, switches and row mask (vg_corpus_clone)"""
@@ -464,6 +491,9 @@ class Corpus:
 
     def within_batch_plan(self, metric):
         return within_batch_plan(self, metric)
+
+    def within_batch_masked_plan(self, metric):
+        return within_batch_masked_plan(self, metric)
 
     def set_within_batch_initial_capacity(self, keys_per_query):
         set_within_batch_initial_capacity(self, keys_per_query)
@@ -783,14 +813,15 @@ class Shards:
 
     def scan_within(self, metric, query, radius, limit=None):
         """Corpus.scan_within over all shards, merged by (distance, global scan position): (rowids, distances, matches)"""
-        query = np.ascontiguousarray(query)
-        m, held = C.c_int64(0), C.c_int64(0)
-        _check(lib().vg_shards_scan_within(self.h, metric, _ptr(query), float(radius), 0 if limit is None else max(int(limit), 0), C.byref(m), C.byref(held)))
-        n = 0 if (limit is not None and limit <= 0) else held.value
-        ids, dist = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.float64)
-        if n:
-            _check(lib().vg_shards_scan_within_fetch(self.h, 0, n, _ptr(ids), _ptr(dist)))
-        return ids, dist, m.value
+        return _scan_within(lib().vg_shards_scan_within, lib().vg_shards_scan_within_fetch, self.h, metric, query, radius, limit)
+
+    def scan_within_masked(self, metric, query, radius, limit=None):
+        """Corpus.scan_within_masked over all shards (each over its own bits), merged like scan_within"""
+        return _scan_within(lib().vg_shards_scan_within_masked, lib().vg_shards_scan_within_fetch, self.h, metric, query, radius, limit)
+
+    def scan_within_batch_masked(self, metric, queries, radii, limit=None):
+        """Corpus.scan_within_batch_masked over all shards, merged per query by (distance, global scan position)"""
+        return _scan_within_batch(lib().vg_shards_scan_within_batch_masked, lib().vg_shards_scan_within_batch_fetch, self.h, metric, queries, radii, limit)
 
     def set_within_initial_capacity(self, keys):
         _check(lib().vg_shards_within_set_initial_capacity(self.h, keys))
@@ -804,6 +835,9 @@ class Shards:
 
     def within_batch_plan(self, metric):
         return within_batch_plan(self, metric)
+
+    def within_batch_masked_plan(self, metric):
+        return within_batch_masked_plan(self, metric)
 
     def set_within_batch_initial_capacity(self, keys_per_query):
         set_within_batch_initial_capacity(self, keys_per_query)

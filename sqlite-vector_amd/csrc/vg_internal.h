@@ -169,7 +169,7 @@ struct vg_corpus {
     std::vector<std::vector<uint64_t>> wb_keys;   // per query: the held keys, ascending = (distance, scan position)
     std::vector<int64_t> wb_matches;
     // masked scans (vg_scan_masked.hip): the row mask - bit (p & 63) of word (p >> 6) = the row at scan position p may be returned.  Read
-    // by vg_scan_topk_masked only; dropped (vg_drop_mask) by every call that changes the number of rows or which row sits where
+    // by the masked scans only (vectorgpu.h lists them); dropped (vg_drop_mask) by every call that changes the number of rows or which row sits where
     uint64_t *d_mask = nullptr;               // ceil(n_rows / 64) words while a mask is set (mask_cap_words allocated)
     int64_t mask_cap_words = 0;
     std::vector<uint64_t> mask_host;          // the same words on the host (vg_corpus_clone copies them)
@@ -286,6 +286,13 @@ ScanArgs vg_scan_args(const vg_corpus *c, int metric, int acc, const VgShape &s,
 size_t vg_query_lds_bytes(const vg_corpus *c, const VgShape &s);   // the staged query in LDS (long rows: padded to whole slices)
 // the launch itself (VG_BLOCK threads), behind the dynamic-LDS attribute step a window above 64 KiB needs; enqueue only
 int vg_launch_scan_kernel(scan_fn_t fn, long long blocks, size_t smem, hipStream_t stream, const ScanArgs &a);
+// ---- the single range scan (vg_scan_within.hip: vg_within_run), shared by the unmasked and the masked form: which kernel table
+// (vg_pick_scan<Family> of the unit that holds the kernels), whether ScanArgs.mask is set and a mask required, whose name errors carry
+typedef scan_fn_t (*vg_pick_scan_fn_t)(int vtype, int acc, int U, bool long_rows);
+struct VgWithinForm { const char *who; vg_pick_scan_fn_t pick; bool masked; };
+int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
+                  int64_t *out_held);
+scan_fn_t vg_pick_multi_within_masked(int vtype, int acc, int U, int NQ);   // vg_multi_within_masked.hip: the masked batch range scan's kernel table
 // ---- range-scan results (vg_scan_within.hip), shared by the single and the batch form
 float vg_within_radius(double radius);                              // the largest float not above the radius
 // `count` keys at dev_keys -> *dst, ascending and cut to `limit`.  Up to VG_WITHIN_HOST_SORT keys: the copy is only enqueued and

@@ -12,6 +12,10 @@
 // needed: that pass - and only that pass - runs once more as a whole into regions of the counted sizes; a partial answer is never
 // returned.  From the counted keys of a query on - sorted, cut to `limit`, held, read - the result path is the single range scan's
 // (vg_scan_within.hip: vg_within_collect / _finish / _held_*); the batch's held results stay apart from the single scan's on a handle.
+//
+// The masked batch (vg_scan_within_batch_masked) is the same host code: its kernels are vg_scan_multi_within_masked.h's, held by
+// vg_multi_within_masked.hip, its launches set ScanArgs.mask, its fallback is nq single MASKED range scans - nothing else differs, and
+// it leaves its held results where the unmasked batch leaves its own.
 #include "vg_internal.h"
 
 #include "vg_scan_multi_within.h"
@@ -21,25 +25,33 @@ struct MultiWithinFamily {
     template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_within_kernel<VT, ACC, U, NQ, true>; }
 };
 
-// (queries per pass, launch shape, kernel) of the multi-query range scan; 0 queries per pass: the fallback serves the shape
-static int mw_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn) {
+// (queries per pass, launch shape, kernel) of the multi-query range scan, unmasked or masked; 0 queries per pass: the fallback serves
+// the shape.  Every instance of both tables compiles without scratch or spills: the masked plan is the unmasked one.
+static int mw_plan(const vg_corpus *c, int metric, bool masked, VgShape *s, scan_fn_t *fn) {
     const int NQ = vg_multi_plan(c, metric, s);
     if (NQ == 0) return 0;
-    scan_fn_t f = vg_pick_multi<MultiWithinFamily>(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
+    const int acc = vg_metric_to_acc(metric);
+    scan_fn_t f = masked ? vg_pick_multi_within_masked(c->vtype, acc, s->U, NQ) : vg_pick_multi<MultiWithinFamily>(c->vtype, acc, s->U, NQ);
     if (fn) *fn = f;
     return f ? NQ : 0;
 }
 
-extern "C" int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+static int within_batch_plan(const vg_corpus *c, int metric, bool masked, int *out_queries_per_pass, int *out_lpr, int *out_u) {
     if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     VgShape s{};
-    const int NQ = mw_plan(c, metric, &s, nullptr);
+    const int NQ = mw_plan(c, metric, masked, &s, nullptr);
     if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single range scan's
     if (out_queries_per_pass) *out_queries_per_pass = NQ;
     if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
     if (out_u) *out_u = s.long_rows ? 0 : s.U;
     return VG_OK;
+}
+extern "C" int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    return within_batch_plan(c, metric, false, out_queries_per_pass, out_lpr, out_u);
+}
+extern "C" int vg_within_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    return within_batch_plan(c, metric, true, out_queries_per_pass, out_lpr, out_u);
 }
 
 // queries go up in slices of this many (a multiple of every queries-per-pass): staging and key regions do not grow with the batch
@@ -63,10 +75,14 @@ static int ensure_dev(unsigned long long **p, size_t *have, size_t need) {
     return VG_OK;
 }
 
+// what differs between the unmasked and the masked batch: whose name errors carry, and whether the launches read the handle's mask
+struct WbForm { const char *who; bool masked; };
+
 // one pass: NQ queries + their descriptors at dev_block.  Asynchronous on the corpus stream.
-static int launch_multi_within(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_block) {
+static int launch_multi_within(vg_corpus *c, const WbForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_block) {
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);      // the multi-query scan's launch shape
     ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_block, 0);
+    if (f.masked) a.mask = c->d_mask;
     a.store_lds_off = (int)(((size_t)NQ * c->nch * 16 + 255) / 256 * 256);     // the key queues behind the staged queries
     const size_t smem = (size_t)a.store_lds_off + (size_t)NQ * VG_WITHIN_LDS_BYTES;
     hipEvent_t *evs = vg_prof_slot(c, 0);                      // one slot of the profiling ring per pass
@@ -86,7 +102,7 @@ static int collect_keys(vg_corpus *c, int qi, const unsigned long long *dev_keys
 }
 
 // nq queries, NQ per pass
-static int batch_within_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries, int nq,
+static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries, int nq,
                               const double *radii, int64_t limit) {
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
     const int slice = std::min(nq_pad, VG_WB_SLICE);
@@ -123,11 +139,11 @@ static int batch_within_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, co
         HIP_TRY(hipMemcpyAsync(d_stage, block_of(q0), (size_t)(nqs / NQ) * block_bytes, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(vg_wb_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, c->d_wb, pitch, nqs, (unsigned long long *)nullptr);
         for (int g = 0; g < nqs; g += NQ)
-            if ((rc = launch_multi_within(c, metric, fn, NQ, s, d_stage + (size_t)(g / NQ) * block_bytes)) != VG_OK) { hipStreamSynchronize(c->stream); return rc; }
+            if ((rc = launch_multi_within(c, f, metric, fn, NQ, s, d_stage + (size_t)(g / NQ) * block_bytes)) != VG_OK) { hipStreamSynchronize(c->stream); return rc; }
         hipLaunchKernelGGL(vg_wb_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, c->d_wb, pitch, nqs, c->d_wb_counts);
         hipError_t e = hipMemcpyAsync(c->h_wb, c->d_wb_counts, (size_t)nqs * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
         hipError_t e2 = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess || e2 != hipSuccess) return vg_fail(VG_ERR_HIP, "vg_scan_within_batch: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        if (e != hipSuccess || e2 != hipSuccess) return vg_fail(VG_ERR_HIP, "%s: %s", f.who, hipGetErrorString(e != hipSuccess ? e : e2));
         std::vector<int64_t> counts((size_t)nqs);
         for (int j = 0; j < nqs; ++j) counts[(size_t)j] = (q0 + j < nq) ? (int64_t)c->h_wb[j] : 0;
 
@@ -159,13 +175,13 @@ static int batch_within_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, co
             }
             uint8_t *d_block = d_stage + (size_t)(g / NQ) * block_bytes;
             HIP_TRY(hipMemcpyAsync(d_block + (size_t)NQ * c->stride, desc_of(q0 + g), (size_t)NQ * sizeof(VgWithinQuery), hipMemcpyHostToDevice, c->stream));
-            if ((rc = launch_multi_within(c, metric, fn, NQ, s, d_block)) != VG_OK) { hipStreamSynchronize(c->stream); return rc; }
+            if ((rc = launch_multi_within(c, f, metric, fn, NQ, s, d_block)) != VG_OK) { hipStreamSynchronize(c->stream); return rc; }
             for (int n = 0; n < NQ; ++n)
                 HIP_TRY(hipMemcpyAsync(c->h_wb + VG_WB_SLICE + n, desc_of(q0 + g + n)->out, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(hipStreamSynchronize(c->stream));
             for (int n = 0; n < NQ && q0 + g + n < nq; ++n)
                 if ((int64_t)c->h_wb[VG_WB_SLICE + n] != counts[(size_t)(g + n)])
-                    return vg_fail(VG_ERR_HIP, "vg_scan_within_batch: two launches counted %lld and %lld rows for query %d", (long long)counts[(size_t)(g + n)],
+                    return vg_fail(VG_ERR_HIP, "%s: two launches counted %lld and %lld rows for query %d", f.who, (long long)counts[(size_t)(g + n)],
                                    (long long)c->h_wb[VG_WB_SLICE + n], q0 + g + n);
             pending = false;
             for (int n = 0; n < NQ && q0 + g + n < nq; ++n)
@@ -178,26 +194,27 @@ static int batch_within_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, co
     return VG_OK;
 }
 
-extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
-                                    int64_t *out_matches, int64_t *out_held) {
+static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                        int64_t *out_matches, int64_t *out_held) {
     for (int i = 0; i < nq; ++i) { if (out_matches) out_matches[i] = 0; if (out_held) out_held[i] = 0; }      // (every error leaves the counts zeroed)
-    if (!c || !queries || !radii) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch: NULL argument");
+    if (!c || !queries || !radii) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     c->wb_keys.clear();
     c->wb_matches.clear();
     c->wb_launches = 0;
-    if (nq < 1) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch: nq must be at least 1");
+    if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     for (int i = 0; i < nq; ++i)
-        if (radii[i] != radii[i]) return vg_fail(VG_ERR_INVALID, "vg_scan_within_batch: radius %d is NaN", i);
+        if (radii[i] != radii[i]) return vg_fail(VG_ERR_INVALID, "%s: radius %d is NaN", f.who, i);
+    if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
     c->wb_keys.resize((size_t)nq);
     c->wb_matches.assign((size_t)nq, 0);
-    if (c->n_rows == 0) return VG_OK;
+    if (c->n_rows == 0 || (f.masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
     HIP_TRY(hipSetDevice(c->device));
     VgShape s{};
     scan_fn_t fn = nullptr;
-    const int NQ = mw_plan(c, metric, &s, &fn);
+    const int NQ = mw_plan(c, metric, f.masked, &s, &fn);
     int rc = VG_OK;
-    if (NQ == 0) {                                               // no multi-query form: the single range scans, one by one
+    if (NQ == 0) {                                               // no multi-query form: the single range scans of the same form, one by one
         const size_t row_bytes = (size_t)c->dim * c->es;
         // (the single range scan keeps its own result apart: what the handle held for it is put back behind the loop)
         std::vector<uint64_t> single_keys;
@@ -206,7 +223,8 @@ extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *querie
         const int single_launches = c->within_launches;
         for (int i = 0; i < nq && rc == VG_OK; ++i) {
             int64_t m = 0, h = 0;
-            rc = vg_scan_within(c, metric, (const uint8_t *)queries + (size_t)i * row_bytes, radii[i], limit, &m, &h);
+            const void *q = (const uint8_t *)queries + (size_t)i * row_bytes;
+            rc = f.masked ? vg_scan_within_masked(c, metric, q, radii[i], limit, &m, &h) : vg_scan_within(c, metric, q, radii[i], limit, &m, &h);
             if (rc != VG_OK) break;
             c->wb_keys[(size_t)i] = c->within_keys;
             c->wb_matches[(size_t)i] = m;
@@ -216,7 +234,7 @@ extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *querie
         c->within_matches = single_matches;
         c->within_launches = single_launches;
     } else {
-        rc = batch_within_multi(c, metric, fn, NQ, s, queries, nq, radii, limit);
+        rc = batch_within_multi(c, f, metric, fn, NQ, s, queries, nq, radii, limit);
     }
     if (rc != VG_OK) { c->wb_keys.clear(); c->wb_matches.clear(); return rc; }
     for (int i = 0; i < nq; ++i) {
@@ -224,6 +242,16 @@ extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *querie
         if (out_held) out_held[i] = (int64_t)c->wb_keys[(size_t)i].size();
     }
     return VG_OK;
+}
+
+extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                    int64_t *out_matches, int64_t *out_held) {
+    return within_batch(c, WbForm{"vg_scan_within_batch", false}, metric, queries, nq, radii, limit, out_matches, out_held);
+}
+
+extern "C" int vg_scan_within_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                           int64_t *out_matches, int64_t *out_held) {
+    return within_batch(c, WbForm{"vg_scan_within_batch_masked", true}, metric, queries, nq, radii, limit, out_matches, out_held);
 }
 
 // the held keys of `query`, or nullptr (with the error set) when there is no such query

@@ -107,6 +107,7 @@ __device__ inline void vg_within_offer(uint64_t key, bool match, uint64_t *queue
 }
 
 // ---- "masked" mode (MASKED = true, instantiated in vg_scan_masked.hip): top-k among the rows whose bit is set in ScanArgs.mask.
+// WITHIN && MASKED (vg_scan_within_masked.hip): the masked loops with the within offer and the within tail - no list, no publish.
 // vg_mask_bits: the bits of the `n` rows from `row0` on (n a power of two <= 64 and row0 a multiple of it: adjacent bits of ONE word),
 // bit i = row0 + i, zero when the rows are out of range.  Every lane of the wavefront asks for the same rows, but the compiler cannot
 // know that of a value derived from threadIdx: the start row goes through readfirstlane (0xFFFFFFFF = out of range: a shard holds at
@@ -236,7 +237,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
                                               reinterpret_cast<const uint16_t *>(a.rows + row * a.stride), a.dim, a.root);
         }
         d = vg_clamp(d);
-        if constexpr (WITHIN) {
+        if constexpr (WITHIN && MASKED) {
+            // masked range scan (vg_scan_within_masked.hip): the masked loops below, the within offer, and a row matches when its bit is set too
+            vg_within_offer(vg_make_key(d, (uint32_t)row), owner && ((mbits >> rib) & 1ull) && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
+        } else if constexpr (WITHIN) {
             // d <= r is false for NaN; +Inf never matches, whatever the radius (the top-k contract: such rows never enter a list)
             vg_within_offer(vg_make_key(d, (uint32_t)row), owner && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
         } else if (store_mode) {
@@ -434,7 +438,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
                                                   reinterpret_cast<const uint16_t *>(a.rows + row * a.stride), a.dim, a.root);
             }
             d = vg_clamp(d);
-            if constexpr (WITHIN) {
+            if constexpr (WITHIN) {                                 // (WITHIN && MASKED: a row whose bit is clear never gets here)
                 vg_within_offer(vg_make_key(d, (uint32_t)row), (lane == 0) && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
             } else if (store_mode) {
                 if (lane == 0) a.out_dist[row] = d;

@@ -7,7 +7,8 @@
 // allowed row reads no rows and a row whose bit is clear is never offered to a list.  A translation unit of their own, like
 // vg_scan_ex.hip and vg_scan_within.hip: the plain kernels keep their register budget.  One load policy (non-temporal).
 //
-// Only the masked scans read the mask: vg_scan_topk_masked here, vg_scan_topk_batch_masked in vg_multi_masked.hip.  Order: ascending (distance, scan position) whatever the handle's tie_order.
+// Only the masked scans read the mask: vg_scan_topk_masked here, vg_scan_topk_batch_masked in vg_multi_masked.hip, and the masked range
+// scans (vg_scan_within_masked.hip, vg_multi_within.hip).  Order: ascending (distance, scan position) whatever the handle's tie_order.
 #include "vg_internal.h"
 
 #include "vg_scan.h"

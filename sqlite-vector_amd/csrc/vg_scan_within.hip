@@ -12,6 +12,8 @@
 //
 // The result path - radius rounding, the sort's buffers, "count keys on the device -> held, sorted, cut to limit", the readers of a held
 // result - is here ONCE and serves the batch form (vg_multi_within.hip) too; each form keeps its own held result on the handle.
+// So is the single scan itself (vg_within_run): the masked range scan (vg_scan_within_masked.hip) is this code with its own kernel
+// table and ScanArgs.mask set, and leaves its result where vg_scan_within leaves its own.
 #include "vg_internal.h"
 
 #include "vg_scan.h"
@@ -96,21 +98,22 @@ int vg_within_held_rows(const vg_corpus *c, const char *who, const std::vector<u
 
 // ------------------------------------------------------------------------------------------------ the single range scan
 
-// one launch of the within kernel into c->d_within ([count | cap keys]); the count lands in the pinned c->h_keys[0] behind it
-static int launch_within(vg_corpus *c, int metric, float r, int64_t cap) {
+// one launch of the form's within kernel into c->d_within ([count | cap keys]); the count lands in the pinned c->h_keys[0] behind it
+static int launch_within(vg_corpus *c, const VgWithinForm &f, int metric, float r, int64_t cap) {
     int acc = vg_metric_to_acc(metric);
     VgShape s;
     vg_plain_scan_shape(c, metric, &s);
     int rc = vg_half_cosine_acc(c, s, &acc);                 // the plain scan's cached-norm cosine: the same floats
     if (rc != VG_OK) return rc;
-    scan_fn_t fn = vg_pick_scan<WithinFamily>(c->vtype, acc, s.U, s.long_rows);
-    if (!fn) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_within: no kernel for this type / metric");
+    scan_fn_t fn = f.pick(c->vtype, acc, s.U, s.long_rows);
+    if (!fn) return vg_fail(VG_ERR_UNSUPPORTED, "%s: no kernel for this type / metric", f.who);
 
     const long long blocks = vg_within_scan_blocks(c, c->n_rows, s);
     ScanArgs a = vg_scan_args(c, metric, acc, s, c->d_query, 0);
     a.emit = c->d_within;
     a.within_r = r;
     a.within_cap = (unsigned long long)cap;
+    if (f.masked) a.mask = c->d_mask;
     a.store_lds_off = (int)((vg_query_lds_bytes(c, s) + 255) / 256 * 256);     // the wavefronts' key queues behind the query
     const size_t smem = (size_t)a.store_lds_off + VG_WITHIN_LDS_BYTES;
 
@@ -134,17 +137,19 @@ static int ensure_within_buffer(vg_corpus *c, int64_t cap) {
     return VG_OK;
 }
 
-extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
-                              int64_t *out_held) {
-    if (!c || !query) return vg_fail(VG_ERR_INVALID, "vg_scan_within: NULL argument");
+// a single range scan, unmasked or masked (VgWithinForm, vg_internal.h): argument checks, launch, the overflow protocol, the held result
+int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
+                  int64_t *out_held) {
     if (out_matches) *out_matches = 0;
     if (out_held) *out_held = 0;
+    if (!c || !query) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     c->within_keys.clear();
     c->within_matches = 0;
     c->within_launches = 0;
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    if (radius != radius) return vg_fail(VG_ERR_INVALID, "vg_scan_within: the radius is NaN");
-    if (c->n_rows == 0) return VG_OK;
+    if (radius != radius) return vg_fail(VG_ERR_INVALID, "%s: the radius is NaN", f.who);
+    if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (c->n_rows == 0 || (f.masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
     HIP_TRY(hipSetDevice(c->device));
     c->enqueued = false;                                     // (the pinned key buffer is this scan's landing zone now)
     const float r = vg_within_radius(radius);
@@ -155,13 +160,13 @@ extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, doubl
     memset(c->h_query, 0, (size_t)c->stride);
     memcpy(c->h_query, query, (size_t)c->dim * c->es);
     HIP_TRY(hipMemcpyAsync(c->d_query, c->h_query, (size_t)c->stride, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_within(c, metric, r, cap)) != VG_OK) return rc;
+    if ((rc = launch_within(c, f, metric, r, cap)) != VG_OK) return rc;
     int64_t count = (int64_t)c->h_keys[0];
     if (count > cap) {                                       // overflow: the count IS the size needed - grow, launch once more
         cap = count;
         if ((rc = ensure_within_buffer(c, cap)) != VG_OK) return rc;
-        if ((rc = launch_within(c, metric, r, cap)) != VG_OK) return rc;
-        if ((int64_t)c->h_keys[0] != count) return vg_fail(VG_ERR_HIP, "vg_scan_within: two launches counted %lld and %lld rows", (long long)count, (long long)c->h_keys[0]);
+        if ((rc = launch_within(c, f, metric, r, cap)) != VG_OK) return rc;
+        if ((int64_t)c->h_keys[0] != count) return vg_fail(VG_ERR_HIP, "%s: two launches counted %lld and %lld rows", f.who, (long long)count, (long long)c->h_keys[0]);
     }
     vg_collect_timing(c);
     bool pending = false;
@@ -172,6 +177,12 @@ extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, doubl
     if (out_matches) *out_matches = count;
     if (out_held) *out_held = (int64_t)c->within_keys.size();
     return VG_OK;
+}
+
+extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
+                              int64_t *out_held) {
+    const VgWithinForm form = {"vg_scan_within", vg_pick_scan<WithinFamily>, false};
+    return vg_within_run(c, form, metric, query, radius, limit, out_matches, out_held);
 }
 
 extern "C" int vg_scan_within_keys(const vg_corpus *c, int64_t first, int64_t n, uint64_t *out_keys) {

@@ -890,15 +890,19 @@ static int fetch_within(const vg_shards *s, const char *who, const std::vector<v
     return VG_OK;
 }
 
-extern "C" int vg_shards_scan_within(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
-                                     int64_t *out_held) {
-    if (!s || !query) return fail(VG_ERR_INVALID, "vg_shards_scan_within: NULL argument");
-    if (s->S == 1) return vg_scan_within(s->sh[0], metric, query, radius, limit, out_matches, out_held);
+// the single form, unmasked or masked (every shard over its own bits; a shard whose share of the mask is empty launches nothing)
+static int shards_within(vg_shards *s, bool masked, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
+                         int64_t *out_held) {
+    const char *who = masked ? "vg_shards_scan_within_masked" : "vg_shards_scan_within";
+    auto scan = masked ? vg_scan_within_masked : vg_scan_within;
     if (out_matches) *out_matches = 0;
     if (out_held) *out_held = 0;
+    if (!s || !query) return fail(VG_ERR_INVALID, (std::string(who) + ": NULL argument").c_str());
+    if (s->S == 1) return scan(s->sh[0], metric, query, radius, limit, out_matches, out_held);
     s->within_hits.clear();
+    if (masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_within_masked: no row mask set");
     std::vector<int64_t> matches((size_t)s->S, 0), held((size_t)s->S, 0);
-    int rc = for_each_shard(s, [&](int i) { return vg_scan_within(s->sh[(size_t)i], metric, query, radius, limit, &matches[(size_t)i], &held[(size_t)i]); });
+    int rc = for_each_shard(s, [&](int i) { return scan(s->sh[(size_t)i], metric, query, radius, limit, &matches[(size_t)i], &held[(size_t)i]); });
     if (rc != VG_OK) return rc;
     int64_t total = 0;
     rc = merge_within(s, matches.data(), held.data(), 1, limit,
@@ -907,6 +911,16 @@ extern "C" int vg_shards_scan_within(vg_shards *s, int metric, const void *query
     if (out_matches) *out_matches = total;
     if (out_held) *out_held = (int64_t)s->within_hits.size();
     return VG_OK;
+}
+
+extern "C" int vg_shards_scan_within(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
+                                     int64_t *out_held) {
+    return shards_within(s, false, metric, query, radius, limit, out_matches, out_held);
+}
+
+extern "C" int vg_shards_scan_within_masked(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
+                                            int64_t *out_held) {
+    return shards_within(s, true, metric, query, radius, limit, out_matches, out_held);
 }
 
 extern "C" int vg_shards_scan_within_fetch(const vg_shards *s, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
@@ -928,17 +942,21 @@ extern "C" int vg_shards_within_last_launches(const vg_shards *s) {
     return most;
 }
 
-// ---- batch range scans: every shard answers all nq queries (vg_scan_within_batch: same radii, same limit), then merge_within per query
-extern "C" int vg_shards_scan_within_batch(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
-                                           int64_t *out_matches, int64_t *out_held) {
+// ---- batch range scans: every shard answers all nq queries (vg_scan_within_batch[_masked]: same radii, same limit), then merge_within per query
+static int shards_within_batch(vg_shards *s, bool masked, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                               int64_t *out_matches, int64_t *out_held) {
+    const char *who = masked ? "vg_shards_scan_within_batch_masked" : "vg_shards_scan_within_batch";
+    const char *inner = masked ? "vg_scan_within_batch_masked" : "vg_scan_within_batch";
+    auto scan = masked ? vg_scan_within_batch_masked : vg_scan_within_batch;
     for (int q = 0; q < nq; ++q) { if (out_matches) out_matches[q] = 0; if (out_held) out_held[q] = 0; }
-    if (!s || !queries || !radii) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch: NULL argument");
-    if (s->S == 1) return vg_scan_within_batch(s->sh[0], metric, queries, nq, radii, limit, out_matches, out_held);
+    if (!s || !queries || !radii) return fail(VG_ERR_INVALID, (std::string(who) + ": NULL argument").c_str());
+    if (s->S == 1) return scan(s->sh[0], metric, queries, nq, radii, limit, out_matches, out_held);
     s->within_batch_hits.clear();
-    if (nq < 1) return fail(VG_ERR_INVALID, "vg_scan_within_batch: nq must be at least 1");
+    if (nq < 1) return fail(VG_ERR_INVALID, (std::string(inner) + ": nq must be at least 1").c_str());
+    if (masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_within_batch_masked: no row mask set");
     std::vector<int64_t> matches((size_t)s->S * nq, 0), held((size_t)s->S * nq, 0);
     int rc = for_each_shard(s, [&](int i) {
-        return vg_scan_within_batch(s->sh[(size_t)i], metric, queries, nq, radii, limit, &matches[(size_t)i * nq], &held[(size_t)i * nq]);
+        return scan(s->sh[(size_t)i], metric, queries, nq, radii, limit, &matches[(size_t)i * nq], &held[(size_t)i * nq]);
     });
     if (rc != VG_OK) return rc;
     s->within_batch_hits.resize((size_t)nq);
@@ -954,6 +972,16 @@ extern "C" int vg_shards_scan_within_batch(vg_shards *s, int metric, const void 
     return VG_OK;
 }
 
+extern "C" int vg_shards_scan_within_batch(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                           int64_t *out_matches, int64_t *out_held) {
+    return shards_within_batch(s, false, metric, queries, nq, radii, limit, out_matches, out_held);
+}
+
+extern "C" int vg_shards_scan_within_batch_masked(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
+                                                  int64_t *out_matches, int64_t *out_held) {
+    return shards_within_batch(s, true, metric, queries, nq, radii, limit, out_matches, out_held);
+}
+
 extern "C" int vg_shards_scan_within_batch_fetch(const vg_shards *s, int query, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
     if (!s) return fail(VG_ERR_INVALID, "vg_shards_scan_within_batch_fetch: NULL argument");
     if (s->S == 1) return vg_scan_within_batch_fetch(s->sh[0], query, first, n, out_rowids, out_dist);
@@ -964,6 +992,11 @@ extern "C" int vg_shards_scan_within_batch_fetch(const vg_shards *s, int query, 
 extern "C" int vg_shards_within_batch_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
     if (!s) return fail(VG_ERR_INVALID, "vg_shards_within_batch_plan: NULL argument");
     return vg_within_batch_plan(s->sh[0], metric, out_queries_per_pass, out_lpr, out_u);
+}
+
+extern "C" int vg_shards_within_batch_masked_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    if (!s) return fail(VG_ERR_INVALID, "vg_shards_within_batch_masked_plan: NULL argument");
+    return vg_within_batch_masked_plan(s->sh[0], metric, out_queries_per_pass, out_lpr, out_u);
 }
 
 extern "C" int vg_shards_within_batch_set_initial_capacity(vg_shards *s, int64_t keys_per_query) {

@@ -72,6 +72,8 @@ enum { COL_TBL = 0, COL_VECTOR = 1, COL_K = 2, COL_MEMIDX = 3, COL_ID = 4, COL_D
 #include "vext_masked.inc"
 #include "vext_batch_masked.inc"
 #include "vext_batch_within.inc"
+#include "vext_within_masked.inc"
+#include "vext_batch_within_masked.inc"
 
 /* ------------------------------------------------------------------------------------------------ registration */
 
@@ -197,5 +199,11 @@ int sqlite3_vector_init(sqlite3 *db, char **pzErrMsg, const sqlite3_api_routines
     /* range scans for a whole batch of queries, a radius each (vext_batch_within.inc) */
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_within", &full_bwithin_module, ctx);
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_within", &quant_bwithin_module, ctx);
+    /* masked range scans: every row within a distance among those a filter names, one query (vext_within_masked.inc) or a batch
+     * (vext_batch_within_masked.inc) */
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_within_filtered", &full_wmasked_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_within_filtered", &quant_wmasked_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_within_filtered", &full_bwmasked_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_within_filtered", &quant_bwmasked_module, ctx);
     return rc;
 }
