@@ -272,6 +272,49 @@ int     vg_scan_within_masked(vg_corpus *c, int metric, const void *query, doubl
 int     vg_scan_within_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                     int64_t *out_matches, int64_t *out_held);
 
+/* ---- paged scans: the next k rows behind a (distance, rowid) cursor ("search after"; the reference's surface has LIMIT k OFFSET m,
+ * a top-(m + k) scan) ----
+ * A cursor is (after_dist, after_rowid): the distance and rowid of the last row of the previous page.  The row at scan position p
+ * with distance d - the float vg_scan_distances reports for it, bit for bit - is BEHIND the cursor iff d < +Inf (NaN / +Inf never
+ * enter, -Inf is a legal distance) and ((double)d > after_dist, or (double)d == after_dist and rowid(p) > after_rowid).  Returned:
+ * the first k such rows in ascending (distance, scan position) order whatever the handle's tie_order, fewer when fewer qualify.
+ * 1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below).  Pages are exact when the cut falls inside a run of equal distances.
+ * (-INFINITY, INT64_MIN) is "from the start"; a NaN distance: VG_ERR_INVALID; +Inf or a distance above FLT_MAX: *out_count = 0 without
+ * a launch; -0.0 is 0.0; after_dist need not be a float (a midpoint between two held distances is valid).  The rowid form needs
+ * ascending rowids (implicit ones are), as vg_corpus_set_mask_rowids does: VG_ERR_UNSUPPORTED otherwise.  rowid(p) > after_rowid is
+ * then p >= P, P = rows held with rowid <= after_rowid (a lower bound, not a find): the cursor's row need not exist any more, a page
+ * taken after it was deleted continues where it should.
+ * How: every kernel ranks rows by the key sortable(distance) << 32 | scan position; the host turns the cursor into the smallest key
+ * behind it (vg_after_floor, vectorgpu_diag.h) and the kernel admits a key iff key >= floor - one 64-bit compare in the offer of the
+ * plain (or the masked) streaming kernel.  Timings not measured yet.
+ * The _keys forms take the cursor as after_key, the LAST key of the previous page (floor = after_key + 1), and return packed keys with
+ * positions local to this corpus; they work for any rowid layout; after_key = VG_KEY_EMPTY: VG_ERR_INVALID; 0 starts in front of every row.
+ * The _masked forms read the handle's row mask (vg_corpus_set_mask_*): the same contract restricted to the allowed rows (the
+ * cursor's row need not be allowed); no mask set: VG_ERR_INVALID; an empty mask: count 0 without a launch.
+ * The batch forms answer nq queries (row-major nq x dim, host), a cursor each (after_dists / after_rowids / after_keys hold nq
+ * values); out_rowids / out_dist / out_keys are nq x k, out_counts nq, the slots of query i behind out_counts[i] are NOT written.
+ * Query i's answer is the single form's for its query and cursor, bit for bit, for every element type - a cursor taken from a
+ * single page or from vg_scan_distances is valid in the batch form and the reverse.  uint8 / int8 rows of a register-resident shape,
+ * and f32 rows whose multi-query launch shape is the plain scan's (the same summation order), share every row load of a pass among 4
+ * (or 2) queries (vg_scan_multi_after.h - the multi-query scan, not the matrix-core filters, whose thresholds assume an unrestricted
+ * top-k); every other f32 shape, f16 / bf16 and long rows take one single paged scan per query. */
+int     vg_scan_topk_after(vg_corpus *c, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
+                           int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_scan_topk_after_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t after_key,
+                                uint64_t *out_keys, int *out_count);
+int     vg_scan_topk_after_masked(vg_corpus *c, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
+                                  int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_scan_topk_after_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t after_key,
+                                       uint64_t *out_keys, int *out_count);
+int     vg_scan_topk_batch_after(vg_corpus *c, int metric, const void *queries, int nq, int k, const double *after_dists,
+                                 const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_scan_topk_batch_after_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint64_t *after_keys,
+                                      uint64_t *out_keys, int *out_counts);
+int     vg_scan_topk_batch_after_masked(vg_corpus *c, int metric, const void *queries, int nq, int k, const double *after_dists,
+                                        const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_scan_topk_batch_after_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint64_t *after_keys,
+                                             uint64_t *out_keys, int *out_counts);
+
 /* nq queries at once (row-major nq x dim, host).  out_rowids / out_dist are nq x k, out_counts nq.
  * f32 corpora, k <= 32, rows <= 512 floats, metric DOT / COSINE / L2 / SQUARED_L2: one pass over the corpus on the
  * matrix cores (Q x C^T tiles feed per-query candidate lists; L2 survivors are re-evaluated with the direct formula);
@@ -369,6 +412,26 @@ int     vg_shards_scan_within_masked(vg_shards *s, int metric, const void *query
                                      int64_t *out_matches, int64_t *out_held);
 int     vg_shards_scan_within_batch_masked(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                            int64_t *out_matches, int64_t *out_held);
+/* the paged scans over every shard: the cursor is one over GLOBAL scan order - each shard gets the floor over its own positions
+ * ("local rows of this shard in front of global position P", by the block-cyclic map) and the lists merge by (distance, GLOBAL scan
+ * position): the rowids, order and distance bits of one corpus holding all rows.  Same contracts.  The _keys forms take and return keys
+ * over GLOBAL positions (sortable(distance) << 32 | global position): VG_ERR_UNSUPPORTED for 2^32 rows or more. */
+int     vg_shards_scan_topk_after(vg_shards *s, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
+                                  int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_shards_scan_topk_after_keys(vg_shards *s, int metric, const void *query, int k, uint64_t after_key,
+                                       uint64_t *out_keys, int *out_count);
+int     vg_shards_scan_topk_after_masked(vg_shards *s, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
+                                         int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_shards_scan_topk_after_masked_keys(vg_shards *s, int metric, const void *query, int k, uint64_t after_key,
+                                              uint64_t *out_keys, int *out_count);
+int     vg_shards_scan_topk_batch_after(vg_shards *s, int metric, const void *queries, int nq, int k, const double *after_dists,
+                                        const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_shards_scan_topk_batch_after_keys(vg_shards *s, int metric, const void *queries, int nq, int k, const uint64_t *after_keys,
+                                             uint64_t *out_keys, int *out_counts);
+int     vg_shards_scan_topk_batch_after_masked(vg_shards *s, int metric, const void *queries, int nq, int k, const double *after_dists,
+                                               const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_shards_scan_topk_batch_after_masked_keys(vg_shards *s, int metric, const void *queries, int nq, int k, const uint64_t *after_keys,
+                                                    uint64_t *out_keys, int *out_counts);
 int     vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative);
 int     vg_shards_quantize_rows(vg_shards *s, float scale, float offset, int qtype, int64_t row0, int64_t n_rows, uint8_t *out_host);
 

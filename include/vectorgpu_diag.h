@@ -56,6 +56,13 @@ int vg_batch_q8_status(const vg_corpus *c);
  * lane (the single masked scan's shape for the fallback; 64 / 0 for the long-row kernel).  Pure host logic.  Every pass of a masked
  * batch takes one slot of the profiling ring (vg_set_profiling / vg_profile_mean_ms: kernel and merge time per pass). */
 int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
+/* the floor key of a paged scan (vg_scan_topk_after, vectorgpu.h): the smallest key behind a cursor whose distance is after_dist, when
+ * the rows at scan positions < first_pos_behind are not behind it at that distance (P = rows held with rowid <= after_rowid).  f = the
+ * smallest float >= after_dist (the double rounded towards +Inf, -0.0 normalised to 0.0): floor = key(f, first_pos_behind) when
+ * (double)f == after_dist, key(f, 0) otherwise; key(d, p) = sortable(d) << 32 | p.  A row is behind the cursor iff its distance is
+ * below +Inf and its key >= floor.  *out_empty = 1 (floor = VG_KEY_EMPTY) when nothing can be: after_dist = +Inf or above FLT_MAX.
+ * NaN: VG_ERR_INVALID.  Pure host arithmetic, no device. */
+int vg_after_floor(double after_dist, uint32_t first_pos_behind, uint64_t *out_floor, int *out_empty);
 
 /* kernel milliseconds (HIP events on the corpus stream) and rows of the corpus' last vg_corpus_minmax (which = 0) /
  * vg_corpus_quantize_rows (1) pass, and - while profiling is on - of the last int8 shadow-copy pass of the filter scans (2) */

@@ -208,7 +208,15 @@ def _load():
         "vg_shards_within_batch_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_shards_within_batch_set_initial_capacity": (i32, [vp, i64]),
         "vg_shards_within_batch_last_launches": (i32, [vp]),
+        # paged scans: the next k rows behind a (distance, rowid) cursor / behind the last key of the previous page
+        "vg_after_floor": (i32, [C.c_double, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(i32)]),
     }
+    for pre in ("vg_scan_topk_", "vg_shards_scan_topk_"):
+        for m in ("", "_masked"):
+            sig[pre + "after" + m] = (i32, [vp, i32, vp, i32, C.c_double, i64, vp, vp, C.POINTER(i32)])
+            sig[pre + "after" + m + "_keys"] = (i32, [vp, i32, vp, i32, C.c_uint64, vp, C.POINTER(i32)])
+            sig[pre + "batch_after" + m] = (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp])
+            sig[pre + "batch_after" + m + "_keys"] = (i32, [vp, i32, vp, i32, i32, vp, vp, vp])
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
         fn.restype = res
@@ -267,6 +275,88 @@ def _scan_topk_batch_masked(fn, h, metric, queries, k):
     cnt = np.zeros(max(nq, 1), dtype=np.int32)
     _check(fn(h, metric, _ptr(queries), nq, k, _ptr(ids), _ptr(dist), _ptr(cnt)))
     return ids, dist, cnt[:nq]
+
+
+AFTER_START = (float("-inf"), -(1 << 63))          # the cursor in front of every row
+
+
+def after_floor(after_dist, first_pos_behind):
+    """(floor key, empty?) of a paged scan's cursor (vg_after_floor) - host arithmetic only, no device"""
+    floor, empty = C.c_uint64(0), C.c_int(0)
+    _check(lib().vg_after_floor(float(after_dist), int(first_pos_behind), C.byref(floor), C.byref(empty)))
+    return floor.value, bool(empty.value)
+
+
+def _after_name(obj, batch, masked, keys):
+    return ("vg_shards_scan_topk_" if isinstance(obj, Shards) else "vg_scan_topk_") + ("batch_after" if batch else "after") + \
+        ("_masked" if masked else "") + ("_keys" if keys else "")
+
+
+def _scan_topk_after(obj, metric, query, k, after, masked):
+    query = np.ascontiguousarray(query)
+    d, r = AFTER_START if after is None else after
+    ids = np.zeros(max(k, 1), dtype=np.int64)
+    dist = np.zeros(max(k, 1), dtype=np.float64)
+    cnt = C.c_int(0)
+    _check(getattr(lib(), _after_name(obj, False, masked, False))(obj.h, metric, _ptr(query), k, float(d), int(r), _ptr(ids), _ptr(dist), C.byref(cnt)))
+    return ids[:cnt.value], dist[:cnt.value]
+
+
+def _scan_topk_after_keys(obj, metric, query, k, after_key, masked):
+    query = np.ascontiguousarray(query)
+    keys = np.zeros(max(k, 1), dtype=np.uint64)
+    cnt = C.c_int(0)
+    _check(getattr(lib(), _after_name(obj, False, masked, True))(obj.h, metric, _ptr(query), k, int(after_key or 0), _ptr(keys), C.byref(cnt)))
+    return keys[:cnt.value]
+
+
+def _scan_topk_batch_after(obj, metric, queries, k, after, masked):
+    queries = np.ascontiguousarray(queries)
+    nq = queries.shape[0]
+    cur = [AFTER_START] * nq if after is None else [AFTER_START if a is None else a for a in after]
+    if len(cur) != nq:
+        raise ValueError("one cursor per query")
+    ad = np.array([float(a[0]) for a in cur] or [0.0], dtype=np.float64)
+    ar = np.array([int(a[1]) for a in cur] or [0], dtype=np.int64)
+    ids = np.zeros((nq, max(k, 1)), dtype=np.int64)
+    dist = np.zeros((nq, max(k, 1)), dtype=np.float64)
+    cnt = np.zeros(max(nq, 1), dtype=np.int32)
+    _check(getattr(lib(), _after_name(obj, True, masked, False))(obj.h, metric, _ptr(queries), nq, k, _ptr(ad), _ptr(ar), _ptr(ids), _ptr(dist), _ptr(cnt)))
+    return ids, dist, cnt[:nq]
+
+
+def _scan_topk_batch_after_keys(obj, metric, queries, k, after_keys, masked):
+    queries = np.ascontiguousarray(queries)
+    nq = queries.shape[0]
+    ak = np.zeros(max(nq, 1), dtype=np.uint64) if after_keys is None else np.ascontiguousarray(after_keys, dtype=np.uint64)
+    if after_keys is not None and len(ak) != nq:
+        raise ValueError("one cursor key per query")
+    keys = np.zeros((nq, max(k, 1)), dtype=np.uint64)
+    cnt = np.zeros(max(nq, 1), dtype=np.int32)
+    _check(getattr(lib(), _after_name(obj, True, masked, True))(obj.h, metric, _ptr(queries), nq, k, _ptr(ak), _ptr(keys), _ptr(cnt)))
+    return keys, cnt[:nq]
+
+
+class _PagedScans:
+    """paged scans ("search after"), shared by Corpus and Shards: the next k rows behind a cursor, in ascending (distance, scan
+    position) order; masked=True reads the handle's row mask"""
+
+    def scan_topk_after(self, metric, query, k, after=None, masked=False):
+        """the next k rows behind `after` = (distance, rowid) of the previous page's last row (None: from the start): (rowids, distances)"""
+        return _scan_topk_after(self, metric, query, k, after, masked)
+
+    def scan_topk_after_keys(self, metric, query, k, after_key=None, masked=False):
+        """the same with the cursor as the previous page's last packed key (None: from the start), returning packed keys; any rowid layout"""
+        return _scan_topk_after_keys(self, metric, query, k, after_key, masked)
+
+    def scan_topk_batch_after(self, metric, queries, k, after=None, masked=False):
+        """scan_topk_after for every row of `queries`, a cursor each (`after`: a list of (distance, rowid) pairs or None entries):
+        (rowids [nq, k], distances [nq, k], counts [nq]); slots behind a query's count stay zero"""
+        return _scan_topk_batch_after(self, metric, queries, k, after, masked)
+
+    def scan_topk_batch_after_keys(self, metric, queries, k, after_keys=None, masked=False):
+        """the same with one cursor key per query: (keys [nq, k], counts [nq])"""
+        return _scan_topk_batch_after_keys(self, metric, queries, k, after_keys, masked)
 
 
 def _wb_prefix(obj):
@@ -356,7 +446,7 @@ def _set_mask(obj, prefix, rows, bits, positions, rowids):
     return int(getattr(L, prefix + "_mask_count")(obj.h))
 
 
-class Corpus:
+class Corpus(_PagedScans):
     """One HBM-resident corpus shard (opaque vg_corpus handle)."""
 
     def __init__(self, vtype, dim, device=0, capacity=0):
@@ -675,7 +765,7 @@ def device_memory(device=0):
     return f.value, t.value
 
 
-class Shards:
+class Shards(_PagedScans):
     """One logical corpus dealt block-cyclically over several devices of this process (opaque vg_shards handle)."""
 
     def __init__(self, vtype, dim, devices, block_rows=0):

@@ -152,8 +152,8 @@ extern "C" int vg_corpus_create(int device, int vtype, int dim, int64_t capacity
     c->max_blocks = c->cu_count * 8;
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipMalloc(&c->d_query, (size_t)c->stride)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_query, (size_t)c->stride)) != hipSuccess ||
+        (e = hipMalloc(&c->d_query, (size_t)c->stride + 16)) != hipSuccess ||      // (+ 16: a paged scan's floor key rides behind the query)
+        (e = hipHostMalloc(&c->h_query, (size_t)c->stride + 16)) != hipSuccess ||
         (e = hipMalloc(&c->d_cand, (size_t)c->max_blocks * VG_WAVE * sizeof(uint64_t))) != hipSuccess ||
         (e = hipMalloc(&c->d_keys, VG_WAVE * sizeof(uint64_t))) != hipSuccess ||
         (e = hipHostMalloc(&c->h_keys, VG_WAVE * sizeof(uint64_t))) != hipSuccess) {

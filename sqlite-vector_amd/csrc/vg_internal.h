@@ -293,6 +293,26 @@ struct VgWithinForm { const char *who; vg_pick_scan_fn_t pick; bool masked; };
 int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                   int64_t *out_held);
 scan_fn_t vg_pick_multi_within_masked(int vtype, int acc, int U, int NQ);   // vg_multi_within_masked.hip: the masked batch range scan's kernel table
+// ---- the fused top-k scan of a variant (k <= 64, ascending (distance, scan position) order), shared by the masked and the paged
+// scans: the kernel table, whether ScanArgs.mask is set and a mask required, whether ScanArgs.floor is, whose name errors carry.
+// vg_fused_run (vg_scan_masked.hip): one query; `floor` = the smallest key admitted (after forms).  vg_fused_batch_run
+// (vg_multi_masked.hip): nq queries, `floors` = a key each (after forms, nullptr otherwise); the fallback of a shape without a
+// multi-query form is nq calls of vg_fused_run with the single form.
+typedef scan_fn_t (*vg_pick_multi_fn_t)(int vtype, int acc, int U, int NQ);
+scan_fn_t vg_pick_scan_masked(int vtype, int acc, int U, bool long_rows);   // vg_scan_masked.hip: the masked single scan's kernel table
+scan_fn_t vg_pick_scan_after(int vtype, int acc, int U, bool long_rows);    // vg_scan_after.hip: the paged single scans' tables,
+scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows);   // ... all rows / the allowed rows
+struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; };
+struct VgFusedBatchForm { const char *who; vg_pick_multi_fn_t pick; VgFusedForm single; };
+int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count);
+int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                       uint64_t *out_keys, int *out_counts);
+// ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): the floor-key forms behind the C ABI, what the shards call per shard.
+// Floors are keys over positions LOCAL to the corpus; a floor of VG_KEY_EMPTY admits nothing (no launch in the single form).
+int vg_after_floor_run(vg_corpus *c, bool masked, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count);
+int vg_after_floor_batch_run(vg_corpus *c, bool masked, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                             uint64_t *out_keys, int *out_counts);
+int64_t vg_corpus_rows_upto_rowid(const vg_corpus *c, int64_t rowid);   // vg_scan_after.hip: rows held with rowid <= `rowid`; -2: rowids not ascending
 // ---- range-scan results (vg_scan_within.hip), shared by the single and the batch form
 float vg_within_radius(double radius);                              // the largest float not above the radius
 // `count` keys at dev_keys -> *dst, ascending and cut to `limit`.  Up to VG_WITHIN_HOST_SORT keys: the copy is only enqueued and

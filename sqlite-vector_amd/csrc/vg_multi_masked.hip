@@ -1,4 +1,6 @@
 // vg_multi_masked.hip - masked batch scans: the k nearest ALLOWED rows for many queries (vg_scan_topk_batch_masked, include/vectorgpu.h).
+// Also the home of vg_fused_batch_run, the form-driven batch routine the paged batch scans (vg_multi_after.hip) share with it: the
+// fused_* / launch_fused_* routines below serve every VgFusedBatchForm, masked or not.
 //
 // Host side of the masked multi-query scan (vg_scan_multi_masked.h): kernel table, launch, and the batch entry points.  The plan is
 // the multi-query scan's (vg_multi_plan: 4 queries per pass with up to 3 chunks per lane, 2 with 4 or 6; f32 / uint8 / int8 rows that
@@ -15,10 +17,10 @@ struct MultiMaskedFamily {
 };
 
 // (queries per pass, launch shape, kernel) of the masked multi-query scan; 0 queries per pass: the fallback serves the shape
-static int mm_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn) {
+static int fused_multi_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn, vg_pick_multi_fn_t pick = vg_pick_multi<MultiMaskedFamily>) {
     const int NQ = vg_multi_plan(c, metric, s);
     if (NQ == 0) return 0;
-    scan_fn_t f = vg_pick_multi<MultiMaskedFamily>(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
+    scan_fn_t f = pick(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
     if (fn) *fn = f;
     return f ? NQ : 0;
 }
@@ -27,7 +29,7 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
     if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     VgShape s{};
-    const int NQ = mm_plan(c, metric, &s, nullptr);
+    const int NQ = fused_multi_plan(c, metric, &s, nullptr);
     if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single masked scan's
     if (out_queries_per_pass) *out_queries_per_pass = NQ;
     if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
@@ -36,13 +38,15 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
 }
 
 // NQ queries (zero-padded rows of the corpus stride, back to back at dev_queries) against the allowed rows in ONE pass; dev_cand:
-// NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on the corpus stream.
-static int launch_multi_masked(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_queries, int k,
-                               uint64_t *dev_cand, uint64_t *dev_out_keys) {
+// NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on the corpus stream.  One launcher for every form
+// (VgFusedBatchForm, vg_internal.h): the masked batch, and the paged batches of vg_multi_after.hip (dev_floors: NQ keys).
+static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s,
+                               const uint8_t *dev_queries, const uint64_t *dev_floors, int k, uint64_t *dev_cand, uint64_t *dev_out_keys) {
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);
     ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_queries, k);
     a.cand = dev_cand;
-    a.mask = c->d_mask;
+    if (f.single.masked) a.mask = c->d_mask;
+    if (f.single.after) a.floor = dev_floors;
     const size_t smem = std::max<size_t>((size_t)NQ * c->nch * 16, (size_t)VG_PUBLISH_LDS_BYTES);
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);          // one slot of the profiling ring per pass
     if (evs) hipEventRecord(evs[0], c->stream);
@@ -51,20 +55,22 @@ static int launch_multi_masked(vg_corpus *c, int metric, scan_fn_t fn, int NQ, c
     if (evs) hipEventRecord(evs[2], c->stream);
     rc = vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
-    if (rc != 0) return vg_fail(VG_ERR_HIP, "vg_scan_topk_batch_masked: merge launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (rc != 0) return vg_fail(VG_ERR_HIP, "%s: merge launch failed: %s", f.who, hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipGetLastError());
     return VG_OK;
 }
 
 // queries go up in slices of this many (a multiple of every queries-per-pass): the device staging area does not grow with the batch
-#define VG_BMASK_SLICE 256
+#define VG_FUSED_SLICE 256
 
 // nq queries, NQ per pass; every pass of every slice is enqueued back to back on the corpus stream, one wait at the end
-static int batch_masked_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries, int nq, int k,
-                              uint64_t *out_keys, int *out_counts) {
+static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries,
+                              int nq, const uint64_t *floors, int k, uint64_t *out_keys, int *out_counts) {
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
-    const int slice = std::min(nq_pad, VG_BMASK_SLICE);
-    const size_t qbytes = (size_t)slice * c->stride, keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
+    const int slice = std::min(nq_pad, VG_FUSED_SLICE);
+    // (an after form: the slice's floor keys sit behind its queries in d_bq and go up with them; a pad slot admits nothing)
+    const size_t fl_off = (size_t)slice * c->stride;
+    const size_t qbytes = fl_off + (f.single.after ? (size_t)slice * sizeof(uint64_t) : 0), keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
     if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
                                 HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
     if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
@@ -74,13 +80,18 @@ static int batch_masked_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, co
     std::vector<uint8_t> hq((size_t)nq_pad * c->stride, 0);
     const size_t row_bytes = (size_t)c->dim * c->es;
     for (int i = 0; i < nq; ++i) memcpy(hq.data() + (size_t)i * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
+    std::vector<uint64_t> hf(f.single.after ? (size_t)nq_pad : 0, VG_KEY_EMPTY);
+    if (f.single.after) for (int i = 0; i < nq; ++i) hf[(size_t)i] = floors[i];
     int rc = VG_OK;
     for (int q0 = 0; q0 < nq_pad && rc == VG_OK; q0 += slice) {
         const int nqs = std::min(slice, nq_pad - q0);
         hipError_t e = hipMemcpyAsync(c->d_bq, hq.data() + (size_t)q0 * c->stride, (size_t)nqs * c->stride, hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) { rc = vg_fail(VG_ERR_HIP, "vg_scan_topk_batch_masked: query upload failed: %s", hipGetErrorString(e)); break; }
+        if (e == hipSuccess && f.single.after)
+            e = hipMemcpyAsync((uint8_t *)c->d_bq + fl_off, hf.data() + q0, (size_t)nqs * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { rc = vg_fail(VG_ERR_HIP, "%s: query upload failed: %s", f.who, hipGetErrorString(e)); break; }
         for (int g = 0; g < nqs && rc == VG_OK; g += NQ)
-            rc = launch_multi_masked(c, metric, fn, NQ, s, (const uint8_t *)c->d_bq + (size_t)g * c->stride, k, c->d_cand,
+            rc = launch_fused_multi(c, f, metric, fn, NQ, s, (const uint8_t *)c->d_bq + (size_t)g * c->stride,
+                                     reinterpret_cast<const uint64_t *>((const uint8_t *)c->d_bq + fl_off) + g, k, c->d_cand,
                                      c->d_bkeys + (size_t)(q0 + g) * 64);
     }
     if (rc != VG_OK) { hipStreamSynchronize(c->stream); return rc; }      // (hq must outlive what was enqueued)
@@ -88,7 +99,7 @@ static int batch_masked_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, co
     hipError_t e = hipMemcpyAsync(keys.data(), c->d_bkeys, (size_t)nq * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
     if (e != hipSuccess || e2 != hipSuccess)
-        return vg_fail(VG_ERR_HIP, "vg_scan_topk_batch_masked: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        return vg_fail(VG_ERR_HIP, "%s: %s", f.who, hipGetErrorString(e != hipSuccess ? e : e2));
     vg_collect_timing(c);
     for (int i = 0; i < nq; ++i) {
         int cnt = 0;
@@ -104,31 +115,38 @@ static int batch_masked_multi(vg_corpus *c, int metric, scan_fn_t fn, int NQ, co
 }
 
 // packed keys (distance image << 32 | position local to this corpus), ascending, nq x k: the form a multi-shard caller merges.
-// Slots behind out_counts[i] are not written.
-extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
-                                              int *out_counts) {
-    if (!c || !queries || !out_counts) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: NULL argument");
-    if (nq < 1) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: nq must be at least 1");
+// Slots behind out_counts[i] are not written.  `floors`: a key per query, read by an after form only.
+int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                       uint64_t *out_keys, int *out_counts) {
+    if (!c || !queries || !out_counts || (f.single.after && !floors)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
+    if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", f.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (k < 1) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: k must be at least 1");
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_batch_masked: k must be in 1..%d (masked scans use the fused list only)", VG_MAX_FUSED_K);
-    if (!out_keys) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: NULL output");
+    if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.masked ? "masked" : "paged");
+    if (!out_keys) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    if (c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: no row mask set");
-    if (c->mask_count == 0 || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
+    if (f.single.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if ((f.single.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     HIP_TRY(hipSetDevice(c->device));
     VgShape s{};
     scan_fn_t fn = nullptr;
-    const int NQ = mm_plan(c, metric, &s, &fn);
-    if (NQ == 0) {                                               // no multi-query form: the single masked scans, one by one
+    const int NQ = fused_multi_plan(c, metric, &s, &fn, f.pick);
+    if (NQ == 0) {                                               // no multi-query form: the single scans of the form, one by one
         const size_t row_bytes = (size_t)c->dim * c->es;
         for (int i = 0; i < nq; ++i) {
-            int rc = vg_scan_topk_masked_keys(c, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, out_keys + (size_t)i * k, &out_counts[i]);
+            int rc = vg_fused_run(c, f.single, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, floors ? floors[i] : 0ull,
+                                  out_keys + (size_t)i * k, &out_counts[i]);
             if (rc != VG_OK) return rc;
         }
         return VG_OK;
     }
-    return batch_masked_multi(c, metric, fn, NQ, s, queries, nq, k, out_keys, out_counts);
+    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, k, out_keys, out_counts);
+}
+
+extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
+                                              int *out_counts) {
+    const VgFusedBatchForm form = {"vg_scan_topk_batch_masked", vg_pick_multi<MultiMaskedFamily>, {"vg_scan_topk_masked", vg_pick_scan_masked, true, false}};
+    return vg_fused_batch_run(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts);
 }
 
 extern "C" int vg_scan_topk_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, int k, int64_t *out_rowids,

@@ -125,7 +125,10 @@ __device__ inline uint64_t vg_mask_bits(const uint64_t *mask, long long row0, in
 // (init_keys), the candidate stream (emit) and "top-k + store" (out_dist != nullptr with k > 0: the replay's prefix pass).  They are
 // instantiations of their own (vg_scan_ex.hip) because the plain kernels sit AT the 128-VGPR / 106-SGPR limit of 16 wavefronts per
 // CU: the few registers the extras take spilled f32 U = 8 and f16 U = 6, shapes the plain scans use.
-template <int VT, int ACC, int U, bool NT, bool EX = false, bool WITHIN = false, bool MASKED = false>
+// AFTER = true (vg_scan_after.hip, with MASKED false and true): paged scans - a row is offered only when its key is >= ScanArgs.floor[0],
+// the key just behind the caller's cursor.  One wave-uniform 64-bit value loaded before the loop and one compare in the offer; loops,
+// loads, arithmetic, lists, publish and merge are the plain / the masked kernel's.
+template <int VT, int ACC, int U, bool NT, bool EX = false, bool WITHIN = false, bool MASKED = false, bool AFTER = false>
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ VgListExtras ex;
@@ -149,6 +152,15 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
         if (k > 0) thr = vg_list_extras_init(&ex, a.init_keys, k, a.emit, a.emit_cap);
         if (a.emit_reset && blockIdx.x == 0 && threadIdx.x == 0) *a.emit_reset = 0ull;
     }
+    // after mode, f16 / bf16: these kernels sit AT the 106-SGPR limit and two more live scalar registers spilled into VGPR lanes; the
+    // floor stays in LDS instead (as VgListExtras does), published by the same barrier as the query, read back in the offer
+    constexpr bool AFTER_LDS = AFTER && (VT == T_F16 || VT == T_BF16);
+    const uint64_t *floor_lds = nullptr;
+    if constexpr (AFTER_LDS) {
+        __shared__ uint64_t floor_slot;
+        if (threadIdx.x == 0) floor_slot = a.floor[0];
+        floor_lds = &floor_slot;
+    }
     __syncthreads();
     uint4 q[U];
 #pragma unroll
@@ -157,7 +169,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
         q[u] = (c < a.nch) ? qs[c] : make_uint4(0u, 0u, 0u, 0u);
     }
     const typename Accum<VT, ACC>::QStat qstat = Accum<VT, ACC>::template query_stat<U>(q, lpr_log2);
-    const bool store_mode = (WITHIN || MASKED) ? false : EX ? ((a.out_dist != nullptr) && k == 0) : (a.out_dist != nullptr);
+    const bool store_mode = (WITHIN || MASKED || AFTER) ? false : EX ? ((a.out_dist != nullptr) && k == 0) : (a.out_dist != nullptr);
+    uint64_t floor_key = 0ull;                                        // after mode only: wave-uniform, scalar registers (f32 / uint8 / int8)
+    if constexpr (AFTER && !AFTER_LDS) floor_key = vg_uniform64(a.floor[0]);
     const bool store_too = EX && (a.out_dist != nullptr) && k != 0; // the reference replay's prefix pass: top-k + every distance
 
     // ---- loop over row batches, one batch prefetched.  Top-k mode: grid-stride (batch b, b + W, ...).  Store mode:
@@ -257,6 +271,14 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
                 in_line = 0;
                 line_row0 = (bcur + wstride) * rpb;
             }
+        } else if constexpr (AFTER && MASKED) {
+            const uint64_t key = vg_make_key(d, (uint32_t)row);
+            if constexpr (AFTER_LDS) floor_key = *reinterpret_cast<const volatile uint64_t *>(floor_lds);
+            vg_list_offer(key, owner && ((mbits >> rib) & 1ull) && (d < INFINITY) && (key >= floor_key), mine, thr, lane, k);
+        } else if constexpr (AFTER) {
+            const uint64_t key = vg_make_key(d, (uint32_t)row);
+            if constexpr (AFTER_LDS) floor_key = *reinterpret_cast<const volatile uint64_t *>(floor_lds);
+            vg_list_offer(key, owner && (d < INFINITY) && (key >= floor_key), mine, thr, lane, k);
         } else if constexpr (MASKED) {
             // a row whose bit is clear was computed with its batch and is simply not offered
             vg_list_offer(vg_make_key(d, (uint32_t)row), owner && ((mbits >> rib) & 1ull) && (d < INFINITY), mine, thr, lane, k);
@@ -352,7 +374,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 // the row is consumed in `S` slices of 64 x VG_LONG_U chunks with the accumulator carried across slices and the
 // query slice read from LDS (ds_read_b128) instead of living in VGPRs.  Same epilogue / top-k tail as above.
 #define VG_LONG_U 2
-template <int VT, int ACC, bool NT, bool WITHIN = false, bool MASKED = false>
+template <int VT, int ACC, bool NT, bool WITHIN = false, bool MASKED = false, bool AFTER = false>
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
@@ -366,6 +388,13 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
     uint4 *qs = reinterpret_cast<uint4 *>(smem);
     for (int c = threadIdx.x; c < nch_pad; c += VG_BLOCK)
         qs[c] = (c < a.nch) ? reinterpret_cast<const uint4 *>(a.query)[c] : make_uint4(0u, 0u, 0u, 0u);
+    constexpr bool AFTER_LDS = AFTER && (VT == T_F16 || VT == T_BF16);      // (see vg_scan_kernel: the floor in LDS for the half types)
+    const uint64_t *floor_lds = nullptr;
+    if constexpr (AFTER_LDS) {
+        __shared__ uint64_t floor_slot;
+        if (threadIdx.x == 0) floor_slot = a.floor[0];
+        floor_lds = &floor_slot;
+    }
     __syncthreads();
 
     // query statistics over the whole query (norm / special flags), folded slice by slice
@@ -384,7 +413,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
 
     uint64_t mine = VG_EMPTY_KEY, thr = VG_EMPTY_KEY;
     const int k = a.k;
-    const bool store_mode = (WITHIN || MASKED) ? false : (a.out_dist != nullptr);
+    const bool store_mode = (WITHIN || MASKED || AFTER) ? false : (a.out_dist != nullptr);
+    uint64_t floor_key = 0ull;                                      // after mode only (see vg_scan_kernel)
+    if constexpr (AFTER && !AFTER_LDS) floor_key = vg_uniform64(a.floor[0]);
     uint64_t *wqueue = reinterpret_cast<uint64_t *>(smem + a.store_lds_off) + wave * VG_WITHIN_QUEUE;   // within mode only (vg_within_offer)
     int wqueued = 0;
     const long long wstride = (long long)gridDim.x * VG_WAVES_PER_BLOCK;
@@ -442,6 +473,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
                 vg_within_offer(vg_make_key(d, (uint32_t)row), (lane == 0) && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
             } else if (store_mode) {
                 if (lane == 0) a.out_dist[row] = d;
+            } else if constexpr (AFTER) {                           // (AFTER && MASKED: a row whose bit is clear never gets here)
+                const uint64_t key = vg_make_key(d, (uint32_t)row);
+                if constexpr (AFTER_LDS) floor_key = *reinterpret_cast<const volatile uint64_t *>(floor_lds);
+                vg_list_offer(key, (lane == 0) && (d < INFINITY) && (key >= floor_key), mine, thr, lane, k);
             } else {
                 vg_list_offer(vg_make_key(d, (uint32_t)row), (lane == 0) && (d < INFINITY), mine, thr, lane, k);
             }

@@ -9,6 +9,8 @@
 //
 // Only the masked scans read the mask: vg_scan_topk_masked here, vg_scan_topk_batch_masked in vg_multi_masked.hip, and the masked range
 // scans (vg_scan_within_masked.hip, vg_multi_within.hip).  Order: ascending (distance, scan position) whatever the handle's tie_order.
+// Also the home of vg_fused_run / launch_fused, the form-driven single-query routine the paged scans (vg_scan_after.hip) share with
+// the masked scan: it serves every VgFusedForm, masked or not.
 #include "vg_internal.h"
 
 #include "vg_scan.h"
@@ -85,20 +87,24 @@ extern "C" int64_t vg_corpus_mask_count(const vg_corpus *c) { return c ? c->mask
 
 // ------------------------------------------------------------------------------------------------ the scan
 
-// the masked kernel + the plain scan's merge; the k winners land in the pinned c->h_keys (copied behind the merge)
-static int launch_masked(vg_corpus *c, int metric, int k) {
+// One routine for every fused top-k variant that differs from the masked scan only in its kernel table and a ScanArgs field (3.11 of
+// DESIGN.md): VgFusedForm names the table, whether ScanArgs.mask is set (and a mask required) and whether ScanArgs.floor is (the paged
+// scans of vg_scan_after.hip; the floor key travels in the 8 bytes behind the query, one upload).
+// the form's kernel + the plain scan's merge; the k winners land in the pinned c->h_keys (copied behind the merge)
+static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     int acc = vg_metric_to_acc(metric);
     VgShape s;
     vg_plain_scan_shape(c, metric, &s);
     int rc = vg_half_cosine_acc(c, s, &acc);                 // the plain scan's cached-norm cosine: the same floats
     if (rc != VG_OK) return rc;
-    scan_fn_t fn = vg_pick_scan<MaskedFamily>(c->vtype, acc, s.U, s.long_rows);
-    if (!fn) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_masked: no kernel for this type / metric");
+    scan_fn_t fn = f.pick(c->vtype, acc, s.U, s.long_rows);
+    if (!fn) return vg_fail(VG_ERR_UNSUPPORTED, "%s: no kernel for this type / metric", f.who);
 
     const long long blocks = vg_plain_scan_blocks(c, c->n_rows, s);      // the launch shape of the plain top-k scan
     ScanArgs a = vg_scan_args(c, metric, acc, s, c->d_query, k);
     a.cand = c->d_cand;
-    a.mask = c->d_mask;
+    if (f.masked) a.mask = c->d_mask;
+    if (f.after) a.floor = reinterpret_cast<const uint64_t *>(c->d_query + c->stride);
     const size_t smem = std::max<size_t>(vg_query_lds_bytes(c, s), (size_t)VG_PUBLISH_LDS_BYTES);
 
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);
@@ -107,35 +113,46 @@ static int launch_masked(vg_corpus *c, int metric, int k) {
     if (evs) hipEventRecord(evs[2], c->stream);
     int rcm = vg_launch_merge_one(c->d_cand, (int)blocks, k, c->d_keys, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
-    if (rcm != 0) return vg_fail(VG_ERR_HIP, "vg_scan_topk_masked: merge launch failed: %s", hipGetErrorString((hipError_t)rcm));
+    if (rcm != 0) return vg_fail(VG_ERR_HIP, "%s: merge launch failed: %s", f.who, hipGetErrorString((hipError_t)rcm));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->h_keys, c->d_keys, VG_WAVE * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VG_OK;
 }
 
-// packed keys (distance image << 32 | position local to this corpus), ascending: the form a multi-shard caller merges
-extern "C" int vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, int *out_count) {
-    if (!c || !query || !out_count) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: NULL argument");
+// packed keys (distance image << 32 | position local to this corpus), ascending: the form a multi-shard caller merges.  `floor`: the
+// smallest key admitted (read by an after form only)
+int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count) {
+    if (!c || !query || !out_count) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     *out_count = 0;
-    if (k < 1) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: k must be at least 1");
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_masked: k must be in 1..%d (masked scans use the fused list only)", VG_MAX_FUSED_K);
-    if (!out_keys) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: NULL output");
+    if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.masked ? "masked" : "paged");
+    if (!out_keys) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    if (c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_masked: no row mask set");
-    if (c->mask_count == 0 || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
+    if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if ((f.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
+    if (f.after && floor == VG_EMPTY_KEY) return VG_OK;      // nothing is behind the cursor: no launch
     HIP_TRY(hipSetDevice(c->device));
-    c->enqueued = false;                                     // (the pinned key buffer is this scan's landing zone now)
+    c->enqueued = false;                                    // (the pinned key buffer is this scan's landing zone now)
     memset(c->h_query, 0, (size_t)c->stride);
     memcpy(c->h_query, query, (size_t)c->dim * c->es);
-    HIP_TRY(hipMemcpyAsync(c->d_query, c->h_query, (size_t)c->stride, hipMemcpyHostToDevice, c->stream));
-    int rc = launch_masked(c, metric, k);
+    if (f.after) memcpy(c->h_query + c->stride, &floor, sizeof(uint64_t));
+    HIP_TRY(hipMemcpyAsync(c->d_query, c->h_query, (size_t)c->stride + (f.after ? sizeof(uint64_t) : 0), hipMemcpyHostToDevice, c->stream));
+    int rc = launch_fused(c, f, metric, k);
     if (rc != VG_OK) return rc;
     vg_collect_timing(c);
     int cnt = 0;
     while (cnt < k && c->h_keys[cnt] != VG_EMPTY_KEY) { out_keys[cnt] = c->h_keys[cnt]; ++cnt; }
     *out_count = cnt;
     return VG_OK;
+}
+
+// the masked kernel table as a plain function: the fallback of the masked batch (vg_multi_masked.hip) names it in its form
+scan_fn_t vg_pick_scan_masked(int vtype, int acc, int U, bool long_rows) { return vg_pick_scan<MaskedFamily>(vtype, acc, U, long_rows); }
+
+extern "C" int vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, int *out_count) {
+    const VgFusedForm form = {"vg_scan_topk_masked", vg_pick_scan_masked, true, false};
+    return vg_fused_run(c, form, metric, query, k, 0ull, out_keys, out_count);
 }
 
 extern "C" int vg_scan_topk_masked(vg_corpus *c, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,

@@ -505,8 +505,9 @@ static inline bool cand_less(const Cand &a, const Cand &b) { return a.img != b.i
 // ref_k >= 0: the lists were taken with one more slot than asked for (tie_order = reference, see vg_scan_topk_reference): when the
 // best ref_k + 1 distances are pairwise distinct the reference's own result IS the first ref_k in ascending order and that is what
 // comes back; when they hold a tie nothing is written and -1 comes back (the caller replays the reference's slots).
+// out_gkeys (optional): the winners as keys over GLOBAL positions (distance image << 32 | global position; the paged scans' _keys forms).
 static int merge_lists(const vg_shards *s, const uint64_t *keys, size_t pitch, const int *counts, int cpitch, int k, int64_t *out_rowids,
-                       double *out_dist, int ref_k = -1) {
+                       double *out_dist, int ref_k = -1, uint64_t *out_gkeys = nullptr) {
     std::vector<Cand> all;
     for (int i = 0; i < s->S; ++i)
         for (int j = 0; j < counts[(size_t)i * cpitch]; ++j) {
@@ -524,13 +525,14 @@ static int merge_lists(const vg_shards *s, const uint64_t *keys, size_t pitch, c
     for (size_t i = 0; i < take; ++i) {
         out_dist[i] = (double)vg_key_distance((uint64_t)all[i].img << 32);
         out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)all[i].shard], (int64_t)all[i].local);
+        if (out_gkeys) out_gkeys[i] = ((uint64_t)all[i].img << 32) | (uint64_t)all[i].gpos;
     }
     return (int)take;
 }
 // the same for query q of a batch: keys [S][nq][kk], counts [S][nq]
 static int merge_query_lists(const vg_shards *s, const uint64_t *keys, const int *counts, int nq, int q, int kk, int k, int64_t *out_rowids,
-                             double *out_dist, int ref_k = -1) {
-    return merge_lists(s, keys + (size_t)q * kk, (size_t)nq * kk, counts + q, nq, k, out_rowids, out_dist, ref_k);
+                             double *out_dist, int ref_k = -1, uint64_t *out_gkeys = nullptr) {
+    return merge_lists(s, keys + (size_t)q * kk, (size_t)nq * kk, counts + q, nq, k, out_rowids, out_dist, ref_k, out_gkeys);
 }
 
 // ---- tie_order = reference over several shards: the same replay (vg_refslots.h), its stream assembled in GLOBAL scan
@@ -543,6 +545,13 @@ extern "C" int vg_shards_set_tie_order(vg_shards *s, int mode) {
     }
     s->tie_order = mode;
     return VG_OK;
+}
+
+// local rows of shard i in front of GLOBAL scan position g0: its whole blocks below block g0 / B, + g0 % B when that block is its own
+static inline int64_t local_rows_before(const vg_shards *s, int i, int64_t g0) {
+    const int64_t pb = g0 / s->B, rem = g0 % s->B;
+    const int64_t full = (pb + s->S - 1 - i) / s->S;
+    return full * s->B + ((int)(pb % s->S) == i ? rem : 0);
 }
 
 namespace {
@@ -565,11 +574,8 @@ struct ShardsSrc {
     }
     int below(int64_t g0, float bound, std::vector<VgRefCand> &out, bool *overflow) {
         pairs.resize((size_t)kCap);
-        const int64_t pb = g0 / s->B, rem = g0 % s->B;
         for (int i = 0; i < s->S; ++i) {
-            // local rows of shard i in front of global position g0: its whole blocks below block pb, + rem when pb is its own
-            const int64_t full = (pb + s->S - 1 - i) / s->S;
-            const int64_t local_from = full * s->B + ((int)(pb % s->S) == i ? rem : 0);
+            const int64_t local_from = local_rows_before(s, i, g0);
             int64_t count = 0;
             int rc = vg_resident_distances_below(s->sh[(size_t)i], local_from, bound, pairs.data(), kCap, &count);
             if (rc != VG_OK) return rc;
@@ -1135,6 +1141,185 @@ extern "C" int vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const 
     for (int q = 0; q < nq; ++q)
         out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
     return VG_OK;
+}
+
+// ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): a cursor over GLOBAL scan order becomes one floor key per shard over ITS
+// positions - the cursor's distance image with "local rows of this shard in front of global position P" (local_rows_before) - every
+// shard runs its floor form and the lists merge like the masked scans', by (distance image, global position)
+struct AfterWho { const char *one, *batch; };
+static AfterWho after_who(bool masked) {
+    return masked ? AfterWho{"vg_scan_topk_after_masked", "vg_scan_topk_batch_after_masked"} : AfterWho{"vg_scan_topk_after", "vg_scan_topk_batch_after"};
+}
+static int after_fail(int code, const char *who, const char *what) {
+    return fail(code, (std::string(who) + ": " + what).c_str());
+}
+// floors[i] for a (distance, rowid) cursor; every shard's rowids must be ascending (the rows are dealt out in global order)
+static int shard_floors_cursor(const vg_shards *s, const char *who, double after_dist, int64_t after_rowid, uint64_t *floors) {
+    if (after_dist != after_dist) return after_fail(VG_ERR_INVALID, who, "the cursor's distance is NaN");
+    int64_t P = 0;
+    for (auto *c : s->sh) {
+        const int64_t p = vg_corpus_rows_upto_rowid(c, after_rowid);
+        if (p == -2) return after_fail(VG_ERR_UNSUPPORTED, who, "the rowids are not ascending (no rowid order); page by key (the _keys form)");
+        P += p;
+    }
+    // ascending inside every shard is not ascending in GLOBAL order: blocks are dealt out cyclically, so every block border is
+    // compared too (n_rows / B lookups) - one corpus holding these rows would refuse them, and so do the shards
+    for (int64_t g = s->B; g < s->n_rows; g += s->B)
+        if (vg_shards_rowid_at(s, g - 1) >= vg_shards_rowid_at(s, g))
+            return after_fail(VG_ERR_UNSUPPORTED, who, "the rowids are not ascending in global order (no rowid order); page by key (the _keys form)");
+    for (int i = 0; i < s->S; ++i) {
+        int empty = 0;
+        const int64_t local = std::min<int64_t>(local_rows_before(s, i, P), vg_corpus_rows(s->sh[(size_t)i]));
+        int rc = vg_after_floor(after_dist, (uint32_t)local, &floors[i], &empty);      // (empty: VG_KEY_EMPTY, no launch)
+        if (rc != VG_OK) return rc;
+    }
+    return VG_OK;
+}
+// floors[i] for a cursor given as the last GLOBAL key of the previous page
+static int shard_floors_key(const vg_shards *s, const char *who, uint64_t after_key, uint64_t *floors) {
+    if (after_key == VG_KEY_EMPTY) return after_fail(VG_ERR_INVALID, who, "after_key is the empty key");
+    if (s->n_rows >= (1ll << 32)) return after_fail(VG_ERR_UNSUPPORTED, who, "keys over global positions need fewer than 2^32 rows");
+    const uint64_t g = after_key + 1ull;
+    for (int i = 0; i < s->S; ++i) {
+        const int64_t local = std::min<int64_t>(local_rows_before(s, i, (int64_t)(g & 0xFFFFFFFFull)), vg_corpus_rows(s->sh[(size_t)i]));
+        floors[i] = (g & 0xFFFFFFFF00000000ull) | (uint64_t)local;
+    }
+    return VG_OK;
+}
+
+// one query, the floors of the S shards given; out_gkeys (keys form) or out_rowids / out_dist
+static int shards_after_run(vg_shards *s, bool masked, int metric, const void *query, int k, const uint64_t *floors, int64_t *out_rowids,
+                            double *out_dist, uint64_t *out_gkeys, int *out_count) {
+    const char *who = after_who(masked).one;
+    if (k < 1) return after_fail(VG_ERR_INVALID, who, "k must be at least 1");
+    if (k > VG_WAVE_KEYS) return after_fail(VG_ERR_UNSUPPORTED, who, "k must be in 1..64 (paged scans use the fused list only)");
+    if (masked && vg_shards_mask_count(s) < 0) return after_fail(VG_ERR_INVALID, who, "no row mask set");
+    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
+    std::vector<int> counts((size_t)s->S, 0);
+    int rc = for_each_shard(s, [&](int i) {
+        return vg_after_floor_run(s->sh[(size_t)i], masked, metric, query, k, floors[i], &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]);
+    });
+    if (rc != VG_OK) return rc;
+    int64_t ids[VG_WAVE_KEYS];
+    double dist[VG_WAVE_KEYS];
+    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids ? out_rowids : ids, out_dist ? out_dist : dist, -1, out_gkeys);
+    return VG_OK;
+}
+
+static int shards_after(vg_shards *s, bool masked, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
+                        int64_t *out_rowids, double *out_dist, int *out_count) {
+    const char *who = after_who(masked).one;
+    if (!s || !query || !out_count) return after_fail(VG_ERR_INVALID, who, "NULL argument");
+    if (s->S == 1) return masked ? vg_scan_topk_after_masked(s->sh[0], metric, query, k, after_dist, after_rowid, out_rowids, out_dist, out_count)
+                                 : vg_scan_topk_after(s->sh[0], metric, query, k, after_dist, after_rowid, out_rowids, out_dist, out_count);
+    *out_count = 0;
+    if (k >= 1 && k <= VG_WAVE_KEYS && (!out_rowids || !out_dist)) return after_fail(VG_ERR_INVALID, who, "NULL output");
+    std::vector<uint64_t> floors((size_t)s->S, VG_KEY_EMPTY);
+    int rc = shard_floors_cursor(s, who, after_dist, after_rowid, floors.data());
+    if (rc != VG_OK) return rc;
+    return shards_after_run(s, masked, metric, query, k, floors.data(), out_rowids, out_dist, nullptr, out_count);
+}
+static int shards_after_keys(vg_shards *s, bool masked, int metric, const void *query, int k, uint64_t after_key, uint64_t *out_keys, int *out_count) {
+    const char *who = after_who(masked).one;
+    if (!s || !query || !out_count) return after_fail(VG_ERR_INVALID, who, "NULL argument");
+    if (s->S == 1) return masked ? vg_scan_topk_after_masked_keys(s->sh[0], metric, query, k, after_key, out_keys, out_count)
+                                 : vg_scan_topk_after_keys(s->sh[0], metric, query, k, after_key, out_keys, out_count);
+    *out_count = 0;
+    if (k >= 1 && k <= VG_WAVE_KEYS && !out_keys) return after_fail(VG_ERR_INVALID, who, "NULL output");
+    std::vector<uint64_t> floors((size_t)s->S, VG_KEY_EMPTY);
+    int rc = shard_floors_key(s, who, after_key, floors.data());
+    if (rc != VG_OK) return rc;
+    return shards_after_run(s, masked, metric, query, k, floors.data(), nullptr, nullptr, out_keys, out_count);
+}
+
+// the batch: floors [S][nq]; every shard answers all nq queries behind its own floors, then one merge per query
+static int shards_after_batch_run(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                                  int64_t *out_rowids, double *out_dist, uint64_t *out_gkeys, int *out_counts) {
+    const char *who = after_who(masked).batch;
+    if (k < 1) return after_fail(VG_ERR_INVALID, who, "k must be at least 1");
+    if (k > VG_WAVE_KEYS) return after_fail(VG_ERR_UNSUPPORTED, who, "k must be in 1..64 (paged scans use the fused list only)");
+    if (masked && vg_shards_mask_count(s) < 0) return after_fail(VG_ERR_INVALID, who, "no row mask set");
+    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
+    std::vector<int> counts((size_t)s->S * nq, 0);
+    int rc = for_each_shard(s, [&](int i) {
+        return vg_after_floor_batch_run(s->sh[(size_t)i], masked, metric, queries, nq, k, floors + (size_t)i * nq, &keys[(size_t)i * nq * k],
+                                        &counts[(size_t)i * nq]);
+    });
+    if (rc != VG_OK) return rc;
+    int64_t ids[VG_WAVE_KEYS];
+    double dist[VG_WAVE_KEYS];
+    for (int q = 0; q < nq; ++q)
+        out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids ? out_rowids + (size_t)q * k : ids,
+                                          out_dist ? out_dist + (size_t)q * k : dist, -1, out_gkeys ? out_gkeys + (size_t)q * k : nullptr);
+    return VG_OK;
+}
+
+static int shards_after_batch(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, const double *after_dists,
+                              const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts) {
+    const char *who = after_who(masked).batch;
+    if (!s || !queries || !out_counts || !after_dists || !after_rowids) return after_fail(VG_ERR_INVALID, who, "NULL argument");
+    if (s->S == 1) return masked ? vg_scan_topk_batch_after_masked(s->sh[0], metric, queries, nq, k, after_dists, after_rowids, out_rowids, out_dist, out_counts)
+                                 : vg_scan_topk_batch_after(s->sh[0], metric, queries, nq, k, after_dists, after_rowids, out_rowids, out_dist, out_counts);
+    if (nq < 1) return after_fail(VG_ERR_INVALID, who, "nq must be at least 1");
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k >= 1 && k <= VG_WAVE_KEYS && (!out_rowids || !out_dist)) return after_fail(VG_ERR_INVALID, who, "NULL output");
+    std::vector<uint64_t> floors((size_t)s->S * nq, VG_KEY_EMPTY), one((size_t)s->S);
+    for (int q = 0; q < nq; ++q) {
+        int rc = shard_floors_cursor(s, who, after_dists[q], after_rowids[q], one.data());
+        if (rc != VG_OK) return rc;
+        for (int i = 0; i < s->S; ++i) floors[(size_t)i * nq + q] = one[(size_t)i];
+    }
+    return shards_after_batch_run(s, masked, metric, queries, nq, k, floors.data(), out_rowids, out_dist, nullptr, out_counts);
+}
+static int shards_after_batch_keys(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, const uint64_t *after_keys,
+                                   uint64_t *out_keys, int *out_counts) {
+    const char *who = after_who(masked).batch;
+    if (!s || !queries || !out_counts || !after_keys) return after_fail(VG_ERR_INVALID, who, "NULL argument");
+    if (s->S == 1) return masked ? vg_scan_topk_batch_after_masked_keys(s->sh[0], metric, queries, nq, k, after_keys, out_keys, out_counts)
+                                 : vg_scan_topk_batch_after_keys(s->sh[0], metric, queries, nq, k, after_keys, out_keys, out_counts);
+    if (nq < 1) return after_fail(VG_ERR_INVALID, who, "nq must be at least 1");
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k >= 1 && k <= VG_WAVE_KEYS && !out_keys) return after_fail(VG_ERR_INVALID, who, "NULL output");
+    std::vector<uint64_t> floors((size_t)s->S * nq, VG_KEY_EMPTY), one((size_t)s->S);
+    for (int q = 0; q < nq; ++q) {
+        int rc = shard_floors_key(s, who, after_keys[q], one.data());
+        if (rc != VG_OK) return rc;
+        for (int i = 0; i < s->S; ++i) floors[(size_t)i * nq + q] = one[(size_t)i];
+    }
+    return shards_after_batch_run(s, masked, metric, queries, nq, k, floors.data(), nullptr, nullptr, out_keys, out_counts);
+}
+
+extern "C" int vg_shards_scan_topk_after(vg_shards *s, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
+                                         int64_t *out_rowids, double *out_dist, int *out_count) {
+    return shards_after(s, false, metric, query, k, after_dist, after_rowid, out_rowids, out_dist, out_count);
+}
+extern "C" int vg_shards_scan_topk_after_keys(vg_shards *s, int metric, const void *query, int k, uint64_t after_key, uint64_t *out_keys,
+                                              int *out_count) {
+    return shards_after_keys(s, false, metric, query, k, after_key, out_keys, out_count);
+}
+extern "C" int vg_shards_scan_topk_after_masked(vg_shards *s, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
+                                                int64_t *out_rowids, double *out_dist, int *out_count) {
+    return shards_after(s, true, metric, query, k, after_dist, after_rowid, out_rowids, out_dist, out_count);
+}
+extern "C" int vg_shards_scan_topk_after_masked_keys(vg_shards *s, int metric, const void *query, int k, uint64_t after_key,
+                                                     uint64_t *out_keys, int *out_count) {
+    return shards_after_keys(s, true, metric, query, k, after_key, out_keys, out_count);
+}
+extern "C" int vg_shards_scan_topk_batch_after(vg_shards *s, int metric, const void *queries, int nq, int k, const double *after_dists,
+                                               const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts) {
+    return shards_after_batch(s, false, metric, queries, nq, k, after_dists, after_rowids, out_rowids, out_dist, out_counts);
+}
+extern "C" int vg_shards_scan_topk_batch_after_keys(vg_shards *s, int metric, const void *queries, int nq, int k, const uint64_t *after_keys,
+                                                    uint64_t *out_keys, int *out_counts) {
+    return shards_after_batch_keys(s, false, metric, queries, nq, k, after_keys, out_keys, out_counts);
+}
+extern "C" int vg_shards_scan_topk_batch_after_masked(vg_shards *s, int metric, const void *queries, int nq, int k, const double *after_dists,
+                                                      const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts) {
+    return shards_after_batch(s, true, metric, queries, nq, k, after_dists, after_rowids, out_rowids, out_dist, out_counts);
+}
+extern "C" int vg_shards_scan_topk_batch_after_masked_keys(vg_shards *s, int metric, const void *queries, int nq, int k,
+                                                           const uint64_t *after_keys, uint64_t *out_keys, int *out_counts) {
+    return shards_after_batch_keys(s, true, metric, queries, nq, k, after_keys, out_keys, out_counts);
 }
 
 extern "C" int vg_shards_minmax(vg_shards *s, float *out_min, float *out_max, int *out_any_negative) {

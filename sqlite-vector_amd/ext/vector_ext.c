@@ -22,7 +22,7 @@
  *   - the JSON query vector is freed (the reference leaks it, :1771).
  *
  * Layout: this file holds the includes, the registration and the entry point; the rest lives in vext_*.inc by concern
- * (gpulib, context, tracking, sqlutil, convert, staging, quantize, tvf, batch, cursor, within, masked, batch_masked, batch_within).  The JSON and option-string parsers
+ * (gpulib, context, tracking, sqlutil, convert, staging, quantize, tvf, batch, cursor, within, masked, batch_masked, batch_within, after).  The JSON and option-string parsers
  * (vext_convert.inc / vext_sqlutil.inc) implement the reference's user-visible contract - what is accepted, every error
  * text - in this repository's own structure; a differential test against the reference extension pins that contract.
  */
@@ -74,6 +74,7 @@ enum { COL_TBL = 0, COL_VECTOR = 1, COL_K = 2, COL_MEMIDX = 3, COL_ID = 4, COL_D
 #include "vext_batch_within.inc"
 #include "vext_within_masked.inc"
 #include "vext_batch_within_masked.inc"
+#include "vext_after.inc"
 
 /* ------------------------------------------------------------------------------------------------ registration */
 
@@ -205,5 +206,10 @@ int sqlite3_vector_init(sqlite3 *db, char **pzErrMsg, const sqlite3_api_routines
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_within_filtered", &quant_wmasked_module, ctx);
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_within_filtered", &full_bwmasked_module, ctx);
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_within_filtered", &quant_bwmasked_module, ctx);
+    /* paged scans: the next k rows behind a (distance, rowid) cursor, over all rows or those a filter names (vext_after.inc) */
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_after", &full_after_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_after", &quant_after_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_filtered_after", &full_fafter_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_filtered_after", &quant_fafter_module, ctx);
     return rc;
 }

@@ -111,8 +111,11 @@ static int masked_filter_arg(scan_vtab *vt, const char *fname, sqlite3_value *ar
 
 /* one query against a table that does not fit the device: every distance through the slab path (k = 0), filtered against the SORTED
  * rowids, sorted by (distance, scan position) and cut to k here; out_ids / out_dist hold k slots */
-static int masked_ooc_topk(scan_vtab *vt, const char *fname, table_ctx *t, int quantized, const void *scan_query, int k,
-                           const int64_t *sorted_ids, int64_t filter_n, int64_t *out_ids, double *out_dist, int64_t *out_held) {
+/* (has_filter = 0: every row is allowed; after_dist != NULL: only rows behind the cursor (*after_dist, after_rowid) of the paged forms,
+ * vext_after.inc - (double)d > D, or d == D and rowid > R) */
+static int masked_ooc_topk_ex(scan_vtab *vt, const char *fname, table_ctx *t, int quantized, const void *scan_query, int k, int has_filter,
+                              const int64_t *sorted_ids, int64_t filter_n, const double *after_dist, int64_t after_rowid,
+                              int64_t *out_ids, double *out_dist, int64_t *out_held) {
     char *err = NULL;
     float *all_dist = NULL;
     int64_t *all_ids = NULL;
@@ -126,8 +129,9 @@ static int masked_ooc_topk(scan_vtab *vt, const char *fname, table_ctx *t, int q
     if (!hits) { rc = SQLITE_NOMEM; goto done; }
     int64_t m = 0;
     for (int64_t i = 0; i < n; ++i) {
-        if (!(all_dist[i] < INFINITY) || filter_n == 0) continue;                        /* NaN / +Inf never enter */
-        if (!bsearch(&all_ids[i], sorted_ids, (size_t)filter_n, sizeof(int64_t), masked_i64_cmp)) continue;
+        if (!(all_dist[i] < INFINITY) || (has_filter && filter_n == 0)) continue;        /* NaN / +Inf never enter */
+        if (has_filter && !bsearch(&all_ids[i], sorted_ids, (size_t)filter_n, sizeof(int64_t), masked_i64_cmp)) continue;
+        if (after_dist && !((double)all_dist[i] > *after_dist || ((double)all_dist[i] == *after_dist && all_ids[i] > after_rowid))) continue;
         hits[m].d = all_dist[i]; hits[m].pos = i; ++m;
     }
     qsort(hits, (size_t)m, sizeof(within_hit), within_hit_cmp);
@@ -142,19 +146,46 @@ done:
     return rc;
 }
 
-static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized) {
+static int masked_ooc_topk(scan_vtab *vt, const char *fname, table_ctx *t, int quantized, const void *scan_query, int k,
+                           const int64_t *sorted_ids, int64_t filter_n, int64_t *out_ids, double *out_dist, int64_t *out_held) {
+    return masked_ooc_topk_ex(vt, fname, t, quantized, scan_query, k, 1, sorted_ids, filter_n, NULL, 0, out_ids, out_dist, out_held);
+}
+
+/* the paged forms' entry points (vext_after.inc), resolved like the masked ones */
+typedef int (*after_scan_fn)(vg_shards *, int, const void *, int, double, int64_t, int64_t *, double *, int *);
+
+/* One filter routine for the masked scans and the paged scans (vext_after.inc), which differ in their argument list and the engine
+ * call only: (table, column, vector, k [, filter] [, after_distance, after_rowid]).  has_filter: a filter argument, the row mask set
+ * under the lock.  has_after: a (distance, rowid) cursor - both NULL = the first page. */
+static int masked_filter_form(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized, int has_filter, int has_after) {
     scan_cursor *c = (scan_cursor *)cur;
     scan_vtab *vt = (scan_vtab *)cur->pVtab;
     c->streaming = 0;
     c->stream_pos = 0;
     c->stream_n = 0;
-    if (argc != 5) return vtab_error(&vt->base, "%s expects %d arguments, but %d were provided.", fname, 5, argc);
+    const int want_argc = 4 + (has_filter ? 1 : 0) + (has_after ? 2 : 0), fi = has_filter ? 4 : -1, ai = has_after ? want_argc - 2 : -1;
+    if (argc != want_argc) return vtab_error(&vt->base, "%s expects %d arguments, but %d were provided.", fname, want_argc, argc);
     for (int i = 0; i < argc; ++i) {
         int t = sqlite3_value_type(argv[i]);
         if (i < 2 && t != SQLITE_TEXT) return vtab_error(&vt->base, "%s: argument %d must be of type TEXT (got %s).", fname, i + 1, sql_type_name(t));
-        if (i == 4 && t == SQLITE_NULL) return vtab_error(&vt->base, "%s: filter cannot be NULL.", fname);
-        if ((i == 2 || i == 4) && t != SQLITE_TEXT && t != SQLITE_BLOB) return vtab_error(&vt->base, "%s: argument %d must be of type TEXT or BLOB (got %s).", fname, i + 1, sql_type_name(t));
+        if (i == fi && t == SQLITE_NULL) return vtab_error(&vt->base, "%s: filter cannot be NULL.", fname);
+        if ((i == 2 || i == fi) && t != SQLITE_TEXT && t != SQLITE_BLOB) return vtab_error(&vt->base, "%s: argument %d must be of type TEXT or BLOB (got %s).", fname, i + 1, sql_type_name(t));
         if (i == 3 && t != SQLITE_INTEGER) return vtab_error(&vt->base, "%s: argument %d must be of type INTEGER (got %s).", fname, i + 1, sql_type_name(t));
+    }
+    /* the cursor: both NULL = the first page, (-Inf, INT64_MIN) */
+    double after_dist = -INFINITY;
+    int64_t after_rowid = INT64_MIN;
+    if (has_after) {
+        const int td = sqlite3_value_type(argv[ai]), tr = sqlite3_value_type(argv[ai + 1]);
+        if ((td == SQLITE_NULL) != (tr == SQLITE_NULL))
+            return vtab_error(&vt->base, "%s: after_distance and after_rowid must both be NULL (the first page) or both be given.", fname);
+        if (td != SQLITE_NULL) {
+            if (td != SQLITE_FLOAT && td != SQLITE_INTEGER) return vtab_error(&vt->base, "%s: argument %d must be a number (got %s).", fname, ai + 1, sql_type_name(td));
+            if (tr != SQLITE_INTEGER) return vtab_error(&vt->base, "%s: argument %d must be of type INTEGER (got %s).", fname, ai + 2, sql_type_name(tr));
+            after_dist = sqlite3_value_double(argv[ai]);
+            after_rowid = (int64_t)sqlite3_value_int64(argv[ai + 1]);
+            if (after_dist != after_dist) return vtab_error(&vt->base, "%s: after_distance cannot be NaN.", fname);
+        }
     }
     const char *tbl = (const char *)sqlite3_value_text(argv[0]);
     const char *col = (const char *)sqlite3_value_text(argv[1]);
@@ -192,18 +223,24 @@ static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_valu
         }
     }
     const int k = sqlite3_value_int(argv[3]);
-    if (k == 0) goto out;                                                                /* no rows, no device (decided here) */
-    if (k < 0) { rc = vtab_error(&vt->base, "%s: k must be positive.", fname); goto out; }
+    if (k == 0 && !has_after) goto out;                                                  /* no rows, no device (decided here) */
+    if (k <= 0) { rc = vtab_error(&vt->base, "%s: k must be positive.", fname); goto out; }
     if (k > 64) { rc = vtab_error(&vt->base, "%s: k must not exceed 64.", fname); goto out; }
 
     /* the allowed rowids: before anything is staged - a refused filter runs nothing */
-    rc = masked_filter_arg(vt, fname, argv[4], &filter_owned, &filter_n);
+    if (has_filter) rc = masked_filter_arg(vt, fname, argv[4], &filter_owned, &filter_n);
     if (rc != SQLITE_OK) goto out;
     filter_ids = filter_owned;
 
     masked_set_fn set_mask = NULL;
     masked_scan_fn scan = NULL;
+    after_scan_fn scan_after = NULL;
     const char *missing = masked_resolve(&set_mask, &scan);
+    if (!missing && has_after && G.handle) {
+        const char *sym = has_filter ? "vg_shards_scan_topk_after_masked" : "vg_shards_scan_topk_after";
+        scan_after = (after_scan_fn)dlsym(G.handle, sym);
+        if (!scan_after) missing = sym;
+    }
     if (missing) { rc = vtab_error(&vt->base, "%s: the GPU engine lacks symbol %s (masked scans need a newer libvectorgpu.so).", fname, missing); goto out; }
 
     vg_shards *corpus = NULL;
@@ -224,7 +261,7 @@ static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_valu
         if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "staging failed"); goto out; }
         corpus = t->full;
     }
-    if (!set_mask || !scan) { rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error()); goto out; }
+    if (!set_mask || !scan || (has_after && !scan_after)) { rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error()); goto out; }
 
     sqlite3_free(c->rowids); c->rowids = NULL;
     sqlite3_free(c->distance); c->distance = NULL;
@@ -236,7 +273,8 @@ static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_valu
         /* the table does not fit the device: every distance through the slab path (k = 0), filtered, sorted and cut here */
         int64_t held = 0;
         if (filter_n > 1) qsort(filter_owned, (size_t)filter_n, sizeof(int64_t), masked_i64_cmp);
-        rc = masked_ooc_topk(vt, fname, t, quantized, scan_query, k, filter_ids, filter_n, c->rowids, c->distance, &held);
+        rc = masked_ooc_topk_ex(vt, fname, t, quantized, scan_query, k, has_filter, filter_ids, filter_n, has_after ? &after_dist : NULL, after_rowid,
+                                c->rowids, c->distance, &held);
         if (rc != SQLITE_OK) goto out;
         c->stream_n = held;
         goto out;
@@ -247,8 +285,9 @@ static int masked_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_valu
     {
         int got = 0;
         int64_t allowed = 0;
-        if (set_mask(corpus, filter_ids, filter_n, &allowed) != VG_OK ||
-            scan(corpus, t->opt.v_distance, scan_query, k, c->rowids, c->distance, &got) != VG_OK) {
+        if ((has_filter && set_mask(corpus, filter_ids, filter_n, &allowed) != VG_OK) ||
+            (has_after ? scan_after(corpus, t->opt.v_distance, scan_query, k, after_dist, after_rowid, c->rowids, c->distance, &got)
+                       : scan(corpus, t->opt.v_distance, scan_query, k, c->rowids, c->distance, &got)) != VG_OK) {
             rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error());
             goto unlock;
         }
@@ -264,8 +303,8 @@ out:
     return rc;
 }
 
-static int full_masked_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return masked_filter_common(c, argc, argv, "vector_full_scan_filtered", 0); }
-static int quant_masked_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return masked_filter_common(c, argc, argv, "vector_quantize_scan_filtered", 1); }
+static int full_masked_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return masked_filter_form(c, argc, argv, "vector_full_scan_filtered", 0, 1, 0); }
+static int quant_masked_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return masked_filter_form(c, argc, argv, "vector_quantize_scan_filtered", 1, 1, 0); }
 
 static sqlite3_module full_masked_module = {0, 0, masked_connect, within_best_index, tvf_disconnect, 0, tvf_open, tvf_close, full_masked_filter,
                                             within_next, within_eof, within_column, within_rowid, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
