@@ -174,7 +174,7 @@ int vg_scan_within_keys(const vg_corpus *c, int64_t first, int64_t n, uint64_t *
  * distance; each radius is turned into the largest float not above it; ascending (distance, scan position) whatever the handle's
  * tie_order; limit > 0 holds the first `limit` matches PER QUERY while out_matches[i] still counts all of them.
  * f32 / uint8 / int8 rows of a register-resident shape: 4 queries (2 where a lane holds 4 or 6 chunks of the row) share every row
- * load of a pass (vg_scan_multi_within.h; the plan: vg_within_batch_plan, vectorgpu_diag.h), nq queries cost ceil(nq / 4) - or
+ * load of a pass (vg_scan_multi.h, range form; the plan: vg_within_batch_plan, vectorgpu_diag.h), nq queries cost ceil(nq / 4) - or
  * ceil(nq / 2) - such passes.  Queries go up in slices; the passes of a slice are enqueued back to back with one copy of the counts
  * and one wait behind them.  A query's device region starts as a share of one fixed budget of keys (2^20 over the queries of a
  * slice); a pass in which a query counted past its region runs ONCE more as a whole into regions of the counted sizes - passes that
@@ -228,7 +228,7 @@ int     vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, in
  * Query i's answer is what vg_scan_topk_masked is contracted to return for it: only allowed rows, ascending (distance, scan
  * position) whatever the handle's tie_order, NaN / +Inf never enter, fewer than k rows when fewer allowed rows qualify.
  * f32 / uint8 / int8 rows of a register-resident shape: 4 queries (2 where a lane holds 4 or 6 chunks of the row) share every row
- * load of a pass, and a pass reads only the batches of rows that hold an allowed row (vg_scan_multi_masked.h; the plan:
+ * load of a pass, and a pass reads only the batches of rows that hold an allowed row (vg_scan_multi.h, masked form; the plan:
  * vg_batch_masked_plan, vectorgpu_diag.h); nq queries cost ceil(nq / 4) - or ceil(nq / 2) - such passes, enqueued back to back with
  * one wait at the end.  uint8 / int8: rowids, order and distance bits identical to nq vg_scan_topk_masked calls.  f32: the single
  * scan's arithmetic per (query, row) pair, possibly under another lane decomposition (the multi-query scans' launch shape) - the
@@ -259,7 +259,7 @@ int     vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *que
  * out_held nq (either may be NULL); it leaves its results where vg_scan_within_batch leaves its own and overwrites them (and the
  * reverse): read them with vg_scan_within_batch_fetch / _keys.  The single and the batch form keep their results apart.
  * Batch precision: f32 / uint8 / int8 rows of a register-resident shape share every row load of a pass among 4 (or 2) queries
- * (vg_scan_multi_within_masked.h; the plan: vg_within_batch_masked_plan, vectorgpu_diag.h), slices, key budget and the "a pass that
+ * (vg_scan_multi.h, masked range form; the plan: vg_within_batch_masked_plan, vectorgpu_diag.h), slices, key budget and the "a pass that
  * overflowed runs once more as a whole" rule as in vg_scan_within_batch.  uint8 / int8: rowids, order, distance bits and counts
  * identical to nq vg_scan_within_masked calls.  f32: the single scan's arithmetic per (query, row) pair under the multi-query launch
  * shape - bit for bit the single masked range scan where the two shapes agree, and as in vg_scan_within_batch elsewhere (for an
@@ -296,7 +296,7 @@ int     vg_scan_within_batch_masked(vg_corpus *c, int metric, const void *querie
  * Query i's answer is the single form's for its query and cursor, bit for bit, for every element type - a cursor taken from a
  * single page or from vg_scan_distances is valid in the batch form and the reverse.  uint8 / int8 rows of a register-resident shape,
  * and f32 rows whose multi-query launch shape is the plain scan's (the same summation order), share every row load of a pass among 4
- * (or 2) queries (vg_scan_multi_after.h - the multi-query scan, not the matrix-core filters, whose thresholds assume an unrestricted
+ * (or 2) queries (vg_scan_multi.h, floor forms - the multi-query scan, not the matrix-core filters, whose thresholds assume an unrestricted
  * top-k); every other f32 shape, f16 / bf16 and long rows take one single paged scan per query. */
 int     vg_scan_topk_after(vg_corpus *c, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
                            int64_t *out_rowids, double *out_dist, int *out_count);

@@ -52,7 +52,7 @@ struct ScanArgs {
     // ---- "masked" mode (the MASKED = true instantiations, vg_scan_masked.hip): bit (p & 63) of word (p >> 6) set = the row at scan
     // position p may enter a list; ceil(n_rows / 64) words, bits behind the last row zero.  A field the other kernels never read.
     const uint64_t *mask;
-    // ---- "after" mode (the AFTER = true instantiations, vg_scan_after.hip, and vg_scan_multi_after.h): a row enters a list only when its
+    // ---- "after" mode (the AFTER = true instantiations, vg_scan_after.hip, and the VG_MQ_AFTER forms of vg_scan_multi.h): a row enters a list only when its
     // key is >= its query's floor - one key for the single kernels, NQ keys for a multi-query pass (VG_EMPTY_KEY in the pad slot of a
     // ragged pass: nothing is admitted).  Device memory.  A field the other kernels never read.
     const uint64_t *floor;

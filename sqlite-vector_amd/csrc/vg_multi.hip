@@ -1,13 +1,11 @@
-// vg_multi.hip - host side of the multi-query scan (vg_scan_multi.h): shape choice, kernel table, launch.
-// A translation unit of its own so that its ~100 kernel instances compile next to vg_api.hip's, not after them.
+// vg_multi.hip - host side of the multi-query scan (vg_scan_multi.h): shape choice, kernel table, launch.  Holds the instances of
+// its plain top-k form (MultiFamily<0>); each other form's instances are in a unit of their own (vg_multi_masked.hip,
+// vg_multi_after.hip, vg_multi_within.hip, vg_multi_within_masked.hip), so that the 60 instances per form compile next to each other
+// and to vg_api.hip's, not after them.
 #include "vg_internal.h"
 
 #include "vg_scan_multi.h"
 #include "vg_pick.h"
-
-struct MultiFamily {
-    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_kernel<VT, ACC, U, NQ, true>; }
-};
 
 // (queries per pass, launch shape) of the multi-query scan for this corpus / metric; 0 when there is none
 static int multi_plan(const vg_corpus *c, int metric, VgShape *s) {
@@ -41,7 +39,7 @@ int vg_launch_scan_multi(vg_corpus *c, int metric, const uint8_t *dev_queries, i
     const int NQ = multi_plan(c, metric, &s);
     if (NQ == 0) return -1;
     const int acc = vg_metric_to_acc(metric);
-    scan_fn_t fn = vg_pick_multi<MultiFamily>(c->vtype, acc, s.U, NQ);
+    scan_fn_t fn = vg_pick_multi<MultiFamily<0>>(c->vtype, acc, s.U, NQ);
     if (!fn) return -1;
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);
     if (c->append_pending && stream != c->stream) HIP_TRY(hipStreamWaitEvent(stream, c->append_ev, 0));

@@ -1,27 +1,21 @@
 // vg_multi_after.hip - paged batch scans: for each of nq queries the next k rows behind its own cursor (vg_scan_topk_batch_after,
 // include/vectorgpu.h), over all rows or over the rows the handle's mask allows.
 //
-// Holds the instances of vg_scan_multi_after_kernel (vg_scan_multi_after.h: MASKED false and true) and the batch entry points.  The
+// Holds the instances of the floor forms of the multi-query scan (vg_scan_multi.h: VG_MQ_AFTER without and with VG_MQ_MASKED) and the
+// batch entry points.  The
 // host side is the masked batch's (vg_multi_masked.hip: vg_fused_batch_run - plan, slices, launches, merge, the fallback); this unit
 // hands it its kernel tables and one floor key per query, which go up behind each slice's queries.  The plan is vg_multi_plan's (4
 // queries per pass with up to 3 chunks per lane, 2 with 4 or 6; f32 / uint8 / int8); f16 / bf16 and long rows are answered by one
 // single paged scan per query (vg_scan_after.hip).
 #include "vg_internal.h"
 
-#include "vg_scan_multi_after.h"
+#include "vg_scan_multi.h"
 #include "vg_pick.h"
 
-struct MultiAfterFamily {
-    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_after_kernel<VT, ACC, U, NQ, true, false>; }
-};
-struct MultiAfterMaskedFamily {
-    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_after_kernel<VT, ACC, U, NQ, true, true>; }
-};
-
 static VgFusedBatchForm batch_form(bool masked) {
-    if (masked) return VgFusedBatchForm{"vg_scan_topk_batch_after_masked", vg_pick_multi<MultiAfterMaskedFamily>,
+    if (masked) return VgFusedBatchForm{"vg_scan_topk_batch_after_masked", vg_pick_multi<MultiFamily<VG_MQ_AFTER | VG_MQ_MASKED>>,
                                         {"vg_scan_topk_after_masked", vg_pick_scan_after_masked, true, true}};
-    return VgFusedBatchForm{"vg_scan_topk_batch_after", vg_pick_multi<MultiAfterFamily>, {"vg_scan_topk_after", vg_pick_scan_after, false, true}};
+    return VgFusedBatchForm{"vg_scan_topk_batch_after", vg_pick_multi<MultiFamily<VG_MQ_AFTER>>, {"vg_scan_topk_after", vg_pick_scan_after, false, true}};
 }
 
 // Query i's answer must be the single form's bit for bit - a cursor taken from a single page or from vg_scan_distances is fed to the

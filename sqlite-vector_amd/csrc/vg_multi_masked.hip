@@ -2,22 +2,18 @@
 // Also the home of vg_fused_batch_run, the form-driven batch routine the paged batch scans (vg_multi_after.hip) share with it: the
 // fused_* / launch_fused_* routines below serve every VgFusedBatchForm, masked or not.
 //
-// Host side of the masked multi-query scan (vg_scan_multi_masked.h): kernel table, launch, and the batch entry points.  The plan is
+// Host side of the masked form of the multi-query scan (vg_scan_multi.h, VG_MQ_MASKED): kernel table, launch, and the batch entry points.  The plan is
 // the multi-query scan's (vg_multi_plan: 4 queries per pass with up to 3 chunks per lane, 2 with 4 or 6; f32 / uint8 / int8 rows that
 // fit the register-resident shapes); a pass reads the batches of rows that hold an allowed row, once, for all its queries.  Shapes
 // without a multi-query form (f16 / bf16, long rows) are answered by nq single masked scans (vg_scan_masked.hip): same contract, no
 // sharing.  A translation unit of its own, like vg_multi.hip: its kernel instances compile next to the others, not after them.
 #include "vg_internal.h"
 
-#include "vg_scan_multi_masked.h"
+#include "vg_scan_multi.h"
 #include "vg_pick.h"
 
-struct MultiMaskedFamily {
-    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_masked_kernel<VT, ACC, U, NQ, true>; }
-};
-
 // (queries per pass, launch shape, kernel) of the masked multi-query scan; 0 queries per pass: the fallback serves the shape
-static int fused_multi_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn, vg_pick_multi_fn_t pick = vg_pick_multi<MultiMaskedFamily>) {
+static int fused_multi_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_t *fn, vg_pick_multi_fn_t pick = vg_pick_multi<MultiFamily<VG_MQ_MASKED>>) {
     const int NQ = vg_multi_plan(c, metric, s);
     if (NQ == 0) return 0;
     scan_fn_t f = pick(c->vtype, vg_metric_to_acc(metric), s->U, NQ);
@@ -145,7 +141,7 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
 
 extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
                                               int *out_counts) {
-    const VgFusedBatchForm form = {"vg_scan_topk_batch_masked", vg_pick_multi<MultiMaskedFamily>, {"vg_scan_topk_masked", vg_pick_scan_masked, true, false}};
+    const VgFusedBatchForm form = {"vg_scan_topk_batch_masked", vg_pick_multi<MultiFamily<VG_MQ_MASKED>>, {"vg_scan_topk_masked", vg_pick_scan_masked, true, false}};
     return vg_fused_batch_run(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts);
 }
 

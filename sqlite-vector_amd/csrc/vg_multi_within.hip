@@ -1,7 +1,7 @@
 // vg_multi_within.hip - batch range scans: every row within a radius, for many queries with a radius each (vg_scan_within_batch,
 // include/vectorgpu.h).
 //
-// Host side of the multi-query range scan (vg_scan_multi_within.h): kernel table, launch, the overflow protocol and the entry points.
+// Host side of the range form of the multi-query scan (vg_scan_multi.h, VG_MQ_WITHIN): kernel table, launch, the overflow protocol and the entry points.
 // The plan is the multi-query scan's (vg_multi_plan: 4 queries per pass with up to 3 chunks per lane, 2 with 4 or 6; f32 / uint8 /
 // int8 rows that fit the register-resident shapes).  Shapes without a multi-query form (f16 / bf16, long rows) are answered by nq
 // single range scans (vg_scan_within.hip): same contract, no sharing.
@@ -13,17 +13,13 @@
 // returned.  From the counted keys of a query on - sorted, cut to `limit`, held, read - the result path is the single range scan's
 // (vg_scan_within.hip: vg_within_collect / _finish / _held_*); the batch's held results stay apart from the single scan's on a handle.
 //
-// The masked batch (vg_scan_within_batch_masked) is the same host code: its kernels are vg_scan_multi_within_masked.h's, held by
+// The masked batch (vg_scan_within_batch_masked) is the same host code: its kernels are the VG_MQ_WITHIN | VG_MQ_MASKED instances, held by
 // vg_multi_within_masked.hip, its launches set ScanArgs.mask, its fallback is nq single MASKED range scans - nothing else differs, and
 // it leaves its held results where the unmasked batch leaves its own.
 #include "vg_internal.h"
 
-#include "vg_scan_multi_within.h"
+#include "vg_scan_multi.h"
 #include "vg_pick.h"
-
-struct MultiWithinFamily {
-    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_within_kernel<VT, ACC, U, NQ, true>; }
-};
 
 // (queries per pass, launch shape, kernel) of the multi-query range scan, unmasked or masked; 0 queries per pass: the fallback serves
 // the shape.  Every instance of both tables compiles without scratch or spills: the masked plan is the unmasked one.
@@ -31,7 +27,7 @@ static int mw_plan(const vg_corpus *c, int metric, bool masked, VgShape *s, scan
     const int NQ = vg_multi_plan(c, metric, s);
     if (NQ == 0) return 0;
     const int acc = vg_metric_to_acc(metric);
-    scan_fn_t f = masked ? vg_pick_multi_within_masked(c->vtype, acc, s->U, NQ) : vg_pick_multi<MultiWithinFamily>(c->vtype, acc, s->U, NQ);
+    scan_fn_t f = masked ? vg_pick_multi_within_masked(c->vtype, acc, s->U, NQ) : vg_pick_multi<MultiFamily<VG_MQ_WITHIN>>(c->vtype, acc, s->U, NQ);
     if (fn) *fn = f;
     return f ? NQ : 0;
 }

@@ -1,13 +1,15 @@
 // vg_pick.h - the kernel tables of the scan variants: (element type, accumulation kind, chunks per lane[, queries per pass]) -> kernel.
 //
-// One ladder for the single-query kernels (vg_scan.h) and one for the multi-query kernels (vg_scan_multi*.h); WHICH kernel template
+// One ladder for the single-query kernels (vg_scan.h) and one for the multi-query kernel (vg_scan_multi.h); WHICH kernel template
 // a ladder walks is its family - a struct with templated static getters (a function template cannot be a template argument):
 //     single-query   template <int VT, int ACC, int U> static scan_fn_t fn();         the register-resident kernel
 //                    static const bool has_long;                                       rows no shape covers are served ...
 //                    template <int VT, int ACC> static scan_fn_t long_fn();            ... by this kernel (only when has_long)
 //     multi-query    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn();
+// The single-query families are defined by the units that hold them; the multi-query kernel has ONE family for all its forms,
+// MultiFamily<FORM> below (FORM: the VG_MQ_* flags of vg_scan_multi.h).
 // A getter is instantiated only for the combinations a ladder names, and a kernel only where its getter is: the translation unit
-// that defines a family holds that family's kernels, and exactly these -
+// that walks a ladder over a family holds that family's kernels, and exactly these -
 //     single-query   all five element types x L2 / cosine / dot / L1 x U in {1, 2, 3, 4, 6, 8}; A_COSN (cached row norms) for
 //                    f16 / bf16 only; the long-row kernel without A_COSN
 //     multi-query    f32 / uint8 / int8 x L2 / cosine / dot / L1; U in {1, 2, 3} at 4 queries per pass, U in {4, 6} at 2
@@ -17,6 +19,12 @@
 #include "vg_internal.h"
 
 #include "vg_device.h"
+#include "vg_scan_multi.h"
+
+template <int FORM>
+struct MultiFamily {
+    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn() { return vg_scan_multi_kernel<VT, ACC, U, NQ, FORM>; }
+};
 
 template <class F, int VT, int ACC>
 static scan_fn_t vg_pick_u(int U) {

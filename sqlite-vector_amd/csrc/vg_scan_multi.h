@@ -1,22 +1,96 @@
-// vg_scan_multi.h - several queries per pass over the corpus.
+// vg_scan_multi.h - several queries per pass over the corpus: ONE kernel, its forms are compile-time flags.
 //
-// The batched entry point's path for every shape the matrix-core kernels (vg_batch.hip / vg_batch_i8.hip) do not
-// serve on f32 / uint8 / int8 corpora: L1, rows > 512 floats / 1024 bytes, 32 < k <= 64.  NQ queries share every row
-// load of the HBM-bound scan (f16 / bf16 scans are bound by their f64 arithmetic and gain nothing - vg_multi.hip).
-// The arithmetic of each (query, row) pair is the single-query kernel's (same Accum, same epilogue), so int8 / uint8 results are bit-identical to the single scans and f32 results differ at most by the
-// summation order of another launch shape.  Top-k mode only, k <= 64.
-//   a.query : NQ zero-padded queries back to back (nch * 16 bytes each)
-//   a.cand  : [NQ][gridDim.x][64] candidate keys, merged per query by vg_merge_kernel (grid NQ)
-// Register budget: NQ * U query chunks + 2 * U row chunks per lane -> NQ = 4 with U <= 3, NQ = 2 with U <= 6.
+// The batched entry points' path for every shape the matrix-core kernels (vg_batch.hip / vg_batch_i8.hip) do not serve on f32 /
+// uint8 / int8 corpora: L1, rows > 512 floats / 1024 bytes, 32 < k <= 64 - and the path of the masked, paged and range batches.  NQ
+// queries, staged through LDS into registers, share every row load of the HBM-bound scan
+// (f16 / bf16 scans are bound by their f64 arithmetic and gain nothing - vg_multi.hip).  The arithmetic of each (query, row) pair is
+// the single-query kernel's (same Accum<VT, ACC> chunk order, same finish / vg_clamp epilogue) in EVERY form, so int8 / uint8 results
+// are bit-identical to the single scans and f32 results differ at most by the summation order of another launch shape.
+// Double-buffered only: no prefetch ring for short uint8 / int8 rows.
+//
+// FORM is a set of flags; each changes what happens to a distance, none how it is computed:
+//   (none)           top-k, k <= 64: one candidate list per query (`mine`, `thr`), NQ publishes at the end, merged per query by
+//                    vg_merge_kernel (grid NQ).
+//   VG_MQ_MASKED     only the rows the handle's mask allows, threaded through the way the MASKED branch of vg_scan_kernel does it
+//                    (vg_scan.h):
+//                      * the bits of a batch (vg_mask_bits: wave-uniform, one scalar load) are fetched ONE loop step ahead of the row
+//                        prefetch whose addresses they decide - `mnext` is asked for while the batch in front of it is reduced;
+//                      * a batch without an allowed row points its U loads at the zero chunk (one cache line, always a hit) and does
+//                        nothing else: a scalar branch around all NQ reductions;
+//                      * a row whose bit is clear is computed with its batch and offered to no query (the bit is folded into `owner`).
+//                    So a pass reads the batches that hold an allowed row, once, for NQ queries.  Without the flag mask_of() is the
+//                    constant ~0 and the compiler folds the whole pipeline away.
+//   VG_MQ_AFTER      top-k behind a cursor per query (the paged scans): a row is offered to query n's list only when its key is
+//                    >= a.floor[n] (the key just behind that query's cursor; VG_EMPTY_KEY in the pad slot of a ragged pass admits
+//                    nothing).  The NQ floors are loaded once before the loop, made wave-uniform (vg_uniform64) and live in scalar
+//                    registers (2 per query); the compare is one 64-bit v_cmp folded into the offer's predicate.  This is the batch
+//                    path of the paged scans, NOT the matrix-core filters: their candidate thresholds assume an unrestricted top-k - a
+//                    floor moves the k-th best distance arbitrarily far from what their lower bounds were tuned against.
+//   VG_MQ_WITHIN     range scan in place of the candidate lists: per query the compare against that query's radius and one ballot.
+//                    Only a batch with a match does more: BEHIND the arithmetic of all NQ queries, where the current row chunks are
+//                    dead (the queue / flush temporaries then do not add to the loop's peak register pressure), the keys are parked
+//                    in the wavefront's LDS queue of their query and leave in bursts (vg_mw_offer / vg_mw_flush below).  Nothing is
+//                    written for a row that matches no query: a batch without a match costs NQ ballots.  What a query keeps between
+//                    batches - radius and queue fill - is wave-uniform and lives in scalar registers (`wave` goes through
+//                    readfirstlane so that the queue addresses stay scalar); region and capacity are read from the descriptors when
+//                    a burst leaves.  Not combined with VG_MQ_AFTER.
+// The forms were five hand-copied loops; the code generated for every instance of this template was checked identical to that of the
+// copy it replaced (instruction text, registers, spills, scratch, LDS: DESIGN.md 3.6) at the commit that folded them.
+//
+//   a.query         : NQ zero-padded queries back to back (nch * 16 bytes each); WITHIN: and BEHIND them NQ VgWithinQuery descriptors
+//   a.mask          : (MASKED) ceil(n_rows / 64) words, bits behind the last row clear
+//   a.floor         : (AFTER) NQ keys
+//   a.cand          : (top-k forms) [NQ][gridDim.x][64] candidate keys
+//   descriptor n    : (WITHIN) the [count | cap keys] region of query n, its capacity and its radius (a float: the host rounds down)
+//   a.store_lds_off : (WITHIN) byte offset in dynamic LDS of the key queues, [NQ][wavefront][VG_WITHIN_QUEUE]
+// Register budget: NQ * U query chunks + 2 * U row chunks per lane -> NQ = 4 with U <= 3, NQ = 2 with U <= 6.  The mask lives in scalar
+// registers (three words of bits: current, prefetched, in flight, and the mask pointer).  A range form does without the two 64-bit
+// list words per query: it is at or below the VGPR figure of the top-k instance of the same <VT, ACC, U, NQ>.  DESIGN.md 3.9 - 3.13
+// have the compiler's figures of every instance.
 #pragma once
 
 #include "vg_scan.h"
 
-template <int VT, int ACC, int U, int NQ, bool NT>          // VT: T_F32 / T_U8 / T_I8
+enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4 };
+
+struct VgWithinQuery {                 // 32 bytes, read through wave-uniform addresses (scalar loads)
+    unsigned long long *out;           // [count | cap keys]; the count keeps counting past cap
+    unsigned long long cap;
+    float r;                           // rows with d <= r and d finite match
+    uint32_t pad[3];
+};
+
+// Kernel-local forms of vg_within_offer / vg_within_flush (vg_scan.h, which the single range scan keeps as it is): the same protocol -
+// keys parked in the wavefront's queue, one atomicAdd of the burst size, the count keeps counting past the capacity - with the burst's
+// room worked out in scalar registers and the stores addressed by a 32-bit lane offset against a wave-uniform base, so that the rare
+// path holds a handful of vector temporaries next to the NQ * U query chunks instead of 64-bit indices and addresses per lane.
+__device__ inline void vg_mw_flush(const uint64_t *queue, int &queued, unsigned long long *out, unsigned long long cap, int lane) {
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(out, (unsigned long long)queued);
+    base = vg_readlane64(base, 0);
+    const unsigned long long left = base < cap ? cap - base : 0ull;                    // keys that still fit (wave-uniform)
+    const int room = left < (unsigned long long)queued ? (int)left : queued;
+    unsigned long long *dst = out + 1 + base;                                          // wave-uniform
+    for (int i = lane; i < room; i += VG_WAVE) dst[i] = queue[i];
+    queued = 0;
+}
+__device__ inline void vg_mw_offer(uint64_t key, bool match, uint64_t *queue, int &queued, unsigned long long *out, unsigned long long cap, int lane) {
+    const unsigned long long m = __ballot(match);
+    if (m == 0ull) return;
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (match) queue[queued + rank] = key;
+    queued += __popcll(m);
+    if (queued > VG_WITHIN_QUEUE - VG_WAVE) vg_mw_flush(queue, queued, out, cap, lane);
+}
+
+template <int VT, int ACC, int U, int NQ, int FORM>          // VT: T_F32 / T_U8 / T_I8; FORM: VG_MQ_* flags
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
+    constexpr bool MASKED = (FORM & VG_MQ_MASKED) != 0, AFTER = (FORM & VG_MQ_AFTER) != 0, WITHIN = (FORM & VG_MQ_WITHIN) != 0;
+    static_assert(!(AFTER && WITHIN), "a range scan has no cursor");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
-    const int wave = threadIdx.x >> 6;
+    // (WITHIN: wave-uniform by construction; readfirstlane says so to the compiler, and the queue addresses stay scalar)
+    const int wave = WITHIN ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : (int)(threadIdx.x >> 6);
     const int lpr_log2 = a.lpr_log2;
     const int lpr = 1 << lpr_log2;
     const int rpb = VG_WAVE >> lpr_log2;
@@ -37,37 +111,93 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         }
         qstat[n] = Accum<VT, ACC>::template query_stat<U>(q[n], lpr_log2);
     }
-    uint64_t mine[NQ], thr[NQ];
-#pragma unroll
-    for (int n = 0; n < NQ; ++n) { mine[n] = VG_EMPTY_KEY; thr[n] = VG_EMPTY_KEY; }
+    // what a query keeps between batches: its candidate list (and floor), or its radius and queue
+    uint64_t mine[NQ], thr[NQ], floor_key[NQ];
     const int k = a.k;
+    const VgWithinQuery *wq = reinterpret_cast<const VgWithinQuery *>(a.query + (long long)NQ * a.nch * 16);
+    float r[NQ];
+    uint64_t *queue[NQ];
+    int queued[NQ];
+#pragma unroll
+    for (int n = 0; n < NQ; ++n) {
+        if constexpr (WITHIN) {
+            r[n] = wq[n].r;
+            queue[n] = reinterpret_cast<uint64_t *>(smem + a.store_lds_off) + (n * VG_WAVES_PER_BLOCK + wave) * VG_WITHIN_QUEUE;
+            queued[n] = 0;
+        } else {
+            mine[n] = VG_EMPTY_KEY;
+            thr[n] = VG_EMPTY_KEY;
+            if constexpr (AFTER) floor_key[n] = vg_uniform64(a.floor[n]);
+        }
+    }
 
     const long long nbatch = (a.n_rows + rpb - 1) / rpb;
     const long long wstride = (long long)gridDim.x * VG_WAVES_PER_BLOCK;
     long long b = (long long)blockIdx.x * VG_WAVES_PER_BLOCK + wave;
+    // MASKED: the mask bits of a batch (wave-uniform; 0 behind the last batch).  Otherwise every batch in range is live.
+    auto mask_of = [&](long long batch) -> uint64_t {
+        if constexpr (MASKED) return vg_mask_bits(a.mask, batch * rpb, rpb, batch < nbatch);
+        else return ~0ull;
+    };
     uint4 cur[U], nxt[U];
-    vg_load_batch<U, NT>(cur, a.rows, b * rpb + rib, (b < nbatch) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
+    uint64_t mcur = mask_of(b);
+    uint64_t mnext = mask_of(b + wstride);
+    vg_load_batch<U, true>(cur, a.rows, b * rpb + rib, (b < nbatch && mcur != 0ull) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
     while (b < nbatch) {
         const long long bn = b + wstride;
-        vg_load_batch<U, NT>(nxt, a.rows, bn * rpb + rib, (bn < nbatch) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
-        const long long row = b * rpb + rib;
-        const bool owner = (sub == 0) && (row < a.n_rows);
+        const uint64_t mnxt = mnext;                                   // the bits of batch bn: asked for one step ago
+        mnext = mask_of(bn + wstride);
+        vg_load_batch<U, true>(nxt, a.rows, bn * rpb + rib, (bn < nbatch && mnxt != 0ull) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
+        if (mcur != 0ull) {
+            const long long row = b * rpb + rib;
+            const bool owner = (sub == 0) && (row < a.n_rows) && ((mcur >> rib) & 1ull);      // the row's lane, and the row is allowed
+            // (WITHIN: every query's distance first, one ballot each; the rare batch with a match parks its keys BEHIND the arithmetic)
+            float d[NQ];
+            unsigned long long any = 0ull;
 #pragma unroll
-        for (int n = 0; n < NQ; ++n) {
-            Accum<VT, ACC> acc;
-            acc.init();
+            for (int n = 0; n < NQ; ++n) {
+                Accum<VT, ACC> acc;
+                acc.init();
 #pragma unroll
-            for (int u = 0; u < U; ++u) acc.chunk(q[n][u], cur[u]);
-            const float d = vg_clamp(acc.finish(qstat[n], lpr_log2, a.root));
-            vg_list_offer(vg_make_key(d, (uint32_t)row), owner && (d < INFINITY), mine[n], thr[n], lane, k);
+                for (int u = 0; u < U; ++u) acc.chunk(q[n][u], cur[u]);
+                const float dn = vg_clamp(acc.finish(qstat[n], lpr_log2, a.root));
+                if constexpr (WITHIN) {
+                    d[n] = dn;
+                    // d <= r is false for NaN; +Inf never matches, whatever the radius (the single range scan's rule)
+                    any |= __ballot(owner && (d[n] <= r[n]) && (d[n] < INFINITY));
+                } else {
+                    // (a top-k form uses the distance at once, NOT through d[]: with it the ten f32 L1 floor instances came out with
+                    //  another, equivalent, predicate sequence than the copies had)
+                    const uint64_t key = vg_make_key(dn, (uint32_t)row);
+                    vg_list_offer(key, owner && (dn < INFINITY) && (!AFTER || key >= floor_key[n]), mine[n], thr[n], lane, k);
+                }
+            }
+            if constexpr (WITHIN) if (any != 0ull) {
+                // (the lane index goes through an opaque move: queue and store addresses derived from it are then worked out HERE, in the
+                //  rare path, instead of being hoisted out of the loop into vector registers that stay live across the arithmetic)
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                // (region and capacity are read from the descriptors here, by scalar loads, rather than held in 4 scalar registers per query
+                //  across the loop: with them the NQ = 4 instances ran out of scalar registers)
+                const VgWithinQuery *w = wq;
+                asm volatile("" : "+s"(w));
+#pragma unroll
+                for (int n = 0; n < NQ; ++n)
+                    vg_mw_offer(vg_make_key(d[n], (uint32_t)row), owner && (d[n] <= r[n]) && (d[n] < INFINITY), queue[n], queued[n], w[n].out, w[n].cap, ln);
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        mcur = mnxt;
         b = bn;
     }
 #pragma unroll
     for (int n = 0; n < NQ; ++n) {
-        __syncthreads();                                   // query staging area / the previous publish is done with LDS
-        vg_block_publish(smem, mine[n], k, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE);
+        if constexpr (WITHIN) {
+            if (queued[n] > 0) vg_mw_flush(queue[n], queued[n], wq[n].out, wq[n].cap, lane);
+        } else {
+            __syncthreads();                               // query staging area / the previous publish is done with LDS
+            vg_block_publish(smem, mine[n], k, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE);
+        }
     }
 }

@@ -320,7 +320,7 @@ def test_batch_small_corpus_and_fallback_shapes(pkg, orc):
 
 @pytest.mark.parametrize("vt", [dg.F32, dg.F16, dg.BF16, dg.I8, dg.U8])
 def test_batch_multi_query_scan_vs_single_scans(pkg, orc, vt, monkeypatch):
-    """Batches the matrix-core kernels do not serve (f16 / bf16, L1, k > 32, long rows) run vg_scan_multi_kernel: 4
+    """Batches the matrix-core kernels do not serve (f16 / bf16, L1, k > 32, long rows) run vg_scan_multi_kernel's plain form: 4
     (2 for f16 / bf16) queries share every pass over the rows.  Same arithmetic per (query, row) as the single scan:
     int8 / uint8 bit-exact, floats <= 1e-5 relative (summation order), same total order of the results."""
     for dim, n in ((7, 300), (100, 5000), (384, 9001), (1000, 2500), (1536, 1200)):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU-box measurement of the multi-query scan (vg_scan_multi_kernel), the batch path of the shapes the matrix-core
+"""GPU-box measurement of the multi-query scan (the plain top-k form of vg_scan_multi_kernel), the batch path of the shapes the matrix-core
 kernels do not serve: wall time per batch with VG_MULTI_SCAN=1 against nq single scans (VG_MULTI_SCAN=0), plus a
 result comparison of the two.
     python tools_multi_bench.py [--rows 10000000] [--nq 64]
