@@ -35,8 +35,6 @@
 
 #include "vg_batch_common.h"
 
-typedef float vgb_f32x16 __attribute__((ext_vector_type(16)));
-
 #define VGB_THREADS 256
 #define VGB_WAVES 4
 #define VGB_QPW 32                      // queries per wavefront
@@ -72,21 +70,9 @@ struct BatchArgs {
 };
 enum { VGB_DOT = 0, VGB_COS = 1, VGB_L2 = 2 };
 
-typedef float vgb_f32x4 __attribute__((ext_vector_type(4)));
 #ifndef VGB_BPIPE
 #define VGB_BPIPE 4                      // B-operand ring depth, in k-steps of 4 MFMAs
 #endif
-
-// (free functions: clang rejects asm operands that name captured variables inside a generic lambda)
-template <int OFF>
-__device__ __forceinline__ void vgb_lds_read128(vgb_f32x4 &dst, uint32_t lds_addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_addr), "n"(OFF) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void vgb_wait_lds(vgb_f32x4 &v) {        // v is usable once at most N later LDS reads are in flight
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N));
-}
-
 
 template <int NT, int MODE>
 __global__ __launch_bounds__(VGB_THREADS, 1) void vg_batch_kernel(BatchArgs a) {
@@ -147,9 +133,8 @@ __global__ __launch_bounds__(VGB_THREADS, 1) void vg_batch_kernel(BatchArgs a) {
     const long long tile_first = a.tile_begin + (long long)part * a.tiles_per_part;
     const long long tile_last = min(tile_first + a.tiles_per_part, a.tile_end);
     // One 1-KiB DMA piece: piece index pc in [0, 8*PIECES) = (row slot i, piece p) of this wavefront's 8 rows.
-    // LDS-DMA from inline asm: hipcc's waitcnt pass does not see it, so it cannot put "s_waitcnt vmcnt(0)" in front
-    // of every ds_read of the CURRENT tile while the NEXT tile is in flight (it did with the builtin: 16 exposed HBM
-    // round trips per tile).  Completion is waited for explicitly before the tile barrier.
+    // LDS-DMA from inline asm (vg_batch_dma.h; with the builtin the compiler's waits cost 16 exposed HBM round trips per
+    // tile).  Completion is waited for explicitly before the tile barrier.
     // Addressing is scalar: SGPR pair = row base, one VGPR per piece column = lane byte offset (computed once);
     // M0 = wave-uniform LDS byte address of the piece; lane i lands at M0 + 16*i; inactive lanes write nothing.
     const uint32_t n_rows32 = (uint32_t)a.n_rows;
@@ -168,13 +153,7 @@ __global__ __launch_bounds__(VGB_THREADS, 1) void vg_batch_kernel(BatchArgs a) {
         grow = grow < n_rows32 ? grow : n_rows32 - 1u;
         const uint8_t *sbase = reinterpret_cast<const uint8_t *>(a.rows) + (unsigned long long)grow * stride_b;
         const uint32_t lds_dst = lds_tile0 + (uint32_t)((buf * TILE_FLOATS + rr * PITCH + p * 256) * 4);
-        // lanes past the end of the row are switched off by EXEC inside the asm (no branch: the k loop stays ONE
-        // basic block, so the scheduler can keep the B-operand ds_reads several MFMAs ahead of their use)
-        uint32_t keep;
-        uint64_t keep_exec;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %4\n\ts_and_b64 exec, exec, %5\n\t"
-                     "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep), "=&s"(keep_exec) : "v"(lane_off[p]), "s"(sbase), "s"(lds_dst), "s"(piece_mask[p]) : "memory", "scc");
+        vgb_dma_masked(lane_off[p], sbase, lds_dst, piece_mask[p]);      // (lanes past the end of the row: off)
     };
     constexpr int NPIECE = (VGB_TILE / VGB_WAVES) * PIECES;
 
@@ -433,11 +412,7 @@ extern "C" int vg_batch_merge_launch(const uint64_t *dev_cand, int nq_pad, int l
 
 template <int NT, int MODE>
 static int launch_nt_mode(const BatchArgs &a, int blocks, size_t smem, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(vg_batch_kernel<NT, MODE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((vg_batch_kernel<NT, MODE>), dim3((unsigned)blocks), dim3(VGB_THREADS), smem, stream, a);
-    return (int)hipGetLastError();
+    return vgb_launch(vg_batch_kernel<NT, MODE>, blocks, VGB_THREADS, smem, stream, a);
 }
 template <int NT>
 static int launch_nt(const BatchArgs &a, int blocks, size_t smem, hipStream_t stream) {
@@ -508,8 +483,7 @@ extern "C" int vg_batch_launch(const float *dev_rows, long long n_rows, long lon
         a.npart_total = 2 * npart;
         a.tile_begin = 0; a.tile_end = pre; a.tiles_per_part = (int)(pre / npart); a.part_base = 0; a.init_keys = nullptr;
         if ((rc = launch(a)) != 0) return rc;
-        hipLaunchKernelGGL(vg_batch_merge_kernel, dim3((unsigned)nq_pad), dim3(256), 0, stream, (const uint64_t *)dev_cand,
-                           nq_pad, a.npart_total, npart, k, dev_out_keys);
+        if ((rc = vg_batch_merge_launch(dev_cand, nq_pad, a.npart_total, npart, k, dev_out_keys, stream)) != 0) return rc;
         a.tile_begin = pre; a.tile_end = ntiles; a.tiles_per_part = (int)((ntiles - pre + npart - 1) / npart);
         a.part_base = npart; a.init_keys = dev_out_keys;
         if ((rc = launch(a)) != 0) return rc;
@@ -518,7 +492,5 @@ extern "C" int vg_batch_launch(const float *dev_rows, long long n_rows, long lon
         a.tile_begin = 0; a.tile_end = ntiles; a.tiles_per_part = tiles_per_part; a.part_base = 0; a.init_keys = nullptr;
         if ((rc = launch(a)) != 0) return rc;
     }
-    hipLaunchKernelGGL(vg_batch_merge_kernel, dim3((unsigned)nq_pad), dim3(256), 0, stream, (const uint64_t *)dev_cand,
-                       nq_pad, a.npart_total, a.npart_total, k, dev_out_keys);
-    return (int)hipGetLastError();
+    return vg_batch_merge_launch(dev_cand, nq_pad, a.npart_total, a.npart_total, k, dev_out_keys, stream);
 }

@@ -1,4 +1,7 @@
-// vg_batch_common.h - pieces shared by the batched kernels (vg_batch.hip: f32, vg_batch_i8.hip: uint8 / int8).
+// vg_batch_common.h - what the matrix-core batch kernels share (vg_batch.hip: f32, vg_batch_h.hip / vg_batch_hl.hip: f16 / bf16 and f32
+// behind a bf16 filter, vg_batch_i8.hip: uint8 / int8, vg_batch_q8.hip: f32 behind an int8 filter): the compile-time loop and the list
+// insert of the kernels, the device-side primitives of vg_batch_dma.h, and the host side - row-length buckets, the kernel launch, the
+// merge, the staged-pass driver.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -6,6 +9,7 @@
 
 #include <type_traits>
 
+#include "vg_batch_dma.h"
 #include "vg_lists.h"
 #include "vg_switches.h"
 
@@ -65,4 +69,60 @@ static inline int vgb_stage_bounds(long long ntiles, long long pre_tiles, long l
     }
     bounds[++n] = ntiles;
     return n;
+}
+
+// ---- the rest of the host side
+// per query: its lists in the candidate buffer -> the final k keys (vg_batch.hip)
+extern "C" int vg_batch_merge_launch(const uint64_t *dev_cand, int nq_pad, int lists_per_query, int npart, int k,
+                                     uint64_t *dev_out_keys, hipStream_t stream);
+
+// the k-step counts (32 bytes of a row each) the kernels with 64-k-step register files are instantiated for; 0: not served
+static inline int vgb_ksteps(long long stride_bytes) { return (int)((stride_bytes + 31) / 32); }
+static inline int vgb_ntb64(long long stride_bytes) {
+    const int ntb = vgb_ksteps(stride_bytes);
+    if (ntb <= 8) return 8;
+    if (ntb <= 16) return 16;
+    if (ntb <= 24) return 24;
+    if (ntb <= 32) return 32;
+    if (ntb <= 48) return 48;                                     // rows of 1 - 2 KiB: 4-wavefront workgroups
+    if (ntb <= 64) return 64;
+    return 0;
+}
+
+// one kernel launch with `smem` bytes of dynamic LDS (the kernel's limit is raised to it first); 0 or a hipError_t
+template <typename Kernel, typename Args>
+static inline int vgb_launch(Kernel kernel, int blocks, int threads, size_t smem, hipStream_t stream, const Args &args) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3((unsigned)threads), smem, stream, args);
+    return (int)hipGetLastError();
+}
+
+// The pre-pass over tiles [0, pre) (pre == 0: none), then the staged real passes above: every pass writes - and every merge reads -
+// lists 0 .. a.npart - 1 of a query; a stage after the first starts from the merged keys (a.seed, a.init_keys).  launch_pre(a) /
+// launch_stage(a) launch one pass over [a.tile_begin, a.tile_end) - one kernel, or filter then exact evaluation.  How large `pre` is
+// stays with the caller: the kernels differ there on purpose.
+template <typename Args, typename LaunchPre, typename LaunchStage>
+static inline int vgb_run_staged(Args &a, long long ntiles, long long pre, int default_growth_pct, uint64_t *dev_out_keys, hipStream_t stream,
+                                 LaunchPre launch_pre, LaunchStage launch_stage) {
+    const int npart = a.npart;
+    int rc;
+    a.npart_total = npart; a.part_base = 0; a.seed = 0; a.init_keys = nullptr;
+    if (pre > 0) {
+        a.tile_begin = 0; a.tile_end = pre; a.tiles_per_part = (int)((pre + npart - 1) / npart);
+        if ((rc = launch_pre(a)) != 0) return rc;
+        if ((rc = vg_batch_merge_launch(a.cand, a.nq_pad, a.npart_total, npart, a.k, dev_out_keys, stream)) != 0) return rc;
+        a.init_keys = dev_out_keys;
+    }
+    long long bounds[16];
+    const int nstages = vgb_stage_bounds(ntiles, pre, bounds, 16, default_growth_pct);
+    for (int s = 0; s < nstages; ++s) {
+        a.tile_begin = bounds[s]; a.tile_end = bounds[s + 1];
+        a.tiles_per_part = (int)((a.tile_end - a.tile_begin + npart - 1) / npart);
+        a.seed = (s > 0) ? 1 : 0;
+        if ((rc = launch_stage(a)) != 0) return rc;
+        if ((rc = vg_batch_merge_launch(a.cand, a.nq_pad, a.npart_total, npart, a.k, dev_out_keys, stream)) != 0) return rc;
+        a.init_keys = dev_out_keys;
+    }
+    return 0;
 }

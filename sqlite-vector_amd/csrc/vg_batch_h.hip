@@ -71,20 +71,7 @@ extern "C" int vg_batch_h_timing(unsigned long long *out8, int reset) {
     if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(vgh_ticks), z, sizeof(z)) != hipSuccess) return -1; }
     return 0;
 }
-#define VGH_TICK(var) const unsigned long long var = __builtin_readcyclecounter()
-#else
-#define VGH_TICK(var)
 #endif
-
-template <int OFF>
-__device__ __forceinline__ void vgh_lds_read128(vgh_i32x4 &dst, uint32_t lds_addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_addr), "n"(OFF) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void vgh_wait_lds(vgh_i32x4 &v) {
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N));
-}
-
 
 // NTB = 32-byte k-steps per row (rows up to NTB * 16 elements)
 // BOUND = the pre-pass variant: no exact evaluation at all.  A pair that passes the filter enters its list with an UPPER
@@ -136,7 +123,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
     const int xchunks = (int)(a.xstride / 16);                           // 16-byte chunks of an exact-evaluation row
 
     // ---- A operand: lane (x, h) keeps bytes [32t + 16h, +16) of query x
-    vgh_i32x4 areg[NTB];
+    vgb_i32x4 areg[NTB];
     {
         if constexpr (XF32) {                                             // f32 query -> bf16 (round to nearest even) on the fly
             const uint8_t *qrow = a.xqueries + (long long)(q0 + x) * a.xstride;
@@ -150,7 +137,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
                 uint4 v0 = make_uint4(0u, 0u, 0u, 0u), v1 = make_uint4(0u, 0u, 0u, 0u);
                 if (off + 16 <= a.xstride) v0 = *reinterpret_cast<const uint4 *>(qrow + off);
                 if (off + 32 <= a.xstride) v1 = *reinterpret_cast<const uint4 *>(qrow + off + 16);
-                areg[t] = vgh_i32x4{bf(v0.x, v0.y), bf(v0.z, v0.w), bf(v1.x, v1.y), bf(v1.z, v1.w)};
+                areg[t] = vgb_i32x4{bf(v0.x, v0.y), bf(v0.z, v0.w), bf(v1.x, v1.y), bf(v1.z, v1.w)};
             });
         } else {
             const uint8_t *qrow = a.queries + (long long)(q0 + x) * a.stride;
@@ -159,7 +146,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
                 const int off = 32 * t + 16 * h;
                 uint4 v = make_uint4(0u, 0u, 0u, 0u);
                 if (off < a.stride) v = *reinterpret_cast<const uint4 *>(qrow + off);
-                areg[t] = vgh_i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+                areg[t] = vgb_i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
             });
         }
     }
@@ -188,7 +175,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
         const float qqx = (float)qq_w[x];
         if ((qsp_w[x] != 0u) || !(qqx >= VGH_NORM_LO && qqx <= VGH_NORM_HI)) {
 #pragma unroll
-            for (int t = 0; t < NTB; ++t) areg[t] = vgh_i32x4{0, 0, 0, 0};
+            for (int t = 0; t < NTB; ++t) areg[t] = vgb_i32x4{0, 0, 0, 0};
         }
     }
     if (lane < VGH_QPW) {                               // thresholds: the pre-pass bound; padding queries never accept
@@ -246,12 +233,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
     auto dma_stat_group = [&](long long tile4, int slot) {          // tiles tile4 .. tile4 + 3
         const uint8_t *b0 = reinterpret_cast<const uint8_t *>(a.row_nn + tile4 * VGH_TILE);
         const uint32_t d0 = lds_rstat0 + (uint32_t)(slot * 512);
-        uint32_t keep;
-        uint64_t keep_exec;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_and_b64 exec, exec, %5\n\t"
-                     "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-                     "s_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep), "=&s"(keep_exec) : "v"(stat_goff), "s"(b0), "s"(d0), "s"(stat_mask) : "memory", "scc");
+        vgb_dma_masked_exec_first(stat_goff, b0, d0, stat_mask);
     };
     auto dma_piece = [&](long long tile, uint32_t lane_goff, int buf, int i) {
         if (i >= np_mine) return;
@@ -260,34 +242,14 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
         if (pmask == 0) return;
         const uint8_t *sbase = a.rows + (unsigned long long)(tile * VGH_TILE) * stride_b + (unsigned)p * (tiled ? 1024u : 32u);
         const uint32_t lds_dst = lds_tile0 + (uint32_t)(buf * TILE_BYTES + p * 1024);
-        uint32_t keep;
-        uint64_t keep_exec;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %4\n\ts_and_b64 exec, exec, %5\n\t"
-                     "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep), "=&s"(keep_exec) : "v"(lane_goff), "s"(sbase), "s"(lds_dst), "s"(pmask) : "memory", "scc");
+        vgb_dma_masked(lane_goff, sbase, lds_dst, pmask);
     };
     // N (1 .. 4) whole pieces of the tile-major copy starting at piece slot i0, back to back
     auto dma_run = [&](long long tile, uint32_t lane_goff, int buf, auto i0c, auto nc) __attribute__((always_inline)) {
         constexpr int i0 = decltype(i0c)::value, N = decltype(nc)::value;
         const uint8_t *sbase = a.rows + (unsigned long long)(tile * VGH_TILE) * stride_b + (unsigned)(wave * NPIECE + i0) * 1024u;
         const uint32_t lds_dst = lds_tile0 + (uint32_t)(buf * TILE_BYTES + (wave * NPIECE + i0) * 1024);
-        uint32_t keep;
-        if constexpr (N == 1)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else if constexpr (N == 2)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else if constexpr (N == 3)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:3072\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
+        vgb_dma_run<N>(lane_goff, sbase, lds_dst);
     };
     // run r (pieces 4r .. 4r+3 of this wavefront's share) of a tile
     constexpr int NRUN = (NPIECE + 3) / 4;
@@ -298,8 +260,8 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
     };
 
     // (every lambda of this kernel is always_inline: left to its heuristics the compiler may keep one of the survivor-path
-    // lambdas as a real function, which puts everything it captures - gates, A - in scratch memory and makes the tile
-    // counter a VGPR, i.e. breaks the "s" operands of the DMA asm)
+    // lambdas as a real function, which puts everything it captures - gates, A - in scratch memory and breaks the "s"
+    // operands of the LDS-DMA primitives: vg_batch_dma.h)
     // ---- per-register filter state (register r of lane (x, h) belongs to query qi(r, h) = (r&3) + 8*(r>>2) + 4*h).
     // The accumulator of register r STARTS at init_reg[r] and the test after the k loop is
     //     acc[r] + gmul[r] * lane_term >= 0         lane_term: |x| (dot, cosine), (1 - c)/2 |x|^2 (L2)
@@ -440,11 +402,11 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
                 // and a list costs one insert per (query, tile) instead of one per passing row (half the inserts of
                 // the warm-up; each is an LDS round trip of the whole wavefront)
                 uint64_t key = ok ? vg_make_key(ub, (uint32_t)row) : VG_EMPTY_KEY;
-                key = vgh_min64(key, vgh_dpp64<VG_DPP_QUAD_PERM(1, 0, 3, 2)>(key));
-                key = vgh_min64(key, vgh_dpp64<VG_DPP_QUAD_PERM(2, 3, 0, 1)>(key));
-                key = vgh_min64(key, vgh_dpp64<VG_DPP_ROW_HALF_MIRROR>(key));
-                key = vgh_min64(key, vgh_dpp64<VG_DPP_ROW_MIRROR>(key));
-                key = vgh_min64(key, (uint64_t)__shfl_xor((unsigned long long)key, 16));       // lanes 0-31 / 32-63: one query each
+                key = vgb_min64(key, vgb_dpp64<VG_DPP_QUAD_PERM(1, 0, 3, 2)>(key));
+                key = vgb_min64(key, vgb_dpp64<VG_DPP_QUAD_PERM(2, 3, 0, 1)>(key));
+                key = vgb_min64(key, vgb_dpp64<VG_DPP_ROW_HALF_MIRROR>(key));
+                key = vgb_min64(key, vgb_dpp64<VG_DPP_ROW_MIRROR>(key));
+                key = vgb_min64(key, (uint64_t)__shfl_xor((unsigned long long)key, 16));       // lanes 0-31 / 32-63: one query each
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     const uint64_t c = vg_readlane64(key, 32 * hh);
@@ -480,7 +442,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
     unsigned n_pairs = 0;                                            // (wave-uniform)
 
     constexpr int BP = VGH_BPIPE < NTB ? VGH_BPIPE : NTB;
-    vgh_i32x4 bq[BP];
+    vgb_i32x4 bq[BP];
 #if VGH_TIMING
     unsigned long long tk_loop = 0, tk_gate = 0, tk_surv = 0, tk_dma = 0, tk_bar = 0;
     const unsigned long long tk_begin = __builtin_readcyclecounter();
@@ -493,7 +455,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
     constexpr bool PIPE = (VGH_PIPE != 0) && !BOUND;
     constexpr bool STAGGER = (VGH_STAGGER != 0) && FILT && WAVES == 8;
     constexpr int GPS = (16 + NTB - 1) / NTB;                         // gate registers per k step
-    vgh_f32x16 accp;                                                  // PIPE: the accumulators of the tile in front
+    vgb_f32x16 accp;                                                  // PIPE: the accumulators of the tile in front
 #pragma unroll
     for (int r = 0; r < 16; ++r) accp[r] = 0.0f;
     float nn_p = 0.0f;
@@ -501,7 +463,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
     bool have_p = false;
     const long long tile_stop = (PIPE && tile_first < tile_last) ? tile_last + 1 : tile_last;
     for (long long tile = tile_first; tile < tile_stop; ++tile) {
-        VGH_TICK(t0);
+        VGB_TICK(VGH_TIMING, t0);
         const long long ti = tile - tile_first;
         const int cur_buf = (int)(ti % NB), fill_buf = (int)((ti + NB - 1) % NB);
         const long long tile_next = min(tile + NB - 1, tile_last - 1);        // the tile whose DMA this trip issues
@@ -518,22 +480,22 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
         // instruction - the B-operand read and its wait, a DMA piece, the pipelined gate - breaks the back-to-back issue
         // (MI355X_MICROARCH.md: +43 cycles for the first extra issue slot); with two chains the next MFMA never waits for the last one.
         constexpr bool TWO = (VGH_CHAINS == 2) && PIPE && NTB >= 2;
-        vgh_f32x16 acc, acc1;
+        vgb_f32x16 acc, acc1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc[r] = init_reg[r]; acc1[r] = 0.0f; }
         const uint32_t baddr = lds_tile0 + (uint32_t)(cur_buf * TILE_BYTES + h * 512 + x * 16);
         vgb_static_for<0, BP>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
-            vgh_lds_read128<1024 * t>(bq[t], baddr);
+            vgb_lds_read128<1024 * t>(bq[t], baddr);
         });
         vgb_static_for<0, NTB>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
             constexpr int in_flight_after = (NTB - 1 - t) < (BP - 1) ? (NTB - 1 - t) : (BP - 1);
-            vgh_wait_lds<in_flight_after>(bq[t % BP]);
-            const vgh_i32x4 b = bq[t % BP];
+            vgb_wait_lds<in_flight_after>(bq[t % BP]);
+            const vgb_i32x4 b = bq[t % BP];
             if constexpr (TWO && (t & 1)) acc1 = vgh_mfma<FT>(areg[t], b, acc1);
             else acc = vgh_mfma<FT>(areg[t], b, acc);
-            if constexpr (t + BP < NTB && VGH_ABLATE < 5) vgh_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
+            if constexpr (t + BP < NTB && VGH_ABLATE < 5) vgb_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
             // the next tile's DMA (runs of up to four pieces) over the first half of the k loop; every fourth tile one of
             // the issuing wavefronts adds the row norms of the four tiles after this one
             constexpr int NTD = (NTB + 1) / 2;
@@ -567,7 +529,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
 #if VGH_TIMING
         if (!PIPE) asm volatile("s_nop 0" :: "v"(acc[15]));           // the k loop's last MFMA has retired
 #endif
-        VGH_TICK(t1);
+        VGB_TICK(VGH_TIMING, t1);
 
         // ---- tile boundary: one fused multiply-add + max per register, one ballot
         // (a row of ZEROS is judged like any other: every product is exactly 0 and so is the bound's |x| term - a corpus with empty vectors
@@ -602,7 +564,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
             }
         }
         if (VGH_ABLATE == 1) { if (pend) asm volatile("" :: "s"(pend)); pend = 0; mybits = 0u; }
-        VGH_TICK(t2);
+        VGB_TICK(VGH_TIMING, t2);
 #if VGH_TIMING
         if (pend) tk_cnt += 1;
 #endif
@@ -634,7 +596,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
                         else if (lane == 0) a.pair_counts[a.n_regions] = 1u;     // region full: the host repeats the batch (fused kernel)
                         ++n_pairs;
                     } else {
-                        VGH_TICK(te0);
+                        VGB_TICK(VGH_TIMING, te0);
                         // every lane holds the same value (butterfly sums): say so, or the branch in offer() counts as divergent
                         const float de = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, exact_distance(qi_u, row_u, nn_u))));
 #if VGH_TIMING
@@ -647,7 +609,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
                 }
             }
         }
-        VGH_TICK(t3);
+        VGB_TICK(VGH_TIMING, t3);
 #if VGH_TIMING
         if (!BOUND && pend) { tk_entries += 1; tk_phase += t3 - t2; }
 #endif
@@ -658,7 +620,7 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
             for (int r = 0; r < 16; ++r) accp[r] = TWO ? acc[r] + acc1[r] : acc[r];
             nn_p = nn_row; row_p = row_cur; have_p = tile < tile_last;
         }
-        VGH_TICK(t4);
+        VGB_TICK(VGH_TIMING, t4);
         if constexpr (STAGGER) { if (wave < WAVES / 2) { asm volatile("" ::: "memory"); if (VGH_ABLATE < 4) __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } }
         else __syncthreads();
 #if VGH_TIMING
@@ -707,11 +669,7 @@ extern "C" int vgh_launch_bound_f32(const BatchArgsH *a, int ntb, int waves, int
 
 template <int VT, int NTB, int MODE, int BOUND, int W>
 static int launch_h(const BatchArgsH &a, int blocks, size_t smem, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(vg_batch_h_kernel<VT, NTB, MODE, BOUND, W>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((vg_batch_h_kernel<VT, NTB, MODE, BOUND, W>), dim3((unsigned)blocks), dim3(64 * W), smem, stream, a);
-    return (int)hipGetLastError();
+    return vgb_launch(vg_batch_h_kernel<VT, NTB, MODE, BOUND, W>, blocks, 64 * W, smem, stream, a);
 }
 template <int VT, int NTB, int BOUND, int W>
 static int launch_h_mode(const BatchArgsH &a, int blocks, size_t smem, hipStream_t stream) {
@@ -817,21 +775,6 @@ extern "C" int vgh_launch_real_f16(const BatchArgsH *a, int ntb, int waves, int 
     return launch_h_ntb<T_F16, VGH_REAL>(*a, ntb, waves, blocks, smem, stream);
 }
 
-extern "C" int vg_batch_merge_launch(const uint64_t *dev_cand, int nq_pad, int lists_per_query, int npart, int k,
-                                     uint64_t *dev_out_keys, hipStream_t stream);        // vg_batch.hip
-
-
-static int vgh_ntb(long long stride_bytes) {
-    const int ntb = (int)((stride_bytes + 31) / 32);
-    if (ntb <= 8) return 8;
-    if (ntb <= 16) return 16;
-    if (ntb <= 24) return 24;
-    if (ntb <= 32) return 32;
-    if (ntb <= 48) return 48;                                     // rows up to 768 / 1024 elements: 4-wavefront workgroups
-    if (ntb <= 64) return 64;
-    return 0;
-}
-
 static size_t vgh_lds_bytes(int NTB, int k, int waves) {
     return (size_t)2 * NTB * 1024 + 1024 + (size_t)waves * VGH_QPW * (8 + 4 + 4) + (size_t)waves * VGH_QPW * k * 8;
 }
@@ -842,12 +785,12 @@ static size_t vgh_lds_bytes(int NTB, int k, int waves) {
 // The split form (filter kernel + exact-evaluation kernel, see the FILTER kind) serves every shape the fused kernel serves:
 // VG_BATCH_H_SPLIT=1 switches it on.
 extern "C" int vg_batch_h_split(long long stride_bytes, int k) {
-    const int NTB = vgh_ntb(stride_bytes);
+    const int NTB = vgb_ntb64(stride_bytes);
     if (!NTB || k < 1 || k > VGH_MAX_K) return 0;
     return vg_sw(SW_VG_BATCH_H_SPLIT, 0) != 0;                         // opt-in: the two forms measure equal (7.98 against 7.95 ms, profiles/r6k_*)
 }
 extern "C" int vg_batch_h_plan(long long stride_bytes, int k, int nq, int *waves, int *blocks_per_cu) {
-    const int NTB = vgh_ntb(stride_bytes);
+    const int NTB = vgb_ntb64(stride_bytes);
     if (!NTB || k < 1 || k > VGH_MAX_K) return -1;
     int w = VGH_WAVES_OF(NTB), bpc = 1;
     if (vg_batch_h_split(stride_bytes, k)) {                     // one workgroup per CU: a tile is streamed once for all its queries
@@ -862,10 +805,10 @@ extern "C" int vg_batch_h_plan(long long stride_bytes, int k, int nq, int *waves
     if (blocks_per_cu) *blocks_per_cu = bpc;
     return 0;
 }
-extern "C" int vg_batch_h_queries_per_block(long long stride_bytes) { return VGH_WAVES_OF(vgh_ntb(stride_bytes)) * VGH_QPW; }
+extern "C" int vg_batch_h_queries_per_block(long long stride_bytes) { return VGH_WAVES_OF(vgb_ntb64(stride_bytes)) * VGH_QPW; }
 
 extern "C" size_t vg_batch_h_lds_bytes(long long stride_bytes, int k) {          // (the default 8-wavefront form: the larger of the two)
-    const int NTB = vgh_ntb(stride_bytes);
+    const int NTB = vgb_ntb64(stride_bytes);
     if (!NTB || k < 1 || k > VGH_MAX_K) return 0;
     const size_t b = vgh_lds_bytes(NTB, k, VGH_WAVES_OF(NTB));
     return b <= 160 * 1024 ? b : 0;
@@ -967,7 +910,7 @@ extern "C" int vg_batch_h_launch(const uint8_t *dev_rows, int rows_tiled, long l
                                  const float *dev_row_nn, uint64_t *dev_cand, int npart, int tiles_per_part,
                                  uint64_t *dev_out_keys, unsigned long long *dev_evals, int waves,
                                  uint64_t *dev_pairs, uint32_t *dev_pair_counts, int pair_cap, hipStream_t stream) {
-    const int ntb = vgh_ntb(stride_bytes);
+    const int ntb = vgb_ntb64(stride_bytes);
     const bool split = dev_pairs != nullptr && dev_pair_counts != nullptr && pair_cap > 0 && waves == VGH_WAVES_OF(ntb);
     if (!ntb || k < 1 || k > VGH_MAX_K || (waves != VGH_WAVES_OF(ntb) && !(waves == 4 && VGH_HAS_W4(ntb)))) return -1;
     const size_t smem = vgh_lds_bytes(ntb, k, waves);
@@ -1016,32 +959,14 @@ extern "C" int vg_batch_h_launch(const uint8_t *dev_rows, int rows_tiled, long l
         const int denom = vg_sw(SW_VG_BATCH_PREPASS, VGB_PREPASS_DENOM_DEFAULT);     // (vg_batch_common.h: re-measured in round 3)
         if (denom > 0 && ntiles >= 65536) pre = ((ntiles / denom + npart - 1) / npart) * npart;      // whole partitions; < 2M rows: one pass
     }
-    int rc;
-    a.npart_total = npart;                                        // every pass writes (and the merges read) lists 0 .. npart-1
-    a.part_base = 0; a.seed = 0;
-    if (pre > 0) {
-        a.tile_begin = 0; a.tile_end = pre; a.tiles_per_part = (int)(pre / npart); a.init_keys = nullptr;
-        if ((rc = launch(a, true)) != 0) return rc;
-        if ((rc = vg_batch_merge_launch(dev_cand, nq_pad, a.npart_total, npart, k, dev_out_keys, stream)) != 0) return rc;
-        a.init_keys = dev_out_keys;
-    } else {
-        a.init_keys = nullptr;
-    }
     // the real pass, in stages over growing row ranges (vg_batch_common.h): the first one scans the pre-pass rows again (their
     // lists hold bounds, not distances), every later one starts from - and partition 0 carries on - the merged lists so far
-    long long bounds[16];
-    const int nstages = vgb_stage_bounds(ntiles, pre, bounds, 16, G >= 2 ? 200 : 400);     // (several query groups: doubling)
-    for (int s = 0; s < nstages; ++s) {
-        a.tile_begin = bounds[s]; a.tile_end = bounds[s + 1];
-        a.tiles_per_part = (int)((a.tile_end - a.tile_begin + npart - 1) / npart);
-        a.seed = (s > 0) ? 1 : 0;
-        if (split) {                                              // filter -> pairs -> exact evaluation + lists
-            if ((rc = launch_filter(a)) != 0) return rc;
-            if ((rc = launch_exact(a)) != 0) return rc;
-        } else if ((rc = launch(a, false)) != 0) return rc;
-        if ((rc = vg_batch_merge_launch(dev_cand, nq_pad, a.npart_total, npart, k, dev_out_keys, stream)) != 0) return rc;
-        a.init_keys = dev_out_keys;
-    }
-    return 0;
+    return vgb_run_staged(a, ntiles, pre, G >= 2 ? 200 : 400, dev_out_keys, stream,                 // (several query groups: doubling)
+                          [&](const BatchArgsH &b) { return launch(b, true); },
+                          [&](const BatchArgsH &b) {
+                              if (!split) return launch(b, false);
+                              const int rc = launch_filter(b);                   // filter -> pairs -> exact evaluation + lists
+                              return rc != 0 ? rc : launch_exact(b);
+                          });
 }
 #endif   // VGH_TU

@@ -11,8 +11,6 @@
 
 typedef _Float16 vgh_f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 vgh_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float vgh_f32x16 __attribute__((ext_vector_type(16)));
-typedef int vgh_i32x4 __attribute__((ext_vector_type(4)));
 
 #define VGH_QPW 32
 #define VGH_TILE 32
@@ -63,13 +61,8 @@ struct BatchArgsH {
                               // over them - 64 pair words per look, one look per pair - then costs LDS reads instead of an L2 round trip each
 };
 
-template <int CTRL> __device__ __forceinline__ uint64_t vgh_dpp64(uint64_t v) {
-    return ((uint64_t)vg_dpp_u32<CTRL>((uint32_t)(v >> 32)) << 32) | vg_dpp_u32<CTRL>((uint32_t)v);
-}
-__device__ __forceinline__ uint64_t vgh_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
 template <int VT>
-__device__ __forceinline__ vgh_f32x16 vgh_mfma(const vgh_i32x4 &a, const vgh_i32x4 &b, const vgh_f32x16 &c) {
+__device__ __forceinline__ vgb_f32x16 vgh_mfma(const vgb_i32x4 &a, const vgb_i32x4 &b, const vgb_f32x16 &c) {
     if constexpr (VT == T_F16)
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(vgh_f16x8, a), __builtin_bit_cast(vgh_f16x8, b), c, 0, 0, 0);
     else

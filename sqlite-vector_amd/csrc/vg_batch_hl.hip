@@ -89,7 +89,7 @@ __global__ __launch_bounds__(64 * VGHL_WAVES, 1) void vg_batch_hl_kernel(BatchAr
     __syncthreads();
 
     // ---- A operand: lane (x, h) keeps bytes [32 t + 16 h, +16) of query x of every set, for this wavefront's k-steps
-    vgh_i32x4 areg[QS][NTBP];
+    vgb_i32x4 areg[QS][NTBP];
     vgb_static_for<0, QS>([&](auto sc) __attribute__((always_inline)) {
         constexpr int s = decltype(sc)::value;
         const float qqx = qq_l[s * VGH_QPW + x];
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(64 * VGHL_WAVES, 1) void vg_batch_hl_kernel(BatchAr
                 uint4 v0 = make_uint4(0u, 0u, 0u, 0u), v1 = make_uint4(0u, 0u, 0u, 0u);
                 if (!qzero && off + 16 <= a.xstride) v0 = *reinterpret_cast<const uint4 *>(qrow + off);
                 if (!qzero && off + 32 <= a.xstride) v1 = *reinterpret_cast<const uint4 *>(qrow + off + 16);
-                areg[s][t] = vgh_i32x4{bf(v0.x, v0.y), bf(v0.z, v0.w), bf(v1.x, v1.y), bf(v1.z, v1.w)};
+                areg[s][t] = vgb_i32x4{bf(v0.x, v0.y), bf(v0.z, v0.w), bf(v1.x, v1.y), bf(v1.z, v1.w)};
             });
         } else {
             const uint8_t *qrow = a.queries + (long long)(q0 + s * VGH_QPW + x) * a.stride;
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64 * VGHL_WAVES, 1) void vg_batch_hl_kernel(BatchAr
                 const long long off = (long long)32 * (kbase + t) + 16 * h;
                 uint4 v = make_uint4(0u, 0u, 0u, 0u);
                 if (!qzero && off < a.stride) v = *reinterpret_cast<const uint4 *>(qrow + off);
-                areg[s][t] = vgh_i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+                areg[s][t] = vgb_i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
             });
         }
     });
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(64 * VGHL_WAVES, 1) void vg_batch_hl_kernel(BatchAr
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(a.rows) + (unsigned long long)tile * tile_bytes, 0, (int)tile_bytes, 0x00020000);
     };
     const int lane_off = lane * 16;
-    auto load_b = [&](__amdgpu_buffer_rsrc_t rs, auto tc) __attribute__((always_inline)) -> vgh_i32x4 {
+    auto load_b = [&](__amdgpu_buffer_rsrc_t rs, auto tc) __attribute__((always_inline)) -> vgb_i32x4 {
         constexpr int t = decltype(tc)::value;
         return __builtin_amdgcn_raw_buffer_load_b128(rs, lane_off, (kbase + t) * 1024, 0);
     };
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64 * VGHL_WAVES, 1) void vg_batch_hl_kernel(BatchAr
     // tiles ahead: what is in flight per CU (4 wavefronts x DEPTH x NTBP KiB: 192 KiB) is what bounds the stream - with one tile
     // (96 KiB at 24 k-steps) the first version ran at ~19 B / clk / CU from L2, 30 % of the matrix rate (profiles/r7b_*)
     constexpr int DEPTH = BOUND ? 1 : VGHL_DEPTH(NTBP);                  // (the pre-pass - 1 / 512 of the rows - keeps its registers for the lists' code)
-    vgh_i32x4 breg[DEPTH][NTBP];
+    vgb_i32x4 breg[DEPTH][NTBP];
     float nn_ring[DEPTH];
     if (tile_first < tile_last) {
         vgb_static_for<0, DEPTH>([&](auto dc) __attribute__((always_inline)) {
@@ -278,11 +278,11 @@ __global__ __launch_bounds__(64 * VGHL_WAVES, 1) void vg_batch_hl_kernel(BatchAr
                     // only the SMALLEST bound of each query in this tile enters its list (k entries then stand for k different rows all
                     // the same, and a list costs one insert per (query, tile))
                     uint64_t key = ok ? vg_make_key(ub, (uint32_t)row_prev) : VG_EMPTY_KEY;
-                    key = vgh_min64(key, vgh_dpp64<VG_DPP_QUAD_PERM(1, 0, 3, 2)>(key));
-                    key = vgh_min64(key, vgh_dpp64<VG_DPP_QUAD_PERM(2, 3, 0, 1)>(key));
-                    key = vgh_min64(key, vgh_dpp64<VG_DPP_ROW_HALF_MIRROR>(key));
-                    key = vgh_min64(key, vgh_dpp64<VG_DPP_ROW_MIRROR>(key));
-                    key = vgh_min64(key, (uint64_t)__shfl_xor((unsigned long long)key, 16));       // lanes 0-31 / 32-63: one query each
+                    key = vgb_min64(key, vgb_dpp64<VG_DPP_QUAD_PERM(1, 0, 3, 2)>(key));
+                    key = vgb_min64(key, vgb_dpp64<VG_DPP_QUAD_PERM(2, 3, 0, 1)>(key));
+                    key = vgb_min64(key, vgb_dpp64<VG_DPP_ROW_HALF_MIRROR>(key));
+                    key = vgb_min64(key, vgb_dpp64<VG_DPP_ROW_MIRROR>(key));
+                    key = vgb_min64(key, (uint64_t)__shfl_xor((unsigned long long)key, 16));       // lanes 0-31 / 32-63: one query each
 #pragma unroll
                     for (int hh = 0; hh < 2; ++hh) {
                         const uint64_t c = vg_readlane64(key, 32 * hh);
@@ -320,14 +320,14 @@ __global__ __launch_bounds__(64 * VGHL_WAVES, 1) void vg_batch_hl_kernel(BatchAr
         const __amdgpu_buffer_rsrc_t rs_next = tile_rsrc(tile_next);
         float nn_row = nn_ring[d];
         nn_ring[d] = a.row_nn[tile_next * VGH_TILE + x];                 // (in front of that tile's loads: it lands first)
-        vgh_f32x16 acc[QS];
+        vgb_f32x16 acc[QS];
 #pragma unroll
         for (int s = 0; s < QS; ++s)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[s][r] = 0.0f;
         auto k_step = [&](auto tc) __attribute__((always_inline)) {
             constexpr int t = decltype(tc)::value;
-            const vgh_i32x4 b = breg[d][t];
+            const vgb_i32x4 b = breg[d][t];
             vgb_static_for<0, QS>([&](auto sc) __attribute__((always_inline)) { constexpr int s = decltype(sc)::value; acc[s] = vgh_mfma<FT>(areg[s][t], b, acc[s]); });
             if constexpr (!(VGHL_ABLATE & 2)) breg[d][t] = load_b(rs_next, tc);     // the same k-step of the tile DEPTH ahead
         };
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(64 * VGHL_WAVES, 1) void vg_batch_hl_kernel(BatchAr
 #endif
 
 static int vghl_ntbp(long long stride_bytes) {
-    const int ksteps = (int)((stride_bytes + 31) / 32);
+    const int ksteps = vgb_ksteps(stride_bytes);
     if (ksteps <= 64 || ksteps > VGHL_MAX_KSTEPS) return 0;              // (up to 64: vg_batch_h.hip)
     const int per = (ksteps + VGHL_WAVES - 1) / VGHL_WAVES;
     return per <= 24 ? 24 : (per <= 32 ? 32 : 48);
@@ -392,12 +392,7 @@ static size_t vghl_lds_bytes(int ntbp, int k, bool bound) {
 }
 template <int VT, int NTBP, int KIND>
 static int launch_hl_mode(const BatchArgsH &a, int blocks, size_t smem, hipStream_t stream) {
-    auto go = [&](auto kern) -> int {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * VGHL_WAVES), smem, stream, a);
-        return (int)hipGetLastError();
-    };
+    auto go = [&](auto kern) -> int { return vgb_launch(kern, blocks, 64 * VGHL_WAVES, smem, stream, a); };
 #ifndef VGHL_ONLY_DOT                   // (measurement / disassembly builds: one instantiation per unit)
     if (a.mode == VGH_COS) return go(vg_batch_hl_kernel<VT, NTBP, VGH_COS, KIND>);
     if (a.mode == VGH_L2) return go(vg_batch_hl_kernel<VT, NTBP, VGH_L2, KIND>);
@@ -470,9 +465,6 @@ extern "C" int vg_batch_hl_regions(long long stride_bytes, int nq_pad, int npart
     const int qpb = vg_batch_hl_queries_per_block(stride_bytes);
     return qpb ? (nq_pad / qpb) * npart * VGHL_WAVES : 0;
 }
-
-extern "C" int vg_batch_merge_launch(const uint64_t *dev_cand, int nq_pad, int lists_per_query, int npart, int k,
-                                     uint64_t *dev_out_keys, hipStream_t stream);        // vg_batch.hip
 
 // (float) sum q^2 of every query of a batch (f64 sums, one wavefront per query): what the kernels' gates and the A operand's "multiplies
 // as zero" rule read.  -1 for a query the filter cannot judge - Inf / NaN elements, a norm of zero or out of [1e-30, 1e30] - which the
@@ -558,26 +550,11 @@ extern "C" int vg_batch_hl_launch(const uint8_t *dev_rows, long long n_rows, lon
         if (denom > 0) pre = ((std::max<long long>(ntiles / denom, 2 * (long long)k) + npart - 1) / npart) * npart;
         if (pre * 2 > ntiles) pre = ntiles;              // a small corpus: bounds over all of it, then ONE filter + exact stage
     }
-    int rc;
-    a.npart_total = npart; a.part_base = 0; a.seed = 0;
-    a.init_keys = nullptr;
-    if (pre > 0) {
-        a.tile_begin = 0; a.tile_end = pre; a.tiles_per_part = (int)((pre + npart - 1) / npart);
-        if ((rc = launch(a, VGH_BOUNDK)) != 0) return rc;
-        if ((rc = vg_batch_merge_launch(dev_cand, nq_pad, a.npart_total, npart, k, dev_out_keys, stream)) != 0) return rc;
-        a.init_keys = dev_out_keys;
-    }
-    long long bounds[16];
-    const int nstages = vgb_stage_bounds(ntiles, pre, bounds, 16, 200);
-    for (int s = 0; s < nstages; ++s) {
-        a.tile_begin = bounds[s]; a.tile_end = bounds[s + 1];
-        a.tiles_per_part = (int)((a.tile_end - a.tile_begin + npart - 1) / npart);
-        a.seed = (s > 0) ? 1 : 0;
-        if ((rc = launch(a, VGH_FILTER)) != 0) return rc;
-        if ((rc = launch_exact(a)) != 0) return rc;
-        if ((rc = vg_batch_merge_launch(dev_cand, nq_pad, a.npart_total, npart, k, dev_out_keys, stream)) != 0) return rc;
-        a.init_keys = dev_out_keys;
-    }
-    return 0;
+    return vgb_run_staged(a, ntiles, pre, 200, dev_out_keys, stream,
+                          [&](const BatchArgsH &b) { return launch(b, VGH_BOUNDK); },
+                          [&](const BatchArgsH &b) {
+                              const int rc = launch(b, VGH_FILTER);
+                              return rc != 0 ? rc : launch_exact(b);
+                          });
 }
 #endif   // VGHL_TU

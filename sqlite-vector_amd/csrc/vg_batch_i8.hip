@@ -33,9 +33,6 @@
 
 #include "vg_batch_common.h"
 
-typedef int vgi_i32x16 __attribute__((ext_vector_type(16)));
-typedef int vgi_i32x4 __attribute__((ext_vector_type(4)));
-
 #ifndef VGI_WAVES
 #define VGI_WAVES 8                     // two wavefronts per SIMD
 #endif
@@ -74,9 +71,6 @@ extern "C" int vg_batch_i8_timing(unsigned long long *out16, int reset) {
     if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(vgi_ticks), z, sizeof(z)) != hipSuccess) return -1; }
     return 0;
 }
-#define VGI_TICK(var) const unsigned long long var = __builtin_readcyclecounter()
-#else
-#define VGI_TICK(var)
 #endif
 
 struct BatchArgsI8 {
@@ -96,22 +90,8 @@ struct BatchArgsI8 {
     int seed;                 // staged real passes (vg_batch_common.h): partition 0 starts its lists from init_keys
 };
 
-typedef float vgi_f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned vgi_u32x2 __attribute__((ext_vector_type(2)));
 
-template <int CTRL> __device__ __forceinline__ uint64_t vgi_dpp64(uint64_t v) {
-    return ((uint64_t)vg_dpp_u32<CTRL>((uint32_t)(v >> 32)) << 32) | vg_dpp_u32<CTRL>((uint32_t)v);
-}
-__device__ __forceinline__ uint64_t vgi_min64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
-template <int OFF>
-__device__ __forceinline__ void vgi_lds_read128(vgi_i32x4 &dst, uint32_t lds_addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_addr), "n"(OFF) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void vgi_wait_lds(vgi_i32x4 &v) {
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N));
-}
 // tile buffers of the pipelined schedule (the DMA runs one tile ahead of the reads; a fourth buffer and DMA two tiles ahead
 // with counted vmcnt waits was measured: the mid-tile wait did not shrink - it is not the DMA's latency)
 #define VGI_PIPE_NBUF 3
@@ -153,7 +133,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
     const int q0 = g * QPB + wave * VGI_QPW;
 
     // ---- A operand (+ the query's sums in its ORIGINAL representation)
-    vgi_i32x4 areg[NTB];
+    vgb_i32x4 areg[NTB];
     uint32_t sq_part = 0, sqq_part = 0;
     {
         const uint8_t *qrow = a.queries + (long long)(q0 + x) * a.stride;
@@ -174,7 +154,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
                 }
             }
             const uint32_t flip = IS_U8 ? 0x80808080u : 0u;
-            areg[t] = vgi_i32x4{(int)(v.x ^ flip), (int)(v.y ^ flip), (int)(v.z ^ flip), (int)(v.w ^ flip)};
+            areg[t] = vgb_i32x4{(int)(v.x ^ flip), (int)(v.y ^ flip), (int)(v.z ^ flip), (int)(v.w ^ flip)};
         });
     }
     uint32_t *qs_w = qstat_lds + wave * VGI_QPW * 2;
@@ -230,34 +210,14 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
         const int p = wave * NPIECE + i;
         const uint8_t *sbase = a.rows + (unsigned long long)(tile * VGI_TILE) * stride_b + (unsigned)p * 1024u;   // 1 KiB contiguous
         const uint32_t lds_dst = lds_tile0 + (uint32_t)(buf * TILE_BYTES + p * 1024);
-        uint32_t keep;
-        uint64_t keep_exec;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %4\n\ts_and_b64 exec, exec, %5\n\t"
-                     "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep), "=&s"(keep_exec) : "v"(lane_goff), "s"(sbase), "s"(lds_dst), "s"(piece_mask[i]) : "memory", "scc");
+        vgb_dma_masked(lane_goff, sbase, lds_dst, piece_mask[i]);
     };
     // N (1 .. 4) whole pieces starting at piece slot i0, back to back
     auto dma_run = [&](long long tile, int buf, auto i0c, auto nc) {
         constexpr int i0 = decltype(i0c)::value, N = decltype(nc)::value;
         const uint8_t *sbase = a.rows + (unsigned long long)(tile * VGI_TILE) * stride_b + (unsigned)(wave * NPIECE + i0) * 1024u;
         const uint32_t lds_dst = lds_tile0 + (uint32_t)(buf * TILE_BYTES + (wave * NPIECE + i0) * 1024);
-        uint32_t keep;
-        if constexpr (N == 1)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else if constexpr (N == 2)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else if constexpr (N == 3)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:3072\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
+        vgb_dma_run<N>(lane_goff, sbase, lds_dst);
     };
     auto dma_tile = [&](long long tile, int buf) {
         if (all_full) {                                              // the common case: whole pieces, back to back in runs of <= 4
@@ -278,9 +238,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
     auto dma_stat_group = [&](long long tile4, int slot) {          // tiles tile4 .. tile4 + 3
         const uint8_t *sbase = reinterpret_cast<const uint8_t *>(a.row_stat + tile4 * (VGI_TILE * 2));
         const uint32_t lds_dst = lds_rstat0 + (uint32_t)(slot * 1024);
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
+        vgb_dma_run<1>(lane_goff, sbase, lds_dst);
     };
     const uint32_t stat_goff = (uint32_t)x * 8u;
     auto load_stats = [&](long long tile, vgi_u32x2 &dst) {          // (the barrier-per-tile schedule: straight into registers)
@@ -299,8 +257,8 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
     // with cq / cx the query / row parts of what turns the raw accumulator into sum q x (uint8: 128 sum q - 16384 L, 128 sum x).
     // The exact test - (float) distance < thr, the single-query kernel's arithmetic - is the slow path's.
     // (Vectors, not arrays: the slow path indexes them with a run-time register number.)
-    vgi_i32x16 ng, cinit;
-    vgi_f32x16 invg;
+    vgb_i32x16 ng, cinit;
+    vgb_f32x16 invg;
     uint32_t open_mask = 0;
     const bool l2_root = a.root != 0;
     auto as_float_like = [](uint32_t v) -> float { return IS_U8 ? (float)v : (float)(int32_t)v; };
@@ -340,7 +298,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
 
     // the fast test of a tile, in 8 pieces of two registers each (the pipelined schedule spreads them over the k loop of the
     // NEXT tile); jm accumulates the lane's best margin
-    auto judge_item = [&](auto ic, const vgi_i32x16 &acc, int cx, int &jm_i, float &jm_f) __attribute__((always_inline)) {
+    auto judge_item = [&](auto ic, const vgb_i32x16 &acc, int cx, int &jm_i, float &jm_f) __attribute__((always_inline)) {
         constexpr int r0 = 2 * decltype(ic)::value, r1 = r0 + 1;
         if constexpr (COS) {
             const float f0 = as_float_like((uint32_t)(acc[r0] + cx)) * invg[r0], f1 = as_float_like((uint32_t)(acc[r1] + cx)) * invg[r1];
@@ -360,7 +318,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
     // pending registers by run-time index - the exact distance of each pair from the raw accumulator (the single-query kernel's
     // epilogue, vg_accum.h), the list inserts, the refreshed gate.  (Unrolled over the 16 registers, the slow paths were most
     // of the kernel's code: entering one cost ~16k cycles of instruction-cache misses.)
-    auto judge_slow = [&](const vgi_i32x16 &acc, long long tile, int sx, uint32_t xx) __attribute__((always_inline)) {
+    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int sx, uint32_t xx) __attribute__((always_inline)) {
         const long long row = tile * VGI_TILE + x;
         const int cx = IS_U8 ? 128 * sx : 0;
         unsigned pend = 0;
@@ -403,11 +361,11 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
             if (!m) continue;
             if constexpr (PRE) {
                 uint64_t kmin = pass ? vg_make_key(d, (uint32_t)row) : VG_EMPTY_KEY;     // min over the 32 rows of each query
-                kmin = vgi_min64(kmin, vgi_dpp64<VG_DPP_QUAD_PERM(1, 0, 3, 2)>(kmin));
-                kmin = vgi_min64(kmin, vgi_dpp64<VG_DPP_QUAD_PERM(2, 3, 0, 1)>(kmin));
-                kmin = vgi_min64(kmin, vgi_dpp64<VG_DPP_ROW_HALF_MIRROR>(kmin));
-                kmin = vgi_min64(kmin, vgi_dpp64<VG_DPP_ROW_MIRROR>(kmin));
-                kmin = vgi_min64(kmin, (uint64_t)__shfl_xor((unsigned long long)kmin, 16));
+                kmin = vgb_min64(kmin, vgb_dpp64<VG_DPP_QUAD_PERM(1, 0, 3, 2)>(kmin));
+                kmin = vgb_min64(kmin, vgb_dpp64<VG_DPP_QUAD_PERM(2, 3, 0, 1)>(kmin));
+                kmin = vgb_min64(kmin, vgb_dpp64<VG_DPP_ROW_HALF_MIRROR>(kmin));
+                kmin = vgb_min64(kmin, vgb_dpp64<VG_DPP_ROW_MIRROR>(kmin));
+                kmin = vgb_min64(kmin, (uint64_t)__shfl_xor((unsigned long long)kmin, 16));
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     const uint64_t c = vg_readlane64(kmin, 32 * hh);
@@ -433,7 +391,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
         }
     };
     // fast test + slow path in one piece (the barrier-per-tile schedule, and the last tile of the pipelined one)
-    auto judge_all = [&](const vgi_i32x16 &acc, long long tile, vgi_u32x2 st) __attribute__((always_inline)) {
+    auto judge_all = [&](const vgb_i32x16 &acc, long long tile, vgi_u32x2 st) __attribute__((always_inline)) {
         const int sx = (int)st[0];
         const uint32_t xx = st[1];
         const int cx = IS_U8 ? 128 * sx : 0;
@@ -444,7 +402,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
     };
 
     constexpr int BP = VGI_BPIPE < NTB / 2 ? VGI_BPIPE : NTB / 2;
-    vgi_i32x4 bq[BP];
+    vgb_i32x4 bq[BP];
     const int T = (int)(tile_last - tile_first);
 #if VGI_TIMING
     unsigned long long tk_sync = 0, tk_slow = 0, tk_nslow = 0, tk_h1 = 0, tk_h2 = 0, tk_mid = 0;
@@ -472,18 +430,18 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (T > 0) {
-            vgi_i32x16 accA, accB;
+            vgb_i32x16 accA, accB;
 #pragma unroll
             for (int r = 0; r < 16; ++r) accB[r] = 0;
             const uint32_t lane_b = lds_tile0 + (uint32_t)(h * 512 + x * 16);
             const uint32_t lane_stat = lds_rstat0 + (uint32_t)(x * 8);
-            vgb_static_for<0, BP>([&](auto tc) { vgi_lds_read128<1024 * decltype(tc)::value>(bq[decltype(tc)::value], lane_b); });
-            VGI_TICK(t_loop0);
+            vgb_static_for<0, BP>([&](auto tc) { vgb_lds_read128<1024 * decltype(tc)::value>(bq[decltype(tc)::value], lane_b); });
+            VGB_TICK(VGI_TIMING, t_loop0);
             int bcur = 0;                                                    // buffer of tile t
             // `car` = the row sums of the tile under test: read (inline asm, like the B operand) just before a step's
             // synchronisation, used by the next step
             vgi_u32x2 car = {0u, 0u};
-            auto step = [&](vgi_i32x16 &cur, const vgi_i32x16 &prev, int ti, bool prev_valid) __attribute__((always_inline)) {
+            auto step = [&](vgb_i32x16 &cur, const vgb_i32x16 &prev, int ti, bool prev_valid) __attribute__((always_inline)) {
                 const int bnext = bcur + 1 == NBUF ? 0 : bcur + 1, bdma = bcur == 0 ? NBUF - 1 : bcur - 1;
                 const long long tile = tile_first + ti;
                 const long long tile_dma = min(tile + 2, tile_last - 1);
@@ -495,34 +453,34 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
                 const bool stat_turn = ((ti + 2) & 3) == 0 && wave == (((ti + 2) >> 2) & (NISSUE - 1));
                 int jm_i = -0x7FFFFFFF;
                 float jm_f = -INFINITY;
-                VGI_TICK(tstep0);
+                VGB_TICK(VGI_TIMING, tstep0);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) cur[r] = cinit[r];
                 vgb_static_for<0, NTB>([&](auto tc) {
                     constexpr int t = decltype(tc)::value;
-                    vgi_wait_lds<BP - 1>(bq[t % BP]);
+                    vgb_wait_lds<BP - 1>(bq[t % BP]);
                     cur = __builtin_amdgcn_mfma_i32_32x32x32_i8(areg[t], bq[t % BP], cur, 0, 0, 0);
                     if constexpr (t == M) {
                         const bool any = VGI_ABLATE >= 1 ? false : (judge_any(jm_i, jm_f, pcx, pxx) && prev_valid);
                         if (VGI_ABLATE >= 2) asm volatile("" :: "v"(prev));        // (the accumulators stay alive without their test)
-                        VGI_TICK(ts0);
+                        VGB_TICK(VGI_TIMING, ts0);
                         // this tile's row sums for the next step; then every LDS read in flight has returned (the slow path may
                         // move registers around), my DMA pieces of tile t+1 have landed, barrier
                         const uint32_t sa = lane_stat + (uint32_t)((((ti >> 2) & 1) << 10) + ((ti & 3) << 8));
                         asm volatile("ds_read_b64 %0, %1" : "=v"(car) : "v"(sa) : "memory");
                         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(car));
-                        vgb_static_for<0, BP>([&](auto bc) { vgi_wait_lds<0>(bq[decltype(bc)::value]); });
+                        vgb_static_for<0, BP>([&](auto bc) { vgb_wait_lds<0>(bq[decltype(bc)::value]); });
                         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                         if (VGI_ABLATE < 4) __syncthreads();
-                        VGI_TICK(ts1);
+                        VGB_TICK(VGI_TIMING, ts1);
                         if (any) judge_slow(prev, tile - 1, psx, pxx);
 #if VGI_TIMING
                         const unsigned long long ts2 = __builtin_readcyclecounter();
                         tk_sync += ts1 - ts0; tk_slow += ts2 - ts1; tk_nslow += any ? 1 : 0; tk_h1 += ts0 - tstep0; tk_mid = ts2;
 #endif
                     }
-                    if constexpr (t + BP < NTB) vgi_lds_read128<1024 * (t + BP)>(bq[t % BP], base_cur);
-                    else vgi_lds_read128<1024 * (t + BP - NTB)>(bq[t % BP], base_next);
+                    if constexpr (t + BP < NTB) vgb_lds_read128<1024 * (t + BP)>(bq[t % BP], base_cur);
+                    else vgb_lds_read128<1024 * (t + BP - NTB)>(bq[t % BP], base_next);
                     if constexpr (VGI_ABLATE < 2 && t >= 1 && t < M) {
                         vgb_static_for<0, 8>([&](auto ic) {
                             if constexpr (1 + decltype(ic)::value * (M - 1) / 8 == t) {
@@ -547,7 +505,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
                 if (ti + 1 < T) step(accB, accA, ti + 1, true);
             }
             // the last tile: nothing left to hide its test under (`car` holds its row sums since its own mid-step)
-            vgb_static_for<0, BP>([&](auto bc) { vgi_wait_lds<0>(bq[decltype(bc)::value]); });
+            vgb_static_for<0, BP>([&](auto bc) { vgb_wait_lds<0>(bq[decltype(bc)::value]); });
             if (VGI_ABLATE >= 1) { asm volatile("" :: "v"(accA)); asm volatile("" :: "v"(accB)); }
             else if (T & 1) judge_all(accA, tile_last - 1, car);
             else judge_all(accB, tile_last - 1, car);
@@ -565,7 +523,7 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
     } else {
         // BARRIER PER TILE (rows of 1 - 2 KiB, and long lists next to 1 KiB rows: no room for a second accumulator set / a
         // third tile buffer): k loop with the DMA of the next tile, test, barrier
-        vgi_i32x16 acc;
+        vgb_i32x16 acc;
         vgi_u32x2 st = {0u, 0u};
         if (T > 0) dma_tile(tile_first, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -576,13 +534,13 @@ __global__ __launch_bounds__(64 * VGI_WAVES_OF(NTB), 1) void vg_batch_i8_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = cinit[r];
             const uint32_t baddr = lds_tile0 + (uint32_t)(cur_buf * TILE_BYTES + h * 512 + x * 16);
-            vgb_static_for<0, BP>([&](auto tc) { vgi_lds_read128<1024 * decltype(tc)::value>(bq[decltype(tc)::value], baddr); });
+            vgb_static_for<0, BP>([&](auto tc) { vgb_lds_read128<1024 * decltype(tc)::value>(bq[decltype(tc)::value], baddr); });
             vgb_static_for<0, NTB>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
                 constexpr int in_flight_after = (NTB - 1 - t) < (BP - 1) ? (NTB - 1 - t) : (BP - 1);
-                vgi_wait_lds<in_flight_after>(bq[t % BP]);
+                vgb_wait_lds<in_flight_after>(bq[t % BP]);
                 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(areg[t], bq[t % BP], acc, 0, 0, 0);
-                if constexpr (t + BP < NTB) vgi_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
+                if constexpr (t + BP < NTB) vgb_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
                 // this tile's row sums and the DMA pieces of the next tile, spread over the first half of the k loop
                 if constexpr (t == 0) load_stats(tile, st);
                 constexpr int NTD = (NTB + 1) / 2;
@@ -664,11 +622,7 @@ static bool vgi_pipelined(int NTB, int k) { return VGI_PIPE && NTB <= 32 && vgi_
 
 template <int NTB, int MODE, bool IS_U8, bool PRE, bool PIPE>
 static int launch_i8(const BatchArgsI8 &a, int blocks, size_t smem, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(vg_batch_i8_kernel<NTB, MODE, IS_U8, PRE, PIPE>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((vg_batch_i8_kernel<NTB, MODE, IS_U8, PRE, PIPE>), dim3((unsigned)blocks), dim3(64 * VGI_WAVES_OF(NTB)), smem, stream, a);
-    return (int)hipGetLastError();
+    return vgb_launch(vg_batch_i8_kernel<NTB, MODE, IS_U8, PRE, PIPE>, blocks, 64 * VGI_WAVES_OF(NTB), smem, stream, a);
 }
 template <int NTB, bool PRE, bool PIPE>
 static int launch_i8_mode(const BatchArgsI8 &a, int blocks, size_t smem, hipStream_t stream) {
@@ -701,24 +655,10 @@ extern "C" int vgi_launch_real(const BatchArgsI8 *a, int ntb, int blocks, size_t
     return launch_i8_ntb<false>(*a, ntb, blocks, smem, stream);
 }
 
-extern "C" int vg_batch_merge_launch(const uint64_t *dev_cand, int nq_pad, int lists_per_query, int npart, int k,
-                                     uint64_t *dev_out_keys, hipStream_t stream);        // vg_batch.hip
-
-static int vgi_ntb(long long stride_bytes) {                      // the instantiated k-step counts (32 bytes each)
-    const int ntb = (int)((stride_bytes + 31) / 32);
-    if (ntb <= 8) return 8;
-    if (ntb <= 16) return 16;
-    if (ntb <= 24) return 24;
-    if (ntb <= 32) return 32;
-    if (ntb <= 48) return 48;                                     // rows of 1 - 2 KiB: 4-wavefront workgroups
-    if (ntb <= 64) return 64;
-    return 0;
-}
-
-extern "C" int vg_batch_i8_queries_per_block(long long stride_bytes) { return VGI_WAVES_OF(vgi_ntb(stride_bytes)) * VGI_QPW; }
+extern "C" int vg_batch_i8_queries_per_block(long long stride_bytes) { return VGI_WAVES_OF(vgb_ntb64(stride_bytes)) * VGI_QPW; }
 
 extern "C" size_t vg_batch_i8_lds_bytes(long long stride_bytes, int k) {
-    const int NTB = vgi_ntb(stride_bytes);
+    const int NTB = vgb_ntb64(stride_bytes);
     if (!NTB || k < 1 || k > VGI_MAX_K) return 0;
     const size_t b = vgi_lds(NTB, k, vgi_pipelined(NTB, k) ? VGI_PIPE_NBUF : 2);
     return b <= 160 * 1024 ? b : 0;
@@ -737,7 +677,7 @@ extern "C" int vg_batch_i8_launch(const uint8_t *dev_rows_signed, long long n_ro
     a.rows = dev_rows_signed; a.queries = dev_queries; a.row_stat = dev_row_stat; a.cand = dev_cand;
     a.n_rows = n_rows; a.stride = stride_bytes; a.nq_pad = nq_pad; a.nq_real = nq_real; a.npart = npart; a.k = k;
     a.mode = mode; a.root = root; a.is_u8 = is_u8;
-    const int ntb = (int)((stride_bytes + 31) / 32);
+    const int ntb = vgb_ksteps(stride_bytes);
     const int G = nq_pad / vg_batch_i8_queries_per_block(stride_bytes);
     const int blocks = G * ((npart + 7) / 8) * 8;
     const long long ntiles = (n_rows + VGI_TILE - 1) / VGI_TILE;
@@ -748,26 +688,10 @@ extern "C" int vg_batch_i8_launch(const uint8_t *dev_rows_signed, long long n_ro
         const int denom = vg_sw(SW_VG_BATCH_PREPASS, VGB_PREPASS_DENOM_DEFAULT);     // (vg_batch_common.h: re-measured in round 3)
         if (denom > 0 && ntiles >= 65536) pre = ((ntiles / denom + npart - 1) / npart) * npart;      // < 2M rows: one pass
     }
-    int rc;
-    a.npart_total = npart; a.part_base = 0; a.init_keys = nullptr; a.seed = 0;
-    if (pre > 0) {
-        a.tile_begin = 0; a.tile_end = pre; a.tiles_per_part = (int)(pre / npart);
-        if ((rc = vgi_launch_pre(&a, ntb, blocks, smem, stream)) != 0) return rc;
-        if ((rc = vg_batch_merge_launch(dev_cand, nq_pad, a.npart_total, npart, k, dev_out_keys, stream)) != 0) return rc;
-        a.init_keys = dev_out_keys;
-    }
     // the real pass, in stages over growing row ranges (vg_batch_common.h): the first one meets the pre-pass rows again (their
     // lists hold tile minima only), every later one starts from - and partition 0 carries on - the merged lists so far
-    long long bounds[16];
-    const int nstages = vgb_stage_bounds(ntiles, pre, bounds, 16);
-    for (int s = 0; s < nstages; ++s) {
-        a.tile_begin = bounds[s]; a.tile_end = bounds[s + 1];
-        a.tiles_per_part = (int)((a.tile_end - a.tile_begin + npart - 1) / npart);
-        a.seed = (s > 0) ? 1 : 0;
-        if ((rc = vgi_launch_real(&a, ntb, blocks, smem, stream)) != 0) return rc;
-        if ((rc = vg_batch_merge_launch(dev_cand, nq_pad, a.npart_total, npart, k, dev_out_keys, stream)) != 0) return rc;
-        a.init_keys = dev_out_keys;
-    }
-    return 0;
+    return vgb_run_staged(a, ntiles, pre, 400, dev_out_keys, stream,
+                          [&](const BatchArgsI8 &b) { return vgi_launch_pre(&b, ntb, blocks, smem, stream); },
+                          [&](const BatchArgsI8 &b) { return vgi_launch_real(&b, ntb, blocks, smem, stream); });
 }
 #endif   // !VGI_TU_PRE

@@ -37,8 +37,6 @@
 #include "vg_batch_common.h"
 #include "vg_batch_h_defs.h"
 
-typedef int vgq_i32x16 __attribute__((ext_vector_type(16)));
-
 #define VGQ_WAVES 4                     // one wavefront per SIMD; two workgroups per CU
 #define VGQ_QS 2                        // query sets of 32 per wavefront
 #define VGQ_QPW (32 * VGQ_QS)
@@ -112,9 +110,6 @@ extern "C" int vg_batch_q8_timing(unsigned long long *out16, int reset) {
     if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(vgq_ticks), z, sizeof(z)) != hipSuccess) return -1; }
     return 0;
 }
-#define VGQ_TICK(var) const unsigned long long var = __builtin_readcyclecounter()
-#else
-#define VGQ_TICK(var)
 #endif
 #ifndef VGQ_TRACE
 #define VGQ_TRACE 0                     // measurement builds: per-tile timestamps of ONE workgroup's eight wavefronts (tools/r6_q8_tile_trace.py)
@@ -310,15 +305,6 @@ __global__ __launch_bounds__(256) void vg_q8_pre_select_kernel(const float *prem
     }
 }
 
-template <int OFF>
-__device__ __forceinline__ void vgq_lds_read128(vgh_i32x4 &dst, uint32_t lds_addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(lds_addr), "n"(OFF) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void vgq_wait_lds(vgh_i32x4 &v) {
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N));
-}
-
 // NTB = 32-byte k-steps per int8 row (rows up to NTB * 32 elements)
 // WAVES x QS x 32 = 256 queries per workgroup; KS = K-parts per tile (1: the whole row is one ring buffer)
 // PRE = the bound-only pre-pass (round 6): no gate, no pairs - per (query, tile) the smallest UPPER bound of the distance (see pre_boundary)
@@ -364,7 +350,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
     const int chunks_per_row = (int)(a.stride / 16);
 
     // ---- A operands: lane (x, h) keeps bytes [32t + 16h, +16) of query x of each set
-    vgh_i32x4 areg[QS][KS * NTB];
+    vgb_i32x4 areg[QS][KS * NTB];
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
         const uint8_t *qrow = a.qcodes + (long long)(q0 + 32 * s + x) * a.stride;
@@ -373,7 +359,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
             const int off = 32 * t + 16 * h;
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
             if (off < a.stride) v = *reinterpret_cast<const uint4 *>(qrow + off);
-            areg[s][t] = vgh_i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+            areg[s][t] = vgb_i32x4{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
         });
     }
     // ---- the gates, in the query's own integer units (everything divided by its scale sq): a pair (query r, row x) passes when
@@ -473,9 +459,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
     auto dma_stat_group = [&](long long tile2, int slot) {          // the row statistics of tiles tile2, tile2 + 1: 1 KiB
         const uint8_t *b0 = reinterpret_cast<const uint8_t *>(a.rstat + tile2 * VGQ_TILE);
         const uint32_t d0 = lds_rstat0 + (uint32_t)(slot * 1024);
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(lane_goff), "s"(b0), "s"(d0) : "memory");
+        vgb_dma_run<1>(lane_goff, b0, d0);
     };
     auto dma_piece = [&](long long tile, int part_k, int buf, int i) __attribute__((always_inline)) {
         const int p = wave * NPIECE + i;
@@ -483,32 +467,12 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
         if (pmask == 0) return;
         const uint8_t *sbase = a.rows + (unsigned long long)(tile * VGQ_TILE) * stride_b + (unsigned)(part_k * NTB + p) * 1024u;
         const uint32_t lds_dst = lds_tile0 + (uint32_t)(buf * TILE_BYTES + p * 1024);
-        uint32_t keep;
-        uint64_t keep_exec;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %4\n\ts_and_b64 exec, exec, %5\n\t"
-                     "global_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep), "=&s"(keep_exec) : "v"(lane_goff), "s"(sbase), "s"(lds_dst), "s"(pmask) : "memory", "scc");
+        vgb_dma_masked(lane_goff, sbase, lds_dst, pmask);
     };
     auto dma_run = [&](long long tile, int part_k, int buf) __attribute__((always_inline)) {           // NPIECE (1 .. 4) whole pieces, back to back
         const uint8_t *sbase = a.rows + (unsigned long long)(tile * VGQ_TILE) * stride_b + (unsigned)(part_k * NTB + wave * NPIECE) * 1024u;
         const uint32_t lds_dst = lds_tile0 + (uint32_t)(buf * TILE_BYTES + (wave * NPIECE) * 1024);
-        uint32_t keep;
-        if constexpr (NPIECE == 1)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else if constexpr (NPIECE == 2)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else if constexpr (NPIECE == 3)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
-        else
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                         "global_load_lds_dwordx4 %1, %2 offset:3072\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(lane_goff), "s"(sbase), "s"(lds_dst) : "memory");
+        vgb_dma_run<NPIECE>(lane_goff, sbase, lds_dst);
     };
     // ring trip u = K-part u % KS of tile tile_first + u / KS
     auto dma_share = [&](int u, int buf) __attribute__((always_inline)) {
@@ -622,7 +586,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
         n_q = 0; q_head = 0;
     };
     constexpr int BP = VGQ_BPIPE < NTB ? VGQ_BPIPE : NTB;
-    vgh_i32x4 bq[BP];
+    vgb_i32x4 bq[BP];
     int cur_buf = 0;
     // ---- tile boundary of tile ti over the accumulators acc0 / acc1.  First test, per query set: the lane's LARGEST accumulator of the set
     // against the set's loosest gate, as an integer: I >= ithr = (-(amax ||ex|| + bbmax ||x|| + ccmax - m uumin)) / sx, rounded down.  Only a
@@ -630,7 +594,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
     // pairs get the query's own four coefficients.
     auto stat_of = [&](int ti) __attribute__((always_inline)) -> float4 { return rstat_lds[((ti >> 1) & (VGQ_STAT_SLOTS - 1)) * 64 + (ti & 1) * 32 + x]; };
     // (first test: the lanes with a candidate, and the two sets' integer thresholds; candidate path: those lanes park their accumulators)
-    auto boundary_first = [&](const float4 rs, const vgq_i32x16 &acc0, const vgq_i32x16 &acc1, int (&ithr)[2]) __attribute__((always_inline)) -> unsigned long long {
+    auto boundary_first = [&](const float4 rs, const vgb_i32x16 &acc0, const vgb_i32x16 &acc1, int (&ithr)[2]) __attribute__((always_inline)) -> unsigned long long {
         if (VGQ_ABLATE >= 2) asm volatile("" :: "v"(acc0[0]), "v"(acc0[15]), "v"(acc1[0]), "v"(acc1[15]));
         const float sx = rs.x, rx = rs.y, nx = rs.z;
         // 1 / sx from the statistics (a zero row, and the zero-filled statistics behind the corpus' last row: +Inf - the accumulators are all 0
@@ -671,7 +635,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
         }
         return 0ull;
     };
-    auto boundary_cands = [&](int ti, unsigned long long m, const float4 rs, const int (&ithr)[2], const vgq_i32x16 &acc0, const vgq_i32x16 &acc1) __attribute__((always_inline)) {
+    auto boundary_cands = [&](int ti, unsigned long long m, const float4 rs, const int (&ithr)[2], const vgb_i32x16 &acc0, const vgb_i32x16 &acc1) __attribute__((always_inline)) {
         const long long row_cur = (tile_first + ti) * VGQ_TILE + x;
         const float sx = rs.x, rx = rs.y, nx = rs.z;
         {
@@ -699,7 +663,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
             }
         }
     };
-    auto boundary = [&](int ti, const vgq_i32x16 &acc0, const vgq_i32x16 &acc1) __attribute__((always_inline)) {
+    auto boundary = [&](int ti, const vgb_i32x16 &acc0, const vgb_i32x16 &acc1) __attribute__((always_inline)) {
         const float4 rs = stat_of(ti);
         int ithr[2];
         const unsigned long long m = boundary_first(rs, acc0, acc1, ithr);
@@ -712,7 +676,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
     // tile minima (vg_q8_pre_select_kernel) therefore stands for k different rows whose exact distances are no larger: a valid start
     // threshold for the first real stage - without the five warm-up stages (two tiles with every gate open, then x8, x8, x8, x8) that cost
     // 1.0 of a 1024 x 10M x 384 batch's 5.2 ms (profiles/r10_q8_stage_timeline_before.txt).
-    auto pre_boundary = [&](int ti, const vgq_i32x16 &acc0, const vgq_i32x16 &acc1) __attribute__((always_inline)) -> float {
+    auto pre_boundary = [&](int ti, const vgb_i32x16 &acc0, const vgb_i32x16 &acc1) __attribute__((always_inline)) -> float {
         const long long tile = tile_first + ti;
         const long long row_cur = tile * VGQ_TILE + x;
         const float4 rs = rstat_lds[((ti >> 1) & (VGQ_STAT_SLOTS - 1)) * 64 + (ti & 1) * 32 + x];
@@ -777,7 +741,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
     // reads the other, in the SAME instruction stream - the matrix pipe takes 32 cycles per MFMA and the issue port 4, so up to ~5 other
     // instructions fit beside every MFMA (MI355X_MICROARCH.md) instead of a block of VALU work during which this wavefront offers the pipe nothing.
     constexpr bool SWP = VGQ_SWP != 0 && !PRE && KS == 1 && QS == 2 && NTB <= 12;    // (both short-row forms: eight wavefronts x 512 queries, four x 256)     // (16 k-steps: the second pair spills)
-    vgq_i32x16 acc0, acc1, accb0, accb1;
+    vgb_i32x16 acc0, acc1, accb0, accb1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0; acc1[r] = 0; accb0[r] = 0; accb1[r] = 0; }
     float4 rs_prev = make_float4(0.0f, 0.0f, 0.0f, 0.0f);                 // (SWP) the previous tile's row statistics
@@ -793,7 +757,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
     // ride the B operands' in-order queue), the pair's own test and the compaction into the pair buffers in the last two k-steps.  Runs
     // remain for a queue that fills faster than that (the first stages) and for the partition's end.
     constexpr bool CAN_DRAIN = SWP && VGQ_SWP_DRAIN != 0 && NTB >= 8 && VGQ_BPIPE + 3 <= NTB;
-    auto tile_step = [&](int ti, vgq_i32x16 &acc0, vgq_i32x16 &acc1, const vgq_i32x16 &old0, const vgq_i32x16 &old1, auto drain_c) __attribute__((always_inline)) {
+    auto tile_step = [&](int ti, vgb_i32x16 &acc0, vgb_i32x16 &acc1, const vgb_i32x16 &old0, const vgb_i32x16 &old1, auto drain_c) __attribute__((always_inline)) {
         constexpr bool DRAIN = decltype(drain_c)::value;
         const int sj = (ti + LEAD) >> 1;                                      // the statistics group this tile's first trip may issue
         const bool stat_turn = ((ti + LEAD) & 1) == 0 && 2 * sj < T + 1 && wave == (sj & (WAVES - 1));
@@ -804,7 +768,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
         // one ring trip per K-part of the tile (KS = 1: the whole row): the accumulators run on across the parts
         vgb_static_for<0, KS>([&](auto kc) {
         constexpr int kp = decltype(kc)::value;
-        VGQ_TICK(tk0);
+        VGB_TICK(VGQ_TIMING, tk0);
 #if VGQ_TRACE
         const unsigned long long tr_k0 = __builtin_readcyclecounter();
 #endif
@@ -835,7 +799,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
                 asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(it) : "v"(tf2));
                 ithr_prev[p - 2] = it;
             } else if constexpr (p >= 4 && p <= 7) {
-                const vgq_i32x16 &o = p < 6 ? old0 : old1;
+                const vgb_i32x16 &o = p < 6 ? old0 : old1;
                 constexpr int b = (p & 1) * 8;
                 sw_gm[p - 4] = max(max(max(o[b], o[b + 1]), max(o[b + 2], o[b + 3])), max(max(o[b + 4], o[b + 5]), max(o[b + 6], o[b + 7])));
             } else if constexpr (p == 8) {
@@ -854,10 +818,10 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
         const uint32_t d_kqa = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float4 *)const_cast<float4 *>(kq_w) +
                                (uint32_t)((32 * d_set + (d_r & 3) + 8 * (d_r >> 2)) * 16);
         int d_I = 0;
-        vgh_i32x4 d_m0 = {0, 0, 0, 0}, d_m1 = {0, 0, 0, 0}, d_kq0 = {0, 0, 0, 0}, d_kq1 = {0, 0, 0, 0};
+        vgb_i32x4 d_m0 = {0, 0, 0, 0}, d_m1 = {0, 0, 0, 0}, d_kq0 = {0, 0, 0, 0}, d_kq1 = {0, 0, 0, 0};
         vgb_static_for<0, BP>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
-            vgq_lds_read128<1024 * t>(bq[t], baddr);
+            vgb_lds_read128<1024 * t>(bq[t], baddr);
         });
         vgb_static_for<0, NTB>([&](auto tc) {
             constexpr int t = decltype(tc)::value;
@@ -866,17 +830,17 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
             if constexpr (DRAIN && t == BP + 1)
                 asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(bq[t % BP]), "+v"(d_I), "+v"(d_m0), "+v"(d_m1), "+v"(d_kq0), "+v"(d_kq1) : "n"(in_flight_after));
             else
-            vgq_wait_lds<in_flight_after>(bq[t % BP]);
-            const vgh_i32x4 b = bq[t % BP];
+            vgb_wait_lds<in_flight_after>(bq[t % BP]);
+            const vgb_i32x4 b = bq[t % BP];
             acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(areg[0][kp * NTB + t], b, acc0, 0, 0, 0);
             if constexpr (QS > 1) acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(areg[QS - 1][kp * NTB + t], b, acc1, 0, 0, 0);
-            if constexpr (t + BP < NTB) vgq_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
+            if constexpr (t + BP < NTB) vgb_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
             if constexpr (DRAIN && t == 0) {
                 asm volatile("ds_read_b32 %0, %1" : "=v"(d_I) : "v"(d_ent + (uint32_t)((16 * d_set + d_r) * 4)) : "memory");
-                vgq_lds_read128<16 * QS * 4>(d_m0, d_ent);
-                vgq_lds_read128<16 * QS * 4 + 16>(d_m1, d_ent);
-                vgq_lds_read128<0>(d_kq0, d_kqa);
-                vgq_lds_read128<64>(d_kq1, d_kqa);
+                vgb_lds_read128<16 * QS * 4>(d_m0, d_ent);
+                vgb_lds_read128<16 * QS * 4 + 16>(d_m1, d_ent);
+                vgb_lds_read128<0>(d_kq0, d_kqa);
+                vgb_lds_read128<64>(d_kq1, d_kqa);
             }
             if constexpr (DRAIN && t == NTB - 2) {
                 // the pair's own test (process_queue's arithmetic) and its slot in the set's pair buffer
@@ -884,7 +848,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
                 const int ithr_e = d_set ? d_m0[2] : d_m0[1];
                 const float sx_e = __int_as_float(d_m0[3]), rx_e = __int_as_float(d_m1[0]), nx_e = __int_as_float(d_m1[1]);
                 const int h_e = d_m1[2];
-                const vgh_i32x4 kqi = h_e ? d_kq1 : d_kq0;
+                const vgb_i32x4 kqi = h_e ? d_kq1 : d_kq0;
                 const float kqx = __int_as_float(kqi[0]), kqy = __int_as_float(kqi[1]), kqz = __int_as_float(kqi[2]), kqw = __int_as_float(kqi[3]);
                 float lhs = fmaf((float)d_I, sx_e, fmaf(kqx, rx_e, fmaf(kqy, nx_e, kqz)));
                 if constexpr (L2M) lhs = fmaf(-(mfac * nx_e * nx_e), kqw, lhs);
@@ -916,7 +880,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
             }
             __builtin_amdgcn_sched_barrier(0);
         });
-        VGQ_TICK(tk1);
+        VGB_TICK(VGQ_TIMING, tk1);
 #if VGQ_TRACE
         const unsigned long long tr_k1 = __builtin_readcyclecounter();
 #endif
@@ -937,7 +901,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
                 rs_prev = stat_of(ti);                                       // (read before the group's barrier, as the boundary itself would)
             } else boundary(ti, acc0, acc1);
         }
-        VGQ_TICK(tk2);
+        VGB_TICK(VGQ_TIMING, tk2);
 #if VGQ_TRACE
         const unsigned long long tr_b1 = __builtin_readcyclecounter();
 #endif
@@ -966,7 +930,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
 #endif
         });
     };
-    auto step = [&](int ti, vgq_i32x16 &n0, vgq_i32x16 &n1, const vgq_i32x16 &o0, const vgq_i32x16 &o1) __attribute__((always_inline)) {
+    auto step = [&](int ti, vgb_i32x16 &n0, vgb_i32x16 &n1, const vgb_i32x16 &o0, const vgb_i32x16 &o1) __attribute__((always_inline)) {
         if constexpr (CAN_DRAIN) {
             if (n_q >= (unsigned)VGQ_DRAIN_MIN) tile_step(ti, n0, n1, o0, o1, std::true_type{});
             else tile_step(ti, n0, n1, o0, o1, std::false_type{});
@@ -1012,10 +976,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && KS == 1 ? 2 : 1)) void v
 template <int NTB, int MODE, int WAVES, int QS, int KS>
 static int launch_q8_form(const BatchArgsQ8 &a, int blocks, size_t smem, hipStream_t stream, bool pre) {
     auto kern = pre ? vg_batch_q8_kernel<NTB, MODE, WAVES, QS, KS, true> : vg_batch_q8_kernel<NTB, MODE, WAVES, QS, KS, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * WAVES), smem, stream, a);
-    return (int)hipGetLastError();
+    return vgb_launch(kern, blocks, 64 * WAVES, smem, stream, a);
 }
 template <int NTB, int WAVES, int QS, int KS>
 static int launch_q8_form_mode(const BatchArgsQ8 &a, int blocks, size_t smem, hipStream_t stream, bool pre) {
@@ -1053,7 +1014,7 @@ static int launch_q8l_mode(const BatchArgsQ8 &a, int blocks, size_t smem, hipStr
 }
 // rows of 513 .. 1536 int8 elements: (k-steps per K-part) * 8 + (K-parts), 0 if not served
 static int vgql_cfg(long long stride_bytes) {
-    const int ntb = (int)((stride_bytes + 31) / 32);
+    const int ntb = vgb_ksteps(stride_bytes);
     if (ntb <= 16) return 0;
     if (ntb <= 24) return 12 * 8 + 2;
     if (ntb <= 32) return 16 * 8 + 2;
@@ -1065,7 +1026,7 @@ static size_t vgql_lds_bytes(int NTB) {
            (size_t)VGQL_WAVES * VGQ_QCAP * (16 * VGQL_QS + 8) * 4;
 }
 static int vgq_ntb(long long stride_bytes) {
-    const int ntb = (int)((stride_bytes + 31) / 32);
+    const int ntb = vgb_ksteps(stride_bytes);
     if (ntb <= 4) return 4;
     if (ntb <= 8) return 8;
     if (ntb <= 12) return 12;
@@ -1083,8 +1044,6 @@ extern "C" int vgh_launch_exact_bf16(const BatchArgsH *a, int ntb, int waves, in
 extern "C" int vghl_exact_regions_f16(const BatchArgsH *a, int waves, int regions, size_t smem, hipStream_t stream);
 extern "C" int vghl_exact_regions_bf16(const BatchArgsH *a, int waves, int regions, size_t smem, hipStream_t stream);
 extern "C" int vghl_exact_regions_f32(const BatchArgsH *a, int waves, int regions, size_t smem, hipStream_t stream);
-extern "C" int vg_batch_merge_launch(const uint64_t *dev_cand, int nq_pad, int lists_per_query, int npart, int k,
-                                     uint64_t *dev_out_keys, hipStream_t stream);        // vg_batch.hip
 
 // does the int8 batch filter serve rows of q8stride_bytes int8 elements (xstride_bytes: the f32 rows) with lists of k?
 extern "C" int vg_batch_q8_serves(long long q8stride_bytes, long long xstride_bytes, int k) {

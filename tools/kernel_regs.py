@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Register / scratch usage of every kernel of one HIP translation unit (from the code object metadata):
-    python tools/kernel_regs.py sqlite-vector_amd/csrc/vg_multi.hip [--all | --digest]
+    python tools/kernel_regs.py sqlite-vector_amd/csrc/vg_multi.hip [--all | --digest] [-DNAME[=VALUE] ...]
 prints name, VGPRs, spilled VGPRs, scratch bytes; without --all only kernels that spill or use scratch.
+-D... arguments go to the compile: the batch units exist only under their unit flags (HIP_UNITS in build.py), for instance
+vg_batch_i8.hip -DVGI_TU_PRE, vg_batch_h.hip -DVGH_TU=1..8, vg_batch_hl.hip -DVGHL_TU=0..5.
 --digest: one line per kernel - VGPRs, SGPRs, spilled VGPRs / SGPRs, scratch, static LDS and a hash of the kernel's instruction text
 (comments stripped, local label numbers and mangled symbol names blanked), then the demangled name: two revisions of a unit whose
 lines agree generate the same code."""
@@ -16,7 +18,8 @@ show_all = "--all" in sys.argv
 digest = "--digest" in sys.argv
 with tempfile.NamedTemporaryFile(suffix=".s") as f:
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value",
-                           "-Wno-unused-result", "--cuda-device-only", "-S", "-o", f.name, src], stderr=subprocess.DEVNULL)
+                           "-Wno-unused-result", "--cuda-device-only", "-S", "-o", f.name, src] +
+                          [a for a in sys.argv[2:] if a.startswith("-D")], stderr=subprocess.DEVNULL)
     text = open(f.name).read()
 
 
