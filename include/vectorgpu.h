@@ -204,7 +204,8 @@ int vg_scan_within_batch_keys(const vg_corpus *c, int query, int64_t first, int6
  * mapped to positions on the host (implicit rowids: rowid - base; an ascending map: the search behind vg_corpus_find_rowid; a map
  * that is not ascending: VG_ERR_UNSUPPORTED); rowids the corpus does not hold are ignored, duplicates are harmless, *out_set (may
  * be NULL) = rows allowed.  vg_corpus_mask_count: rows allowed, -1 without a mask.
- * ONLY the masked scans (vg_scan_topk_masked[_keys], vg_scan_topk_batch_masked[_keys], vg_scan_within_masked, vg_scan_within_batch_masked) read the mask: every other call behaves the same with and without one.  A call that changes the
+ * ONLY the masked scans (vg_scan_topk_masked[_keys], vg_scan_topk_batch_masked[_keys], vg_scan_within_masked, vg_scan_within_batch_masked) read the mask: every other call behaves the same with and without one.  The row mask and the
+ * labels (labeled scans, below) are independent: the labeled scans do not read the mask, the masked scans do not read the labels.  A call that changes the
  * number of rows or which row sits at which position (append*, delete_rows, clear) drops the mask; patch_rows, reserve and trim
  * keep it; vg_corpus_clone copies it.
  * vg_scan_topk_masked: the contract of vg_scan_topk restricted to the allowed rows - NaN / +Inf never enter, fewer than k rows
@@ -242,6 +243,42 @@ int     vg_scan_topk_batch_masked(vg_corpus *c, int metric, const void *queries,
                                   int64_t *out_rowids, double *out_dist, int *out_counts);
 int     vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k,
                                        uint64_t *out_keys, int *out_counts);
+
+/* ---- labeled scans: a label per row, each query its own label - the equality filter on a metadata column ("the k nearest rows of
+ * tenant T", and in a batch a different T per query; no reference entry point) ----
+ * A label is a uint32_t per scan position kept on the handle, in device memory (4 bytes per row).  vg_corpus_set_labels: n must equal
+ * vg_corpus_rows(c) (VG_ERR_INVALID otherwise); VG_LABEL_NONE is the "no label" value - such a row matches no query.
+ * vg_corpus_has_labels: 1 while labels are set.  Lifetime: the mask's, rule for rule - append*, delete_rows and clear drop the
+ * labels; patch_rows, reserve and trim keep them; vg_corpus_clone copies them.
+ * ONLY the labeled scans (vg_scan_topk_labeled[_keys], vg_scan_topk_batch_labeled[_keys]) read the labels: every other call behaves
+ * the same with and without them.  Labels and row mask are independent: the labeled scans do not read the mask (and leave it as it
+ * is), the masked scans do not read the labels.
+ * vg_scan_topk_labeled: the contract of vg_scan_topk_masked with "allowed" meaning labels[p] == label - ascending (distance, scan
+ * position) whatever the handle's tie_order, NaN / +Inf never enter, every distance the float vg_scan_distances reports for that
+ * row, bit for bit.  A small kernel turns (labels, label) into a bitmap in a scratch buffer of the handle, then the single masked
+ * kernels run over it: two launches on the corpus stream, one wait.  1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below);
+ * no labels set: VG_ERR_INVALID; label == VG_LABEL_NONE: VG_ERR_INVALID; an empty corpus or a label no row carries: *out_count = 0.
+ * vg_scan_topk_labeled_keys: the same as packed keys with positions local to this corpus (out_keys[k]).
+ * vg_scan_topk_batch_labeled: nq queries (row-major nq x dim, host), query i's answer is what vg_scan_topk_labeled(c, metric, q_i,
+ * k, query_labels[i], ..) is contracted to return; out_rowids / out_dist are nq x k, the slots of query i behind out_counts[i] are
+ * NOT written.  f32 / uint8 / int8 rows of a register-resident shape: the queries are ordered by label, then 4 (or 2) of them share
+ * every row load of a pass; a row is computed once with its batch and offered only to the queries whose label it carries, and a
+ * batch of rows that carries none of the pass' labels is not read (vg_scan_multi.h, labeled form; the plan: vg_batch_labeled_plan,
+ * vectorgpu_diag.h).  uint8 / int8: identical to nq vg_scan_topk_labeled calls; f32: the floats of vg_scan_topk_batch_masked under
+ * the same launch shape.  f16 / bf16, long rows and every other shape without a multi-query form: one single labeled scan per query,
+ * one bitmap per distinct label of the batch.  Any query_labels[i] == VG_LABEL_NONE, nq < 1 or a NULL argument: VG_ERR_INVALID, with
+ * the counts zeroed first.  Timings not measured yet. */
+#define VG_LABEL_NONE 0xFFFFFFFFu
+int     vg_corpus_set_labels(vg_corpus *c, const uint32_t *labels, int64_t n);
+int     vg_corpus_clear_labels(vg_corpus *c);
+int     vg_corpus_has_labels(const vg_corpus *c);
+int     vg_scan_topk_labeled(vg_corpus *c, int metric, const void *query, int k, uint32_t label,
+                             int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_scan_topk_labeled_keys(vg_corpus *c, int metric, const void *query, int k, uint32_t label, uint64_t *out_keys, int *out_count);
+int     vg_scan_topk_batch_labeled(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
+                                   int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_scan_topk_batch_labeled_keys(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
+                                        uint64_t *out_keys, int *out_counts);
 
 /* ---- masked range scans: every ALLOWED row within a distance of the query - "every row of this tenant within r", near-duplicate
  * detection inside one category (no reference entry point; the reference's form is "SELECT ... FROM vector_full_scan_stream(...)
@@ -404,6 +441,17 @@ int     vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *query, 
  * GLOBAL scan position): the answer of one corpus holding all rows.  Same contract. */
 int     vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const void *queries, int nq, int k,
                                          int64_t *out_rowids, double *out_dist, int *out_counts);
+/* the labels over GLOBAL scan positions (vg_corpus_set_labels: n must equal vg_shards_rows), dealt out to the shards by the
+ * block-cyclic map of the rows; vg_shards_has_labels: 1 while every shard holds labels.  The labeled scans over every shard: each
+ * shard answers over its own rows, merged per query by (distance, GLOBAL scan position) = one corpus holding all rows (rowids,
+ * order and distance bits). */
+int     vg_shards_set_labels(vg_shards *s, const uint32_t *labels, int64_t n);
+int     vg_shards_clear_labels(vg_shards *s);
+int     vg_shards_has_labels(const vg_shards *s);
+int     vg_shards_scan_topk_labeled(vg_shards *s, int metric, const void *query, int k, uint32_t label,
+                                    int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
+                                          int64_t *out_rowids, double *out_dist, int *out_counts);
 /* the masked range scans over every shard: each shard answers over its own bits (a shard whose share of the mask is empty launches
  * nothing and contributes nothing), merged like vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus
  * holding all rows.  Same contract; the results are read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and

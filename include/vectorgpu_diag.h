@@ -56,6 +56,9 @@ int vg_batch_q8_status(const vg_corpus *c);
  * lane (the single masked scan's shape for the fallback; 64 / 0 for the long-row kernel).  Pure host logic.  Every pass of a masked
  * batch takes one slot of the profiling ring (vg_set_profiling / vg_profile_mean_ms: kernel and merge time per pass). */
 int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
+/* the same for vg_scan_topk_batch_labeled: queries per pass of the labeled multi-query scan (4 or 2; 0 = the fallback, one single
+ * labeled scan per query, one bitmap per distinct label) and the launch shape of the kernel that runs.  Pure host logic. */
+int vg_batch_labeled_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 /* the floor key of a paged scan (vg_scan_topk_after, vectorgpu.h): the smallest key behind a cursor whose distance is after_dist, when
  * the rows at scan positions < first_pos_behind are not behind it at that distance (P = rows held with rowid <= after_rowid).  f = the
  * smallest float >= after_dist (the double rounded towards +Inf, -0.0 normalised to 0.0): floor = key(f, first_pos_behind) when

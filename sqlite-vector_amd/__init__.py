@@ -197,6 +197,20 @@ def _load():
         "vg_scan_topk_batch_masked_keys": (i32, [vp, i32, vp, i32, i32, vp, vp]),
         "vg_shards_scan_topk_batch_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
         "vg_batch_masked_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        # labeled scans: a uint32 label per row on the handle, each query names one
+        "vg_corpus_set_labels": (i32, [vp, vp, i64]),
+        "vg_corpus_clear_labels": (i32, [vp]),
+        "vg_corpus_has_labels": (i32, [vp]),
+        "vg_scan_topk_labeled": (i32, [vp, i32, vp, i32, C.c_uint32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_labeled_keys": (i32, [vp, i32, vp, i32, C.c_uint32, vp, C.POINTER(i32)]),
+        "vg_scan_topk_batch_labeled": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp]),
+        "vg_scan_topk_batch_labeled_keys": (i32, [vp, i32, vp, i32, vp, i32, vp, vp]),
+        "vg_batch_labeled_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "vg_shards_set_labels": (i32, [vp, vp, i64]),
+        "vg_shards_clear_labels": (i32, [vp]),
+        "vg_shards_has_labels": (i32, [vp]),
+        "vg_shards_scan_topk_labeled": (i32, [vp, i32, vp, i32, C.c_uint32, vp, vp, C.POINTER(i32)]),
+        "vg_shards_scan_topk_batch_labeled": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp]),
         "vg_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
         "vg_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
         "vg_scan_within_batch_keys": (i32, [vp, i32, i64, i64, vp]),
@@ -275,6 +289,63 @@ def _scan_topk_batch_masked(fn, h, metric, queries, k):
     cnt = np.zeros(max(nq, 1), dtype=np.int32)
     _check(fn(h, metric, _ptr(queries), nq, k, _ptr(ids), _ptr(dist), _ptr(cnt)))
     return ids, dist, cnt[:nq]
+
+
+LABEL_NONE = 0xFFFFFFFF                             # VG_LABEL_NONE: a row with this label matches no query
+
+
+def batch_labeled_plan(corpus, metric):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_topk_batch_labeled serves this corpus with; 0 queries per pass =
+    one single labeled scan per query (f16 / bf16, long rows) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().vg_batch_labeled_plan(corpus.h, metric, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
+
+
+def _labels_u32(labels):
+    a = np.asarray(labels)
+    if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > LABEL_NONE):
+        raise ValueError("labels are integers in 0 .. 2^32 - 1 (LABEL_NONE = 2^32 - 1: no label)")
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.uint32)
+
+
+class _LabeledOps:
+    """the labeled scans, shared by Corpus and Shards (`_lprefix`: vg_corpus / vg_shards, `_sprefix`: vg_ / vg_shards_): a uint32 label
+    per scan position on the handle, a query names the label its rows must carry; ascending (distance, scan position) order"""
+
+    def set_labels(self, labels):
+        """one label per scan position (len == rows); LABEL_NONE marks a row no query matches"""
+        lab = _labels_u32(labels)
+        _check(getattr(lib(), self._lprefix + "_set_labels")(self.h, _ptr(lab), lab.size))
+
+    def clear_labels(self):
+        _check(getattr(lib(), self._lprefix + "_clear_labels")(self.h))
+
+    def has_labels(self):
+        return bool(getattr(lib(), self._lprefix + "_has_labels")(self.h))
+
+    def scan_topk_labeled(self, metric, query, k, label):
+        """the k nearest rows whose label is `label`: (rowids, distances)"""
+        query = np.ascontiguousarray(query)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        cnt = C.c_int(0)
+        _check(getattr(lib(), self._sprefix + "scan_topk_labeled")(self.h, metric, _ptr(query), k, int(label), _ptr(ids), _ptr(dist), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value]
+
+    def scan_topk_batch_labeled(self, metric, queries, labels, k):
+        """scan_topk_labeled for every row of `queries` with its own label, in shared passes: (rowids [nq, k], distances [nq, k],
+        counts [nq]); the slots of query i behind counts[i] are not written"""
+        queries = np.ascontiguousarray(queries)
+        nq = queries.shape[0]
+        lab = _labels_u32(labels)
+        if lab.size != nq:
+            raise ValueError("scan_topk_batch_labeled takes one label per query")
+        ids = np.zeros((nq, max(k, 1)), dtype=np.int64)
+        dist = np.zeros((nq, max(k, 1)), dtype=np.float64)
+        cnt = np.zeros(max(nq, 1), dtype=np.int32)
+        _check(getattr(lib(), self._sprefix + "scan_topk_batch_labeled")(self.h, metric, _ptr(queries), nq, _ptr(lab), k, _ptr(ids), _ptr(dist), _ptr(cnt)))
+        return ids, dist, cnt[:nq]
 
 
 AFTER_START = (float("-inf"), -(1 << 63))          # the cursor in front of every row
@@ -446,8 +517,9 @@ def _set_mask(obj, prefix, rows, bits, positions, rowids):
     return int(getattr(L, prefix + "_mask_count")(obj.h))
 
 
-class Corpus(_PagedScans):
+class Corpus(_PagedScans, _LabeledOps):
     """One HBM-resident corpus shard (opaque vg_corpus handle)."""
+    _lprefix, _sprefix = "vg_corpus", "vg_"
 
     def __init__(self, vtype, dim, device=0, capacity=0):
         self.h = C.c_void_p()
@@ -765,8 +837,9 @@ def device_memory(device=0):
     return f.value, t.value
 
 
-class Shards(_PagedScans):
+class Shards(_PagedScans, _LabeledOps):
     """One logical corpus dealt block-cyclically over several devices of this process (opaque vg_shards handle)."""
+    _lprefix, _sprefix = "vg_shards", "vg_shards_"
 
     def __init__(self, vtype, dim, devices, block_rows=0):
         self.h = C.c_void_p()

@@ -56,6 +56,11 @@ struct ScanArgs {
     // key is >= its query's floor - one key for the single kernels, NQ keys for a multi-query pass (VG_EMPTY_KEY in the pad slot of a
     // ragged pass: nothing is admitted).  Device memory.  A field the other kernels never read.
     const uint64_t *floor;
+    // ---- "labeled" mode (the VG_MQ_LABELED forms of vg_scan_multi.h): a label per scan position (n_rows dwords) and the NQ labels of
+    // the pass' queries; a row is offered to query n only when labels[row] == qlabels[n] (0xFFFFFFFF, on either side, matches nothing).
+    // Device memory.  Fields the other kernels never read - and the last ones, so that every other kernel's arguments keep their offsets.
+    const uint32_t *labels;
+    const uint32_t *qlabels;
 };
 
 // ------------------------------------------------------------------------------------------ keys

@@ -174,6 +174,14 @@ struct vg_corpus {
     int64_t mask_cap_words = 0;
     std::vector<uint64_t> mask_host;          // the same words on the host (vg_corpus_clone copies them)
     int64_t mask_count = -1;                  // rows allowed; -1: no mask
+    // labeled scans (vg_scan_labeled.hip, vg_multi_labeled.hip): a uint32 per scan position in device memory (VG_LABEL_NONE: the row
+    // matches no query).  Read by the labeled scans only; lifetime rule for rule the mask's (vg_drop_labels).  d_label_bits: the bitmap
+    // "rows that carry label L" the single labeled scan builds for itself (vg_label_bits_kernel) - scratch, never the user's mask
+    uint32_t *d_labels = nullptr;             // n_rows dwords while labels are set (labels_cap allocated)
+    int64_t labels_cap = 0;
+    bool has_labels = false;
+    uint64_t *d_label_bits = nullptr;         // ceil(n_rows / 64) words (label_bits_cap_words allocated)
+    int64_t label_bits_cap_words = 0;
     int max_blocks = 0;
     int cu_count = 0;
 
@@ -248,6 +256,9 @@ static inline void vg_drop_within_results(vg_corpus *c) {           // (held ran
 }
 static inline void vg_drop_mask(vg_corpus *c) { c->mask_count = -1; c->mask_host.clear(); }   // (the device words stay allocated for the next mask)
 int vg_mask_upload(vg_corpus *c);             // vg_scan_masked.hip: mask_host -> d_mask
+static inline void vg_drop_labels(vg_corpus *c) { c->has_labels = false; }   // (the device dwords stay allocated for the next labels)
+// vg_scan_labeled.hip: d_label_bits <- "labels[p] == label" for every row, enqueued on the corpus stream (no wait)
+int vg_label_bits_enqueue(vg_corpus *c, uint32_t label);
 
 // next slot of the profiling ring (nullptr when profiling is off)
 static inline hipEvent_t *vg_prof_slot(vg_corpus *c, uint8_t flags) {
@@ -302,11 +313,15 @@ typedef scan_fn_t (*vg_pick_multi_fn_t)(int vtype, int acc, int U, int NQ);
 scan_fn_t vg_pick_scan_masked(int vtype, int acc, int U, bool long_rows);   // vg_scan_masked.hip: the masked single scan's kernel table
 scan_fn_t vg_pick_scan_after(int vtype, int acc, int U, bool long_rows);    // vg_scan_after.hip: the paged single scans' tables,
 scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows);   // ... all rows / the allowed rows
-struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; };
+// `labeled` (the labeled scans, vg_scan_labeled.hip / vg_multi_labeled.hip): the single form runs the masked kernels over
+// c->d_label_bits - the caller enqueued vg_label_bits_enqueue in front - and requires labels, not a mask; the batch form sets
+// ScanArgs.labels / .qlabels, `qlabels` = a label per query (the caller hands the queries over ordered by label: the fallback
+// builds one bitmap per run of equal labels).
+struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; };
 struct VgFusedBatchForm { const char *who; vg_pick_multi_fn_t pick; VgFusedForm single; };
 int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count);
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
-                       uint64_t *out_keys, int *out_counts);
+                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr);
 // ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): the floor-key forms behind the C ABI, what the shards call per shard.
 // Floors are keys over positions LOCAL to the corpus; a floor of VG_KEY_EMPTY admits nothing (no launch in the single form).
 int vg_after_floor_run(vg_corpus *c, bool masked, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count);

@@ -37,12 +37,14 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
 // NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on the corpus stream.  One launcher for every form
 // (VgFusedBatchForm, vg_internal.h): the masked batch, and the paged batches of vg_multi_after.hip (dev_floors: NQ keys).
 static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s,
-                               const uint8_t *dev_queries, const uint64_t *dev_floors, int k, uint64_t *dev_cand, uint64_t *dev_out_keys) {
+                               const uint8_t *dev_queries, const uint64_t *dev_floors, const uint32_t *dev_qlabels, int k, uint64_t *dev_cand,
+                               uint64_t *dev_out_keys) {
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);
     ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_queries, k);
     a.cand = dev_cand;
     if (f.single.masked) a.mask = c->d_mask;
     if (f.single.after) a.floor = dev_floors;
+    if (f.single.labeled) { a.labels = c->d_labels; a.qlabels = dev_qlabels; }
     const size_t smem = std::max<size_t>((size_t)NQ * c->nch * 16, (size_t)VG_PUBLISH_LDS_BYTES);
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);          // one slot of the profiling ring per pass
     if (evs) hipEventRecord(evs[0], c->stream);
@@ -61,12 +63,14 @@ static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metri
 
 // nq queries, NQ per pass; every pass of every slice is enqueued back to back on the corpus stream, one wait at the end
 static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries,
-                              int nq, const uint64_t *floors, int k, uint64_t *out_keys, int *out_counts) {
+                              int nq, const uint64_t *floors, const uint32_t *qlabels, int k, uint64_t *out_keys, int *out_counts) {
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
     const int slice = std::min(nq_pad, VG_FUSED_SLICE);
-    // (an after form: the slice's floor keys sit behind its queries in d_bq and go up with them; a pad slot admits nothing)
+    // (an after form: the slice's floor keys sit behind its queries in d_bq and go up with them; a pad slot admits nothing.  A labeled
+    //  form: the slice's query labels, behind those; a pad slot carries VG_LABEL_NONE and matches nothing)
     const size_t fl_off = (size_t)slice * c->stride;
-    const size_t qbytes = fl_off + (f.single.after ? (size_t)slice * sizeof(uint64_t) : 0), keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
+    const size_t lb_off = fl_off + (f.single.after ? (size_t)slice * sizeof(uint64_t) : 0);
+    const size_t qbytes = lb_off + (f.single.labeled ? (size_t)slice * sizeof(uint32_t) : 0), keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
     if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
                                 HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
     if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
@@ -78,16 +82,21 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
     for (int i = 0; i < nq; ++i) memcpy(hq.data() + (size_t)i * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
     std::vector<uint64_t> hf(f.single.after ? (size_t)nq_pad : 0, VG_KEY_EMPTY);
     if (f.single.after) for (int i = 0; i < nq; ++i) hf[(size_t)i] = floors[i];
+    std::vector<uint32_t> hl(f.single.labeled ? (size_t)nq_pad : 0, VG_LABEL_NONE);
+    if (f.single.labeled) for (int i = 0; i < nq; ++i) hl[(size_t)i] = qlabels[i];
     int rc = VG_OK;
     for (int q0 = 0; q0 < nq_pad && rc == VG_OK; q0 += slice) {
         const int nqs = std::min(slice, nq_pad - q0);
         hipError_t e = hipMemcpyAsync(c->d_bq, hq.data() + (size_t)q0 * c->stride, (size_t)nqs * c->stride, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess && f.single.after)
             e = hipMemcpyAsync((uint8_t *)c->d_bq + fl_off, hf.data() + q0, (size_t)nqs * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && f.single.labeled)
+            e = hipMemcpyAsync((uint8_t *)c->d_bq + lb_off, hl.data() + q0, (size_t)nqs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) { rc = vg_fail(VG_ERR_HIP, "%s: query upload failed: %s", f.who, hipGetErrorString(e)); break; }
         for (int g = 0; g < nqs && rc == VG_OK; g += NQ)
             rc = launch_fused_multi(c, f, metric, fn, NQ, s, (const uint8_t *)c->d_bq + (size_t)g * c->stride,
-                                     reinterpret_cast<const uint64_t *>((const uint8_t *)c->d_bq + fl_off) + g, k, c->d_cand,
+                                     reinterpret_cast<const uint64_t *>((const uint8_t *)c->d_bq + fl_off) + g,
+                                     reinterpret_cast<const uint32_t *>((const uint8_t *)c->d_bq + lb_off) + g, k, c->d_cand,
                                      c->d_bkeys + (size_t)(q0 + g) * 64);
     }
     if (rc != VG_OK) { hipStreamSynchronize(c->stream); return rc; }      // (hq must outlive what was enqueued)
@@ -113,15 +122,20 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
 // packed keys (distance image << 32 | position local to this corpus), ascending, nq x k: the form a multi-shard caller merges.
 // Slots behind out_counts[i] are not written.  `floors`: a key per query, read by an after form only.
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
-                       uint64_t *out_keys, int *out_counts) {
-    if (!c || !queries || !out_counts || (f.single.after && !floors)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
+                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels) {
+    if (!c || !queries || !out_counts || (f.single.after && !floors) || (f.single.labeled && !qlabels)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", f.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.masked ? "masked" : "paged");
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.labeled ? "labeled" : f.single.masked ? "masked" : "paged");
     if (!out_keys) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (f.single.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (f.single.labeled) {
+        if (!c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+        for (int i = 0; i < nq; ++i)
+            if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", f.who, i);
+    }
     if ((f.single.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     HIP_TRY(hipSetDevice(c->device));
     VgShape s{};
@@ -130,13 +144,18 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
     if (NQ == 0) {                                               // no multi-query form: the single scans of the form, one by one
         const size_t row_bytes = (size_t)c->dim * c->es;
         for (int i = 0; i < nq; ++i) {
+            // (a labeled form: the bitmap of a label is built once and serves the run of queries that share it)
+            if (f.single.labeled && (i == 0 || qlabels[i] != qlabels[i - 1])) {
+                int rcb = vg_label_bits_enqueue(c, qlabels[i]);
+                if (rcb != VG_OK) return rcb;
+            }
             int rc = vg_fused_run(c, f.single, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, floors ? floors[i] : 0ull,
                                   out_keys + (size_t)i * k, &out_counts[i]);
             if (rc != VG_OK) return rc;
         }
         return VG_OK;
     }
-    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, k, out_keys, out_counts);
+    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, qlabels, k, out_keys, out_counts);
 }
 
 extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,

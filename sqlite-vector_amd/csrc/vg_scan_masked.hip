@@ -104,6 +104,7 @@ static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     ScanArgs a = vg_scan_args(c, metric, acc, s, c->d_query, k);
     a.cand = c->d_cand;
     if (f.masked) a.mask = c->d_mask;
+    if (f.labeled) a.mask = c->d_label_bits;                 // (the bitmap of one label, built on this stream in front of the scan)
     if (f.after) a.floor = reinterpret_cast<const uint64_t *>(c->d_query + c->stride);
     const size_t smem = std::max<size_t>(vg_query_lds_bytes(c, s), (size_t)VG_PUBLISH_LDS_BYTES);
 
@@ -126,10 +127,11 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
     if (!c || !query || !out_count) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     *out_count = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.masked ? "masked" : "paged");
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.labeled ? "labeled" : f.masked ? "masked" : "paged");
     if (!out_keys) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (f.labeled && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
     if ((f.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     if (f.after && floor == VG_EMPTY_KEY) return VG_OK;      // nothing is behind the cursor: no launch
     HIP_TRY(hipSetDevice(c->device));

@@ -34,12 +34,27 @@
 //                    batches - radius and queue fill - is wave-uniform and lives in scalar registers (`wave` goes through
 //                    readfirstlane so that the queue addresses stay scalar); region and capacity are read from the descriptors when
 //                    a burst leaves.  Not combined with VG_MQ_AFTER.
+//   VG_MQ_LABELED    a label per row, each query its own label: a row is offered to query n only when labels[row] == qlabels[n].
+//                    The masked form's pipeline with a per-lane dword in place of the wave-uniform mask word:
+//                      * every lane loads the label of its own row (lanes of one row read the same dword; row 0 stands in for a row
+//                        out of range, whose result is then unused, as for row_nn) ONE loop step ahead of the row prefetch whose
+//                        addresses it decides, and inside a step BEFORE that prefetch: vector loads return in order, so waiting for
+//                        a label leaves the row loads issued before it - the current batch - as the only ones that must have landed;
+//                      * one ballot over "carries the label of any of the pass' NQ queries" is the batch's wave-uniform word: zero
+//                        points the U loads at the zero chunk and skips all arithmetic with a scalar branch;
+//                      * the NQ query labels are loaded once, made wave-uniform and live in scalar registers; `label == qlabel[n]`
+//                        is folded into query n's offer predicate.  VG_LABEL_NONE (0xFFFFFFFF) matches nothing on either side: it
+//                        is folded into `owner`, so a pad query of a ragged pass (label NONE) collects nothing.
+//                    What the pipeline carries: three label dwords per lane (current, prefetched, in flight) and the current batch's
+//                    ballot - per-stage ballots PER QUERY would be 2 * NQ scalar registers a stage.  Not combined
+//                    with MASKED / AFTER / WITHIN.  Without the flag the label values are never defined and everything folds away.
 // The forms were five hand-copied loops; the code generated for every instance of this template was checked identical to that of the
 // copy it replaced (instruction text, registers, spills, scratch, LDS: DESIGN.md 3.6) at the commit that folded them.
 //
 //   a.query         : NQ zero-padded queries back to back (nch * 16 bytes each); WITHIN: and BEHIND them NQ VgWithinQuery descriptors
 //   a.mask          : (MASKED) ceil(n_rows / 64) words, bits behind the last row clear
 //   a.floor         : (AFTER) NQ keys
+//   a.labels        : (LABELED) n_rows dwords;  a.qlabels : (LABELED) NQ dwords
 //   a.cand          : (top-k forms) [NQ][gridDim.x][64] candidate keys
 //   descriptor n    : (WITHIN) the [count | cap keys] region of query n, its capacity and its radius (a float: the host rounds down)
 //   a.store_lds_off : (WITHIN) byte offset in dynamic LDS of the key queues, [NQ][wavefront][VG_WITHIN_QUEUE]
@@ -51,7 +66,8 @@
 
 #include "vg_scan.h"
 
-enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4 };
+enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4, VG_MQ_LABELED = 8 };
+#define VG_MQ_LABEL_NONE 0xFFFFFFFFu      // (VG_LABEL_NONE of vectorgpu.h)
 
 struct VgWithinQuery {                 // 32 bytes, read through wave-uniform addresses (scalar loads)
     unsigned long long *out;           // [count | cap keys]; the count keeps counting past cap
@@ -86,7 +102,9 @@ __device__ inline void vg_mw_offer(uint64_t key, bool match, uint64_t *queue, in
 template <int VT, int ACC, int U, int NQ, int FORM>          // VT: T_F32 / T_U8 / T_I8; FORM: VG_MQ_* flags
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
     constexpr bool MASKED = (FORM & VG_MQ_MASKED) != 0, AFTER = (FORM & VG_MQ_AFTER) != 0, WITHIN = (FORM & VG_MQ_WITHIN) != 0;
+    constexpr bool LABELED = (FORM & VG_MQ_LABELED) != 0;
     static_assert(!(AFTER && WITHIN), "a range scan has no cursor");
+    static_assert(!LABELED || FORM == VG_MQ_LABELED, "the labeled form is not combined with the masked, paged or range forms");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
     // (WITHIN: wave-uniform by construction; readfirstlane says so to the compiler, and the queue addresses stay scalar)
@@ -130,6 +148,11 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
             if constexpr (AFTER) floor_key[n] = vg_uniform64(a.floor[n]);
         }
     }
+    uint32_t qlabel[NQ];                                               // LABELED: wave-uniform, scalar registers
+    if constexpr (LABELED) {
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) qlabel[n] = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.qlabels[n]);
+    }
 
     const long long nbatch = (a.n_rows + rpb - 1) / rpb;
     const long long wstride = (long long)gridDim.x * VG_WAVES_PER_BLOCK;
@@ -139,18 +162,40 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         if constexpr (MASKED) return vg_mask_bits(a.mask, batch * rpb, rpb, batch < nbatch);
         else return ~0ull;
     };
+    // LABELED: the label of this lane's row of a batch (unconditional load, only the address is selected: see vg_load_batch), and
+    // the batch's word - which lanes hold a row that carries the label of any query of the pass (0 behind the last batch)
+    auto label_of = [&](long long batch) -> uint32_t {
+        const long long r0 = batch * rpb + rib;
+        return a.labels[(batch < nbatch && r0 < a.n_rows) ? r0 : 0];
+    };
+    auto label_hits = [&](uint32_t lab, long long batch) -> uint64_t {
+        bool hit = false;
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) hit |= (lab == qlabel[n]);
+        return __ballot(hit && lab != VG_MQ_LABEL_NONE && batch < nbatch && batch * rpb + rib < a.n_rows);
+    };
     uint4 cur[U], nxt[U];
-    uint64_t mcur = mask_of(b);
-    uint64_t mnext = mask_of(b + wstride);
+    uint32_t lcur = 0u, lnext = 0u;
+    if constexpr (LABELED) { lcur = label_of(b); lnext = label_of(b + wstride); }
+    uint64_t mcur = LABELED ? label_hits(lcur, b) : mask_of(b);
+    uint64_t mnext = LABELED ? 0ull : mask_of(b + wstride);
     vg_load_batch<U, true>(cur, a.rows, b * rpb + rib, (b < nbatch && mcur != 0ull) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
     while (b < nbatch) {
         const long long bn = b + wstride;
-        const uint64_t mnxt = mnext;                                   // the bits of batch bn: asked for one step ago
-        mnext = mask_of(bn + wstride);
+        uint64_t mnxt = mnext;                                         // the bits of batch bn: asked for one step ago
+        const uint32_t lnxt = lnext;                                   // LABELED: and the labels of batch bn
+        if constexpr (LABELED) {
+            mnxt = label_hits(lnxt, bn);
+            lnext = label_of(bn + wstride);                            // (issued in front of the row prefetch below)
+        } else {
+            mnext = mask_of(bn + wstride);
+        }
         vg_load_batch<U, true>(nxt, a.rows, bn * rpb + rib, (bn < nbatch && mnxt != 0ull) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
         if (mcur != 0ull) {
             const long long row = b * rpb + rib;
-            const bool owner = (sub == 0) && (row < a.n_rows) && ((mcur >> rib) & 1ull);      // the row's lane, and the row is allowed
+            // the row's lane, and the row is allowed (LABELED: carries a label at all - which query's is the offer's business)
+            const bool owner = LABELED ? (sub == 0) && (row < a.n_rows) && (lcur != VG_MQ_LABEL_NONE)
+                                       : (sub == 0) && (row < a.n_rows) && ((mcur >> rib) & 1ull);
             // (WITHIN: every query's distance first, one ballot each; the rare batch with a match parks its keys BEHIND the arithmetic)
             float d[NQ];
             unsigned long long any = 0ull;
@@ -169,7 +214,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
                     // (a top-k form uses the distance at once, NOT through d[]: with it the ten f32 L1 floor instances came out with
                     //  another, equivalent, predicate sequence than the copies had)
                     const uint64_t key = vg_make_key(dn, (uint32_t)row);
-                    vg_list_offer(key, owner && (dn < INFINITY) && (!AFTER || key >= floor_key[n]), mine[n], thr[n], lane, k);
+                    if constexpr (LABELED) vg_list_offer(key, owner && (dn < INFINITY) && (lcur == qlabel[n]), mine[n], thr[n], lane, k);
+                    else vg_list_offer(key, owner && (dn < INFINITY) && (!AFTER || key >= floor_key[n]), mine[n], thr[n], lane, k);
                 }
             }
             if constexpr (WITHIN) if (any != 0ull) {
@@ -189,6 +235,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
 #pragma unroll
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
         mcur = mnxt;
+        if constexpr (LABELED) lcur = lnxt;
         b = bn;
     }
 #pragma unroll

@@ -1143,6 +1143,85 @@ extern "C" int vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const 
     return VG_OK;
 }
 
+// ---- labeled scans: the labels are given over GLOBAL scan positions and dealt out by the block-cyclic map of the rows, like the mask;
+// every shard runs vg_scan_topk_labeled[_batch] over its own rows and the lists merge like the masked scans'
+extern "C" int vg_shards_set_labels(vg_shards *s, const uint32_t *labels, int64_t n) {
+    if (!s) return fail(VG_ERR_INVALID, "shards handle is NULL");
+    if (s->S == 1) return vg_corpus_set_labels(s->sh[0], labels, n);
+    if (n != s->n_rows) return fail(VG_ERR_INVALID, "vg_shards_set_labels: the label count must equal the rows held");
+    if (n > 0 && !labels) return fail(VG_ERR_INVALID, "vg_shards_set_labels: labels is NULL");
+    std::vector<std::vector<uint32_t>> local((size_t)s->S);
+    for (int i = 0; i < s->S; ++i) local[(size_t)i].assign((size_t)vg_corpus_rows(s->sh[(size_t)i]), VG_LABEL_NONE);
+    for (int64_t g = 0; g < n; g += s->B) {                                    // block by block: one shard, consecutive local positions
+        int shard;
+        int64_t l0;
+        locate(s, g, &shard, &l0);
+        const int64_t len = std::min<int64_t>(s->B, n - g);
+        if (l0 + len > (int64_t)local[(size_t)shard].size()) return fail(VG_ERR_INVALID, "vg_shards_set_labels: the shards do not hold the rows of the map");
+        memcpy(local[(size_t)shard].data() + l0, labels + g, (size_t)len * sizeof(uint32_t));
+    }
+    for (int i = 0; i < s->S; ++i) {                   // a failure on the way leaves NO shard with labels
+        int rc = vg_corpus_set_labels(s->sh[(size_t)i], local[(size_t)i].data(), (int64_t)local[(size_t)i].size());
+        if (rc != VG_OK) {
+            const std::string msg = vg_last_error();
+            for (auto *c : s->sh) vg_corpus_clear_labels(c);
+            return fail(rc, msg.c_str());
+        }
+    }
+    return VG_OK;
+}
+
+extern "C" int vg_shards_clear_labels(vg_shards *s) {
+    if (!s) return fail(VG_ERR_INVALID, "shards handle is NULL");
+    for (auto *c : s->sh) { int rc = vg_corpus_clear_labels(c); if (rc != VG_OK) return rc; }
+    return VG_OK;
+}
+
+// 1 while every shard holds labels (an append drops the labels of the shards it reaches)
+extern "C" int vg_shards_has_labels(const vg_shards *s) {
+    if (!s) return 0;
+    for (auto *c : s->sh) if (!vg_corpus_has_labels(c)) return 0;
+    return 1;
+}
+
+extern "C" int vg_shards_scan_topk_labeled(vg_shards *s, int metric, const void *query, int k, uint32_t label, int64_t *out_rowids,
+                                           double *out_dist, int *out_count) {
+    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_labeled: NULL argument");
+    if (s->S == 1) return vg_scan_topk_labeled(s->sh[0], metric, query, k, label, out_rowids, out_dist, out_count);
+    *out_count = 0;
+    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_labeled: k must be at least 1");
+    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_labeled: k must be in 1..64 (labeled scans use the fused list only)");
+    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_labeled: NULL output");
+    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_labeled: no labels set");
+    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
+    std::vector<int> counts((size_t)s->S, 0);
+    int rc = for_each_shard(s, [&](int i) { return vg_scan_topk_labeled_keys(s->sh[(size_t)i], metric, query, k, label, &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]); });
+    if (rc != VG_OK) return rc;
+    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids, out_dist);
+    return VG_OK;
+}
+
+extern "C" int vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
+                                                 int64_t *out_rowids, double *out_dist, int *out_counts) {
+    if (!s || !queries || !out_counts || !query_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labeled: NULL argument");
+    if (s->S == 1) return vg_scan_topk_batch_labeled(s->sh[0], metric, queries, nq, query_labels, k, out_rowids, out_dist, out_counts);
+    if (nq < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labeled: nq must be at least 1");
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labeled: k must be at least 1");
+    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_batch_labeled: k must be in 1..64 (labeled scans use the fused list only)");
+    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labeled: NULL output");
+    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labeled: no labels set");
+    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
+    std::vector<int> counts((size_t)s->S * nq, 0);
+    int rc = for_each_shard(s, [&](int i) {
+        return vg_scan_topk_batch_labeled_keys(s->sh[(size_t)i], metric, queries, nq, query_labels, k, &keys[(size_t)i * nq * k], &counts[(size_t)i * nq]);
+    });
+    if (rc != VG_OK) return rc;
+    for (int q = 0; q < nq; ++q)
+        out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
+    return VG_OK;
+}
+
 // ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): a cursor over GLOBAL scan order becomes one floor key per shard over ITS
 // positions - the cursor's distance image with "local rows of this shard in front of global position P" (local_rows_before) - every
 // shard runs its floor form and the lists merge like the masked scans', by (distance image, global position)

@@ -75,6 +75,8 @@ enum { COL_TBL = 0, COL_VECTOR = 1, COL_K = 2, COL_MEMIDX = 3, COL_ID = 4, COL_D
 #include "vext_within_masked.inc"
 #include "vext_batch_within_masked.inc"
 #include "vext_after.inc"
+#include "vext_labeled.inc"
+#include "vext_batch_labeled.inc"
 
 /* ------------------------------------------------------------------------------------------------ registration */
 
@@ -211,5 +213,11 @@ int sqlite3_vector_init(sqlite3 *db, char **pzErrMsg, const sqlite3_api_routines
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_after", &quant_after_module, ctx);
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_filtered_after", &full_fafter_module, ctx);
     if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_filtered_after", &quant_fafter_module, ctx);
+    /* labeled scans: the k nearest rows whose label column equals a label, one query (vext_labeled.inc) or a batch with a label per
+     * query (vext_batch_labeled.inc) */
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_labeled", &full_labeled_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_labeled", &quant_labeled_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_labeled", &full_blabeled_module, ctx);
+    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_labeled", &quant_blabeled_module, ctx);
     return rc;
 }

@@ -84,6 +84,14 @@ typedef struct {
     int64_t host_data_version, host_changes, host_schema;
     int host_in_txn, host_off;                  /* host_off: tried and refused (limit, allocation, more rows than the bound) - until the stamps move */
     int host_sink;                              /* the staging loop's rows go to the host copy (vext_staging.inc: stage_rows_put) */
+    /* labeled scans (vext_labeled.inc), [0] the raw copy, [1] the quantized one: which label column this connection last set on the
+     * staged copy, on which handle, under which stamps (db_stamps; in_txn: read inside an open transaction - never reused), and the
+     * generation it left on a shared copy (another connection's set_labels moves it) */
+    char *lab_col[2];
+    vg_shards *lab_corpus[2];
+    int64_t lab_data_version[2], lab_changes[2], lab_schema[2];
+    int lab_in_txn[2];
+    uint64_t lab_gen[2];
 } table_ctx;
 
 typedef struct {
@@ -225,6 +233,8 @@ static void context_free(void *p) {
         sqlite3_free(c->tables[i].c_name);
         sqlite3_free(c->tables[i].pk_name);
         sqlite3_free(c->tables[i].touched);
+        sqlite3_free(c->tables[i].lab_col[0]);
+        sqlite3_free(c->tables[i].lab_col[1]);
     }
     sqlite3_free(c);
 }

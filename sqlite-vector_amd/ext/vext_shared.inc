@@ -31,6 +31,7 @@ typedef struct shared_corpus {
     pthread_mutex_t mu;                         /* one scan of this corpus at a time */
     int64_t table_rows, max_pk;                 /* the staging pass' watermark (vext_staging.inc) travels with the copy */
     int have_pk;
+    uint64_t label_gen;                         /* labeled scans (vext_labeled.inc): which set_labels the copy's labels are from (under mu) */
     struct shared_corpus *next;
 } shared_corpus;
 
