@@ -22,7 +22,8 @@
  *   - the JSON query vector is freed (the reference leaks it, :1771).
  *
  * Layout: this file holds the includes, the registration and the entry point; the rest lives in vext_*.inc by concern
- * (gpulib, context, tracking, sqlutil, convert, staging, quantize, tvf, batch, cursor, within, masked, batch_masked, batch_within, after).  The JSON and option-string parsers
+ * (gpulib, shared, context, tracking, sqlutil, convert, staging, quantize; then cursor and scanform - what every table-valued function
+ * shares - and the forms: tvf, batch, range, topk, labeled).  The JSON and option-string parsers
  * (vext_convert.inc / vext_sqlutil.inc) implement the reference's user-visible contract - what is accepted, every error
  * text - in this repository's own structure; a differential test against the reference extension pins that contract.
  */
@@ -65,18 +66,13 @@ enum { COL_TBL = 0, COL_VECTOR = 1, COL_K = 2, COL_MEMIDX = 3, COL_ID = 4, COL_D
 #include "vext_convert.inc"
 #include "vext_staging.inc"
 #include "vext_quantize.inc"
+#include "vext_cursor.inc"
+#include "vext_scanform.inc"
 #include "vext_tvf.inc"
 #include "vext_batch.inc"
-#include "vext_cursor.inc"
-#include "vext_within.inc"
-#include "vext_masked.inc"
-#include "vext_batch_masked.inc"
-#include "vext_batch_within.inc"
-#include "vext_within_masked.inc"
-#include "vext_batch_within_masked.inc"
-#include "vext_after.inc"
+#include "vext_range.inc"
+#include "vext_topk.inc"
 #include "vext_labeled.inc"
-#include "vext_batch_labeled.inc"
 
 /* ------------------------------------------------------------------------------------------------ registration */
 
@@ -183,41 +179,17 @@ int sqlite3_vector_init(sqlite3 *db, char **pzErrMsg, const sqlite3_api_routines
         rc = sqlite3_create_function(db, fns[i].name, fns[i].nargs, SQLITE_UTF8, ctx, fns[i].fn, NULL, NULL);
         if (rc != SQLITE_OK) return rc;
     }
-    rc = sqlite3_create_module(db, "vector_full_scan", &full_scan_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan", &quant_scan_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_stream", &full_stream_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_stream", &quant_stream_module, ctx);
-    /* additions over the reference's surface (batched queries) */
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch", &full_batch_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch", &quant_batch_module, ctx);
-    /* range scans: every row within a distance (vext_within.inc) */
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_within", &full_within_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_within", &quant_within_module, ctx);
-    /* masked scans: the k nearest rows among those a filter names (vext_masked.inc) */
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_filtered", &full_masked_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_filtered", &quant_masked_module, ctx);
-    /* ... for a whole batch of queries under one filter (vext_batch_masked.inc) */
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_filtered", &full_bmasked_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_filtered", &quant_bmasked_module, ctx);
-    /* range scans for a whole batch of queries, a radius each (vext_batch_within.inc) */
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_within", &full_bwithin_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_within", &quant_bwithin_module, ctx);
-    /* masked range scans: every row within a distance among those a filter names, one query (vext_within_masked.inc) or a batch
-     * (vext_batch_within_masked.inc) */
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_within_filtered", &full_wmasked_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_within_filtered", &quant_wmasked_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_within_filtered", &full_bwmasked_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_within_filtered", &quant_bwmasked_module, ctx);
-    /* paged scans: the next k rows behind a (distance, rowid) cursor, over all rows or those a filter names (vext_after.inc) */
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_after", &full_after_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_after", &quant_after_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_filtered_after", &full_fafter_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_filtered_after", &quant_fafter_module, ctx);
-    /* labeled scans: the k nearest rows whose label column equals a label, one query (vext_labeled.inc) or a batch with a label per
-     * query (vext_batch_labeled.inc) */
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_labeled", &full_labeled_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_labeled", &quant_labeled_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_full_scan_batch_labeled", &full_blabeled_module, ctx);
-    if (rc == SQLITE_OK) rc = sqlite3_create_module(db, "vector_quantize_scan_batch_labeled", &quant_blabeled_module, ctx);
+    /* the table-valued functions, a full and a quantized one per form: the reference's four (vext_tvf.inc), then the additions over its
+     * surface - batched queries (vext_batch.inc), range scans (vext_range.inc), filtered and paged top-k scans (vext_topk.inc),
+     * labeled scans (vext_labeled.inc) */
+#define FORM(stem, suffix) {"vector_full_scan" suffix, &full_##stem##_module}, {"vector_quantize_scan" suffix, &quant_##stem##_module}
+    static const struct { const char *name; const sqlite3_module *module; } modules[] = {
+        FORM(scan, ""), FORM(stream, "_stream"), FORM(batch, "_batch"),
+        FORM(within, "_within"), FORM(wmasked, "_within_filtered"), FORM(bwithin, "_batch_within"), FORM(bwmasked, "_batch_within_filtered"),
+        FORM(masked, "_filtered"), FORM(bmasked, "_batch_filtered"), FORM(after, "_after"), FORM(fafter, "_filtered_after"),
+        FORM(labeled, "_labeled"), FORM(blabeled, "_batch_labeled"),
+    };
+#undef FORM
+    for (size_t i = 0; rc == SQLITE_OK && i < sizeof(modules) / sizeof(modules[0]); ++i) rc = sqlite3_create_module(db, modules[i].name, modules[i].module, ctx);
     return rc;
 }

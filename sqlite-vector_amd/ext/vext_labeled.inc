@@ -1,75 +1,35 @@
 /* vext_labeled.inc - part of vector_ext.c (one translation unit: #include'd there, in order; every function is static).
- * labeled scans: vector_full_scan_labeled / vector_quantize_scan_labeled(table, column, vector, k, label_column, label) -> (id, distance),
- * the k nearest rows whose `label_column` equals `label`, ordered by (distance, scan position) - the equality filter on a metadata
- * column ("... of this tenant").  The question it answers is "... FROM vector_full_scan_stream(...) JOIN t ... WHERE t.label = ? ORDER
- * BY distance, id LIMIT k" without stepping N rows per call.
+ * labeled scans, ordered by (distance, scan position) -
+ *     vector_full_scan_labeled / vector_quantize_scan_labeled(table, column, vector, k, label_column, label)               -> (id, distance)
+ *     vector_full_scan_batch_labeled / vector_quantize_scan_batch_labeled(table, column, queries, k, label_column, labels) -> (query, id, distance)
+ * the k nearest rows whose `label_column` equals `label` - the equality filter on a metadata column ("... of this tenant").  The
+ * question it answers is "... FROM vector_full_scan_stream(...) JOIN t ... WHERE t.label = ? ORDER BY distance, id LIMIT k" without
+ * stepping N rows per call.  The batch form takes the batch functions' `queries` and `labels`, a BLOB of packed little-endian int64, one
+ * per query: each query's rows are what the single form returns for it and ITS label, and they come by query number (0-based) first;
+ * the engine orders the queries by label and offers a row only to the queries whose label it carries.
  * Label values are SQLite integers in 0 .. 2^32 - 2.  A NULL or non-integer cell is "no label" (the row matches no query); an integer
  * cell outside the range, or such a `label` argument, is an error naming the value.
  * The column is read once - SELECT rowid, "label_column" FROM "table" - mapped to scan positions through the engine's rowid lookup
- * (ascending rowids, as the filter forms need) and set on the staged copy inside the SAME hold of full_lock / quant_lock as the scan: a
- * copy may be shared between connections.  Later calls reuse the labels only while the engine still holds labels, they are this
+ * (ascending rowids, as the filter forms need) and set on the staged copy inside the SAME hold of the lock as the scan: a copy may be
+ * shared between connections.  Later calls reuse the labels only while the engine still holds labels, they are this
  * connection's labels of that same column on that same handle (a generation on a shared copy says so), and NOTHING has moved since
  * they were read: PRAGMA data_version, sqlite3_total_changes() and the schema version are what they were, and neither the read nor this
  * call sits inside an open transaction.  That is stricter than stage_full's own freshness (an UPDATE of the label column alone moves
  * total_changes; a tracked change or an append behind the staged rows does too) - correct before clever: in doubt the column is read again.
- * An out-of-core table answers through the slab path with k = 0, a host-side label compare and a sort: correct, not fast.
- * Staging, cursor, columns and index plan are the filtered functions' (vext_masked.inc, vext_within.inc).  labeled_label_value,
- * labeled_resolve, labeled_ensure and labeled_rowids_of are shared with the batch form (vext_batch_labeled.inc).
+ * An out-of-core table answers query by query through scan_ooc_query against the rowids that carry the query's label (each query reads
+ * column and table again): correct, not fast.
  */
 #define LABEL_MAX 0xFFFFFFFEll                  /* the largest label; 0xFFFFFFFF is VG_LABEL_NONE */
 
-enum { LCOL_TBL = 2, LCOL_LABEL = 7 };
+SCAN_CONNECT(labeled_connect, "CREATE TABLE x(id, distance, tbl hidden, col hidden, vector hidden, k hidden, label_column hidden, label hidden);")
+SCAN_CONNECT(blabeled_connect, "CREATE TABLE x(query, id, distance, tbl hidden, col hidden, queries hidden, k hidden, label_column hidden, labels hidden);")
 
-static int labeled_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
-    int rc = sqlite3_declare_vtab(db, "CREATE TABLE x(id, distance, tbl hidden, col hidden, vector hidden, k hidden, label_column hidden, label hidden);");
-    if (rc != SQLITE_OK) return rc;
-    scan_vtab *v = (scan_vtab *)sqlite3_malloc(sizeof(scan_vtab));
-    if (!v) return SQLITE_NOMEM;
-    memset(v, 0, sizeof(*v));
-    v->db = db;
-    v->ctx = (vec_context *)aux;
-    *out = &v->base;
-    return SQLITE_OK;
-}
-
-static int labeled_best_index(sqlite3_vtab *v, sqlite3_index_info *info) {
-    info->estimatedCost = 1.0;
-    info->estimatedRows = 100;
-    info->orderByConsumed = 1;                   /* output is distance-ascending, like the top-k functions */
-    info->idxNum = 1;
-    for (int i = 0; i < info->nConstraint; ++i) {
-        const struct sqlite3_index_constraint *c = &info->aConstraint[i];
-        if (!c->usable || c->op != SQLITE_INDEX_CONSTRAINT_EQ) continue;
-        if (c->iColumn >= LCOL_TBL && c->iColumn <= LCOL_LABEL) {
-            info->aConstraintUsage[i].argvIndex = c->iColumn - LCOL_TBL + 1;
-            info->aConstraintUsage[i].omit = 1;
-        }
-    }
-    return SQLITE_OK;
-}
-
-/* the engine's labeled entry points, resolved like the masked ones: an engine without them still loads, the functions then say so */
+/* the engine's labeled entry points */
 typedef int (*labeled_set_fn)(vg_shards *, const uint32_t *, int64_t);
 typedef int (*labeled_has_fn)(const vg_shards *);
 typedef int (*labeled_scan_fn)(vg_shards *, int, const void *, int, uint32_t, int64_t *, double *, int *);
 typedef int (*blabeled_scan_fn)(vg_shards *, int, const void *, int, const uint32_t *, int, int64_t *, double *, int *);
-typedef struct { labeled_set_fn set; labeled_has_fn has; labeled_scan_fn scan; blabeled_scan_fn scan_batch; } labeled_api;
-static const char *labeled_resolve(labeled_api *a, int batch) {
-    memset(a, 0, sizeof(*a));
-    if (!gpu_load()) return NULL;                /* (no engine at all: the staging step reports why) */
-    a->set = (labeled_set_fn)dlsym(G.handle, "vg_shards_set_labels");
-    if (!a->set) return "vg_shards_set_labels";
-    a->has = (labeled_has_fn)dlsym(G.handle, "vg_shards_has_labels");
-    if (!a->has) return "vg_shards_has_labels";
-    if (batch) {
-        a->scan_batch = (blabeled_scan_fn)dlsym(G.handle, "vg_shards_scan_topk_batch_labeled");
-        if (!a->scan_batch) return "vg_shards_scan_topk_batch_labeled";
-    } else {
-        a->scan = (labeled_scan_fn)dlsym(G.handle, "vg_shards_scan_topk_labeled");
-        if (!a->scan) return "vg_shards_scan_topk_labeled";
-    }
-    return NULL;
-}
+typedef struct { labeled_set_fn set; labeled_has_fn has; } labeled_api;
 
 /* a label given as an argument (or an element of the batch's BLOB): in range, or an error naming the value */
 static int labeled_label_value(scan_vtab *vt, const char *fname, int64_t v, uint32_t *out) {
@@ -130,11 +90,11 @@ fail:
     return rc;
 }
 
-/* the rowids of an out-of-core table whose label is `want`, sorted: what masked_ooc_topk filters against */
+/* the rowids of an out-of-core table whose label is `want`, sorted: what scan_ooc_query filters against */
 static int labeled_rowids_of(scan_vtab *vt, const char *fname, table_ctx *t, const char *label_col, uint32_t want, int64_t **out_ids, int64_t *out_n) {
     *out_ids = NULL; *out_n = 0;
     int rc = labeled_read_column(vt, fname, t, label_col, NULL, NULL, 0, want, out_ids, out_n);
-    if (rc == SQLITE_OK && *out_n > 1) qsort(*out_ids, (size_t)*out_n, sizeof(int64_t), masked_i64_cmp);
+    if (rc == SQLITE_OK && *out_n > 1) qsort(*out_ids, (size_t)*out_n, sizeof(int64_t), i64_cmp);
     return rc;
 }
 
@@ -168,122 +128,88 @@ static int labeled_ensure(scan_vtab *vt, const char *fname, table_ctx *t, int qu
     return SQLITE_OK;
 }
 
-static int labeled_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized) {
-    scan_cursor *c = (scan_cursor *)cur;
-    scan_vtab *vt = (scan_vtab *)cur->pVtab;
-    c->streaming = 0;
-    c->stream_pos = 0;
-    c->stream_n = 0;
-    if (argc != 6) return vtab_error(&vt->base, "%s expects %d arguments, but %d were provided.", fname, 6, argc);
-    for (int i = 0; i < argc; ++i) {
-        int t = sqlite3_value_type(argv[i]);
-        if ((i < 2 || i == 4) && t != SQLITE_TEXT) return vtab_error(&vt->base, "%s: argument %d must be of type TEXT (got %s).", fname, i + 1, sql_type_name(t));
-        if (i == 2 && t != SQLITE_TEXT && t != SQLITE_BLOB) return vtab_error(&vt->base, "%s: argument %d must be of type TEXT or BLOB (got %s).", fname, i + 1, sql_type_name(t));
-        if ((i == 3 || i == 5) && t != SQLITE_INTEGER) return vtab_error(&vt->base, "%s: argument %d must be of type INTEGER (got %s).", fname, i + 1, sql_type_name(t));
-    }
-    const char *tbl = (const char *)sqlite3_value_text(argv[0]);
-    const char *col = (const char *)sqlite3_value_text(argv[1]);
-    const char *label_col = (const char *)sqlite3_value_text(argv[4]);
-    table_ctx *t = context_lookup(vt->ctx, tbl, col);
-    if (!t) return vtab_error(&vt->base, "%s: unable to retrieve context.", fname);
-    uint32_t label = 0;
-    int rc = labeled_label_value(vt, fname, (int64_t)sqlite3_value_int64(argv[5]), &label);
+/* One xFilter for both forms: (table, column, vector | queries, k, label_column, label | labels) */
+static int labeled_filter_form(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized, int batch) {
+    static const arg_spec specs[2] = {{6, NULL, {ARG_TEXT, ARG_TEXT, ARG_VECTOR, ARG_INTEGER, ARG_TEXT, ARG_INTEGER}},
+                                      {6, NULL, {ARG_TEXT, ARG_TEXT, ARG_VECTOR, ARG_INTEGER, ARG_TEXT, ARG_ANY}}};
+    scan_call s;
+    scan_begin(&s, cur, fname, quantized, 0);
+    scan_vtab *vt = s.vt;
+    uint32_t *qlabels = NULL, label = 0;
+    int rc = scan_check_args(vt, fname, &specs[batch], argc, argv);
     if (rc != SQLITE_OK) return rc;
-
-    const void *query = NULL;
-    void *owned = NULL;
-    int qbytes = 0;
-    if (sqlite3_value_type(argv[2]) == SQLITE_TEXT) {
-        owned = vector_from_json(NULL, &vt->base, t->opt.v_type, (const char *)sqlite3_value_text(argv[2]), &qbytes, t->opt.v_dim);
-        if (!owned) return SQLITE_ERROR;
-        query = owned;
-    } else {
-        query = sqlite3_value_blob(argv[2]);
-        qbytes = sqlite3_value_bytes(argv[2]);
-        if (!query) return vtab_error(&vt->base, "%s: input vector cannot be NULL.", fname);
-    }
-    char *err = NULL;
-    uint8_t *qquant = NULL;
-    int64_t *ooc_ids = NULL;
-    if (qbytes < t->opt.v_dim * elem_size(t->opt.v_type)) {
-        rc = vtab_error(&vt->base, "%s: query vector has %d bytes, expected %d.", fname, qbytes, t->opt.v_dim * elem_size(t->opt.v_type));
-        goto out;
-    }
-    if (quantized) {
-        char name[SQL_BUF];
-        sqlite3_snprintf(sizeof(name), name, "vector0_%q_%q", tbl, col);
-        if (!exists_in_master(vt->db, "table", name)) {
-            rc = vtab_error(&vt->base, "Quantization table not found for table '%s' and column '%s'. Ensure that vector_quantize() has been called before using %s().", tbl, col, fname);
+    if (batch && sqlite3_value_type(argv[5]) != SQLITE_BLOB)
+        return vtab_error(&vt->base, "%s: argument %d must be a BLOB of packed 64-bit labels (got %s).", fname, 6, sql_type_name(sqlite3_value_type(argv[5])));
+    const char *label_col = (const char *)sqlite3_value_text(argv[4]);
+    if ((rc = scan_lookup(&s, argv)) != SQLITE_OK) goto out;
+    table_ctx *t = s.t;
+    /* (the single form's label is checked before its query is decoded) */
+    if (!batch && (rc = labeled_label_value(vt, fname, (int64_t)sqlite3_value_int64(argv[5]), &label)) != SQLITE_OK) goto out;
+    if ((rc = scan_open(&s, argv, batch, fname)) != SQLITE_OK) goto out;
+    if (batch) {
+        /* one label per query (copied: alignment, and the host's byte order), each checked before anything is staged */
+        const int lbytes = sqlite3_value_bytes(argv[5]);
+        const uint8_t *p = (const uint8_t *)sqlite3_value_blob(argv[5]);
+        if (lbytes % 8 || lbytes / 8 != s.nq) {
+            rc = vtab_error(&vt->base, "%s: the labels hold %d bytes, expected %d (one packed 64-bit label per query, %d queries).", fname, lbytes, s.nq * 8, s.nq);
             goto out;
         }
+        qlabels = (uint32_t *)sqlite3_malloc64((sqlite3_uint64)(s.nq > 0 ? s.nq : 1) * sizeof(uint32_t));
+        if (!qlabels) { rc = SQLITE_NOMEM; goto out; }
+        for (int i = 0; i < s.nq; ++i) {
+            uint64_t v = 0;
+            for (int b = 0; b < 8; ++b) v |= (uint64_t)p[i * 8 + b] << (8 * b);
+            if ((rc = labeled_label_value(vt, fname, (int64_t)v, &qlabels[i])) != SQLITE_OK) goto out;
+        }
     }
+    const uint32_t *labels = batch ? qlabels : &label;
     const int k = sqlite3_value_int(argv[3]);
-    if (k == 0) goto out;                                                                /* no rows, no device (decided here) */
+    if (k == 0 || s.nq == 0) goto out;                                                   /* no rows, no device (decided here) */
     if (k < 0) { rc = vtab_error(&vt->base, "%s: k must be positive.", fname); goto out; }
     if (k > 64) { rc = vtab_error(&vt->base, "%s: k must not exceed 64.", fname); goto out; }
 
-    labeled_api api;
-    const char *missing = labeled_resolve(&api, 0);
-    if (missing) { rc = vtab_error(&vt->base, "%s: the GPU engine lacks symbol %s (labeled scans need a newer libvectorgpu.so).", fname, missing); goto out; }
+    /* an engine without the entry points still loads, the functions then say so */
+    const char *const names[3] = {"vg_shards_set_labels", "vg_shards_has_labels", batch ? "vg_shards_scan_topk_batch_labeled" : "vg_shards_scan_topk_labeled"};
+    void *fn[3];
+    const char *missing = scan_resolve(&s, names, fn, 3);
+    if (missing) {
+        rc = batch ? vtab_error(&vt->base, "%s: the GPU engine lacks symbol %s (labeled batch scans need a newer libvectorgpu.so).", fname, missing)
+                   : vtab_error(&vt->base, "%s: the GPU engine lacks symbol %s (labeled scans need a newer libvectorgpu.so).", fname, missing);
+        goto out;
+    }
+    const labeled_api api = {(labeled_set_fn)fn[0], (labeled_has_fn)fn[1]};
+    if ((rc = scan_stage(&s)) != SQLITE_OK) goto out;
+    if ((rc = scan_topk_buffers(&s, k)) != SQLITE_OK) goto out;
 
-    vg_shards *corpus = NULL;
-    const void *scan_query = query;
-    if (quantized) {
-        if (!t->quant_preloaded || !t->quant) rc = stage_quant(vt->db, t, 0, &err);
-        if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "staging failed"); goto out; }
-        qquant = (uint8_t *)sqlite3_malloc(t->opt.v_dim);
-        if (!qquant) { rc = SQLITE_NOMEM; goto out; }
-        if (G.quantize_query(t->opt.v_type, query, t->opt.v_dim, t->scale, t->offset, t->opt.q_type, qquant) != VG_OK) {
+    if (s.ooc) {
+        for (int q = 0; q < s.nq; ++q) {
+            ooc_keep keep = {NULL, 1, NULL, 0, NULL, 0};
+            int64_t *lab_ids = NULL;
+            rc = labeled_rowids_of(vt, fname, t, label_col, labels[q], &lab_ids, &keep.n_ids);
+            keep.ids = lab_ids;
+            if (rc == SQLITE_OK) rc = scan_ooc_topk(&s, q, &keep, k);
+            sqlite3_free(lab_ids);
+            if (rc != SQLITE_OK) goto out;
+        }
+    } else {
+        /* the labels are state of the staged copy, which other connections may hold too: make sure of them and scan inside one hold of the lock */
+        scan_lock(&s);
+        if ((rc = labeled_ensure(vt, fname, t, quantized, s.corpus, &api, label_col)) != SQLITE_OK) goto out;
+        if ((batch ? ((blabeled_scan_fn)fn[2])(s.corpus, t->opt.v_distance, s.scan_queries, s.nq, labels, k, s.ids, s.dist, s.counts)
+                   : ((labeled_scan_fn)fn[2])(s.corpus, t->opt.v_distance, s.scan_queries, k, labels[0], s.ids, s.dist, s.counts)) != VG_OK) {
             rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error());
             goto out;
         }
-        scan_query = qquant;
-        corpus = t->quant;
-    } else {
-        rc = stage_full(vt->db, vt->ctx, t, &err);
-        if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "staging failed"); goto out; }
-        corpus = t->full;
+        scan_unlock(&s);
     }
-    if (!api.scan) { rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error()); goto out; }
-
-    sqlite3_free(c->rowids); c->rowids = NULL;
-    sqlite3_free(c->distance); c->distance = NULL;
-    c->rowids = (int64_t *)sqlite3_malloc64((sqlite3_uint64)k * sizeof(int64_t));
-    c->distance = (double *)sqlite3_malloc64((sqlite3_uint64)k * sizeof(double));
-    if (!c->rowids || !c->distance) { rc = SQLITE_NOMEM; goto out; }
-
-    if (quantized ? t->quant_ooc : t->full_ooc) {
-        /* the table does not fit the device: the rowids of the label from the column, then every distance through the slab path
-         * (k = 0), compared, sorted and cut on the host */
-        int64_t held = 0, n_ids = 0;
-        rc = labeled_rowids_of(vt, fname, t, label_col, label, &ooc_ids, &n_ids);
-        if (rc == SQLITE_OK) rc = masked_ooc_topk(vt, fname, t, quantized, scan_query, k, ooc_ids, n_ids, c->rowids, c->distance, &held);
-        if (rc == SQLITE_OK) c->stream_n = held;
-        goto out;
-    }
-
-    /* the labels are state of the staged copy, which other connections may hold too: make sure of them and scan inside one hold of the lock */
-    if (quantized) quant_lock(t); else full_lock(t);
-    {
-        int got = 0;
-        rc = labeled_ensure(vt, fname, t, quantized, corpus, &api, label_col);
-        if (rc == SQLITE_OK && api.scan(corpus, t->opt.v_distance, scan_query, k, label, c->rowids, c->distance, &got) != VG_OK)
-            rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error());
-        if (rc == SQLITE_OK) c->stream_n = got;
-    }
-    if (quantized) quant_unlock(t); else full_unlock(t);
+    rc = batch_emit(s.c, s.nq, k, s.ids, s.dist, s.counts);
 out:
-    sqlite3_free(err);
-    sqlite3_free(owned);
-    sqlite3_free(qquant);
-    sqlite3_free(ooc_ids);
-    return rc;
+    sqlite3_free(qlabels);
+    return scan_close(&s, rc);
 }
 
-static int full_labeled_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return labeled_filter_common(c, argc, argv, "vector_full_scan_labeled", 0); }
-static int quant_labeled_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return labeled_filter_common(c, argc, argv, "vector_quantize_scan_labeled", 1); }
+static int labeled_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized) { return labeled_filter_form(cur, argc, argv, fname, quantized, 0); }
+static int blabeled_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized) { return labeled_filter_form(cur, argc, argv, fname, quantized, 1); }
 
-static sqlite3_module full_labeled_module = {0, 0, labeled_connect, labeled_best_index, tvf_disconnect, 0, tvf_open, tvf_close, full_labeled_filter,
-                                             within_next, within_eof, within_column, within_rowid, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static sqlite3_module quant_labeled_module = {0, 0, labeled_connect, labeled_best_index, tvf_disconnect, 0, tvf_open, tvf_close, quant_labeled_filter,
-                                              within_next, within_eof, within_column, within_rowid, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+SCAN_FORM(labeled, "_labeled", labeled_filter_common, labeled_connect, single_best_index, within_next, within_eof, within_column, within_rowid);
+SCAN_FORM(blabeled, "_batch_labeled", blabeled_filter_common, blabeled_connect, btopk_best_index, tvf_next, tvf_eof, bmasked_column, tvf_rowid);

@@ -1,226 +1,81 @@
 /* vext_tvf.inc - part of vector_ext.c (one translation unit: #include'd there, in order; every function is static).
- * the four table-valued functions of the reference surface: argument checks, scan through the C-ABI, cursors
+ * the four table-valued functions of the reference surface: argument checks, scan through the C-ABI
  */
 /* ------------------------------------------------------------------------------------------------ table-valued functions */
 
-typedef struct {
-    sqlite3_vtab base;
-    sqlite3 *db;
-    vec_context *ctx;
-} scan_vtab;
+SCAN_CONNECT(tvf_connect, "CREATE TABLE x(tbl hidden, vector hidden, k hidden, memidx hidden, id, distance);")
 
-typedef struct {
-    sqlite3_vtab_cursor base;
-    int streaming;
-    /* materialised top-k */
-    int64_t *rowids;
-    double *distance;
-    int row_index, row_count;
-    int *query_no;                     /* batch TVFs: which query of the batch each output row answers */
-    /* streaming: all N distances computed by ONE kernel launch, paged out row by row */
-    float *all_dist;
-    int64_t *all_rowids;               /* the cursor's own snapshot: the corpus may be re-staged / destroyed while it is stepped */
-    int64_t stream_pos, stream_n;
-} scan_cursor;
-
-static int tvf_connect(sqlite3 *db, void *aux, int argc, const char *const *argv, sqlite3_vtab **out, char **err) {
-    int rc = sqlite3_declare_vtab(db, "CREATE TABLE x(tbl hidden, vector hidden, k hidden, memidx hidden, id, distance);");
-    if (rc != SQLITE_OK) return rc;
-    scan_vtab *v = (scan_vtab *)sqlite3_malloc(sizeof(scan_vtab));
-    if (!v) return SQLITE_NOMEM;
-    memset(v, 0, sizeof(*v));
-    v->db = db;
-    v->ctx = (vec_context *)aux;
-    *out = &v->base;
-    return SQLITE_OK;
-}
-
-static int tvf_disconnect(sqlite3_vtab *v) { sqlite3_free(v); return SQLITE_OK; }
-
-static void map_constraints(sqlite3_index_info *info) {
-    for (int i = 0; i < info->nConstraint; ++i) {
-        const struct sqlite3_index_constraint *c = &info->aConstraint[i];
-        if (!c->usable || c->op != SQLITE_INDEX_CONSTRAINT_EQ) continue;
-        if (c->iColumn >= COL_TBL && c->iColumn <= COL_MEMIDX) {
-            info->aConstraintUsage[i].argvIndex = c->iColumn + 1;
-            info->aConstraintUsage[i].omit = 1;
-        }
-    }
-}
-
-static int topk_best_index(sqlite3_vtab *v, sqlite3_index_info *info) {
-    info->estimatedCost = 1.0;
-    info->estimatedRows = 100;
-    info->orderByConsumed = 1;                   /* output is distance-ascending (sqlite-vector.c:1853) */
-    info->idxNum = 1;
-    map_constraints(info);
-    return SQLITE_OK;
-}
+static int topk_best_index(sqlite3_vtab *v, sqlite3_index_info *info) { return plan_single(info, 1, COL_TBL, COL_MEMIDX); }
 
 static int stream_best_index(sqlite3_vtab *v, sqlite3_index_info *info) {
     info->estimatedCost = 1e8;                   /* no ordering promise (sqlite-vector.c:2245-2275) */
     info->estimatedRows = 100000;
-    map_constraints(info);
-    return SQLITE_OK;
-}
-
-static int tvf_open(sqlite3_vtab *v, sqlite3_vtab_cursor **out) {
-    scan_cursor *c = (scan_cursor *)sqlite3_malloc(sizeof(scan_cursor));
-    if (!c) return SQLITE_NOMEM;
-    memset(c, 0, sizeof(*c));
-    *out = &c->base;
-    return SQLITE_OK;
-}
-
-static int tvf_close(sqlite3_vtab_cursor *cur) {
-    scan_cursor *c = (scan_cursor *)cur;
-    sqlite3_free(c->rowids);
-    sqlite3_free(c->distance);
-    sqlite3_free(c->all_dist);
-    sqlite3_free(c->all_rowids);
-    sqlite3_free(c->query_no);
-    sqlite3_free(c);
+    plan_args(info, COL_TBL, COL_MEMIDX);
     return SQLITE_OK;
 }
 
 /* the common xFilter (reference: vCursorFilterCommon, sqlite-vector.c:1723-1826) */
-static int filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int streaming, int quantized) {
-    scan_cursor *c = (scan_cursor *)cur;
-    scan_vtab *vt = (scan_vtab *)cur->pVtab;
-    c->streaming = streaming;
-    c->row_index = 0;
-    c->row_count = 0;
-    c->stream_pos = 0;
-    c->stream_n = 0;
-    const int nargs = streaming ? 3 : 4;
-    if (argc != nargs) return vtab_error(&vt->base, "%s expects %d arguments, but %d were provided.", fname, nargs, argc);
-    for (int i = 0; i < argc; ++i) {
-        int t = sqlite3_value_type(argv[i]);
-        if (i < 2 && t != SQLITE_TEXT) return vtab_error(&vt->base, "%s: argument %d must be of type TEXT (got %s).", fname, i + 1, sql_type_name(t));
-        if (i == 2 && t != SQLITE_TEXT && t != SQLITE_BLOB) return vtab_error(&vt->base, "%s: argument %d must be of type TEXT or BLOB (got %s).", fname, i + 1, sql_type_name(t));
-        if (i == 3 && t != SQLITE_INTEGER) return vtab_error(&vt->base, "%s: argument %d must be of type INTEGER (got %s).", fname, i + 1, sql_type_name(t));
-    }
-    const char *tbl = (const char *)sqlite3_value_text(argv[0]);
-    const char *col = (const char *)sqlite3_value_text(argv[1]);
-    table_ctx *t = context_lookup(vt->ctx, tbl, col);
-    if (!t) return vtab_error(&vt->base, "%s: unable to retrieve context.", fname);
-
-    const void *query = NULL;
-    void *owned = NULL;
-    int qbytes = 0;
-    if (sqlite3_value_type(argv[2]) == SQLITE_TEXT) {
-        owned = vector_from_json(NULL, &vt->base, t->opt.v_type, (const char *)sqlite3_value_text(argv[2]), &qbytes, t->opt.v_dim);
-        if (!owned) return SQLITE_ERROR;
-        query = owned;
-    } else {
-        query = sqlite3_value_blob(argv[2]);
-        qbytes = sqlite3_value_bytes(argv[2]);
-        if (!query) return vtab_error(&vt->base, "%s: input vector cannot be NULL.", fname);
-    }
-    int rc = SQLITE_OK;
-    char *err = NULL;
-    uint8_t *qquant = NULL;
-    if (qbytes < t->opt.v_dim * elem_size(t->opt.v_type)) {
-        /* the reference reads past a short query BLOB (:1774); refuse instead of faulting on the device */
-        rc = vtab_error(&vt->base, "%s: query vector has %d bytes, expected %d.", fname, qbytes, t->opt.v_dim * elem_size(t->opt.v_type));
-        goto out;
-    }
-    if (quantized) {
-        char name[SQL_BUF];
-        sqlite3_snprintf(sizeof(name), name, "vector0_%q_%q", tbl, col);
-        if (!exists_in_master(vt->db, "table", name)) {
-            rc = vtab_error(&vt->base, "Quantization table not found for table '%s' and column '%s'. Ensure that vector_quantize() has been called before using vector_quantize_scan().", tbl, col);
-            goto out;
-        }
-    }
+static int filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized, int streaming) {
+    static const arg_spec topk_args = {4, NULL, {ARG_TEXT, ARG_TEXT, ARG_VECTOR, ARG_INTEGER}}, stream_args = {3, NULL, {ARG_TEXT, ARG_TEXT, ARG_VECTOR}};
+    scan_call s;
+    scan_begin(&s, cur, fname, quantized, streaming);
+    scan_cursor *c = s.c;
+    scan_vtab *vt = s.vt;
+    int rc = scan_check_args(vt, fname, streaming ? &stream_args : &topk_args, argc, argv);
+    if (rc != SQLITE_OK) return rc;
+    if ((rc = scan_open(&s, argv, 0, "vector_quantize_scan")) != SQLITE_OK) goto out;     /* (the reference's text names this function whatever was called) */
+    table_ctx *t = s.t;
     int k = streaming ? 0 : sqlite3_value_int(argv[3]);
     if (!streaming && k == 0) { rc = SQLITE_DONE; goto out; }       /* sqlite-vector.c:1796 (ends the statement) */
     if (!streaming && k < 0) { rc = vtab_error(&vt->base, "%s: k must be positive.", fname); goto out; }
+    if ((rc = scan_stage(&s)) != SQLITE_OK) goto out;
 
-    /* the corpus to scan + the query in its element type */
-    vg_shards *corpus = NULL;
-    const void *scan_query = query;
-    if (quantized) {
-        if (!t->quant_preloaded || !t->quant) rc = stage_quant(vt->db, t, 0, &err);   /* not preloaded: stage on first use */
-        if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "staging failed"); goto out; }
-        qquant = (uint8_t *)sqlite3_malloc(t->opt.v_dim);
-        if (!qquant) { rc = SQLITE_NOMEM; goto out; }
-        /* the query is quantized with the stored scale/offset on every scan (sqlite-vector.c:2166-2177) */
-        if (G.quantize_query(t->opt.v_type, query, t->opt.v_dim, t->scale, t->offset, t->opt.q_type, qquant) != VG_OK) {
-            rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error());
-            goto out;
-        }
-        scan_query = qquant;
-        corpus = t->quant;
-    } else {
-        rc = stage_full(vt->db, vt->ctx, t, &err);
-        if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "staging failed"); goto out; }
-        corpus = t->full;
-    }
-
-    if (quantized ? t->quant_ooc : t->full_ooc) {
-        /* the table does not fit the device: this scan reads it again, slab by slab (vext_staging.inc: ooc_plan) */
-        int got = 0;
-        if (streaming) {
-            sqlite3_free(c->all_dist); c->all_dist = NULL;
-            sqlite3_free(c->all_rowids); c->all_rowids = NULL;
-            c->stream_n = 0;
-        } else {
-            sqlite3_free(c->rowids);
-            sqlite3_free(c->distance);
-            c->rowids = (int64_t *)sqlite3_malloc64((sqlite3_uint64)k * sizeof(int64_t));
-            c->distance = (double *)sqlite3_malloc64((sqlite3_uint64)k * sizeof(double));
-            if (!c->rowids || !c->distance) { rc = SQLITE_NOMEM; goto out; }
-        }
-        rc = quantized ? ooc_scan_quant(vt->db, t, scan_query, k, c->rowids, c->distance, &got, &c->all_dist, &c->all_rowids, &c->stream_n, &err)
-                       : ooc_scan_full(vt->db, t, scan_query, k, c->rowids, c->distance, &got, &c->all_dist, &c->all_rowids, &c->stream_n, &err);
-        if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, err ? err : "scan failed"); goto out; }
-        if (streaming) c->stream_pos = 0;
-        else c->row_count = got;
-        goto out;
-    }
-
-    /* a copy shared with other connections is scanned by one of them at a time (vext_shared.inc) */
-    if (quantized) quant_lock(t); else full_lock(t);
     if (streaming) {
-        int64_t n = G.corpus_rows(corpus);
-        sqlite3_free(c->all_dist);
-        sqlite3_free(c->all_rowids);
-        c->all_dist = (float *)sqlite3_malloc64((sqlite3_uint64)(n > 0 ? n : 1) * sizeof(float));
-        c->all_rowids = (int64_t *)sqlite3_malloc64((sqlite3_uint64)(n > 0 ? n : 1) * sizeof(int64_t));
-        if (!c->all_dist || !c->all_rowids) { rc = SQLITE_NOMEM; goto unlock; }
-        /* distances AND rowids are copied into the cursor here (the reference's stream cursor reads its own statement,
-         * sqlite-vector.c:2277-2313): later re-staging / vector_quantize / cleanup on the table cannot touch them */
-        if (n > 0 && (G.scan_distances(corpus, t->opt.v_distance, scan_query, c->all_dist) != VG_OK ||
-                      G.corpus_rowids(corpus, 0, n, c->all_rowids) != VG_OK)) {
-            rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error());
-            goto unlock;
-        }
-        c->stream_n = n;
-        c->stream_pos = 0;
+        sqlite3_free(c->all_dist); c->all_dist = NULL;
+        sqlite3_free(c->all_rowids); c->all_rowids = NULL;
     } else {
         sqlite3_free(c->rowids);
         sqlite3_free(c->distance);
         c->rowids = (int64_t *)sqlite3_malloc64((sqlite3_uint64)k * sizeof(int64_t));
         c->distance = (double *)sqlite3_malloc64((sqlite3_uint64)k * sizeof(double));
-        if (!c->rowids || !c->distance) { rc = SQLITE_NOMEM; goto unlock; }
-        int got = 0;
-        if (G.scan_topk(corpus, t->opt.v_distance, scan_query, k, c->rowids, c->distance, &got) != VG_OK) {
+        if (!c->rowids || !c->distance) { rc = SQLITE_NOMEM; goto out; }
+    }
+    int got = 0;
+    if (s.ooc) {
+        rc = quantized ? ooc_scan_quant(vt->db, t, s.scan_queries, k, c->rowids, c->distance, &got, &c->all_dist, &c->all_rowids, &c->stream_n, &s.err)
+                       : ooc_scan_full(vt->db, t, s.scan_queries, k, c->rowids, c->distance, &got, &c->all_dist, &c->all_rowids, &c->stream_n, &s.err);
+        if (rc != SQLITE_OK) { rc = vtab_error(&vt->base, "%s: %s", fname, s.err ? s.err : "scan failed"); goto out; }
+        if (!streaming) c->row_count = got;
+        goto out;
+    }
+
+    scan_lock(&s);
+    if (streaming) {
+        int64_t n = G.corpus_rows(s.corpus);
+        c->all_dist = (float *)sqlite3_malloc64((sqlite3_uint64)(n > 0 ? n : 1) * sizeof(float));
+        c->all_rowids = (int64_t *)sqlite3_malloc64((sqlite3_uint64)(n > 0 ? n : 1) * sizeof(int64_t));
+        if (!c->all_dist || !c->all_rowids) { rc = SQLITE_NOMEM; goto out; }
+        /* distances AND rowids are copied into the cursor here (the reference's stream cursor reads its own statement,
+         * sqlite-vector.c:2277-2313): later re-staging / vector_quantize / cleanup on the table cannot touch them */
+        if (n > 0 && (G.scan_distances(s.corpus, t->opt.v_distance, s.scan_queries, c->all_dist) != VG_OK ||
+                      G.corpus_rowids(s.corpus, 0, n, c->all_rowids) != VG_OK)) {
             rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error());
-            goto unlock;
+            goto out;
+        }
+        c->stream_n = n;
+    } else {
+        if (G.scan_topk(s.corpus, t->opt.v_distance, s.scan_queries, k, c->rowids, c->distance, &got) != VG_OK) {
+            rc = vtab_error(&vt->base, "%s: %s", fname, gpu_error());
+            goto out;
         }
         c->row_count = got;                       /* fewer than k when fewer rows qualify (:1816-1817) */
     }
-unlock:
-    if (quantized) quant_unlock(t); else full_unlock(t);
 out:
-    sqlite3_free(err);
-    sqlite3_free(owned);
-    sqlite3_free(qquant);
-    return rc;
+    return scan_close(&s, rc);
 }
 
-static int full_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return filter_common(c, argc, argv, "vector_full_scan", 0, 0); }
-static int quant_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return filter_common(c, argc, argv, "vector_quantize_scan", 0, 1); }
-static int full_stream_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return filter_common(c, argc, argv, "vector_full_scan_stream", 1, 0); }
-static int quant_stream_filter(sqlite3_vtab_cursor *c, int n, const char *s, int argc, sqlite3_value **argv) { return filter_common(c, argc, argv, "vector_quantize_scan_stream", 1, 1); }
+static int stream_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized) { return filter_common(cur, argc, argv, fname, quantized, 1); }
+static int topk_filter_common(sqlite3_vtab_cursor *cur, int argc, sqlite3_value **argv, const char *fname, int quantized) { return filter_common(cur, argc, argv, fname, quantized, 0); }
+
+SCAN_FORM(scan, "", topk_filter_common, tvf_connect, topk_best_index, tvf_next, tvf_eof, tvf_column, tvf_rowid);
+SCAN_FORM(stream, "_stream", stream_filter_common, tvf_connect, stream_best_index, tvf_next, tvf_eof, tvf_column, tvf_rowid);

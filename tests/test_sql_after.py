@@ -215,3 +215,35 @@ def test_two_connections_share_one_staged_copy(ext_path, tmp_path):
     assert not errors, errors[:3]
     for c in conns:
         c.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("quantized", [False, True])
+def test_out_of_core_table_gives_the_resident_pages(ext_path, quantized, monkeypatch):
+    """a table that does not fit the device answers through the slab route: three pages of 20 from the first page on are the first 60
+    rows of the ordered stream (of the filtered stream), and the very rows of the resident scan"""
+    n, dim = 3000, 64
+    rows = dg.corpus(dg.F32, n, dim, 51)
+    q = dg.query(dg.F32, dim, 52).tobytes()
+    kind = "quantize" if quantized else "full"
+    flt = "SELECT id FROM t WHERE tenant IN (3, 7)"
+
+    def run():
+        db = connect(ext_path)
+        load_table(db, rows, dg.F32, dg.L2)
+        if quantized:
+            db.execute("SELECT vector_quantize('t','v')")
+        out = (bits(_pages(db, "vector_%s_scan_after" % kind, q, 20, limit_pages=3)),
+               bits(_pages(db, "vector_%s_scan_filtered_after" % kind, q, 20, flt, limit_pages=3)),
+               bits(_stream(db, "vector_%s_scan_stream" % kind, q)[:60]),
+               bits(_stream(db, "vector_%s_scan_stream" % kind, q, flt)[:60]))
+        db.close()
+        return out
+
+    resident = run()
+    monkeypatch.setenv("VECTORGPU_HBM_LIMIT", "16K")
+    ooc = run()
+    assert len(resident[0]) == 60 and len(resident[1]) == 60
+    assert resident[0] == resident[2] and resident[1] == resident[3]
+    assert ooc[0] == ooc[2] and ooc[1] == ooc[3]
+    assert ooc == resident

@@ -179,3 +179,35 @@ def test_freshness_update_and_insert(ext_path, extra, quantized):
         assert got and all(r[0] % 4 == 1 for r in got)
         check(db, fns, q, labels=(3,), ks=(20,))
     db.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("quantized", [False, True])
+def test_out_of_core_table_gives_the_resident_rows(ext_path, quantized, monkeypatch):
+    """a table that does not fit the device answers through the slab route with a host-side label compare: the very rows of the resident
+    scan, single form and batch form (a label per query), and no row for a label nobody carries"""
+    n, dim, k = 3000, 64, 20
+    rows = dg.corpus(dg.F32, n, dim, 51)
+    qs = [dg.query(dg.F32, dim, 52 + i).tobytes() for i in range(3)]
+    fn, bfn, _ = PAIRS[1 if quantized else 0]
+
+    def run():
+        db = connect(ext_path)
+        db.execute("CREATE TABLE t (id INTEGER PRIMARY KEY, label, v BLOB)")
+        db.executemany("INSERT INTO t(id, label, v) VALUES (?, ?, ?)", [(j + 1, (j + 1) % 10, rows[j].tobytes()) for j in range(n)])
+        db.execute("SELECT vector_init('t', 'v', 'type=FLOAT32,dimension=%d,distance=L2')" % dim)
+        if quantized:
+            db.execute("SELECT vector_quantize('t','v')")
+        out = (bits(single(db, fn, qs[0], k, 3)), bits(single(db, fn, qs[0], k, 99)),
+               bits(db.execute("SELECT query, id, distance FROM %s('t','v',?,?,'label',?)" % bfn,
+                               (b"".join(qs), k, struct.pack("<3q", 7, 99, 2))).fetchall()))
+        db.close()
+        return out
+
+    resident = run()
+    monkeypatch.setenv("VECTORGPU_HBM_LIMIT", "16K")
+    ooc = run()
+    assert len(resident[0]) == k and all(r[0] % 10 == 3 for r in resident[0])
+    assert resident[1] == []                                         # the label nobody carries: exactly no rows
+    assert [(r[0], r[1] % 10) for r in resident[2]] == [(0, 7)] * k + [(2, 2)] * k
+    assert ooc == resident

@@ -183,3 +183,32 @@ def test_a_second_connection_shares_the_staged_copy_with_another_filter_in_betwe
             [r[1:] for r in want[1] if r[0] == 0]
     for c in conns:
         c.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("quantized", [False, True])
+def test_out_of_core_table_gives_the_resident_rows(ext_path, quantized, monkeypatch):
+    """a table that does not fit the device answers through the slab route, query by query: the very rows of the resident scan"""
+    n, dim, nq = 3000, 64, 3
+    rows = dg.corpus(dg.F32, n, dim, 51)
+    qs = np.ascontiguousarray(dg.corpus(dg.F32, nq, dim, 52))
+    fn = FUNCS[1 if quantized else 0]
+    flt = "SELECT id FROM t WHERE tenant IN (3, 7)"                 # 600 rows
+
+    def run():
+        db = connect(ext_path)
+        load_table(db, rows, dg.F32, dg.L2)
+        if quantized:
+            db.execute("SELECT vector_quantize('t','v')")
+        ids = [r[0] for r in db.execute(flt).fetchall()]
+        blob = struct.pack("<%dq" % len(ids), *ids)
+        out = [_batch(db, fn, qs.tobytes(), k, f) for k in (1, 20, 64) for f in (flt, blob)]
+        db.close()
+        return out
+
+    resident = run()
+    monkeypatch.setenv("VECTORGPU_HBM_LIMIT", "16K")
+    ooc = run()
+    assert [len(r) for r in resident] == [nq * k for k in (1, 20, 64) for _ in range(2)]
+    assert all(r[1] % 10 in (3, 7) for out in resident for r in out)
+    assert ooc == resident

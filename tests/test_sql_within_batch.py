@@ -201,3 +201,38 @@ def test_quantize_scan_batch_within_equals_the_single_within_scans(ext_path):
     db.execute("SELECT vector_quantize('t','v')")                             # (a uint8 table)
     _check(db, FUNCS[1], "vector_quantize_scan_within", qs)
     db.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("quantized", [False, True])
+def test_out_of_core_table_gives_the_resident_rows(ext_path, quantized, monkeypatch):
+    """a table that does not fit the device answers through the slab route, query by query: the very rows of the resident scan"""
+    n, dim, nq = 3000, 64, 3
+    rows = dg.corpus(dg.F32, n, dim, 51)
+    qs = np.ascontiguousarray(dg.corpus(dg.F32, nq, dim, 52))
+    fn = FUNCS[1 if quantized else 0]
+    stream = "vector_quantize_scan_stream" if quantized else "vector_full_scan_stream"
+
+    def run():
+        db = connect(ext_path)
+        db.execute("CREATE TABLE t (id INTEGER PRIMARY KEY, v BLOB)")
+        db.executemany("INSERT INTO t(id, v) VALUES (?, ?)", [(j + 1, rows[j].tobytes()) for j in range(n)])
+        db.execute("SELECT vector_init('t', 'v', 'type=FLOAT32,dimension=%d,distance=L2')" % dim)
+        if quantized:
+            db.execute("SELECT vector_quantize('t','v')")
+        radii = []
+        for i in range(nq):                               # a radius per query: its 10th, 25th, 40th smallest distance
+            d = np.sort(np.array([r[0] for r in db.execute("SELECT distance FROM %s('t','v',?)" % stream, (qs[i].tobytes(),)).fetchall()]))
+            radii.append(float(d[9 + 15 * i]))
+        arr = "[" + ", ".join(repr(r) for r in radii) + "]"
+        out = (_batch(db, fn, qs.tobytes(), arr), _batch(db, fn, qs.tobytes(), arr, 5))
+        db.close()
+        return out
+
+    resident = run()
+    monkeypatch.setenv("VECTORGPU_HBM_LIMIT", "16K")
+    ooc = run()
+    for q in range(nq):
+        assert sum(1 for r in resident[0] if r[0] == q) >= 10, q
+    assert [r[0] for r in resident[1]] == [0] * 5 + [1] * 5 + [2] * 5
+    assert ooc == resident
