@@ -119,16 +119,9 @@ extern "C" int vg_plan_scan_shape(int vtype, int dim, int metric, int *lanes_per
     return VG_OK;
 }
 
-// the plain kernels, one family per load policy (vg_pick.h)
-template <bool NT>
-struct PlainFamily {
-    static const bool has_long = true;
-    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, NT>; }
-    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, NT>; }
-};
-
+// the plain kernels (FORM 0), both load policies (vg_pick.h)
 static scan_fn_t pick_kernel(int vtype, int acc, const Shape &s, bool nt) {
-    return nt ? vg_pick_scan<PlainFamily<true>>(vtype, acc, s.U, s.long_rows) : vg_pick_scan<PlainFamily<false>>(vtype, acc, s.U, s.long_rows);
+    return nt ? vg_pick_scan<ScanFamily<0, true, true>>(vtype, acc, s.U, s.long_rows) : vg_pick_scan<ScanFamily<0, false, true>>(vtype, acc, s.U, s.long_rows);
 }
 
 // stream with non-temporal loads once the corpus cannot live in the 256 MiB Infinity Cache anyway

@@ -44,15 +44,15 @@ struct ScanArgs {
     unsigned long long *emit_reset;   // zeroed by this launch's first thread (the prefix pass resets the counter of the pass behind it)
     int order;                 // top-k mode: 0 = grid-stride batches (the whole chip sweeps one contiguous window), 1 = every workgroup owns a
                                //   contiguous run of batches, its 16 wavefronts striding inside it (one CU stays on one page for many iterations)
-    // ---- "within" mode (the WITHIN = true instantiations, vg_scan_within.hip): every row whose distance is <= within_r and finite is
+    // ---- "within" mode (the VG_SQ_WITHIN instances, vg_scan_within.hip): every row whose distance is <= within_r and finite is
     // appended as a key to `emit` = [count | within_cap keys]; the count keeps counting past the capacity (the host grows the buffer and
     // launches once more), the per-wavefront queues live at store_lds_off.  Fields the other kernels never read.
     float within_r;
     unsigned long long within_cap;
-    // ---- "masked" mode (the MASKED = true instantiations, vg_scan_masked.hip): bit (p & 63) of word (p >> 6) set = the row at scan
+    // ---- "masked" mode (the VG_SQ_MASKED instances, vg_scan_masked.hip): bit (p & 63) of word (p >> 6) set = the row at scan
     // position p may enter a list; ceil(n_rows / 64) words, bits behind the last row zero.  A field the other kernels never read.
     const uint64_t *mask;
-    // ---- "after" mode (the AFTER = true instantiations, vg_scan_after.hip, and the VG_MQ_AFTER forms of vg_scan_multi.h): a row enters a list only when its
+    // ---- "after" mode (the VG_SQ_AFTER instances, vg_scan_after.hip, and the VG_MQ_AFTER forms of vg_scan_multi.h): a row enters a list only when its
     // key is >= its query's floor - one key for the single kernels, NQ keys for a multi-query pass (VG_EMPTY_KEY in the pad slot of a
     // ragged pass: nothing is admitted).  Device memory.  A field the other kernels never read.
     const uint64_t *floor;

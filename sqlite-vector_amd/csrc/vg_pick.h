@@ -6,8 +6,8 @@
 //                    static const bool has_long;                                       rows no shape covers are served ...
 //                    template <int VT, int ACC> static scan_fn_t long_fn();            ... by this kernel (only when has_long)
 //     multi-query    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn();
-// The single-query families are defined by the units that hold them; the multi-query kernel has ONE family for all its forms,
-// MultiFamily<FORM> below (FORM: the VG_MQ_* flags of vg_scan_multi.h).
+// Each kernel has ONE family for all its forms: ScanFamily<FORM, NT, HAS_LONG> (FORM: the VG_SQ_* flags of vg_scan.h, NT: the load
+// policy) and MultiFamily<FORM> (FORM: the VG_MQ_* flags of vg_scan_multi.h) below.
 // A getter is instantiated only for the combinations a ladder names, and a kernel only where its getter is: the translation unit
 // that walks a ladder over a family holds that family's kernels, and exactly these -
 //     single-query   all five element types x L2 / cosine / dot / L1 x U in {1, 2, 3, 4, 6, 8}; A_COSN (cached row norms) for
@@ -20,6 +20,13 @@
 
 #include "vg_device.h"
 #include "vg_scan_multi.h"
+
+template <int FORM, bool NT, bool HAS_LONG>
+struct ScanFamily {
+    static const bool has_long = HAS_LONG;
+    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, NT, FORM>; }
+    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, NT, FORM>; }
+};
 
 template <int FORM>
 struct MultiFamily {

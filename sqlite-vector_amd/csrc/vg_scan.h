@@ -1,5 +1,34 @@
 // vg_scan.h - the brute-force scan kernel (single query): HBM-bound streaming read of the N x D corpus with a
-// fused wavefront-level top-k.  One template, instantiated per (element type, accumulation kind, U).
+// fused wavefront-level top-k.  One template, instantiated per (element type, accumulation kind, U, load policy, FORM).
+//
+// FORM is a set of flags (VG_SQ_*); each changes which rows are read or what happens to a distance, none how it is computed:
+//   (none)           top-k, k <= 64: one candidate list per wavefront, one published list per workgroup, vg_merge_kernel behind it.
+//                    Store mode (ScanArgs.out_dist set) is this form too - a runtime branch: every distance to HBM, no lists.
+//   VG_SQ_EX         what tie_order = reference needs (vg_reforder.hip) on top of the plain form: a start threshold from a pass
+//                    over the rows in front (init_keys), the candidate stream (emit) and "top-k + store" (out_dist != nullptr with
+//                    k > 0: the replay's prefix pass).  Instances of their own (vg_scan_ex.hip) because the plain kernels sit AT the
+//                    128-VGPR / 106-SGPR limit of 16 wavefronts per CU: the few registers the extras take spilled f32 U = 8 and
+//                    f16 U = 6, shapes the plain scans use.  Not combined with another flag; no long-row kernel.
+//   VG_SQ_WITHIN     range scan in place of the candidate list (vg_scan_within.hip): a row matches when d <= ScanArgs.within_r and d
+//                    is finite.  The keys of the matches are parked in a per-wavefront LDS queue and leave in bursts
+//                    (vg_within_offer / vg_within_flush below); the tail flushes the queue - no list, no publish.
+//   VG_SQ_MASKED     only the rows whose bit is set in ScanArgs.mask (vg_scan_masked.hip):
+//                      * the bits of a batch (vg_mask_bits: wave-uniform, one scalar load) are fetched ONE loop step ahead of the row
+//                        prefetch whose addresses they decide - `mnext` is asked for one step before the batch it describes is
+//                        prefetched and has a whole step (the current batch's arithmetic) to arrive;
+//                      * a batch without an allowed row points its U loads at vg_zero_chunk (one cache line, always a hit) and does
+//                        no arithmetic: a scalar branch around `process`;
+//                      * a row whose bit is clear was computed with its batch and is simply not offered.
+//                    In the ring form the row prefetch is NB - 1 batches ahead of the arithmetic, the mask fetch therefore NB: still
+//                    one scalar load in flight per wavefront, NB + 1 words of bits held (scalar registers).  Without the flag
+//                    every statement of the pipeline is discarded (if constexpr): nothing of it reaches the generated code.  With
+//                    VG_SQ_WITHIN: the masked range scan (vg_scan_within_masked.hip).
+//   VG_SQ_AFTER      paged scans (vg_scan_after.hip, with and without VG_SQ_MASKED): a row is offered only when its key is >=
+//                    ScanArgs.floor[0], the key just behind the caller's cursor.  One wave-uniform 64-bit value loaded before the
+//                    loop and one compare in the offer.  Not combined with VG_SQ_WITHIN: a range scan has no cursor.
+// The streaming loop was four hand-copied loops and the offer a ladder of seven branches; the code generated for every instance of
+// the two templates was checked identical to that of the copies it replaced (instruction text, registers, spills, scratch, LDS:
+// DESIGN.md 3.6) at the commit that folded them.
 //
 // Work decomposition (CDNA4):
 //   * a row is `nch` 16-byte chunks; LPR = 2^lpr_log2 lanes share a row, lane `sub` owns chunks sub + u*LPR
@@ -81,8 +110,10 @@ __device__ inline void vg_load_batch(uint4 (&dst)[U], const uint8_t *rows, long 
 #endif
 #define VG_STORE_FLOATS 1024          // store mode: distances parked in LDS per wavefront between bursts of stores
 
-// ---- "within" mode (WITHIN = true, instantiated in vg_scan_within.hip): the keys of the rows within the radius are parked in a
-// per-wavefront LDS queue and leave in bursts - one atomicAdd of the burst size by one lane, then coalesced 8-byte-per-lane stores.
+// the forms of vg_scan_kernel / vg_scan_long_kernel (the head of this file); the first three have the values of VG_MQ_*
+enum : int { VG_SQ_MASKED = 1, VG_SQ_AFTER = 2, VG_SQ_WITHIN = 4, VG_SQ_EX = 8 };
+
+// ---- VG_SQ_WITHIN: the keys of the rows within the radius are parked in a per-wavefront LDS queue and leave in bursts - one atomicAdd of the burst size by one lane, then coalesced 8-byte-per-lane stores.
 // A store (and the atomic's return) shares vmcnt with the batch prefetch, see the store-mode note in vg_scan_kernel: a burst of 64+
 // keys makes that drain rare, and a batch without a match - nearly every batch - costs one ballot.
 #define VG_WITHIN_QUEUE 128           // keys per wavefront: flushed once a further batch (<= 64 rows) might not fit
@@ -106,9 +137,7 @@ __device__ inline void vg_within_offer(uint64_t key, bool match, uint64_t *queue
     if (queued > VG_WITHIN_QUEUE - VG_WAVE) vg_within_flush(queue, queued, out, cap, lane);
 }
 
-// ---- "masked" mode (MASKED = true, instantiated in vg_scan_masked.hip): top-k among the rows whose bit is set in ScanArgs.mask.
-// WITHIN && MASKED (vg_scan_within_masked.hip): the masked loops with the within offer and the within tail - no list, no publish.
-// vg_mask_bits: the bits of the `n` rows from `row0` on (n a power of two <= 64 and row0 a multiple of it: adjacent bits of ONE word),
+// ---- VG_SQ_MASKED: the bits of the `n` rows from `row0` on (n a power of two <= 64 and row0 a multiple of it: adjacent bits of ONE word),
 // bit i = row0 + i, zero when the rows are out of range.  Every lane of the wavefront asks for the same rows, but the compiler cannot
 // know that of a value derived from threadIdx: the start row goes through readfirstlane (0xFFFFFFFF = out of range: a shard holds at
 // most 2^32 - 1 rows), and from there on index, word, shift and result are wave-uniform - one scalar load (s_load_dwordx2) per call on
@@ -121,15 +150,12 @@ __device__ inline uint64_t vg_mask_bits(const uint64_t *mask, long long row0, in
     return ok ? (bits & keep) : 0ull;
 }
 
-// EX = true: the variants tie_order = reference needs (vg_reforder.hip) - a start threshold from a pass over the rows in front
-// (init_keys), the candidate stream (emit) and "top-k + store" (out_dist != nullptr with k > 0: the replay's prefix pass).  They are
-// instantiations of their own (vg_scan_ex.hip) because the plain kernels sit AT the 128-VGPR / 106-SGPR limit of 16 wavefronts per
-// CU: the few registers the extras take spilled f32 U = 8 and f16 U = 6, shapes the plain scans use.
-// AFTER = true (vg_scan_after.hip, with MASKED false and true): paged scans - a row is offered only when its key is >= ScanArgs.floor[0],
-// the key just behind the caller's cursor.  One wave-uniform 64-bit value loaded before the loop and one compare in the offer; loops,
-// loads, arithmetic, lists, publish and merge are the plain / the masked kernel's.
-template <int VT, int ACC, int U, bool NT, bool EX = false, bool WITHIN = false, bool MASKED = false, bool AFTER = false>
+template <int VT, int ACC, int U, bool NT, int FORM = 0>      // FORM: VG_SQ_* flags
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
+    constexpr bool EX = (FORM & VG_SQ_EX) != 0, WITHIN = (FORM & VG_SQ_WITHIN) != 0, MASKED = (FORM & VG_SQ_MASKED) != 0;
+    constexpr bool AFTER = (FORM & VG_SQ_AFTER) != 0;
+    static_assert(!EX || FORM == VG_SQ_EX, "the reference-order extras are not combined with the range, masked or paged forms");
+    static_assert(!(WITHIN && AFTER), "a range scan has no cursor");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ VgListExtras ex;
     const int lane = threadIdx.x & (VG_WAVE - 1);
@@ -216,15 +242,15 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 #pragma unroll
     for (int j = 0; j < NB; ++j) nn[j] = 0.0f;
     // (masked mode: `live` = the batch has an allowed row; a batch without one points every load at vg_zero_chunk - no row is read)
-    auto load = [&](uint4 (&dst)[U], float &nn_dst, long long batch, bool live = true) {
+    auto load = [&](uint4 (&dst)[U], float &nn_dst, long long batch, bool live) {
         vg_load_batch<U, NT>(dst, a.rows, batch * rpb + rib, (batch < b_end && live) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
         // A_COSN: the row's squared norm rides along with the batch prefetch (one dword per row from the cached vector)
         // (unconditional for the same reason as the chunk loads: row 0's norm stands in, the row's result is never used)
         if constexpr (ACC == A_COSN) { const long long r0 = batch * rpb + rib; nn_dst = a.row_nn[(batch < b_end && live && r0 < a.n_rows) ? r0 : 0]; }
     };
-    // masked mode: the mask bits of a batch (wave-uniform; 0 behind the wavefront's last batch)
+    // MASKED: the mask bits of a batch (wave-uniform; 0 behind the wavefront's last batch)
     auto mask_of = [&](long long batch) -> uint64_t { return vg_mask_bits(a.mask, batch * rpb, rpb, batch < b_end); };
-    auto process = [&](uint4 (&cur)[U], float nn_cur, long long bcur, uint64_t mbits = 0ull) {
+    auto process = [&](uint4 (&cur)[U], float nn_cur, long long bcur, uint64_t mbits) {
         Accum<VT, ACC> acc;
         acc.init();
         if constexpr (VT == T_F16 || VT == T_BF16) {
@@ -251,107 +277,75 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
                                               reinterpret_cast<const uint16_t *>(a.rows + row * a.stride), a.dim, a.root);
         }
         d = vg_clamp(d);
-        if constexpr (WITHIN && MASKED) {
-            // masked range scan (vg_scan_within_masked.hip): the masked loops below, the within offer, and a row matches when its bit is set too
-            vg_within_offer(vg_make_key(d, (uint32_t)row), owner && ((mbits >> rib) & 1ull) && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
-        } else if constexpr (WITHIN) {
-            // d <= r is false for NaN; +Inf never matches, whatever the radius (the top-k contract: such rows never enter a list)
-            vg_within_offer(vg_make_key(d, (uint32_t)row), owner && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
-        } else if (store_mode) {
-            if (sub == 0) line[in_line * rpb + rib] = d;          // rows of consecutive batches are consecutive
-            if (++in_line == flush_every) {
-                // same wavefront wrote the lines: LDS ops are ordered, no barrier needed
-                if (line_row0 + VG_STORE_FLOATS <= a.n_rows) {
+        if constexpr (!WITHIN) {                                  // (a range scan has no store mode)
+            if (store_mode) {                                     // (stores share vmcnt with the prefetch: the note above the loop)
+                if (sub == 0) line[in_line * rpb + rib] = d;          // rows of consecutive batches are consecutive
+                if (++in_line == flush_every) {
+                    // same wavefront wrote the lines: LDS ops are ordered, no barrier needed
+                    if (line_row0 + VG_STORE_FLOATS <= a.n_rows) {
 #pragma unroll
-                    for (int j = 0; j < VG_STORE_FLOATS / (4 * VG_WAVE); ++j)
-                        reinterpret_cast<float4 *>(a.out_dist + line_row0)[j * VG_WAVE + lane] = reinterpret_cast<const float4 *>(line)[j * VG_WAVE + lane];
-                } else {
-                    for (int j = lane; j < VG_STORE_FLOATS && line_row0 + j < a.n_rows; j += VG_WAVE) a.out_dist[line_row0 + j] = line[j];
+                        for (int j = 0; j < VG_STORE_FLOATS / (4 * VG_WAVE); ++j)
+                            reinterpret_cast<float4 *>(a.out_dist + line_row0)[j * VG_WAVE + lane] = reinterpret_cast<const float4 *>(line)[j * VG_WAVE + lane];
+                    } else {
+                        for (int j = lane; j < VG_STORE_FLOATS && line_row0 + j < a.n_rows; j += VG_WAVE) a.out_dist[line_row0 + j] = line[j];
+                    }
+                    in_line = 0;
+                    line_row0 = (bcur + wstride) * rpb;
                 }
-                in_line = 0;
-                line_row0 = (bcur + wstride) * rpb;
+                return;
             }
-        } else if constexpr (AFTER && MASKED) {
-            const uint64_t key = vg_make_key(d, (uint32_t)row);
-            if constexpr (AFTER_LDS) floor_key = *reinterpret_cast<const volatile uint64_t *>(floor_lds);
-            vg_list_offer(key, owner && ((mbits >> rib) & 1ull) && (d < INFINITY) && (key >= floor_key), mine, thr, lane, k);
-        } else if constexpr (AFTER) {
-            const uint64_t key = vg_make_key(d, (uint32_t)row);
-            if constexpr (AFTER_LDS) floor_key = *reinterpret_cast<const volatile uint64_t *>(floor_lds);
-            vg_list_offer(key, owner && (d < INFINITY) && (key >= floor_key), mine, thr, lane, k);
-        } else if constexpr (MASKED) {
-            // a row whose bit is clear was computed with its batch and is simply not offered
-            vg_list_offer(vg_make_key(d, (uint32_t)row), owner && ((mbits >> rib) & 1ull) && (d < INFINITY), mine, thr, lane, k);
-        } else if constexpr (EX) {
-            if (store_too && owner) a.out_dist[row] = d;
-            vg_list_offer_ex(vg_make_key(d, (uint32_t)row), owner && (d < INFINITY), mine, thr, lane, k, &ex);
-        } else {
-            // NaN and +Inf never enter (strict '<' against INFINITY-initialised slots, sqlite-vector.c:1809,2102)
-            vg_list_offer(vg_make_key(d, (uint32_t)row), owner && (d < INFINITY), mine, thr, lane, k);
         }
+        // One key, one predicate, one offer.  NaN and +Inf never enter (strict '<' against INFINITY-initialised slots,
+        // sqlite-vector.c:1809,2102); WITHIN: d <= r is false for NaN, and +Inf never matches, whatever the radius (the top-k
+        // contract: such rows never enter a list); MASKED: a row whose bit is clear was computed with its batch and is simply
+        // not offered; AFTER: only keys from the floor on.
+        // (Two spellings of the chain, so that its LAST operand is a real term in every form: behind a compile-time `true` in that
+        //  place the compiler and-ed the same terms in another order than the copies had.)
+        if constexpr (EX) { if (store_too && owner) a.out_dist[row] = d; }
+        const uint64_t key = vg_make_key(d, (uint32_t)row);
+        if constexpr (AFTER_LDS) floor_key = *reinterpret_cast<const volatile uint64_t *>(floor_lds);
+        bool ok;
+        if constexpr (AFTER) ok = owner && (!MASKED || ((mbits >> rib) & 1ull)) && (d < INFINITY) && (key >= floor_key);
+        else ok = owner && (!MASKED || ((mbits >> rib) & 1ull)) && (!WITHIN || d <= a.within_r) && (d < INFINITY);
+        if constexpr (WITHIN) vg_within_offer(key, ok, wqueue, wqueued, a.emit, a.within_cap, lane);
+        else if constexpr (EX) vg_list_offer_ex(key, ok, mine, thr, lane, k, &ex);
+        else vg_list_offer(key, ok, mine, thr, lane, k);
     };
-    if constexpr (MASKED) {
-        // The mask fetch runs ONE step ahead of the row prefetch: the bits of a batch decide the ADDRESSES of its loads, so they must be
-        // in registers when those are issued - `mnext` is asked for one loop step before the batch it describes is prefetched and has a
-        // whole step (the current batch's arithmetic) to arrive.  mb[j] = the bits of the batch in buffer j.  In the ring form the row
-        // prefetch is NB - 1 batches ahead of the arithmetic, the mask fetch therefore NB: still one scalar load in flight per
-        // wavefront, NB + 1 words of bits held (scalar registers).  A batch without an allowed row costs its U loads of the zero chunk
-        // (one cache line, always a hit) and no arithmetic.  These two loops are the plain ring / double-buffer loops below with the
-        // mask threaded through; they are copies so that the plain instantiations stay byte-identical - keep the four in step by hand.
-        uint64_t mb[NB];
-        if constexpr (RING) {
+    // One ring loop and one double-buffer loop for every form.  mb[j] = the mask bits of the batch in buffer j, `mnext` those of the
+    // batch that is prefetched next (MASKED, see the head of this file).  Without the flag every batch is live and neither is ever
+    // written or read: the pipeline's statements are discarded, `!MASKED || ...` / `MASKED ? ... : ...` are constants to the front end.
+    // (They are spelled out at every use on purpose.  Routing them through a helper lambda, or evaluating mask_of()'s argument for a
+    // constant result, leaves the same instructions but in another order in some instances - DESIGN.md 3.6.)
+    uint64_t mb[NB], mnext;
+    if constexpr (RING) {
 #pragma unroll
-            for (int j = 0; j < NB - 1; ++j) { mb[j] = mask_of(b + j * wstride); load(buf[j], nn[j], b + j * wstride, mb[j] != 0ull); }
-            uint64_t mnext = mask_of(b + (NB - 1) * wstride);
-            while (b < b_end) {
-#pragma unroll
-                for (int j = 0; j < NB; ++j) {
-                    const long long bj = b + j * wstride;             // the batch in buffer j
-                    mb[(j + NB - 1) % NB] = mnext;
-                    mnext = mask_of(bj + NB * wstride);
-                    load(buf[(j + NB - 1) % NB], nn[(j + NB - 1) % NB], bj + (NB - 1) * wstride, mb[(j + NB - 1) % NB] != 0ull);
-                    if (mb[j] != 0ull) process(buf[j], nn[j], bj, mb[j]);       // (0 behind b_end)
-                }
-                b += NB * wstride;
-            }
-        } else {
-            mb[0] = mask_of(b);
-            uint64_t mnext = mask_of(b + wstride);
-            load(buf[0], nn[0], b, mb[0] != 0ull);
-            while (b < b_end) {
-                const long long bn = b + wstride;
-                mb[1] = mnext;
-                mnext = mask_of(bn + wstride);
-                load(buf[1], nn[1], bn, mb[1] != 0ull);
-                if (mb[0] != 0ull) process(buf[0], nn[0], b, mb[0]);
-#pragma unroll
-                for (int u = 0; u < U; ++u) buf[0][u] = buf[1][u];
-                nn[0] = nn[1];
-                mb[0] = mb[1];
-                b = bn;
-            }
+        for (int j = 0; j < NB - 1; ++j) {
+            if constexpr (MASKED) mb[j] = mask_of(b + j * wstride);
+            load(buf[j], nn[j], b + j * wstride, !MASKED || mb[j] != 0ull);
         }
-    } else if constexpr (RING) {
-#pragma unroll
-        for (int j = 0; j < NB - 1; ++j) load(buf[j], nn[j], b + j * wstride);
+        if constexpr (MASKED) mnext = mask_of(b + (NB - 1) * wstride);
         while (b < b_end) {
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 const long long bj = b + j * wstride;             // the batch in buffer j
-                load(buf[(j + NB - 1) % NB], nn[(j + NB - 1) % NB], bj + (NB - 1) * wstride);
-                if (bj < b_end) process(buf[j], nn[j], bj);
+                if constexpr (MASKED) { mb[(j + NB - 1) % NB] = mnext; mnext = mask_of(bj + NB * wstride); }
+                load(buf[(j + NB - 1) % NB], nn[(j + NB - 1) % NB], bj + (NB - 1) * wstride, !MASKED || mb[(j + NB - 1) % NB] != 0ull);
+                if (MASKED ? mb[j] != 0ull : bj < b_end) process(buf[j], nn[j], bj, MASKED ? mb[j] : 0ull);       // (the bits are 0 behind b_end)
             }
             b += NB * wstride;
         }
     } else {
-        load(buf[0], nn[0], b);
+        if constexpr (MASKED) { mb[0] = mask_of(b); mnext = mask_of(b + wstride); }
+        load(buf[0], nn[0], b, !MASKED || mb[0] != 0ull);
         while (b < b_end) {
             const long long bn = b + wstride;
-            load(buf[1], nn[1], bn);
-            process(buf[0], nn[0], b);
+            if constexpr (MASKED) { mb[1] = mnext; mnext = mask_of(bn + wstride); }
+            load(buf[1], nn[1], bn, !MASKED || mb[1] != 0ull);
+            if (!MASKED || mb[0] != 0ull) process(buf[0], nn[0], b, MASKED ? mb[0] : 0ull);
 #pragma unroll
             for (int u = 0; u < U; ++u) buf[0][u] = buf[1][u];
             nn[0] = nn[1];
+            if constexpr (MASKED) mb[0] = mb[1];
             b = bn;
         }
     }
@@ -374,8 +368,11 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 // the row is consumed in `S` slices of 64 x VG_LONG_U chunks with the accumulator carried across slices and the
 // query slice read from LDS (ds_read_b128) instead of living in VGPRs.  Same epilogue / top-k tail as above.
 #define VG_LONG_U 2
-template <int VT, int ACC, bool NT, bool WITHIN = false, bool MASKED = false, bool AFTER = false>
+template <int VT, int ACC, bool NT, int FORM = 0>             // FORM: VG_SQ_* flags, without VG_SQ_EX
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
+    constexpr bool WITHIN = (FORM & VG_SQ_WITHIN) != 0, MASKED = (FORM & VG_SQ_MASKED) != 0, AFTER = (FORM & VG_SQ_AFTER) != 0;
+    static_assert(!(FORM & VG_SQ_EX), "a long-row scan neither emits nor stores a prefix");
+    static_assert(!(WITHIN && AFTER), "a range scan has no cursor");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
     const int wave = threadIdx.x >> 6;
@@ -469,16 +466,17 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
                                                   reinterpret_cast<const uint16_t *>(a.rows + row * a.stride), a.dim, a.root);
             }
             d = vg_clamp(d);
-            if constexpr (WITHIN) {                                 // (WITHIN && MASKED: a row whose bit is clear never gets here)
-                vg_within_offer(vg_make_key(d, (uint32_t)row), (lane == 0) && (d <= a.within_r) && (d < INFINITY), wqueue, wqueued, a.emit, a.within_cap, lane);
-            } else if (store_mode) {
+            if (store_mode) {
                 if (lane == 0) a.out_dist[row] = d;
-            } else if constexpr (AFTER) {                           // (AFTER && MASKED: a row whose bit is clear never gets here)
+            } else {
+                // the predicate of vg_scan_kernel's offer (MASKED: a row whose bit is clear never gets here)
                 const uint64_t key = vg_make_key(d, (uint32_t)row);
                 if constexpr (AFTER_LDS) floor_key = *reinterpret_cast<const volatile uint64_t *>(floor_lds);
-                vg_list_offer(key, (lane == 0) && (d < INFINITY) && (key >= floor_key), mine, thr, lane, k);
-            } else {
-                vg_list_offer(vg_make_key(d, (uint32_t)row), (lane == 0) && (d < INFINITY), mine, thr, lane, k);
+                bool ok;
+                if constexpr (AFTER) ok = (lane == 0) && (d < INFINITY) && (key >= floor_key);
+                else ok = (lane == 0) && (!WITHIN || d <= a.within_r) && (d < INFINITY);
+                if constexpr (WITHIN) vg_within_offer(key, ok, wqueue, wqueued, a.emit, a.within_cap, lane);
+                else vg_list_offer(key, ok, mine, thr, lane, k);
             }
             acc.init();
         }

@@ -1,8 +1,8 @@
 // vg_scan_after.hip - paged scans: the next k rows behind a (distance, rowid) cursor (vg_scan_topk_after, include/vectorgpu.h).
 //
 // Every scan kernel ranks rows by one 64-bit key, sortable(distance) << 32 | scan position (vg_make_key), and the fused top-k result
-// is ascending in that key.  "The k rows behind a cursor" is therefore "the top-k among keys >= a floor": the kernels are the AFTER =
-// true instantiations of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h) with MASKED false (all rows) and true (the rows the handle's
+// is ascending in that key.  "The k rows behind a cursor" is therefore "the top-k among keys >= a floor": the kernels are the VG_SQ_AFTER
+// instances of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h) without VG_SQ_MASKED (all rows) and with it (the rows the handle's
 // mask allows) - the plain / the masked scan's loops, loads, arithmetic, lists and merge plus one wave-uniform 64-bit value and one
 // compare in the offer.  A translation unit of their own: every other kernel keeps its register budget.
 //
@@ -15,19 +15,10 @@
 
 #include <cfloat>
 
-struct AfterFamily {
-    static const bool has_long = true;
-    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, true, false, false, false, true>; }
-    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, true, false, false, true>; }
-};
-struct AfterMaskedFamily {
-    static const bool has_long = true;
-    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, true, false, false, true, true>; }
-    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, true, false, true, true>; }
-};
-
-scan_fn_t vg_pick_scan_after(int vtype, int acc, int U, bool long_rows) { return vg_pick_scan<AfterFamily>(vtype, acc, U, long_rows); }
-scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows) { return vg_pick_scan<AfterMaskedFamily>(vtype, acc, U, long_rows); }
+scan_fn_t vg_pick_scan_after(int vtype, int acc, int U, bool long_rows) { return vg_pick_scan<ScanFamily<VG_SQ_AFTER, true, true>>(vtype, acc, U, long_rows); }
+scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows) {
+    return vg_pick_scan<ScanFamily<VG_SQ_AFTER | VG_SQ_MASKED, true, true>>(vtype, acc, U, long_rows);
+}
 
 // ------------------------------------------------------------------------------------------------ the floor
 

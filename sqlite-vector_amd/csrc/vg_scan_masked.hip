@@ -1,8 +1,8 @@
 // vg_scan_masked.hip - masked scans: the k nearest rows among an allowed set (vg_scan_topk_masked, include/vectorgpu.h).
 //
 // The row mask is a bitmap over scan positions on the corpus handle (bit p & 63 of word p >> 6 = the row at position p may be returned;
-// bits behind the last row are zero), set once and read by any number of masked scans.  The kernels are the MASKED = true
-// instantiations of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h): the plain top-k scan's launch shape, loads, arithmetic, candidate
+// bits behind the last row are zero), set once and read by any number of masked scans.  The kernels are the VG_SQ_MASKED
+// instances of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h; ScanFamily, vg_pick.h): the plain top-k scan's launch shape, loads, arithmetic, candidate
 // lists and merge - plus one scalar load of mask bits per batch, fetched one step ahead of the row prefetch, so that a batch without an
 // allowed row reads no rows and a row whose bit is clear is never offered to a list.  A translation unit of their own, like
 // vg_scan_ex.hip and vg_scan_within.hip: the plain kernels keep their register budget.  One load policy (non-temporal).
@@ -15,12 +15,6 @@
 
 #include "vg_scan.h"
 #include "vg_pick.h"
-
-struct MaskedFamily {
-    static const bool has_long = true;
-    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, true, false, false, true>; }
-    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, true, false, true>; }
-};
 
 // ------------------------------------------------------------------------------------------------ the mask on the handle
 
@@ -150,7 +144,7 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
 }
 
 // the masked kernel table as a plain function: the fallback of the masked batch (vg_multi_masked.hip) names it in its form
-scan_fn_t vg_pick_scan_masked(int vtype, int acc, int U, bool long_rows) { return vg_pick_scan<MaskedFamily>(vtype, acc, U, long_rows); }
+scan_fn_t vg_pick_scan_masked(int vtype, int acc, int U, bool long_rows) { return vg_pick_scan<ScanFamily<VG_SQ_MASKED, true, true>>(vtype, acc, U, long_rows); }
 
 extern "C" int vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, int *out_count) {
     const VgFusedForm form = {"vg_scan_topk_masked", vg_pick_scan_masked, true, false};

@@ -1,6 +1,6 @@
 // vg_scan_within.hip - range scans: every row within a distance of the query (vg_scan_within, include/vectorgpu.h).
 //
-// The kernels are the WITHIN = true instantiations of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h): the plain scan's loads,
+// The kernels are the VG_SQ_WITHIN instances of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h; ScanFamily, vg_pick.h): the plain scan's loads,
 // arithmetic and summation order with a fixed threshold in place of the converging k-th best - compare, ballot, and only for the rare
 // batch with a match a key parked in the wavefront's LDS queue, flushed in bursts (vg_within_offer / vg_within_flush).  A translation
 // unit of their own, like vg_scan_ex.hip: the plain kernels keep their register budget.  One load policy (non-temporal).
@@ -18,12 +18,6 @@
 
 #include "vg_scan.h"
 #include "vg_pick.h"
-
-struct WithinFamily {
-    static const bool has_long = true;
-    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, true, false, true>; }
-    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, true, true>; }
-};
 
 // ------------------------------------------------------------------------------------------------ the result path
 
@@ -181,7 +175,7 @@ int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *q
 
 extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                               int64_t *out_held) {
-    const VgWithinForm form = {"vg_scan_within", vg_pick_scan<WithinFamily>, false};
+    const VgWithinForm form = {"vg_scan_within", vg_pick_scan<ScanFamily<VG_SQ_WITHIN, true, true>>, false};
     return vg_within_run(c, form, metric, query, radius, limit, out_matches, out_held);
 }
 

@@ -1,7 +1,7 @@
 // vg_scan_within_masked.hip - masked range scans: every ALLOWED row within a distance of the query (vg_scan_within_masked,
 // include/vectorgpu.h).
 //
-// The kernels are the WITHIN && MASKED instantiations of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h): the masked scan's loops -
+// The kernels are the VG_SQ_WITHIN | VG_SQ_MASKED instances of vg_scan_kernel / vg_scan_long_kernel (vg_scan.h): the masked pipeline -
 // the mask bits of a batch one step ahead of its row prefetch, the zero chunk and no arithmetic for a batch without an allowed row -
 // with the range scan's offer (a row matches when its bit is set, d <= r and d is finite) and the range scan's tail (flush the
 // wavefront's queue; no list, no publish).  A translation unit of their own: every other kernel keeps its register budget.
@@ -13,14 +13,8 @@
 #include "vg_scan.h"
 #include "vg_pick.h"
 
-struct WithinMaskedFamily {
-    static const bool has_long = true;
-    template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, true, false, true, true>; }
-    template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, true, true, true>; }
-};
-
 extern "C" int vg_scan_within_masked(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                                      int64_t *out_held) {
-    const VgWithinForm form = {"vg_scan_within_masked", vg_pick_scan<WithinMaskedFamily>, true};
+    const VgWithinForm form = {"vg_scan_within_masked", vg_pick_scan<ScanFamily<VG_SQ_WITHIN | VG_SQ_MASKED, true, true>>, true};
     return vg_within_run(c, form, metric, query, radius, limit, out_matches, out_held);
 }
