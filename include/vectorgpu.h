@@ -280,6 +280,37 @@ int     vg_scan_topk_batch_labeled(vg_corpus *c, int metric, const void *queries
 int     vg_scan_topk_batch_labeled_keys(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
                                         uint64_t *out_keys, int *out_counts);
 
+/* ---- grouped scans: the k nearest LABELS, each represented by its best row - rows are chunks, the label is the document (product,
+ * user) a chunk belongs to, the caller wants the k nearest documents (no reference entry point).  The labels are those of the labeled
+ * scans (vg_corpus_set_labels).  Contract:
+ *   take every row with a finite distance and a label other than VG_LABEL_NONE (the masked forms: whose mask bit is set as well);
+ *   1. order them by the 64-bit scan key, i.e. by (distance, scan position), whatever the handle's tie_order;
+ *   2. walk that order and keep the first row of each label;
+ *   3. return the first k rows kept - (rowid, distance, label), ascending by key.
+ * Fewer than k labels present: fewer results.  Every distance is the float vg_scan_distances reports for that row, bit for bit; NaN /
+ * +Inf rows never enter; a row without a label is never returned.  One pass over the rows: the label (4 bytes per row) rides with the
+ * row prefetch and the candidate lists stay distinct by label in the kernel, the workgroup merge and the final merge (all on the
+ * device, corpus stream); one copy brings back k keys and k labels.  A top-k with a host-side dedupe is NOT this: one label owning
+ * the 64 nearest rows hides every other label from it.
+ * 1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below); no labels set: VG_ERR_INVALID; the masked forms without a mask:
+ * VG_ERR_INVALID; NULL arguments: VG_ERR_INVALID; an empty corpus or an empty mask: *out_count = 0, nothing is launched.
+ * Not served: f16 corpora with rows of 2049 .. 3072 elements under the cosine and dot metrics (VG_ERR_UNSUPPORTED: the kernels of that
+ * shape do not fit the register file with a label per lane; L2 and L1 are served).
+ * The _keys forms return packed keys with positions local to this corpus (out_keys[k], out_labels[k]).
+ * vg_merge_keys_grouped (host): the label-deduping twin of vg_merge_keys for lists of several corpora, because one label can live on
+ * several of them - keys / labels are n_lists x list_len (ascending lists, VG_KEY_EMPTY padded), list i's positions are offset by
+ * pos_offsets[i] (NULL = 0); the three steps above over the union, by (distance, global position); out_keys carry the GLOBAL position
+ * (which must fit 32 bits: VG_ERR_UNSUPPORTED otherwise).  n_lists, list_len or k < 1, or a NULL argument: VG_ERR_INVALID. */
+int     vg_scan_topk_grouped(vg_corpus *c, int metric, const void *query, int k,
+                             int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_grouped_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_grouped_masked(vg_corpus *c, int metric, const void *query, int k,
+                                    int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_grouped_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, uint32_t *out_labels,
+                                         int *out_count);
+int     vg_merge_keys_grouped(const uint64_t *keys, const uint32_t *labels, int n_lists, int list_len, const int64_t *pos_offsets, int k,
+                              uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+
 /* ---- masked range scans: every ALLOWED row within a distance of the query - "every row of this tenant within r", near-duplicate
  * detection inside one category (no reference entry point; the reference's form is "SELECT ... FROM vector_full_scan_stream(...)
  * WHERE id IN (...) AND distance <= r": N rows stepped).  The contract is the conjunction of vg_scan_within's and vg_scan_topk_masked's.
@@ -452,6 +483,13 @@ int     vg_shards_scan_topk_labeled(vg_shards *s, int metric, const void *query,
                                     int64_t *out_rowids, double *out_dist, int *out_count);
 int     vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
                                           int64_t *out_rowids, double *out_dist, int *out_counts);
+/* the grouped scans over every shard: each shard answers over its own rows (its k nearest labels), the lists merge through
+ * vg_merge_keys_grouped by (distance, GLOBAL scan position) - a label's rows may sit on several shards: the rowids, labels, order and
+ * distance bits of one corpus holding all rows.  Same contract; at most 2^32 - 1 rows over all shards. */
+int     vg_shards_scan_topk_grouped(vg_shards *s, int metric, const void *query, int k,
+                                    int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_shards_scan_topk_grouped_masked(vg_shards *s, int metric, const void *query, int k,
+                                           int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
 /* the masked range scans over every shard: each shard answers over its own bits (a shard whose share of the mask is empty launches
  * nothing and contributes nothing), merged like vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus
  * holding all rows.  Same contract; the results are read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and

@@ -211,6 +211,14 @@ def _load():
         "vg_shards_has_labels": (i32, [vp]),
         "vg_shards_scan_topk_labeled": (i32, [vp, i32, vp, i32, C.c_uint32, vp, vp, C.POINTER(i32)]),
         "vg_shards_scan_topk_batch_labeled": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp]),
+        # grouped scans: the k nearest labels, each by its best row
+        "vg_scan_topk_grouped": (i32, [vp, i32, vp, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_grouped_keys": (i32, [vp, i32, vp, i32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_grouped_masked": (i32, [vp, i32, vp, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_grouped_masked_keys": (i32, [vp, i32, vp, i32, vp, vp, C.POINTER(i32)]),
+        "vg_merge_keys_grouped": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, C.POINTER(i32)]),
+        "vg_shards_scan_topk_grouped": (i32, [vp, i32, vp, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_shards_scan_topk_grouped_masked": (i32, [vp, i32, vp, i32, vp, vp, vp, C.POINTER(i32)]),
         "vg_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
         "vg_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
         "vg_scan_within_batch_keys": (i32, [vp, i32, i64, i64, vp]),
@@ -346,6 +354,36 @@ class _LabeledOps:
         cnt = np.zeros(max(nq, 1), dtype=np.int32)
         _check(getattr(lib(), self._sprefix + "scan_topk_batch_labeled")(self.h, metric, _ptr(queries), nq, _ptr(lab), k, _ptr(ids), _ptr(dist), _ptr(cnt)))
         return ids, dist, cnt[:nq]
+
+
+class _GroupedOps:
+    """the grouped scans, shared by Corpus and Shards (`_sprefix`: vg_ / vg_shards_): the k nearest labels (set_labels), each represented
+    by its best row; ascending (distance, scan position) order"""
+
+    def scan_topk_grouped(self, metric, query, k, masked=False):
+        """order the labeled rows with a finite distance (masked: whose mask bit is set) by (distance, scan position), keep the first row
+        of each label, return the first k kept: (rowids, distances, labels); fewer than k labels present give fewer results"""
+        query = np.ascontiguousarray(query)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        lab = np.zeros(max(k, 1), dtype=np.uint32)
+        cnt = C.c_int(0)
+        fn = getattr(lib(), self._sprefix + "scan_topk_grouped" + ("_masked" if masked else ""))
+        _check(fn(self.h, metric, _ptr(query), k, _ptr(ids), _ptr(dist), _ptr(lab), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value], lab[:cnt.value]
+
+
+def merge_keys_grouped(keys, labels, pos_offsets, k):
+    """vg_merge_keys_grouped: keys / labels [n_lists, list_len] -> (keys with global positions, labels), one row per label - host only"""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    n_lists, list_len = keys.shape
+    off = None if pos_offsets is None else np.ascontiguousarray(pos_offsets, dtype=np.int64)
+    out_keys = np.zeros(max(k, 1), dtype=np.uint64)
+    out_lab = np.zeros(max(k, 1), dtype=np.uint32)
+    cnt = C.c_int(0)
+    _check(lib().vg_merge_keys_grouped(_ptr(keys), _ptr(labels), n_lists, list_len, _ptr(off), k, _ptr(out_keys), _ptr(out_lab), C.byref(cnt)))
+    return out_keys[:cnt.value], out_lab[:cnt.value]
 
 
 AFTER_START = (float("-inf"), -(1 << 63))          # the cursor in front of every row
@@ -517,7 +555,7 @@ def _set_mask(obj, prefix, rows, bits, positions, rowids):
     return int(getattr(L, prefix + "_mask_count")(obj.h))
 
 
-class Corpus(_PagedScans, _LabeledOps):
+class Corpus(_PagedScans, _LabeledOps, _GroupedOps):
     """One HBM-resident corpus shard (opaque vg_corpus handle)."""
     _lprefix, _sprefix = "vg_corpus", "vg_"
 
@@ -837,7 +875,7 @@ def device_memory(device=0):
     return f.value, t.value
 
 
-class Shards(_PagedScans, _LabeledOps):
+class Shards(_PagedScans, _LabeledOps, _GroupedOps):
     """One logical corpus dealt block-cyclically over several devices of this process (opaque vg_shards handle)."""
     _lprefix, _sprefix = "vg_shards", "vg_shards_"
 

@@ -155,8 +155,8 @@ extern "C" int vg_corpus_create(int device, int vtype, int dim, int64_t capacity
         (e = hipMalloc(&c->d_query, (size_t)c->stride + 16)) != hipSuccess ||      // (+ 16: a paged scan's floor key rides behind the query)
         (e = hipHostMalloc(&c->h_query, (size_t)c->stride + 16)) != hipSuccess ||
         (e = hipMalloc(&c->d_cand, (size_t)c->max_blocks * VG_WAVE * sizeof(uint64_t))) != hipSuccess ||
-        (e = hipMalloc(&c->d_keys, VG_WAVE * sizeof(uint64_t))) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_keys, VG_WAVE * sizeof(uint64_t))) != hipSuccess) {
+        (e = hipMalloc(&c->d_keys, VG_KEYS_BYTES)) != hipSuccess ||
+        (e = hipHostMalloc(&c->h_keys, VG_KEYS_BYTES)) != hipSuccess) {
         vg_corpus_destroy(c);
         return vg_fail(VG_ERR_HIP, "vg_corpus_create: device setup failed: %s", hipGetErrorString(e));
     }

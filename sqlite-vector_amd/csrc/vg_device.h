@@ -134,6 +134,46 @@ __device__ inline void vg_list_offer(uint64_t key, bool valid, uint64_t &mine, u
         if (c < thr) vg_list_insert(mine, thr, c, lane, k);
     }
 }
+// ---- the grouped list (VG_SQ_GROUPED, vg_scan_grouped.hip): the same sorted one-key-per-lane layout plus one label register per
+// lane, and never two entries of one label.  Invariants: all 64 lanes are distinct by label (an empty lane holds VG_EMPTY_KEY and the
+// label 0xFFFFFFFF, which no candidate carries: the callers never offer an unlabeled row), thr is the key in slot k-1, thr never rises.
+// An accepted candidate (c, cl) meets at most ONE entry of its label (one ballot):
+//   * that entry's key is <= c: the candidate is dropped - the group is already represented by a better row;
+//   * it sits at lane j with a larger key: c is inserted at its place p <= j (lane j holds a key > c, so the first lane that does is
+//     at or below j), ONLY lanes p..j move up by one and the old entry at j is overwritten - no other group loses its slot;
+//   * there is none: j = 64, the ordinary insert (every lane from p on moves up, the last one falls off).
+// Slot k-1 afterwards holds its old key, the key of slot k-2 or c - never a larger one.
+// Exact: in any subset of the rows every group's best key is >= its best key over all rows, so the subset's k-th best group key is >=
+// the global one - a row that represents one of the k best groups overall is below every partial list's thr and is never dropped for
+// a row of another group; within its group only a better row replaces it.
+__device__ inline uint32_t vg_wave_shr1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }
+__device__ inline void vg_list_insert_grouped(uint64_t &mine, uint32_t &mlab, uint64_t &thr, uint64_t c, uint32_t cl, int lane, int k) {
+    const unsigned long long same = __ballot(mlab == cl);            // at most one bit
+    int j = VG_WAVE;
+    if (same) {
+        j = __ffsll((long long)same) - 1;
+        if (vg_readlane64(mine, j) <= c) return;                     // (wave-uniform: c, j and the key read are)
+    }
+    const uint64_t prev = vg_wave_shr1(mine);                        // lane 0 sees 0, which is never > c
+    const uint32_t plab = vg_wave_shr1(mlab);
+    const bool move = (mine > c) && (lane <= j);
+    const bool pgt = prev > c;
+    mine = move ? (pgt ? prev : c) : mine;
+    mlab = move ? (pgt ? plab : cl) : mlab;
+    thr = vg_readlane64(mine, k - 1);
+}
+// Offer one candidate per lane (valid lanes only; a valid lane's label is never 0xFFFFFFFF).  The entry test is vg_list_offer's: one
+// ballot per call once thr has tightened.
+__device__ inline void vg_list_offer_grouped(uint64_t key, uint32_t label, bool valid, uint64_t &mine, uint32_t &mlab, uint64_t &thr, int lane, int k) {
+    unsigned long long m = __ballot(valid && key < thr);
+    while (m) {
+        int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        uint64_t c = vg_readlane64(key, src);
+        uint32_t cl = (uint32_t)__builtin_amdgcn_readlane((int)label, src);
+        if (c < thr) vg_list_insert_grouped(mine, mlab, thr, c, cl, lane, k);
+    }
+}
 // The same with a start threshold and the reference-order candidate stream (vg_reforder.hip).  The three values involved are
 // needed only when a list accepts a key - about once per wavefront and scan - so they live in LDS, not in the scalar registers the
 // streaming loop is short of (every scan kernel sits at the 106-SGPR limit; holding them there spilled SGPRs into VGPR lanes).

@@ -24,6 +24,7 @@
 #define VG_EVF_MERGE 1            // ev_flags bits: the launch had a merge kernel / a pre-pass of its own
 #define VG_EVF_PREPASS 2
 #define VG_WAVE_HOST 64
+#define VG_KEYS_BYTES (VG_WAVE_HOST * (sizeof(uint64_t) + sizeof(uint32_t)))   // d_keys / h_keys: 64 keys, then (grouped scans) their 64 labels
 
 int vg_fail(int code, const char *fmt, ...);         // sets the thread-local message, returns code (vg_corpus.hip)
 
@@ -64,8 +65,8 @@ struct vg_corpus {
     uint8_t *h_query = nullptr;    // pinned
     uint64_t *d_cand = nullptr;    // max_blocks * 64 keys
     uint64_t *d_cand_pre = nullptr; // the same size: a filter scan's pre-pass lists, read unmerged by the filter kernel
-    uint64_t *d_keys = nullptr;    // 64 keys
-    uint64_t *h_keys = nullptr;    // pinned, 64 keys
+    uint64_t *d_keys = nullptr;    // 64 keys (+ 64 labels behind them: VG_KEYS_BYTES)
+    uint64_t *h_keys = nullptr;    // pinned, the same
     float *d_dist = nullptr;       // lazily sized to n_rows (stream scans / large k / tie_order = reference)
     int64_t d_dist_cap = 0;
     int64_t dist_valid_rows = 0;   // rows of d_dist the last vg_scan_distances_resident filled (0: none)
@@ -317,9 +318,15 @@ scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows); 
 // c->d_label_bits - the caller enqueued vg_label_bits_enqueue in front - and requires labels, not a mask; the batch form sets
 // ScanArgs.labels / .qlabels, `qlabels` = a label per query (the caller hands the queries over ordered by label: the fallback
 // builds one bitmap per run of equal labels).
-struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; };
+// `grouped` (the grouped scans, vg_scan_grouped.hip): ScanArgs.labels is set and labels are required, the lists of the workgroups go
+// through vg_launch_merge_grouped instead of the rank-select merge, and vg_fused_run also yields the winners' labels (out_labels).
+struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; bool grouped; };
 struct VgFusedBatchForm { const char *who; vg_pick_multi_fn_t pick; VgFusedForm single; };
-int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count);
+int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count,
+                 uint32_t *out_labels = nullptr);
+// vg_scan_grouped.hip: the label-deduping final merge of `nlists` <= 256 per-workgroup lists (keys only; a key's label is
+// labels[position]) on `stream`: dev_out receives 64 keys (VG_EMPTY_KEY padded) followed by their 64 labels - VG_KEYS_BYTES in all
+int vg_launch_merge_grouped(const uint64_t *dev_cand, int nlists, int k, const uint32_t *dev_labels, uint64_t *dev_out, hipStream_t stream);
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                        uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr);
 // ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): the floor-key forms behind the C ABI, what the shards call per shard.

@@ -26,6 +26,13 @@
 //   VG_SQ_AFTER      paged scans (vg_scan_after.hip, with and without VG_SQ_MASKED): a row is offered only when its key is >=
 //                    ScanArgs.floor[0], the key just behind the caller's cursor.  One wave-uniform 64-bit value loaded before the
 //                    loop and one compare in the offer.  Not combined with VG_SQ_WITHIN: a range scan has no cursor.
+//   VG_SQ_GROUPED    grouped scans (vg_scan_grouped.hip, with and without VG_SQ_MASKED): the k nearest LABELS, each by its best row.  The
+//                    row's label (ScanArgs.labels, one dword) rides with the batch prefetch exactly like A_COSN's row norm - issued with
+//                    the row's chunk loads, unconditional, nothing loaded between batches - and the candidate list stays distinct by
+//                    label (vg_list_offer_grouped, vg_device.h: one more register per lane).  A row without a label is never offered.
+//                    The workgroup's lists merge through the same routine (vg_block_publish_grouped) and leave as keys only: a key's
+//                    label is labels[position], gathered again by the final merge (vg_merge_grouped_kernel).  Not combined with
+//                    EX, WITHIN or AFTER; no store mode.
 // The streaming loop was four hand-copied loops and the offer a ladder of seven branches; the code generated for every instance of
 // the two templates was checked identical to that of the copies it replaced (instruction text, registers, spills, scratch, LDS:
 // DESIGN.md 3.6) at the commit that folded them.
@@ -57,6 +64,31 @@ __device__ inline void vg_block_publish(uint8_t *smem, uint64_t mine, int k, uin
     lists[wave * VG_WAVE + lane] = (lane < k) ? mine : VG_EMPTY_KEY;
     __syncthreads();
     vg_select_lists(lists, VG_WAVES_PER_BLOCK, k, dst, smem + VG_WAVES_PER_BLOCK * VG_WAVE * 8);
+}
+
+// The grouped counterpart (VG_SQ_GROUPED): a rank-select over keys would return two rows of one label, so wavefront 0 offers the
+// other wavefronts' first k entries, one list of 64 at a time from LDS, to its own list (vg_list_offer_grouped: sorted lists are offered
+// in ascending order, so once thr has tightened a list costs one ballot) and writes the k keys to `dst` (global; labels to
+// `dst_labels` when asked for).  Every wavefront of the workgroup calls; the keys and labels take VG_WAVES * 64 * 12 bytes of smem
+// - within the VG_PUBLISH_LDS_BYTES every fused launch asks for (launch_fused, vg_scan_masked.hip).  `nwaves` <= VG_WAVES_PER_BLOCK:
+// wavefronts of the workgroup that hold a list.
+static_assert(VG_WAVES_PER_BLOCK * VG_WAVE * 12 <= VG_PUBLISH_LDS_BYTES, "the grouped publish parks keys and labels in the plain publish's LDS");
+__device__ inline void vg_block_publish_grouped(uint8_t *smem, uint64_t mine, uint32_t mlab, int k, int nwaves, uint64_t *dst, uint32_t *dst_labels) {
+    const int lane = threadIdx.x & (VG_WAVE - 1);
+    const int wave = threadIdx.x >> 6;
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);
+    uint32_t *labs = reinterpret_cast<uint32_t *>(smem + (size_t)nwaves * VG_WAVE * 8);
+    lists[wave * VG_WAVE + lane] = (lane < k) ? mine : VG_EMPTY_KEY;
+    labs[wave * VG_WAVE + lane] = mlab;
+    __syncthreads();
+    if (wave != 0) return;
+    uint64_t thr = vg_readlane64(mine, k - 1);
+    for (int w = 1; w < nwaves; ++w) {
+        const uint64_t key = lists[w * VG_WAVE + lane];
+        vg_list_offer_grouped(key, labs[w * VG_WAVE + lane], key != VG_EMPTY_KEY, mine, mlab, thr, lane, k);
+    }
+    dst[lane] = (lane < k) ? mine : VG_EMPTY_KEY;
+    if (dst_labels) dst_labels[lane] = (lane < k) ? mlab : 0xFFFFFFFFu;
 }
 
 typedef uint32_t vg_u32x4 __attribute__((ext_vector_type(4)));
@@ -111,7 +143,7 @@ __device__ inline void vg_load_batch(uint4 (&dst)[U], const uint8_t *rows, long 
 #define VG_STORE_FLOATS 1024          // store mode: distances parked in LDS per wavefront between bursts of stores
 
 // the forms of vg_scan_kernel / vg_scan_long_kernel (the head of this file); the first three have the values of VG_MQ_*
-enum : int { VG_SQ_MASKED = 1, VG_SQ_AFTER = 2, VG_SQ_WITHIN = 4, VG_SQ_EX = 8 };
+enum : int { VG_SQ_MASKED = 1, VG_SQ_AFTER = 2, VG_SQ_WITHIN = 4, VG_SQ_EX = 8, VG_SQ_GROUPED = 16 };
 
 // ---- VG_SQ_WITHIN: the keys of the rows within the radius are parked in a per-wavefront LDS queue and leave in bursts - one atomicAdd of the burst size by one lane, then coalesced 8-byte-per-lane stores.
 // A store (and the atomic's return) shares vmcnt with the batch prefetch, see the store-mode note in vg_scan_kernel: a burst of 64+
@@ -153,9 +185,10 @@ __device__ inline uint64_t vg_mask_bits(const uint64_t *mask, long long row0, in
 template <int VT, int ACC, int U, bool NT, int FORM = 0>      // FORM: VG_SQ_* flags
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
     constexpr bool EX = (FORM & VG_SQ_EX) != 0, WITHIN = (FORM & VG_SQ_WITHIN) != 0, MASKED = (FORM & VG_SQ_MASKED) != 0;
-    constexpr bool AFTER = (FORM & VG_SQ_AFTER) != 0;
+    constexpr bool AFTER = (FORM & VG_SQ_AFTER) != 0, GROUPED = (FORM & VG_SQ_GROUPED) != 0;
     static_assert(!EX || FORM == VG_SQ_EX, "the reference-order extras are not combined with the range, masked or paged forms");
     static_assert(!(WITHIN && AFTER), "a range scan has no cursor");
+    static_assert(!GROUPED || !(EX || WITHIN || AFTER), "a grouped scan is combined with the mask only");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ VgListExtras ex;
     const int lane = threadIdx.x & (VG_WAVE - 1);
@@ -195,7 +228,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
         q[u] = (c < a.nch) ? qs[c] : make_uint4(0u, 0u, 0u, 0u);
     }
     const typename Accum<VT, ACC>::QStat qstat = Accum<VT, ACC>::template query_stat<U>(q, lpr_log2);
-    const bool store_mode = (WITHIN || MASKED || AFTER) ? false : EX ? ((a.out_dist != nullptr) && k == 0) : (a.out_dist != nullptr);
+    const bool store_mode = (WITHIN || MASKED || AFTER || GROUPED) ? false : EX ? ((a.out_dist != nullptr) && k == 0) : (a.out_dist != nullptr);
+    uint32_t mlab = 0xFFFFFFFFu;                                      // grouped mode only: the label of the key in `mine`
     uint64_t floor_key = 0ull;                                        // after mode only: wave-uniform, scalar registers (f32 / uint8 / int8)
     if constexpr (AFTER && !AFTER_LDS) floor_key = vg_uniform64(a.floor[0]);
     const bool store_too = EX && (a.out_dist != nullptr) && k != 0; // the reference replay's prefix pass: top-k + every distance
@@ -239,18 +273,21 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
     constexpr int NB = !RING ? 2 : RING_F32 ? (VG_RING_F32 > 2 ? VG_RING_F32 : 3) : (U == 2) ? 4 : 6;
     uint4 buf[NB][U];
     float nn[NB];
+    uint32_t lab[NB];                                                 // grouped mode only
 #pragma unroll
-    for (int j = 0; j < NB; ++j) nn[j] = 0.0f;
+    for (int j = 0; j < NB; ++j) { nn[j] = 0.0f; lab[j] = 0xFFFFFFFFu; }
     // (masked mode: `live` = the batch has an allowed row; a batch without one points every load at vg_zero_chunk - no row is read)
-    auto load = [&](uint4 (&dst)[U], float &nn_dst, long long batch, bool live) {
+    auto load = [&](uint4 (&dst)[U], float &nn_dst, uint32_t &lab_dst, long long batch, bool live) {
         vg_load_batch<U, NT>(dst, a.rows, batch * rpb + rib, (batch < b_end && live) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
         // A_COSN: the row's squared norm rides along with the batch prefetch (one dword per row from the cached vector)
         // (unconditional for the same reason as the chunk loads: row 0's norm stands in, the row's result is never used)
         if constexpr (ACC == A_COSN) { const long long r0 = batch * rpb + rib; nn_dst = a.row_nn[(batch < b_end && live && r0 < a.n_rows) ? r0 : 0]; }
+        // GROUPED: so does the row's label (row 0's stands in for a row that is not read: its result is never offered)
+        if constexpr (GROUPED) { const long long r0 = batch * rpb + rib; lab_dst = a.labels[(batch < b_end && live && r0 < a.n_rows) ? r0 : 0]; }
     };
     // MASKED: the mask bits of a batch (wave-uniform; 0 behind the wavefront's last batch)
     auto mask_of = [&](long long batch) -> uint64_t { return vg_mask_bits(a.mask, batch * rpb, rpb, batch < b_end); };
-    auto process = [&](uint4 (&cur)[U], float nn_cur, long long bcur, uint64_t mbits) {
+    auto process = [&](uint4 (&cur)[U], float nn_cur, uint32_t lab_cur, long long bcur, uint64_t mbits) {
         Accum<VT, ACC> acc;
         acc.init();
         if constexpr (VT == T_F16 || VT == T_BF16) {
@@ -309,6 +346,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
         else ok = owner && (!MASKED || ((mbits >> rib) & 1ull)) && (!WITHIN || d <= a.within_r) && (d < INFINITY);
         if constexpr (WITHIN) vg_within_offer(key, ok, wqueue, wqueued, a.emit, a.within_cap, lane);
         else if constexpr (EX) vg_list_offer_ex(key, ok, mine, thr, lane, k, &ex);
+        else if constexpr (GROUPED) vg_list_offer_grouped(key, lab_cur, ok && (lab_cur != 0xFFFFFFFFu), mine, mlab, thr, lane, k);
         else vg_list_offer(key, ok, mine, thr, lane, k);
     };
     // One ring loop and one double-buffer loop for every form.  mb[j] = the mask bits of the batch in buffer j, `mnext` those of the
@@ -321,7 +359,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 #pragma unroll
         for (int j = 0; j < NB - 1; ++j) {
             if constexpr (MASKED) mb[j] = mask_of(b + j * wstride);
-            load(buf[j], nn[j], b + j * wstride, !MASKED || mb[j] != 0ull);
+            load(buf[j], nn[j], lab[j], b + j * wstride, !MASKED || mb[j] != 0ull);
         }
         if constexpr (MASKED) mnext = mask_of(b + (NB - 1) * wstride);
         while (b < b_end) {
@@ -329,22 +367,27 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
             for (int j = 0; j < NB; ++j) {
                 const long long bj = b + j * wstride;             // the batch in buffer j
                 if constexpr (MASKED) { mb[(j + NB - 1) % NB] = mnext; mnext = mask_of(bj + NB * wstride); }
-                load(buf[(j + NB - 1) % NB], nn[(j + NB - 1) % NB], bj + (NB - 1) * wstride, !MASKED || mb[(j + NB - 1) % NB] != 0ull);
-                if (MASKED ? mb[j] != 0ull : bj < b_end) process(buf[j], nn[j], bj, MASKED ? mb[j] : 0ull);       // (the bits are 0 behind b_end)
+                load(buf[(j + NB - 1) % NB], nn[(j + NB - 1) % NB], lab[(j + NB - 1) % NB], bj + (NB - 1) * wstride, !MASKED || mb[(j + NB - 1) % NB] != 0ull);
+                if (MASKED ? mb[j] != 0ull : bj < b_end) process(buf[j], nn[j], lab[j], bj, MASKED ? mb[j] : 0ull);       // (the bits are 0 behind b_end)
             }
             b += NB * wstride;
         }
     } else {
         if constexpr (MASKED) { mb[0] = mask_of(b); mnext = mask_of(b + wstride); }
-        load(buf[0], nn[0], b, !MASKED || mb[0] != 0ull);
+        load(buf[0], nn[0], lab[0], b, !MASKED || mb[0] != 0ull);
         while (b < b_end) {
             const long long bn = b + wstride;
             if constexpr (MASKED) { mb[1] = mnext; mnext = mask_of(bn + wstride); }
-            load(buf[1], nn[1], bn, !MASKED || mb[1] != 0ull);
-            if (!MASKED || mb[0] != 0ull) process(buf[0], nn[0], b, MASKED ? mb[0] : 0ull);
+            load(buf[1], nn[1], lab[1], bn, !MASKED || mb[1] != 0ull);
+            // GROUPED: the whole prefetch is issued before the arithmetic starts.  Left to itself the scheduler spreads the label's
+            // address arithmetic and load over `process`, which holds three more registers live through it: bf16 L2 at U = 6 spilled
+            // query registers into scratch and reloaded them - a vmcnt(0) - behind every prefetch (128 VGPRs, 28 bytes; 112 and none now).
+            if constexpr (GROUPED) __builtin_amdgcn_sched_barrier(0);
+            if (!MASKED || mb[0] != 0ull) process(buf[0], nn[0], lab[0], b, MASKED ? mb[0] : 0ull);
 #pragma unroll
             for (int u = 0; u < U; ++u) buf[0][u] = buf[1][u];
             nn[0] = nn[1];
+            if constexpr (GROUPED) lab[0] = lab[1];
             if constexpr (MASKED) mb[0] = mb[1];
             b = bn;
         }
@@ -361,7 +404,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 
     // ---- the workgroup's 16 wave lists -> ONE list per CU in HBM (parallel rank-select, vg_lists.h)
     __syncthreads();                                   // everyone is done with the query staging area
-    vg_block_publish(smem, mine, k, a.cand + (long long)blockIdx.x * VG_WAVE);
+    if constexpr (GROUPED) vg_block_publish_grouped(smem, mine, mlab, k, VG_WAVES_PER_BLOCK, a.cand + (long long)blockIdx.x * VG_WAVE, nullptr);
+    else vg_block_publish(smem, mine, k, a.cand + (long long)blockIdx.x * VG_WAVE);
 }
 
 // Long rows (more 16-byte chunks than 64 lanes x the largest register-resident U): one row per wavefront per step,
@@ -371,8 +415,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 template <int VT, int ACC, bool NT, int FORM = 0>             // FORM: VG_SQ_* flags, without VG_SQ_EX
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
     constexpr bool WITHIN = (FORM & VG_SQ_WITHIN) != 0, MASKED = (FORM & VG_SQ_MASKED) != 0, AFTER = (FORM & VG_SQ_AFTER) != 0;
+    constexpr bool GROUPED = (FORM & VG_SQ_GROUPED) != 0;
     static_assert(!(FORM & VG_SQ_EX), "a long-row scan neither emits nor stores a prefix");
     static_assert(!(WITHIN && AFTER), "a range scan has no cursor");
+    static_assert(!GROUPED || !(WITHIN || AFTER), "a grouped scan is combined with the mask only");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
     const int wave = threadIdx.x >> 6;
@@ -410,7 +456,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
 
     uint64_t mine = VG_EMPTY_KEY, thr = VG_EMPTY_KEY;
     const int k = a.k;
-    const bool store_mode = (WITHIN || MASKED || AFTER) ? false : (a.out_dist != nullptr);
+    const bool store_mode = (WITHIN || MASKED || AFTER || GROUPED) ? false : (a.out_dist != nullptr);
+    uint32_t mlab = 0xFFFFFFFFu;                                    // grouped mode only: the label of the key in `mine`
     uint64_t floor_key = 0ull;                                      // after mode only (see vg_scan_kernel)
     if constexpr (AFTER && !AFTER_LDS) floor_key = vg_uniform64(a.floor[0]);
     uint64_t *wqueue = reinterpret_cast<uint64_t *>(smem + a.store_lds_off) + wave * VG_WITHIN_QUEUE;   // within mode only (vg_within_offer)
@@ -420,7 +467,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
 
     // flattened (row, slice) stream per wavefront, one slice prefetched
     // (masked mode: `live` = the row's bit is set; a row whose bit is clear issues no slice loads - the same address selection)
-    auto load_slice = [&](uint4 (&dst)[U], long long row, int s, bool live = true) {
+    // (grouped mode: the row's label comes with EVERY slice of the row - one dword, the same address for all lanes and for all slices
+    //  of a row, unconditional like the chunk loads - so that nothing is loaded outside the prefetch)
+    auto load_slice = [&](uint4 (&dst)[U], uint32_t &lab_dst, long long row, int s, bool live = true) {
+        if constexpr (GROUPED) lab_dst = a.labels[(row < a.n_rows && live) ? row : 0];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int c = s * slice + u * VG_WAVE + lane;
@@ -435,6 +485,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
         }
     };
     uint4 cur[U], nxt[U];
+    uint32_t lab_cur = 0xFFFFFFFFu, lab_nxt = 0xFFFFFFFFu;          // grouped mode only
     long long row = gw;
     // masked mode: the bit of the current row and of the wavefront's next one (wave-uniform, vg_mask_bits).  The next row's first slice is
     // prefetched during the current row's last step, so its bit is fetched when the current row STARTS: one step ahead of that prefetch
@@ -444,7 +495,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
         m_cur = vg_mask_bits(a.mask, row, 1, row < a.n_rows) != 0ull;
         m_nxt = vg_mask_bits(a.mask, row + wstride, 1, row + wstride < a.n_rows) != 0ull;
     }
-    load_slice(cur, row, 0, m_cur);
+    load_slice(cur, lab_cur, row, 0, m_cur);
     Accum<VT, ACC> acc;
     acc.init();
     int s = 0;
@@ -453,7 +504,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
         int ns = s + 1;
         bool m_load = m_cur;
         if (ns == S || (MASKED && !m_cur)) { ns = 0; nrow = row + wstride; m_load = m_nxt; }
-        load_slice(nxt, nrow, ns, m_load);
+        load_slice(nxt, lab_nxt, nrow, ns, m_load);
         if (!MASKED || m_cur) {
 #pragma unroll
             for (int u = 0; u < U; ++u) acc.chunk(qs[s * slice + u * VG_WAVE + lane], cur[u]);
@@ -476,6 +527,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
                 if constexpr (AFTER) ok = (lane == 0) && (d < INFINITY) && (key >= floor_key);
                 else ok = (lane == 0) && (!WITHIN || d <= a.within_r) && (d < INFINITY);
                 if constexpr (WITHIN) vg_within_offer(key, ok, wqueue, wqueued, a.emit, a.within_cap, lane);
+                else if constexpr (GROUPED) vg_list_offer_grouped(key, lab_cur, ok && (lab_cur != 0xFFFFFFFFu), mine, mlab, thr, lane, k);
                 else vg_list_offer(key, ok, mine, thr, lane, k);
             }
             acc.init();
@@ -485,6 +537,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
+        if constexpr (GROUPED) lab_cur = lab_nxt;
         row = nrow;
         s = ns;
     }
@@ -495,7 +548,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
     if (store_mode) return;
 
     __syncthreads();                                   // everyone is done with the query staging area
-    vg_block_publish(smem, mine, k, a.cand + (long long)blockIdx.x * VG_WAVE);
+    if constexpr (GROUPED) vg_block_publish_grouped(smem, mine, mlab, k, VG_WAVES_PER_BLOCK, a.cand + (long long)blockIdx.x * VG_WAVE, nullptr);
+    else vg_block_publish(smem, mine, k, a.cand + (long long)blockIdx.x * VG_WAVE);
 }
 
 

@@ -83,7 +83,8 @@ extern "C" int64_t vg_corpus_mask_count(const vg_corpus *c) { return c ? c->mask
 
 // One routine for every fused top-k variant that differs from the masked scan only in its kernel table and a ScanArgs field (3.11 of
 // DESIGN.md): VgFusedForm names the table, whether ScanArgs.mask is set (and a mask required) and whether ScanArgs.floor is (the paged
-// scans of vg_scan_after.hip; the floor key travels in the 8 bytes behind the query, one upload).
+// scans of vg_scan_after.hip; the floor key travels in the 8 bytes behind the query, one upload) and whether the scan is grouped (the
+// grouped scans of vg_scan_grouped.hip: ScanArgs.labels, the label-deduping merge, labels in the result).
 // the form's kernel + the plain scan's merge; the k winners land in the pinned c->h_keys (copied behind the merge)
 static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     int acc = vg_metric_to_acc(metric);
@@ -100,32 +101,35 @@ static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     if (f.masked) a.mask = c->d_mask;
     if (f.labeled) a.mask = c->d_label_bits;                 // (the bitmap of one label, built on this stream in front of the scan)
     if (f.after) a.floor = reinterpret_cast<const uint64_t *>(c->d_query + c->stride);
+    if (f.grouped) a.labels = c->d_labels;
     const size_t smem = std::max<size_t>(vg_query_lds_bytes(c, s), (size_t)VG_PUBLISH_LDS_BYTES);
 
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);
     if (evs) hipEventRecord(evs[0], c->stream);
     if ((rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a)) != VG_OK) return rc;
     if (evs) hipEventRecord(evs[2], c->stream);
-    int rcm = vg_launch_merge_one(c->d_cand, (int)blocks, k, c->d_keys, c->stream);
+    int rcm = f.grouped ? vg_launch_merge_grouped(c->d_cand, (int)blocks, k, c->d_labels, c->d_keys, c->stream)
+                        : vg_launch_merge_one(c->d_cand, (int)blocks, k, c->d_keys, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
     if (rcm != 0) return vg_fail(VG_ERR_HIP, "%s: merge launch failed: %s", f.who, hipGetErrorString((hipError_t)rcm));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_keys, c->d_keys, VG_WAVE * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_keys, c->d_keys, f.grouped ? VG_KEYS_BYTES : VG_WAVE * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VG_OK;
 }
 
 // packed keys (distance image << 32 | position local to this corpus), ascending: the form a multi-shard caller merges.  `floor`: the
 // smallest key admitted (read by an after form only)
-int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count) {
+int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count,
+                 uint32_t *out_labels) {
     if (!c || !query || !out_count) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     *out_count = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.labeled ? "labeled" : f.masked ? "masked" : "paged");
-    if (!out_keys) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.grouped ? "grouped" : f.labeled ? "labeled" : f.masked ? "masked" : "paged");
+    if (!out_keys || (f.grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
-    if (f.labeled && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+    if ((f.labeled || f.grouped) && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
     if ((f.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     if (f.after && floor == VG_EMPTY_KEY) return VG_OK;      // nothing is behind the cursor: no launch
     HIP_TRY(hipSetDevice(c->device));
@@ -138,7 +142,12 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
     if (rc != VG_OK) return rc;
     vg_collect_timing(c);
     int cnt = 0;
-    while (cnt < k && c->h_keys[cnt] != VG_EMPTY_KEY) { out_keys[cnt] = c->h_keys[cnt]; ++cnt; }
+    const uint32_t *h_labels = reinterpret_cast<const uint32_t *>(c->h_keys + VG_WAVE);      // (grouped forms: the labels behind the keys)
+    while (cnt < k && c->h_keys[cnt] != VG_EMPTY_KEY) {
+        out_keys[cnt] = c->h_keys[cnt];
+        if (f.grouped) out_labels[cnt] = h_labels[cnt];
+        ++cnt;
+    }
     *out_count = cnt;
     return VG_OK;
 }

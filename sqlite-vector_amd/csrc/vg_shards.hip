@@ -1201,6 +1201,60 @@ extern "C" int vg_shards_scan_topk_labeled(vg_shards *s, int metric, const void 
     return VG_OK;
 }
 
+// ---- grouped scans: every shard answers over its own rows (k groups, its best row of each); one label can live on several shards, so
+// the shards' lists merge through vg_merge_keys_grouped over keys rewritten to GLOBAL scan positions - the answer of one corpus holding
+// all rows (a group's best row over all shards is the best of the shards' best rows, and a group among the k best overall is among
+// the k best of every shard that holds its best row)
+static int shards_grouped(vg_shards *s, bool masked, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
+                          uint32_t *out_labels, int *out_count) {
+    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_grouped: NULL argument");
+    if (s->S == 1) return masked ? vg_scan_topk_grouped_masked(s->sh[0], metric, query, k, out_rowids, out_dist, out_labels, out_count)
+                                 : vg_scan_topk_grouped(s->sh[0], metric, query, k, out_rowids, out_dist, out_labels, out_count);
+    *out_count = 0;
+    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_grouped: k must be at least 1");
+    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_grouped: k must be in 1..64 (grouped scans use the fused list only)");
+    if (!out_rowids || !out_dist || !out_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_grouped: NULL output");
+    if (masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_topk_grouped_masked: no row mask set");
+    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_grouped: no labels set");
+    if (s->n_rows > 0xFFFFFFFFll) return fail(VG_ERR_UNSUPPORTED, "vg_shards_scan_topk_grouped: more than 2^32 - 1 rows over all shards");
+    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
+    std::vector<uint32_t> labels((size_t)s->S * VG_WAVE_KEYS, VG_LABEL_NONE);
+    std::vector<int> counts((size_t)s->S, 0);
+    auto scan = masked ? vg_scan_topk_grouped_masked_keys : vg_scan_topk_grouped_keys;
+    int rc = for_each_shard(s, [&](int i) {
+        return scan(s->sh[(size_t)i], metric, query, k, &keys[(size_t)i * VG_WAVE_KEYS], &labels[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]);
+    });
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < s->S; ++i)                           // local positions -> global ones (a shard's list stays ascending: the map is monotonic)
+        for (int j = 0; j < counts[(size_t)i]; ++j) {
+            uint64_t &key = keys[(size_t)i * VG_WAVE_KEYS + j];
+            key = (key & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(key));
+        }
+    uint64_t gkeys[VG_WAVE_KEYS];
+    uint32_t glabels[VG_WAVE_KEYS];
+    int cnt = 0;
+    rc = vg_merge_keys_grouped(keys.data(), labels.data(), s->S, VG_WAVE_KEYS, nullptr, k, gkeys, glabels, &cnt);
+    if (rc != VG_OK) return fail(rc, vg_last_error());
+    for (int i = 0; i < cnt; ++i) {
+        int shard;
+        int64_t local;
+        locate(s, (int64_t)vg_key_position(gkeys[i]), &shard, &local);
+        out_dist[i] = (double)vg_key_distance(gkeys[i]);
+        out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
+        out_labels[i] = glabels[i];
+    }
+    *out_count = cnt;
+    return VG_OK;
+}
+extern "C" int vg_shards_scan_topk_grouped(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
+                                           uint32_t *out_labels, int *out_count) {
+    return shards_grouped(s, false, metric, query, k, out_rowids, out_dist, out_labels, out_count);
+}
+extern "C" int vg_shards_scan_topk_grouped_masked(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
+                                                  uint32_t *out_labels, int *out_count) {
+    return shards_grouped(s, true, metric, query, k, out_rowids, out_dist, out_labels, out_count);
+}
+
 extern "C" int vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
                                                  int64_t *out_rowids, double *out_dist, int *out_counts) {
     if (!s || !queries || !out_counts || !query_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labeled: NULL argument");
