@@ -311,6 +311,31 @@ int     vg_scan_topk_grouped_masked_keys(vg_corpus *c, int metric, const void *q
 int     vg_merge_keys_grouped(const uint64_t *keys, const uint32_t *labels, int n_lists, int list_len, const int64_t *pos_offsets, int k,
                               uint64_t *out_keys, uint32_t *out_labels, int *out_count);
 
+/* ---- grouped batch scans: the k nearest labels for each of nq queries (row-major nq x dim, host) - "the k nearest documents, for
+ * these 64 requests".  Query i's answer is exactly what vg_scan_topk_grouped (the _masked forms: vg_scan_topk_grouped_masked) is
+ * contracted to return for query i alone.  out_rowids / out_dist / out_labels are nq x k, out_counts nq; the slots of query i behind
+ * out_counts[i] are NOT written.
+ * f32 / uint8 / int8 rows of a register-resident shape: 4 queries (2 where a lane holds 4 or 6 chunks of the row) share every row
+ * load - and every label load - of a pass (vg_scan_multi.h, grouped form; the plan: vg_batch_grouped_plan, vectorgpu_diag.h); each
+ * query keeps its own list, distinct by label, and the lists of a query merge on the device; nq queries cost ceil(nq / 4) - or
+ * ceil(nq / 2) - passes, enqueued back to back, one copy of keys and labels, one wait.  uint8 / int8: rowids, labels, order and
+ * distance bits identical to nq vg_scan_topk_grouped calls; f32: the floats of vg_scan_topk_batch_masked under the same launch
+ * shape.  f16 / bf16, long rows and every other shape without a multi-query form (the masked forms only: also rows of 193 .. 384
+ * 16-byte chunks under cosine, and under L2 for f32 - DESIGN.md 3.16): one single grouped scan per query - a shape that
+ * scan refuses (f16 cosine / dot over rows of 2049 .. 3072 elements) is VG_ERR_UNSUPPORTED here too.
+ * 1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below); nq < 1 or a NULL argument: VG_ERR_INVALID, with the counts zeroed
+ * first where there are counts; no labels set: VG_ERR_INVALID; the masked forms without a mask: VG_ERR_INVALID; an empty corpus or an
+ * empty mask: every count 0, nothing is launched.  The _keys forms return packed keys with positions local to this corpus (out_keys
+ * and out_labels nq x k) - the form a multi-shard caller merges per query with vg_merge_keys_grouped. */
+int     vg_scan_topk_batch_grouped(vg_corpus *c, int metric, const void *queries, int nq, int k,
+                                   int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
+int     vg_scan_topk_batch_grouped_keys(vg_corpus *c, int metric, const void *queries, int nq, int k,
+                                        uint64_t *out_keys, uint32_t *out_labels, int *out_counts);
+int     vg_scan_topk_batch_grouped_masked(vg_corpus *c, int metric, const void *queries, int nq, int k,
+                                          int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
+int     vg_scan_topk_batch_grouped_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k,
+                                               uint64_t *out_keys, uint32_t *out_labels, int *out_counts);
+
 /* ---- masked range scans: every ALLOWED row within a distance of the query - "every row of this tenant within r", near-duplicate
  * detection inside one category (no reference entry point; the reference's form is "SELECT ... FROM vector_full_scan_stream(...)
  * WHERE id IN (...) AND distance <= r": N rows stepped).  The contract is the conjunction of vg_scan_within's and vg_scan_topk_masked's.
@@ -490,6 +515,12 @@ int     vg_shards_scan_topk_grouped(vg_shards *s, int metric, const void *query,
                                     int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
 int     vg_shards_scan_topk_grouped_masked(vg_shards *s, int metric, const void *query, int k,
                                            int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+/* vg_scan_topk_batch_grouped[_masked] over every shard: each shard answers all nq queries over its own rows, then every query's
+ * lists merge through vg_merge_keys_grouped as above.  Same contract and errors. */
+int     vg_shards_scan_topk_batch_grouped(vg_shards *s, int metric, const void *queries, int nq, int k,
+                                          int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
+int     vg_shards_scan_topk_batch_grouped_masked(vg_shards *s, int metric, const void *queries, int nq, int k,
+                                                 int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
 /* the masked range scans over every shard: each shard answers over its own bits (a shard whose share of the mask is empty launches
  * nothing and contributes nothing), merged like vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus
  * holding all rows.  Same contract; the results are read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and

@@ -219,6 +219,14 @@ def _load():
         "vg_merge_keys_grouped": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, C.POINTER(i32)]),
         "vg_shards_scan_topk_grouped": (i32, [vp, i32, vp, i32, vp, vp, vp, C.POINTER(i32)]),
         "vg_shards_scan_topk_grouped_masked": (i32, [vp, i32, vp, i32, vp, vp, vp, C.POINTER(i32)]),
+        # grouped batch scans: the same for many queries, in shared passes
+        "vg_scan_topk_batch_grouped": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "vg_scan_topk_batch_grouped_keys": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
+        "vg_scan_topk_batch_grouped_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "vg_scan_topk_batch_grouped_masked_keys": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
+        "vg_shards_scan_topk_batch_grouped": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "vg_shards_scan_topk_batch_grouped_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+        "vg_batch_grouped_plan": (i32, [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
         "vg_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
         "vg_scan_within_batch_keys": (i32, [vp, i32, i64, i64, vp]),
@@ -371,6 +379,27 @@ class _GroupedOps:
         fn = getattr(lib(), self._sprefix + "scan_topk_grouped" + ("_masked" if masked else ""))
         _check(fn(self.h, metric, _ptr(query), k, _ptr(ids), _ptr(dist), _ptr(lab), C.byref(cnt)))
         return ids[:cnt.value], dist[:cnt.value], lab[:cnt.value]
+
+    def scan_topk_batch_grouped(self, metric, queries, k, masked=False):
+        """scan_topk_grouped for every row of `queries`, in shared passes: (rowids [nq, k], distances [nq, k], labels [nq, k],
+        counts [nq]); the slots of query i behind counts[i] are not written"""
+        queries = np.ascontiguousarray(queries)
+        nq = queries.shape[0]
+        ids = np.zeros((nq, max(k, 1)), dtype=np.int64)
+        dist = np.zeros((nq, max(k, 1)), dtype=np.float64)
+        lab = np.zeros((nq, max(k, 1)), dtype=np.uint32)
+        cnt = np.zeros(max(nq, 1), dtype=np.int32)
+        fn = getattr(lib(), self._sprefix + "scan_topk_batch_grouped" + ("_masked" if masked else ""))
+        _check(fn(self.h, metric, _ptr(queries), nq, k, _ptr(ids), _ptr(dist), _ptr(lab), _ptr(cnt)))
+        return ids, dist, lab, cnt[:nq]
+
+
+def batch_grouped_plan(corpus, metric, masked=False):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_topk_batch_grouped serves this corpus with; 0 queries per pass =
+    one single grouped scan per query (f16 / bf16, long rows) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().vg_batch_grouped_plan(corpus.h, metric, 1 if masked else 0, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
 
 
 def merge_keys_grouped(keys, labels, pos_offsets, k):

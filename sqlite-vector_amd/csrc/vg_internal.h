@@ -328,7 +328,14 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
 // labels[position]) on `stream`: dev_out receives 64 keys (VG_EMPTY_KEY padded) followed by their 64 labels - VG_KEYS_BYTES in all
 int vg_launch_merge_grouped(const uint64_t *dev_cand, int nlists, int k, const uint32_t *dev_labels, uint64_t *dev_out, hipStream_t stream);
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
-                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr);
+                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr, uint32_t *out_labels = nullptr);
+// the batch launch of that merge (vg_multi_grouped.hip): workgroup n merges query n's `nlists` lists ([nq][nlists][64] keys at dev_cand) and writes its 64
+// keys and 64 labels at dev_out + n * VG_KEYS_BYTES.  A grouped VgFusedBatchForm (`single.grouped`, vg_multi_grouped.hip) ends in it:
+// vg_fused_batch_run then sets ScanArgs.labels, requires labels, sizes a slice's key buffer for the labels and fills out_labels (nq x k)
+int vg_launch_merge_grouped_batch(const uint64_t *dev_cand, int nlists, int k, const uint32_t *dev_labels, uint64_t *dev_out, int nq, hipStream_t stream);
+scan_fn_t vg_pick_scan_grouped(int vtype, int acc, int U, bool long_rows);          // vg_scan_grouped.hip: the grouped single scans' tables,
+scan_fn_t vg_pick_scan_grouped_masked(int vtype, int acc, int U, bool long_rows);   // ... all rows / the allowed rows
+scan_fn_t vg_pick_multi_grouped_masked(int vtype, int acc, int U, int NQ);          // vg_multi_grouped_masked.hip: the masked grouped batch's table
 // ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): the floor-key forms behind the C ABI, what the shards call per shard.
 // Floors are keys over positions LOCAL to the corpus; a floor of VG_KEY_EMPTY admits nothing (no launch in the single form).
 int vg_after_floor_run(vg_corpus *c, bool masked, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count);

@@ -36,6 +36,8 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
 // NQ queries (zero-padded rows of the corpus stride, back to back at dev_queries) against the allowed rows in ONE pass; dev_cand:
 // NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on the corpus stream.  One launcher for every form
 // (VgFusedBatchForm, vg_internal.h): the masked batch, and the paged batches of vg_multi_after.hip (dev_floors: NQ keys).
+// A grouped form (vg_multi_grouped.hip): the lists merge through the label-deduping merge and dev_out_keys receives, per query, 64
+// keys followed by their 64 labels (VG_KEYS_BYTES).
 static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s,
                                const uint8_t *dev_queries, const uint64_t *dev_floors, const uint32_t *dev_qlabels, int k, uint64_t *dev_cand,
                                uint64_t *dev_out_keys) {
@@ -45,13 +47,15 @@ static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metri
     if (f.single.masked) a.mask = c->d_mask;
     if (f.single.after) a.floor = dev_floors;
     if (f.single.labeled) { a.labels = c->d_labels; a.qlabels = dev_qlabels; }
+    if (f.single.grouped) a.labels = c->d_labels;
     const size_t smem = std::max<size_t>((size_t)NQ * c->nch * 16, (size_t)VG_PUBLISH_LDS_BYTES);
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);          // one slot of the profiling ring per pass
     if (evs) hipEventRecord(evs[0], c->stream);
     int rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a);
     if (rc != VG_OK) return rc;
     if (evs) hipEventRecord(evs[2], c->stream);
-    rc = vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
+    rc = f.single.grouped ? vg_launch_merge_grouped_batch(dev_cand, (int)blocks, k, c->d_labels, dev_out_keys, NQ, c->stream)
+                          : vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
     if (rc != 0) return vg_fail(VG_ERR_HIP, "%s: merge launch failed: %s", f.who, hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipGetLastError());
@@ -63,14 +67,17 @@ static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metri
 
 // nq queries, NQ per pass; every pass of every slice is enqueued back to back on the corpus stream, one wait at the end
 static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries,
-                              int nq, const uint64_t *floors, const uint32_t *qlabels, int k, uint64_t *out_keys, int *out_counts) {
+                              int nq, const uint64_t *floors, const uint32_t *qlabels, int k, uint64_t *out_keys, int *out_counts,
+                              uint32_t *out_labels) {
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
     const int slice = std::min(nq_pad, VG_FUSED_SLICE);
     // (an after form: the slice's floor keys sit behind its queries in d_bq and go up with them; a pad slot admits nothing.  A labeled
     //  form: the slice's query labels, behind those; a pad slot carries VG_LABEL_NONE and matches nothing)
     const size_t fl_off = (size_t)slice * c->stride;
     const size_t lb_off = fl_off + (f.single.after ? (size_t)slice * sizeof(uint64_t) : 0);
-    const size_t qbytes = lb_off + (f.single.labeled ? (size_t)slice * sizeof(uint32_t) : 0), keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
+    // (a grouped form: a query's 64 keys are followed by their 64 labels, so its pitch in d_bkeys is VG_KEYS_BYTES)
+    const size_t kpitch = f.single.grouped ? VG_KEYS_BYTES / sizeof(uint64_t) : 64;
+    const size_t qbytes = lb_off + (f.single.labeled ? (size_t)slice * sizeof(uint32_t) : 0), keybytes = (size_t)nq_pad * kpitch * sizeof(uint64_t);
     if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
                                 HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
     if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
@@ -97,11 +104,11 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
             rc = launch_fused_multi(c, f, metric, fn, NQ, s, (const uint8_t *)c->d_bq + (size_t)g * c->stride,
                                      reinterpret_cast<const uint64_t *>((const uint8_t *)c->d_bq + fl_off) + g,
                                      reinterpret_cast<const uint32_t *>((const uint8_t *)c->d_bq + lb_off) + g, k, c->d_cand,
-                                     c->d_bkeys + (size_t)(q0 + g) * 64);
+                                     c->d_bkeys + (size_t)(q0 + g) * kpitch);
     }
     if (rc != VG_OK) { hipStreamSynchronize(c->stream); return rc; }      // (hq must outlive what was enqueued)
-    std::vector<uint64_t> keys((size_t)nq * 64);
-    hipError_t e = hipMemcpyAsync(keys.data(), c->d_bkeys, (size_t)nq * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+    std::vector<uint64_t> keys((size_t)nq * kpitch);
+    hipError_t e = hipMemcpyAsync(keys.data(), c->d_bkeys, (size_t)nq * kpitch * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
     hipError_t e2 = hipStreamSynchronize(c->stream);
     if (e != hipSuccess || e2 != hipSuccess)
         return vg_fail(VG_ERR_HIP, "%s: %s", f.who, hipGetErrorString(e != hipSuccess ? e : e2));
@@ -109,9 +116,10 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
     for (int i = 0; i < nq; ++i) {
         int cnt = 0;
         for (int j = 0; j < k; ++j) {
-            const uint64_t key = keys[(size_t)i * 64 + j];
+            const uint64_t key = keys[(size_t)i * kpitch + j];
             if (key == VG_KEY_EMPTY) break;
             out_keys[(size_t)i * k + cnt] = key;
+            if (f.single.grouped) out_labels[(size_t)i * k + cnt] = reinterpret_cast<const uint32_t *>(&keys[(size_t)i * kpitch + 64])[j];
             ++cnt;
         }
         out_counts[i] = cnt;
@@ -120,15 +128,16 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
 }
 
 // packed keys (distance image << 32 | position local to this corpus), ascending, nq x k: the form a multi-shard caller merges.
-// Slots behind out_counts[i] are not written.  `floors`: a key per query, read by an after form only.
+// Slots behind out_counts[i] are not written.  `floors`: a key per query, read by an after form only.  `out_labels` (nq x k): the
+// winners' labels, filled by a grouped form only.
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
-                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels) {
+                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels) {
     if (!c || !queries || !out_counts || (f.single.after && !floors) || (f.single.labeled && !qlabels)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", f.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.labeled ? "labeled" : f.single.masked ? "masked" : "paged");
-    if (!out_keys) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.grouped ? "grouped" : f.single.labeled ? "labeled" : f.single.masked ? "masked" : "paged");
+    if (!out_keys || (f.single.grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (f.single.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
     if (f.single.labeled) {
@@ -136,6 +145,7 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
         for (int i = 0; i < nq; ++i)
             if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", f.who, i);
     }
+    if (f.single.grouped && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
     if ((f.single.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     HIP_TRY(hipSetDevice(c->device));
     VgShape s{};
@@ -150,12 +160,12 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
                 if (rcb != VG_OK) return rcb;
             }
             int rc = vg_fused_run(c, f.single, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, floors ? floors[i] : 0ull,
-                                  out_keys + (size_t)i * k, &out_counts[i]);
+                                  out_keys + (size_t)i * k, &out_counts[i], f.single.grouped ? out_labels + (size_t)i * k : nullptr);
             if (rc != VG_OK) return rc;
         }
         return VG_OK;
     }
-    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, qlabels, k, out_keys, out_counts);
+    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, qlabels, k, out_keys, out_counts, out_labels);
 }
 
 extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,

@@ -41,6 +41,7 @@ scan_fn_t vg_pick_scan_grouped_masked(int vtype, int acc, int U, bool long_rows)
 // One workgroup of 16 wavefronts over nlists <= 256 sorted lists of 64 keys: wavefront w takes lists w, w + 16, ... - all their keys
 // first, then all their labels (two memory round trips per wavefront, not two per list), offered list by list to its own grouped
 // list - and the 16 lists merge through LDS like a scan workgroup's (vg_block_publish_grouped).  out: 64 keys, then 64 labels.
+// (vg_merge_grouped_batch_kernel, vg_multi_grouped.hip, is these statements behind a per-query offset: a change here belongs there too)
 #define VG_GMERGE_PER_WAVE (VG_SEL_MAX_HEADS / VG_WAVES_PER_BLOCK)
 __global__ __launch_bounds__(VG_BLOCK) void vg_merge_grouped_kernel(const uint64_t *cand, int nlists, int k, const uint32_t *labels, uint64_t *out) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[VG_WAVES_PER_BLOCK * VG_WAVE * 12];

@@ -48,13 +48,21 @@
 //                    What the pipeline carries: three label dwords per lane (current, prefetched, in flight) and the current batch's
 //                    ballot - per-stage ballots PER QUERY would be 2 * NQ scalar registers a stage.  Not combined
 //                    with MASKED / AFTER / WITHIN.  Without the flag the label values are never defined and everything folds away.
+//   VG_MQ_GROUPED    the k nearest LABELS per query, each by its best row (the batch form of VG_SQ_GROUPED, vg_scan.h).  Combined with
+//                    VG_MQ_MASKED only.  Every lane loads the label of its own row WITH the row prefetch of that batch (row 0 stands
+//                    in for a row out of range or in a batch that is not read); the label decides no address, so - unlike LABELED -
+//                    it does not run a step ahead: two label dwords per lane, current and prefetched.  Each query keeps one more
+//                    register next to `mine` / `thr`: `mlab`, the label of the key in `mine`, and its list stays distinct by label
+//                    (vg_list_offer_grouped).  A row without a label is offered to no query.  The pad queries of a ragged pass
+//                    collect whatever they collect; their lists are never read.  Lists leave as keys only
+//                    (vg_block_publish_grouped), merged per query by vg_merge_grouped_batch_kernel (vg_multi_grouped.hip, grid NQ).
 // The forms were five hand-copied loops; the code generated for every instance of this template was checked identical to that of the
 // copy it replaced (instruction text, registers, spills, scratch, LDS: DESIGN.md 3.6) at the commit that folded them.
 //
 //   a.query         : NQ zero-padded queries back to back (nch * 16 bytes each); WITHIN: and BEHIND them NQ VgWithinQuery descriptors
 //   a.mask          : (MASKED) ceil(n_rows / 64) words, bits behind the last row clear
 //   a.floor         : (AFTER) NQ keys
-//   a.labels        : (LABELED) n_rows dwords;  a.qlabels : (LABELED) NQ dwords
+//   a.labels        : (LABELED, GROUPED) n_rows dwords;  a.qlabels : (LABELED) NQ dwords
 //   a.cand          : (top-k forms) [NQ][gridDim.x][64] candidate keys
 //   descriptor n    : (WITHIN) the [count | cap keys] region of query n, its capacity and its radius (a float: the host rounds down)
 //   a.store_lds_off : (WITHIN) byte offset in dynamic LDS of the key queues, [NQ][wavefront][VG_WITHIN_QUEUE]
@@ -66,7 +74,7 @@
 
 #include "vg_scan.h"
 
-enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4, VG_MQ_LABELED = 8 };
+enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4, VG_MQ_LABELED = 8, VG_MQ_GROUPED = 16 };
 #define VG_MQ_LABEL_NONE 0xFFFFFFFFu      // (VG_LABEL_NONE of vectorgpu.h)
 
 struct VgWithinQuery {                 // 32 bytes, read through wave-uniform addresses (scalar loads)
@@ -102,9 +110,10 @@ __device__ inline void vg_mw_offer(uint64_t key, bool match, uint64_t *queue, in
 template <int VT, int ACC, int U, int NQ, int FORM>          // VT: T_F32 / T_U8 / T_I8; FORM: VG_MQ_* flags
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
     constexpr bool MASKED = (FORM & VG_MQ_MASKED) != 0, AFTER = (FORM & VG_MQ_AFTER) != 0, WITHIN = (FORM & VG_MQ_WITHIN) != 0;
-    constexpr bool LABELED = (FORM & VG_MQ_LABELED) != 0;
+    constexpr bool LABELED = (FORM & VG_MQ_LABELED) != 0, GROUPED = (FORM & VG_MQ_GROUPED) != 0;
     static_assert(!(AFTER && WITHIN), "a range scan has no cursor");
     static_assert(!LABELED || FORM == VG_MQ_LABELED, "the labeled form is not combined with the masked, paged or range forms");
+    static_assert(!GROUPED || (FORM & ~VG_MQ_MASKED) == VG_MQ_GROUPED, "the grouped form is combined with the mask only");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
     // (WITHIN: wave-uniform by construction; readfirstlane says so to the compiler, and the queue addresses stay scalar)
@@ -131,6 +140,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
     }
     // what a query keeps between batches: its candidate list (and floor), or its radius and queue
     uint64_t mine[NQ], thr[NQ], floor_key[NQ];
+    uint32_t mlab[NQ];                                                 // GROUPED: the label of the key in `mine`
     const int k = a.k;
     const VgWithinQuery *wq = reinterpret_cast<const VgWithinQuery *>(a.query + (long long)NQ * a.nch * 16);
     float r[NQ];
@@ -145,6 +155,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         } else {
             mine[n] = VG_EMPTY_KEY;
             thr[n] = VG_EMPTY_KEY;
+            if constexpr (GROUPED) mlab[n] = VG_MQ_LABEL_NONE;
             if constexpr (AFTER) floor_key[n] = vg_uniform64(a.floor[n]);
         }
     }
@@ -174,12 +185,18 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         for (int n = 0; n < NQ; ++n) hit |= (lab == qlabel[n]);
         return __ballot(hit && lab != VG_MQ_LABEL_NONE && batch < nbatch && batch * rpb + rib < a.n_rows);
     };
+    // GROUPED: the label of this lane's row of a batch, loaded with the batch's rows (`live`: the batch is read at all)
+    auto group_label_of = [&](long long batch, bool live) -> uint32_t {
+        const long long r0 = batch * rpb + rib;
+        return a.labels[(batch < nbatch && live && r0 < a.n_rows) ? r0 : 0];
+    };
     uint4 cur[U], nxt[U];
     uint32_t lcur = 0u, lnext = 0u;
     if constexpr (LABELED) { lcur = label_of(b); lnext = label_of(b + wstride); }
     uint64_t mcur = LABELED ? label_hits(lcur, b) : mask_of(b);
     uint64_t mnext = LABELED ? 0ull : mask_of(b + wstride);
     vg_load_batch<U, true>(cur, a.rows, b * rpb + rib, (b < nbatch && mcur != 0ull) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
+    if constexpr (GROUPED) lcur = group_label_of(b, mcur != 0ull);
     while (b < nbatch) {
         const long long bn = b + wstride;
         uint64_t mnxt = mnext;                                         // the bits of batch bn: asked for one step ago
@@ -191,6 +208,11 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
             mnext = mask_of(bn + wstride);
         }
         vg_load_batch<U, true>(nxt, a.rows, bn * rpb + rib, (bn < nbatch && mnxt != 0ull) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
+        if constexpr (GROUPED) {
+            lnext = group_label_of(bn, mnxt != 0ull);
+            // (the whole prefetch, label included, is issued before the arithmetic starts: see the grouped single form, vg_scan.h)
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (mcur != 0ull) {
             const long long row = b * rpb + rib;
             // the row's lane, and the row is allowed (LABELED: carries a label at all - which query's is the offer's business)
@@ -214,7 +236,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
                     // (a top-k form uses the distance at once, NOT through d[]: with it the ten f32 L1 floor instances came out with
                     //  another, equivalent, predicate sequence than the copies had)
                     const uint64_t key = vg_make_key(dn, (uint32_t)row);
-                    if constexpr (LABELED) vg_list_offer(key, owner && (dn < INFINITY) && (lcur == qlabel[n]), mine[n], thr[n], lane, k);
+                    if constexpr (GROUPED) vg_list_offer_grouped(key, lcur, owner && (dn < INFINITY) && (lcur != VG_MQ_LABEL_NONE), mine[n], mlab[n], thr[n], lane, k);
+                    else if constexpr (LABELED) vg_list_offer(key, owner && (dn < INFINITY) && (lcur == qlabel[n]), mine[n], thr[n], lane, k);
                     else vg_list_offer(key, owner && (dn < INFINITY) && (!AFTER || key >= floor_key[n]), mine[n], thr[n], lane, k);
                 }
             }
@@ -236,6 +259,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
         mcur = mnxt;
         if constexpr (LABELED) lcur = lnxt;
+        if constexpr (GROUPED) lcur = lnext;
         b = bn;
     }
 #pragma unroll
@@ -244,7 +268,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
             if (queued[n] > 0) vg_mw_flush(queue[n], queued[n], wq[n].out, wq[n].cap, lane);
         } else {
             __syncthreads();                               // query staging area / the previous publish is done with LDS
-            vg_block_publish(smem, mine[n], k, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE);
+            if constexpr (GROUPED) vg_block_publish_grouped(smem, mine[n], mlab[n], k, VG_WAVES_PER_BLOCK, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE, nullptr);
+            else vg_block_publish(smem, mine[n], k, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE);
         }
     }
 }
