@@ -336,6 +336,37 @@ int     vg_scan_topk_batch_grouped_masked(vg_corpus *c, int metric, const void *
 int     vg_scan_topk_batch_grouped_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k,
                                                uint64_t *out_keys, uint32_t *out_labels, int *out_counts);
 
+/* ---- capped scans: the k nearest ROWS, at most per_label of one label - rows are chunks, the label is the document (product, brand) a
+ * chunk belongs to, the caller wants "the 20 nearest chunks, but no more than 3 of any document" (group_size / max hits per group
+ * elsewhere; no reference entry point).  The labels are those of the labeled scans (vg_corpus_set_labels).  Contract, m = per_label:
+ *   1. take every row with a finite distance and a label other than VG_LABEL_NONE (the masked forms: whose mask bit is set as well);
+ *   2. order them by the 64-bit scan key, i.e. by (distance, scan position), whatever the handle's tie_order;
+ *   3. walk that order and keep a row iff fewer than m rows of its label have been kept;
+ *   4. return the first k rows kept - (rowid, distance, label), ascending by key.
+ * m = 1 is vg_scan_topk_grouped's contract and returns its answer bit for bit; m above k behaves as k.  Every distance is the float
+ * vg_scan_distances reports for that row; NaN / +Inf rows never enter; a row without a label is never returned.  One pass over the
+ * rows: the grouped scans' kernels with a list that holds up to m rows of a label (a new row of a full label replaces the label's
+ * worst kept row), the same merges on the device, one copy of k keys and k labels.  A top-k with a host-side cap is NOT this: one label
+ * owning the 64 nearest rows hides every other row from it.
+ * 1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below); per_label < 1: VG_ERR_INVALID; no labels set: VG_ERR_INVALID; the
+ * masked forms without a mask: VG_ERR_INVALID; NULL arguments: VG_ERR_INVALID; an empty corpus or an empty mask: *out_count = 0,
+ * nothing is launched.  Not served, like the grouped scans: f16 corpora with rows of 2049 .. 3072 elements under the cosine and dot
+ * metrics (VG_ERR_UNSUPPORTED; L2 and L1 are served).  No batch form and no SQL function yet.
+ * The _keys forms return packed keys with positions local to this corpus (out_keys[k], out_labels[k]).
+ * vg_merge_keys_capped (host): vg_merge_keys_grouped with the cap, for lists of several corpora that are each a capped answer with
+ * the same k and per_label - the four steps over the union, by (distance, global position); same layout, offsets and errors, and
+ * per_label < 1: VG_ERR_INVALID. */
+int     vg_scan_topk_capped(vg_corpus *c, int metric, const void *query, int k, int per_label,
+                            int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_capped_keys(vg_corpus *c, int metric, const void *query, int k, int per_label,
+                                 uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_capped_masked(vg_corpus *c, int metric, const void *query, int k, int per_label,
+                                   int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_capped_masked_keys(vg_corpus *c, int metric, const void *query, int k, int per_label,
+                                        uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+int     vg_merge_keys_capped(const uint64_t *keys, const uint32_t *labels, int n_lists, int list_len, const int64_t *pos_offsets, int k,
+                             int per_label, uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+
 /* ---- masked range scans: every ALLOWED row within a distance of the query - "every row of this tenant within r", near-duplicate
  * detection inside one category (no reference entry point; the reference's form is "SELECT ... FROM vector_full_scan_stream(...)
  * WHERE id IN (...) AND distance <= r": N rows stepped).  The contract is the conjunction of vg_scan_within's and vg_scan_topk_masked's.
@@ -521,6 +552,13 @@ int     vg_shards_scan_topk_batch_grouped(vg_shards *s, int metric, const void *
                                           int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
 int     vg_shards_scan_topk_batch_grouped_masked(vg_shards *s, int metric, const void *queries, int nq, int k,
                                                  int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
+/* the capped scans over every shard: each shard answers over its own rows (its k nearest rows under the cap), the lists merge
+ * through vg_merge_keys_capped by (distance, GLOBAL scan position): the rowids, labels, order and distance bits of one corpus holding
+ * all rows.  Same contract; at most 2^32 - 1 rows over all shards. */
+int     vg_shards_scan_topk_capped(vg_shards *s, int metric, const void *query, int k, int per_label,
+                                   int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_shards_scan_topk_capped_masked(vg_shards *s, int metric, const void *query, int k, int per_label,
+                                          int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
 /* the masked range scans over every shard: each shard answers over its own bits (a shard whose share of the mask is empty launches
  * nothing and contributes nothing), merged like vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus
  * holding all rows.  Same contract; the results are read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and

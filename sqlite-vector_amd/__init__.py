@@ -227,6 +227,14 @@ def _load():
         "vg_shards_scan_topk_batch_grouped": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp]),
         "vg_shards_scan_topk_batch_grouped_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp]),
         "vg_batch_grouped_plan": (i32, [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        # capped scans: the k nearest rows, at most per_label of one label
+        "vg_scan_topk_capped": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_capped_keys": (i32, [vp, i32, vp, i32, i32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_capped_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_capped_masked_keys": (i32, [vp, i32, vp, i32, i32, vp, vp, C.POINTER(i32)]),
+        "vg_merge_keys_capped": (i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, C.POINTER(i32)]),
+        "vg_shards_scan_topk_capped": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_shards_scan_topk_capped_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, C.POINTER(i32)]),
         "vg_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
         "vg_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
         "vg_scan_within_batch_keys": (i32, [vp, i32, i64, i64, vp]),
@@ -393,6 +401,19 @@ class _GroupedOps:
         _check(fn(self.h, metric, _ptr(queries), nq, k, _ptr(ids), _ptr(dist), _ptr(lab), _ptr(cnt)))
         return ids, dist, lab, cnt[:nq]
 
+    def scan_topk_capped(self, metric, query, k, per_label, masked=False):
+        """order the labeled rows with a finite distance (masked: whose mask bit is set) by (distance, scan position), keep a row iff
+        fewer than `per_label` rows of its label have been kept, return the first k kept: (rowids, distances, labels); per_label = 1
+        is scan_topk_grouped, per_label above k behaves as k"""
+        query = np.ascontiguousarray(query)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        lab = np.zeros(max(k, 1), dtype=np.uint32)
+        cnt = C.c_int(0)
+        fn = getattr(lib(), self._sprefix + "scan_topk_capped" + ("_masked" if masked else ""))
+        _check(fn(self.h, metric, _ptr(query), k, per_label, _ptr(ids), _ptr(dist), _ptr(lab), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value], lab[:cnt.value]
+
 
 def batch_grouped_plan(corpus, metric, masked=False):
     """(queries per pass, lanes per row, 16-byte chunks per lane) scan_topk_batch_grouped serves this corpus with; 0 queries per pass =
@@ -412,6 +433,21 @@ def merge_keys_grouped(keys, labels, pos_offsets, k):
     out_lab = np.zeros(max(k, 1), dtype=np.uint32)
     cnt = C.c_int(0)
     _check(lib().vg_merge_keys_grouped(_ptr(keys), _ptr(labels), n_lists, list_len, _ptr(off), k, _ptr(out_keys), _ptr(out_lab), C.byref(cnt)))
+    return out_keys[:cnt.value], out_lab[:cnt.value]
+
+
+def merge_keys_capped(keys, labels, pos_offsets, k, per_label):
+    """vg_merge_keys_capped: keys / labels [n_lists, list_len] -> (keys with global positions, labels), at most per_label rows of a
+    label - host only"""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    n_lists, list_len = keys.shape
+    off = None if pos_offsets is None else np.ascontiguousarray(pos_offsets, dtype=np.int64)
+    out_keys = np.zeros(max(k, 1), dtype=np.uint64)
+    out_lab = np.zeros(max(k, 1), dtype=np.uint32)
+    cnt = C.c_int(0)
+    _check(lib().vg_merge_keys_capped(_ptr(keys), _ptr(labels), n_lists, list_len, _ptr(off), k, per_label, _ptr(out_keys), _ptr(out_lab),
+                                      C.byref(cnt)))
     return out_keys[:cnt.value], out_lab[:cnt.value]
 
 

@@ -174,6 +174,42 @@ __device__ inline void vg_list_offer_grouped(uint64_t key, uint32_t label, bool 
         if (c < thr) vg_list_insert_grouped(mine, mlab, thr, c, cl, lane, k);
     }
 }
+// ---- the capped list (VG_SQ_CAPPED, vg_scan_capped.hip): the grouped list with a cap m >= 1 (wave-uniform) in place of 1 - the same
+// layout, and never more than m of the 64 lanes on one label.  The ballot on an accepted candidate's label (c, cl) finds up to m lanes:
+//   * fewer than m: j = 64, the ordinary insert;
+//   * m of them: j = the HIGHEST one, the label's worst kept row.  Its key is <= c: the candidate is dropped - m better rows of the
+//     label are kept.  Otherwise c is inserted at its place p <= j, only lanes p..j move up by one and the entry at j is overwritten:
+//     the grouped routine's moves, and the label still sits in m lanes.
+// With m = 1 every decision is the grouped routine's.  Slot k-1 afterwards holds its old key, the key of slot k-2 or c: thr never rises.
+// Exact: a row is in the capped top-k of a set iff fewer than m rows of its label and fewer than k kept rows are in
+// front of it; both hold in every subset that contains the row, so no partial list drops a row of the answer, and a rejected candidate
+// (key >= thr) has k kept rows in front of it.  Lanes k..63 only ever hold rows that were accepted below thr and pushed up: a row a
+// lane below k holds never moves back down, so what those lanes keep (and count against the cap) decides nothing below k.
+__device__ inline void vg_list_insert_capped(uint64_t &mine, uint32_t &mlab, uint64_t &thr, uint64_t c, uint32_t cl, int lane, int k, int m) {
+    const unsigned long long same = __ballot(mlab == cl);            // at most m bits
+    int j = VG_WAVE;
+    if (__popcll(same) >= m) {                                       // (m >= 1: never with an empty ballot)
+        j = 63 - __clzll((long long)same);
+        if (vg_readlane64(mine, j) <= c) return;                     // (wave-uniform: c, j and the key read are)
+    }
+    const uint64_t prev = vg_wave_shr1(mine);                        // lane 0 sees 0, which is never > c
+    const uint32_t plab = vg_wave_shr1(mlab);
+    const bool move = (mine > c) && (lane <= j);
+    const bool pgt = prev > c;
+    mine = move ? (pgt ? prev : c) : mine;
+    mlab = move ? (pgt ? plab : cl) : mlab;
+    thr = vg_readlane64(mine, k - 1);
+}
+__device__ inline void vg_list_offer_capped(uint64_t key, uint32_t label, bool valid, uint64_t &mine, uint32_t &mlab, uint64_t &thr, int lane, int k, int m) {
+    unsigned long long b = __ballot(valid && key < thr);
+    while (b) {
+        int src = __ffsll((long long)b) - 1;
+        b &= b - 1;
+        uint64_t c = vg_readlane64(key, src);
+        uint32_t cl = (uint32_t)__builtin_amdgcn_readlane((int)label, src);
+        if (c < thr) vg_list_insert_capped(mine, mlab, thr, c, cl, lane, k, m);
+    }
+}
 // The same with a start threshold and the reference-order candidate stream (vg_reforder.hip).  The three values involved are
 // needed only when a list accepts a key - about once per wavefront and scan - so they live in LDS, not in the scalar registers the
 // streaming loop is short of (every scan kernel sits at the 106-SGPR limit; holding them there spilled SGPRs into VGPR lanes).

@@ -320,13 +320,17 @@ scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows); 
 // builds one bitmap per run of equal labels).
 // `grouped` (the grouped scans, vg_scan_grouped.hip): ScanArgs.labels is set and labels are required, the lists of the workgroups go
 // through vg_launch_merge_grouped instead of the rank-select merge, and vg_fused_run also yields the winners' labels (out_labels).
-struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; bool grouped; };
+// `per_label` >= 1 (the capped scans, vg_scan_capped.hip; with `grouped` set, whose host path they share): the cap m travels in
+// ScanArgs.within_cap, clamped to k, and the lists of the workgroups go through vg_launch_merge_capped.  0: not a capped form.
+struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; bool grouped; int per_label; };
 struct VgFusedBatchForm { const char *who; vg_pick_multi_fn_t pick; VgFusedForm single; };
 int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count,
                  uint32_t *out_labels = nullptr);
 // vg_scan_grouped.hip: the label-deduping final merge of `nlists` <= 256 per-workgroup lists (keys only; a key's label is
 // labels[position]) on `stream`: dev_out receives 64 keys (VG_EMPTY_KEY padded) followed by their 64 labels - VG_KEYS_BYTES in all
 int vg_launch_merge_grouped(const uint64_t *dev_cand, int nlists, int k, const uint32_t *dev_labels, uint64_t *dev_out, hipStream_t stream);
+// vg_scan_capped.hip: the same for the capped scans - at most `per_label` (1 .. k) keys of one label among the k
+int vg_launch_merge_capped(const uint64_t *dev_cand, int nlists, int k, int per_label, const uint32_t *dev_labels, uint64_t *dev_out, hipStream_t stream);
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                        uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr, uint32_t *out_labels = nullptr);
 // the batch launch of that merge (vg_multi_grouped.hip): workgroup n merges query n's `nlists` lists ([nq][nlists][64] keys at dev_cand) and writes its 64

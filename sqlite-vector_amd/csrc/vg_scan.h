@@ -33,6 +33,11 @@
 //                    The workgroup's lists merge through the same routine (vg_block_publish_grouped) and leave as keys only: a key's
 //                    label is labels[position], gathered again by the final merge (vg_merge_grouped_kernel).  Not combined with
 //                    EX, WITHIN or AFTER; no store mode.
+//   VG_SQ_CAPPED     capped scans (vg_scan_capped.hip; set together with VG_SQ_GROUPED, with and without VG_SQ_MASKED): the k nearest
+//                    rows, at most m = ScanArgs.within_cap of one label (a field that is dead here, like within_r: ScanArgs keeps its
+//                    size).  Every statement of the grouped form stands - the label load, the scheduling barrier, row 0 standing in -
+//                    except the two that touch the list: the offer is vg_list_offer_capped and the workgroup merge
+//                    vg_block_publish_capped; the final merge is vg_merge_capped_kernel.
 // The streaming loop was four hand-copied loops and the offer a ladder of seven branches; the code generated for every instance of
 // the two templates was checked identical to that of the copies it replaced (instruction text, registers, spills, scratch, LDS:
 // DESIGN.md 3.6) at the commit that folded them.
@@ -91,6 +96,27 @@ __device__ inline void vg_block_publish_grouped(uint8_t *smem, uint64_t mine, ui
     if (dst_labels) dst_labels[lane] = (lane < k) ? mlab : 0xFFFFFFFFu;
 }
 
+// The capped counterpart (VG_SQ_CAPPED): the same statements with the cap m handed to the offer - wavefront 0 re-offers the other
+// wavefronts' first k entries through vg_list_offer_capped.  A routine of its own: the grouped one, and every kernel that calls
+// it, keeps its code.
+__device__ inline void vg_block_publish_capped(uint8_t *smem, uint64_t mine, uint32_t mlab, int k, int m, int nwaves, uint64_t *dst, uint32_t *dst_labels) {
+    const int lane = threadIdx.x & (VG_WAVE - 1);
+    const int wave = threadIdx.x >> 6;
+    uint64_t *lists = reinterpret_cast<uint64_t *>(smem);
+    uint32_t *labs = reinterpret_cast<uint32_t *>(smem + (size_t)nwaves * VG_WAVE * 8);
+    lists[wave * VG_WAVE + lane] = (lane < k) ? mine : VG_EMPTY_KEY;
+    labs[wave * VG_WAVE + lane] = mlab;
+    __syncthreads();
+    if (wave != 0) return;
+    uint64_t thr = vg_readlane64(mine, k - 1);
+    for (int w = 1; w < nwaves; ++w) {
+        const uint64_t key = lists[w * VG_WAVE + lane];
+        vg_list_offer_capped(key, labs[w * VG_WAVE + lane], key != VG_EMPTY_KEY, mine, mlab, thr, lane, k, m);
+    }
+    dst[lane] = (lane < k) ? mine : VG_EMPTY_KEY;
+    if (dst_labels) dst_labels[lane] = (lane < k) ? mlab : 0xFFFFFFFFu;
+}
+
 typedef uint32_t vg_u32x4 __attribute__((ext_vector_type(4)));
 
 // NT = true streams the corpus with non-temporal loads (global_load_dwordx4 ... nt): every byte is read exactly
@@ -143,7 +169,7 @@ __device__ inline void vg_load_batch(uint4 (&dst)[U], const uint8_t *rows, long 
 #define VG_STORE_FLOATS 1024          // store mode: distances parked in LDS per wavefront between bursts of stores
 
 // the forms of vg_scan_kernel / vg_scan_long_kernel (the head of this file); the first three have the values of VG_MQ_*
-enum : int { VG_SQ_MASKED = 1, VG_SQ_AFTER = 2, VG_SQ_WITHIN = 4, VG_SQ_EX = 8, VG_SQ_GROUPED = 16 };
+enum : int { VG_SQ_MASKED = 1, VG_SQ_AFTER = 2, VG_SQ_WITHIN = 4, VG_SQ_EX = 8, VG_SQ_GROUPED = 16, VG_SQ_CAPPED = 32 };
 
 // ---- VG_SQ_WITHIN: the keys of the rows within the radius are parked in a per-wavefront LDS queue and leave in bursts - one atomicAdd of the burst size by one lane, then coalesced 8-byte-per-lane stores.
 // A store (and the atomic's return) shares vmcnt with the batch prefetch, see the store-mode note in vg_scan_kernel: a burst of 64+
@@ -185,10 +211,11 @@ __device__ inline uint64_t vg_mask_bits(const uint64_t *mask, long long row0, in
 template <int VT, int ACC, int U, bool NT, int FORM = 0>      // FORM: VG_SQ_* flags
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
     constexpr bool EX = (FORM & VG_SQ_EX) != 0, WITHIN = (FORM & VG_SQ_WITHIN) != 0, MASKED = (FORM & VG_SQ_MASKED) != 0;
-    constexpr bool AFTER = (FORM & VG_SQ_AFTER) != 0, GROUPED = (FORM & VG_SQ_GROUPED) != 0;
+    constexpr bool AFTER = (FORM & VG_SQ_AFTER) != 0, GROUPED = (FORM & VG_SQ_GROUPED) != 0, CAPPED = (FORM & VG_SQ_CAPPED) != 0;
     static_assert(!EX || FORM == VG_SQ_EX, "the reference-order extras are not combined with the range, masked or paged forms");
     static_assert(!(WITHIN && AFTER), "a range scan has no cursor");
     static_assert(!GROUPED || !(EX || WITHIN || AFTER), "a grouped scan is combined with the mask only");
+    static_assert(!CAPPED || (GROUPED && !(EX || WITHIN || AFTER)), "a capped scan is the grouped form with a cap, combined with the mask only");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ VgListExtras ex;
     const int lane = threadIdx.x & (VG_WAVE - 1);
@@ -346,6 +373,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
         else ok = owner && (!MASKED || ((mbits >> rib) & 1ull)) && (!WITHIN || d <= a.within_r) && (d < INFINITY);
         if constexpr (WITHIN) vg_within_offer(key, ok, wqueue, wqueued, a.emit, a.within_cap, lane);
         else if constexpr (EX) vg_list_offer_ex(key, ok, mine, thr, lane, k, &ex);
+        else if constexpr (CAPPED) vg_list_offer_capped(key, lab_cur, ok && (lab_cur != 0xFFFFFFFFu), mine, mlab, thr, lane, k, (int)a.within_cap);
         else if constexpr (GROUPED) vg_list_offer_grouped(key, lab_cur, ok && (lab_cur != 0xFFFFFFFFu), mine, mlab, thr, lane, k);
         else vg_list_offer(key, ok, mine, thr, lane, k);
     };
@@ -404,7 +432,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 
     // ---- the workgroup's 16 wave lists -> ONE list per CU in HBM (parallel rank-select, vg_lists.h)
     __syncthreads();                                   // everyone is done with the query staging area
-    if constexpr (GROUPED) vg_block_publish_grouped(smem, mine, mlab, k, VG_WAVES_PER_BLOCK, a.cand + (long long)blockIdx.x * VG_WAVE, nullptr);
+    if constexpr (CAPPED) vg_block_publish_capped(smem, mine, mlab, k, (int)a.within_cap, VG_WAVES_PER_BLOCK, a.cand + (long long)blockIdx.x * VG_WAVE, nullptr);
+    else if constexpr (GROUPED) vg_block_publish_grouped(smem, mine, mlab, k, VG_WAVES_PER_BLOCK, a.cand + (long long)blockIdx.x * VG_WAVE, nullptr);
     else vg_block_publish(smem, mine, k, a.cand + (long long)blockIdx.x * VG_WAVE);
 }
 
@@ -415,10 +444,11 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_kernel(ScanArgs a) {
 template <int VT, int ACC, bool NT, int FORM = 0>             // FORM: VG_SQ_* flags, without VG_SQ_EX
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
     constexpr bool WITHIN = (FORM & VG_SQ_WITHIN) != 0, MASKED = (FORM & VG_SQ_MASKED) != 0, AFTER = (FORM & VG_SQ_AFTER) != 0;
-    constexpr bool GROUPED = (FORM & VG_SQ_GROUPED) != 0;
+    constexpr bool GROUPED = (FORM & VG_SQ_GROUPED) != 0, CAPPED = (FORM & VG_SQ_CAPPED) != 0;
     static_assert(!(FORM & VG_SQ_EX), "a long-row scan neither emits nor stores a prefix");
     static_assert(!(WITHIN && AFTER), "a range scan has no cursor");
     static_assert(!GROUPED || !(WITHIN || AFTER), "a grouped scan is combined with the mask only");
+    static_assert(!CAPPED || (GROUPED && !(WITHIN || AFTER)), "a capped scan is the grouped form with a cap, combined with the mask only");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
     const int wave = threadIdx.x >> 6;
@@ -527,6 +557,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
                 if constexpr (AFTER) ok = (lane == 0) && (d < INFINITY) && (key >= floor_key);
                 else ok = (lane == 0) && (!WITHIN || d <= a.within_r) && (d < INFINITY);
                 if constexpr (WITHIN) vg_within_offer(key, ok, wqueue, wqueued, a.emit, a.within_cap, lane);
+                else if constexpr (CAPPED) vg_list_offer_capped(key, lab_cur, ok && (lab_cur != 0xFFFFFFFFu), mine, mlab, thr, lane, k, (int)a.within_cap);
                 else if constexpr (GROUPED) vg_list_offer_grouped(key, lab_cur, ok && (lab_cur != 0xFFFFFFFFu), mine, mlab, thr, lane, k);
                 else vg_list_offer(key, ok, mine, thr, lane, k);
             }
@@ -548,7 +579,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_long_kernel(ScanArgs a) {
     if (store_mode) return;
 
     __syncthreads();                                   // everyone is done with the query staging area
-    if constexpr (GROUPED) vg_block_publish_grouped(smem, mine, mlab, k, VG_WAVES_PER_BLOCK, a.cand + (long long)blockIdx.x * VG_WAVE, nullptr);
+    if constexpr (CAPPED) vg_block_publish_capped(smem, mine, mlab, k, (int)a.within_cap, VG_WAVES_PER_BLOCK, a.cand + (long long)blockIdx.x * VG_WAVE, nullptr);
+    else if constexpr (GROUPED) vg_block_publish_grouped(smem, mine, mlab, k, VG_WAVES_PER_BLOCK, a.cand + (long long)blockIdx.x * VG_WAVE, nullptr);
     else vg_block_publish(smem, mine, k, a.cand + (long long)blockIdx.x * VG_WAVE);
 }
 

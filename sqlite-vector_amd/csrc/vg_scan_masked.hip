@@ -84,7 +84,9 @@ extern "C" int64_t vg_corpus_mask_count(const vg_corpus *c) { return c ? c->mask
 // One routine for every fused top-k variant that differs from the masked scan only in its kernel table and a ScanArgs field (3.11 of
 // DESIGN.md): VgFusedForm names the table, whether ScanArgs.mask is set (and a mask required) and whether ScanArgs.floor is (the paged
 // scans of vg_scan_after.hip; the floor key travels in the 8 bytes behind the query, one upload) and whether the scan is grouped (the
-// grouped scans of vg_scan_grouped.hip: ScanArgs.labels, the label-deduping merge, labels in the result).
+// grouped scans of vg_scan_grouped.hip: ScanArgs.labels, the label-deduping merge, labels in the result) or capped (the capped scans
+// of vg_scan_capped.hip: a grouped form whose per_label is set - the cap in ScanArgs.within_cap, which no top-k kernel reads, and the
+// capped merge).
 // the form's kernel + the plain scan's merge; the k winners land in the pinned c->h_keys (copied behind the merge)
 static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     int acc = vg_metric_to_acc(metric);
@@ -102,13 +104,16 @@ static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     if (f.labeled) a.mask = c->d_label_bits;                 // (the bitmap of one label, built on this stream in front of the scan)
     if (f.after) a.floor = reinterpret_cast<const uint64_t *>(c->d_query + c->stride);
     if (f.grouped) a.labels = c->d_labels;
+    const int cap = std::min(f.per_label, k);               // (capped forms: more than k of one label cannot be returned)
+    if (cap > 0) a.within_cap = (unsigned long long)cap;
     const size_t smem = std::max<size_t>(vg_query_lds_bytes(c, s), (size_t)VG_PUBLISH_LDS_BYTES);
 
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);
     if (evs) hipEventRecord(evs[0], c->stream);
     if ((rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a)) != VG_OK) return rc;
     if (evs) hipEventRecord(evs[2], c->stream);
-    int rcm = f.grouped ? vg_launch_merge_grouped(c->d_cand, (int)blocks, k, c->d_labels, c->d_keys, c->stream)
+    int rcm = cap > 0   ? vg_launch_merge_capped(c->d_cand, (int)blocks, k, cap, c->d_labels, c->d_keys, c->stream)
+              : f.grouped ? vg_launch_merge_grouped(c->d_cand, (int)blocks, k, c->d_labels, c->d_keys, c->stream)
                         : vg_launch_merge_one(c->d_cand, (int)blocks, k, c->d_keys, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
     if (rcm != 0) return vg_fail(VG_ERR_HIP, "%s: merge launch failed: %s", f.who, hipGetErrorString((hipError_t)rcm));
@@ -125,7 +130,7 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
     if (!c || !query || !out_count) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     *out_count = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.grouped ? "grouped" : f.labeled ? "labeled" : f.masked ? "masked" : "paged");
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.per_label > 0 ? "capped" : f.grouped ? "grouped" : f.labeled ? "labeled" : f.masked ? "masked" : "paged");
     if (!out_keys || (f.grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);

@@ -1315,6 +1315,60 @@ extern "C" int vg_shards_scan_topk_batch_grouped_masked(vg_shards *s, int metric
     return shards_grouped_batch(s, true, metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts);
 }
 
+// ---- capped scans: shards_grouped with the cap - every shard answers over its own rows (its capped top-k), the lists merge through
+// vg_merge_keys_capped over GLOBAL scan positions: a row of the answer over all rows is in the capped top-k of its own shard
+// (DESIGN.md 3.17), so the union of the shards' lists holds the answer and the merge selects it
+static int shards_capped(vg_shards *s, bool masked, int metric, const void *query, int k, int per_label, int64_t *out_rowids, double *out_dist,
+                         uint32_t *out_labels, int *out_count) {
+    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_capped: NULL argument");
+    if (s->S == 1) return masked ? vg_scan_topk_capped_masked(s->sh[0], metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count)
+                                 : vg_scan_topk_capped(s->sh[0], metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
+    *out_count = 0;
+    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_capped: k must be at least 1");
+    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_capped: k must be in 1..64 (capped scans use the fused list only)");
+    if (per_label < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_capped: per_label must be at least 1");
+    if (!out_rowids || !out_dist || !out_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_capped: NULL output");
+    if (masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_topk_capped_masked: no row mask set");
+    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_capped: no labels set");
+    if (s->n_rows > 0xFFFFFFFFll) return fail(VG_ERR_UNSUPPORTED, "vg_shards_scan_topk_capped: more than 2^32 - 1 rows over all shards");
+    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
+    std::vector<uint32_t> labels((size_t)s->S * VG_WAVE_KEYS, VG_LABEL_NONE);
+    std::vector<int> counts((size_t)s->S, 0);
+    auto scan = masked ? vg_scan_topk_capped_masked_keys : vg_scan_topk_capped_keys;
+    int rc = for_each_shard(s, [&](int i) {
+        return scan(s->sh[(size_t)i], metric, query, k, per_label, &keys[(size_t)i * VG_WAVE_KEYS], &labels[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]);
+    });
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < s->S; ++i)                           // local positions -> global ones (a shard's list stays ascending: the map is monotonic)
+        for (int j = 0; j < counts[(size_t)i]; ++j) {
+            uint64_t &key = keys[(size_t)i * VG_WAVE_KEYS + j];
+            key = (key & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(key));
+        }
+    uint64_t gkeys[VG_WAVE_KEYS];
+    uint32_t glabels[VG_WAVE_KEYS];
+    int cnt = 0;
+    rc = vg_merge_keys_capped(keys.data(), labels.data(), s->S, VG_WAVE_KEYS, nullptr, k, per_label, gkeys, glabels, &cnt);
+    if (rc != VG_OK) return fail(rc, vg_last_error());
+    for (int i = 0; i < cnt; ++i) {
+        int shard;
+        int64_t local;
+        locate(s, (int64_t)vg_key_position(gkeys[i]), &shard, &local);
+        out_dist[i] = (double)vg_key_distance(gkeys[i]);
+        out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
+        out_labels[i] = glabels[i];
+    }
+    *out_count = cnt;
+    return VG_OK;
+}
+extern "C" int vg_shards_scan_topk_capped(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t *out_rowids,
+                                          double *out_dist, uint32_t *out_labels, int *out_count) {
+    return shards_capped(s, false, metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
+}
+extern "C" int vg_shards_scan_topk_capped_masked(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t *out_rowids,
+                                                 double *out_dist, uint32_t *out_labels, int *out_count) {
+    return shards_capped(s, true, metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
+}
+
 extern "C" int vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
                                                  int64_t *out_rowids, double *out_dist, int *out_counts) {
     if (!s || !queries || !out_counts || !query_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labeled: NULL argument");
