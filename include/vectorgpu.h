@@ -351,7 +351,7 @@ int     vg_scan_topk_batch_grouped_masked_keys(vg_corpus *c, int metric, const v
  * 1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below); per_label < 1: VG_ERR_INVALID; no labels set: VG_ERR_INVALID; the
  * masked forms without a mask: VG_ERR_INVALID; NULL arguments: VG_ERR_INVALID; an empty corpus or an empty mask: *out_count = 0,
  * nothing is launched.  Not served, like the grouped scans: f16 corpora with rows of 2049 .. 3072 elements under the cosine and dot
- * metrics (VG_ERR_UNSUPPORTED; L2 and L1 are served).  No batch form and no SQL function yet.
+ * metrics (VG_ERR_UNSUPPORTED; L2 and L1 are served).  The batch form: vg_scan_topk_batch_capped, below; no SQL function yet.
  * The _keys forms return packed keys with positions local to this corpus (out_keys[k], out_labels[k]).
  * vg_merge_keys_capped (host): vg_merge_keys_grouped with the cap, for lists of several corpora that are each a capped answer with
  * the same k and per_label - the four steps over the union, by (distance, global position); same layout, offsets and errors, and
@@ -366,6 +366,34 @@ int     vg_scan_topk_capped_masked_keys(vg_corpus *c, int metric, const void *qu
                                         uint64_t *out_keys, uint32_t *out_labels, int *out_count);
 int     vg_merge_keys_capped(const uint64_t *keys, const uint32_t *labels, int n_lists, int list_len, const int64_t *pos_offsets, int k,
                              int per_label, uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+
+/* ---- capped batch scans: the k nearest rows, at most per_label of one label, for each of nq queries (row-major nq x dim, host) -
+ * "the 20 nearest chunks, no more than 3 of any document, for these 64 requests".  Query i's answer is exactly what
+ * vg_scan_topk_capped (the _masked forms: vg_scan_topk_capped_masked) is contracted to return for query i alone - the four steps
+ * above; one per_label = m covers the whole batch, m above k behaves as k, and m = 1 returns what vg_scan_topk_batch_grouped returns,
+ * bit for bit.  out_rowids / out_dist / out_labels are nq x k, out_counts nq; the slots of query i behind out_counts[i] are NOT
+ * written.
+ * f32 / uint8 / int8 rows of a register-resident shape: the grouped batch's passes - 4 queries (2 where a lane holds 4 or 6 chunks
+ * of the row) share every row load and every label load (vg_scan_multi.h, capped form; the plan: vg_batch_capped_plan,
+ * vectorgpu_diag.h) - each query keeps its own capped list, and the lists of a query merge on the device; one copy of keys and
+ * labels, one wait.  uint8 / int8: rowids, labels, order and distance bits identical to nq vg_scan_topk_capped calls; f32: the floats
+ * of vg_scan_topk_batch_masked under the same launch shape.  f16 / bf16, long rows and every other shape without a multi-query form
+ * (the masked forms only: also rows of 193 .. 384 16-byte chunks under cosine, and under L2 for f32 - DESIGN.md 3.18): one single
+ * capped scan per query - a shape that scan refuses (f16 cosine / dot over rows of 2049 .. 3072 elements) is VG_ERR_UNSUPPORTED here
+ * too.
+ * nq < 1 or a NULL argument: VG_ERR_INVALID, answered before the handle is read; k < 1 or per_label < 1: VG_ERR_INVALID, k > 64:
+ * VG_ERR_UNSUPPORTED, with the counts zeroed first; no labels set: VG_ERR_INVALID; the masked forms without a mask: VG_ERR_INVALID; an
+ * empty corpus or an empty mask: every count 0, nothing is launched.  No cap per query and no SQL function.  The _keys forms return
+ * packed keys with positions local to this corpus (out_keys and out_labels nq x k) - the form a multi-shard caller merges per query
+ * with vg_merge_keys_capped. */
+int     vg_scan_topk_batch_capped(vg_corpus *c, int metric, const void *queries, int nq, int k, int per_label,
+                                  int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
+int     vg_scan_topk_batch_capped_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, int per_label,
+                                       uint64_t *out_keys, uint32_t *out_labels, int *out_counts);
+int     vg_scan_topk_batch_capped_masked(vg_corpus *c, int metric, const void *queries, int nq, int k, int per_label,
+                                         int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
+int     vg_scan_topk_batch_capped_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, int per_label,
+                                              uint64_t *out_keys, uint32_t *out_labels, int *out_counts);
 
 /* ---- masked range scans: every ALLOWED row within a distance of the query - "every row of this tenant within r", near-duplicate
  * detection inside one category (no reference entry point; the reference's form is "SELECT ... FROM vector_full_scan_stream(...)
@@ -559,6 +587,12 @@ int     vg_shards_scan_topk_capped(vg_shards *s, int metric, const void *query, 
                                    int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
 int     vg_shards_scan_topk_capped_masked(vg_shards *s, int metric, const void *query, int k, int per_label,
                                           int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+/* vg_scan_topk_batch_capped[_masked] over every shard: each shard answers all nq queries over its own rows, then every query's
+ * lists merge through vg_merge_keys_capped as above.  Same contract and errors. */
+int     vg_shards_scan_topk_batch_capped(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label,
+                                         int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
+int     vg_shards_scan_topk_batch_capped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label,
+                                                int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
 /* the masked range scans over every shard: each shard answers over its own bits (a shard whose share of the mask is empty launches
  * nothing and contributes nothing), merged like vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus
  * holding all rows.  Same contract; the results are read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and

@@ -63,6 +63,9 @@ int vg_batch_labeled_plan(const vg_corpus *c, int metric, int *out_queries_per_p
  * multi-query scan (4 or 2; 0 = the fallback, one single grouped scan per query) and the launch shape of the kernel that runs.  Pure
  * host logic. */
 int vg_batch_grouped_plan(const vg_corpus *c, int metric, int masked, int *out_queries_per_pass, int *out_lpr, int *out_u);
+/* the same for vg_scan_topk_batch_capped (masked != 0: vg_scan_topk_batch_capped_masked): queries per pass of the capped multi-query
+ * scan (4 or 2; 0 = the fallback, one single capped scan per query) and the launch shape of the kernel that runs.  Pure host logic. */
+int vg_batch_capped_plan(const vg_corpus *c, int metric, int masked, int *out_queries_per_pass, int *out_lpr, int *out_u);
 /* the floor key of a paged scan (vg_scan_topk_after, vectorgpu.h): the smallest key behind a cursor whose distance is after_dist, when
  * the rows at scan positions < first_pos_behind are not behind it at that distance (P = rows held with rowid <= after_rowid).  f = the
  * smallest float >= after_dist (the double rounded towards +Inf, -0.0 normalised to 0.0): floor = key(f, first_pos_behind) when

@@ -235,6 +235,14 @@ def _load():
         "vg_merge_keys_capped": (i32, [vp, vp, i32, i32, vp, i32, i32, vp, vp, C.POINTER(i32)]),
         "vg_shards_scan_topk_capped": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, C.POINTER(i32)]),
         "vg_shards_scan_topk_capped_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, C.POINTER(i32)]),
+        # capped batch scans: the same for many queries, in shared passes
+        "vg_scan_topk_batch_capped": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "vg_scan_topk_batch_capped_keys": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp]),
+        "vg_scan_topk_batch_capped_masked": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "vg_scan_topk_batch_capped_masked_keys": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp]),
+        "vg_shards_scan_topk_batch_capped": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "vg_shards_scan_topk_batch_capped_masked": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "vg_batch_capped_plan": (i32, [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
         "vg_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
         "vg_scan_within_batch_keys": (i32, [vp, i32, i64, i64, vp]),
@@ -413,6 +421,27 @@ class _GroupedOps:
         fn = getattr(lib(), self._sprefix + "scan_topk_capped" + ("_masked" if masked else ""))
         _check(fn(self.h, metric, _ptr(query), k, per_label, _ptr(ids), _ptr(dist), _ptr(lab), C.byref(cnt)))
         return ids[:cnt.value], dist[:cnt.value], lab[:cnt.value]
+
+    def scan_topk_batch_capped(self, metric, queries, k, per_label, masked=False):
+        """scan_topk_capped for every row of `queries`, in shared passes, one `per_label` for the whole batch: (rowids [nq, k],
+        distances [nq, k], labels [nq, k], counts [nq]); the slots of query i behind counts[i] are not written"""
+        queries = np.ascontiguousarray(queries)
+        nq = queries.shape[0]
+        ids = np.zeros((nq, max(k, 1)), dtype=np.int64)
+        dist = np.zeros((nq, max(k, 1)), dtype=np.float64)
+        lab = np.zeros((nq, max(k, 1)), dtype=np.uint32)
+        cnt = np.zeros(max(nq, 1), dtype=np.int32)
+        fn = getattr(lib(), self._sprefix + "scan_topk_batch_capped" + ("_masked" if masked else ""))
+        _check(fn(self.h, metric, _ptr(queries), nq, k, per_label, _ptr(ids), _ptr(dist), _ptr(lab), _ptr(cnt)))
+        return ids, dist, lab, cnt[:nq]
+
+
+def batch_capped_plan(corpus, metric, masked=False):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_topk_batch_capped serves this corpus with; 0 queries per pass =
+    one single capped scan per query (f16 / bf16, long rows, an instance left out of the table) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().vg_batch_capped_plan(corpus.h, metric, 1 if masked else 0, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
 
 
 def batch_grouped_plan(corpus, metric, masked=False):

@@ -340,6 +340,13 @@ int vg_launch_merge_grouped_batch(const uint64_t *dev_cand, int nlists, int k, c
 scan_fn_t vg_pick_scan_grouped(int vtype, int acc, int U, bool long_rows);          // vg_scan_grouped.hip: the grouped single scans' tables,
 scan_fn_t vg_pick_scan_grouped_masked(int vtype, int acc, int U, bool long_rows);   // ... all rows / the allowed rows
 scan_fn_t vg_pick_multi_grouped_masked(int vtype, int acc, int U, int NQ);          // vg_multi_grouped_masked.hip: the masked grouped batch's table
+// the capped batch (vg_multi_capped.hip): a grouped VgFusedBatchForm whose `single.per_label` is set - vg_fused_batch_run then puts the
+// cap, clamped to k, into ScanArgs.within_cap and ends every pass in this merge in place of the grouped batch's; the rest is that path
+int vg_launch_merge_capped_batch(const uint64_t *dev_cand, int nlists, int k, int per_label, const uint32_t *dev_labels, uint64_t *dev_out, int nq,
+                                 hipStream_t stream);
+scan_fn_t vg_pick_scan_capped(int vtype, int acc, int U, bool long_rows);           // vg_scan_capped.hip: the capped single scans' tables,
+scan_fn_t vg_pick_scan_capped_masked(int vtype, int acc, int U, bool long_rows);    // ... all rows / the allowed rows
+scan_fn_t vg_pick_multi_capped_masked(int vtype, int acc, int U, int NQ);           // vg_multi_capped_masked.hip: the masked capped batch's table
 // ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): the floor-key forms behind the C ABI, what the shards call per shard.
 // Floors are keys over positions LOCAL to the corpus; a floor of VG_KEY_EMPTY admits nothing (no launch in the single form).
 int vg_after_floor_run(vg_corpus *c, bool masked, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count);

@@ -24,6 +24,7 @@ static scan_fn_t pick_multi_grouped_masked(int vtype, int acc, int U, int NQ) { 
 // [NQ][nlists][64] keys - and writes 64 keys, then 64 labels, at its own offset (VG_KEYS_BYTES per query).  The same statements
 // behind two offsets, in a kernel of its own: the single-query kernel keeps its grid of 1, its output layout and its code.
 // Two bodies to keep in step: a change to the statements below belongs in vg_merge_grouped_kernel too, and the other way round.
+// (vg_merge_capped_batch_kernel, vg_multi_capped.hip, is these statements with the cap handed to the list routines: a third one)
 #define VG_GMERGE_BATCH_PER_WAVE (VG_SEL_MAX_HEADS / VG_WAVES_PER_BLOCK)
 __global__ __launch_bounds__(VG_BLOCK) void vg_merge_grouped_batch_kernel(const uint64_t *cand, int nlists, int k, const uint32_t *labels, uint64_t *out) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[VG_WAVES_PER_BLOCK * VG_WAVE * 12];

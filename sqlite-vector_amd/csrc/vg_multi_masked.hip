@@ -37,7 +37,9 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
 // NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on the corpus stream.  One launcher for every form
 // (VgFusedBatchForm, vg_internal.h): the masked batch, and the paged batches of vg_multi_after.hip (dev_floors: NQ keys).
 // A grouped form (vg_multi_grouped.hip): the lists merge through the label-deduping merge and dev_out_keys receives, per query, 64
-// keys followed by their 64 labels (VG_KEYS_BYTES).
+// keys followed by their 64 labels (VG_KEYS_BYTES).  A capped form (vg_multi_capped.hip: grouped, with single.per_label set): the
+// cap, clamped to k, travels in ScanArgs.within_cap - which no other top-k instance reads - and the lists merge through the capped
+// batch merge; everything else is the grouped form's.
 static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s,
                                const uint8_t *dev_queries, const uint64_t *dev_floors, const uint32_t *dev_qlabels, int k, uint64_t *dev_cand,
                                uint64_t *dev_out_keys) {
@@ -48,14 +50,17 @@ static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metri
     if (f.single.after) a.floor = dev_floors;
     if (f.single.labeled) { a.labels = c->d_labels; a.qlabels = dev_qlabels; }
     if (f.single.grouped) a.labels = c->d_labels;
+    const int cap = std::min(f.single.per_label, k);          // (capped forms: more than k of one label cannot be returned)
+    if (cap > 0) a.within_cap = (unsigned long long)cap;
     const size_t smem = std::max<size_t>((size_t)NQ * c->nch * 16, (size_t)VG_PUBLISH_LDS_BYTES);
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);          // one slot of the profiling ring per pass
     if (evs) hipEventRecord(evs[0], c->stream);
     int rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a);
     if (rc != VG_OK) return rc;
     if (evs) hipEventRecord(evs[2], c->stream);
-    rc = f.single.grouped ? vg_launch_merge_grouped_batch(dev_cand, (int)blocks, k, c->d_labels, dev_out_keys, NQ, c->stream)
-                          : vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
+    rc = cap > 0          ? vg_launch_merge_capped_batch(dev_cand, (int)blocks, k, cap, c->d_labels, dev_out_keys, NQ, c->stream)
+         : f.single.grouped ? vg_launch_merge_grouped_batch(dev_cand, (int)blocks, k, c->d_labels, dev_out_keys, NQ, c->stream)
+                            : vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
     if (rc != 0) return vg_fail(VG_ERR_HIP, "%s: merge launch failed: %s", f.who, hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipGetLastError());
@@ -136,7 +141,7 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
     if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", f.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.grouped ? "grouped" : f.single.labeled ? "labeled" : f.single.masked ? "masked" : "paged");
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.per_label > 0 ? "capped" : f.single.grouped ? "grouped" : f.single.labeled ? "labeled" : f.single.masked ? "masked" : "paged");
     if (!out_keys || (f.single.grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (f.single.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);

@@ -26,11 +26,11 @@
 static bool capped_shape_spills(int vtype, int acc, int U, bool long_rows) {
     return vtype == VG_TYPE_F16 && U == 6 && !long_rows && (acc == A_COS || acc == A_COSN || acc == A_DOT);
 }
-static scan_fn_t pick_scan_capped(int vtype, int acc, int U, bool long_rows) {
+scan_fn_t vg_pick_scan_capped(int vtype, int acc, int U, bool long_rows) {
     if (capped_shape_spills(vtype, acc, U, long_rows)) return nullptr;
     return vg_pick_scan<ScanFamily<VG_SQ_GROUPED | VG_SQ_CAPPED, true, true>>(vtype, acc, U, long_rows);
 }
-static scan_fn_t pick_scan_capped_masked(int vtype, int acc, int U, bool long_rows) {
+scan_fn_t vg_pick_scan_capped_masked(int vtype, int acc, int U, bool long_rows) {
     if (capped_shape_spills(vtype, acc, U, long_rows)) return nullptr;
     return vg_pick_scan<ScanFamily<VG_SQ_GROUPED | VG_SQ_CAPPED | VG_SQ_MASKED, true, true>>(vtype, acc, U, long_rows);
 }
@@ -41,6 +41,7 @@ static scan_fn_t pick_scan_capped_masked(int vtype, int acc, int U, bool long_ro
 // keys, wavefront w takes lists w, w + 16, ... - all their keys first, then all their labels - offers them list by list to its own
 // capped list, and the 16 lists merge through LDS like a scan workgroup's (vg_block_publish_capped).  out: 64 keys, then 64 labels.
 // A kernel of its own, not a parameter of the grouped one: sharing a body moved that kernel's code.
+// (vg_merge_capped_batch_kernel, vg_multi_capped.hip, is these statements behind a per-query offset: a change here belongs there too)
 #define VG_CMERGE_PER_WAVE (VG_SEL_MAX_HEADS / VG_WAVES_PER_BLOCK)
 __global__ __launch_bounds__(VG_BLOCK) void vg_merge_capped_kernel(const uint64_t *cand, int nlists, int k, int m, const uint32_t *labels, uint64_t *out) {
     __shared__ __attribute__((aligned(16))) uint8_t smem[VG_WAVES_PER_BLOCK * VG_WAVE * 12];
@@ -71,8 +72,8 @@ int vg_launch_merge_capped(const uint64_t *dev_cand, int nlists, int k, int per_
 // ------------------------------------------------------------------------------------------------ the scans
 
 static VgFusedForm capped_form(bool masked, int per_label) {
-    if (masked) return VgFusedForm{"vg_scan_topk_capped_masked", pick_scan_capped_masked, true, false, false, true, per_label};
-    return VgFusedForm{"vg_scan_topk_capped", pick_scan_capped, false, false, false, true, per_label};
+    if (masked) return VgFusedForm{"vg_scan_topk_capped_masked", vg_pick_scan_capped_masked, true, false, false, true, per_label};
+    return VgFusedForm{"vg_scan_topk_capped", vg_pick_scan_capped, false, false, false, true, per_label};
 }
 
 static int capped_keys(vg_corpus *c, bool masked, int metric, const void *query, int k, int per_label, uint64_t *out_keys, uint32_t *out_labels,

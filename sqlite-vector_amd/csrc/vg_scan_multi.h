@@ -56,6 +56,13 @@
 //                    (vg_list_offer_grouped).  A row without a label is offered to no query.  The pad queries of a ragged pass
 //                    collect whatever they collect; their lists are never read.  Lists leave as keys only
 //                    (vg_block_publish_grouped), merged per query by vg_merge_grouped_batch_kernel (vg_multi_grouped.hip, grid NQ).
+//   VG_MQ_CAPPED     the k nearest ROWS per query, at most m = ScanArgs.within_cap of one label (the batch form of VG_SQ_CAPPED,
+//                    vg_scan.h; vg_multi_capped.hip).  A modifier of VG_MQ_GROUPED: legal only together with it, alone or with
+//                    VG_MQ_MASKED.  Every statement of the grouped form stands - the label load behind the row prefetch, the
+//                    scheduling barrier, row 0 standing in, the mlab registers - except the two that touch a list: the offer is
+//                    vg_list_offer_capped and the workgroup merge vg_block_publish_capped.  m is wave-uniform, clamped to k by the
+//                    host and shared by the NQ queries of a pass; within_cap is read by no other top-k instance of this kernel, so
+//                    ScanArgs keeps its size.  Lists merge per query in vg_merge_capped_batch_kernel (vg_multi_capped.hip, grid NQ).
 // The forms were five hand-copied loops; the code generated for every instance of this template was checked identical to that of the
 // copy it replaced (instruction text, registers, spills, scratch, LDS: DESIGN.md 3.6) at the commit that folded them.
 //
@@ -63,6 +70,7 @@
 //   a.mask          : (MASKED) ceil(n_rows / 64) words, bits behind the last row clear
 //   a.floor         : (AFTER) NQ keys
 //   a.labels        : (LABELED, GROUPED) n_rows dwords;  a.qlabels : (LABELED) NQ dwords
+//   a.within_cap    : (CAPPED) the cap m, 1 .. k
 //   a.cand          : (top-k forms) [NQ][gridDim.x][64] candidate keys
 //   descriptor n    : (WITHIN) the [count | cap keys] region of query n, its capacity and its radius (a float: the host rounds down)
 //   a.store_lds_off : (WITHIN) byte offset in dynamic LDS of the key queues, [NQ][wavefront][VG_WITHIN_QUEUE]
@@ -74,7 +82,7 @@
 
 #include "vg_scan.h"
 
-enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4, VG_MQ_LABELED = 8, VG_MQ_GROUPED = 16 };
+enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4, VG_MQ_LABELED = 8, VG_MQ_GROUPED = 16, VG_MQ_CAPPED = 32 };
 #define VG_MQ_LABEL_NONE 0xFFFFFFFFu      // (VG_LABEL_NONE of vectorgpu.h)
 
 struct VgWithinQuery {                 // 32 bytes, read through wave-uniform addresses (scalar loads)
@@ -110,10 +118,11 @@ __device__ inline void vg_mw_offer(uint64_t key, bool match, uint64_t *queue, in
 template <int VT, int ACC, int U, int NQ, int FORM>          // VT: T_F32 / T_U8 / T_I8; FORM: VG_MQ_* flags
 __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
     constexpr bool MASKED = (FORM & VG_MQ_MASKED) != 0, AFTER = (FORM & VG_MQ_AFTER) != 0, WITHIN = (FORM & VG_MQ_WITHIN) != 0;
-    constexpr bool LABELED = (FORM & VG_MQ_LABELED) != 0, GROUPED = (FORM & VG_MQ_GROUPED) != 0;
+    constexpr bool LABELED = (FORM & VG_MQ_LABELED) != 0, GROUPED = (FORM & VG_MQ_GROUPED) != 0, CAPPED = (FORM & VG_MQ_CAPPED) != 0;
     static_assert(!(AFTER && WITHIN), "a range scan has no cursor");
     static_assert(!LABELED || FORM == VG_MQ_LABELED, "the labeled form is not combined with the masked, paged or range forms");
-    static_assert(!GROUPED || (FORM & ~VG_MQ_MASKED) == VG_MQ_GROUPED, "the grouped form is combined with the mask only");
+    static_assert(!GROUPED || (FORM & ~(VG_MQ_MASKED | VG_MQ_CAPPED)) == VG_MQ_GROUPED, "the grouped form is combined with the mask and the cap only");
+    static_assert(!CAPPED || GROUPED, "a capped scan is the grouped form with a cap");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
     // (WITHIN: wave-uniform by construction; readfirstlane says so to the compiler, and the queue addresses stay scalar)
@@ -236,7 +245,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
                     // (a top-k form uses the distance at once, NOT through d[]: with it the ten f32 L1 floor instances came out with
                     //  another, equivalent, predicate sequence than the copies had)
                     const uint64_t key = vg_make_key(dn, (uint32_t)row);
-                    if constexpr (GROUPED) vg_list_offer_grouped(key, lcur, owner && (dn < INFINITY) && (lcur != VG_MQ_LABEL_NONE), mine[n], mlab[n], thr[n], lane, k);
+                    if constexpr (CAPPED) vg_list_offer_capped(key, lcur, owner && (dn < INFINITY) && (lcur != VG_MQ_LABEL_NONE), mine[n], mlab[n], thr[n], lane, k, (int)a.within_cap);
+                    else if constexpr (GROUPED) vg_list_offer_grouped(key, lcur, owner && (dn < INFINITY) && (lcur != VG_MQ_LABEL_NONE), mine[n], mlab[n], thr[n], lane, k);
                     else if constexpr (LABELED) vg_list_offer(key, owner && (dn < INFINITY) && (lcur == qlabel[n]), mine[n], thr[n], lane, k);
                     else vg_list_offer(key, owner && (dn < INFINITY) && (!AFTER || key >= floor_key[n]), mine[n], thr[n], lane, k);
                 }
@@ -268,7 +278,8 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
             if (queued[n] > 0) vg_mw_flush(queue[n], queued[n], wq[n].out, wq[n].cap, lane);
         } else {
             __syncthreads();                               // query staging area / the previous publish is done with LDS
-            if constexpr (GROUPED) vg_block_publish_grouped(smem, mine[n], mlab[n], k, VG_WAVES_PER_BLOCK, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE, nullptr);
+            if constexpr (CAPPED) vg_block_publish_capped(smem, mine[n], mlab[n], k, (int)a.within_cap, VG_WAVES_PER_BLOCK, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE, nullptr);
+            else if constexpr (GROUPED) vg_block_publish_grouped(smem, mine[n], mlab[n], k, VG_WAVES_PER_BLOCK, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE, nullptr);
             else vg_block_publish(smem, mine[n], k, a.cand + ((long long)n * gridDim.x + blockIdx.x) * VG_WAVE);
         }
     }

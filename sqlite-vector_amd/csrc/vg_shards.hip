@@ -1369,6 +1369,68 @@ extern "C" int vg_shards_scan_topk_capped_masked(vg_shards *s, int metric, const
     return shards_capped(s, true, metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
 }
 
+// the batch form: shards_grouped_batch with the cap - every shard answers all nq queries (its capped top-k per query, keys + labels,
+// positions local to it), then query by query the shards' lists are rewritten to global positions and merged through
+// vg_merge_keys_capped like the single form's
+static int shards_capped_batch(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
+                               double *out_dist, uint32_t *out_labels, int *out_counts) {
+    // (every message carries the name of the entry point that was called)
+    const std::string who = masked ? "vg_shards_scan_topk_batch_capped_masked" : "vg_shards_scan_topk_batch_capped";
+    auto refuse = [&](int code, const char *what) { return fail(code, (who + ": " + what).c_str()); };
+    if (!s || !queries || !out_counts) return refuse(VG_ERR_INVALID, "NULL argument");
+    if (s->S == 1) return masked ? vg_scan_topk_batch_capped_masked(s->sh[0], metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts)
+                                 : vg_scan_topk_batch_capped(s->sh[0], metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
+    if (nq < 1) return refuse(VG_ERR_INVALID, "nq must be at least 1");
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k < 1) return refuse(VG_ERR_INVALID, "k must be at least 1");
+    if (k > VG_WAVE_KEYS) return refuse(VG_ERR_UNSUPPORTED, "k must be in 1..64 (capped scans use the fused list only)");
+    if (per_label < 1) return refuse(VG_ERR_INVALID, "per_label must be at least 1");
+    if (!out_rowids || !out_dist || !out_labels) return refuse(VG_ERR_INVALID, "NULL output");
+    if (masked && vg_shards_mask_count(s) < 0) return refuse(VG_ERR_INVALID, "no row mask set");
+    if (!vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, "no labels set");
+    if (s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, "more than 2^32 - 1 rows over all shards");
+    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
+    std::vector<uint32_t> labels((size_t)s->S * nq * k, VG_LABEL_NONE);
+    std::vector<int> counts((size_t)s->S * nq, 0);
+    auto scan = masked ? vg_scan_topk_batch_capped_masked_keys : vg_scan_topk_batch_capped_keys;
+    int rc = for_each_shard(s, [&](int i) {
+        return scan(s->sh[(size_t)i], metric, queries, nq, k, per_label, &keys[(size_t)i * nq * k], &labels[(size_t)i * nq * k], &counts[(size_t)i * nq]);
+    });
+    if (rc != VG_OK) return rc;
+    std::vector<uint64_t> qkeys((size_t)s->S * k), gkeys((size_t)k);
+    std::vector<uint32_t> qlabels((size_t)s->S * k), glabels((size_t)k);
+    for (int q = 0; q < nq; ++q) {
+        for (int i = 0; i < s->S; ++i)                       // local positions -> global ones; slots behind a shard's count: empty
+            for (int j = 0; j < k; ++j) {
+                const size_t src = ((size_t)i * nq + q) * k + j, dst = (size_t)i * k + j;
+                const bool held = j < counts[(size_t)i * nq + q];
+                qkeys[dst] = held ? ((keys[src] & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(keys[src]))) : VG_KEY_EMPTY;
+                qlabels[dst] = held ? labels[src] : VG_LABEL_NONE;
+            }
+        int cnt = 0;
+        rc = vg_merge_keys_capped(qkeys.data(), qlabels.data(), s->S, k, nullptr, k, per_label, gkeys.data(), glabels.data(), &cnt);
+        if (rc != VG_OK) return fail(rc, vg_last_error());
+        for (int j = 0; j < cnt; ++j) {
+            int shard;
+            int64_t local;
+            locate(s, (int64_t)vg_key_position(gkeys[(size_t)j]), &shard, &local);
+            out_dist[(size_t)q * k + j] = (double)vg_key_distance(gkeys[(size_t)j]);
+            out_rowids[(size_t)q * k + j] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
+            out_labels[(size_t)q * k + j] = glabels[(size_t)j];
+        }
+        out_counts[q] = cnt;
+    }
+    return VG_OK;
+}
+extern "C" int vg_shards_scan_topk_batch_capped(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
+                                                double *out_dist, uint32_t *out_labels, int *out_counts) {
+    return shards_capped_batch(s, false, metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
+}
+extern "C" int vg_shards_scan_topk_batch_capped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
+                                                       double *out_dist, uint32_t *out_labels, int *out_counts) {
+    return shards_capped_batch(s, true, metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
+}
+
 extern "C" int vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
                                                  int64_t *out_rowids, double *out_dist, int *out_counts) {
     if (!s || !queries || !out_counts || !query_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labeled: NULL argument");
