@@ -26,10 +26,10 @@ import numpy as np
 import pytest
 
 import capped_cases as cc
+from capped_cases import _judge_f64
 import datagen as dg
 import grouped_cases as gc
 import labeled_cases as lc
-from batch_reference import completeness_tol
 
 pytestmark = pytest.mark.gpu
 
@@ -82,33 +82,6 @@ def _path_distances(pkg, c, vt, metric, qs, masked=False):
         d[ids - 1] = dist.astype(np.float32)
         out.append(d)
     return out
-
-
-def _judge_f64(got, ref, labels, metric, q, k, m, ctx):
-    """one f32 answer against float64 distances of every row: the cap, the count, per-row value, order, and no row left behind that
-    is better than what was returned in its place - each within 1e-5 relative (batch_reference.completeness_tol)"""
-    gi, gd, gl = got
-    _, per = np.unique(labels[labels != gc.NONE], return_counts=True)
-    assert len(gi) == min(k, int(np.minimum(per, m).sum())), ctx
-    pos = gi - 1
-    assert (labels[pos] == gl).all() and len(set(pos.tolist())) == len(pos), ctx
-    kept = dict(zip(*np.unique(gl, return_counts=True)))
-    assert max(kept.values()) <= m, ctx
-    q_l1 = float(np.abs(q.astype(np.float64)).sum())
-    for p, d in zip(pos, gd):
-        assert abs(d - ref[p]) <= completeness_tol(metric, q_l1, ref[p]), (ctx, p, d, ref[p])
-    assert np.all(np.diff(gd) >= 0), ctx
-    out = np.ones(len(labels), dtype=bool)
-    out[pos] = False
-    out &= labels != gc.NONE
-    for l in np.unique(labels[out]):
-        best_left = float(ref[out & (labels == l)].min())
-        if kept.get(l, 0) == m:                                 # a full label: its rows left out are no better than its worst kept row
-            worst = float(gd[gl == l].max())
-            assert best_left >= worst - completeness_tol(metric, q_l1, worst), (ctx, "a full label left a better row out", l)
-        else:                                                   # room under the cap: only a full answer may leave a row out
-            assert len(gi) == k, (ctx, l)
-            assert best_left >= float(gd[-1]) - completeness_tol(metric, q_l1, gd[-1]), (ctx, "a better row left out", l)
 
 
 @pytest.mark.parametrize("vt,dim,per_pass,metrics", lc.SHAPES, ids=lc.SHAPE_IDS)
