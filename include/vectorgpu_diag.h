@@ -51,6 +51,10 @@ int vg_batch_last_path(const vg_corpus *c);
 /* how this corpus' last attempt at the int8 batch filter ended: 0 it answered, 1 no room for the tile-major int8 copy, 2 shape not
  * served, 3 a pair region overflowed (the batch was answered by another path and the next 16 batches skip the int8 filter) */
 int vg_batch_q8_status(const vg_corpus *c);
+/* 1 once a batch in the split form of the half-precision kernel (VG_BATCH_H_SPLIT=1: filter kernel + exact-evaluation kernel) overflowed
+ * a pair region: that batch was answered again by the fused kernel, and so is every later one over this corpus.  0: the split form, where
+ * switched on, is what answers. */
+int vg_batch_h_split_off(const vg_corpus *c);
 /* how vg_scan_topk_batch_masked would serve this corpus under `metric`: queries per pass of the masked multi-query scan (4 or 2; 0 =
  * the fallback, one single masked scan per query) and the launch shape of the kernel that runs - lanes per row, 16-byte chunks per
  * lane (the single masked scan's shape for the fallback; 64 / 0 for the long-row kernel).  Pure host logic.  Every pass of a masked

@@ -137,6 +137,7 @@ def _load():
         "vg_reload_switches": (None, []),
         "vg_batch_last_path": (i32, [vp]),
         "vg_batch_q8_status": (i32, [vp]),
+        "vg_batch_h_split_off": (i32, [vp]),
         "vg_corpus_set_scan_filter": (i32, [vp, i32]),
         "vg_corpus_set_tie_order": (i32, [vp, i32]),
         "vg_corpus_tie_order": (i32, [vp]),
@@ -878,6 +879,10 @@ class Corpus(_PagedScans, _LabeledOps, _GroupedOps):
     def batch_q8_status(self):
         """how the last attempt at the int8 batch filter ended (vectorgpu_diag.h)"""
         return lib().vg_batch_q8_status(self.h)
+
+    def batch_half_split_off(self):
+        """True once a split-form batch over this corpus overflowed a pair region: the fused kernel answers from then on"""
+        return bool(lib().vg_batch_h_split_off(self.h))
 
     def last_batch_path(self):
         """1 f32 matrix-core kernel, 2 int8, 3 half-precision kernel, 4 its long-row form, 5 multi-query scan, 6 one scan per query"""

@@ -774,6 +774,7 @@ bool vg_batch_keys_are_scan_exact(const vg_corpus *c, int metric, int k) {
 
 extern "C" int vg_batch_last_path(const vg_corpus *c) { return c ? c->last_batch_path : 0; }
 extern "C" int vg_batch_q8_status(const vg_corpus *c) { return c ? c->bq8_status : 0; }
+extern "C" int vg_batch_h_split_off(const vg_corpus *c) { return (c && c->bsplit_off) ? 1 : 0; }
 
 extern "C" int vg_batch_filter_exact_evals(vg_corpus *c, unsigned long long *out_evals) {
     if (!c || !out_evals) return vg_fail(VG_ERR_INVALID, "vg_batch_filter_exact_evals: NULL argument");
