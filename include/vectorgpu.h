@@ -395,6 +395,52 @@ int     vg_scan_topk_batch_capped_masked(vg_corpus *c, int metric, const void *q
 int     vg_scan_topk_batch_capped_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, int per_label,
                                               uint64_t *out_keys, uint32_t *out_labels, int *out_counts);
 
+/* ---- label-set scans: the labeled, grouped and capped scans over the rows whose label is in a SET of labels, or - exclude != 0 - is
+ * not in it: access control ("the documents of the groups this user belongs to"), facets ("category IN (...)"), exclusion ("not the
+ * documents already shown" - and with it exact paging through grouped results, which stop at 64 labels per call; no reference entry
+ * point).  The labels are those of the labeled scans (vg_corpus_set_labels).
+ * A label set is n_labels >= 0 labels (labels may be NULL when n_labels == 0): order does not matter, duplicates are allowed and mean
+ * nothing, VG_LABEL_NONE in a set is VG_ERR_INVALID.  exclude == 0: a row is ALLOWED iff it carries a label and that label is in the
+ * set; exclude != 0: iff it carries a label and that label is NOT in the set.  A row without a label (VG_LABEL_NONE) is never
+ * allowed.  An empty set with exclude == 0 allows no row: count 0, not an error; an empty set with exclude != 0 allows every labeled
+ * row.  The handle's row mask is neither read nor written by any of these calls.
+ * vg_scan_topk_labelset: the contract of vg_scan_topk_masked over the allowed rows - rows with a finite distance, ascending (distance,
+ * scan position) whatever the handle's tie_order, the first k, every distance the float vg_scan_distances reports for that row, bit
+ * for bit.  The host sorts the set and uploads it into scratch the handle owns; a small kernel (one binary search per row) turns
+ * (labels, set, exclude) into a bitmap in the scratch buffer the labeled scans use, then the single masked kernels run over it.
+ * vg_scan_topk_grouped_labelset / vg_scan_topk_capped_labelset: what vg_scan_topk_grouped_masked / vg_scan_topk_capped_masked are
+ * contracted to return under a mask holding exactly the allowed rows - the same bitmap in front of the masked grouped / capped
+ * kernels, so the shapes those leave out stay VG_ERR_UNSUPPORTED (f16 cosine and dot over rows of 2049 .. 3072 halves).
+ * Paging grouped results: call with exclude = 1 and the labels returned so far; the pages, concatenated, are the grouped order.
+ * All forms: 1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below, the count(s) zeroed first); no labels set: VG_ERR_INVALID;
+ * an empty corpus: VG_OK with count 0; per_label < 1: VG_ERR_INVALID.  The _keys forms: packed keys, positions local to this corpus.
+ * vg_scan_topk_batch_labelset: nq queries (row-major nq x dim, host), each its OWN set - query i's is set_labels[set_offsets[i] ..
+ * set_offsets[i + 1]) (CSR: nq + 1 offsets that do not decrease, VG_ERR_INVALID otherwise), one `exclude` for the whole batch.  Query
+ * i's answer is what vg_scan_topk_labelset(c, metric, q_i, k, its set, exclude, ..) is contracted to return, in caller order;
+ * out_rowids / out_dist are nq x k, the slots of query i behind out_counts[i] are NOT written; nq < 1: VG_ERR_INVALID.  f32 / uint8 /
+ * int8 rows of a register-resident shape: the queries are ordered by their sets, a pre-pass per 32 queries reads the labels once and
+ * writes one membership dword per row (n_rows dwords of scratch whatever nq), then 4 (or 2) queries share every row load of a pass;
+ * a row is offered only to the queries that may see it and a batch of rows none of them may see is not read (vg_scan_multi.h,
+ * label-set form; the plan: vg_batch_labelset_plan, vectorgpu_diag.h).  uint8 / int8: identical to nq single calls; f32: the floats
+ * of vg_scan_topk_batch_masked under the same launch shape.  Every other shape: one single label-set scan per query, the bitmap
+ * rebuilt only where the set changes.  Timings NOT measured. */
+int     vg_scan_topk_labelset(vg_corpus *c, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels, int exclude,
+                              int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_scan_topk_labelset_keys(vg_corpus *c, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels, int exclude,
+                                   uint64_t *out_keys, int *out_count);
+int     vg_scan_topk_grouped_labelset(vg_corpus *c, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels, int exclude,
+                                      int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_grouped_labelset_keys(vg_corpus *c, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels,
+                                           int exclude, uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_capped_labelset(vg_corpus *c, int metric, const void *query, int k, int per_label, const uint32_t *labels,
+                                     int64_t n_labels, int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_capped_labelset_keys(vg_corpus *c, int metric, const void *query, int k, int per_label, const uint32_t *labels,
+                                          int64_t n_labels, int exclude, uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_batch_labelset(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
+                                    const int64_t *set_offsets, int exclude, int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_scan_topk_batch_labelset_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
+                                         const int64_t *set_offsets, int exclude, uint64_t *out_keys, int *out_counts);
+
 /* ---- masked range scans: every ALLOWED row within a distance of the query - "every row of this tenant within r", near-duplicate
  * detection inside one category (no reference entry point; the reference's form is "SELECT ... FROM vector_full_scan_stream(...)
  * WHERE id IN (...) AND distance <= r": N rows stepped).  The contract is the conjunction of vg_scan_within's and vg_scan_topk_masked's.
@@ -593,6 +639,17 @@ int     vg_shards_scan_topk_batch_capped(vg_shards *s, int metric, const void *q
                                          int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
 int     vg_shards_scan_topk_batch_capped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label,
                                                 int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_counts);
+/* label-set scans (see above): the sets name labels, which mean the same on every shard - every shard answers over its own rows and
+ * the lists merge like the labeled / grouped / capped scans' */
+int     vg_shards_scan_topk_labelset(vg_shards *s, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels, int exclude,
+                                     int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_shards_scan_topk_batch_labelset(vg_shards *s, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
+                                           const int64_t *set_offsets, int exclude, int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_shards_scan_topk_grouped_labelset(vg_shards *s, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels,
+                                             int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_shards_scan_topk_capped_labelset(vg_shards *s, int metric, const void *query, int k, int per_label, const uint32_t *labels,
+                                            int64_t n_labels, int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels,
+                                            int *out_count);
 /* the masked range scans over every shard: each shard answers over its own bits (a shard whose share of the mask is empty launches
  * nothing and contributes nothing), merged like vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus
  * holding all rows.  Same contract; the results are read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and

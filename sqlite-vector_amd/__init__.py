@@ -244,6 +244,20 @@ def _load():
         "vg_shards_scan_topk_batch_capped": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
         "vg_shards_scan_topk_batch_capped_masked": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]),
         "vg_batch_capped_plan": (i32, [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        # label-set scans: the labeled / grouped / capped scans over the rows whose label is in (exclude: not in) a set of labels
+        "vg_scan_topk_labelset": (i32, [vp, i32, vp, i32, vp, i64, i32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_labelset_keys": (i32, [vp, i32, vp, i32, vp, i64, i32, vp, C.POINTER(i32)]),
+        "vg_scan_topk_grouped_labelset": (i32, [vp, i32, vp, i32, vp, i64, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_grouped_labelset_keys": (i32, [vp, i32, vp, i32, vp, i64, i32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_capped_labelset": (i32, [vp, i32, vp, i32, i32, vp, i64, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_capped_labelset_keys": (i32, [vp, i32, vp, i32, i32, vp, i64, i32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_batch_labelset": (i32, [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp]),
+        "vg_scan_topk_batch_labelset_keys": (i32, [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp]),
+        "vg_batch_labelset_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "vg_shards_scan_topk_labelset": (i32, [vp, i32, vp, i32, vp, i64, i32, vp, vp, C.POINTER(i32)]),
+        "vg_shards_scan_topk_batch_labelset": (i32, [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp]),
+        "vg_shards_scan_topk_grouped_labelset": (i32, [vp, i32, vp, i32, vp, i64, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_shards_scan_topk_capped_labelset": (i32, [vp, i32, vp, i32, i32, vp, i64, i32, vp, vp, vp, C.POINTER(i32)]),
         "vg_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
         "vg_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
         "vg_scan_within_batch_keys": (i32, [vp, i32, i64, i64, vp]),
@@ -435,6 +449,104 @@ class _GroupedOps:
         fn = getattr(lib(), self._sprefix + "scan_topk_batch_capped" + ("_masked" if masked else ""))
         _check(fn(self.h, metric, _ptr(queries), nq, k, per_label, _ptr(ids), _ptr(dist), _ptr(lab), _ptr(cnt)))
         return ids, dist, lab, cnt[:nq]
+
+
+def batch_labelset_plan(corpus, metric):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_topk_batch_labelset serves this corpus with; 0 queries per pass =
+    one single label-set scan per query (f16 / bf16, long rows) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().vg_batch_labelset_plan(corpus.h, metric, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
+
+
+def _labelset_u32(labels):
+    """one label set -> contiguous uint32; integers in 0 .. 2^32 - 2 (LABEL_NONE names no row), order and duplicates as given"""
+    a = np.asarray(labels)
+    if a.size == 0:
+        return np.zeros(0, dtype=np.uint32)
+    if a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) >= LABEL_NONE:
+        raise ValueError("a label set holds integers in 0 .. 2^32 - 2 (LABEL_NONE names no row)")
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.uint32)
+
+
+def labelset_csr(sets):
+    """the per-query label sets of scan_topk_batch_labelset in CSR form: (flat uint32 [total], offsets int64 [nq + 1]) - pure host
+    code, no device.  `sets`: a sequence (list, or a tuple of another length than 2) of nq integer arrays, one set each - or a
+    (flat, offsets) pair, a TUPLE of length 2, which is validated and passed through.  Labels are integers in 0 .. 2^32 - 2
+    (LABEL_NONE and negative values: ValueError); offsets start at 0, do not decrease and end at len(flat).  Sorting and
+    de-duplication are the engine's job: the flat array keeps the caller's order and duplicates."""
+    if isinstance(sets, tuple) and len(sets) == 2:
+        flat = _labelset_u32(sets[0])
+        off = np.asarray(sets[1])
+        if off.ndim != 1 or off.size < 1 or off.dtype.kind not in "iu":
+            raise ValueError("offsets: a 1-d integer array of nq + 1 entries")
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        if int(off[0]) != 0 or int(off[-1]) != flat.size or (np.diff(off) < 0).any():
+            raise ValueError("offsets start at 0, do not decrease and end at len(flat)")
+        return flat, off
+    parts = [_labelset_u32(s) for s in sets]
+    off = np.zeros(len(parts) + 1, dtype=np.int64)
+    if parts:
+        off[1:] = np.cumsum([p.size for p in parts])
+    flat = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint32)
+    return np.ascontiguousarray(flat, dtype=np.uint32), off
+
+
+class _LabelsetOps:
+    """the label-set scans, shared by Corpus and Shards (`_sprefix`: vg_ / vg_shards_): the labeled, grouped and capped scans over
+    the rows whose label (set_labels) is in a set of labels - exclude=True: is a label and not in it.  Order and duplicates in a set
+    mean nothing; an unlabeled row is never allowed; the row mask is neither read nor written"""
+
+    def scan_topk_labelset(self, metric, query, k, labels, exclude=False):
+        """the k nearest allowed rows: (rowids, distances); an empty set allows nothing (exclude: every labeled row)"""
+        query = np.ascontiguousarray(query)
+        lab = _labelset_u32(labels)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        cnt = C.c_int(0)
+        fn = getattr(lib(), self._sprefix + "scan_topk_labelset")
+        _check(fn(self.h, metric, _ptr(query), k, _ptr(lab), lab.size, 1 if exclude else 0, _ptr(ids), _ptr(dist), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value]
+
+    def scan_topk_batch_labelset(self, metric, queries, sets, k, exclude=False):
+        """scan_topk_labelset for every row of `queries` under its own set (labelset_csr: nq arrays, or a (flat, offsets) pair), one
+        `exclude` for the batch, in shared passes: (rowids [nq, k], distances [nq, k], counts [nq]); the slots of query i behind
+        counts[i] are not written"""
+        queries = np.ascontiguousarray(queries)
+        nq = queries.shape[0]
+        flat, off = labelset_csr(sets)
+        if off.size != nq + 1:
+            raise ValueError("scan_topk_batch_labelset takes one label set per query")
+        ids = np.zeros((nq, max(k, 1)), dtype=np.int64)
+        dist = np.zeros((nq, max(k, 1)), dtype=np.float64)
+        cnt = np.zeros(max(nq, 1), dtype=np.int32)
+        fn = getattr(lib(), self._sprefix + "scan_topk_batch_labelset")
+        _check(fn(self.h, metric, _ptr(queries), nq, k, _ptr(flat), _ptr(off), 1 if exclude else 0, _ptr(ids), _ptr(dist), _ptr(cnt)))
+        return ids, dist, cnt[:nq]
+
+    def scan_topk_grouped_labelset(self, metric, query, k, labels, exclude=False):
+        """scan_topk_grouped over the allowed rows: (rowids, distances, labels).  Paging: exclude=True with the labels returned so far"""
+        query = np.ascontiguousarray(query)
+        lab = _labelset_u32(labels)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        out = np.zeros(max(k, 1), dtype=np.uint32)
+        cnt = C.c_int(0)
+        fn = getattr(lib(), self._sprefix + "scan_topk_grouped_labelset")
+        _check(fn(self.h, metric, _ptr(query), k, _ptr(lab), lab.size, 1 if exclude else 0, _ptr(ids), _ptr(dist), _ptr(out), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value], out[:cnt.value]
+
+    def scan_topk_capped_labelset(self, metric, query, k, per_label, labels, exclude=False):
+        """scan_topk_capped over the allowed rows: (rowids, distances, labels)"""
+        query = np.ascontiguousarray(query)
+        lab = _labelset_u32(labels)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        out = np.zeros(max(k, 1), dtype=np.uint32)
+        cnt = C.c_int(0)
+        fn = getattr(lib(), self._sprefix + "scan_topk_capped_labelset")
+        _check(fn(self.h, metric, _ptr(query), k, per_label, _ptr(lab), lab.size, 1 if exclude else 0, _ptr(ids), _ptr(dist), _ptr(out), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value], out[:cnt.value]
 
 
 def batch_capped_plan(corpus, metric, masked=False):
@@ -650,7 +762,7 @@ def _set_mask(obj, prefix, rows, bits, positions, rowids):
     return int(getattr(L, prefix + "_mask_count")(obj.h))
 
 
-class Corpus(_PagedScans, _LabeledOps, _GroupedOps):
+class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps):
     """One HBM-resident corpus shard (opaque vg_corpus handle)."""
     _lprefix, _sprefix = "vg_corpus", "vg_"
 
@@ -974,7 +1086,7 @@ def device_memory(device=0):
     return f.value, t.value
 
 
-class Shards(_PagedScans, _LabeledOps, _GroupedOps):
+class Shards(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps):
     """One logical corpus dealt block-cyclically over several devices of this process (opaque vg_shards handle)."""
     _lprefix, _sprefix = "vg_shards", "vg_shards_"
 

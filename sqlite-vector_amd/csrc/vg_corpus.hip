@@ -218,6 +218,8 @@ extern "C" void vg_corpus_destroy(vg_corpus *c) {
     if (c->d_mask) hipFree(c->d_mask);
     if (c->d_labels) hipFree(c->d_labels);
     if (c->d_label_bits) hipFree(c->d_label_bits);
+    if (c->d_lset) hipFree(c->d_lset);
+    if (c->d_member) hipFree(c->d_member);
     if (c->d_ref_prefix) hipFree(c->d_ref_prefix);
     if (c->h_ref) hipHostFree(c->h_ref);
     if (c->norm_ev) hipEventDestroy(c->norm_ev);
@@ -270,7 +272,7 @@ extern "C" int vg_corpus_device_bytes(const vg_corpus *c, long long *out3) {
     out3[0] = size_of(c->d_rows);
     const void *derived[] = {c->d_rows_s8, c->d_sx, c->d_rows_tm, c->d_rows_bf, c->d_rows_q8, c->d_q8stat, c->d_rows_q8tm, c->d_q8tm_stat, c->d_rows_n4, c->d_n4stat, c->d_xnorm};
     const void *working[] = {c->d_query, c->d_cand, c->d_cand_pre, c->d_keys, c->d_dist, c->d_below, c->d_ref_prefix, c->d_sel_keys, c->d_sel_sorted,
-                             c->d_sel_temp, c->d_sel_state, c->d_within, c->d_within_sorted, c->d_within_temp, c->d_wb, c->d_wb_grow, c->d_wb_counts, c->d_mask, c->d_labels, c->d_label_bits, c->d_stage, c->d_filter_evals, c->d_bq, c->d_bcand, c->d_bkeys, c->d_bpairs, c->d_bpcounts};
+                             c->d_sel_temp, c->d_sel_state, c->d_within, c->d_within_sorted, c->d_within_temp, c->d_wb, c->d_wb_grow, c->d_wb_counts, c->d_mask, c->d_labels, c->d_label_bits, c->d_lset, c->d_member, c->d_stage, c->d_filter_evals, c->d_bq, c->d_bcand, c->d_bkeys, c->d_bpairs, c->d_bpcounts};
     out3[1] = 0; out3[2] = 0;
     for (const void *p : derived) out3[1] += size_of(p);
     for (const void *p : working) out3[2] += size_of(p);

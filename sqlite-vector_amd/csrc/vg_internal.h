@@ -183,6 +183,15 @@ struct vg_corpus {
     bool has_labels = false;
     uint64_t *d_label_bits = nullptr;         // ceil(n_rows / 64) words (label_bits_cap_words allocated)
     int64_t label_bits_cap_words = 0;
+    // label-set scans (vg_scan_labelset.hip, vg_multi_labelset.hip): scratch the handle owns.  d_lset: the sorted, de-duplicated
+    // set(s) of the call in flight (single forms: one set; the batch: every membership group's sets, offsets and query masks);
+    // lset_host: what the single forms upload from - it must not move before the upload ran, and every call ends in a wait.
+    // d_member: the batch form's membership dword per row, refilled for every group of up to 32 queries in stream order
+    uint32_t *d_lset = nullptr;
+    size_t lset_bytes = 0;
+    std::vector<uint32_t> lset_host;
+    uint32_t *d_member = nullptr;
+    int64_t member_cap = 0;
     int max_blocks = 0;
     int cu_count = 0;
 
@@ -260,6 +269,16 @@ int vg_mask_upload(vg_corpus *c);             // vg_scan_masked.hip: mask_host -
 static inline void vg_drop_labels(vg_corpus *c) { c->has_labels = false; }   // (the device dwords stay allocated for the next labels)
 // vg_scan_labeled.hip: d_label_bits <- "labels[p] == label" for every row, enqueued on the corpus stream (no wait)
 int vg_label_bits_enqueue(vg_corpus *c, uint32_t label);
+// vg_scan_labelset.hip: d_label_bits <- "labels[p] is in the set" (exclude: "labels[p] is a label and not in the set") for every
+// row, enqueued on the corpus stream (no wait).  `sorted`: n ascending, distinct labels on the HOST, none of them VG_LABEL_NONE
+int vg_labelset_bits_enqueue(vg_corpus *c, const uint32_t *sorted, int64_t n, int exclude);
+int vg_lset_reserve(vg_corpus *c, size_t bytes);      // vg_scan_labelset.hip: d_lset holds at least `bytes`
+// `n` labels of a caller's set -> ascending and distinct in *out; false (and the message set in `who`'s name): a bad pointer / count
+// or VG_LABEL_NONE in the set
+bool vg_labelset_normalise(const char *who, const uint32_t *labels, int64_t n, std::vector<uint32_t> *out);
+// the label-set batch (vg_multi_labelset.hip): what vg_fused_batch_run needs next to a form whose `single.labelset` is set - the
+// queries' normalised sets in CSR form over the queries AS HANDED OVER (ordered by set: equal sets are neighbours), all on the host
+struct VgLabelsetBatch { const uint32_t *flat; const int64_t *offsets; int exclude; };
 
 // next slot of the profiling ring (nullptr when profiling is off)
 static inline hipEvent_t *vg_prof_slot(vg_corpus *c, uint8_t flags) {
@@ -322,7 +341,11 @@ scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows); 
 // through vg_launch_merge_grouped instead of the rank-select merge, and vg_fused_run also yields the winners' labels (out_labels).
 // `per_label` >= 1 (the capped scans, vg_scan_capped.hip; with `grouped` set, whose host path they share): the cap m travels in
 // ScanArgs.within_cap, clamped to k, and the lists of the workgroups go through vg_launch_merge_capped.  0: not a capped form.
-struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; bool grouped; int per_label; };
+// `labelset` (the label-set scans, vg_scan_labelset.hip / vg_multi_labelset.hip; with `labeled` set, whose single path they share - the
+// caller enqueued vg_labelset_bits_enqueue in front): the batch form reads no query labels; it points ScanArgs.labels at the
+// membership dwords of the pass' group (c->d_member, filled by a pre-pass per 32 queries) and puts the pass' bit offset into
+// ScanArgs.within_cap; its fallback builds one bitmap per run of equal sets.
+struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; bool grouped; int per_label; bool labelset; };
 struct VgFusedBatchForm { const char *who; vg_pick_multi_fn_t pick; VgFusedForm single; };
 int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count,
                  uint32_t *out_labels = nullptr);
@@ -332,7 +355,11 @@ int vg_launch_merge_grouped(const uint64_t *dev_cand, int nlists, int k, const u
 // vg_scan_capped.hip: the same for the capped scans - at most `per_label` (1 .. k) keys of one label among the k
 int vg_launch_merge_capped(const uint64_t *dev_cand, int nlists, int k, int per_label, const uint32_t *dev_labels, uint64_t *dev_out, hipStream_t stream);
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
-                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr, uint32_t *out_labels = nullptr);
+                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr, uint32_t *out_labels = nullptr,
+                       const VgLabelsetBatch *lsets = nullptr);
+// vg_multi_labelset.hip: the membership pre-pass of one group - d_member[row] bit j <- query j of the group may see the row.  The
+// group's data sits in d_lset at dword offset `at`: [nd offsets + 1 | nd query masks | the nd distinct sets back to back]
+int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, int exclude);
 // the batch launch of that merge (vg_multi_grouped.hip): workgroup n merges query n's `nlists` lists ([nq][nlists][64] keys at dev_cand) and writes its 64
 // keys and 64 labels at dev_out + n * VG_KEYS_BYTES.  A grouped VgFusedBatchForm (`single.grouped`, vg_multi_grouped.hip) ends in it:
 // vg_fused_batch_run then sets ScanArgs.labels, requires labels, sizes a slice's key buffer for the labels and fills out_labels (nq x k)

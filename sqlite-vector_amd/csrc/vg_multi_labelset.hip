@@ -1,0 +1,162 @@
+// vg_multi_labelset.hip - label-set batch scans: for each of many queries the k nearest rows whose label is in (exclude: is a label
+// and not in) ITS set of labels (vg_scan_topk_batch_labelset, include/vectorgpu.h).
+//
+// Host side of the label-set form of the multi-query scan (vg_scan_multi.h, VG_MQ_LABELSET), the home of its 60 kernel instances -
+// those of the labeled form: f32 / uint8 / int8 x L2 / cosine / dot / L1 x U in {1, 2, 3} at 4 queries per pass, {4, 6} at 2 - and of
+// the membership pre-pass in front of them.  The batch itself is vg_fused_batch_run (vg_multi_masked.hip) with a label-set form.
+// What is this unit's own:
+//   * the queries are ordered by their normalised (sorted, de-duplicated) sets, lexicographically and stable, before they are cut
+//     into groups and passes: requests with one set are neighbours, share passes and their skip, and share ONE search in the pre-pass;
+//     the results are scattered back to caller order;
+//   * the queries are cut into membership groups of up to 32 (VG_LSET_GROUP; a multiple of every queries-per-pass, and a slice of
+//     vg_fused_batch_run is a multiple of it).  Every group's DISTINCT sets go up once, for the whole batch, into the handle's
+//     d_lset: per group [nd + 1 offsets | nd query masks | the nd sets back to back] - query mask d has bit j set when query j of the
+//     group asks under set d;
+//   * vg_labelset_member_kernel runs once per group, in stream order in front of the group's passes: it reads labels[row] once and
+//     writes ONE dword per row into d_member - bit j: query j of the group may see the row, exclusion folded in, 0 for a row without
+//     a label.  n_rows dwords whatever the batch: a later group refills it behind the passes of the one in front.  The passes then
+//     read 4 bytes per row of a batch they visit where the labeled form reads its label - and no set at all.
+// Where the sets are searched: a group whose distinct sets hold at most VG_LSET_LDS_MAX labels in all (8192: 32 KiB + the offsets and
+// masks) is staged into LDS by every workgroup and searched there; a larger group is searched in global memory, where the upper
+// levels of every search stay in the cache (DESIGN.md 3.20 has the sizes both were tested at).
+// Shapes without a multi-query form (f16 / bf16, long rows): one single label-set scan per query (vg_scan_labelset.hip) in that same
+// order, the bitmap rebuilt only where the set changes.
+#include "vg_internal.h"
+
+#include "vg_scan_multi.h"
+#include "vg_pick.h"
+
+#include <numeric>
+
+#define VG_LSET_GROUP 32
+#define VG_LSET_LDS_MAX 8192
+static_assert(VG_LSET_GROUP == 32, "a membership word is a dword");
+
+// d_member[row] for one group.  `grp`: [nd + 1 offsets | nd query masks | sets], `total` = offsets[nd] labels in the sets.  One
+// thread a row, grid-stride; per distinct set one binary search (the first element >= the label), and the set's query mask is OR-ed
+// in when the label was found - with `exclude`, when it was not.  IN_LDS: the whole of `grp` is copied into LDS first.
+template <bool IN_LDS>
+__global__ __launch_bounds__(256) void vg_labelset_member_kernel(const uint32_t *labels, long long n_rows, const uint32_t *grp, int nd, int total,
+                                                                  int exclude, uint32_t *member) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t *g = grp;
+    if constexpr (IN_LDS) {
+        const int words = 2 * nd + 1 + total;
+        for (int i = threadIdx.x; i < words; i += blockDim.x) lds[i] = grp[i];
+        __syncthreads();
+        g = lds;
+    }
+    const uint32_t *off = g, *qmask = g + nd + 1, *sets = g + 2 * nd + 1;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x; row < n_rows; row += stride) {
+        const uint32_t lab = labels[row];
+        uint32_t word = 0u;
+        if (lab != VG_MQ_LABEL_NONE) {
+            for (int d = 0; d < nd; ++d) {
+                uint32_t lo = off[d];
+                const uint32_t end = off[d + 1];
+                uint32_t hi = end;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (sets[mid] < lab) lo = mid + 1; else hi = mid;
+                }
+                const bool found = lo < end && sets[lo] == lab;
+                if (found != (exclude != 0)) word |= qmask[d];
+            }
+        }
+        member[row] = word;
+    }
+}
+
+int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, int exclude) {
+    if (c->member_cap < c->n_rows) {
+        if (c->d_member) { hipFree(c->d_member); c->d_member = nullptr; c->member_cap = 0; }
+        HIP_TRY(hipMalloc(&c->d_member, (size_t)c->n_rows * sizeof(uint32_t)));
+        c->member_cap = c->n_rows;
+    }
+    const long long blocks = std::min<long long>((c->n_rows + 255) / 256, 2048);
+    const bool in_lds = total <= VG_LSET_LDS_MAX;
+    const size_t smem = in_lds ? (size_t)(2 * nd + 1 + total) * sizeof(uint32_t) : 0;
+    hipLaunchKernelGGL(in_lds ? vg_labelset_member_kernel<true> : vg_labelset_member_kernel<false>, dim3((unsigned)blocks), dim3(256), smem, c->stream,
+                       (const uint32_t *)c->d_labels, (long long)c->n_rows, (const uint32_t *)c->d_lset + at, nd, (int)total, exclude ? 1 : 0,
+                       c->d_member);
+    HIP_TRY(hipGetLastError());
+    return VG_OK;
+}
+
+static scan_fn_t pick_multi_labelset(int vtype, int acc, int U, int NQ) { return vg_pick_multi<MultiFamily<VG_MQ_LABELSET>>(vtype, acc, U, NQ); }
+
+extern "C" int vg_batch_labelset_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    const int acc = vg_metric_to_acc(metric);
+    if (acc < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    VgShape s{};
+    int NQ = vg_multi_plan(c, metric, &s);
+    if (NQ != 0 && !pick_multi_labelset(c->vtype, acc, s.U, NQ)) NQ = 0;
+    if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single masked scan's
+    if (out_queries_per_pass) *out_queries_per_pass = NQ;
+    if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
+    if (out_u) *out_u = s.long_rows ? 0 : s.U;
+    return VG_OK;
+}
+
+extern "C" int vg_scan_topk_batch_labelset_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
+                                                const int64_t *set_offsets, int exclude, uint64_t *out_keys, int *out_counts) {
+    const VgFusedBatchForm form = {"vg_scan_topk_batch_labelset", pick_multi_labelset,
+                                   {"vg_scan_topk_labelset", vg_pick_scan_masked, false, false, true, false, 0, true}};
+    if (!c || !queries || !out_counts || !set_offsets) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", form.who);
+    if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", form.who);
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", form.who);
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (label-set scans use the fused list only)", form.who, VG_MAX_FUSED_K);
+    if (set_offsets[0] < 0) return vg_fail(VG_ERR_INVALID, "%s: set_offsets[0] is negative", form.who);
+    for (int i = 0; i < nq; ++i)
+        if (set_offsets[i + 1] < set_offsets[i]) return vg_fail(VG_ERR_INVALID, "%s: set_offsets decrease at query %d", form.who, i);
+    if (set_offsets[nq] > set_offsets[0] && !set_labels) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", form.who);
+    // every query's set, normalised; then the queries in set order (stable: equal sets keep caller order)
+    std::vector<std::vector<uint32_t>> sets((size_t)nq);
+    for (int i = 0; i < nq; ++i)
+        if (!vg_labelset_normalise(form.who, set_labels + set_offsets[i], set_offsets[i + 1] - set_offsets[i], &sets[(size_t)i])) return VG_ERR_INVALID;
+    std::vector<int> order((size_t)nq);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return sets[(size_t)x] < sets[(size_t)y]; });
+    const size_t row_bytes = (size_t)c->dim * c->es;
+    std::vector<uint8_t> sq((size_t)nq * row_bytes);
+    std::vector<uint32_t> flat;
+    std::vector<int64_t> offs((size_t)nq + 1, 0);
+    for (int i = 0; i < nq; ++i) {
+        const std::vector<uint32_t> &s = sets[(size_t)order[(size_t)i]];
+        memcpy(sq.data() + (size_t)i * row_bytes, (const uint8_t *)queries + (size_t)order[(size_t)i] * row_bytes, row_bytes);
+        flat.insert(flat.end(), s.begin(), s.end());
+        offs[(size_t)i + 1] = (int64_t)flat.size();
+    }
+    const VgLabelsetBatch ls = {flat.data(), offs.data(), exclude ? 1 : 0};
+    std::vector<uint64_t> skeys((size_t)nq * k);
+    std::vector<int> scounts((size_t)nq, 0);
+    int rc = vg_fused_batch_run(c, form, metric, sq.data(), nq, k, nullptr, out_keys ? skeys.data() : nullptr, scounts.data(), nullptr, nullptr, &ls);
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < nq; ++i) {
+        const int dst = order[(size_t)i];
+        out_counts[dst] = scounts[(size_t)i];
+        memcpy(out_keys + (size_t)dst * k, skeys.data() + (size_t)i * k, (size_t)scounts[(size_t)i] * sizeof(uint64_t));
+    }
+    return VG_OK;
+}
+
+extern "C" int vg_scan_topk_batch_labelset(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
+                                           const int64_t *set_offsets, int exclude, int64_t *out_rowids, double *out_dist, int *out_counts) {
+    if (!c || !queries || !out_counts || !set_offsets) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: NULL argument");
+    const bool k_ok = k >= 1 && k <= VG_MAX_FUSED_K;
+    if (nq >= 1) for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (nq >= 1 && k_ok && (!out_rowids || !out_dist)) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: NULL output");
+    std::vector<uint64_t> keys((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
+    int rc = vg_scan_topk_batch_labelset_keys(c, metric, queries, nq, k, set_labels, set_offsets, exclude, keys.data(), out_counts);
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < nq; ++i)
+        for (int j = 0; j < out_counts[i]; ++j) {
+            const uint64_t key = keys[(size_t)i * k + j];
+            out_dist[(size_t)i * k + j] = (double)vg_key_distance(key);
+            out_rowids[(size_t)i * k + j] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
+        }
+    return VG_OK;
+}

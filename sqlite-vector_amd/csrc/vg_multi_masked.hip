@@ -39,16 +39,19 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
 // A grouped form (vg_multi_grouped.hip): the lists merge through the label-deduping merge and dev_out_keys receives, per query, 64
 // keys followed by their 64 labels (VG_KEYS_BYTES).  A capped form (vg_multi_capped.hip: grouped, with single.per_label set): the
 // cap, clamped to k, travels in ScanArgs.within_cap - which no other top-k instance reads - and the lists merge through the capped
-// batch merge; everything else is the grouped form's.
+// batch merge; everything else is the grouped form's.  A label-set form (vg_multi_labelset.hip: labeled, with single.labelset set):
+// ScanArgs.labels is the membership buffer of the pass' group and `member_shift`, the pass' bit offset inside that group, travels in
+// ScanArgs.within_cap; no query labels.
 static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s,
                                const uint8_t *dev_queries, const uint64_t *dev_floors, const uint32_t *dev_qlabels, int k, uint64_t *dev_cand,
-                               uint64_t *dev_out_keys) {
+                               uint64_t *dev_out_keys, int member_shift = 0) {
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);
     ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_queries, k);
     a.cand = dev_cand;
     if (f.single.masked) a.mask = c->d_mask;
     if (f.single.after) a.floor = dev_floors;
-    if (f.single.labeled) { a.labels = c->d_labels; a.qlabels = dev_qlabels; }
+    if (f.single.labeled && !f.single.labelset) { a.labels = c->d_labels; a.qlabels = dev_qlabels; }
+    if (f.single.labelset) { a.labels = c->d_member; a.within_cap = (unsigned long long)member_shift; }
     if (f.single.grouped) a.labels = c->d_labels;
     const int cap = std::min(f.single.per_label, k);          // (capped forms: more than k of one label cannot be returned)
     if (cap > 0) a.within_cap = (unsigned long long)cap;
@@ -69,20 +72,51 @@ static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metri
 
 // queries go up in slices of this many (a multiple of every queries-per-pass): the device staging area does not grow with the batch
 #define VG_FUSED_SLICE 256
+// a label-set form: queries per membership word (vg_multi_labelset.hip) - a multiple of every queries-per-pass, and it divides a slice
+#define VG_MEMBER_GROUP 32
+static_assert(VG_FUSED_SLICE % VG_MEMBER_GROUP == 0, "a slice is whole membership groups");
 
 // nq queries, NQ per pass; every pass of every slice is enqueued back to back on the corpus stream, one wait at the end
 static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries,
                               int nq, const uint64_t *floors, const uint32_t *qlabels, int k, uint64_t *out_keys, int *out_counts,
-                              uint32_t *out_labels) {
+                              uint32_t *out_labels, const VgLabelsetBatch *lsets) {
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
     const int slice = std::min(nq_pad, VG_FUSED_SLICE);
+    const bool qlab = f.single.labeled && !f.single.labelset;          // a label per query goes up with the queries
+    // (a label-set form: the DISTINCT sets of every membership group of VG_MEMBER_GROUP queries - equal sets are neighbours - go up
+    //  once, in front of everything: per group [nd + 1 offsets | nd query masks | the sets].  A pad query is in no mask)
+    struct MemberGroup { size_t at; int nd; size_t total; };
+    std::vector<MemberGroup> mgroups;
+    std::vector<uint32_t> mdata;
+    if (f.single.labelset) {
+        for (int g0 = 0; g0 < nq; g0 += VG_MEMBER_GROUP) {
+            const int g1 = std::min(nq, g0 + VG_MEMBER_GROUP);
+            std::vector<uint32_t> off(1, 0u), qmask, sets;
+            for (int i = g0; i < g1; ++i) {
+                const uint32_t *si = lsets->flat + lsets->offsets[i];
+                const size_t ni = (size_t)(lsets->offsets[i + 1] - lsets->offsets[i]);
+                const size_t np = i > g0 ? (size_t)(lsets->offsets[i] - lsets->offsets[i - 1]) : 0;
+                if (i > g0 && ni == np && std::equal(si, si + ni, lsets->flat + lsets->offsets[i - 1])) { qmask.back() |= 1u << (i - g0); continue; }
+                sets.insert(sets.end(), si, si + ni);
+                if (sets.size() > 0x7FFFFFFFull) return vg_fail(VG_ERR_UNSUPPORTED, "%s: the sets of 32 queries hold more than 2^31 - 1 labels", f.who);
+                off.push_back((uint32_t)sets.size());
+                qmask.push_back(1u << (i - g0));
+            }
+            mgroups.push_back(MemberGroup{mdata.size(), (int)qmask.size(), sets.size()});
+            mdata.insert(mdata.end(), off.begin(), off.end());
+            mdata.insert(mdata.end(), qmask.begin(), qmask.end());
+            mdata.insert(mdata.end(), sets.begin(), sets.end());
+        }
+        int rcl = vg_lset_reserve(c, mdata.size() * sizeof(uint32_t));
+        if (rcl != VG_OK) return rcl;
+    }
     // (an after form: the slice's floor keys sit behind its queries in d_bq and go up with them; a pad slot admits nothing.  A labeled
     //  form: the slice's query labels, behind those; a pad slot carries VG_LABEL_NONE and matches nothing)
     const size_t fl_off = (size_t)slice * c->stride;
     const size_t lb_off = fl_off + (f.single.after ? (size_t)slice * sizeof(uint64_t) : 0);
     // (a grouped form: a query's 64 keys are followed by their 64 labels, so its pitch in d_bkeys is VG_KEYS_BYTES)
     const size_t kpitch = f.single.grouped ? VG_KEYS_BYTES / sizeof(uint64_t) : 64;
-    const size_t qbytes = lb_off + (f.single.labeled ? (size_t)slice * sizeof(uint32_t) : 0), keybytes = (size_t)nq_pad * kpitch * sizeof(uint64_t);
+    const size_t qbytes = lb_off + (qlab ? (size_t)slice * sizeof(uint32_t) : 0), keybytes = (size_t)nq_pad * kpitch * sizeof(uint64_t);
     if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
                                 HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
     if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
@@ -94,22 +128,32 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
     for (int i = 0; i < nq; ++i) memcpy(hq.data() + (size_t)i * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
     std::vector<uint64_t> hf(f.single.after ? (size_t)nq_pad : 0, VG_KEY_EMPTY);
     if (f.single.after) for (int i = 0; i < nq; ++i) hf[(size_t)i] = floors[i];
-    std::vector<uint32_t> hl(f.single.labeled ? (size_t)nq_pad : 0, VG_LABEL_NONE);
-    if (f.single.labeled) for (int i = 0; i < nq; ++i) hl[(size_t)i] = qlabels[i];
+    std::vector<uint32_t> hl(qlab ? (size_t)nq_pad : 0, VG_LABEL_NONE);
+    if (qlab) for (int i = 0; i < nq; ++i) hl[(size_t)i] = qlabels[i];
     int rc = VG_OK;
+    if (f.single.labelset) {                                          // (mdata, like hq, stays where it is until the wait)
+        hipError_t e = hipMemcpyAsync(c->d_lset, mdata.data(), mdata.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) rc = vg_fail(VG_ERR_HIP, "%s: label-set upload failed: %s", f.who, hipGetErrorString(e));
+    }
     for (int q0 = 0; q0 < nq_pad && rc == VG_OK; q0 += slice) {
         const int nqs = std::min(slice, nq_pad - q0);
         hipError_t e = hipMemcpyAsync(c->d_bq, hq.data() + (size_t)q0 * c->stride, (size_t)nqs * c->stride, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess && f.single.after)
             e = hipMemcpyAsync((uint8_t *)c->d_bq + fl_off, hf.data() + q0, (size_t)nqs * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && f.single.labeled)
+        if (e == hipSuccess && qlab)
             e = hipMemcpyAsync((uint8_t *)c->d_bq + lb_off, hl.data() + q0, (size_t)nqs * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) { rc = vg_fail(VG_ERR_HIP, "%s: query upload failed: %s", f.who, hipGetErrorString(e)); break; }
-        for (int g = 0; g < nqs && rc == VG_OK; g += NQ)
+        for (int g = 0; g < nqs && rc == VG_OK; g += NQ) {
+            // (a label-set form: the first pass of a membership group is preceded by the group's pre-pass; a slice is whole groups)
+            if (f.single.labelset && (q0 + g) % VG_MEMBER_GROUP == 0) {
+                const MemberGroup &mg = mgroups[(size_t)((q0 + g) / VG_MEMBER_GROUP)];
+                if ((rc = vg_labelset_member_enqueue(c, mg.at, mg.nd, mg.total, lsets->exclude)) != VG_OK) break;
+            }
             rc = launch_fused_multi(c, f, metric, fn, NQ, s, (const uint8_t *)c->d_bq + (size_t)g * c->stride,
                                      reinterpret_cast<const uint64_t *>((const uint8_t *)c->d_bq + fl_off) + g,
                                      reinterpret_cast<const uint32_t *>((const uint8_t *)c->d_bq + lb_off) + g, k, c->d_cand,
-                                     c->d_bkeys + (size_t)(q0 + g) * kpitch);
+                                     c->d_bkeys + (size_t)(q0 + g) * kpitch, (q0 + g) % VG_MEMBER_GROUP);
+        }
     }
     if (rc != VG_OK) { hipStreamSynchronize(c->stream); return rc; }      // (hq must outlive what was enqueued)
     std::vector<uint64_t> keys((size_t)nq * kpitch);
@@ -136,8 +180,9 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
 // Slots behind out_counts[i] are not written.  `floors`: a key per query, read by an after form only.  `out_labels` (nq x k): the
 // winners' labels, filled by a grouped form only.
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
-                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels) {
-    if (!c || !queries || !out_counts || (f.single.after && !floors) || (f.single.labeled && !qlabels)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
+                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgLabelsetBatch *lsets) {
+    if (!c || !queries || !out_counts || (f.single.after && !floors) || (f.single.labeled && !f.single.labelset && !qlabels) ||
+        (f.single.labelset && !lsets)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", f.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
@@ -147,7 +192,7 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
     if (f.single.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
     if (f.single.labeled) {
         if (!c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
-        for (int i = 0; i < nq; ++i)
+        for (int i = 0; i < nq && !f.single.labelset; ++i)
             if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", f.who, i);
     }
     if (f.single.grouped && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
@@ -160,9 +205,20 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
         const size_t row_bytes = (size_t)c->dim * c->es;
         for (int i = 0; i < nq; ++i) {
             // (a labeled form: the bitmap of a label is built once and serves the run of queries that share it)
-            if (f.single.labeled && (i == 0 || qlabels[i] != qlabels[i - 1])) {
+            if (f.single.labeled && !f.single.labelset && (i == 0 || qlabels[i] != qlabels[i - 1])) {
                 int rcb = vg_label_bits_enqueue(c, qlabels[i]);
                 if (rcb != VG_OK) return rcb;
+            }
+            // (a label-set form: the same per run of equal sets; an empty allowed set has no rows - no launch, count 0)
+            if (f.single.labelset) {
+                const uint32_t *si = lsets->flat + lsets->offsets[i];
+                const int64_t ni = lsets->offsets[i + 1] - lsets->offsets[i];
+                if (ni == 0 && !lsets->exclude) continue;
+                const int64_t np = i > 0 ? lsets->offsets[i] - lsets->offsets[i - 1] : -1;
+                if (ni != np || !std::equal(si, si + ni, lsets->flat + lsets->offsets[i - 1])) {
+                    int rcb = vg_labelset_bits_enqueue(c, si, ni, lsets->exclude);
+                    if (rcb != VG_OK) return rcb;
+                }
             }
             int rc = vg_fused_run(c, f.single, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, floors ? floors[i] : 0ull,
                                   out_keys + (size_t)i * k, &out_counts[i], f.single.grouped ? out_labels + (size_t)i * k : nullptr);
@@ -170,7 +226,7 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
         }
         return VG_OK;
     }
-    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, qlabels, k, out_keys, out_counts, out_labels);
+    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, qlabels, k, out_keys, out_counts, out_labels, lsets);
 }
 
 extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,

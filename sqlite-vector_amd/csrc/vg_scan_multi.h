@@ -48,6 +48,17 @@
 //                    What the pipeline carries: three label dwords per lane (current, prefetched, in flight) and the current batch's
 //                    ballot - per-stage ballots PER QUERY would be 2 * NQ scalar registers a stage.  Not combined
 //                    with MASKED / AFTER / WITHIN.  Without the flag the label values are never defined and everything folds away.
+//   VG_MQ_LABELSET   a SET of labels per query (allowed or excluded; vg_multi_labelset.hip): the LABELED pipeline, statement for
+//                    statement, with other predicates.  The per-lane dword loaded one step ahead of the row prefetch is the row's
+//                    MEMBERSHIP word - a.labels points at the membership buffer a pre-pass filled for a group of up to 32 queries
+//                    (bit j: query j of the group may see the row; exclusion folded in, 0 for a row without a label) - shifted right
+//                    by the pass' offset inside its group, so that bit n is query n of the pass.  The batch's wave-uniform word is
+//                    one ballot over "any of the pass' NQ bits set": zero points the U loads at the zero chunk and skips all
+//                    arithmetic.  Bit n is folded into query n's offer predicate in place of `lcur == qlabel[n]`; no query labels
+//                    are loaded.  The shift (wave-uniform, 0 .. 32 - NQ) travels in a.within_cap, which no other top-k instance of
+//                    this form reads: ScanArgs keeps its size and every field its offset.  A pad query of a ragged pass has no bit
+//                    set in any word (the pre-pass sets bits of real queries only) and collects nothing.  Not combined with any
+//                    other flag.
 //   VG_MQ_GROUPED    the k nearest LABELS per query, each by its best row (the batch form of VG_SQ_GROUPED, vg_scan.h).  Combined with
 //                    VG_MQ_MASKED only.  Every lane loads the label of its own row WITH the row prefetch of that batch (row 0 stands
 //                    in for a row out of range or in a batch that is not read); the label decides no address, so - unlike LABELED -
@@ -70,7 +81,8 @@
 //   a.mask          : (MASKED) ceil(n_rows / 64) words, bits behind the last row clear
 //   a.floor         : (AFTER) NQ keys
 //   a.labels        : (LABELED, GROUPED) n_rows dwords;  a.qlabels : (LABELED) NQ dwords
-//   a.within_cap    : (CAPPED) the cap m, 1 .. k
+//                     (LABELSET) n_rows membership dwords
+//   a.within_cap    : (CAPPED) the cap m, 1 .. k;  (LABELSET) the pass' bit offset inside its membership group
 //   a.cand          : (top-k forms) [NQ][gridDim.x][64] candidate keys
 //   descriptor n    : (WITHIN) the [count | cap keys] region of query n, its capacity and its radius (a float: the host rounds down)
 //   a.store_lds_off : (WITHIN) byte offset in dynamic LDS of the key queues, [NQ][wavefront][VG_WITHIN_QUEUE]
@@ -82,7 +94,7 @@
 
 #include "vg_scan.h"
 
-enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4, VG_MQ_LABELED = 8, VG_MQ_GROUPED = 16, VG_MQ_CAPPED = 32 };
+enum : int { VG_MQ_MASKED = 1, VG_MQ_AFTER = 2, VG_MQ_WITHIN = 4, VG_MQ_LABELED = 8, VG_MQ_GROUPED = 16, VG_MQ_CAPPED = 32, VG_MQ_LABELSET = 64 };
 #define VG_MQ_LABEL_NONE 0xFFFFFFFFu      // (VG_LABEL_NONE of vectorgpu.h)
 
 struct VgWithinQuery {                 // 32 bytes, read through wave-uniform addresses (scalar loads)
@@ -123,6 +135,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
     static_assert(!LABELED || FORM == VG_MQ_LABELED, "the labeled form is not combined with the masked, paged or range forms");
     static_assert(!GROUPED || (FORM & ~(VG_MQ_MASKED | VG_MQ_CAPPED)) == VG_MQ_GROUPED, "the grouped form is combined with the mask and the cap only");
     static_assert(!CAPPED || GROUPED, "a capped scan is the grouped form with a cap");
+    constexpr bool LABELSET = (FORM & VG_MQ_LABELSET) != 0;
+    static_assert(!LABELSET || FORM == VG_MQ_LABELSET, "the label-set form is not combined with any other form");
+    constexpr bool LANEWORD = LABELED || LABELSET;                     // a per-lane dword runs one step ahead of the row prefetch
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & (VG_WAVE - 1);
     // (WITHIN: wave-uniform by construction; readfirstlane says so to the compiler, and the queue addresses stay scalar)
@@ -174,6 +189,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         for (int n = 0; n < NQ; ++n) qlabel[n] = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.qlabels[n]);
     }
 
+    // LABELSET: the pass' bit offset inside its membership group (wave-uniform, a scalar register)
+    int mshift = 0;
+    if constexpr (LABELSET) mshift = __builtin_amdgcn_readfirstlane((int)a.within_cap);
+
     const long long nbatch = (a.n_rows + rpb - 1) / rpb;
     const long long wstride = (long long)gridDim.x * VG_WAVES_PER_BLOCK;
     long long b = (long long)blockIdx.x * VG_WAVES_PER_BLOCK + wave;
@@ -194,6 +213,15 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         for (int n = 0; n < NQ; ++n) hit |= (lab == qlabel[n]);
         return __ballot(hit && lab != VG_MQ_LABEL_NONE && batch < nbatch && batch * rpb + rib < a.n_rows);
     };
+    // LABELSET: the membership word of this lane's row with the pass' NQ bits at the bottom (the same unconditional load), and the
+    // batch's word - which lanes hold a row that any query of the pass may see
+    auto member_of = [&](long long batch) -> uint32_t {
+        const long long r0 = batch * rpb + rib;
+        return (a.labels[(batch < nbatch && r0 < a.n_rows) ? r0 : 0] >> mshift) & ((1u << NQ) - 1u);
+    };
+    auto member_hits = [&](uint32_t bits, long long batch) -> uint64_t {
+        return __ballot(bits != 0u && batch < nbatch && batch * rpb + rib < a.n_rows);
+    };
     // GROUPED: the label of this lane's row of a batch, loaded with the batch's rows (`live`: the batch is read at all)
     auto group_label_of = [&](long long batch, bool live) -> uint32_t {
         const long long r0 = batch * rpb + rib;
@@ -202,8 +230,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
     uint4 cur[U], nxt[U];
     uint32_t lcur = 0u, lnext = 0u;
     if constexpr (LABELED) { lcur = label_of(b); lnext = label_of(b + wstride); }
-    uint64_t mcur = LABELED ? label_hits(lcur, b) : mask_of(b);
-    uint64_t mnext = LABELED ? 0ull : mask_of(b + wstride);
+    if constexpr (LABELSET) { lcur = member_of(b); lnext = member_of(b + wstride); }
+    uint64_t mcur = LABELSET ? member_hits(lcur, b) : LABELED ? label_hits(lcur, b) : mask_of(b);
+    uint64_t mnext = LANEWORD ? 0ull : mask_of(b + wstride);
     vg_load_batch<U, true>(cur, a.rows, b * rpb + rib, (b < nbatch && mcur != 0ull) ? a.n_rows : 0, a.stride, sub, lpr, a.nch);
     if constexpr (GROUPED) lcur = group_label_of(b, mcur != 0ull);
     while (b < nbatch) {
@@ -213,6 +242,9 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         if constexpr (LABELED) {
             mnxt = label_hits(lnxt, bn);
             lnext = label_of(bn + wstride);                            // (issued in front of the row prefetch below)
+        } else if constexpr (LABELSET) {
+            mnxt = member_hits(lnxt, bn);
+            lnext = member_of(bn + wstride);                           // (the same)
         } else {
             mnext = mask_of(bn + wstride);
         }
@@ -225,8 +257,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         if (mcur != 0ull) {
             const long long row = b * rpb + rib;
             // the row's lane, and the row is allowed (LABELED: carries a label at all - which query's is the offer's business)
-            const bool owner = LABELED ? (sub == 0) && (row < a.n_rows) && (lcur != VG_MQ_LABEL_NONE)
-                                       : (sub == 0) && (row < a.n_rows) && ((mcur >> rib) & 1ull);
+            // (LABELSET: in range - which query may see it is the offer's business; a row without a label has no bit set)
+            const bool owner = LABELSET  ? (sub == 0) && (row < a.n_rows)
+                               : LABELED ? (sub == 0) && (row < a.n_rows) && (lcur != VG_MQ_LABEL_NONE)
+                                         : (sub == 0) && (row < a.n_rows) && ((mcur >> rib) & 1ull);
             // (WITHIN: every query's distance first, one ballot each; the rare batch with a match parks its keys BEHIND the arithmetic)
             float d[NQ];
             unsigned long long any = 0ull;
@@ -248,6 +282,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
                     if constexpr (CAPPED) vg_list_offer_capped(key, lcur, owner && (dn < INFINITY) && (lcur != VG_MQ_LABEL_NONE), mine[n], mlab[n], thr[n], lane, k, (int)a.within_cap);
                     else if constexpr (GROUPED) vg_list_offer_grouped(key, lcur, owner && (dn < INFINITY) && (lcur != VG_MQ_LABEL_NONE), mine[n], mlab[n], thr[n], lane, k);
                     else if constexpr (LABELED) vg_list_offer(key, owner && (dn < INFINITY) && (lcur == qlabel[n]), mine[n], thr[n], lane, k);
+                    else if constexpr (LABELSET) vg_list_offer(key, owner && (dn < INFINITY) && ((lcur >> n) & 1u), mine[n], thr[n], lane, k);
                     else vg_list_offer(key, owner && (dn < INFINITY) && (!AFTER || key >= floor_key[n]), mine[n], thr[n], lane, k);
                 }
             }
@@ -268,7 +303,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
 #pragma unroll
         for (int u = 0; u < U; ++u) cur[u] = nxt[u];
         mcur = mnxt;
-        if constexpr (LABELED) lcur = lnxt;
+        if constexpr (LANEWORD) lcur = lnxt;
         if constexpr (GROUPED) lcur = lnext;
         b = bn;
     }

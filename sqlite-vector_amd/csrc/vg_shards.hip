@@ -1452,6 +1452,108 @@ extern "C" int vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const
     return VG_OK;
 }
 
+// ---- label-set scans (vg_scan_labelset.hip, vg_multi_labelset.hip): a set names labels, and a label means the same on every shard -
+// every shard runs the form over its own rows with the caller's set(s) (and refuses a bad set itself), the lists merge like the
+// labeled scans' (top-k, batch) or through vg_merge_keys_grouped / vg_merge_keys_capped over GLOBAL positions (grouped, capped)
+extern "C" int vg_shards_scan_topk_labelset(vg_shards *s, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels,
+                                            int exclude, int64_t *out_rowids, double *out_dist, int *out_count) {
+    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_labelset: NULL argument");
+    if (s->S == 1) return vg_scan_topk_labelset(s->sh[0], metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_count);
+    *out_count = 0;
+    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_labelset: k must be at least 1");
+    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_labelset: k must be in 1..64 (label-set scans use the fused list only)");
+    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_labelset: NULL output");
+    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_labelset: no labels set");
+    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
+    std::vector<int> counts((size_t)s->S, 0);
+    int rc = for_each_shard(s, [&](int i) {
+        return vg_scan_topk_labelset_keys(s->sh[(size_t)i], metric, query, k, labels, n_labels, exclude, &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]);
+    });
+    if (rc != VG_OK) return rc;
+    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids, out_dist);
+    return VG_OK;
+}
+
+extern "C" int vg_shards_scan_topk_batch_labelset(vg_shards *s, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
+                                                  const int64_t *set_offsets, int exclude, int64_t *out_rowids, double *out_dist, int *out_counts) {
+    if (!s || !queries || !out_counts || !set_offsets) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labelset: NULL argument");
+    if (s->S == 1) return vg_scan_topk_batch_labelset(s->sh[0], metric, queries, nq, k, set_labels, set_offsets, exclude, out_rowids, out_dist, out_counts);
+    if (nq < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: nq must be at least 1");
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: k must be at least 1");
+    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_batch_labelset: k must be in 1..64 (label-set scans use the fused list only)");
+    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labelset: NULL output");
+    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: no labels set");
+    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
+    std::vector<int> counts((size_t)s->S * nq, 0);
+    int rc = for_each_shard(s, [&](int i) {
+        return vg_scan_topk_batch_labelset_keys(s->sh[(size_t)i], metric, queries, nq, k, set_labels, set_offsets, exclude, &keys[(size_t)i * nq * k],
+                                                &counts[(size_t)i * nq]);
+    });
+    if (rc != VG_OK) return rc;
+    for (int q = 0; q < nq; ++q)
+        out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
+    return VG_OK;
+}
+
+// per_label == 0: the grouped form; >= 1: the capped form (shards_grouped / shards_capped with a set in place of the mask)
+static int shards_labelset_grouped(vg_shards *s, const char *who, int per_label, int metric, const void *query, int k, const uint32_t *labels,
+                                   int64_t n_labels, int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
+    auto refuse = [&](int code, const char *what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
+    if (!s || !query || !out_count) return refuse(VG_ERR_INVALID, "NULL argument");
+    if (s->S == 1)
+        return per_label > 0 ? vg_scan_topk_capped_labelset(s->sh[0], metric, query, k, per_label, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count)
+                             : vg_scan_topk_grouped_labelset(s->sh[0], metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
+    *out_count = 0;
+    if (k < 1) return refuse(VG_ERR_INVALID, "k must be at least 1");
+    if (k > VG_WAVE_KEYS) return refuse(VG_ERR_UNSUPPORTED, "k must be in 1..64 (label-set scans use the fused list only)");
+    if (!out_rowids || !out_dist || !out_labels) return refuse(VG_ERR_INVALID, "NULL output");
+    if (!vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, "no labels set");
+    if (s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, "more than 2^32 - 1 rows over all shards");
+    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
+    std::vector<uint32_t> klabels((size_t)s->S * VG_WAVE_KEYS, VG_LABEL_NONE);
+    std::vector<int> counts((size_t)s->S, 0);
+    int rc = for_each_shard(s, [&](int i) {
+        uint64_t *ki = &keys[(size_t)i * VG_WAVE_KEYS];
+        uint32_t *li = &klabels[(size_t)i * VG_WAVE_KEYS];
+        return per_label > 0 ? vg_scan_topk_capped_labelset_keys(s->sh[(size_t)i], metric, query, k, per_label, labels, n_labels, exclude, ki, li, &counts[(size_t)i])
+                             : vg_scan_topk_grouped_labelset_keys(s->sh[(size_t)i], metric, query, k, labels, n_labels, exclude, ki, li, &counts[(size_t)i]);
+    });
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < s->S; ++i)                           // local positions -> global ones (a shard's list stays ascending: the map is monotonic)
+        for (int j = 0; j < counts[(size_t)i]; ++j) {
+            uint64_t &key = keys[(size_t)i * VG_WAVE_KEYS + j];
+            key = (key & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(key));
+        }
+    uint64_t gkeys[VG_WAVE_KEYS];
+    uint32_t glabels[VG_WAVE_KEYS];
+    int cnt = 0;
+    rc = per_label > 0 ? vg_merge_keys_capped(keys.data(), klabels.data(), s->S, VG_WAVE_KEYS, nullptr, k, per_label, gkeys, glabels, &cnt)
+                       : vg_merge_keys_grouped(keys.data(), klabels.data(), s->S, VG_WAVE_KEYS, nullptr, k, gkeys, glabels, &cnt);
+    if (rc != VG_OK) return fail(rc, vg_last_error());
+    for (int i = 0; i < cnt; ++i) {
+        int shard;
+        int64_t local;
+        locate(s, (int64_t)vg_key_position(gkeys[i]), &shard, &local);
+        out_dist[i] = (double)vg_key_distance(gkeys[i]);
+        out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
+        out_labels[i] = glabels[i];
+    }
+    *out_count = cnt;
+    return VG_OK;
+}
+extern "C" int vg_shards_scan_topk_grouped_labelset(vg_shards *s, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels,
+                                                    int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
+    return shards_labelset_grouped(s, "vg_shards_scan_topk_grouped_labelset", 0, metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
+}
+extern "C" int vg_shards_scan_topk_capped_labelset(vg_shards *s, int metric, const void *query, int k, int per_label, const uint32_t *labels,
+                                                   int64_t n_labels, int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels,
+                                                   int *out_count) {
+    if (out_count) *out_count = 0;
+    if (per_label < 1) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_capped_labelset: per_label must be at least 1");
+    return shards_labelset_grouped(s, "vg_shards_scan_topk_capped_labelset", per_label, metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
+}
+
 // ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): a cursor over GLOBAL scan order becomes one floor key per shard over ITS
 // positions - the cursor's distance image with "local rows of this shard in front of global position P" (local_rows_before) - every
 // shard runs its floor form and the lists merge like the masked scans', by (distance image, global position)
