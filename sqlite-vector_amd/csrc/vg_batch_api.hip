@@ -830,11 +830,6 @@ extern "C" int vg_scan_topk_batch(vg_corpus *c, int metric, const void *queries,
     std::vector<uint64_t> keys((size_t)nq * k);
     int rc = vg_scan_topk_batch_keys(c, metric, queries, nq, k, keys.data(), out_counts);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < nq; ++i)
-        for (int j = 0; j < out_counts[i]; ++j) {
-            const uint64_t key = keys[(size_t)i * k + j];
-            out_dist[(size_t)i * k + j] = (double)vg_key_distance(key);
-            out_rowids[(size_t)i * k + j] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
-        }
+    vg_keys_to_rows(c, keys.data(), nullptr, nq, k, out_counts, out_rowids, out_dist, nullptr);
     return VG_OK;
 }

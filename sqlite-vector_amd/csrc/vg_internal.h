@@ -357,6 +357,18 @@ int vg_launch_merge_capped(const uint64_t *dev_cand, int nlists, int k, int per_
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                        uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr, uint32_t *out_labels = nullptr,
                        const VgLabelsetBatch *lsets = nullptr);
+// vg_scan_masked.hip: the winners' keys as rows - query i's counts[i] keys at keys + i * k become (rowid, distance[, label]) at
+// out_* + i * k.  labels / out_labels: both or neither; a single scan is nq = 1
+void vg_keys_to_rows(const vg_corpus *c, const uint64_t *keys, const uint32_t *labels, int nq, int k, const int *counts, int64_t *out_rowids,
+                     double *out_dist, uint32_t *out_labels);
+// vg_multi_masked.hip: what every vg_batch_*_plan answers - `pick`: the form's multi-query kernel table; queries per pass (0: the
+// table has no instance for the shape, the single scans serve it) and the launch shape of whichever runs.  Refuses a NULL corpus and
+// an unknown metric
+int vg_batch_plan_report(const vg_corpus *c, int metric, vg_pick_multi_fn_t pick, int *out_queries_per_pass, int *out_lpr, int *out_u);
+// vg_scan_grouped.hip: the host merge of several corpora's labeled lists behind vg_merge_keys_grouped (cap 1) and
+// vg_merge_keys_capped (cap per_label), whose argument checks stay their own; `who` names the caller in the core's one refusal
+int vg_merge_keys_by_label(const char *who, const uint64_t *keys, const uint32_t *labels, int n_lists, int list_len, const int64_t *pos_offsets,
+                           int k, int cap, uint64_t *out_keys, uint32_t *out_labels, int *out_count);
 // vg_multi_labelset.hip: the membership pre-pass of one group - d_member[row] bit j <- query j of the group may see the row.  The
 // group's data sits in d_lset at dword offset `at`: [nd offsets + 1 | nd query masks | the nd distinct sets back to back]
 int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, int exclude);

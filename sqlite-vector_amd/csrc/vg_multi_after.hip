@@ -79,12 +79,7 @@ static int batch_after_rows(vg_corpus *c, bool masked, int metric, const void *q
     std::vector<uint64_t> keys(k_ok ? (size_t)nq * k : 1);
     int rc = vg_after_floor_batch_run(c, masked, metric, queries, nq, k, floors.data(), keys.data(), out_counts);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < nq; ++i)
-        for (int j = 0; j < out_counts[i]; ++j) {
-            const uint64_t key = keys[(size_t)i * k + j];
-            out_dist[(size_t)i * k + j] = (double)vg_key_distance(key);
-            out_rowids[(size_t)i * k + j] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
-        }
+    vg_keys_to_rows(c, keys.data(), nullptr, nq, k, out_counts, out_rowids, out_dist, nullptr);
     return VG_OK;
 }
 

@@ -66,17 +66,7 @@ static VgFusedBatchForm capped_batch_form(bool masked, int per_label) {
 }
 
 extern "C" int vg_batch_capped_plan(const vg_corpus *c, int metric, int masked, int *out_queries_per_pass, int *out_lpr, int *out_u) {
-    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
-    const int acc = vg_metric_to_acc(metric);
-    if (acc < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    VgShape s{};
-    int NQ = vg_multi_plan(c, metric, &s);
-    if (NQ != 0 && !(masked ? pick_multi_capped_masked : pick_multi_capped)(c->vtype, acc, s.U, NQ)) NQ = 0;
-    if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single capped scan's
-    if (out_queries_per_pass) *out_queries_per_pass = NQ;
-    if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
-    if (out_u) *out_u = s.long_rows ? 0 : s.U;
-    return VG_OK;
+    return vg_batch_plan_report(c, metric, masked ? pick_multi_capped_masked : pick_multi_capped, out_queries_per_pass, out_lpr, out_u);
 }
 
 // (the order of the answers: NULL arguments and nq, then - with the counts zeroed - k, per_label, the outputs, the handle)
@@ -102,13 +92,7 @@ static int capped_batch_rows(vg_corpus *c, bool masked, int metric, const void *
     std::vector<uint32_t> labels((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
     int rc = capped_batch_keys(c, masked, metric, queries, nq, k, per_label, keys.data(), labels.data(), out_counts);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < nq; ++i)
-        for (int j = 0; j < out_counts[i]; ++j) {
-            const uint64_t key = keys[(size_t)i * k + j];
-            out_dist[(size_t)i * k + j] = (double)vg_key_distance(key);
-            out_rowids[(size_t)i * k + j] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
-            out_labels[(size_t)i * k + j] = labels[(size_t)i * k + j];
-        }
+    vg_keys_to_rows(c, keys.data(), labels.data(), nq, k, out_counts, out_rowids, out_dist, out_labels);
     return VG_OK;
 }
 

@@ -87,17 +87,7 @@ int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, in
 static scan_fn_t pick_multi_labelset(int vtype, int acc, int U, int NQ) { return vg_pick_multi<MultiFamily<VG_MQ_LABELSET>>(vtype, acc, U, NQ); }
 
 extern "C" int vg_batch_labelset_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
-    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
-    const int acc = vg_metric_to_acc(metric);
-    if (acc < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    VgShape s{};
-    int NQ = vg_multi_plan(c, metric, &s);
-    if (NQ != 0 && !pick_multi_labelset(c->vtype, acc, s.U, NQ)) NQ = 0;
-    if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single masked scan's
-    if (out_queries_per_pass) *out_queries_per_pass = NQ;
-    if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
-    if (out_u) *out_u = s.long_rows ? 0 : s.U;
-    return VG_OK;
+    return vg_batch_plan_report(c, metric, pick_multi_labelset, out_queries_per_pass, out_lpr, out_u);
 }
 
 extern "C" int vg_scan_topk_batch_labelset_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
@@ -152,11 +142,6 @@ extern "C" int vg_scan_topk_batch_labelset(vg_corpus *c, int metric, const void 
     std::vector<uint64_t> keys((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
     int rc = vg_scan_topk_batch_labelset_keys(c, metric, queries, nq, k, set_labels, set_offsets, exclude, keys.data(), out_counts);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < nq; ++i)
-        for (int j = 0; j < out_counts[i]; ++j) {
-            const uint64_t key = keys[(size_t)i * k + j];
-            out_dist[(size_t)i * k + j] = (double)vg_key_distance(key);
-            out_rowids[(size_t)i * k + j] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
-        }
+    vg_keys_to_rows(c, keys.data(), nullptr, nq, k, out_counts, out_rowids, out_dist, nullptr);
     return VG_OK;
 }

@@ -21,16 +21,20 @@ static int fused_multi_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_
     return f ? NQ : 0;
 }
 
-extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+int vg_batch_plan_report(const vg_corpus *c, int metric, vg_pick_multi_fn_t pick, int *out_queries_per_pass, int *out_lpr, int *out_u) {
     if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     VgShape s{};
-    const int NQ = fused_multi_plan(c, metric, &s, nullptr);
-    if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single masked scan's
+    const int NQ = fused_multi_plan(c, metric, &s, nullptr, pick);
+    if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the form's single scan has the plain scan's
     if (out_queries_per_pass) *out_queries_per_pass = NQ;
     if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
     if (out_u) *out_u = s.long_rows ? 0 : s.U;
     return VG_OK;
+}
+
+extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    return vg_batch_plan_report(c, metric, vg_pick_multi<MultiFamily<VG_MQ_MASKED>>, out_queries_per_pass, out_lpr, out_u);
 }
 
 // NQ queries (zero-padded rows of the corpus stride, back to back at dev_queries) against the allowed rows in ONE pass; dev_cand:
@@ -242,11 +246,6 @@ extern "C" int vg_scan_topk_batch_masked(vg_corpus *c, int metric, const void *q
     std::vector<uint64_t> keys((nq >= 1 && k >= 1 && k <= VG_MAX_FUSED_K) ? (size_t)nq * k : 1);
     int rc = vg_scan_topk_batch_masked_keys(c, metric, queries, nq, k, keys.data(), out_counts);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < nq; ++i)
-        for (int j = 0; j < out_counts[i]; ++j) {
-            const uint64_t key = keys[(size_t)i * k + j];
-            out_dist[(size_t)i * k + j] = (double)vg_key_distance(key);
-            out_rowids[(size_t)i * k + j] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(key));
-        }
+    vg_keys_to_rows(c, keys.data(), nullptr, nq, k, out_counts, out_rowids, out_dist, nullptr);
     return VG_OK;
 }

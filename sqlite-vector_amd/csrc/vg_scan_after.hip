@@ -90,10 +90,7 @@ static int after_rows(vg_corpus *c, bool masked, int metric, const void *query, 
     int cnt = 0;
     rc = vg_after_floor_run(c, masked, metric, query, k, empty ? VG_KEY_EMPTY : floor, keys, &cnt);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-        out_dist[i] = (double)vg_key_distance(keys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(keys[i]));
-    }
+    vg_keys_to_rows(c, keys, nullptr, 1, k, &cnt, out_rowids, out_dist, nullptr);
     *out_count = cnt;
     return VG_OK;
 }

@@ -95,11 +95,7 @@ static int capped_rows(vg_corpus *c, bool masked, int metric, const void *query,
     int cnt = 0;
     int rc = capped_keys(c, masked, metric, query, k, per_label, keys, labels, &cnt);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-        out_dist[i] = (double)vg_key_distance(keys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(keys[i]));
-        out_labels[i] = labels[i];
-    }
+    vg_keys_to_rows(c, keys, labels, 1, k, &cnt, out_rowids, out_dist, out_labels);
     *out_count = cnt;
     return VG_OK;
 }
@@ -132,30 +128,5 @@ extern "C" int vg_merge_keys_capped(const uint64_t *keys, const uint32_t *labels
     if (!keys || !labels || !out_keys || !out_labels || !out_count) return vg_fail(VG_ERR_INVALID, "vg_merge_keys_capped: NULL argument");
     if (n_lists < 1 || list_len < 1 || k < 1 || per_label < 1)
         return vg_fail(VG_ERR_INVALID, "vg_merge_keys_capped: n_lists, list_len, k and per_label must be at least 1");
-    struct Ent { uint32_t img; int64_t gpos; uint32_t label; };
-    std::vector<Ent> all;
-    for (int l = 0; l < n_lists; ++l)
-        for (int j = 0; j < list_len; ++j) {
-            const uint64_t key = keys[(size_t)l * list_len + j];
-            if (key == VG_KEY_EMPTY) break;                  // (a list is ascending and padded at its end)
-            const uint32_t lab = labels[(size_t)l * list_len + j];
-            if (lab == VG_LABEL_NONE) continue;
-            const int64_t g = (pos_offsets ? pos_offsets[l] : 0) + (int64_t)vg_key_position(key);
-            if (g < 0 || g > 0xFFFFFFFFll) return vg_fail(VG_ERR_UNSUPPORTED, "vg_merge_keys_capped: a global position does not fit a key's 32 bits");
-            all.push_back(Ent{(uint32_t)(key >> 32), g, lab});
-        }
-    std::sort(all.begin(), all.end(), [](const Ent &a, const Ent &b) { return a.img != b.img ? a.img < b.img : a.gpos < b.gpos; });
-    std::vector<std::pair<uint32_t, int>> seen;              // (label, rows kept of it), sorted by label
-    int cnt = 0;
-    for (size_t i = 0; i < all.size() && cnt < k; ++i) {
-        auto it = std::lower_bound(seen.begin(), seen.end(), std::make_pair(all[i].label, 0));
-        if (it == seen.end() || it->first != all[i].label) it = seen.insert(it, std::make_pair(all[i].label, 0));
-        if (it->second >= per_label) continue;
-        ++it->second;
-        out_keys[cnt] = ((uint64_t)all[i].img << 32) | (uint64_t)all[i].gpos;
-        out_labels[cnt] = all[i].label;
-        ++cnt;
-    }
-    *out_count = cnt;
-    return VG_OK;
+    return vg_merge_keys_by_label("vg_merge_keys_capped", keys, labels, n_lists, list_len, pos_offsets, k, per_label, out_keys, out_labels, out_count);
 }

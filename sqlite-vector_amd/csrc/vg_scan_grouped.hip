@@ -87,11 +87,7 @@ static int grouped_rows(vg_corpus *c, bool masked, int metric, const void *query
     int cnt = 0;
     int rc = vg_fused_run(c, form, metric, query, k, 0ull, keys, &cnt, labels);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-        out_dist[i] = (double)vg_key_distance(keys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(keys[i]));
-        out_labels[i] = labels[i];
-    }
+    vg_keys_to_rows(c, keys, labels, 1, k, &cnt, out_rowids, out_dist, out_labels);
     *out_count = cnt;
     return VG_OK;
 }
@@ -115,13 +111,11 @@ extern "C" int vg_scan_topk_grouped_masked_keys(vg_corpus *c, int metric, const 
 
 // ------------------------------------------------------------------------------------------------ the host merge
 
-// The label-deduping twin of vg_merge_keys: one label can live in several lists (shards), so the lists' first rows of a label
-// compete - the three-step contract over the union of the lists, by (distance image, GLOBAL position = pos_offsets[list] + position).
-extern "C" int vg_merge_keys_grouped(const uint64_t *keys, const uint32_t *labels, int n_lists, int list_len, const int64_t *pos_offsets,
-                                     int k, uint64_t *out_keys, uint32_t *out_labels, int *out_count) {
-    if (out_count) *out_count = 0;
-    if (!keys || !labels || !out_keys || !out_labels || !out_count) return vg_fail(VG_ERR_INVALID, "vg_merge_keys_grouped: NULL argument");
-    if (n_lists < 1 || list_len < 1 || k < 1) return vg_fail(VG_ERR_INVALID, "vg_merge_keys_grouped: n_lists, list_len and k must be at least 1");
+// The core of vg_merge_keys_grouped (cap = 1) and vg_merge_keys_capped (vg_scan_capped.hip; cap = per_label), which check their own
+// arguments: the labeled keys of all lists ordered by (distance image, GLOBAL position = pos_offsets[list] + position), the first k
+// of them kept that find fewer than `cap` rows of their label kept.  `who`: the caller, named by the one refusal of its own.
+int vg_merge_keys_by_label(const char *who, const uint64_t *keys, const uint32_t *labels, int n_lists, int list_len, const int64_t *pos_offsets,
+                           int k, int cap, uint64_t *out_keys, uint32_t *out_labels, int *out_count) {
     struct Ent { uint32_t img; int64_t gpos; uint32_t label; };
     std::vector<Ent> all;
     for (int l = 0; l < n_lists; ++l)
@@ -131,20 +125,31 @@ extern "C" int vg_merge_keys_grouped(const uint64_t *keys, const uint32_t *label
             const uint32_t lab = labels[(size_t)l * list_len + j];
             if (lab == VG_LABEL_NONE) continue;
             const int64_t g = (pos_offsets ? pos_offsets[l] : 0) + (int64_t)vg_key_position(key);
-            if (g < 0 || g > 0xFFFFFFFFll) return vg_fail(VG_ERR_UNSUPPORTED, "vg_merge_keys_grouped: a global position does not fit a key's 32 bits");
+            if (g < 0 || g > 0xFFFFFFFFll) return vg_fail(VG_ERR_UNSUPPORTED, "%s: a global position does not fit a key's 32 bits", who);
             all.push_back(Ent{(uint32_t)(key >> 32), g, lab});
         }
     std::sort(all.begin(), all.end(), [](const Ent &a, const Ent &b) { return a.img != b.img ? a.img < b.img : a.gpos < b.gpos; });
-    std::vector<uint32_t> seen;                              // labels kept so far, sorted
+    std::vector<std::pair<uint32_t, int>> seen;              // (label, rows kept of it), sorted by label
     int cnt = 0;
     for (size_t i = 0; i < all.size() && cnt < k; ++i) {
-        auto it = std::lower_bound(seen.begin(), seen.end(), all[i].label);
-        if (it != seen.end() && *it == all[i].label) continue;
-        seen.insert(it, all[i].label);
+        auto it = std::lower_bound(seen.begin(), seen.end(), std::make_pair(all[i].label, 0));
+        if (it == seen.end() || it->first != all[i].label) it = seen.insert(it, std::make_pair(all[i].label, 0));
+        if (it->second >= cap) continue;
+        ++it->second;
         out_keys[cnt] = ((uint64_t)all[i].img << 32) | (uint64_t)all[i].gpos;
         out_labels[cnt] = all[i].label;
         ++cnt;
     }
     *out_count = cnt;
     return VG_OK;
+}
+
+// The label-deduping twin of vg_merge_keys: one label can live in several lists (shards), so the lists' first rows of a label
+// compete - the three-step contract over the union of the lists.
+extern "C" int vg_merge_keys_grouped(const uint64_t *keys, const uint32_t *labels, int n_lists, int list_len, const int64_t *pos_offsets,
+                                     int k, uint64_t *out_keys, uint32_t *out_labels, int *out_count) {
+    if (out_count) *out_count = 0;
+    if (!keys || !labels || !out_keys || !out_labels || !out_count) return vg_fail(VG_ERR_INVALID, "vg_merge_keys_grouped: NULL argument");
+    if (n_lists < 1 || list_len < 1 || k < 1) return vg_fail(VG_ERR_INVALID, "vg_merge_keys_grouped: n_lists, list_len and k must be at least 1");
+    return vg_merge_keys_by_label("vg_merge_keys_grouped", keys, labels, n_lists, list_len, pos_offsets, k, 1, out_keys, out_labels, out_count);
 }

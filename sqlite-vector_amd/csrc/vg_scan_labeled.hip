@@ -68,10 +68,7 @@ extern "C" int vg_scan_topk_labeled(vg_corpus *c, int metric, const void *query,
     int cnt = 0;
     int rc = vg_scan_topk_labeled_keys(c, metric, query, k, label, keys, &cnt);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-        out_dist[i] = (double)vg_key_distance(keys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(keys[i]));
-    }
+    vg_keys_to_rows(c, keys, nullptr, 1, k, &cnt, out_rowids, out_dist, nullptr);
     *out_count = cnt;
     return VG_OK;
 }

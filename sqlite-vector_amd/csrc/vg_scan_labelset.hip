@@ -116,11 +116,7 @@ static int labelset_rows(vg_corpus *c, const VgFusedForm &form, int metric, cons
     int cnt = 0;
     int rc = labelset_keys(c, form, metric, query, k, labels, n_labels, exclude, keys, labs, &cnt);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-        out_dist[i] = (double)vg_key_distance(keys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(keys[i]));
-        if (form.grouped) out_labels[i] = labs[i];
-    }
+    vg_keys_to_rows(c, keys, form.grouped ? labs : nullptr, 1, k, &cnt, out_rowids, out_dist, out_labels);
     *out_count = cnt;
     return VG_OK;
 }

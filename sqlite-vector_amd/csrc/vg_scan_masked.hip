@@ -174,10 +174,18 @@ extern "C" int vg_scan_topk_masked(vg_corpus *c, int metric, const void *query, 
     int cnt = 0;
     int rc = vg_scan_topk_masked_keys(c, metric, query, k, keys, &cnt);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < cnt; ++i) {
-        out_dist[i] = (double)vg_key_distance(keys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(keys[i]));
-    }
+    vg_keys_to_rows(c, keys, nullptr, 1, k, &cnt, out_rowids, out_dist, nullptr);
     *out_count = cnt;
     return VG_OK;
+}
+
+void vg_keys_to_rows(const vg_corpus *c, const uint64_t *keys, const uint32_t *labels, int nq, int k, const int *counts, int64_t *out_rowids,
+                     double *out_dist, uint32_t *out_labels) {
+    for (int i = 0; i < nq; ++i)
+        for (int j = 0; j < counts[i]; ++j) {
+            const size_t at = (size_t)i * k + j;
+            out_dist[at] = (double)vg_key_distance(keys[at]);
+            out_rowids[at] = vg_corpus_rowid_at(c, (int64_t)vg_key_position(keys[at]));
+            if (labels) out_labels[at] = labels[at];
+        }
 }

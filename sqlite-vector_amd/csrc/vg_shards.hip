@@ -1104,47 +1104,7 @@ extern "C" int64_t vg_shards_mask_count(const vg_shards *s) {
     return total;
 }
 
-extern "C" int vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
-                                          int *out_count) {
-    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_masked: NULL argument");
-    if (s->S == 1) return vg_scan_topk_masked(s->sh[0], metric, query, k, out_rowids, out_dist, out_count);
-    *out_count = 0;
-    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_masked: k must be at least 1");
-    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_masked: k must be in 1..64 (masked scans use the fused list only)");
-    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_masked: NULL output");
-    if (vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_topk_masked: no row mask set");
-    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
-    std::vector<int> counts((size_t)s->S, 0);
-    int rc = for_each_shard(s, [&](int i) { return vg_scan_topk_masked_keys(s->sh[(size_t)i], metric, query, k, &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]); });
-    if (rc != VG_OK) return rc;
-    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids, out_dist);
-    return VG_OK;
-}
-
-// the masked batch: every shard answers all nq queries over its own bits (vg_scan_topk_batch_masked_keys), then one merge per query
-extern "C" int vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
-                                                double *out_dist, int *out_counts) {
-    if (!s || !queries || !out_counts) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_masked: NULL argument");
-    if (s->S == 1) return vg_scan_topk_batch_masked(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_counts);
-    if (nq < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: nq must be at least 1");
-    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: k must be at least 1");
-    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_batch_masked: k must be in 1..64 (masked scans use the fused list only)");
-    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_masked: NULL output");
-    if (vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: no row mask set");
-    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
-    std::vector<int> counts((size_t)s->S * nq, 0);
-    int rc = for_each_shard(s, [&](int i) {
-        return vg_scan_topk_batch_masked_keys(s->sh[(size_t)i], metric, queries, nq, k, &keys[(size_t)i * nq * k], &counts[(size_t)i * nq]);
-    });
-    if (rc != VG_OK) return rc;
-    for (int q = 0; q < nq; ++q)
-        out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
-    return VG_OK;
-}
-
-// ---- labeled scans: the labels are given over GLOBAL scan positions and dealt out by the block-cyclic map of the rows, like the mask;
-// every shard runs vg_scan_topk_labeled[_batch] over its own rows and the lists merge like the masked scans'
+// ---- labels: given over GLOBAL scan positions and dealt out by the block-cyclic map of the rows, like the mask
 extern "C" int vg_shards_set_labels(vg_shards *s, const uint32_t *labels, int64_t n) {
     if (!s) return fail(VG_ERR_INVALID, "shards handle is NULL");
     if (s->S == 1) return vg_corpus_set_labels(s->sh[0], labels, n);
@@ -1184,375 +1144,339 @@ extern "C" int vg_shards_has_labels(const vg_shards *s) {
     return 1;
 }
 
+// ---- the fused scan forms over several shards (masked, labeled, label-set, grouped, capped; the paged scans further down): every
+// shard answers over its own rows, mask bits and labels through the form's _keys entry point - positions local to it - and the host
+// merges the S lists of a query over GLOBAL positions.  One scaffold for all of them (point 4):
+//   fused_preamble       the refusals, in one order, worded by the entry point's row of kFusedForms
+//   gather_lists         keys [S][nq][pitch] (+ labels), counts [S][nq]: one call per shard, all shards in flight
+//   merge_back_plain     the k best of the union by (distance image, global position) - merge_lists per query
+//   merge_back_by_label  the same order, at most per_label rows of a label (grouped: one): a label can live on several shards, so
+//                        the shards' rows of it compete (vg_merge_keys_capped / vg_merge_keys_grouped).  Exact: a row of the answer
+//                        over all rows is in the answer of its own shard
+// A single scan is a batch of one query.  A new form adds one row and one entry point whose lambda is its _keys call.
+static int refuse(int code, const char *who, const char *what) {
+    return fail(code, (std::string(who) + ": " + what).c_str());
+}
+
+struct FusedForm {
+    const char *outer;     // whose name "NULL argument", "NULL output" and "more than 2^32 - 1 rows" carry
+    const char *inner;     // ... and the nq, k, per_label and "no labels set" refusals
+    const char *mask;      // ... and "no row mask set"; nullptr: the form reads no mask
+    const char *family;    // "k must be in 1..64 (<family> scans use the fused list only)"
+    bool batch, labels, by_label, capped;
+};
+enum {
+    F_MASKED, F_BATCH_MASKED, F_LABELED, F_BATCH_LABELED, F_LABELSET, F_BATCH_LABELSET, F_GROUPED, F_GROUPED_MASKED, F_BATCH_GROUPED,
+    F_BATCH_GROUPED_MASKED, F_CAPPED, F_CAPPED_MASKED, F_BATCH_CAPPED, F_BATCH_CAPPED_MASKED, F_GROUPED_LABELSET, F_CAPPED_LABELSET
+};
+static const FusedForm kFusedForms[] = {
+    {"vg_shards_scan_topk_masked", "vg_scan_topk_masked", "vg_scan_topk_masked", "masked", false, false, false, false},
+    {"vg_shards_scan_topk_batch_masked", "vg_scan_topk_batch_masked", "vg_scan_topk_batch_masked", "masked", true, false, false, false},
+    {"vg_shards_scan_topk_labeled", "vg_scan_topk_labeled", nullptr, "labeled", false, true, false, false},
+    {"vg_shards_scan_topk_batch_labeled", "vg_scan_topk_batch_labeled", nullptr, "labeled", true, true, false, false},
+    {"vg_shards_scan_topk_labelset", "vg_scan_topk_labelset", nullptr, "label-set", false, true, false, false},
+    {"vg_shards_scan_topk_batch_labelset", "vg_scan_topk_batch_labelset", nullptr, "label-set", true, true, false, false},
+    {"vg_shards_scan_topk_grouped", "vg_scan_topk_grouped", nullptr, "grouped", false, true, true, false},
+    {"vg_shards_scan_topk_grouped", "vg_scan_topk_grouped", "vg_scan_topk_grouped_masked", "grouped", false, true, true, false},
+    {"vg_shards_scan_topk_batch_grouped", "vg_shards_scan_topk_batch_grouped", nullptr, "grouped", true, true, true, false},
+    {"vg_shards_scan_topk_batch_grouped_masked", "vg_shards_scan_topk_batch_grouped_masked", "vg_shards_scan_topk_batch_grouped_masked", "grouped",
+     true, true, true, false},
+    {"vg_shards_scan_topk_capped", "vg_scan_topk_capped", nullptr, "capped", false, true, true, true},
+    {"vg_shards_scan_topk_capped", "vg_scan_topk_capped", "vg_scan_topk_capped_masked", "capped", false, true, true, true},
+    {"vg_shards_scan_topk_batch_capped", "vg_shards_scan_topk_batch_capped", nullptr, "capped", true, true, true, true},
+    {"vg_shards_scan_topk_batch_capped_masked", "vg_shards_scan_topk_batch_capped_masked", "vg_shards_scan_topk_batch_capped_masked", "capped",
+     true, true, true, true},
+    {"vg_shards_scan_topk_grouped_labelset", "vg_shards_scan_topk_grouped_labelset", nullptr, "label-set", false, true, true, false},
+    {"vg_shards_scan_topk_capped_labelset", "vg_shards_scan_topk_capped_labelset", nullptr, "label-set", false, true, true, true},
+};
+
+// VG_OK: go on; FUSED_ONE_SHARD: the handle is one corpus, whose own entry point answers (and refuses); anything else: refused.
+// `inputs`: the form's input pointers are all there; `outputs`: its output arrays are (the counts: out_counts, nq of them, zeroed here)
+enum { FUSED_ONE_SHARD = -1 };
+static int fused_preamble(int form, const vg_shards *s, bool inputs, int nq, int k, int per_label, bool outputs, int *out_counts) {
+    const FusedForm &f = kFusedForms[form];
+    if (!s || !inputs || !out_counts) return refuse(VG_ERR_INVALID, f.outer, "NULL argument");
+    if (s->S == 1) return FUSED_ONE_SHARD;
+    if (f.batch && nq < 1) return refuse(VG_ERR_INVALID, f.inner, "nq must be at least 1");
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    if (k < 1) return refuse(VG_ERR_INVALID, f.inner, "k must be at least 1");
+    if (k > VG_WAVE_KEYS) return refuse(VG_ERR_UNSUPPORTED, f.inner, (std::string("k must be in 1..64 (") + f.family + " scans use the fused list only)").c_str());
+    if (f.capped && per_label < 1) return refuse(VG_ERR_INVALID, f.inner, "per_label must be at least 1");
+    if (!outputs) return refuse(VG_ERR_INVALID, f.outer, "NULL output");
+    if (f.mask && vg_shards_mask_count(s) < 0) return refuse(VG_ERR_INVALID, f.mask, "no row mask set");
+    if (f.labels && !vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, f.inner, "no labels set");
+    if (f.by_label && s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, f.outer, "more than 2^32 - 1 rows over all shards");
+    return VG_OK;
+}
+
+// what the shards handed back: list (shard i, query q) at (i * nq + q) * pitch, counts[i * nq + q] of its slots valid
+struct ShardLists {
+    int nq = 0;
+    size_t pitch = 0;
+    std::vector<uint64_t> keys;
+    std::vector<uint32_t> labels;
+    std::vector<int> counts;
+};
+// scan(shard, keys, labels, counts): that shard's nq lists (labels: nullptr unless with_labels); the first failure comes back unchanged
+template <typename Scan>
+static int gather_lists(vg_shards *s, int nq, size_t pitch, bool with_labels, ShardLists *L, Scan scan) {
+    const size_t per_shard = (size_t)nq * pitch;
+    L->nq = nq;
+    L->pitch = pitch;
+    L->keys.assign((size_t)s->S * per_shard, VG_KEY_EMPTY);
+    if (with_labels) L->labels.assign((size_t)s->S * per_shard, VG_LABEL_NONE);
+    L->counts.assign((size_t)s->S * nq, 0);
+    return for_each_shard(s, [&](int i) {
+        return scan(i, &L->keys[(size_t)i * per_shard], with_labels ? &L->labels[(size_t)i * per_shard] : nullptr, &L->counts[(size_t)i * nq]);
+    });
+}
+
+// k winners per query at out_rowids / out_dist + q * k (either may be nullptr), out_gkeys (optional): see merge_lists.  k <= 64
+static int merge_back_plain(const vg_shards *s, const ShardLists &L, int k, int64_t *out_rowids, double *out_dist, uint64_t *out_gkeys,
+                            int *out_counts) {
+    int64_t ids[VG_WAVE_KEYS];
+    double dist[VG_WAVE_KEYS];
+    for (int q = 0; q < L.nq; ++q)
+        out_counts[q] = merge_query_lists(s, L.keys.data(), L.counts.data(), L.nq, q, (int)L.pitch, k, out_rowids ? out_rowids + (size_t)q * k : ids,
+                                          out_dist ? out_dist + (size_t)q * k : dist, -1, out_gkeys ? out_gkeys + (size_t)q * k : nullptr);
+    return VG_OK;
+}
+
+// per_label >= 1: at most that many rows of a label among a query's k; otherwise the grouped form (one).  Winners at out_* + q * k
+static int merge_back_by_label(const vg_shards *s, const ShardLists &L, int k, int per_label, int64_t *out_rowids, double *out_dist,
+                               uint32_t *out_labels, int *out_counts) {
+    const int pitch = (int)L.pitch;
+    std::vector<uint64_t> qkeys((size_t)s->S * pitch), gkeys((size_t)k);
+    std::vector<uint32_t> qlabels((size_t)s->S * pitch), glabels((size_t)k);
+    for (int q = 0; q < L.nq; ++q) {
+        for (int i = 0; i < s->S; ++i)                       // local positions -> global ones (a list stays ascending: the map is monotonic);
+            for (int j = 0; j < pitch; ++j) {                // slots behind a shard's count: empty
+                const size_t src = ((size_t)i * L.nq + q) * pitch + j, dst = (size_t)i * pitch + j;
+                const bool held = j < L.counts[(size_t)i * L.nq + q];
+                qkeys[dst] = held ? ((L.keys[src] & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(L.keys[src]))) : VG_KEY_EMPTY;
+                qlabels[dst] = held ? L.labels[src] : VG_LABEL_NONE;
+            }
+        int cnt = 0;
+        const int rc = per_label > 0 ? vg_merge_keys_capped(qkeys.data(), qlabels.data(), s->S, pitch, nullptr, k, per_label, gkeys.data(), glabels.data(), &cnt)
+                                     : vg_merge_keys_grouped(qkeys.data(), qlabels.data(), s->S, pitch, nullptr, k, gkeys.data(), glabels.data(), &cnt);
+        if (rc != VG_OK) return rc;
+        for (int j = 0; j < cnt; ++j) {
+            int shard;
+            int64_t local;
+            locate(s, (int64_t)vg_key_position(gkeys[(size_t)j]), &shard, &local);
+            out_dist[(size_t)q * k + j] = (double)vg_key_distance(gkeys[(size_t)j]);
+            out_rowids[(size_t)q * k + j] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
+            out_labels[(size_t)q * k + j] = glabels[(size_t)j];
+        }
+        out_counts[q] = cnt;
+    }
+    return VG_OK;
+}
+
+extern "C" int vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
+                                          int *out_count) {
+    int rc = fused_preamble(F_MASKED, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_masked(s->sh[0], metric, query, k, out_rowids, out_dist, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_masked_keys(s->sh[(size_t)i], metric, query, k, keys, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_count);
+}
+
+extern "C" int vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
+                                                double *out_dist, int *out_counts) {
+    int rc = fused_preamble(F_BATCH_MASKED, s, queries, nq, k, 0, out_rowids && out_dist, out_counts);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_batch_masked(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_counts);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, nq, (size_t)k, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_batch_masked_keys(s->sh[(size_t)i], metric, queries, nq, k, keys, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_counts);
+}
+
 extern "C" int vg_shards_scan_topk_labeled(vg_shards *s, int metric, const void *query, int k, uint32_t label, int64_t *out_rowids,
                                            double *out_dist, int *out_count) {
-    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_labeled: NULL argument");
-    if (s->S == 1) return vg_scan_topk_labeled(s->sh[0], metric, query, k, label, out_rowids, out_dist, out_count);
-    *out_count = 0;
-    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_labeled: k must be at least 1");
-    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_labeled: k must be in 1..64 (labeled scans use the fused list only)");
-    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_labeled: NULL output");
-    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_labeled: no labels set");
-    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
-    std::vector<int> counts((size_t)s->S, 0);
-    int rc = for_each_shard(s, [&](int i) { return vg_scan_topk_labeled_keys(s->sh[(size_t)i], metric, query, k, label, &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]); });
+    int rc = fused_preamble(F_LABELED, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_labeled(s->sh[0], metric, query, k, label, out_rowids, out_dist, out_count);
     if (rc != VG_OK) return rc;
-    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids, out_dist);
-    return VG_OK;
-}
-
-// ---- grouped scans: every shard answers over its own rows (k groups, its best row of each); one label can live on several shards, so
-// the shards' lists merge through vg_merge_keys_grouped over keys rewritten to GLOBAL scan positions - the answer of one corpus holding
-// all rows (a group's best row over all shards is the best of the shards' best rows, and a group among the k best overall is among
-// the k best of every shard that holds its best row)
-static int shards_grouped(vg_shards *s, bool masked, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
-                          uint32_t *out_labels, int *out_count) {
-    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_grouped: NULL argument");
-    if (s->S == 1) return masked ? vg_scan_topk_grouped_masked(s->sh[0], metric, query, k, out_rowids, out_dist, out_labels, out_count)
-                                 : vg_scan_topk_grouped(s->sh[0], metric, query, k, out_rowids, out_dist, out_labels, out_count);
-    *out_count = 0;
-    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_grouped: k must be at least 1");
-    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_grouped: k must be in 1..64 (grouped scans use the fused list only)");
-    if (!out_rowids || !out_dist || !out_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_grouped: NULL output");
-    if (masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_topk_grouped_masked: no row mask set");
-    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_grouped: no labels set");
-    if (s->n_rows > 0xFFFFFFFFll) return fail(VG_ERR_UNSUPPORTED, "vg_shards_scan_topk_grouped: more than 2^32 - 1 rows over all shards");
-    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
-    std::vector<uint32_t> labels((size_t)s->S * VG_WAVE_KEYS, VG_LABEL_NONE);
-    std::vector<int> counts((size_t)s->S, 0);
-    auto scan = masked ? vg_scan_topk_grouped_masked_keys : vg_scan_topk_grouped_keys;
-    int rc = for_each_shard(s, [&](int i) {
-        return scan(s->sh[(size_t)i], metric, query, k, &keys[(size_t)i * VG_WAVE_KEYS], &labels[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]);
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_labeled_keys(s->sh[(size_t)i], metric, query, k, label, keys, counts);
     });
-    if (rc != VG_OK) return rc;
-    for (int i = 0; i < s->S; ++i)                           // local positions -> global ones (a shard's list stays ascending: the map is monotonic)
-        for (int j = 0; j < counts[(size_t)i]; ++j) {
-            uint64_t &key = keys[(size_t)i * VG_WAVE_KEYS + j];
-            key = (key & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(key));
-        }
-    uint64_t gkeys[VG_WAVE_KEYS];
-    uint32_t glabels[VG_WAVE_KEYS];
-    int cnt = 0;
-    rc = vg_merge_keys_grouped(keys.data(), labels.data(), s->S, VG_WAVE_KEYS, nullptr, k, gkeys, glabels, &cnt);
-    if (rc != VG_OK) return fail(rc, vg_last_error());
-    for (int i = 0; i < cnt; ++i) {
-        int shard;
-        int64_t local;
-        locate(s, (int64_t)vg_key_position(gkeys[i]), &shard, &local);
-        out_dist[i] = (double)vg_key_distance(gkeys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
-        out_labels[i] = glabels[i];
-    }
-    *out_count = cnt;
-    return VG_OK;
-}
-extern "C" int vg_shards_scan_topk_grouped(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
-                                           uint32_t *out_labels, int *out_count) {
-    return shards_grouped(s, false, metric, query, k, out_rowids, out_dist, out_labels, out_count);
-}
-extern "C" int vg_shards_scan_topk_grouped_masked(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
-                                                  uint32_t *out_labels, int *out_count) {
-    return shards_grouped(s, true, metric, query, k, out_rowids, out_dist, out_labels, out_count);
-}
-
-// the batch form: every shard answers all nq queries (keys + labels, positions local to it), then query by query the shards' lists
-// are rewritten to global positions and merged like the single form's
-static int shards_grouped_batch(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
-                                double *out_dist, uint32_t *out_labels, int *out_counts) {
-    // (every message carries the name of the entry point that was called)
-    const std::string who = masked ? "vg_shards_scan_topk_batch_grouped_masked" : "vg_shards_scan_topk_batch_grouped";
-    auto refuse = [&](int code, const char *what) { return fail(code, (who + ": " + what).c_str()); };
-    if (!s || !queries || !out_counts) return refuse(VG_ERR_INVALID, "NULL argument");
-    if (s->S == 1) return masked ? vg_scan_topk_batch_grouped_masked(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts)
-                                 : vg_scan_topk_batch_grouped(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts);
-    if (nq < 1) return refuse(VG_ERR_INVALID, "nq must be at least 1");
-    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (k < 1) return refuse(VG_ERR_INVALID, "k must be at least 1");
-    if (k > VG_WAVE_KEYS) return refuse(VG_ERR_UNSUPPORTED, "k must be in 1..64 (grouped scans use the fused list only)");
-    if (!out_rowids || !out_dist || !out_labels) return refuse(VG_ERR_INVALID, "NULL output");
-    if (masked && vg_shards_mask_count(s) < 0) return refuse(VG_ERR_INVALID, "no row mask set");
-    if (!vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, "no labels set");
-    if (s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, "more than 2^32 - 1 rows over all shards");
-    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
-    std::vector<uint32_t> labels((size_t)s->S * nq * k, VG_LABEL_NONE);
-    std::vector<int> counts((size_t)s->S * nq, 0);
-    auto scan = masked ? vg_scan_topk_batch_grouped_masked_keys : vg_scan_topk_batch_grouped_keys;
-    int rc = for_each_shard(s, [&](int i) {
-        return scan(s->sh[(size_t)i], metric, queries, nq, k, &keys[(size_t)i * nq * k], &labels[(size_t)i * nq * k], &counts[(size_t)i * nq]);
-    });
-    if (rc != VG_OK) return rc;
-    std::vector<uint64_t> qkeys((size_t)s->S * k), gkeys((size_t)k);
-    std::vector<uint32_t> qlabels((size_t)s->S * k), glabels((size_t)k);
-    for (int q = 0; q < nq; ++q) {
-        for (int i = 0; i < s->S; ++i)                       // local positions -> global ones; slots behind a shard's count: empty
-            for (int j = 0; j < k; ++j) {
-                const size_t src = ((size_t)i * nq + q) * k + j, dst = (size_t)i * k + j;
-                const bool held = j < counts[(size_t)i * nq + q];
-                qkeys[dst] = held ? ((keys[src] & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(keys[src]))) : VG_KEY_EMPTY;
-                qlabels[dst] = held ? labels[src] : VG_LABEL_NONE;
-            }
-        int cnt = 0;
-        rc = vg_merge_keys_grouped(qkeys.data(), qlabels.data(), s->S, k, nullptr, k, gkeys.data(), glabels.data(), &cnt);
-        if (rc != VG_OK) return fail(rc, vg_last_error());
-        for (int j = 0; j < cnt; ++j) {
-            int shard;
-            int64_t local;
-            locate(s, (int64_t)vg_key_position(gkeys[(size_t)j]), &shard, &local);
-            out_dist[(size_t)q * k + j] = (double)vg_key_distance(gkeys[(size_t)j]);
-            out_rowids[(size_t)q * k + j] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
-            out_labels[(size_t)q * k + j] = glabels[(size_t)j];
-        }
-        out_counts[q] = cnt;
-    }
-    return VG_OK;
-}
-extern "C" int vg_shards_scan_topk_batch_grouped(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
-                                                 double *out_dist, uint32_t *out_labels, int *out_counts) {
-    return shards_grouped_batch(s, false, metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts);
-}
-extern "C" int vg_shards_scan_topk_batch_grouped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
-                                                        double *out_dist, uint32_t *out_labels, int *out_counts) {
-    return shards_grouped_batch(s, true, metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts);
-}
-
-// ---- capped scans: shards_grouped with the cap - every shard answers over its own rows (its capped top-k), the lists merge through
-// vg_merge_keys_capped over GLOBAL scan positions: a row of the answer over all rows is in the capped top-k of its own shard
-// (DESIGN.md 3.17), so the union of the shards' lists holds the answer and the merge selects it
-static int shards_capped(vg_shards *s, bool masked, int metric, const void *query, int k, int per_label, int64_t *out_rowids, double *out_dist,
-                         uint32_t *out_labels, int *out_count) {
-    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_capped: NULL argument");
-    if (s->S == 1) return masked ? vg_scan_topk_capped_masked(s->sh[0], metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count)
-                                 : vg_scan_topk_capped(s->sh[0], metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
-    *out_count = 0;
-    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_capped: k must be at least 1");
-    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_capped: k must be in 1..64 (capped scans use the fused list only)");
-    if (per_label < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_capped: per_label must be at least 1");
-    if (!out_rowids || !out_dist || !out_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_capped: NULL output");
-    if (masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_topk_capped_masked: no row mask set");
-    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_capped: no labels set");
-    if (s->n_rows > 0xFFFFFFFFll) return fail(VG_ERR_UNSUPPORTED, "vg_shards_scan_topk_capped: more than 2^32 - 1 rows over all shards");
-    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
-    std::vector<uint32_t> labels((size_t)s->S * VG_WAVE_KEYS, VG_LABEL_NONE);
-    std::vector<int> counts((size_t)s->S, 0);
-    auto scan = masked ? vg_scan_topk_capped_masked_keys : vg_scan_topk_capped_keys;
-    int rc = for_each_shard(s, [&](int i) {
-        return scan(s->sh[(size_t)i], metric, query, k, per_label, &keys[(size_t)i * VG_WAVE_KEYS], &labels[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]);
-    });
-    if (rc != VG_OK) return rc;
-    for (int i = 0; i < s->S; ++i)                           // local positions -> global ones (a shard's list stays ascending: the map is monotonic)
-        for (int j = 0; j < counts[(size_t)i]; ++j) {
-            uint64_t &key = keys[(size_t)i * VG_WAVE_KEYS + j];
-            key = (key & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(key));
-        }
-    uint64_t gkeys[VG_WAVE_KEYS];
-    uint32_t glabels[VG_WAVE_KEYS];
-    int cnt = 0;
-    rc = vg_merge_keys_capped(keys.data(), labels.data(), s->S, VG_WAVE_KEYS, nullptr, k, per_label, gkeys, glabels, &cnt);
-    if (rc != VG_OK) return fail(rc, vg_last_error());
-    for (int i = 0; i < cnt; ++i) {
-        int shard;
-        int64_t local;
-        locate(s, (int64_t)vg_key_position(gkeys[i]), &shard, &local);
-        out_dist[i] = (double)vg_key_distance(gkeys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
-        out_labels[i] = glabels[i];
-    }
-    *out_count = cnt;
-    return VG_OK;
-}
-extern "C" int vg_shards_scan_topk_capped(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t *out_rowids,
-                                          double *out_dist, uint32_t *out_labels, int *out_count) {
-    return shards_capped(s, false, metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
-}
-extern "C" int vg_shards_scan_topk_capped_masked(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t *out_rowids,
-                                                 double *out_dist, uint32_t *out_labels, int *out_count) {
-    return shards_capped(s, true, metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
-}
-
-// the batch form: shards_grouped_batch with the cap - every shard answers all nq queries (its capped top-k per query, keys + labels,
-// positions local to it), then query by query the shards' lists are rewritten to global positions and merged through
-// vg_merge_keys_capped like the single form's
-static int shards_capped_batch(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
-                               double *out_dist, uint32_t *out_labels, int *out_counts) {
-    // (every message carries the name of the entry point that was called)
-    const std::string who = masked ? "vg_shards_scan_topk_batch_capped_masked" : "vg_shards_scan_topk_batch_capped";
-    auto refuse = [&](int code, const char *what) { return fail(code, (who + ": " + what).c_str()); };
-    if (!s || !queries || !out_counts) return refuse(VG_ERR_INVALID, "NULL argument");
-    if (s->S == 1) return masked ? vg_scan_topk_batch_capped_masked(s->sh[0], metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts)
-                                 : vg_scan_topk_batch_capped(s->sh[0], metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
-    if (nq < 1) return refuse(VG_ERR_INVALID, "nq must be at least 1");
-    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (k < 1) return refuse(VG_ERR_INVALID, "k must be at least 1");
-    if (k > VG_WAVE_KEYS) return refuse(VG_ERR_UNSUPPORTED, "k must be in 1..64 (capped scans use the fused list only)");
-    if (per_label < 1) return refuse(VG_ERR_INVALID, "per_label must be at least 1");
-    if (!out_rowids || !out_dist || !out_labels) return refuse(VG_ERR_INVALID, "NULL output");
-    if (masked && vg_shards_mask_count(s) < 0) return refuse(VG_ERR_INVALID, "no row mask set");
-    if (!vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, "no labels set");
-    if (s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, "more than 2^32 - 1 rows over all shards");
-    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
-    std::vector<uint32_t> labels((size_t)s->S * nq * k, VG_LABEL_NONE);
-    std::vector<int> counts((size_t)s->S * nq, 0);
-    auto scan = masked ? vg_scan_topk_batch_capped_masked_keys : vg_scan_topk_batch_capped_keys;
-    int rc = for_each_shard(s, [&](int i) {
-        return scan(s->sh[(size_t)i], metric, queries, nq, k, per_label, &keys[(size_t)i * nq * k], &labels[(size_t)i * nq * k], &counts[(size_t)i * nq]);
-    });
-    if (rc != VG_OK) return rc;
-    std::vector<uint64_t> qkeys((size_t)s->S * k), gkeys((size_t)k);
-    std::vector<uint32_t> qlabels((size_t)s->S * k), glabels((size_t)k);
-    for (int q = 0; q < nq; ++q) {
-        for (int i = 0; i < s->S; ++i)                       // local positions -> global ones; slots behind a shard's count: empty
-            for (int j = 0; j < k; ++j) {
-                const size_t src = ((size_t)i * nq + q) * k + j, dst = (size_t)i * k + j;
-                const bool held = j < counts[(size_t)i * nq + q];
-                qkeys[dst] = held ? ((keys[src] & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(keys[src]))) : VG_KEY_EMPTY;
-                qlabels[dst] = held ? labels[src] : VG_LABEL_NONE;
-            }
-        int cnt = 0;
-        rc = vg_merge_keys_capped(qkeys.data(), qlabels.data(), s->S, k, nullptr, k, per_label, gkeys.data(), glabels.data(), &cnt);
-        if (rc != VG_OK) return fail(rc, vg_last_error());
-        for (int j = 0; j < cnt; ++j) {
-            int shard;
-            int64_t local;
-            locate(s, (int64_t)vg_key_position(gkeys[(size_t)j]), &shard, &local);
-            out_dist[(size_t)q * k + j] = (double)vg_key_distance(gkeys[(size_t)j]);
-            out_rowids[(size_t)q * k + j] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
-            out_labels[(size_t)q * k + j] = glabels[(size_t)j];
-        }
-        out_counts[q] = cnt;
-    }
-    return VG_OK;
-}
-extern "C" int vg_shards_scan_topk_batch_capped(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
-                                                double *out_dist, uint32_t *out_labels, int *out_counts) {
-    return shards_capped_batch(s, false, metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
-}
-extern "C" int vg_shards_scan_topk_batch_capped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
-                                                       double *out_dist, uint32_t *out_labels, int *out_counts) {
-    return shards_capped_batch(s, true, metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_count);
 }
 
 extern "C" int vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
                                                  int64_t *out_rowids, double *out_dist, int *out_counts) {
-    if (!s || !queries || !out_counts || !query_labels) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labeled: NULL argument");
-    if (s->S == 1) return vg_scan_topk_batch_labeled(s->sh[0], metric, queries, nq, query_labels, k, out_rowids, out_dist, out_counts);
-    if (nq < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labeled: nq must be at least 1");
-    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labeled: k must be at least 1");
-    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_batch_labeled: k must be in 1..64 (labeled scans use the fused list only)");
-    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labeled: NULL output");
-    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labeled: no labels set");
-    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
-    std::vector<int> counts((size_t)s->S * nq, 0);
-    int rc = for_each_shard(s, [&](int i) {
-        return vg_scan_topk_batch_labeled_keys(s->sh[(size_t)i], metric, queries, nq, query_labels, k, &keys[(size_t)i * nq * k], &counts[(size_t)i * nq]);
-    });
+    int rc = fused_preamble(F_BATCH_LABELED, s, queries && query_labels, nq, k, 0, out_rowids && out_dist, out_counts);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_batch_labeled(s->sh[0], metric, queries, nq, query_labels, k, out_rowids, out_dist, out_counts);
     if (rc != VG_OK) return rc;
-    for (int q = 0; q < nq; ++q)
-        out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
-    return VG_OK;
+    ShardLists L;
+    rc = gather_lists(s, nq, (size_t)k, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_batch_labeled_keys(s->sh[(size_t)i], metric, queries, nq, query_labels, k, keys, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_counts);
 }
 
-// ---- label-set scans (vg_scan_labelset.hip, vg_multi_labelset.hip): a set names labels, and a label means the same on every shard -
-// every shard runs the form over its own rows with the caller's set(s) (and refuses a bad set itself), the lists merge like the
-// labeled scans' (top-k, batch) or through vg_merge_keys_grouped / vg_merge_keys_capped over GLOBAL positions (grouped, capped)
+// label-set scans: a set names labels, and a label means the same on every shard - every shard gets the caller's set(s) as they are
+// (and refuses a bad set itself)
 extern "C" int vg_shards_scan_topk_labelset(vg_shards *s, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels,
                                             int exclude, int64_t *out_rowids, double *out_dist, int *out_count) {
-    if (!s || !query || !out_count) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_labelset: NULL argument");
-    if (s->S == 1) return vg_scan_topk_labelset(s->sh[0], metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_count);
-    *out_count = 0;
-    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_labelset: k must be at least 1");
-    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_labelset: k must be in 1..64 (label-set scans use the fused list only)");
-    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_labelset: NULL output");
-    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_labelset: no labels set");
-    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
-    std::vector<int> counts((size_t)s->S, 0);
-    int rc = for_each_shard(s, [&](int i) {
-        return vg_scan_topk_labelset_keys(s->sh[(size_t)i], metric, query, k, labels, n_labels, exclude, &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]);
-    });
+    int rc = fused_preamble(F_LABELSET, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_labelset(s->sh[0], metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_count);
     if (rc != VG_OK) return rc;
-    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids, out_dist);
-    return VG_OK;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_labelset_keys(s->sh[(size_t)i], metric, query, k, labels, n_labels, exclude, keys, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_count);
 }
 
 extern "C" int vg_shards_scan_topk_batch_labelset(vg_shards *s, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
                                                   const int64_t *set_offsets, int exclude, int64_t *out_rowids, double *out_dist, int *out_counts) {
-    if (!s || !queries || !out_counts || !set_offsets) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labelset: NULL argument");
-    if (s->S == 1) return vg_scan_topk_batch_labelset(s->sh[0], metric, queries, nq, k, set_labels, set_offsets, exclude, out_rowids, out_dist, out_counts);
-    if (nq < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: nq must be at least 1");
-    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (k < 1) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: k must be at least 1");
-    if (k > VG_WAVE_KEYS) return fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_batch_labelset: k must be in 1..64 (label-set scans use the fused list only)");
-    if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch_labelset: NULL output");
-    if (!vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: no labels set");
-    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
-    std::vector<int> counts((size_t)s->S * nq, 0);
-    int rc = for_each_shard(s, [&](int i) {
-        return vg_scan_topk_batch_labelset_keys(s->sh[(size_t)i], metric, queries, nq, k, set_labels, set_offsets, exclude, &keys[(size_t)i * nq * k],
-                                                &counts[(size_t)i * nq]);
-    });
+    int rc = fused_preamble(F_BATCH_LABELSET, s, queries && set_offsets, nq, k, 0, out_rowids && out_dist, out_counts);
+    if (rc == FUSED_ONE_SHARD)
+        return vg_scan_topk_batch_labelset(s->sh[0], metric, queries, nq, k, set_labels, set_offsets, exclude, out_rowids, out_dist, out_counts);
     if (rc != VG_OK) return rc;
-    for (int q = 0; q < nq; ++q)
-        out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids + (size_t)q * k, out_dist + (size_t)q * k);
-    return VG_OK;
+    ShardLists L;
+    rc = gather_lists(s, nq, (size_t)k, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_batch_labelset_keys(s->sh[(size_t)i], metric, queries, nq, k, set_labels, set_offsets, exclude, keys, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_counts);
 }
 
-// per_label == 0: the grouped form; >= 1: the capped form (shards_grouped / shards_capped with a set in place of the mask)
-static int shards_labelset_grouped(vg_shards *s, const char *who, int per_label, int metric, const void *query, int k, const uint32_t *labels,
-                                   int64_t n_labels, int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
-    auto refuse = [&](int code, const char *what) { return fail(code, (std::string(who) + ": " + what).c_str()); };
-    if (!s || !query || !out_count) return refuse(VG_ERR_INVALID, "NULL argument");
-    if (s->S == 1)
-        return per_label > 0 ? vg_scan_topk_capped_labelset(s->sh[0], metric, query, k, per_label, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count)
-                             : vg_scan_topk_grouped_labelset(s->sh[0], metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
-    *out_count = 0;
-    if (k < 1) return refuse(VG_ERR_INVALID, "k must be at least 1");
-    if (k > VG_WAVE_KEYS) return refuse(VG_ERR_UNSUPPORTED, "k must be in 1..64 (label-set scans use the fused list only)");
-    if (!out_rowids || !out_dist || !out_labels) return refuse(VG_ERR_INVALID, "NULL output");
-    if (!vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, "no labels set");
-    if (s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, "more than 2^32 - 1 rows over all shards");
-    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
-    std::vector<uint32_t> klabels((size_t)s->S * VG_WAVE_KEYS, VG_LABEL_NONE);
-    std::vector<int> counts((size_t)s->S, 0);
-    int rc = for_each_shard(s, [&](int i) {
-        uint64_t *ki = &keys[(size_t)i * VG_WAVE_KEYS];
-        uint32_t *li = &klabels[(size_t)i * VG_WAVE_KEYS];
-        return per_label > 0 ? vg_scan_topk_capped_labelset_keys(s->sh[(size_t)i], metric, query, k, per_label, labels, n_labels, exclude, ki, li, &counts[(size_t)i])
-                             : vg_scan_topk_grouped_labelset_keys(s->sh[(size_t)i], metric, query, k, labels, n_labels, exclude, ki, li, &counts[(size_t)i]);
-    });
+// grouped scans: the k nearest labels, the best row of each
+extern "C" int vg_shards_scan_topk_grouped(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
+                                           uint32_t *out_labels, int *out_count) {
+    int rc = fused_preamble(F_GROUPED, s, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_grouped(s->sh[0], metric, query, k, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;
-    for (int i = 0; i < s->S; ++i)                           // local positions -> global ones (a shard's list stays ascending: the map is monotonic)
-        for (int j = 0; j < counts[(size_t)i]; ++j) {
-            uint64_t &key = keys[(size_t)i * VG_WAVE_KEYS + j];
-            key = (key & 0xFFFFFFFF00000000ull) | (uint64_t)global_of(s, i, (int64_t)vg_key_position(key));
-        }
-    uint64_t gkeys[VG_WAVE_KEYS];
-    uint32_t glabels[VG_WAVE_KEYS];
-    int cnt = 0;
-    rc = per_label > 0 ? vg_merge_keys_capped(keys.data(), klabels.data(), s->S, VG_WAVE_KEYS, nullptr, k, per_label, gkeys, glabels, &cnt)
-                       : vg_merge_keys_grouped(keys.data(), klabels.data(), s->S, VG_WAVE_KEYS, nullptr, k, gkeys, glabels, &cnt);
-    if (rc != VG_OK) return fail(rc, vg_last_error());
-    for (int i = 0; i < cnt; ++i) {
-        int shard;
-        int64_t local;
-        locate(s, (int64_t)vg_key_position(gkeys[i]), &shard, &local);
-        out_dist[i] = (double)vg_key_distance(gkeys[i]);
-        out_rowids[i] = vg_corpus_rowid_at(s->sh[(size_t)shard], local);
-        out_labels[i] = glabels[i];
-    }
-    *out_count = cnt;
-    return VG_OK;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, true, &L, [&](int i, uint64_t *keys, uint32_t *labels, int *counts) {
+        return vg_scan_topk_grouped_keys(s->sh[(size_t)i], metric, query, k, keys, labels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, 0, out_rowids, out_dist, out_labels, out_count);
 }
+
+extern "C" int vg_shards_scan_topk_grouped_masked(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
+                                                  uint32_t *out_labels, int *out_count) {
+    int rc = fused_preamble(F_GROUPED_MASKED, s, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_grouped_masked(s->sh[0], metric, query, k, out_rowids, out_dist, out_labels, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, true, &L, [&](int i, uint64_t *keys, uint32_t *labels, int *counts) {
+        return vg_scan_topk_grouped_masked_keys(s->sh[(size_t)i], metric, query, k, keys, labels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, 0, out_rowids, out_dist, out_labels, out_count);
+}
+
+extern "C" int vg_shards_scan_topk_batch_grouped(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
+                                                 double *out_dist, uint32_t *out_labels, int *out_counts) {
+    int rc = fused_preamble(F_BATCH_GROUPED, s, queries, nq, k, 0, out_rowids && out_dist && out_labels, out_counts);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_batch_grouped(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, nq, (size_t)k, true, &L, [&](int i, uint64_t *keys, uint32_t *labels, int *counts) {
+        return vg_scan_topk_batch_grouped_keys(s->sh[(size_t)i], metric, queries, nq, k, keys, labels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, 0, out_rowids, out_dist, out_labels, out_counts);
+}
+
+extern "C" int vg_shards_scan_topk_batch_grouped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
+                                                        double *out_dist, uint32_t *out_labels, int *out_counts) {
+    int rc = fused_preamble(F_BATCH_GROUPED_MASKED, s, queries, nq, k, 0, out_rowids && out_dist && out_labels, out_counts);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_batch_grouped_masked(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, nq, (size_t)k, true, &L, [&](int i, uint64_t *keys, uint32_t *labels, int *counts) {
+        return vg_scan_topk_batch_grouped_masked_keys(s->sh[(size_t)i], metric, queries, nq, k, keys, labels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, 0, out_rowids, out_dist, out_labels, out_counts);
+}
+
+// capped scans: the k nearest rows, at most per_label of one label
+extern "C" int vg_shards_scan_topk_capped(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t *out_rowids,
+                                          double *out_dist, uint32_t *out_labels, int *out_count) {
+    int rc = fused_preamble(F_CAPPED, s, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_capped(s->sh[0], metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, true, &L, [&](int i, uint64_t *keys, uint32_t *labels, int *counts) {
+        return vg_scan_topk_capped_keys(s->sh[(size_t)i], metric, query, k, per_label, keys, labels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, per_label, out_rowids, out_dist, out_labels, out_count);
+}
+
+extern "C" int vg_shards_scan_topk_capped_masked(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t *out_rowids,
+                                                 double *out_dist, uint32_t *out_labels, int *out_count) {
+    int rc = fused_preamble(F_CAPPED_MASKED, s, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_capped_masked(s->sh[0], metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, true, &L, [&](int i, uint64_t *keys, uint32_t *labels, int *counts) {
+        return vg_scan_topk_capped_masked_keys(s->sh[(size_t)i], metric, query, k, per_label, keys, labels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, per_label, out_rowids, out_dist, out_labels, out_count);
+}
+
+extern "C" int vg_shards_scan_topk_batch_capped(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
+                                                double *out_dist, uint32_t *out_labels, int *out_counts) {
+    int rc = fused_preamble(F_BATCH_CAPPED, s, queries, nq, k, per_label, out_rowids && out_dist && out_labels, out_counts);
+    if (rc == FUSED_ONE_SHARD)
+        return vg_scan_topk_batch_capped(s->sh[0], metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, nq, (size_t)k, true, &L, [&](int i, uint64_t *keys, uint32_t *labels, int *counts) {
+        return vg_scan_topk_batch_capped_keys(s->sh[(size_t)i], metric, queries, nq, k, per_label, keys, labels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, per_label, out_rowids, out_dist, out_labels, out_counts);
+}
+
+extern "C" int vg_shards_scan_topk_batch_capped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
+                                                       double *out_dist, uint32_t *out_labels, int *out_counts) {
+    int rc = fused_preamble(F_BATCH_CAPPED_MASKED, s, queries, nq, k, per_label, out_rowids && out_dist && out_labels, out_counts);
+    if (rc == FUSED_ONE_SHARD)
+        return vg_scan_topk_batch_capped_masked(s->sh[0], metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, nq, (size_t)k, true, &L, [&](int i, uint64_t *keys, uint32_t *labels, int *counts) {
+        return vg_scan_topk_batch_capped_masked_keys(s->sh[(size_t)i], metric, queries, nq, k, per_label, keys, labels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, per_label, out_rowids, out_dist, out_labels, out_counts);
+}
+
 extern "C" int vg_shards_scan_topk_grouped_labelset(vg_shards *s, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels,
                                                     int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
-    return shards_labelset_grouped(s, "vg_shards_scan_topk_grouped_labelset", 0, metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
+    int rc = fused_preamble(F_GROUPED_LABELSET, s, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
+    if (rc == FUSED_ONE_SHARD)
+        return vg_scan_topk_grouped_labelset(s->sh[0], metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, true, &L, [&](int i, uint64_t *keys, uint32_t *klabels, int *counts) {
+        return vg_scan_topk_grouped_labelset_keys(s->sh[(size_t)i], metric, query, k, labels, n_labels, exclude, keys, klabels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, 0, out_rowids, out_dist, out_labels, out_count);
 }
+
 extern "C" int vg_shards_scan_topk_capped_labelset(vg_shards *s, int metric, const void *query, int k, int per_label, const uint32_t *labels,
                                                    int64_t n_labels, int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels,
                                                    int *out_count) {
     if (out_count) *out_count = 0;
     if (per_label < 1) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_capped_labelset: per_label must be at least 1");
-    return shards_labelset_grouped(s, "vg_shards_scan_topk_capped_labelset", per_label, metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
+    int rc = fused_preamble(F_CAPPED_LABELSET, s, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
+    if (rc == FUSED_ONE_SHARD)
+        return vg_scan_topk_capped_labelset(s->sh[0], metric, query, k, per_label, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, true, &L, [&](int i, uint64_t *keys, uint32_t *klabels, int *counts) {
+        return vg_scan_topk_capped_labelset_keys(s->sh[(size_t)i], metric, query, k, per_label, labels, n_labels, exclude, keys, klabels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, per_label, out_rowids, out_dist, out_labels, out_count);
 }
+
 
 // ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): a cursor over GLOBAL scan order becomes one floor key per shard over ITS
 // positions - the cursor's distance image with "local rows of this shard in front of global position P" (local_rows_before) - every
@@ -1561,23 +1485,20 @@ struct AfterWho { const char *one, *batch; };
 static AfterWho after_who(bool masked) {
     return masked ? AfterWho{"vg_scan_topk_after_masked", "vg_scan_topk_batch_after_masked"} : AfterWho{"vg_scan_topk_after", "vg_scan_topk_batch_after"};
 }
-static int after_fail(int code, const char *who, const char *what) {
-    return fail(code, (std::string(who) + ": " + what).c_str());
-}
 // floors[i] for a (distance, rowid) cursor; every shard's rowids must be ascending (the rows are dealt out in global order)
 static int shard_floors_cursor(const vg_shards *s, const char *who, double after_dist, int64_t after_rowid, uint64_t *floors) {
-    if (after_dist != after_dist) return after_fail(VG_ERR_INVALID, who, "the cursor's distance is NaN");
+    if (after_dist != after_dist) return refuse(VG_ERR_INVALID, who, "the cursor's distance is NaN");
     int64_t P = 0;
     for (auto *c : s->sh) {
         const int64_t p = vg_corpus_rows_upto_rowid(c, after_rowid);
-        if (p == -2) return after_fail(VG_ERR_UNSUPPORTED, who, "the rowids are not ascending (no rowid order); page by key (the _keys form)");
+        if (p == -2) return refuse(VG_ERR_UNSUPPORTED, who, "the rowids are not ascending (no rowid order); page by key (the _keys form)");
         P += p;
     }
     // ascending inside every shard is not ascending in GLOBAL order: blocks are dealt out cyclically, so every block border is
     // compared too (n_rows / B lookups) - one corpus holding these rows would refuse them, and so do the shards
     for (int64_t g = s->B; g < s->n_rows; g += s->B)
         if (vg_shards_rowid_at(s, g - 1) >= vg_shards_rowid_at(s, g))
-            return after_fail(VG_ERR_UNSUPPORTED, who, "the rowids are not ascending in global order (no rowid order); page by key (the _keys form)");
+            return refuse(VG_ERR_UNSUPPORTED, who, "the rowids are not ascending in global order (no rowid order); page by key (the _keys form)");
     for (int i = 0; i < s->S; ++i) {
         int empty = 0;
         const int64_t local = std::min<int64_t>(local_rows_before(s, i, P), vg_corpus_rows(s->sh[(size_t)i]));
@@ -1588,8 +1509,8 @@ static int shard_floors_cursor(const vg_shards *s, const char *who, double after
 }
 // floors[i] for a cursor given as the last GLOBAL key of the previous page
 static int shard_floors_key(const vg_shards *s, const char *who, uint64_t after_key, uint64_t *floors) {
-    if (after_key == VG_KEY_EMPTY) return after_fail(VG_ERR_INVALID, who, "after_key is the empty key");
-    if (s->n_rows >= (1ll << 32)) return after_fail(VG_ERR_UNSUPPORTED, who, "keys over global positions need fewer than 2^32 rows");
+    if (after_key == VG_KEY_EMPTY) return refuse(VG_ERR_INVALID, who, "after_key is the empty key");
+    if (s->n_rows >= (1ll << 32)) return refuse(VG_ERR_UNSUPPORTED, who, "keys over global positions need fewer than 2^32 rows");
     const uint64_t g = after_key + 1ull;
     for (int i = 0; i < s->S; ++i) {
         const int64_t local = std::min<int64_t>(local_rows_before(s, i, (int64_t)(g & 0xFFFFFFFFull)), vg_corpus_rows(s->sh[(size_t)i]));
@@ -1602,29 +1523,24 @@ static int shard_floors_key(const vg_shards *s, const char *who, uint64_t after_
 static int shards_after_run(vg_shards *s, bool masked, int metric, const void *query, int k, const uint64_t *floors, int64_t *out_rowids,
                             double *out_dist, uint64_t *out_gkeys, int *out_count) {
     const char *who = after_who(masked).one;
-    if (k < 1) return after_fail(VG_ERR_INVALID, who, "k must be at least 1");
-    if (k > VG_WAVE_KEYS) return after_fail(VG_ERR_UNSUPPORTED, who, "k must be in 1..64 (paged scans use the fused list only)");
-    if (masked && vg_shards_mask_count(s) < 0) return after_fail(VG_ERR_INVALID, who, "no row mask set");
-    std::vector<uint64_t> keys((size_t)s->S * VG_WAVE_KEYS, VG_KEY_EMPTY);
-    std::vector<int> counts((size_t)s->S, 0);
-    int rc = for_each_shard(s, [&](int i) {
-        return vg_after_floor_run(s->sh[(size_t)i], masked, metric, query, k, floors[i], &keys[(size_t)i * VG_WAVE_KEYS], &counts[(size_t)i]);
+    if (k < 1) return refuse(VG_ERR_INVALID, who, "k must be at least 1");
+    if (k > VG_WAVE_KEYS) return refuse(VG_ERR_UNSUPPORTED, who, "k must be in 1..64 (paged scans use the fused list only)");
+    if (masked && vg_shards_mask_count(s) < 0) return refuse(VG_ERR_INVALID, who, "no row mask set");
+    ShardLists L;
+    const int rc = gather_lists(s, 1, VG_WAVE_KEYS, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_after_floor_run(s->sh[(size_t)i], masked, metric, query, k, floors[i], keys, counts);
     });
-    if (rc != VG_OK) return rc;
-    int64_t ids[VG_WAVE_KEYS];
-    double dist[VG_WAVE_KEYS];
-    *out_count = merge_lists(s, keys.data(), VG_WAVE_KEYS, counts.data(), 1, k, out_rowids ? out_rowids : ids, out_dist ? out_dist : dist, -1, out_gkeys);
-    return VG_OK;
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, out_gkeys, out_count);
 }
 
 static int shards_after(vg_shards *s, bool masked, int metric, const void *query, int k, double after_dist, int64_t after_rowid,
                         int64_t *out_rowids, double *out_dist, int *out_count) {
     const char *who = after_who(masked).one;
-    if (!s || !query || !out_count) return after_fail(VG_ERR_INVALID, who, "NULL argument");
+    if (!s || !query || !out_count) return refuse(VG_ERR_INVALID, who, "NULL argument");
     if (s->S == 1) return masked ? vg_scan_topk_after_masked(s->sh[0], metric, query, k, after_dist, after_rowid, out_rowids, out_dist, out_count)
                                  : vg_scan_topk_after(s->sh[0], metric, query, k, after_dist, after_rowid, out_rowids, out_dist, out_count);
     *out_count = 0;
-    if (k >= 1 && k <= VG_WAVE_KEYS && (!out_rowids || !out_dist)) return after_fail(VG_ERR_INVALID, who, "NULL output");
+    if (k >= 1 && k <= VG_WAVE_KEYS && (!out_rowids || !out_dist)) return refuse(VG_ERR_INVALID, who, "NULL output");
     std::vector<uint64_t> floors((size_t)s->S, VG_KEY_EMPTY);
     int rc = shard_floors_cursor(s, who, after_dist, after_rowid, floors.data());
     if (rc != VG_OK) return rc;
@@ -1632,11 +1548,11 @@ static int shards_after(vg_shards *s, bool masked, int metric, const void *query
 }
 static int shards_after_keys(vg_shards *s, bool masked, int metric, const void *query, int k, uint64_t after_key, uint64_t *out_keys, int *out_count) {
     const char *who = after_who(masked).one;
-    if (!s || !query || !out_count) return after_fail(VG_ERR_INVALID, who, "NULL argument");
+    if (!s || !query || !out_count) return refuse(VG_ERR_INVALID, who, "NULL argument");
     if (s->S == 1) return masked ? vg_scan_topk_after_masked_keys(s->sh[0], metric, query, k, after_key, out_keys, out_count)
                                  : vg_scan_topk_after_keys(s->sh[0], metric, query, k, after_key, out_keys, out_count);
     *out_count = 0;
-    if (k >= 1 && k <= VG_WAVE_KEYS && !out_keys) return after_fail(VG_ERR_INVALID, who, "NULL output");
+    if (k >= 1 && k <= VG_WAVE_KEYS && !out_keys) return refuse(VG_ERR_INVALID, who, "NULL output");
     std::vector<uint64_t> floors((size_t)s->S, VG_KEY_EMPTY);
     int rc = shard_floors_key(s, who, after_key, floors.data());
     if (rc != VG_OK) return rc;
@@ -1647,33 +1563,25 @@ static int shards_after_keys(vg_shards *s, bool masked, int metric, const void *
 static int shards_after_batch_run(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                                   int64_t *out_rowids, double *out_dist, uint64_t *out_gkeys, int *out_counts) {
     const char *who = after_who(masked).batch;
-    if (k < 1) return after_fail(VG_ERR_INVALID, who, "k must be at least 1");
-    if (k > VG_WAVE_KEYS) return after_fail(VG_ERR_UNSUPPORTED, who, "k must be in 1..64 (paged scans use the fused list only)");
-    if (masked && vg_shards_mask_count(s) < 0) return after_fail(VG_ERR_INVALID, who, "no row mask set");
-    std::vector<uint64_t> keys((size_t)s->S * nq * k, VG_KEY_EMPTY);
-    std::vector<int> counts((size_t)s->S * nq, 0);
-    int rc = for_each_shard(s, [&](int i) {
-        return vg_after_floor_batch_run(s->sh[(size_t)i], masked, metric, queries, nq, k, floors + (size_t)i * nq, &keys[(size_t)i * nq * k],
-                                        &counts[(size_t)i * nq]);
+    if (k < 1) return refuse(VG_ERR_INVALID, who, "k must be at least 1");
+    if (k > VG_WAVE_KEYS) return refuse(VG_ERR_UNSUPPORTED, who, "k must be in 1..64 (paged scans use the fused list only)");
+    if (masked && vg_shards_mask_count(s) < 0) return refuse(VG_ERR_INVALID, who, "no row mask set");
+    ShardLists L;
+    const int rc = gather_lists(s, nq, (size_t)k, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_after_floor_batch_run(s->sh[(size_t)i], masked, metric, queries, nq, k, floors + (size_t)i * nq, keys, counts);
     });
-    if (rc != VG_OK) return rc;
-    int64_t ids[VG_WAVE_KEYS];
-    double dist[VG_WAVE_KEYS];
-    for (int q = 0; q < nq; ++q)
-        out_counts[q] = merge_query_lists(s, keys.data(), counts.data(), nq, q, k, k, out_rowids ? out_rowids + (size_t)q * k : ids,
-                                          out_dist ? out_dist + (size_t)q * k : dist, -1, out_gkeys ? out_gkeys + (size_t)q * k : nullptr);
-    return VG_OK;
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, out_gkeys, out_counts);
 }
 
 static int shards_after_batch(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, const double *after_dists,
                               const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts) {
     const char *who = after_who(masked).batch;
-    if (!s || !queries || !out_counts || !after_dists || !after_rowids) return after_fail(VG_ERR_INVALID, who, "NULL argument");
+    if (!s || !queries || !out_counts || !after_dists || !after_rowids) return refuse(VG_ERR_INVALID, who, "NULL argument");
     if (s->S == 1) return masked ? vg_scan_topk_batch_after_masked(s->sh[0], metric, queries, nq, k, after_dists, after_rowids, out_rowids, out_dist, out_counts)
                                  : vg_scan_topk_batch_after(s->sh[0], metric, queries, nq, k, after_dists, after_rowids, out_rowids, out_dist, out_counts);
-    if (nq < 1) return after_fail(VG_ERR_INVALID, who, "nq must be at least 1");
+    if (nq < 1) return refuse(VG_ERR_INVALID, who, "nq must be at least 1");
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (k >= 1 && k <= VG_WAVE_KEYS && (!out_rowids || !out_dist)) return after_fail(VG_ERR_INVALID, who, "NULL output");
+    if (k >= 1 && k <= VG_WAVE_KEYS && (!out_rowids || !out_dist)) return refuse(VG_ERR_INVALID, who, "NULL output");
     std::vector<uint64_t> floors((size_t)s->S * nq, VG_KEY_EMPTY), one((size_t)s->S);
     for (int q = 0; q < nq; ++q) {
         int rc = shard_floors_cursor(s, who, after_dists[q], after_rowids[q], one.data());
@@ -1685,12 +1593,12 @@ static int shards_after_batch(vg_shards *s, bool masked, int metric, const void 
 static int shards_after_batch_keys(vg_shards *s, bool masked, int metric, const void *queries, int nq, int k, const uint64_t *after_keys,
                                    uint64_t *out_keys, int *out_counts) {
     const char *who = after_who(masked).batch;
-    if (!s || !queries || !out_counts || !after_keys) return after_fail(VG_ERR_INVALID, who, "NULL argument");
+    if (!s || !queries || !out_counts || !after_keys) return refuse(VG_ERR_INVALID, who, "NULL argument");
     if (s->S == 1) return masked ? vg_scan_topk_batch_after_masked_keys(s->sh[0], metric, queries, nq, k, after_keys, out_keys, out_counts)
                                  : vg_scan_topk_batch_after_keys(s->sh[0], metric, queries, nq, k, after_keys, out_keys, out_counts);
-    if (nq < 1) return after_fail(VG_ERR_INVALID, who, "nq must be at least 1");
+    if (nq < 1) return refuse(VG_ERR_INVALID, who, "nq must be at least 1");
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (k >= 1 && k <= VG_WAVE_KEYS && !out_keys) return after_fail(VG_ERR_INVALID, who, "NULL output");
+    if (k >= 1 && k <= VG_WAVE_KEYS && !out_keys) return refuse(VG_ERR_INVALID, who, "NULL output");
     std::vector<uint64_t> floors((size_t)s->S * nq, VG_KEY_EMPTY), one((size_t)s->S);
     for (int q = 0; q < nq; ++q) {
         int rc = shard_floors_key(s, who, after_keys[q], one.data());
