@@ -470,6 +470,45 @@ int     vg_scan_within_masked(vg_corpus *c, int metric, const void *query, doubl
 int     vg_scan_within_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                     int64_t *out_matches, int64_t *out_held);
 
+/* ---- labeled range scans: every row of a label within a distance of the query - "every row of this tenant within r" for a caller
+ * who keeps tenants as labels: no bitmap per tenant, no upload per request, and in a batch a different tenant per query (no
+ * reference entry point).  The labels are those of the labeled scans (vg_corpus_set_labels).  The contract is the conjunction of
+ * vg_scan_within's and the labeled scans': a row matches when it carries an ALLOWED label AND its distance d - the float
+ * vg_scan_distances reports for it, bit for bit - satisfies (double)d <= radius; NaN and +Inf distances never match, whatever the
+ * radius; a row without a label (VG_LABEL_NONE) never matches; the radius is turned into the largest float not above it.  Order:
+ * ascending (distance, scan position), whatever the handle's tie_order.  limit > 0: the first `limit` matches in that order are held
+ * (per query), *out_matches still counts all of them; limit <= 0: all are held.  The row mask is neither read nor written.
+ * vg_scan_within_labeled: allowed = labels[p] == label.  vg_scan_within_labelset: the set semantics of vg_scan_topk_labelset - order
+ * and duplicates mean nothing, VG_LABEL_NONE in the set is VG_ERR_INVALID, exclude == 0: allowed iff the row's label is in the set
+ * (an empty set allows nothing: counts 0, no launch), exclude != 0: iff the row carries a label that is NOT in the set (an empty set:
+ * every labeled row).  Both: a small kernel turns (labels, label or set) into a bitmap in the scratch buffer the labeled scans use,
+ * then the single masked range kernels run over it (no scan kernels of their own: the distances are vg_scan_within_masked's, bit for
+ * bit, where both see the row) - two launches on the corpus stream, the scan once more when the result outgrew the device buffer.
+ * They leave their result where vg_scan_within leaves its own and overwrite it (and the reverse): read it with vg_scan_within_fetch
+ * / _keys.
+ * vg_scan_within_batch_labeled: nq queries (row-major nq x dim, host), query i's answer is what vg_scan_within_labeled(c, metric,
+ * q_i, radii[i], limit, query_labels[i], ..) is contracted to return, at the caller's index i; out_matches / out_held nq (either may
+ * be NULL).  A query whose label is VG_LABEL_NONE: the rule of vg_scan_topk_batch_labeled - the whole call is VG_ERR_INVALID, with
+ * every count zeroed first and nothing launched.  f32 / uint8 / int8 rows of a register-resident shape: the queries are ordered by
+ * label, then 4 (or 2) of them share every row load of a pass; a row is computed once with its batch and compared only against the
+ * radii of the queries whose label it carries, and a batch of rows that carries none of the pass' labels is not read (vg_scan_multi.h,
+ * labeled range form; the plan: vg_within_batch_labeled_plan, vectorgpu_diag.h); slices, key budget and the "a pass that overflowed
+ * runs once more as a whole" rule as in vg_scan_within_batch.  uint8 / int8: rowids, order, distance bits and counts identical to nq
+ * vg_scan_within_labeled calls.  f32: the single scan's arithmetic per (query, row) pair under the multi-query launch shape - for a
+ * row of the query's label, vg_scan_within_batch's float, bit for bit.  f16 / bf16, long rows and every other shape without a
+ * multi-query form: nq single vg_scan_within_labeled calls whose results are copied into the per-query storage.  It leaves its
+ * results where vg_scan_within_batch leaves its own and overwrites them (and the reverse): read them with vg_scan_within_batch_fetch
+ * / _keys.  The single and the batch form keep their results apart.  Timings not measured yet.
+ * No labels set: VG_ERR_INVALID; label == VG_LABEL_NONE: VG_ERR_INVALID; a NaN radius: VG_ERR_INVALID before any launch; an unknown
+ * metric, a NULL c / query / queries / query_labels / radii or nq < 1: VG_ERR_INVALID - each with the counts zeroed first.  An empty
+ * corpus or a label no row carries: every count 0 (the empty corpus without a launch). */
+int     vg_scan_within_labeled(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, uint32_t label,
+                               int64_t *out_matches, int64_t *out_held);
+int     vg_scan_within_labelset(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, const uint32_t *labels,
+                                int64_t n_labels, int exclude, int64_t *out_matches, int64_t *out_held);
+int     vg_scan_within_batch_labeled(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *query_labels,
+                                     const double *radii, int64_t limit, int64_t *out_matches, int64_t *out_held);
+
 /* ---- paged scans: the next k rows behind a (distance, rowid) cursor ("search after"; the reference's surface has LIMIT k OFFSET m,
  * a top-(m + k) scan) ----
  * A cursor is (after_dist, after_rowid): the distance and rowid of the last row of the previous page.  The row at scan position p
@@ -658,6 +697,16 @@ int     vg_shards_scan_within_masked(vg_shards *s, int metric, const void *query
                                      int64_t *out_matches, int64_t *out_held);
 int     vg_shards_scan_within_batch_masked(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                            int64_t *out_matches, int64_t *out_held);
+/* the labeled range scans over every shard: labels mean the same on every shard - each shard answers over its own rows, merged like
+ * vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus holding all rows.  Same contract; the results are
+ * read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and overwrite what the other range forms held there (and
+ * the reverse). */
+int     vg_shards_scan_within_labeled(vg_shards *s, int metric, const void *query, double radius, int64_t limit, uint32_t label,
+                                      int64_t *out_matches, int64_t *out_held);
+int     vg_shards_scan_within_labelset(vg_shards *s, int metric, const void *query, double radius, int64_t limit, const uint32_t *labels,
+                                       int64_t n_labels, int exclude, int64_t *out_matches, int64_t *out_held);
+int     vg_shards_scan_within_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels,
+                                            const double *radii, int64_t limit, int64_t *out_matches, int64_t *out_held);
 /* the paged scans over every shard: the cursor is one over GLOBAL scan order - each shard gets the floor over its own positions
  * ("local rows of this shard in front of global position P", by the block-cyclic map) and the lists merge by (distance, GLOBAL scan
  * position): the rowids, order and distance bits of one corpus holding all rows.  Same contracts.  The _keys forms take and return keys

@@ -140,6 +140,12 @@ int vg_shards_within_batch_last_launches(const vg_shards *s);
  * vg_within_batch_plan (0 queries per pass = the fallback, one single masked range scan per query).  Shards: shard 0's plan. */
 int vg_within_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 int vg_shards_within_batch_masked_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
+/* labeled range scans (vg_scan_within_labeled, vg_scan_within_labelset, vg_scan_within_batch_labeled): capacities and launch counts
+ * are the other range forms' too (the bitmap pass of a single form is not counted: vg_within_last_launches counts scan kernels).
+ * vg_within_batch_labeled_plan: how vg_scan_within_batch_labeled would serve this corpus under `metric` - the outputs of
+ * vg_within_batch_plan (0 queries per pass = the fallback, one single labeled range scan per query).  Shards: shard 0's plan. */
+int vg_within_batch_labeled_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
+int vg_shards_within_batch_labeled_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 
 /* host-only: the same replay over n distances the caller holds (scan order); returns the count (<= k) or -1.
  * below_cap <= 0: the device path's candidate capacity. */

@@ -179,6 +179,15 @@ def _load():
         "vg_shards_scan_within_batch_masked": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
         "vg_within_batch_masked_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_shards_within_batch_masked_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        # labeled range scans: every row of a label (of a set of labels) within a distance; the batch: a label and a radius per query
+        "vg_scan_within_labeled": (i32, [vp, i32, vp, C.c_double, i64, C.c_uint32, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_scan_within_labelset": (i32, [vp, i32, vp, C.c_double, i64, vp, i64, i32, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_scan_within_batch_labeled": (i32, [vp, i32, vp, i32, vp, vp, i64, vp, vp]),
+        "vg_within_batch_labeled_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "vg_shards_scan_within_labeled": (i32, [vp, i32, vp, C.c_double, i64, C.c_uint32, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_shards_scan_within_labelset": (i32, [vp, i32, vp, C.c_double, i64, vp, i64, i32, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_shards_scan_within_batch_labeled": (i32, [vp, i32, vp, i32, vp, vp, i64, vp, vp]),
+        "vg_shards_within_batch_labeled_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_within_set_initial_capacity": (i32, [vp, i64]),
         "vg_within_last_launches": (i32, [vp]),
         "vg_shards_within_set_initial_capacity": (i32, [vp, i64]),
@@ -695,6 +704,14 @@ def within_batch_masked_plan(corpus, metric):
     return nq.value, lpr.value, u.value
 
 
+def within_batch_labeled_plan(corpus, metric):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_within_batch_labeled serves this corpus (or shard set) with; 0
+    queries per pass = one single labeled range scan per query (f16 / bf16, long rows) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(getattr(lib(), _wb_prefix(corpus) + "labeled_plan")(corpus.h, metric, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
+
+
 def set_within_batch_initial_capacity(corpus, keys_per_query):
     """keys the device region of each query of the next scan_within_batch calls starts with (0: the default) - vectorgpu_diag.h"""
     _check(getattr(lib(), _wb_prefix(corpus) + "set_initial_capacity")(corpus.h, int(keys_per_query)))
@@ -736,6 +753,42 @@ def _scan_within_batch(scan, fetch, h, metric, queries, radii, limit):
     return out
 
 
+class _WithinLabeledOps:
+    """the labeled range scans, shared by Corpus and Shards (`_sprefix`: vg_ / vg_shards_): every row that carries an allowed label
+    (set_labels) and lies within `radius` of the query, ascending (distance, scan position); return shapes are scan_within's and
+    scan_within_batch's, and the results are held where those hold theirs.  The row mask is neither read nor written"""
+
+    def _within_fetch(self, batch):
+        return getattr(lib(), self._sprefix + ("scan_within_batch_fetch" if batch else "scan_within_fetch"))
+
+    def scan_within_labeled(self, metric, query, radius, label, limit=None):
+        """scan_within among the rows whose label is `label`: (rowids, distances, matches)"""
+        fn = getattr(lib(), self._sprefix + "scan_within_labeled")
+        scan = lambda h, metric, q, r, lim, m, held: fn(h, metric, q, r, lim, int(label), m, held)
+        return _scan_within(scan, self._within_fetch(False), self.h, metric, query, radius, limit)
+
+    def scan_within_labelset(self, metric, query, radius, labels, exclude=False, limit=None):
+        """scan_within among the rows whose label is in `labels` - exclude=True: is a label and not in it; an empty set allows nothing
+        (exclude: every labeled row): (rowids, distances, matches)"""
+        lab = _labelset_u32(labels)
+        fn = getattr(lib(), self._sprefix + "scan_within_labelset")
+        scan = lambda h, metric, q, r, lim, m, held: fn(h, metric, q, r, lim, _ptr(lab), lab.size, 1 if exclude else 0, m, held)
+        return _scan_within(scan, self._within_fetch(False), self.h, metric, query, radius, limit)
+
+    def scan_within_batch_labeled(self, metric, queries, labels, radii, limit=None):
+        """scan_within_labeled for every row of `queries` with its own label and its own radius (a scalar radius is broadcast), in
+        shared passes: a list of (rowids, distances, matches) per query, in the caller's order"""
+        lab = _labels_u32(labels)
+        if lab.size != np.shape(queries)[0]:
+            raise ValueError("scan_within_batch_labeled takes one label per query")
+        fn = getattr(lib(), self._sprefix + "scan_within_batch_labeled")
+        scan = lambda h, metric, qs, nq, r, lim, m, held: fn(h, metric, qs, nq, _ptr(lab), r, lim, m, held)
+        return _scan_within_batch(scan, self._within_fetch(True), self.h, metric, queries, radii, limit)
+
+    def within_batch_labeled_plan(self, metric):
+        return within_batch_labeled_plan(self, metric)
+
+
 def _set_mask(obj, prefix, rows, bits, positions, rowids):
     """Corpus.set_mask / Shards.set_mask: bits | positions | rowids -> the handle's row mask; returns the rows allowed"""
     if (bits is not None) + (positions is not None) + (rowids is not None) != 1:
@@ -762,7 +815,7 @@ def _set_mask(obj, prefix, rows, bits, positions, rowids):
     return int(getattr(L, prefix + "_mask_count")(obj.h))
 
 
-class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps):
+class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeledOps):
     """One HBM-resident corpus shard (opaque vg_corpus handle)."""
     _lprefix, _sprefix = "vg_corpus", "vg_"
 
@@ -1086,7 +1139,7 @@ def device_memory(device=0):
     return f.value, t.value
 
 
-class Shards(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps):
+class Shards(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeledOps):
     """One logical corpus dealt block-cyclically over several devices of this process (opaque vg_shards handle)."""
     _lprefix, _sprefix = "vg_shards", "vg_shards_"
 

@@ -317,13 +317,17 @@ ScanArgs vg_scan_args(const vg_corpus *c, int metric, int acc, const VgShape &s,
 size_t vg_query_lds_bytes(const vg_corpus *c, const VgShape &s);   // the staged query in LDS (long rows: padded to whole slices)
 // the launch itself (VG_BLOCK threads), behind the dynamic-LDS attribute step a window above 64 KiB needs; enqueue only
 int vg_launch_scan_kernel(scan_fn_t fn, long long blocks, size_t smem, hipStream_t stream, const ScanArgs &a);
-// ---- the single range scan (vg_scan_within.hip: vg_within_run), shared by the unmasked and the masked form: which kernel table
-// (vg_pick_scan<Family> of the unit that holds the kernels), whether ScanArgs.mask is set and a mask required, whose name errors carry
+// ---- the single range scan (vg_scan_within.hip: vg_within_run), shared by the unmasked, the masked and the labeled forms: which
+// kernel table (vg_pick_scan<Family> of the unit that holds the kernels), whether ScanArgs.mask is set and a mask required, whose name
+// errors carry.  `labeled` (the labeled range scans, vg_scan_within_labeled.hip), as in VgFusedForm: the masked kernels run over
+// c->d_label_bits - the caller enqueued vg_label_bits_enqueue / vg_labelset_bits_enqueue in front - and labels are required, not a mask
 typedef scan_fn_t (*vg_pick_scan_fn_t)(int vtype, int acc, int U, bool long_rows);
-struct VgWithinForm { const char *who; vg_pick_scan_fn_t pick; bool masked; };
+struct VgWithinForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool labeled; };
 int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                   int64_t *out_held);
+scan_fn_t vg_pick_scan_within_masked(int vtype, int acc, int U, bool long_rows);   // vg_scan_within_masked.hip: the masked single range scan's kernel table
 scan_fn_t vg_pick_multi_within_masked(int vtype, int acc, int U, int NQ);   // vg_multi_within_masked.hip: the masked batch range scan's kernel table
+scan_fn_t vg_pick_multi_within_labeled(int vtype, int acc, int U, int NQ);  // vg_multi_within_labeled.hip: the labeled batch range scan's kernel table
 // ---- the fused top-k scan of a variant (k <= 64, ascending (distance, scan position) order), shared by the masked and the paged
 // scans: the kernel table, whether ScanArgs.mask is set and a mask required, whether ScanArgs.floor is, whose name errors carry.
 // vg_fused_run (vg_scan_masked.hip): one query; `floor` = the smallest key admitted (after forms).  vg_fused_batch_run

@@ -1,6 +1,6 @@
 // vg_multi.hip - host side of the multi-query scan (vg_scan_multi.h): shape choice, kernel table, launch.  Holds the instances of
 // its plain top-k form (MultiFamily<0>); each other form's instances are in a unit of their own (vg_multi_masked.hip,
-// vg_multi_after.hip, vg_multi_within.hip, vg_multi_within_masked.hip), so that the 60 instances per form compile next to each other
+// vg_multi_after.hip, vg_multi_within.hip, vg_multi_within_masked.hip, vg_multi_within_labeled.hip), so that the 60 instances per form compile next to each other
 // and to vg_api.hip's, not after them.
 #include "vg_internal.h"
 

@@ -16,27 +16,43 @@
 // The masked batch (vg_scan_within_batch_masked) is the same host code: its kernels are the VG_MQ_WITHIN | VG_MQ_MASKED instances, held by
 // vg_multi_within_masked.hip, its launches set ScanArgs.mask, its fallback is nq single MASKED range scans - nothing else differs, and
 // it leaves its held results where the unmasked batch leaves its own.
+//
+// The labeled batch (vg_scan_within_batch_labeled: each query its own label and its own radius) is the same host code once more: its
+// kernels are the VG_MQ_LABELED | VG_MQ_WITHIN instances, held by vg_multi_within_labeled.hip, its launches set ScanArgs.labels and
+// every query's label travels in its descriptor, its fallback is nq single labeled range scans (vg_scan_within_labeled.hip).  What is
+// its own is the entry point's: the queries are ordered by label (stable) before they are cut into passes, as in vg_multi_labeled.hip
+// - a pass' queries then share as few distinct labels as possible, which is what lets a pass skip the batches of rows that carry none
+// of them - and the held results are put back at the caller's indices.
 #include "vg_internal.h"
 
 #include "vg_scan_multi.h"
 #include "vg_pick.h"
 
-// (queries per pass, launch shape, kernel) of the multi-query range scan, unmasked or masked; 0 queries per pass: the fallback serves
-// the shape.  Every instance of both tables compiles without scratch or spills: the masked plan is the unmasked one.
-static int mw_plan(const vg_corpus *c, int metric, bool masked, VgShape *s, scan_fn_t *fn) {
+#include <numeric>
+
+// what differs between the unmasked, the masked and the labeled batch: whose name errors carry, whether the launches read the handle's
+// mask, whether they read its labels (then every query names one)
+struct WbForm { const char *who; bool masked; bool labeled; };
+
+// (queries per pass, launch shape, kernel) of the multi-query range scan, unmasked, masked or labeled; 0 queries per pass: the fallback
+// serves the shape.  Every instance of the three tables compiles without scratch or spills: the masked and
+// the labeled plan are the unmasked one.
+static int mw_plan(const vg_corpus *c, int metric, const WbForm &form, VgShape *s, scan_fn_t *fn) {
     const int NQ = vg_multi_plan(c, metric, s);
     if (NQ == 0) return 0;
     const int acc = vg_metric_to_acc(metric);
-    scan_fn_t f = masked ? vg_pick_multi_within_masked(c->vtype, acc, s->U, NQ) : vg_pick_multi<MultiFamily<VG_MQ_WITHIN>>(c->vtype, acc, s->U, NQ);
+    scan_fn_t f = form.labeled  ? vg_pick_multi_within_labeled(c->vtype, acc, s->U, NQ)
+                  : form.masked ? vg_pick_multi_within_masked(c->vtype, acc, s->U, NQ)
+                                : vg_pick_multi<MultiFamily<VG_MQ_WITHIN>>(c->vtype, acc, s->U, NQ);
     if (fn) *fn = f;
     return f ? NQ : 0;
 }
 
-static int within_batch_plan(const vg_corpus *c, int metric, bool masked, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+static int within_batch_plan(const vg_corpus *c, int metric, const WbForm &form, int *out_queries_per_pass, int *out_lpr, int *out_u) {
     if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     VgShape s{};
-    const int NQ = mw_plan(c, metric, masked, &s, nullptr);
+    const int NQ = mw_plan(c, metric, form, &s, nullptr);
     if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single range scan's
     if (out_queries_per_pass) *out_queries_per_pass = NQ;
     if (out_lpr) *out_lpr = s.long_rows ? VG_WAVE : (1 << s.lpr_log2);
@@ -44,10 +60,13 @@ static int within_batch_plan(const vg_corpus *c, int metric, bool masked, int *o
     return VG_OK;
 }
 extern "C" int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
-    return within_batch_plan(c, metric, false, out_queries_per_pass, out_lpr, out_u);
+    return within_batch_plan(c, metric, WbForm{"vg_within_batch_plan", false, false}, out_queries_per_pass, out_lpr, out_u);
 }
 extern "C" int vg_within_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
-    return within_batch_plan(c, metric, true, out_queries_per_pass, out_lpr, out_u);
+    return within_batch_plan(c, metric, WbForm{"vg_within_batch_masked_plan", true, false}, out_queries_per_pass, out_lpr, out_u);
+}
+extern "C" int vg_within_batch_labeled_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    return within_batch_plan(c, metric, WbForm{"vg_within_batch_labeled_plan", false, true}, out_queries_per_pass, out_lpr, out_u);
 }
 
 // queries go up in slices of this many (a multiple of every queries-per-pass): staging and key regions do not grow with the batch
@@ -71,14 +90,12 @@ static int ensure_dev(unsigned long long **p, size_t *have, size_t need) {
     return VG_OK;
 }
 
-// what differs between the unmasked and the masked batch: whose name errors carry, and whether the launches read the handle's mask
-struct WbForm { const char *who; bool masked; };
-
 // one pass: NQ queries + their descriptors at dev_block.  Asynchronous on the corpus stream.
 static int launch_multi_within(vg_corpus *c, const WbForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_block) {
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);      // the multi-query scan's launch shape
     ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_block, 0);
     if (f.masked) a.mask = c->d_mask;
+    if (f.labeled) a.labels = c->d_labels;                     // (the queries' labels are in their descriptors)
     a.store_lds_off = (int)(((size_t)NQ * c->nch * 16 + 255) / 256 * 256);     // the key queues behind the staged queries
     const size_t smem = (size_t)a.store_lds_off + (size_t)NQ * VG_WITHIN_LDS_BYTES;
     hipEvent_t *evs = vg_prof_slot(c, 0);                      // one slot of the profiling ring per pass
@@ -97,9 +114,9 @@ static int collect_keys(vg_corpus *c, int qi, const unsigned long long *dev_keys
     return vg_within_collect(c, dev_keys, count, limit, &c->wb_keys[(size_t)qi], pending);
 }
 
-// nq queries, NQ per pass
+// nq queries, NQ per pass; qlabels: a label per query (the labeled form, nullptr otherwise)
 static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries, int nq,
-                              const double *radii, int64_t limit) {
+                              const double *radii, const uint32_t *qlabels, int64_t limit) {
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
     const int slice = std::min(nq_pad, VG_WB_SLICE);
     const size_t block_bytes = (size_t)NQ * c->stride + (size_t)NQ * sizeof(VgWithinQuery);      // one pass: [NQ queries | NQ descriptors]
@@ -108,7 +125,7 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
                                 HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
     if (!c->d_wb_counts) HIP_TRY(hipMalloc(&c->d_wb_counts, (size_t)VG_WB_SLICE * sizeof(unsigned long long)));
     if (!c->h_wb) HIP_TRY(hipHostMalloc(&c->h_wb, (size_t)(VG_WB_SLICE + 8) * sizeof(unsigned long long)));
-    // zero-padded rows of the corpus stride; a pad query is zero with no capacity and a radius nothing is below.  The whole batch stays
+    // zero-padded rows of the corpus stride; a pad query is zero with no capacity, a radius nothing is below and no label.  The whole batch stays
     // on the host until the last wait: a slice's copy is ordered behind the passes of the slice in front of it by the stream
     std::vector<uint8_t> hq((size_t)ngroups * block_bytes, 0);
     const size_t row_bytes = (size_t)c->dim * c->es;
@@ -131,6 +148,7 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
             d->out = c->d_wb + (long long)j * pitch;
             d->cap = real ? (unsigned long long)cap : 0ull;
             d->r = real ? vg_within_radius(radii[q0 + j]) : -INFINITY;
+            d->label = (real && f.labeled) ? qlabels[q0 + j] : VG_LABEL_NONE;
         }
         HIP_TRY(hipMemcpyAsync(d_stage, block_of(q0), (size_t)(nqs / NQ) * block_bytes, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(vg_wb_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, c->d_wb, pitch, nqs, (unsigned long long *)nullptr);
@@ -190,10 +208,10 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
     return VG_OK;
 }
 
-static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *queries, int nq, const double *radii, int64_t limit,
-                        int64_t *out_matches, int64_t *out_held) {
+static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *queries, int nq, const double *radii, const uint32_t *qlabels,
+                        int64_t limit, int64_t *out_matches, int64_t *out_held) {
     for (int i = 0; i < nq; ++i) { if (out_matches) out_matches[i] = 0; if (out_held) out_held[i] = 0; }      // (every error leaves the counts zeroed)
-    if (!c || !queries || !radii) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
+    if (!c || !queries || !radii || (f.labeled && !qlabels)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     c->wb_keys.clear();
     c->wb_matches.clear();
     c->wb_launches = 0;
@@ -202,13 +220,18 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
     for (int i = 0; i < nq; ++i)
         if (radii[i] != radii[i]) return vg_fail(VG_ERR_INVALID, "%s: radius %d is NaN", f.who, i);
     if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (f.labeled) {
+        if (!c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+        for (int i = 0; i < nq; ++i)
+            if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: a query's label is VG_LABEL_NONE, which names no row", f.who);
+    }
     c->wb_keys.resize((size_t)nq);
     c->wb_matches.assign((size_t)nq, 0);
     if (c->n_rows == 0 || (f.masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
     HIP_TRY(hipSetDevice(c->device));
     VgShape s{};
     scan_fn_t fn = nullptr;
-    const int NQ = mw_plan(c, metric, f.masked, &s, &fn);
+    const int NQ = mw_plan(c, metric, f, &s, &fn);
     int rc = VG_OK;
     if (NQ == 0) {                                               // no multi-query form: the single range scans of the same form, one by one
         const size_t row_bytes = (size_t)c->dim * c->es;
@@ -220,7 +243,9 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
         for (int i = 0; i < nq && rc == VG_OK; ++i) {
             int64_t m = 0, h = 0;
             const void *q = (const uint8_t *)queries + (size_t)i * row_bytes;
-            rc = f.masked ? vg_scan_within_masked(c, metric, q, radii[i], limit, &m, &h) : vg_scan_within(c, metric, q, radii[i], limit, &m, &h);
+            rc = f.labeled  ? vg_scan_within_labeled(c, metric, q, radii[i], limit, qlabels[i], &m, &h)
+                 : f.masked ? vg_scan_within_masked(c, metric, q, radii[i], limit, &m, &h)
+                            : vg_scan_within(c, metric, q, radii[i], limit, &m, &h);
             if (rc != VG_OK) break;
             c->wb_keys[(size_t)i] = c->within_keys;
             c->wb_matches[(size_t)i] = m;
@@ -230,7 +255,7 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
         c->within_matches = single_matches;
         c->within_launches = single_launches;
     } else {
-        rc = batch_within_multi(c, f, metric, fn, NQ, s, queries, nq, radii, limit);
+        rc = batch_within_multi(c, f, metric, fn, NQ, s, queries, nq, radii, qlabels, limit);
     }
     if (rc != VG_OK) { c->wb_keys.clear(); c->wb_matches.clear(); return rc; }
     for (int i = 0; i < nq; ++i) {
@@ -242,12 +267,52 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
 
 extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                     int64_t *out_matches, int64_t *out_held) {
-    return within_batch(c, WbForm{"vg_scan_within_batch", false}, metric, queries, nq, radii, limit, out_matches, out_held);
+    return within_batch(c, WbForm{"vg_scan_within_batch", false, false}, metric, queries, nq, radii, nullptr, limit, out_matches, out_held);
 }
 
 extern "C" int vg_scan_within_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                            int64_t *out_matches, int64_t *out_held) {
-    return within_batch(c, WbForm{"vg_scan_within_batch_masked", true}, metric, queries, nq, radii, limit, out_matches, out_held);
+    return within_batch(c, WbForm{"vg_scan_within_batch_masked", true, false}, metric, queries, nq, radii, nullptr, limit, out_matches, out_held);
+}
+
+extern "C" int vg_scan_within_batch_labeled(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *query_labels,
+                                            const double *radii, int64_t limit, int64_t *out_matches, int64_t *out_held) {
+    const WbForm form = {"vg_scan_within_batch_labeled", false, true};
+    if (nq < 1 || !c || !queries || !radii || !query_labels)           // (nothing to order: the shared routine zeroes the counts and refuses)
+        return within_batch(c, form, metric, queries, nq, radii, query_labels, limit, out_matches, out_held);
+    // queries in label order (stable: equal labels keep caller order), their radii with them; everything else - argument checks
+    // included - is the shared routine's
+    std::vector<int> order((size_t)nq);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return query_labels[x] < query_labels[y]; });
+    const size_t row_bytes = (size_t)c->dim * c->es;
+    std::vector<uint8_t> sq((size_t)nq * row_bytes);
+    std::vector<uint32_t> sl((size_t)nq);
+    std::vector<double> sr((size_t)nq);
+    for (int i = 0; i < nq; ++i) {
+        const size_t src = (size_t)order[(size_t)i];
+        memcpy(sq.data() + (size_t)i * row_bytes, (const uint8_t *)queries + src * row_bytes, row_bytes);
+        sl[(size_t)i] = query_labels[src];
+        sr[(size_t)i] = radii[src];
+    }
+    for (int i = 0; i < nq; ++i) { if (out_matches) out_matches[i] = 0; if (out_held) out_held[i] = 0; }
+    int rc = within_batch(c, form, metric, sq.data(), nq, sr.data(), sl.data(), limit, nullptr, nullptr);
+    if (rc != VG_OK) return rc;
+    // held results and counts back at the caller's indices
+    std::vector<std::vector<uint64_t>> keys((size_t)nq);
+    std::vector<int64_t> matches((size_t)nq, 0);
+    for (int i = 0; i < nq; ++i) {
+        const size_t dst = (size_t)order[(size_t)i];
+        keys[dst].swap(c->wb_keys[(size_t)i]);
+        matches[dst] = c->wb_matches[(size_t)i];
+    }
+    c->wb_keys.swap(keys);
+    c->wb_matches.swap(matches);
+    for (int i = 0; i < nq; ++i) {
+        if (out_matches) out_matches[i] = c->wb_matches[(size_t)i];
+        if (out_held) out_held[i] = (int64_t)c->wb_keys[(size_t)i].size();
+    }
+    return VG_OK;
 }
 
 // the held keys of `query`, or nullptr (with the error set) when there is no such query

@@ -46,8 +46,16 @@
 //                        is folded into query n's offer predicate.  VG_LABEL_NONE (0xFFFFFFFF) matches nothing on either side: it
 //                        is folded into `owner`, so a pad query of a ragged pass (label NONE) collects nothing.
 //                    What the pipeline carries: three label dwords per lane (current, prefetched, in flight) and the current batch's
-//                    ballot - per-stage ballots PER QUERY would be 2 * NQ scalar registers a stage.  Not combined
-//                    with MASKED / AFTER / WITHIN.  Without the flag the label values are never defined and everything folds away.
+//                    ballot - per-stage ballots PER QUERY would be 2 * NQ scalar registers a stage.  Combined with
+//                    WITHIN only (next), not with MASKED / AFTER.  Without the flag the label values are never defined and everything
+//                    folds away.
+//   VG_MQ_LABELED | VG_MQ_WITHIN   the labeled range scan, each query its own label AND its own radius (vg_scan_within_batch_labeled,
+//                    vg_multi_within.hip): the LABELED pipeline, statement for statement, with WITHIN's compare-and-compact behind the
+//                    arithmetic.  `lcur == qlabel[n]` is folded into query n's match predicate - in the ballot that decides whether a
+//                    batch does more, and in vg_mw_offer.  The query's label travels in its VgWithinQuery descriptor (12 of its bytes
+//                    were spare) and is read with the radius by a scalar load: a.qlabels is not read, ScanArgs keeps its size and every
+//                    field its offset.  A pad query of a ragged pass: label NONE, capacity 0, radius -Inf.  The instances are
+//                    vg_multi_within_labeled.hip's; DESIGN.md 3.21 has their registers and the ones left out.
 //   VG_MQ_LABELSET   a SET of labels per query (allowed or excluded; vg_multi_labelset.hip): the LABELED pipeline, statement for
 //                    statement, with other predicates.  The per-lane dword loaded one step ahead of the row prefetch is the row's
 //                    MEMBERSHIP word - a.labels points at the membership buffer a pre-pass filled for a group of up to 32 queries
@@ -80,11 +88,12 @@
 //   a.query         : NQ zero-padded queries back to back (nch * 16 bytes each); WITHIN: and BEHIND them NQ VgWithinQuery descriptors
 //   a.mask          : (MASKED) ceil(n_rows / 64) words, bits behind the last row clear
 //   a.floor         : (AFTER) NQ keys
-//   a.labels        : (LABELED, GROUPED) n_rows dwords;  a.qlabels : (LABELED) NQ dwords
+//   a.labels        : (LABELED, GROUPED) n_rows dwords;  a.qlabels : (LABELED without WITHIN) NQ dwords
 //                     (LABELSET) n_rows membership dwords
 //   a.within_cap    : (CAPPED) the cap m, 1 .. k;  (LABELSET) the pass' bit offset inside its membership group
 //   a.cand          : (top-k forms) [NQ][gridDim.x][64] candidate keys
-//   descriptor n    : (WITHIN) the [count | cap keys] region of query n, its capacity and its radius (a float: the host rounds down)
+//   descriptor n    : (WITHIN) the [count | cap keys] region of query n, its capacity and its radius (a float: the host rounds down);
+//                     (LABELED | WITHIN) and its label
 //   a.store_lds_off : (WITHIN) byte offset in dynamic LDS of the key queues, [NQ][wavefront][VG_WITHIN_QUEUE]
 // Register budget: NQ * U query chunks + 2 * U row chunks per lane -> NQ = 4 with U <= 3, NQ = 2 with U <= 6.  The mask lives in scalar
 // registers (three words of bits: current, prefetched, in flight, and the mask pointer).  A range form does without the two 64-bit
@@ -101,7 +110,8 @@ struct VgWithinQuery {                 // 32 bytes, read through wave-uniform ad
     unsigned long long *out;           // [count | cap keys]; the count keeps counting past cap
     unsigned long long cap;
     float r;                           // rows with d <= r and d finite match
-    uint32_t pad[3];
+    uint32_t label;                    // (LABELED | WITHIN) ... and this label; no other range form reads it
+    uint32_t pad[2];
 };
 
 // Kernel-local forms of vg_within_offer / vg_within_flush (vg_scan.h, which the single range scan keeps as it is): the same protocol -
@@ -132,7 +142,7 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
     constexpr bool MASKED = (FORM & VG_MQ_MASKED) != 0, AFTER = (FORM & VG_MQ_AFTER) != 0, WITHIN = (FORM & VG_MQ_WITHIN) != 0;
     constexpr bool LABELED = (FORM & VG_MQ_LABELED) != 0, GROUPED = (FORM & VG_MQ_GROUPED) != 0, CAPPED = (FORM & VG_MQ_CAPPED) != 0;
     static_assert(!(AFTER && WITHIN), "a range scan has no cursor");
-    static_assert(!LABELED || FORM == VG_MQ_LABELED, "the labeled form is not combined with the masked, paged or range forms");
+    static_assert(!LABELED || FORM == VG_MQ_LABELED || FORM == (VG_MQ_LABELED | VG_MQ_WITHIN), "the labeled form is combined with the range form only");
     static_assert(!GROUPED || (FORM & ~(VG_MQ_MASKED | VG_MQ_CAPPED)) == VG_MQ_GROUPED, "the grouped form is combined with the mask and the cap only");
     static_assert(!CAPPED || GROUPED, "a capped scan is the grouped form with a cap");
     constexpr bool LABELSET = (FORM & VG_MQ_LABELSET) != 0;
@@ -184,7 +194,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
         }
     }
     uint32_t qlabel[NQ];                                               // LABELED: wave-uniform, scalar registers
-    if constexpr (LABELED) {
+    if constexpr (LABELED && WITHIN) {                                 // (the label travels with the radius, in the query's descriptor)
+#pragma unroll
+        for (int n = 0; n < NQ; ++n) qlabel[n] = (uint32_t)__builtin_amdgcn_readfirstlane((int)wq[n].label);
+    } else if constexpr (LABELED) {
 #pragma unroll
         for (int n = 0; n < NQ; ++n) qlabel[n] = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.qlabels[n]);
     }
@@ -274,7 +287,10 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
                 if constexpr (WITHIN) {
                     d[n] = dn;
                     // d <= r is false for NaN; +Inf never matches, whatever the radius (the single range scan's rule)
-                    any |= __ballot(owner && (d[n] <= r[n]) && (d[n] < INFINITY));
+                    // (LABELED: and the row carries query n's label.  A branch of its own: the other range forms keep their expression,
+                    //  and with it the code the compiler made of it)
+                    if constexpr (LABELED) any |= __ballot(owner && (d[n] <= r[n]) && (d[n] < INFINITY) && (lcur == qlabel[n]));
+                    else any |= __ballot(owner && (d[n] <= r[n]) && (d[n] < INFINITY));
                 } else {
                     // (a top-k form uses the distance at once, NOT through d[]: with it the ten f32 L1 floor instances came out with
                     //  another, equivalent, predicate sequence than the copies had)
@@ -296,8 +312,12 @@ __global__ __launch_bounds__(VG_BLOCK) void vg_scan_multi_kernel(ScanArgs a) {
                 const VgWithinQuery *w = wq;
                 asm volatile("" : "+s"(w));
 #pragma unroll
-                for (int n = 0; n < NQ; ++n)
-                    vg_mw_offer(vg_make_key(d[n], (uint32_t)row), owner && (d[n] <= r[n]) && (d[n] < INFINITY), queue[n], queued[n], w[n].out, w[n].cap, ln);
+                for (int n = 0; n < NQ; ++n) {
+                    if constexpr (LABELED)
+                        vg_mw_offer(vg_make_key(d[n], (uint32_t)row), owner && (d[n] <= r[n]) && (d[n] < INFINITY) && (lcur == qlabel[n]), queue[n], queued[n], w[n].out, w[n].cap, ln);
+                    else
+                        vg_mw_offer(vg_make_key(d[n], (uint32_t)row), owner && (d[n] <= r[n]) && (d[n] < INFINITY), queue[n], queued[n], w[n].out, w[n].cap, ln);
+                }
             }
         }
 #pragma unroll

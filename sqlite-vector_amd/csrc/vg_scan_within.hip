@@ -13,7 +13,8 @@
 // The result path - radius rounding, the sort's buffers, "count keys on the device -> held, sorted, cut to limit", the readers of a held
 // result - is here ONCE and serves the batch form (vg_multi_within.hip) too; each form keeps its own held result on the handle.
 // So is the single scan itself (vg_within_run): the masked range scan (vg_scan_within_masked.hip) is this code with its own kernel
-// table and ScanArgs.mask set, and leaves its result where vg_scan_within leaves its own.
+// table and ScanArgs.mask set, and leaves its result where vg_scan_within leaves its own; the labeled range scans
+// (vg_scan_within_labeled.hip) are the masked one over a bitmap of their own making.
 #include "vg_internal.h"
 
 #include "vg_scan.h"
@@ -108,6 +109,7 @@ static int launch_within(vg_corpus *c, const VgWithinForm &f, int metric, float 
     a.within_r = r;
     a.within_cap = (unsigned long long)cap;
     if (f.masked) a.mask = c->d_mask;
+    if (f.labeled) a.mask = c->d_label_bits;                 // (the bitmap of a label or a label set, built on this stream in front of the scan)
     a.store_lds_off = (int)((vg_query_lds_bytes(c, s) + 255) / 256 * 256);     // the wavefronts' key queues behind the query
     const size_t smem = (size_t)a.store_lds_off + VG_WITHIN_LDS_BYTES;
 
@@ -131,7 +133,7 @@ static int ensure_within_buffer(vg_corpus *c, int64_t cap) {
     return VG_OK;
 }
 
-// a single range scan, unmasked or masked (VgWithinForm, vg_internal.h): argument checks, launch, the overflow protocol, the held result
+// a single range scan, unmasked, masked or labeled (VgWithinForm, vg_internal.h): argument checks, launch, the overflow protocol, the held result
 int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                   int64_t *out_held) {
     if (out_matches) *out_matches = 0;
@@ -143,6 +145,7 @@ int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *q
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (radius != radius) return vg_fail(VG_ERR_INVALID, "%s: the radius is NaN", f.who);
     if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (f.labeled && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
     if (c->n_rows == 0 || (f.masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
     HIP_TRY(hipSetDevice(c->device));
     c->enqueued = false;                                     // (the pinned key buffer is this scan's landing zone now)

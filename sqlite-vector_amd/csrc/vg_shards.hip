@@ -896,19 +896,29 @@ static int fetch_within(const vg_shards *s, const char *who, const std::vector<v
     return VG_OK;
 }
 
-// the single form, unmasked or masked (every shard over its own bits; a shard whose share of the mask is empty launches nothing)
-static int shards_within(vg_shards *s, bool masked, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
-                         int64_t *out_held) {
-    const char *who = masked ? "vg_shards_scan_within_masked" : "vg_shards_scan_within";
-    auto scan = masked ? vg_scan_within_masked : vg_scan_within;
+// which range form a call over shards stands for: whose names errors carry (the shards' entry point, the per-corpus one), and what
+// every shard must hold - a mask (masked forms: every shard over its own bits; a shard whose share of the mask is empty launches
+// nothing) or labels (labeled forms: labels mean the same on every shard)
+struct WithinShardForm { const char *who; const char *inner; bool masked; bool labeled; };
+
+static int within_shard_refusal(const vg_shards *s, const WithinShardForm &f) {
+    if (f.masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, (std::string(f.inner) + ": no row mask set").c_str());
+    if (f.labeled && !vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, (std::string(f.inner) + ": no labels set").c_str());
+    return VG_OK;
+}
+
+// the single forms; scan(corpus, out_matches, out_held): the form's range scan over one shard
+template <typename Scan>
+static int shards_within(vg_shards *s, const WithinShardForm &f, const void *query, int64_t limit, int64_t *out_matches, int64_t *out_held, Scan scan) {
     if (out_matches) *out_matches = 0;
     if (out_held) *out_held = 0;
-    if (!s || !query) return fail(VG_ERR_INVALID, (std::string(who) + ": NULL argument").c_str());
-    if (s->S == 1) return scan(s->sh[0], metric, query, radius, limit, out_matches, out_held);
+    if (!s || !query) return fail(VG_ERR_INVALID, (std::string(f.who) + ": NULL argument").c_str());
+    if (s->S == 1) return scan(s->sh[0], out_matches, out_held);
     s->within_hits.clear();
-    if (masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_within_masked: no row mask set");
+    int rc = within_shard_refusal(s, f);
+    if (rc != VG_OK) return rc;
     std::vector<int64_t> matches((size_t)s->S, 0), held((size_t)s->S, 0);
-    int rc = for_each_shard(s, [&](int i) { return scan(s->sh[(size_t)i], metric, query, radius, limit, &matches[(size_t)i], &held[(size_t)i]); });
+    rc = for_each_shard(s, [&](int i) { return scan(s->sh[(size_t)i], &matches[(size_t)i], &held[(size_t)i]); });
     if (rc != VG_OK) return rc;
     int64_t total = 0;
     rc = merge_within(s, matches.data(), held.data(), 1, limit,
@@ -921,12 +931,31 @@ static int shards_within(vg_shards *s, bool masked, int metric, const void *quer
 
 extern "C" int vg_shards_scan_within(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                                      int64_t *out_held) {
-    return shards_within(s, false, metric, query, radius, limit, out_matches, out_held);
+    const WithinShardForm f = {"vg_shards_scan_within", "vg_scan_within", false, false};
+    return shards_within(s, f, query, limit, out_matches, out_held,
+                         [&](vg_corpus *c, int64_t *m, int64_t *h) { return vg_scan_within(c, metric, query, radius, limit, m, h); });
 }
 
 extern "C" int vg_shards_scan_within_masked(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                                             int64_t *out_held) {
-    return shards_within(s, true, metric, query, radius, limit, out_matches, out_held);
+    const WithinShardForm f = {"vg_shards_scan_within_masked", "vg_scan_within_masked", true, false};
+    return shards_within(s, f, query, limit, out_matches, out_held,
+                         [&](vg_corpus *c, int64_t *m, int64_t *h) { return vg_scan_within_masked(c, metric, query, radius, limit, m, h); });
+}
+
+extern "C" int vg_shards_scan_within_labeled(vg_shards *s, int metric, const void *query, double radius, int64_t limit, uint32_t label,
+                                             int64_t *out_matches, int64_t *out_held) {
+    const WithinShardForm f = {"vg_shards_scan_within_labeled", "vg_scan_within_labeled", false, true};
+    return shards_within(s, f, query, limit, out_matches, out_held,
+                         [&](vg_corpus *c, int64_t *m, int64_t *h) { return vg_scan_within_labeled(c, metric, query, radius, limit, label, m, h); });
+}
+
+extern "C" int vg_shards_scan_within_labelset(vg_shards *s, int metric, const void *query, double radius, int64_t limit, const uint32_t *labels,
+                                              int64_t n_labels, int exclude, int64_t *out_matches, int64_t *out_held) {
+    const WithinShardForm f = {"vg_shards_scan_within_labelset", "vg_scan_within_labelset", false, true};
+    return shards_within(s, f, query, limit, out_matches, out_held, [&](vg_corpus *c, int64_t *m, int64_t *h) {
+        return vg_scan_within_labelset(c, metric, query, radius, limit, labels, n_labels, exclude, m, h);
+    });
 }
 
 extern "C" int vg_shards_scan_within_fetch(const vg_shards *s, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
@@ -948,22 +977,20 @@ extern "C" int vg_shards_within_last_launches(const vg_shards *s) {
     return most;
 }
 
-// ---- batch range scans: every shard answers all nq queries (vg_scan_within_batch[_masked]: same radii, same limit), then merge_within per query
-static int shards_within_batch(vg_shards *s, bool masked, int metric, const void *queries, int nq, const double *radii, int64_t limit,
-                               int64_t *out_matches, int64_t *out_held) {
-    const char *who = masked ? "vg_shards_scan_within_batch_masked" : "vg_shards_scan_within_batch";
-    const char *inner = masked ? "vg_scan_within_batch_masked" : "vg_scan_within_batch";
-    auto scan = masked ? vg_scan_within_batch_masked : vg_scan_within_batch;
+// ---- batch range scans: every shard answers all nq queries (the form's batch range scan: same radii, same limit, same labels), then
+// merge_within per query.  scan(corpus, out_matches, out_held): that scan over one shard
+template <typename Scan>
+static int shards_within_batch(vg_shards *s, const WithinShardForm &f, const void *queries, int nq, const double *radii, const void *extra,
+                               int64_t limit, int64_t *out_matches, int64_t *out_held, Scan scan) {
     for (int q = 0; q < nq; ++q) { if (out_matches) out_matches[q] = 0; if (out_held) out_held[q] = 0; }
-    if (!s || !queries || !radii) return fail(VG_ERR_INVALID, (std::string(who) + ": NULL argument").c_str());
-    if (s->S == 1) return scan(s->sh[0], metric, queries, nq, radii, limit, out_matches, out_held);
+    if (!s || !queries || !radii || !extra) return fail(VG_ERR_INVALID, (std::string(f.who) + ": NULL argument").c_str());
+    if (s->S == 1) return scan(s->sh[0], out_matches, out_held);
     s->within_batch_hits.clear();
-    if (nq < 1) return fail(VG_ERR_INVALID, (std::string(inner) + ": nq must be at least 1").c_str());
-    if (masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, "vg_scan_within_batch_masked: no row mask set");
+    if (nq < 1) return fail(VG_ERR_INVALID, (std::string(f.inner) + ": nq must be at least 1").c_str());
+    int rc = within_shard_refusal(s, f);
+    if (rc != VG_OK) return rc;
     std::vector<int64_t> matches((size_t)s->S * nq, 0), held((size_t)s->S * nq, 0);
-    int rc = for_each_shard(s, [&](int i) {
-        return scan(s->sh[(size_t)i], metric, queries, nq, radii, limit, &matches[(size_t)i * nq], &held[(size_t)i * nq]);
-    });
+    rc = for_each_shard(s, [&](int i) { return scan(s->sh[(size_t)i], &matches[(size_t)i * nq], &held[(size_t)i * nq]); });
     if (rc != VG_OK) return rc;
     s->within_batch_hits.resize((size_t)nq);
     for (int q = 0; q < nq; ++q) {
@@ -980,12 +1007,24 @@ static int shards_within_batch(vg_shards *s, bool masked, int metric, const void
 
 extern "C" int vg_shards_scan_within_batch(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                            int64_t *out_matches, int64_t *out_held) {
-    return shards_within_batch(s, false, metric, queries, nq, radii, limit, out_matches, out_held);
+    const WithinShardForm f = {"vg_shards_scan_within_batch", "vg_scan_within_batch", false, false};
+    return shards_within_batch(s, f, queries, nq, radii, radii, limit, out_matches, out_held,
+                               [&](vg_corpus *c, int64_t *m, int64_t *h) { return vg_scan_within_batch(c, metric, queries, nq, radii, limit, m, h); });
 }
 
 extern "C" int vg_shards_scan_within_batch_masked(vg_shards *s, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                                   int64_t *out_matches, int64_t *out_held) {
-    return shards_within_batch(s, true, metric, queries, nq, radii, limit, out_matches, out_held);
+    const WithinShardForm f = {"vg_shards_scan_within_batch_masked", "vg_scan_within_batch_masked", true, false};
+    return shards_within_batch(s, f, queries, nq, radii, radii, limit, out_matches, out_held,
+                               [&](vg_corpus *c, int64_t *m, int64_t *h) { return vg_scan_within_batch_masked(c, metric, queries, nq, radii, limit, m, h); });
+}
+
+extern "C" int vg_shards_scan_within_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels,
+                                                   const double *radii, int64_t limit, int64_t *out_matches, int64_t *out_held) {
+    const WithinShardForm f = {"vg_shards_scan_within_batch_labeled", "vg_scan_within_batch_labeled", false, true};
+    return shards_within_batch(s, f, queries, nq, radii, query_labels, limit, out_matches, out_held, [&](vg_corpus *c, int64_t *m, int64_t *h) {
+        return vg_scan_within_batch_labeled(c, metric, queries, nq, query_labels, radii, limit, m, h);
+    });
 }
 
 extern "C" int vg_shards_scan_within_batch_fetch(const vg_shards *s, int query, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
@@ -1003,6 +1042,11 @@ extern "C" int vg_shards_within_batch_plan(const vg_shards *s, int metric, int *
 extern "C" int vg_shards_within_batch_masked_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
     if (!s) return fail(VG_ERR_INVALID, "vg_shards_within_batch_masked_plan: NULL argument");
     return vg_within_batch_masked_plan(s->sh[0], metric, out_queries_per_pass, out_lpr, out_u);
+}
+
+extern "C" int vg_shards_within_batch_labeled_plan(const vg_shards *s, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
+    if (!s) return fail(VG_ERR_INVALID, "vg_shards_within_batch_labeled_plan: NULL argument");
+    return vg_within_batch_labeled_plan(s->sh[0], metric, out_queries_per_pass, out_lpr, out_u);
 }
 
 extern "C" int vg_shards_within_batch_set_initial_capacity(vg_shards *s, int64_t keys_per_query) {
