@@ -509,6 +509,62 @@ int     vg_scan_within_labelset(vg_corpus *c, int metric, const void *query, dou
 int     vg_scan_within_batch_labeled(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *query_labels,
                                      const double *radii, int64_t limit, int64_t *out_matches, int64_t *out_held);
 
+/* ---- value-range scans: an int64 per row, the k nearest rows whose value lies in [lo, hi] - "the 20 nearest chunks newer than T",
+ * "priced between a and b", "of tenant 7 and from the last 30 days", "the nearest documents among the rows of this week" (no
+ * reference entry point).
+ * A value is an int64_t per scan position kept on the handle, in device memory (8 bytes per row); any int64 is a value, there is no
+ * "none".  vg_corpus_set_values: n must equal vg_corpus_rows(c) (VG_ERR_INVALID otherwise); vg_corpus_has_values: 1 while values are
+ * set.  Lifetime: the labels', rule for rule - append*, delete_rows and clear drop the values; patch_rows, reserve and trim keep
+ * them; vg_corpus_clone copies them.  Values, labels and row mask are independent: only the calls below read the values, and they
+ * neither read nor write the row mask.
+ * A row is ALLOWED iff lo <= values[p] <= hi: a signed 64-bit comparison, the interval closed at both ends, INT64_MIN / INT64_MAX the
+ * open ends.  lo > hi is the empty interval: VG_OK, count 0, nothing launched.
+ * vg_scan_topk_valued: the contract of vg_scan_topk_masked over the allowed rows - rows with a finite distance, ascending (distance,
+ * scan position) whatever the handle's tie_order, the first k, every distance the float vg_scan_distances reports for that row, bit
+ * for bit.  A small kernel (one comparison per row, one ballot per 64 rows) turns (values, lo, hi) into a bitmap in the scratch buffer
+ * the labeled scans use, then the single masked kernels run over it.  vg_scan_topk_valued_labeled: allowed additionally requires
+ * labels[p] == label (the labels of vg_corpus_set_labels; none set, or label == VG_LABEL_NONE: VG_ERR_INVALID).
+ * vg_scan_topk_grouped_valued / vg_scan_topk_capped_valued: filter by value, group by label - what vg_scan_topk_grouped_masked /
+ * vg_scan_topk_capped_masked are contracted to return under a mask holding exactly the allowed rows; they need labels and values,
+ * and the shapes those tables leave out stay VG_ERR_UNSUPPORTED.  per_label < 1: VG_ERR_INVALID; per_label = 1 is the grouped form.
+ * vg_scan_within_valued: the contract of vg_scan_within_masked under that bitmap; it leaves its result where vg_scan_within leaves
+ * its own: read it with vg_scan_within_fetch / _keys.
+ * All top-k forms: 1 <= k <= 64 (VG_ERR_UNSUPPORTED above, VG_ERR_INVALID below, the count(s) zeroed first); no values set:
+ * VG_ERR_INVALID; an empty corpus: VG_OK with count 0.  The _keys forms: packed keys, positions local to this corpus.
+ * vg_scan_topk_batch_valued: nq queries (row-major nq x dim, host), query i under its OWN interval [los[i], his[i]]; query_labels is
+ * NULL or a label per query for the conjunction (then labels must be set; VG_LABEL_NONE in it: VG_ERR_INVALID with the counts zeroed
+ * first).  Query i's answer is what the single form is contracted to return for it, in caller order; out_rowids / out_dist are nq x
+ * k, the slots of query i behind out_counts[i] are NOT written; a query with lo > hi gets count 0; nq < 1: VG_ERR_INVALID.  f32 /
+ * uint8 / int8 rows of a register-resident shape: the queries are ordered by (label, lo, hi), a pre-pass per 32 queries reads the
+ * values (and labels) once and writes one membership dword per row, then the label-set multi-query instances run over it, 4 (or 2)
+ * queries a pass (the plan: vg_batch_valued_plan, vectorgpu_diag.h).  Every other shape: one single valued scan per query, the
+ * bitmap rebuilt only where the condition changes. */
+int     vg_corpus_set_values(vg_corpus *c, const int64_t *values, int64_t n);
+int     vg_corpus_clear_values(vg_corpus *c);
+int     vg_corpus_has_values(const vg_corpus *c);
+int     vg_scan_topk_valued(vg_corpus *c, int metric, const void *query, int k, int64_t lo, int64_t hi,
+                            int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_scan_topk_valued_keys(vg_corpus *c, int metric, const void *query, int k, int64_t lo, int64_t hi,
+                                 uint64_t *out_keys, int *out_count);
+int     vg_scan_topk_valued_labeled(vg_corpus *c, int metric, const void *query, int k, int64_t lo, int64_t hi, uint32_t label,
+                                    int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_scan_topk_valued_labeled_keys(vg_corpus *c, int metric, const void *query, int k, int64_t lo, int64_t hi, uint32_t label,
+                                         uint64_t *out_keys, int *out_count);
+int     vg_scan_topk_grouped_valued(vg_corpus *c, int metric, const void *query, int k, int64_t lo, int64_t hi,
+                                    int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_grouped_valued_keys(vg_corpus *c, int metric, const void *query, int k, int64_t lo, int64_t hi,
+                                         uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_capped_valued(vg_corpus *c, int metric, const void *query, int k, int per_label, int64_t lo, int64_t hi,
+                                   int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_scan_topk_capped_valued_keys(vg_corpus *c, int metric, const void *query, int k, int per_label, int64_t lo, int64_t hi,
+                                        uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+int     vg_scan_within_valued(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, int64_t lo, int64_t hi,
+                              int64_t *out_matches, int64_t *out_held);
+int     vg_scan_topk_batch_valued(vg_corpus *c, int metric, const void *queries, int nq, int k, const int64_t *los, const int64_t *his,
+                                  const uint32_t *query_labels, int64_t *out_rowids, double *out_dist, int *out_counts);
+int     vg_scan_topk_batch_valued_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, const int64_t *los, const int64_t *his,
+                                       const uint32_t *query_labels, uint64_t *out_keys, int *out_counts);
+
 /* ---- paged scans: the next k rows behind a (distance, rowid) cursor ("search after"; the reference's surface has LIMIT k OFFSET m,
  * a top-(m + k) scan) ----
  * A cursor is (after_dist, after_rowid): the distance and rowid of the last row of the previous page.  The row at scan position p
@@ -689,6 +745,27 @@ int     vg_shards_scan_topk_grouped_labelset(vg_shards *s, int metric, const voi
 int     vg_shards_scan_topk_capped_labelset(vg_shards *s, int metric, const void *query, int k, int per_label, const uint32_t *labels,
                                             int64_t n_labels, int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels,
                                             int *out_count);
+/* value-range scans (see above): the values over GLOBAL scan positions (n must equal vg_shards_rows), dealt out to the shards as
+ * the labels are; vg_shards_has_values: 1 while every shard holds values.  An interval means the same on every shard: every shard
+ * answers over its own rows and the lists merge like the labeled / grouped / capped scans'; the range form is read with
+ * vg_shards_scan_within_fetch.  The five top-k forms are named vg_shards_valued_scan_topk[_labeled | _batch | _grouped | _capped]
+ * after the vg_scan_topk_valued, _valued_labeled, _batch_valued, _grouped_valued and _capped_valued they fan out to. */
+int     vg_shards_set_values(vg_shards *s, const int64_t *values, int64_t n);
+int     vg_shards_clear_values(vg_shards *s);
+int     vg_shards_has_values(const vg_shards *s);
+int     vg_shards_valued_scan_topk(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi,
+                                   int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_shards_valued_scan_topk_labeled(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi, uint32_t label,
+                                           int64_t *out_rowids, double *out_dist, int *out_count);
+int     vg_shards_valued_scan_topk_batch(vg_shards *s, int metric, const void *queries, int nq, int k, const int64_t *los,
+                                         const int64_t *his, const uint32_t *query_labels, int64_t *out_rowids, double *out_dist,
+                                         int *out_counts);
+int     vg_shards_valued_scan_topk_grouped(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi,
+                                           int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_shards_valued_scan_topk_capped(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t lo, int64_t hi,
+                                          int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int     vg_shards_scan_within_valued(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t lo, int64_t hi,
+                                     int64_t *out_matches, int64_t *out_held);
 /* the masked range scans over every shard: each shard answers over its own bits (a shard whose share of the mask is empty launches
  * nothing and contributes nothing), merged like vg_shards_scan_within[_batch]: the rowids, order and distance bits of one corpus
  * holding all rows.  Same contract; the results are read with vg_shards_scan_within_fetch / vg_shards_scan_within_batch_fetch and

@@ -67,6 +67,10 @@ int vg_batch_labeled_plan(const vg_corpus *c, int metric, int *out_queries_per_p
  * label-set scan per query, one bitmap per run of equal sets) and the launch shape of the kernel that runs - vg_batch_masked_plan's
  * figures wherever the instance exists.  Pure host logic. */
 int vg_batch_labelset_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
+/* the same for vg_scan_topk_batch_valued: it runs the label-set instances over its own membership dwords (0 = the fallback, one
+ * single valued scan per query, one bitmap per run of equal conditions) - vg_batch_masked_plan's figures for every shape.  Pure
+ * host logic. */
+int vg_batch_valued_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 /* the same for vg_scan_topk_batch_grouped (masked != 0: vg_scan_topk_batch_grouped_masked): queries per pass of the grouped
  * multi-query scan (4 or 2; 0 = the fallback, one single grouped scan per query) and the launch shape of the kernel that runs.  Pure
  * host logic. */

@@ -267,6 +267,30 @@ def _load():
         "vg_shards_scan_topk_batch_labelset": (i32, [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp]),
         "vg_shards_scan_topk_grouped_labelset": (i32, [vp, i32, vp, i32, vp, i64, i32, vp, vp, vp, C.POINTER(i32)]),
         "vg_shards_scan_topk_capped_labelset": (i32, [vp, i32, vp, i32, i32, vp, i64, i32, vp, vp, vp, C.POINTER(i32)]),
+        "vg_corpus_set_values": (i32, [vp, vp, i64]),
+        "vg_corpus_clear_values": (i32, [vp]),
+        "vg_corpus_has_values": (i32, [vp]),
+        "vg_shards_set_values": (i32, [vp, vp, i64]),
+        "vg_shards_clear_values": (i32, [vp]),
+        "vg_shards_has_values": (i32, [vp]),
+        "vg_scan_topk_valued": (i32, [vp, i32, vp, i32, i64, i64, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_valued_keys": (i32, [vp, i32, vp, i32, i64, i64, vp, C.POINTER(i32)]),
+        "vg_scan_topk_valued_labeled": (i32, [vp, i32, vp, i32, i64, i64, C.c_uint32, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_valued_labeled_keys": (i32, [vp, i32, vp, i32, i64, i64, C.c_uint32, vp, C.POINTER(i32)]),
+        "vg_scan_topk_grouped_valued": (i32, [vp, i32, vp, i32, i64, i64, vp, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_grouped_valued_keys": (i32, [vp, i32, vp, i32, i64, i64, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_capped_valued": (i32, [vp, i32, vp, i32, i32, i64, i64, vp, vp, vp, C.POINTER(i32)]),
+        "vg_scan_topk_capped_valued_keys": (i32, [vp, i32, vp, i32, i32, i64, i64, vp, vp, C.POINTER(i32)]),
+        "vg_scan_within_valued": (i32, [vp, i32, vp, C.c_double, i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]),
+        "vg_scan_topk_batch_valued": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "vg_scan_topk_batch_valued_keys": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "vg_batch_valued_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "vg_shards_valued_scan_topk": (i32, [vp, i32, vp, i32, i64, i64, vp, vp, C.POINTER(i32)]),
+        "vg_shards_valued_scan_topk_labeled": (i32, [vp, i32, vp, i32, i64, i64, C.c_uint32, vp, vp, C.POINTER(i32)]),
+        "vg_shards_valued_scan_topk_batch": (i32, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+        "vg_shards_valued_scan_topk_grouped": (i32, [vp, i32, vp, i32, i64, i64, vp, vp, vp, C.POINTER(i32)]),
+        "vg_shards_valued_scan_topk_capped": (i32, [vp, i32, vp, i32, i32, i64, i64, vp, vp, vp, C.POINTER(i32)]),
+        "vg_shards_scan_within_valued": (i32, [vp, i32, vp, C.c_double, i64, i64, i64, C.POINTER(i64), C.POINTER(i64)]),
         "vg_scan_within_batch": (i32, [vp, i32, vp, i32, vp, i64, vp, vp]),
         "vg_scan_within_batch_fetch": (i32, [vp, i32, i64, i64, vp, vp]),
         "vg_scan_within_batch_keys": (i32, [vp, i32, i64, i64, vp]),
@@ -558,6 +582,133 @@ class _LabelsetOps:
         return ids[:cnt.value], dist[:cnt.value], out[:cnt.value]
 
 
+def batch_valued_plan(corpus, metric):
+    """(queries per pass, lanes per row, 16-byte chunks per lane) scan_topk_batch_valued serves this corpus with - batch_masked_plan's
+    figures; 0 queries per pass = one single valued scan per query (f16 / bf16, long rows) - host logic only"""
+    nq, lpr, u = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(lib().vg_batch_valued_plan(corpus.h, metric, C.byref(nq), C.byref(lpr), C.byref(u)))
+    return nq.value, lpr.value, u.value
+
+
+VALUE_MIN, VALUE_MAX = -(1 << 63), (1 << 63) - 1   # the open ends of a value interval (lo=None / hi=None)
+
+
+def _value_bound(v, open_end):
+    if v is None:
+        return open_end
+    v = int(v)
+    if v < VALUE_MIN or v > VALUE_MAX:
+        raise ValueError("a value bound is an int64")
+    return v
+
+
+def _values_i64(values):
+    a = np.asarray(values)
+    if a.size and (a.dtype.kind not in "iu" or (a.dtype.kind == "u" and a.dtype.itemsize == 8 and int(a.max()) > VALUE_MAX)):
+        raise ValueError("values are integers that fit an int64")
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.int64)
+
+
+class _ValuedOps:
+    """the value-range scans, shared by Corpus and Shards (`_lprefix`: vg_corpus / vg_shards, `_sprefix`: vg_ / vg_shards_): an int64
+    value per scan position on the handle (set_values), a query names the closed interval [lo, hi] its rows' values must lie in -
+    lo=None / hi=None: the open end.  lo > hi allows nothing.  Values, labels and row mask are independent; the row mask is neither
+    read nor written"""
+
+    _VALUED_TOPK = {"": "vg_scan_topk_valued", "labeled": "vg_scan_topk_valued_labeled", "batch": "vg_scan_topk_batch_valued",
+                    "grouped": "vg_scan_topk_grouped_valued", "capped": "vg_scan_topk_capped_valued"}
+
+    def _valued_topk(self, form):
+        """the top-k entry point of a form: vg_scan_topk_* on a corpus, vg_shards_valued_scan_topk[_<form>] over shards"""
+        if self._sprefix == "vg_":
+            return getattr(lib(), self._VALUED_TOPK[form])
+        return getattr(lib(), "vg_shards_valued_scan_topk" + ("_" + form if form else ""))
+
+    def set_values(self, values):
+        """one int64 value per scan position (len == rows); any int64 is a value"""
+        val = _values_i64(values)
+        _check(getattr(lib(), self._lprefix + "_set_values")(self.h, _ptr(val), val.size))
+
+    def clear_values(self):
+        _check(getattr(lib(), self._lprefix + "_clear_values")(self.h))
+
+    def has_values(self):
+        return bool(getattr(lib(), self._lprefix + "_has_values")(self.h))
+
+    def scan_topk_valued(self, metric, query, k, lo, hi, label=None):
+        """the k nearest rows whose value lies in [lo, hi] - label: and whose label (set_labels) is `label`: (rowids, distances)"""
+        query = np.ascontiguousarray(query)
+        lo, hi = _value_bound(lo, VALUE_MIN), _value_bound(hi, VALUE_MAX)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        cnt = C.c_int(0)
+        if label is None:
+            _check(self._valued_topk("")(self.h, metric, _ptr(query), k, lo, hi, _ptr(ids), _ptr(dist), C.byref(cnt)))
+        else:
+            fn = self._valued_topk("labeled")
+            _check(fn(self.h, metric, _ptr(query), k, lo, hi, int(label), _ptr(ids), _ptr(dist), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value]
+
+    def scan_topk_batch_valued(self, metric, queries, los, his, k, labels=None):
+        """scan_topk_valued for every row of `queries` under its own interval (los / his: nq bounds each, a scalar or None is
+        broadcast) - labels: and its own label - in shared passes: (rowids [nq, k], distances [nq, k], counts [nq]); the slots of
+        query i behind counts[i] are not written"""
+        queries = np.ascontiguousarray(queries)
+        nq = queries.shape[0]
+
+        def bounds(b, open_end):
+            if b is None or np.ndim(b) == 0:
+                return np.full(nq, _value_bound(b, open_end), dtype=np.int64)
+            b = [_value_bound(x, open_end) for x in (b.tolist() if isinstance(b, np.ndarray) else list(b))]
+            return np.array(b, dtype=np.int64)
+
+        lo, hi = bounds(los, VALUE_MIN), bounds(his, VALUE_MAX)
+        if lo.size != nq or hi.size != nq:
+            raise ValueError("scan_topk_batch_valued takes one interval per query")
+        lab = None
+        if labels is not None:
+            lab = _labels_u32(labels)
+            if lab.size != nq:
+                raise ValueError("scan_topk_batch_valued takes one label per query")
+        ids = np.zeros((nq, max(k, 1)), dtype=np.int64)
+        dist = np.zeros((nq, max(k, 1)), dtype=np.float64)
+        cnt = np.zeros(max(nq, 1), dtype=np.int32)
+        fn = self._valued_topk("batch")
+        _check(fn(self.h, metric, _ptr(queries), nq, k, _ptr(lo), _ptr(hi), None if lab is None else _ptr(lab), _ptr(ids), _ptr(dist), _ptr(cnt)))
+        return ids, dist, cnt[:nq]
+
+    def scan_topk_grouped_valued(self, metric, query, k, lo, hi):
+        """scan_topk_grouped over the rows whose value lies in [lo, hi] - filter by value, group by label: (rowids, distances, labels)"""
+        query = np.ascontiguousarray(query)
+        lo, hi = _value_bound(lo, VALUE_MIN), _value_bound(hi, VALUE_MAX)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        out = np.zeros(max(k, 1), dtype=np.uint32)
+        cnt = C.c_int(0)
+        fn = self._valued_topk("grouped")
+        _check(fn(self.h, metric, _ptr(query), k, lo, hi, _ptr(ids), _ptr(dist), _ptr(out), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value], out[:cnt.value]
+
+    def scan_topk_capped_valued(self, metric, query, k, per_label, lo, hi):
+        """scan_topk_capped over the rows whose value lies in [lo, hi]: (rowids, distances, labels)"""
+        query = np.ascontiguousarray(query)
+        lo, hi = _value_bound(lo, VALUE_MIN), _value_bound(hi, VALUE_MAX)
+        ids = np.zeros(max(k, 1), dtype=np.int64)
+        dist = np.zeros(max(k, 1), dtype=np.float64)
+        out = np.zeros(max(k, 1), dtype=np.uint32)
+        cnt = C.c_int(0)
+        fn = self._valued_topk("capped")
+        _check(fn(self.h, metric, _ptr(query), k, per_label, lo, hi, _ptr(ids), _ptr(dist), _ptr(out), C.byref(cnt)))
+        return ids[:cnt.value], dist[:cnt.value], out[:cnt.value]
+
+    def scan_within_valued(self, metric, query, radius, lo, hi, limit=None):
+        """scan_within among the rows whose value lies in [lo, hi]: (rowids, distances, matches)"""
+        lo, hi = _value_bound(lo, VALUE_MIN), _value_bound(hi, VALUE_MAX)
+        fn = getattr(lib(), self._sprefix + "scan_within_valued")
+        scan = lambda h, metric, q, r, lim, m, held: fn(h, metric, q, r, lim, lo, hi, m, held)
+        return _scan_within(scan, getattr(lib(), self._sprefix + "scan_within_fetch"), self.h, metric, query, radius, limit)
+
+
 def batch_capped_plan(corpus, metric, masked=False):
     """(queries per pass, lanes per row, 16-byte chunks per lane) scan_topk_batch_capped serves this corpus with; 0 queries per pass =
     one single capped scan per query (f16 / bf16, long rows, an instance left out of the table) - host logic only"""
@@ -815,7 +966,7 @@ def _set_mask(obj, prefix, rows, bits, positions, rowids):
     return int(getattr(L, prefix + "_mask_count")(obj.h))
 
 
-class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeledOps):
+class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeledOps, _ValuedOps):
     """One HBM-resident corpus shard (opaque vg_corpus handle)."""
     _lprefix, _sprefix = "vg_corpus", "vg_"
 
@@ -1139,7 +1290,7 @@ def device_memory(device=0):
     return f.value, t.value
 
 
-class Shards(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeledOps):
+class Shards(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeledOps, _ValuedOps):
     """One logical corpus dealt block-cyclically over several devices of this process (opaque vg_shards handle)."""
     _lprefix, _sprefix = "vg_shards", "vg_shards_"
 

@@ -217,6 +217,7 @@ extern "C" void vg_corpus_destroy(vg_corpus *c) {
     if (c->h_wb) hipHostFree(c->h_wb);
     if (c->d_mask) hipFree(c->d_mask);
     if (c->d_labels) hipFree(c->d_labels);
+    if (c->d_values) hipFree(c->d_values);
     if (c->d_label_bits) hipFree(c->d_label_bits);
     if (c->d_lset) hipFree(c->d_lset);
     if (c->d_member) hipFree(c->d_member);
@@ -239,6 +240,7 @@ extern "C" int vg_corpus_clear(vg_corpus *c) {
     vg_drop_within_results(c);
     vg_drop_mask(c);
     vg_drop_labels(c);
+    vg_drop_values(c);
     c->xnorm_rows = 0;
     c->i8_rows = 0;
     c->tm_rows = 0;
@@ -272,7 +274,7 @@ extern "C" int vg_corpus_device_bytes(const vg_corpus *c, long long *out3) {
     out3[0] = size_of(c->d_rows);
     const void *derived[] = {c->d_rows_s8, c->d_sx, c->d_rows_tm, c->d_rows_bf, c->d_rows_q8, c->d_q8stat, c->d_rows_q8tm, c->d_q8tm_stat, c->d_rows_n4, c->d_n4stat, c->d_xnorm};
     const void *working[] = {c->d_query, c->d_cand, c->d_cand_pre, c->d_keys, c->d_dist, c->d_below, c->d_ref_prefix, c->d_sel_keys, c->d_sel_sorted,
-                             c->d_sel_temp, c->d_sel_state, c->d_within, c->d_within_sorted, c->d_within_temp, c->d_wb, c->d_wb_grow, c->d_wb_counts, c->d_mask, c->d_labels, c->d_label_bits, c->d_lset, c->d_member, c->d_stage, c->d_filter_evals, c->d_bq, c->d_bcand, c->d_bkeys, c->d_bpairs, c->d_bpcounts};
+                             c->d_sel_temp, c->d_sel_state, c->d_within, c->d_within_sorted, c->d_within_temp, c->d_wb, c->d_wb_grow, c->d_wb_counts, c->d_mask, c->d_labels, c->d_values, c->d_label_bits, c->d_lset, c->d_member, c->d_stage, c->d_filter_evals, c->d_bq, c->d_bcand, c->d_bkeys, c->d_bpairs, c->d_bpcounts};
     out3[1] = 0; out3[2] = 0;
     for (const void *p : derived) out3[1] += size_of(p);
     for (const void *p : working) out3[2] += size_of(p);
@@ -317,6 +319,16 @@ static int labels_reserve(vg_corpus *c, int64_t rows) {
     return VG_OK;
 }
 
+// room for a value per row (value-range scans); what was there is not kept
+static int values_reserve(vg_corpus *c, int64_t rows) {
+    if (rows <= c->values_cap) return VG_OK;
+    if (c->d_values) { hipFree(c->d_values); c->d_values = nullptr; c->values_cap = 0; }
+    const int64_t cap = std::max<int64_t>(rows, 1024);
+    HIP_TRY(hipMalloc(&c->d_values, (size_t)cap * sizeof(int64_t)));
+    c->values_cap = cap;
+    return VG_OK;
+}
+
 // A second corpus with the same rows, rowids and per-corpus switches (device-to-device copy; per-row copies derived from the rows are NOT
 // copied - the clone makes its own when a scan wants them).  What the extension's registry of shared copies uses for copy-on-write: a
 // connection that has to CHANGE a copy other connections hold (append the rows it inserted, patch the rows it updated) clones it - a few
@@ -352,6 +364,14 @@ extern "C" int vg_corpus_clone(const vg_corpus *src, vg_corpus **out) {
         if (e != hipSuccess) { vg_corpus_destroy(c); return vg_fail(VG_ERR_HIP, "corpus clone: label copy failed: %s", hipGetErrorString(e)); }
         c->has_labels = true;
     }
+    if (src->has_values) {                                   // and the values, the same way
+        if ((rc = values_reserve(c, src->n_rows)) != VG_OK) { vg_corpus_destroy(c); return rc; }
+        hipError_t e = hipSuccess;
+        if (src->n_rows > 0) e = hipMemcpyAsync(c->d_values, src->d_values, (size_t)src->n_rows * sizeof(int64_t), hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { vg_corpus_destroy(c); return vg_fail(VG_ERR_HIP, "corpus clone: value copy failed: %s", hipGetErrorString(e)); }
+        c->has_values = true;
+    }
     *out = c;
     return VG_OK;
 }
@@ -379,6 +399,30 @@ extern "C" int vg_corpus_clear_labels(vg_corpus *c) {
 }
 
 extern "C" int vg_corpus_has_labels(const vg_corpus *c) { return (c && c->has_labels) ? 1 : 0; }
+
+extern "C" int vg_corpus_set_values(vg_corpus *c, const int64_t *values, int64_t n) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    if (n != c->n_rows) return vg_fail(VG_ERR_INVALID, "vg_corpus_set_values: %lld values for %lld rows", (long long)n, (long long)c->n_rows);
+    if (n > 0 && !values) return vg_fail(VG_ERR_INVALID, "vg_corpus_set_values: values is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    vg_drop_values(c);                                       // (a failed upload leaves no values)
+    int rc = values_reserve(c, n);
+    if (rc != VG_OK) return rc;
+    if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(c->d_values, values, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));            // (the caller's array may change right behind this call)
+    }
+    c->has_values = true;
+    return VG_OK;
+}
+
+extern "C" int vg_corpus_clear_values(vg_corpus *c) {
+    if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
+    vg_drop_values(c);
+    return VG_OK;
+}
+
+extern "C" int vg_corpus_has_values(const vg_corpus *c) { return (c && c->has_values) ? 1 : 0; }
 
 // Give back what a too-generous reservation holds beyond the rows that arrived (the extension reserves from a cheap UPPER bound of the
 // table's row count - the key span - which sparse keys can put several times above the count; the per-row copies derived later - norms,
@@ -539,6 +583,7 @@ static int append_impl(vg_corpus *c, const void *src, bool src_on_device, int64_
     if (rc != VG_OK) return rc;
     vg_drop_mask(c);                                         // (a row mask covers the rows as they were)
     vg_drop_labels(c);                                       // (and so do the labels)
+    vg_drop_values(c);                                       // (and the values)
     uint8_t *dst = c->d_rows + c->n_rows * c->stride;
     // a plain copy is only valid when source rows have no padding of their own: padding bytes must be ZERO in HBM
     // (they are summed like data), so any row whose size is not a 16-byte multiple goes through the repack kernel
@@ -779,6 +824,7 @@ extern "C" int vg_corpus_delete_rows(vg_corpus *c, const int64_t *positions, int
     c->n_rows -= n;
     vg_drop_mask(c);
     vg_drop_labels(c);
+    vg_drop_values(c);
     invalidate_derived_from(c, positions[0]);
     return VG_OK;
 }

@@ -192,6 +192,12 @@ struct vg_corpus {
     std::vector<uint32_t> lset_host;
     uint32_t *d_member = nullptr;
     int64_t member_cap = 0;
+    // value-range scans (vg_scan_valued.hip, vg_multi_valued.hip): an int64 per scan position in device memory - any int64 is a value.
+    // Read by the valued scans only; lifetime rule for rule the labels' (vg_drop_values).  Their bitmap and membership dwords go into
+    // the label-set scans' scratch (d_label_bits, d_lset, d_member)
+    int64_t *d_values = nullptr;              // n_rows values while values are set (values_cap allocated)
+    int64_t values_cap = 0;
+    bool has_values = false;
     int max_blocks = 0;
     int cu_count = 0;
 
@@ -267,6 +273,7 @@ static inline void vg_drop_within_results(vg_corpus *c) {           // (held ran
 static inline void vg_drop_mask(vg_corpus *c) { c->mask_count = -1; c->mask_host.clear(); }   // (the device words stay allocated for the next mask)
 int vg_mask_upload(vg_corpus *c);             // vg_scan_masked.hip: mask_host -> d_mask
 static inline void vg_drop_labels(vg_corpus *c) { c->has_labels = false; }   // (the device dwords stay allocated for the next labels)
+static inline void vg_drop_values(vg_corpus *c) { c->has_values = false; }   // (the same: the device values stay allocated)
 // vg_scan_labeled.hip: d_label_bits <- "labels[p] == label" for every row, enqueued on the corpus stream (no wait)
 int vg_label_bits_enqueue(vg_corpus *c, uint32_t label);
 // vg_scan_labelset.hip: d_label_bits <- "labels[p] is in the set" (exclude: "labels[p] is a label and not in the set") for every
@@ -279,6 +286,27 @@ bool vg_labelset_normalise(const char *who, const uint32_t *labels, int64_t n, s
 // the label-set batch (vg_multi_labelset.hip): what vg_fused_batch_run needs next to a form whose `single.labelset` is set - the
 // queries' normalised sets in CSR form over the queries AS HANDED OVER (ordered by set: equal sets are neighbours), all on the host
 struct VgLabelsetBatch { const uint32_t *flat; const int64_t *offsets; int exclude; };
+// What a membership form (`single.labelset`) plugs into vg_fused_batch_run: where the allowed rows of its queries come from.  The
+// routine owns groups, slices, passes and the fallback's loop; the form owns the three steps that know its conditions.  `ctx`: the
+// form's conditions over the queries AS HANDED OVER (equal conditions are neighbours), on the host until the routine returns.
+//   pack_group     appends the table of queries [g0, g1) - one membership group - to *data (dwords of d_lset) and says what
+//                  member_enqueue needs to find it again (nd, total); a refusal in `who`'s name
+//   member_enqueue the group's pre-pass on the corpus stream: d_member[row] bit j <- query g0 + j may see the row; the group's table
+//                  sits at dword `at` of d_lset
+//   bits_enqueue   the fallback, query i: d_label_bits <- its allowed rows, enqueued only where the condition differs from query
+//                  i - 1's; *skip <- true where the condition allows no row at all (no launch, count 0)
+struct VgMemberForm {
+    const void *ctx;
+    int (*pack_group)(const void *ctx, const char *who, int g0, int g1, std::vector<uint32_t> *data, int *nd, size_t *total);
+    int (*member_enqueue)(vg_corpus *c, const void *ctx, size_t at, int nd, size_t total);
+    int (*bits_enqueue)(vg_corpus *c, const void *ctx, int i, bool *skip);
+};
+// vg_scan_valued.hip: d_label_bits <- "lo <= values[p] <= hi" (use_label: "... and labels[p] == label") for every row, enqueued on
+// the corpus stream (no wait)
+int vg_value_bits_enqueue(vg_corpus *c, int64_t lo, int64_t hi, int use_label, uint32_t label);
+// vg_multi_valued.hip: the membership pre-pass of one group of the valued batch - `nd` conditions of VG_VALUE_COND_DWORDS dwords
+// each behind one count dword, at dword `at` of d_lset
+int vg_value_member_enqueue(vg_corpus *c, size_t at, int nd, int any_label);
 
 // next slot of the profiling ring (nullptr when profiling is off)
 static inline hipEvent_t *vg_prof_slot(vg_corpus *c, uint8_t flags) {
@@ -322,7 +350,8 @@ int vg_launch_scan_kernel(scan_fn_t fn, long long blocks, size_t smem, hipStream
 // errors carry.  `labeled` (the labeled range scans, vg_scan_within_labeled.hip), as in VgFusedForm: the masked kernels run over
 // c->d_label_bits - the caller enqueued vg_label_bits_enqueue / vg_labelset_bits_enqueue in front - and labels are required, not a mask
 typedef scan_fn_t (*vg_pick_scan_fn_t)(int vtype, int acc, int U, bool long_rows);
-struct VgWithinForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool labeled; };
+// `valued` (the valued range scan, vg_scan_valued.hip; with `labeled` set): the bitmap came from vg_value_bits_enqueue - values are required, not labels
+struct VgWithinForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool labeled; bool valued; };
 int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                   int64_t *out_held);
 scan_fn_t vg_pick_scan_within_masked(int vtype, int acc, int U, bool long_rows);   // vg_scan_within_masked.hip: the masked single range scan's kernel table
@@ -349,7 +378,10 @@ scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows); 
 // caller enqueued vg_labelset_bits_enqueue in front): the batch form reads no query labels; it points ScanArgs.labels at the
 // membership dwords of the pass' group (c->d_member, filled by a pre-pass per 32 queries) and puts the pass' bit offset into
 // ScanArgs.within_cap; its fallback builds one bitmap per run of equal sets.
-struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; bool grouped; int per_label; bool labelset; };
+// `valued` (the value-range scans, vg_scan_valued.hip / vg_multi_valued.hip; with `labeled` and `labelset` set, whose paths they
+// share - the caller enqueued vg_value_bits_enqueue in front): values are required; labels only by a grouped form, or where the
+// caller itself asked for the conjunction with a label and checked.
+struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; bool grouped; int per_label; bool labelset; bool valued; };
 struct VgFusedBatchForm { const char *who; vg_pick_multi_fn_t pick; VgFusedForm single; };
 int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count,
                  uint32_t *out_labels = nullptr);
@@ -360,7 +392,7 @@ int vg_launch_merge_grouped(const uint64_t *dev_cand, int nlists, int k, const u
 int vg_launch_merge_capped(const uint64_t *dev_cand, int nlists, int k, int per_label, const uint32_t *dev_labels, uint64_t *dev_out, hipStream_t stream);
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                        uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr, uint32_t *out_labels = nullptr,
-                       const VgLabelsetBatch *lsets = nullptr);
+                       const VgMemberForm *member = nullptr);
 // vg_scan_masked.hip: the winners' keys as rows - query i's counts[i] keys at keys + i * k become (rowid, distance[, label]) at
 // out_* + i * k.  labels / out_labels: both or neither; a single scan is nq = 1
 void vg_keys_to_rows(const vg_corpus *c, const uint64_t *keys, const uint32_t *labels, int nq, int k, const int *counts, int64_t *out_rowids,
@@ -376,6 +408,8 @@ int vg_merge_keys_by_label(const char *who, const uint64_t *keys, const uint32_t
 // vg_multi_labelset.hip: the membership pre-pass of one group - d_member[row] bit j <- query j of the group may see the row.  The
 // group's data sits in d_lset at dword offset `at`: [nd offsets + 1 | nd query masks | the nd distinct sets back to back]
 int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, int exclude);
+scan_fn_t vg_pick_multi_labelset(int vtype, int acc, int U, int NQ);   // vg_multi_labelset.hip: the label-set batch's kernel table
+int vg_member_reserve(vg_corpus *c);                  // vg_multi_labelset.hip: d_member holds a dword per row
 // the batch launch of that merge (vg_multi_grouped.hip): workgroup n merges query n's `nlists` lists ([nq][nlists][64] keys at dev_cand) and writes its 64
 // keys and 64 labels at dev_out + n * VG_KEYS_BYTES.  A grouped VgFusedBatchForm (`single.grouped`, vg_multi_grouped.hip) ends in it:
 // vg_fused_batch_run then sets ScanArgs.labels, requires labels, sizes a slice's key buffer for the labels and fills out_labels (nq x k)

@@ -68,12 +68,18 @@ __global__ __launch_bounds__(256) void vg_labelset_member_kernel(const uint32_t 
     }
 }
 
-int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, int exclude) {
+int vg_member_reserve(vg_corpus *c) {
     if (c->member_cap < c->n_rows) {
         if (c->d_member) { hipFree(c->d_member); c->d_member = nullptr; c->member_cap = 0; }
         HIP_TRY(hipMalloc(&c->d_member, (size_t)c->n_rows * sizeof(uint32_t)));
         c->member_cap = c->n_rows;
     }
+    return VG_OK;
+}
+
+int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, int exclude) {
+    int rcm = vg_member_reserve(c);
+    if (rcm != VG_OK) return rcm;
     const long long blocks = std::min<long long>((c->n_rows + 255) / 256, 2048);
     const bool in_lds = total <= VG_LSET_LDS_MAX;
     const size_t smem = in_lds ? (size_t)(2 * nd + 1 + total) * sizeof(uint32_t) : 0;
@@ -84,7 +90,48 @@ int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, in
     return VG_OK;
 }
 
+// ---- the label-set batch as a membership form of vg_fused_batch_run (VgMemberForm, vg_internal.h; ctx: a VgLabelsetBatch)
+
+// the DISTINCT sets of queries [g0, g1) - equal sets are neighbours: [nd + 1 offsets | nd query masks | the sets]
+static int labelset_pack_group(const void *ctx, const char *who, int g0, int g1, std::vector<uint32_t> *data, int *nd, size_t *total) {
+    const VgLabelsetBatch *lsets = (const VgLabelsetBatch *)ctx;
+    std::vector<uint32_t> off(1, 0u), qmask, sets;
+    for (int i = g0; i < g1; ++i) {
+        const uint32_t *si = lsets->flat + lsets->offsets[i];
+        const size_t ni = (size_t)(lsets->offsets[i + 1] - lsets->offsets[i]);
+        const size_t np = i > g0 ? (size_t)(lsets->offsets[i] - lsets->offsets[i - 1]) : 0;
+        if (i > g0 && ni == np && std::equal(si, si + ni, lsets->flat + lsets->offsets[i - 1])) { qmask.back() |= 1u << (i - g0); continue; }
+        sets.insert(sets.end(), si, si + ni);
+        if (sets.size() > 0x7FFFFFFFull) return vg_fail(VG_ERR_UNSUPPORTED, "%s: the sets of 32 queries hold more than 2^31 - 1 labels", who);
+        off.push_back((uint32_t)sets.size());
+        qmask.push_back(1u << (i - g0));
+    }
+    *nd = (int)qmask.size();
+    *total = sets.size();
+    data->insert(data->end(), off.begin(), off.end());
+    data->insert(data->end(), qmask.begin(), qmask.end());
+    data->insert(data->end(), sets.begin(), sets.end());
+    return VG_OK;
+}
+
+static int labelset_member_step(vg_corpus *c, const void *ctx, size_t at, int nd, size_t total) {
+    return vg_labelset_member_enqueue(c, at, nd, total, ((const VgLabelsetBatch *)ctx)->exclude);
+}
+
+// the fallback: one bitmap per run of equal sets; an empty allowed set has no rows - no launch, count 0
+static int labelset_bits_step(vg_corpus *c, const void *ctx, int i, bool *skip) {
+    const VgLabelsetBatch *lsets = (const VgLabelsetBatch *)ctx;
+    const uint32_t *si = lsets->flat + lsets->offsets[i];
+    const int64_t ni = lsets->offsets[i + 1] - lsets->offsets[i];
+    if (ni == 0 && !lsets->exclude) { *skip = true; return VG_OK; }
+    const int64_t np = i > 0 ? lsets->offsets[i] - lsets->offsets[i - 1] : -1;
+    if (ni != np || !std::equal(si, si + ni, lsets->flat + lsets->offsets[i - 1])) return vg_labelset_bits_enqueue(c, si, ni, lsets->exclude);
+    return VG_OK;
+}
+
 static scan_fn_t pick_multi_labelset(int vtype, int acc, int U, int NQ) { return vg_pick_multi<MultiFamily<VG_MQ_LABELSET>>(vtype, acc, U, NQ); }
+// the same table as a plain function: the valued batch (vg_multi_valued.hip) runs these instances over its own membership dwords
+scan_fn_t vg_pick_multi_labelset(int vtype, int acc, int U, int NQ) { return pick_multi_labelset(vtype, acc, U, NQ); }
 
 extern "C" int vg_batch_labelset_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
     return vg_batch_plan_report(c, metric, pick_multi_labelset, out_queries_per_pass, out_lpr, out_u);
@@ -123,7 +170,8 @@ extern "C" int vg_scan_topk_batch_labelset_keys(vg_corpus *c, int metric, const 
     const VgLabelsetBatch ls = {flat.data(), offs.data(), exclude ? 1 : 0};
     std::vector<uint64_t> skeys((size_t)nq * k);
     std::vector<int> scounts((size_t)nq, 0);
-    int rc = vg_fused_batch_run(c, form, metric, sq.data(), nq, k, nullptr, out_keys ? skeys.data() : nullptr, scounts.data(), nullptr, nullptr, &ls);
+    const VgMemberForm member = {&ls, labelset_pack_group, labelset_member_step, labelset_bits_step};
+    int rc = vg_fused_batch_run(c, form, metric, sq.data(), nq, k, nullptr, out_keys ? skeys.data() : nullptr, scounts.data(), nullptr, nullptr, &member);
     if (rc != VG_OK) return rc;
     for (int i = 0; i < nq; ++i) {
         const int dst = order[(size_t)i];

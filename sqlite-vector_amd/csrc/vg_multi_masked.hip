@@ -45,7 +45,7 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
 // cap, clamped to k, travels in ScanArgs.within_cap - which no other top-k instance reads - and the lists merge through the capped
 // batch merge; everything else is the grouped form's.  A label-set form (vg_multi_labelset.hip: labeled, with single.labelset set):
 // ScanArgs.labels is the membership buffer of the pass' group and `member_shift`, the pass' bit offset inside that group, travels in
-// ScanArgs.within_cap; no query labels.
+// ScanArgs.within_cap; no query labels.  The valued batch (vg_multi_valued.hip) is a label-set form with another pre-pass.
 static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s,
                                const uint8_t *dev_queries, const uint64_t *dev_floors, const uint32_t *dev_qlabels, int k, uint64_t *dev_cand,
                                uint64_t *dev_out_keys, int member_shift = 0) {
@@ -83,33 +83,21 @@ static_assert(VG_FUSED_SLICE % VG_MEMBER_GROUP == 0, "a slice is whole membershi
 // nq queries, NQ per pass; every pass of every slice is enqueued back to back on the corpus stream, one wait at the end
 static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const void *queries,
                               int nq, const uint64_t *floors, const uint32_t *qlabels, int k, uint64_t *out_keys, int *out_counts,
-                              uint32_t *out_labels, const VgLabelsetBatch *lsets) {
+                              uint32_t *out_labels, const VgMemberForm *member) {
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
     const int slice = std::min(nq_pad, VG_FUSED_SLICE);
     const bool qlab = f.single.labeled && !f.single.labelset;          // a label per query goes up with the queries
-    // (a label-set form: the DISTINCT sets of every membership group of VG_MEMBER_GROUP queries - equal sets are neighbours - go up
-    //  once, in front of everything: per group [nd + 1 offsets | nd query masks | the sets].  A pad query is in no mask)
+    // (a membership form: the table of every membership group of VG_MEMBER_GROUP queries - its DISTINCT conditions, equal ones are
+    //  neighbours - goes up once, in front of everything; the form packs it (VgMemberForm.pack_group).  A pad query is in no mask)
     struct MemberGroup { size_t at; int nd; size_t total; };
     std::vector<MemberGroup> mgroups;
     std::vector<uint32_t> mdata;
     if (f.single.labelset) {
         for (int g0 = 0; g0 < nq; g0 += VG_MEMBER_GROUP) {
-            const int g1 = std::min(nq, g0 + VG_MEMBER_GROUP);
-            std::vector<uint32_t> off(1, 0u), qmask, sets;
-            for (int i = g0; i < g1; ++i) {
-                const uint32_t *si = lsets->flat + lsets->offsets[i];
-                const size_t ni = (size_t)(lsets->offsets[i + 1] - lsets->offsets[i]);
-                const size_t np = i > g0 ? (size_t)(lsets->offsets[i] - lsets->offsets[i - 1]) : 0;
-                if (i > g0 && ni == np && std::equal(si, si + ni, lsets->flat + lsets->offsets[i - 1])) { qmask.back() |= 1u << (i - g0); continue; }
-                sets.insert(sets.end(), si, si + ni);
-                if (sets.size() > 0x7FFFFFFFull) return vg_fail(VG_ERR_UNSUPPORTED, "%s: the sets of 32 queries hold more than 2^31 - 1 labels", f.who);
-                off.push_back((uint32_t)sets.size());
-                qmask.push_back(1u << (i - g0));
-            }
-            mgroups.push_back(MemberGroup{mdata.size(), (int)qmask.size(), sets.size()});
-            mdata.insert(mdata.end(), off.begin(), off.end());
-            mdata.insert(mdata.end(), qmask.begin(), qmask.end());
-            mdata.insert(mdata.end(), sets.begin(), sets.end());
+            MemberGroup mg{mdata.size(), 0, 0};
+            int rcp = member->pack_group(member->ctx, f.who, g0, std::min(nq, g0 + VG_MEMBER_GROUP), &mdata, &mg.nd, &mg.total);
+            if (rcp != VG_OK) return rcp;
+            mgroups.push_back(mg);
         }
         int rcl = vg_lset_reserve(c, mdata.size() * sizeof(uint32_t));
         if (rcl != VG_OK) return rcl;
@@ -151,7 +139,7 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
             // (a label-set form: the first pass of a membership group is preceded by the group's pre-pass; a slice is whole groups)
             if (f.single.labelset && (q0 + g) % VG_MEMBER_GROUP == 0) {
                 const MemberGroup &mg = mgroups[(size_t)((q0 + g) / VG_MEMBER_GROUP)];
-                if ((rc = vg_labelset_member_enqueue(c, mg.at, mg.nd, mg.total, lsets->exclude)) != VG_OK) break;
+                if ((rc = member->member_enqueue(c, member->ctx, mg.at, mg.nd, mg.total)) != VG_OK) break;
             }
             rc = launch_fused_multi(c, f, metric, fn, NQ, s, (const uint8_t *)c->d_bq + (size_t)g * c->stride,
                                      reinterpret_cast<const uint64_t *>((const uint8_t *)c->d_bq + fl_off) + g,
@@ -184,9 +172,9 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
 // Slots behind out_counts[i] are not written.  `floors`: a key per query, read by an after form only.  `out_labels` (nq x k): the
 // winners' labels, filled by a grouped form only.
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
-                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgLabelsetBatch *lsets) {
+                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member) {
     if (!c || !queries || !out_counts || (f.single.after && !floors) || (f.single.labeled && !f.single.labelset && !qlabels) ||
-        (f.single.labelset && !lsets)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
+        (f.single.labelset && !member)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", f.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
@@ -194,7 +182,8 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
     if (!out_keys || (f.single.grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (f.single.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
-    if (f.single.labeled) {
+    if (f.single.valued && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
+    if (f.single.labeled && !f.single.valued) {              // (a valued form needs labels or values, as its caller says and checked)
         if (!c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
         for (int i = 0; i < nq && !f.single.labelset; ++i)
             if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", f.who, i);
@@ -213,16 +202,12 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
                 int rcb = vg_label_bits_enqueue(c, qlabels[i]);
                 if (rcb != VG_OK) return rcb;
             }
-            // (a label-set form: the same per run of equal sets; an empty allowed set has no rows - no launch, count 0)
+            // (a membership form: the same per run of equal conditions; a condition that allows no row at all - no launch, count 0)
             if (f.single.labelset) {
-                const uint32_t *si = lsets->flat + lsets->offsets[i];
-                const int64_t ni = lsets->offsets[i + 1] - lsets->offsets[i];
-                if (ni == 0 && !lsets->exclude) continue;
-                const int64_t np = i > 0 ? lsets->offsets[i] - lsets->offsets[i - 1] : -1;
-                if (ni != np || !std::equal(si, si + ni, lsets->flat + lsets->offsets[i - 1])) {
-                    int rcb = vg_labelset_bits_enqueue(c, si, ni, lsets->exclude);
-                    if (rcb != VG_OK) return rcb;
-                }
+                bool skip = false;
+                int rcb = member->bits_enqueue(c, member->ctx, i, &skip);
+                if (rcb != VG_OK) return rcb;
+                if (skip) continue;
             }
             int rc = vg_fused_run(c, f.single, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, floors ? floors[i] : 0ull,
                                   out_keys + (size_t)i * k, &out_counts[i], f.single.grouped ? out_labels + (size_t)i * k : nullptr);
@@ -230,7 +215,7 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
         }
         return VG_OK;
     }
-    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, qlabels, k, out_keys, out_counts, out_labels, lsets);
+    return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, qlabels, k, out_keys, out_counts, out_labels, member);
 }
 
 extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,

@@ -134,7 +134,8 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
     if (!out_keys || (f.grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
-    if ((f.labeled || f.grouped) && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+    if (f.valued && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
+    if (((f.labeled && !f.valued) || f.grouped) && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
     if ((f.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     if (f.after && floor == VG_EMPTY_KEY) return VG_OK;      // nothing is behind the cursor: no launch
     HIP_TRY(hipSetDevice(c->device));

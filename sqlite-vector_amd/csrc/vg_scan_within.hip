@@ -145,7 +145,8 @@ int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *q
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     if (radius != radius) return vg_fail(VG_ERR_INVALID, "%s: the radius is NaN", f.who);
     if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
-    if (f.labeled && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+    if (f.valued && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
+    if (f.labeled && !f.valued && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
     if (c->n_rows == 0 || (f.masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
     HIP_TRY(hipSetDevice(c->device));
     c->enqueued = false;                                     // (the pinned key buffer is this scan's landing zone now)

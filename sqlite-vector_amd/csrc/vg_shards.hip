@@ -898,12 +898,13 @@ static int fetch_within(const vg_shards *s, const char *who, const std::vector<v
 
 // which range form a call over shards stands for: whose names errors carry (the shards' entry point, the per-corpus one), and what
 // every shard must hold - a mask (masked forms: every shard over its own bits; a shard whose share of the mask is empty launches
-// nothing) or labels (labeled forms: labels mean the same on every shard)
-struct WithinShardForm { const char *who; const char *inner; bool masked; bool labeled; };
+// nothing), labels (labeled forms: labels mean the same on every shard) or values (the valued form: so does an interval)
+struct WithinShardForm { const char *who; const char *inner; bool masked; bool labeled; bool valued; };
 
 static int within_shard_refusal(const vg_shards *s, const WithinShardForm &f) {
     if (f.masked && vg_shards_mask_count(s) < 0) return fail(VG_ERR_INVALID, (std::string(f.inner) + ": no row mask set").c_str());
     if (f.labeled && !vg_shards_has_labels(s)) return fail(VG_ERR_INVALID, (std::string(f.inner) + ": no labels set").c_str());
+    if (f.valued && !vg_shards_has_values(s)) return fail(VG_ERR_INVALID, (std::string(f.inner) + ": no values set").c_str());
     return VG_OK;
 }
 
@@ -956,6 +957,13 @@ extern "C" int vg_shards_scan_within_labelset(vg_shards *s, int metric, const vo
     return shards_within(s, f, query, limit, out_matches, out_held, [&](vg_corpus *c, int64_t *m, int64_t *h) {
         return vg_scan_within_labelset(c, metric, query, radius, limit, labels, n_labels, exclude, m, h);
     });
+}
+
+extern "C" int vg_shards_scan_within_valued(vg_shards *s, int metric, const void *query, double radius, int64_t limit, int64_t lo, int64_t hi,
+                                            int64_t *out_matches, int64_t *out_held) {
+    const WithinShardForm f = {"vg_shards_scan_within_valued", "vg_scan_within_valued", false, false, true};
+    return shards_within(s, f, query, limit, out_matches, out_held,
+                         [&](vg_corpus *c, int64_t *m, int64_t *h) { return vg_scan_within_valued(c, metric, query, radius, limit, lo, hi, m, h); });
 }
 
 extern "C" int vg_shards_scan_within_fetch(const vg_shards *s, int64_t first, int64_t n, int64_t *out_rowids, double *out_dist) {
@@ -1188,7 +1196,47 @@ extern "C" int vg_shards_has_labels(const vg_shards *s) {
     return 1;
 }
 
-// ---- the fused scan forms over several shards (masked, labeled, label-set, grouped, capped; the paged scans further down): every
+// ---- values: given over GLOBAL scan positions and dealt out like the labels
+extern "C" int vg_shards_set_values(vg_shards *s, const int64_t *values, int64_t n) {
+    if (!s) return fail(VG_ERR_INVALID, "shards handle is NULL");
+    if (s->S == 1) return vg_corpus_set_values(s->sh[0], values, n);
+    if (n != s->n_rows) return fail(VG_ERR_INVALID, "vg_shards_set_values: the value count must equal the rows held");
+    if (n > 0 && !values) return fail(VG_ERR_INVALID, "vg_shards_set_values: values is NULL");
+    std::vector<std::vector<int64_t>> local((size_t)s->S);
+    for (int i = 0; i < s->S; ++i) local[(size_t)i].assign((size_t)vg_corpus_rows(s->sh[(size_t)i]), 0);
+    for (int64_t g = 0; g < n; g += s->B) {                                    // block by block: one shard, consecutive local positions
+        int shard;
+        int64_t l0;
+        locate(s, g, &shard, &l0);
+        const int64_t len = std::min<int64_t>(s->B, n - g);
+        if (l0 + len > (int64_t)local[(size_t)shard].size()) return fail(VG_ERR_INVALID, "vg_shards_set_values: the shards do not hold the rows of the map");
+        memcpy(local[(size_t)shard].data() + l0, values + g, (size_t)len * sizeof(int64_t));
+    }
+    for (int i = 0; i < s->S; ++i) {                   // a failure on the way leaves NO shard with values
+        int rc = vg_corpus_set_values(s->sh[(size_t)i], local[(size_t)i].data(), (int64_t)local[(size_t)i].size());
+        if (rc != VG_OK) {
+            const std::string msg = vg_last_error();
+            for (auto *c : s->sh) vg_corpus_clear_values(c);
+            return fail(rc, msg.c_str());
+        }
+    }
+    return VG_OK;
+}
+
+extern "C" int vg_shards_clear_values(vg_shards *s) {
+    if (!s) return fail(VG_ERR_INVALID, "shards handle is NULL");
+    for (auto *c : s->sh) { int rc = vg_corpus_clear_values(c); if (rc != VG_OK) return rc; }
+    return VG_OK;
+}
+
+// 1 while every shard holds values (an append drops the values of the shards it reaches)
+extern "C" int vg_shards_has_values(const vg_shards *s) {
+    if (!s) return 0;
+    for (auto *c : s->sh) if (!vg_corpus_has_values(c)) return 0;
+    return 1;
+}
+
+// ---- the fused scan forms over several shards (masked, labeled, label-set, valued, grouped, capped; the paged scans further down): every
 // shard answers over its own rows, mask bits and labels through the form's _keys entry point - positions local to it - and the host
 // merges the S lists of a query over GLOBAL positions.  One scaffold for all of them (point 4):
 //   fused_preamble       the refusals, in one order, worded by the entry point's row of kFusedForms
@@ -1204,14 +1252,16 @@ static int refuse(int code, const char *who, const char *what) {
 
 struct FusedForm {
     const char *outer;     // whose name "NULL argument", "NULL output" and "more than 2^32 - 1 rows" carry
-    const char *inner;     // ... and the nq, k, per_label and "no labels set" refusals
+    const char *inner;     // ... and the nq, k, per_label, "no labels set" and "no values set" refusals
     const char *mask;      // ... and "no row mask set"; nullptr: the form reads no mask
     const char *family;    // "k must be in 1..64 (<family> scans use the fused list only)"
     bool batch, labels, by_label, capped;
+    bool values;           // the valued forms: every shard must hold values
 };
 enum {
     F_MASKED, F_BATCH_MASKED, F_LABELED, F_BATCH_LABELED, F_LABELSET, F_BATCH_LABELSET, F_GROUPED, F_GROUPED_MASKED, F_BATCH_GROUPED,
-    F_BATCH_GROUPED_MASKED, F_CAPPED, F_CAPPED_MASKED, F_BATCH_CAPPED, F_BATCH_CAPPED_MASKED, F_GROUPED_LABELSET, F_CAPPED_LABELSET
+    F_BATCH_GROUPED_MASKED, F_CAPPED, F_CAPPED_MASKED, F_BATCH_CAPPED, F_BATCH_CAPPED_MASKED, F_GROUPED_LABELSET, F_CAPPED_LABELSET,
+    F_VALUED, F_VALUED_LABELED, F_BATCH_VALUED, F_GROUPED_VALUED, F_CAPPED_VALUED
 };
 static const FusedForm kFusedForms[] = {
     {"vg_shards_scan_topk_masked", "vg_scan_topk_masked", "vg_scan_topk_masked", "masked", false, false, false, false},
@@ -1232,6 +1282,11 @@ static const FusedForm kFusedForms[] = {
      true, true, true, true},
     {"vg_shards_scan_topk_grouped_labelset", "vg_shards_scan_topk_grouped_labelset", nullptr, "label-set", false, true, true, false},
     {"vg_shards_scan_topk_capped_labelset", "vg_shards_scan_topk_capped_labelset", nullptr, "label-set", false, true, true, true},
+    {"vg_shards_valued_scan_topk", "vg_scan_topk_valued", nullptr, "valued", false, false, false, false, true},
+    {"vg_shards_valued_scan_topk_labeled", "vg_scan_topk_valued_labeled", nullptr, "valued", false, true, false, false, true},
+    {"vg_shards_valued_scan_topk_batch", "vg_scan_topk_batch_valued", nullptr, "valued", true, false, false, false, true},   // (labels: where the call names some)
+    {"vg_shards_valued_scan_topk_grouped", "vg_scan_topk_grouped_valued", nullptr, "valued", false, true, true, false, true},
+    {"vg_shards_valued_scan_topk_capped", "vg_scan_topk_capped_valued", nullptr, "valued", false, true, true, true, true},
 };
 
 // VG_OK: go on; FUSED_ONE_SHARD: the handle is one corpus, whose own entry point answers (and refuses); anything else: refused.
@@ -1248,6 +1303,7 @@ static int fused_preamble(int form, const vg_shards *s, bool inputs, int nq, int
     if (f.capped && per_label < 1) return refuse(VG_ERR_INVALID, f.inner, "per_label must be at least 1");
     if (!outputs) return refuse(VG_ERR_INVALID, f.outer, "NULL output");
     if (f.mask && vg_shards_mask_count(s) < 0) return refuse(VG_ERR_INVALID, f.mask, "no row mask set");
+    if (f.values && !vg_shards_has_values(s)) return refuse(VG_ERR_INVALID, f.inner, "no values set");
     if (f.labels && !vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, f.inner, "no labels set");
     if (f.by_label && s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, f.outer, "more than 2^32 - 1 rows over all shards");
     return VG_OK;
@@ -1521,6 +1577,72 @@ extern "C" int vg_shards_scan_topk_capped_labelset(vg_shards *s, int metric, con
     return rc != VG_OK ? rc : merge_back_by_label(s, L, k, per_label, out_rowids, out_dist, out_labels, out_count);
 }
 
+// value-range scans: an interval means the same on every shard - every shard gets the caller's interval(s), and labels, as they are
+extern "C" int vg_shards_valued_scan_topk(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi, int64_t *out_rowids,
+                                          double *out_dist, int *out_count) {
+    int rc = fused_preamble(F_VALUED, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_valued(s->sh[0], metric, query, k, lo, hi, out_rowids, out_dist, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_valued_keys(s->sh[(size_t)i], metric, query, k, lo, hi, keys, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_count);
+}
+
+extern "C" int vg_shards_valued_scan_topk_labeled(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi, uint32_t label,
+                                                  int64_t *out_rowids, double *out_dist, int *out_count) {
+    int rc = fused_preamble(F_VALUED_LABELED, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_valued_labeled(s->sh[0], metric, query, k, lo, hi, label, out_rowids, out_dist, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_valued_labeled_keys(s->sh[(size_t)i], metric, query, k, lo, hi, label, keys, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_count);
+}
+
+extern "C" int vg_shards_valued_scan_topk_batch(vg_shards *s, int metric, const void *queries, int nq, int k, const int64_t *los,
+                                                const int64_t *his, const uint32_t *query_labels, int64_t *out_rowids, double *out_dist,
+                                                int *out_counts) {
+    int rc = fused_preamble(F_BATCH_VALUED, s, queries && los && his, nq, k, 0, out_rowids && out_dist, out_counts);
+    if (rc == FUSED_ONE_SHARD)
+        return vg_scan_topk_batch_valued(s->sh[0], metric, queries, nq, k, los, his, query_labels, out_rowids, out_dist, out_counts);
+    if (rc != VG_OK) return rc;
+    if (query_labels && !vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, kFusedForms[F_BATCH_VALUED].inner, "no labels set");
+    ShardLists L;
+    rc = gather_lists(s, nq, (size_t)k, false, &L, [&](int i, uint64_t *keys, uint32_t *, int *counts) {
+        return vg_scan_topk_batch_valued_keys(s->sh[(size_t)i], metric, queries, nq, k, los, his, query_labels, keys, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_plain(s, L, k, out_rowids, out_dist, nullptr, out_counts);
+}
+
+extern "C" int vg_shards_valued_scan_topk_grouped(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi,
+                                                  int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
+    int rc = fused_preamble(F_GROUPED_VALUED, s, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
+    if (rc == FUSED_ONE_SHARD) return vg_scan_topk_grouped_valued(s->sh[0], metric, query, k, lo, hi, out_rowids, out_dist, out_labels, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, true, &L, [&](int i, uint64_t *keys, uint32_t *klabels, int *counts) {
+        return vg_scan_topk_grouped_valued_keys(s->sh[(size_t)i], metric, query, k, lo, hi, keys, klabels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, 0, out_rowids, out_dist, out_labels, out_count);
+}
+
+extern "C" int vg_shards_valued_scan_topk_capped(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t lo, int64_t hi,
+                                                 int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
+    if (out_count) *out_count = 0;
+    if (per_label < 1) return fail(VG_ERR_INVALID, "vg_shards_valued_scan_topk_capped: per_label must be at least 1");
+    int rc = fused_preamble(F_CAPPED_VALUED, s, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
+    if (rc == FUSED_ONE_SHARD)
+        return vg_scan_topk_capped_valued(s->sh[0], metric, query, k, per_label, lo, hi, out_rowids, out_dist, out_labels, out_count);
+    if (rc != VG_OK) return rc;
+    ShardLists L;
+    rc = gather_lists(s, 1, VG_WAVE_KEYS, true, &L, [&](int i, uint64_t *keys, uint32_t *klabels, int *counts) {
+        return vg_scan_topk_capped_valued_keys(s->sh[(size_t)i], metric, query, k, per_label, lo, hi, keys, klabels, counts);
+    });
+    return rc != VG_OK ? rc : merge_back_by_label(s, L, k, per_label, out_rowids, out_dist, out_labels, out_count);
+}
 
 // ---- paged scans (vg_scan_after.hip, vg_multi_after.hip): a cursor over GLOBAL scan order becomes one floor key per shard over ITS
 // positions - the cursor's distance image with "local rows of this shard in front of global position P" (local_rows_before) - every
