@@ -23,7 +23,7 @@ VEC = os.path.join(HERE, "vector.so")
 # by the total CPU time over the cores (~30 CPU-minutes: ~4 min on 8 cores) instead of by its longest unit
 HIP_UNITS = [("vg_api.hip", "vg_api.hip.o", []), ("vg_corpus.hip", "vg_corpus.hip.o", []), ("vg_batch_api.hip", "vg_batch_api.hip.o", []),
              ("vg_select.hip", "vg_select.hip.o", []), ("vg_batch.hip", "vg_batch.hip.o", []), ("vg_quant.hip", "vg_quant.hip.o", []),
-             ("vg_shards.hip", "vg_shards.hip.o", []), ("vg_multi.hip", "vg_multi.hip.o", []), ("vg_reforder.hip", "vg_reforder.hip.o", []), ("vg_slabscan.hip", "vg_slabscan.hip.o", []), ("vg_scan_ex.hip", "vg_scan_ex.hip.o", []), ("vg_scan_within.hip", "vg_scan_within.hip.o", []), ("vg_scan_masked.hip", "vg_scan_masked.hip.o", []), ("vg_multi_masked.hip", "vg_multi_masked.hip.o", []), ("vg_multi_within.hip", "vg_multi_within.hip.o", []), ("vg_scan_within_masked.hip", "vg_scan_within_masked.hip.o", []), ("vg_multi_within_masked.hip", "vg_multi_within_masked.hip.o", []), ("vg_scan_within_labeled.hip", "vg_scan_within_labeled.hip.o", []), ("vg_multi_within_labeled.hip", "vg_multi_within_labeled.hip.o", []), ("vg_scan_after.hip", "vg_scan_after.hip.o", []), ("vg_multi_after.hip", "vg_multi_after.hip.o", []), ("vg_scan_labeled.hip", "vg_scan_labeled.hip.o", []), ("vg_multi_labeled.hip", "vg_multi_labeled.hip.o", []), ("vg_scan_labelset.hip", "vg_scan_labelset.hip.o", []), ("vg_multi_labelset.hip", "vg_multi_labelset.hip.o", []), ("vg_scan_valued.hip", "vg_scan_valued.hip.o", []), ("vg_multi_valued.hip", "vg_multi_valued.hip.o", []), ("vg_scan_grouped.hip", "vg_scan_grouped.hip.o", []), ("vg_multi_grouped.hip", "vg_multi_grouped.hip.o", []), ("vg_multi_grouped_masked.hip", "vg_multi_grouped_masked.hip.o", []), ("vg_scan_capped.hip", "vg_scan_capped.hip.o", []), ("vg_multi_capped.hip", "vg_multi_capped.hip.o", []), ("vg_multi_capped_masked.hip", "vg_multi_capped_masked.hip.o", []), ("vg_filter.hip", "vg_filter.hip.o", []),
+             ("vg_shards.hip", "vg_shards.hip.o", []), ("vg_multi.hip", "vg_multi.hip.o", []), ("vg_reforder.hip", "vg_reforder.hip.o", []), ("vg_slabscan.hip", "vg_slabscan.hip.o", []), ("vg_scan_ex.hip", "vg_scan_ex.hip.o", []), ("vg_scan_within.hip", "vg_scan_within.hip.o", []), ("vg_scan_masked.hip", "vg_scan_masked.hip.o", []), ("vg_multi_masked.hip", "vg_multi_masked.hip.o", []), ("vg_multi_within.hip", "vg_multi_within.hip.o", []), ("vg_scan_within_masked.hip", "vg_scan_within_masked.hip.o", []), ("vg_multi_within_masked.hip", "vg_multi_within_masked.hip.o", []), ("vg_multi_within_labeled.hip", "vg_multi_within_labeled.hip.o", []), ("vg_scan_after.hip", "vg_scan_after.hip.o", []), ("vg_multi_after.hip", "vg_multi_after.hip.o", []), ("vg_rowpred.hip", "vg_rowpred.hip.o", []), ("vg_multi_labeled.hip", "vg_multi_labeled.hip.o", []), ("vg_multi_labelset.hip", "vg_multi_labelset.hip.o", []), ("vg_multi_valued.hip", "vg_multi_valued.hip.o", []), ("vg_scan_grouped.hip", "vg_scan_grouped.hip.o", []), ("vg_multi_grouped.hip", "vg_multi_grouped.hip.o", []), ("vg_multi_grouped_masked.hip", "vg_multi_grouped_masked.hip.o", []), ("vg_scan_capped.hip", "vg_scan_capped.hip.o", []), ("vg_multi_capped.hip", "vg_multi_capped.hip.o", []), ("vg_multi_capped_masked.hip", "vg_multi_capped_masked.hip.o", []), ("vg_filter.hip", "vg_filter.hip.o", []),
              ("vg_batch_q8.hip", "vg_batch_q8.o", []),
              ("vg_batch_i8.hip", "vg_batch_i8.hip.o", []), ("vg_batch_i8.hip", "vg_batch_i8_pre.o", ["-DVGI_TU_PRE"]),
              ("vg_batch_h.hip", "vg_batch_h.hip.o", []), ("vg_batch_h.hip", "vg_batch_h_bf16.o", ["-DVGH_TU=1"]),

@@ -175,15 +175,15 @@ struct vg_corpus {
     int64_t mask_cap_words = 0;
     std::vector<uint64_t> mask_host;          // the same words on the host (vg_corpus_clone copies them)
     int64_t mask_count = -1;                  // rows allowed; -1: no mask
-    // labeled scans (vg_scan_labeled.hip, vg_multi_labeled.hip): a uint32 per scan position in device memory (VG_LABEL_NONE: the row
+    // labeled scans (vg_rowpred.hip, vg_multi_labeled.hip): a uint32 per scan position in device memory (VG_LABEL_NONE: the row
     // matches no query).  Read by the labeled scans only; lifetime rule for rule the mask's (vg_drop_labels).  d_label_bits: the bitmap
-    // "rows that carry label L" the single labeled scan builds for itself (vg_label_bits_kernel) - scratch, never the user's mask
+    // "rows the query may see" a row predicate's scan builds for itself (vg_pred_bits_enqueue) - scratch, never the user's mask
     uint32_t *d_labels = nullptr;             // n_rows dwords while labels are set (labels_cap allocated)
     int64_t labels_cap = 0;
     bool has_labels = false;
     uint64_t *d_label_bits = nullptr;         // ceil(n_rows / 64) words (label_bits_cap_words allocated)
     int64_t label_bits_cap_words = 0;
-    // label-set scans (vg_scan_labelset.hip, vg_multi_labelset.hip): scratch the handle owns.  d_lset: the sorted, de-duplicated
+    // label-set scans (vg_rowpred.hip, vg_multi_labelset.hip): scratch the handle owns.  d_lset: the sorted, de-duplicated
     // set(s) of the call in flight (single forms: one set; the batch: every membership group's sets, offsets and query masks);
     // lset_host: what the single forms upload from - it must not move before the upload ran, and every call ends in a wait.
     // d_member: the batch form's membership dword per row, refilled for every group of up to 32 queries in stream order
@@ -192,7 +192,7 @@ struct vg_corpus {
     std::vector<uint32_t> lset_host;
     uint32_t *d_member = nullptr;
     int64_t member_cap = 0;
-    // value-range scans (vg_scan_valued.hip, vg_multi_valued.hip): an int64 per scan position in device memory - any int64 is a value.
+    // value-range scans (vg_rowpred.hip, vg_multi_valued.hip): an int64 per scan position in device memory - any int64 is a value.
     // Read by the valued scans only; lifetime rule for rule the labels' (vg_drop_values).  Their bitmap and membership dwords go into
     // the label-set scans' scratch (d_label_bits, d_lset, d_member)
     int64_t *d_values = nullptr;              // n_rows values while values are set (values_cap allocated)
@@ -274,19 +274,42 @@ static inline void vg_drop_mask(vg_corpus *c) { c->mask_count = -1; c->mask_host
 int vg_mask_upload(vg_corpus *c);             // vg_scan_masked.hip: mask_host -> d_mask
 static inline void vg_drop_labels(vg_corpus *c) { c->has_labels = false; }   // (the device dwords stay allocated for the next labels)
 static inline void vg_drop_values(vg_corpus *c) { c->has_values = false; }   // (the same: the device values stay allocated)
-// vg_scan_labeled.hip: d_label_bits <- "labels[p] == label" for every row, enqueued on the corpus stream (no wait)
-int vg_label_bits_enqueue(vg_corpus *c, uint32_t label);
-// vg_scan_labelset.hip: d_label_bits <- "labels[p] is in the set" (exclude: "labels[p] is a label and not in the set") for every
-// row, enqueued on the corpus stream (no wait).  `sorted`: n ascending, distinct labels on the HOST, none of them VG_LABEL_NONE
-int vg_labelset_bits_enqueue(vg_corpus *c, const uint32_t *sorted, int64_t n, int exclude);
-int vg_lset_reserve(vg_corpus *c, size_t bytes);      // vg_scan_labelset.hip: d_lset holds at least `bytes`
+// ---- row predicates (vg_rowpred.hip): "which rows a query may see", as a condition over the handle's labels / values.  The single
+// and the range forms of the labeled, the label-set and the valued scans turn theirs into the scratch bitmap d_label_bits and run the
+// masked kernel tables over it (VG_ROWS_BITMAP below).  A fourth predicate: a kind, a constructor, a device functor, a case each in
+// vg_pred_refusal / vg_pred_allows_nothing / vg_pred_bits_enqueue, and its extern "C" entry points
+enum VgPredKind { VG_PRED_LABEL, VG_PRED_LABELSET, VG_PRED_VALUE };
+struct VgRowPred {
+    VgPredKind kind;
+    const char *noun;                          // "labeled" / "label-set" / "valued": what messages call the scans
+    uint32_t label; bool use_label;            // LABEL: the label.  VALUE: use_label - the row must also carry `label`
+    const uint32_t *set; int64_t n_set; int exclude;   // LABELSET: the caller's labels, any order, on the host
+    int64_t lo, hi;                            // VALUE: the closed interval
+};
+static inline VgRowPred vg_pred_label(uint32_t label) { return VgRowPred{VG_PRED_LABEL, "labeled", label, true, nullptr, 0, 0, 0, 0}; }
+static inline VgRowPred vg_pred_labelset(const uint32_t *labels, int64_t n, int exclude) {
+    return VgRowPred{VG_PRED_LABELSET, "label-set", 0u, false, labels, n, exclude ? 1 : 0, 0, 0};
+}
+static inline VgRowPred vg_pred_value(int64_t lo, int64_t hi) { return VgRowPred{VG_PRED_VALUE, "valued", 0u, false, nullptr, 0, 0, lo, hi}; }
+static inline VgRowPred vg_pred_value_labeled(int64_t lo, int64_t hi, uint32_t label) {
+    return VgRowPred{VG_PRED_VALUE, "valued", label, true, nullptr, 0, 0, lo, hi};
+}
+// what depends on the condition, in the order every form refuses: the column it reads is set (values first, then labels - also
+// required where the result is grouped by label), then the condition itself (VG_LABEL_NONE, a bad set pointer / count).  VG_OK: go on
+int vg_pred_refusal(const vg_corpus *c, const char *who, const VgRowPred &pred, bool needs_labels_for_grouping);
+bool vg_pred_allows_nothing(const VgRowPred &pred);   // lo > hi, an empty set without `exclude`: count 0 without a launch
+// d_label_bits <- "the row at p passes" for every row (bits behind n_rows clear), enqueued on the corpus stream, no wait.  A set is
+// sorted and de-duplicated into lset_host and uploaded into d_lset from there: it does not move before the scan behind this call has
+// waited for the stream
+int vg_pred_bits_enqueue(vg_corpus *c, const VgRowPred &pred);
+int vg_lset_reserve(vg_corpus *c, size_t bytes);      // vg_rowpred.hip: d_lset holds at least `bytes`
 // `n` labels of a caller's set -> ascending and distinct in *out; false (and the message set in `who`'s name): a bad pointer / count
 // or VG_LABEL_NONE in the set
 bool vg_labelset_normalise(const char *who, const uint32_t *labels, int64_t n, std::vector<uint32_t> *out);
-// the label-set batch (vg_multi_labelset.hip): what vg_fused_batch_run needs next to a form whose `single.labelset` is set - the
+// the label-set batch (vg_multi_labelset.hip): what vg_fused_batch_run needs next to a VG_QROWS_MEMBER form - the
 // queries' normalised sets in CSR form over the queries AS HANDED OVER (ordered by set: equal sets are neighbours), all on the host
 struct VgLabelsetBatch { const uint32_t *flat; const int64_t *offsets; int exclude; };
-// What a membership form (`single.labelset`) plugs into vg_fused_batch_run: where the allowed rows of its queries come from.  The
+// What a membership form (VG_QROWS_MEMBER) plugs into vg_fused_batch_run: where the allowed rows of its queries come from.  The
 // routine owns groups, slices, passes and the fallback's loop; the form owns the three steps that know its conditions.  `ctx`: the
 // form's conditions over the queries AS HANDED OVER (equal conditions are neighbours), on the host until the routine returns.
 //   pack_group     appends the table of queries [g0, g1) - one membership group - to *data (dwords of d_lset) and says what
@@ -301,9 +324,6 @@ struct VgMemberForm {
     int (*member_enqueue)(vg_corpus *c, const void *ctx, size_t at, int nd, size_t total);
     int (*bits_enqueue)(vg_corpus *c, const void *ctx, int i, bool *skip);
 };
-// vg_scan_valued.hip: d_label_bits <- "lo <= values[p] <= hi" (use_label: "... and labels[p] == label") for every row, enqueued on
-// the corpus stream (no wait)
-int vg_value_bits_enqueue(vg_corpus *c, int64_t lo, int64_t hi, int use_label, uint32_t label);
 // vg_multi_valued.hip: the membership pre-pass of one group of the valued batch - `nd` conditions of VG_VALUE_COND_DWORDS dwords
 // each behind one count dword, at dword `at` of d_lset
 int vg_value_member_enqueue(vg_corpus *c, size_t at, int nd, int any_label);
@@ -345,44 +365,55 @@ ScanArgs vg_scan_args(const vg_corpus *c, int metric, int acc, const VgShape &s,
 size_t vg_query_lds_bytes(const vg_corpus *c, const VgShape &s);   // the staged query in LDS (long rows: padded to whole slices)
 // the launch itself (VG_BLOCK threads), behind the dynamic-LDS attribute step a window above 64 KiB needs; enqueue only
 int vg_launch_scan_kernel(scan_fn_t fn, long long blocks, size_t smem, hipStream_t stream, const ScanArgs &a);
-// ---- the single range scan (vg_scan_within.hip: vg_within_run), shared by the unmasked, the masked and the labeled forms: which
-// kernel table (vg_pick_scan<Family> of the unit that holds the kernels), whether ScanArgs.mask is set and a mask required, whose name
-// errors carry.  `labeled` (the labeled range scans, vg_scan_within_labeled.hip), as in VgFusedForm: the masked kernels run over
-// c->d_label_bits - the caller enqueued vg_label_bits_enqueue / vg_labelset_bits_enqueue in front - and labels are required, not a mask
+// ---- what the form descriptors below are made of
 typedef scan_fn_t (*vg_pick_scan_fn_t)(int vtype, int acc, int U, bool long_rows);
-// `valued` (the valued range scan, vg_scan_valued.hip; with `labeled` set): the bitmap came from vg_value_bits_enqueue - values are required, not labels
-struct VgWithinForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool labeled; bool valued; };
+// where ScanArgs.mask of a single or a range scan comes from: nowhere, the user's mask (then required), or the scratch bitmap
+// d_label_bits a row predicate built on this stream in front of the scan (vg_pred_bits_enqueue)
+enum VgRows { VG_ROWS_ALL, VG_ROWS_MASK, VG_ROWS_BITMAP };
+// the same for a batch: the user's mask, a label per query (ScanArgs.labels / .qlabels; the caller hands the queries over ordered by
+// label), or the membership dwords of the pass' group (ScanArgs.labels = d_member, the pass' bit offset in ScanArgs.within_cap)
+enum VgBatchRows { VG_QROWS_ALL, VG_QROWS_MASK, VG_QROWS_LABEL, VG_QROWS_MEMBER };
+// the result: the k nearest rows; the k nearest labels by their best row (ScanArgs.labels, the label-deduping merge, labels in the
+// result); or the k nearest rows with at most per_label of one label (the grouped path with the cap, clamped to k, in
+// ScanArgs.within_cap and the capped merge)
+enum VgResultKind { VG_RESULT_PLAIN, VG_RESULT_GROUPED, VG_RESULT_CAPPED };
+struct VgResult {
+    VgResultKind kind; int per_label;
+    bool with_labels() const { return kind != VG_RESULT_PLAIN; }
+};
+static inline VgResult vg_result_plain() { return VgResult{VG_RESULT_PLAIN, 0}; }
+static inline VgResult vg_result_grouped() { return VgResult{VG_RESULT_GROUPED, 0}; }
+static inline VgResult vg_result_capped(int per_label) { return VgResult{VG_RESULT_CAPPED, per_label}; }
+// ---- the single range scan (vg_scan_within.hip: vg_within_run), shared by every range form: whose name errors carry, the kernel
+// table (vg_pick_scan<Family> of the unit that holds the kernels), the allowed rows, and the columns the handle must hold
+struct VgWithinForm { const char *who; vg_pick_scan_fn_t pick; VgRows rows; bool needs_labels; bool needs_values; };
+static inline VgWithinForm vg_within_form(const char *who, vg_pick_scan_fn_t pick, VgRows rows) { return VgWithinForm{who, pick, rows, false, false}; }
+// what every single range scan answers first, whatever its form: the counts zeroed, NULL arguments, the held result and the launch
+// count of the scan in front dropped, then the metric and the radius.  VG_OK: go on
+int vg_within_begin(vg_corpus *c, const char *who, int metric, const void *query, double radius, int64_t *out_matches, int64_t *out_held);
 int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                   int64_t *out_held);
 scan_fn_t vg_pick_scan_within_masked(int vtype, int acc, int U, bool long_rows);   // vg_scan_within_masked.hip: the masked single range scan's kernel table
 scan_fn_t vg_pick_multi_within_masked(int vtype, int acc, int U, int NQ);   // vg_multi_within_masked.hip: the masked batch range scan's kernel table
 scan_fn_t vg_pick_multi_within_labeled(int vtype, int acc, int U, int NQ);  // vg_multi_within_labeled.hip: the labeled batch range scan's kernel table
-// ---- the fused top-k scan of a variant (k <= 64, ascending (distance, scan position) order), shared by the masked and the paged
-// scans: the kernel table, whether ScanArgs.mask is set and a mask required, whether ScanArgs.floor is, whose name errors carry.
-// vg_fused_run (vg_scan_masked.hip): one query; `floor` = the smallest key admitted (after forms).  vg_fused_batch_run
-// (vg_multi_masked.hip): nq queries, `floors` = a key each (after forms, nullptr otherwise); the fallback of a shape without a
-// multi-query form is nq calls of vg_fused_run with the single form.
+// ---- the fused top-k scan of a variant (k <= 64, ascending (distance, scan position) order): whose name errors carry and what they
+// call the scans (`noun`), the kernel table, the allowed rows, the columns the handle must hold, the result, and `after` - ScanArgs.floor
+// is set (the paged scans).  vg_fused_run (vg_scan_masked.hip): one query; `floor` = the smallest key admitted (after forms).
+// vg_fused_batch_run (vg_multi_masked.hip): nq queries, `floors` = a key each (after forms, nullptr otherwise); the fallback of a
+// shape without a multi-query form is nq calls of vg_fused_run with the single form.
 typedef scan_fn_t (*vg_pick_multi_fn_t)(int vtype, int acc, int U, int NQ);
 scan_fn_t vg_pick_scan_masked(int vtype, int acc, int U, bool long_rows);   // vg_scan_masked.hip: the masked single scan's kernel table
 scan_fn_t vg_pick_scan_after(int vtype, int acc, int U, bool long_rows);    // vg_scan_after.hip: the paged single scans' tables,
 scan_fn_t vg_pick_scan_after_masked(int vtype, int acc, int U, bool long_rows);   // ... all rows / the allowed rows
-// `labeled` (the labeled scans, vg_scan_labeled.hip / vg_multi_labeled.hip): the single form runs the masked kernels over
-// c->d_label_bits - the caller enqueued vg_label_bits_enqueue in front - and requires labels, not a mask; the batch form sets
-// ScanArgs.labels / .qlabels, `qlabels` = a label per query (the caller hands the queries over ordered by label: the fallback
-// builds one bitmap per run of equal labels).
-// `grouped` (the grouped scans, vg_scan_grouped.hip): ScanArgs.labels is set and labels are required, the lists of the workgroups go
-// through vg_launch_merge_grouped instead of the rank-select merge, and vg_fused_run also yields the winners' labels (out_labels).
-// `per_label` >= 1 (the capped scans, vg_scan_capped.hip; with `grouped` set, whose host path they share): the cap m travels in
-// ScanArgs.within_cap, clamped to k, and the lists of the workgroups go through vg_launch_merge_capped.  0: not a capped form.
-// `labelset` (the label-set scans, vg_scan_labelset.hip / vg_multi_labelset.hip; with `labeled` set, whose single path they share - the
-// caller enqueued vg_labelset_bits_enqueue in front): the batch form reads no query labels; it points ScanArgs.labels at the
-// membership dwords of the pass' group (c->d_member, filled by a pre-pass per 32 queries) and puts the pass' bit offset into
-// ScanArgs.within_cap; its fallback builds one bitmap per run of equal sets.
-// `valued` (the value-range scans, vg_scan_valued.hip / vg_multi_valued.hip; with `labeled` and `labelset` set, whose paths they
-// share - the caller enqueued vg_value_bits_enqueue in front): values are required; labels only by a grouped form, or where the
-// caller itself asked for the conjunction with a label and checked.
-struct VgFusedForm { const char *who; vg_pick_scan_fn_t pick; bool masked; bool after; bool labeled; bool grouped; int per_label; bool labelset; bool valued; };
-struct VgFusedBatchForm { const char *who; vg_pick_multi_fn_t pick; VgFusedForm single; };
+struct VgFusedForm {
+    const char *who; const char *noun; vg_pick_scan_fn_t pick;
+    VgRows rows; bool needs_labels; bool needs_values; VgResult result; bool after;
+};
+// a form over all rows or the user's mask; a result by label requires labels.  Anything else: set the field by name
+static inline VgFusedForm vg_fused_form(const char *who, const char *noun, vg_pick_scan_fn_t pick, VgRows rows, VgResult result = vg_result_plain()) {
+    return VgFusedForm{who, noun, pick, rows, result.with_labels(), false, result, false};
+}
+struct VgFusedBatchForm { const char *who; vg_pick_multi_fn_t pick; VgBatchRows rows; VgFusedForm single; };
 int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count,
                  uint32_t *out_labels = nullptr);
 // vg_scan_grouped.hip: the label-deduping final merge of `nlists` <= 256 per-workgroup lists (keys only; a key's label is
@@ -397,6 +428,65 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
 // out_* + i * k.  labels / out_labels: both or neither; a single scan is nq = 1
 void vg_keys_to_rows(const vg_corpus *c, const uint64_t *keys, const uint32_t *labels, int nq, int k, const int *counts, int64_t *out_rowids,
                      double *out_dist, uint32_t *out_labels);
+// ---- the single and the range form of every row predicate (vg_rowpred.hip): argument checks, vg_pred_refusal, the answer without a
+// launch, the bitmap, then vg_fused_run / vg_within_run with a VG_ROWS_BITMAP form over the masked table of the result.  out_labels:
+// required by a result with labels, ignored otherwise
+int vg_pred_topk_keys(vg_corpus *c, const char *who, VgResult result, const VgRowPred &pred, int metric, const void *query, int k,
+                      uint64_t *out_keys, uint32_t *out_labels, int *out_count);
+int vg_pred_topk_rows(vg_corpus *c, const char *who, VgResult result, const VgRowPred &pred, int metric, const void *query, int k,
+                      int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count);
+int vg_pred_within(vg_corpus *c, const char *who, const VgRowPred &pred, int metric, const void *query, double radius, int64_t limit,
+                   int64_t *out_matches, int64_t *out_held);
+VgFusedForm vg_pred_form(const char *who, const VgRowPred &pred, VgResult result);   // ... that form (the fallback of the batches names it)
+// ---- a batch that runs its queries in an order of its own (by label, by set, by condition: equal ones become neighbours)
+// the stable order of nq queries under `less(x, y)` over caller indices
+template <class Less> static inline std::vector<int> vg_stable_order(int nq, Less less) {
+    std::vector<int> order((size_t)nq);
+    for (int i = 0; i < nq; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), less);
+    return order;
+}
+// the query block in that order: slot i holds the caller's query order[i]
+static inline std::vector<uint8_t> vg_permute_queries(const vg_corpus *c, const void *queries, const std::vector<int> &order) {
+    const size_t row_bytes = (size_t)c->dim * c->es;
+    std::vector<uint8_t> sq(order.size() * row_bytes);
+    for (size_t i = 0; i < order.size(); ++i) memcpy(sq.data() + i * row_bytes, (const uint8_t *)queries + (size_t)order[i] * row_bytes, row_bytes);
+    return sq;
+}
+// run(ordered queries, keys, counts) over buffers in that order - keys: nq x k, nullptr where the caller's out_keys is; counts: zeroed -
+// then, when it answered VG_OK, keys and counts back at the caller's indices.  out_counts is not touched before `run` returns
+template <class Run> static inline int vg_ordered_batch(const vg_corpus *c, const void *queries, int nq, int k, const std::vector<int> &order,
+                                                        uint64_t *out_keys, int *out_counts, Run run) {
+    const std::vector<uint8_t> sq = vg_permute_queries(c, queries, order);
+    std::vector<uint64_t> skeys((k >= 1 && k <= VG_WAVE_HOST) ? (size_t)nq * k : 1);
+    std::vector<int> scounts((size_t)nq, 0);
+    int rc = run((const void *)sq.data(), out_keys ? skeys.data() : nullptr, scounts.data());
+    if (rc != VG_OK) return rc;
+    for (int i = 0; i < nq; ++i) {
+        const int dst = order[(size_t)i];
+        out_counts[dst] = scounts[(size_t)i];
+        memcpy(out_keys + (size_t)dst * k, skeys.data() + (size_t)i * k, (size_t)scounts[(size_t)i] * sizeof(uint64_t));
+    }
+    return VG_OK;
+}
+// the rows form of a batch over its keys form: NULL arguments (args_null: the caller's own test of them, the corpus included), the
+// counts zeroed, the outputs checked where nq and k (k_ok) size them, then run(keys, labels) into buffers of nq x k - labels only
+// for with_labels - and the keys as rows
+template <class Run> static inline int vg_batch_rows_from_keys(const vg_corpus *c, const char *who, bool args_null, int nq, int k, bool k_ok,
+                                                               bool with_labels, int64_t *out_rowids, double *out_dist, uint32_t *out_labels,
+                                                               int *out_counts, Run run) {
+    if (args_null) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", who);
+    for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    const bool sized = nq >= 1 && k_ok;
+    if (sized && (!out_rowids || !out_dist || (with_labels && !out_labels))) return vg_fail(VG_ERR_INVALID, "%s: NULL output", who);
+    std::vector<uint64_t> keys(sized ? (size_t)nq * k : 1);
+    std::vector<uint32_t> labels(!with_labels ? 0 : sized ? (size_t)nq * k : 1);
+    uint32_t *labs = with_labels ? labels.data() : nullptr;
+    int rc = run(keys.data(), labs);
+    if (rc != VG_OK) return rc;
+    vg_keys_to_rows(c, keys.data(), labs, nq, k, out_counts, out_rowids, out_dist, out_labels);
+    return VG_OK;
+}
 // vg_multi_masked.hip: what every vg_batch_*_plan answers - `pick`: the form's multi-query kernel table; queries per pass (0: the
 // table has no instance for the shape, the single scans serve it) and the launch shape of whichever runs.  Refuses a NULL corpus and
 // an unknown metric
@@ -411,13 +501,13 @@ int vg_labelset_member_enqueue(vg_corpus *c, size_t at, int nd, size_t total, in
 scan_fn_t vg_pick_multi_labelset(int vtype, int acc, int U, int NQ);   // vg_multi_labelset.hip: the label-set batch's kernel table
 int vg_member_reserve(vg_corpus *c);                  // vg_multi_labelset.hip: d_member holds a dword per row
 // the batch launch of that merge (vg_multi_grouped.hip): workgroup n merges query n's `nlists` lists ([nq][nlists][64] keys at dev_cand) and writes its 64
-// keys and 64 labels at dev_out + n * VG_KEYS_BYTES.  A grouped VgFusedBatchForm (`single.grouped`, vg_multi_grouped.hip) ends in it:
+// keys and 64 labels at dev_out + n * VG_KEYS_BYTES.  A VgFusedBatchForm with a grouped result (vg_multi_grouped.hip) ends in it:
 // vg_fused_batch_run then sets ScanArgs.labels, requires labels, sizes a slice's key buffer for the labels and fills out_labels (nq x k)
 int vg_launch_merge_grouped_batch(const uint64_t *dev_cand, int nlists, int k, const uint32_t *dev_labels, uint64_t *dev_out, int nq, hipStream_t stream);
 scan_fn_t vg_pick_scan_grouped(int vtype, int acc, int U, bool long_rows);          // vg_scan_grouped.hip: the grouped single scans' tables,
 scan_fn_t vg_pick_scan_grouped_masked(int vtype, int acc, int U, bool long_rows);   // ... all rows / the allowed rows
 scan_fn_t vg_pick_multi_grouped_masked(int vtype, int acc, int U, int NQ);          // vg_multi_grouped_masked.hip: the masked grouped batch's table
-// the capped batch (vg_multi_capped.hip): a grouped VgFusedBatchForm whose `single.per_label` is set - vg_fused_batch_run then puts the
+// the capped batch (vg_multi_capped.hip): a VgFusedBatchForm with a capped result - vg_fused_batch_run then puts the
 // cap, clamped to k, into ScanArgs.within_cap and ends every pass in this merge in place of the grouped batch's; the rest is that path
 int vg_launch_merge_capped_batch(const uint64_t *dev_cand, int nlists, int k, int per_label, const uint32_t *dev_labels, uint64_t *dev_out, int nq,
                                  hipStream_t stream);

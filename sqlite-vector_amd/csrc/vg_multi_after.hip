@@ -13,9 +13,12 @@
 #include "vg_pick.h"
 
 static VgFusedBatchForm batch_form(bool masked) {
-    if (masked) return VgFusedBatchForm{"vg_scan_topk_batch_after_masked", vg_pick_multi<MultiFamily<VG_MQ_AFTER | VG_MQ_MASKED>>,
-                                        {"vg_scan_topk_after_masked", vg_pick_scan_after_masked, true, true}};
-    return VgFusedBatchForm{"vg_scan_topk_batch_after", vg_pick_multi<MultiFamily<VG_MQ_AFTER>>, {"vg_scan_topk_after", vg_pick_scan_after, false, true}};
+    VgFusedBatchForm f = masked ? VgFusedBatchForm{"vg_scan_topk_batch_after_masked", vg_pick_multi<MultiFamily<VG_MQ_AFTER | VG_MQ_MASKED>>, VG_QROWS_MASK,
+                                                   vg_fused_form("vg_scan_topk_after_masked", "masked", vg_pick_scan_after_masked, VG_ROWS_MASK)}
+                                : VgFusedBatchForm{"vg_scan_topk_batch_after", vg_pick_multi<MultiFamily<VG_MQ_AFTER>>, VG_QROWS_ALL,
+                                                   vg_fused_form("vg_scan_topk_after", "paged", vg_pick_scan_after, VG_ROWS_ALL)};
+    f.single.after = true;
+    return f;
 }
 
 // Query i's answer must be the single form's bit for bit - a cursor taken from a single page or from vg_scan_distances is fed to the
@@ -62,25 +65,20 @@ static int batch_after_keys(vg_corpus *c, bool masked, int metric, const void *q
 static int batch_after_rows(vg_corpus *c, bool masked, int metric, const void *queries, int nq, int k, const double *after_dists,
                             const int64_t *after_rowids, int64_t *out_rowids, double *out_dist, int *out_counts) {
     const char *who = batch_form(masked).who;
-    if (!c || !queries || !out_counts || !after_dists || !after_rowids) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", who);
-    if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", who);
-    const bool k_ok = k >= 1 && k <= VG_MAX_FUSED_K;
-    if (k_ok && (!out_rowids || !out_dist)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", who);
-    std::vector<uint64_t> floors((size_t)nq, VG_KEY_EMPTY);
-    for (int i = 0; i < nq; ++i) {
-        out_counts[i] = 0;
-        if (after_dists[i] != after_dists[i]) return vg_fail(VG_ERR_INVALID, "%s: the distance of cursor %d is NaN", who, i);
-        const int64_t P = vg_corpus_rows_upto_rowid(c, after_rowids[i]);
-        if (P == -2) return vg_fail(VG_ERR_UNSUPPORTED, "%s: the corpus' rowids are not ascending (no rowid order); page by key (the _keys form)", who);
-        int empty = 0;
-        int rc = vg_after_floor(after_dists[i], (uint32_t)P, &floors[(size_t)i], &empty);      // (an exhausted cursor: VG_KEY_EMPTY, nothing admitted)
-        if (rc != VG_OK) return rc;
-    }
-    std::vector<uint64_t> keys(k_ok ? (size_t)nq * k : 1);
-    int rc = vg_after_floor_batch_run(c, masked, metric, queries, nq, k, floors.data(), keys.data(), out_counts);
-    if (rc != VG_OK) return rc;
-    vg_keys_to_rows(c, keys.data(), nullptr, nq, k, out_counts, out_rowids, out_dist, nullptr);
-    return VG_OK;
+    return vg_batch_rows_from_keys(c, who, !c || !queries || !out_counts || !after_dists || !after_rowids, nq, k, k >= 1 && k <= VG_MAX_FUSED_K, false,
+                                   out_rowids, out_dist, nullptr, out_counts, [&](uint64_t *keys, uint32_t *) {
+        if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", who);
+        std::vector<uint64_t> floors((size_t)nq, VG_KEY_EMPTY);
+        for (int i = 0; i < nq; ++i) {
+            if (after_dists[i] != after_dists[i]) return vg_fail(VG_ERR_INVALID, "%s: the distance of cursor %d is NaN", who, i);
+            const int64_t P = vg_corpus_rows_upto_rowid(c, after_rowids[i]);
+            if (P == -2) return vg_fail(VG_ERR_UNSUPPORTED, "%s: the corpus' rowids are not ascending (no rowid order); page by key (the _keys form)", who);
+            int empty = 0;
+            int rc = vg_after_floor(after_dists[i], (uint32_t)P, &floors[(size_t)i], &empty);      // (an exhausted cursor: VG_KEY_EMPTY, nothing admitted)
+            if (rc != VG_OK) return rc;
+        }
+        return vg_after_floor_batch_run(c, masked, metric, queries, nq, k, floors.data(), keys, out_counts);
+    });
 }
 
 extern "C" int vg_scan_topk_batch_after(vg_corpus *c, int metric, const void *queries, int nq, int k, const double *after_dists,

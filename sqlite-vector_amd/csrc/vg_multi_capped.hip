@@ -4,7 +4,7 @@
 // Host side of the capped form of the multi-query scan (vg_scan_multi.h, VG_MQ_GROUPED | VG_MQ_CAPPED) and the home of its unmasked
 // kernel instances (f32 / uint8 / int8 x L2 / cosine / dot / L1 x U in {1, 2, 3} at 4 queries per pass, {4, 6} at 2); the masked
 // family compiles next to it in vg_multi_capped_masked.hip.  The batch itself is vg_fused_batch_run (vg_multi_masked.hip) with a
-// grouped form whose per_label is set: the grouped batch's slices, back-to-back passes, one copy of keys and labels and one wait,
+// capped result: the grouped batch's slices, back-to-back passes, one copy of keys and labels and one wait,
 // with the cap in ScanArgs.within_cap and the capped merge per query (vg_merge_capped_batch_kernel, below).  Query i gets what the
 // single capped scan (vg_scan_capped.hip) is contracted to return for it; one cap serves the whole batch.  Shapes without a
 // multi-query form (f16 / bf16, long rows, an instance left out of a table): one single capped scan per query - a shape that scan
@@ -60,9 +60,10 @@ int vg_launch_merge_capped_batch(const uint64_t *dev_cand, int nlists, int k, in
 // ------------------------------------------------------------------------------------------------ the scans
 
 static VgFusedBatchForm capped_batch_form(bool masked, int per_label) {
-    if (masked) return VgFusedBatchForm{"vg_scan_topk_batch_capped_masked", pick_multi_capped_masked,
-                                        {"vg_scan_topk_capped_masked", vg_pick_scan_capped_masked, true, false, false, true, per_label}};
-    return VgFusedBatchForm{"vg_scan_topk_batch_capped", pick_multi_capped, {"vg_scan_topk_capped", vg_pick_scan_capped, false, false, false, true, per_label}};
+    if (masked) return VgFusedBatchForm{"vg_scan_topk_batch_capped_masked", pick_multi_capped_masked, VG_QROWS_MASK,
+                                        vg_fused_form("vg_scan_topk_capped_masked", "capped", vg_pick_scan_capped_masked, VG_ROWS_MASK, vg_result_capped(per_label))};
+    return VgFusedBatchForm{"vg_scan_topk_batch_capped", pick_multi_capped, VG_QROWS_ALL,
+                            vg_fused_form("vg_scan_topk_capped", "capped", vg_pick_scan_capped, VG_ROWS_ALL, vg_result_capped(per_label))};
 }
 
 extern "C" int vg_batch_capped_plan(const vg_corpus *c, int metric, int masked, int *out_queries_per_pass, int *out_lpr, int *out_u) {
@@ -83,17 +84,11 @@ static int capped_batch_keys(vg_corpus *c, bool masked, int metric, const void *
 
 static int capped_batch_rows(vg_corpus *c, bool masked, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
                              double *out_dist, uint32_t *out_labels, int *out_counts) {
-    const char *who = capped_batch_form(masked, per_label).who;
-    if (!c || !queries || !out_counts) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", who);
-    const bool k_ok = k >= 1 && k <= VG_MAX_FUSED_K && per_label >= 1;
-    if (nq >= 1) for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (nq >= 1 && k_ok && (!out_rowids || !out_dist || !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", who);
-    std::vector<uint64_t> keys((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
-    std::vector<uint32_t> labels((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
-    int rc = capped_batch_keys(c, masked, metric, queries, nq, k, per_label, keys.data(), labels.data(), out_counts);
-    if (rc != VG_OK) return rc;
-    vg_keys_to_rows(c, keys.data(), labels.data(), nq, k, out_counts, out_rowids, out_dist, out_labels);
-    return VG_OK;
+    return vg_batch_rows_from_keys(c, capped_batch_form(masked, per_label).who, !c || !queries || !out_counts, nq, k,
+                                   k >= 1 && k <= VG_MAX_FUSED_K && per_label >= 1, true, out_rowids, out_dist, out_labels, out_counts,
+                                   [&](uint64_t *keys, uint32_t *labels) {
+        return capped_batch_keys(c, masked, metric, queries, nq, k, per_label, keys, labels, out_counts);
+    });
 }
 
 extern "C" int vg_scan_topk_batch_capped(vg_corpus *c, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,

@@ -57,9 +57,10 @@ int vg_launch_merge_grouped_batch(const uint64_t *dev_cand, int nlists, int k, c
 // ------------------------------------------------------------------------------------------------ the scans
 
 static VgFusedBatchForm grouped_batch_form(bool masked) {
-    if (masked) return VgFusedBatchForm{"vg_scan_topk_batch_grouped_masked", pick_multi_grouped_masked,
-                                        {"vg_scan_topk_grouped_masked", vg_pick_scan_grouped_masked, true, false, false, true}};
-    return VgFusedBatchForm{"vg_scan_topk_batch_grouped", pick_multi_grouped, {"vg_scan_topk_grouped", vg_pick_scan_grouped, false, false, false, true}};
+    if (masked) return VgFusedBatchForm{"vg_scan_topk_batch_grouped_masked", pick_multi_grouped_masked, VG_QROWS_MASK,
+                                        vg_fused_form("vg_scan_topk_grouped_masked", "grouped", vg_pick_scan_grouped_masked, VG_ROWS_MASK, vg_result_grouped())};
+    return VgFusedBatchForm{"vg_scan_topk_batch_grouped", pick_multi_grouped, VG_QROWS_ALL,
+                            vg_fused_form("vg_scan_topk_grouped", "grouped", vg_pick_scan_grouped, VG_ROWS_ALL, vg_result_grouped())};
 }
 
 extern "C" int vg_batch_grouped_plan(const vg_corpus *c, int metric, int masked, int *out_queries_per_pass, int *out_lpr, int *out_u) {
@@ -73,17 +74,10 @@ static int grouped_batch_keys(vg_corpus *c, bool masked, int metric, const void 
 
 static int grouped_batch_rows(vg_corpus *c, bool masked, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
                               double *out_dist, uint32_t *out_labels, int *out_counts) {
-    const char *who = grouped_batch_form(masked).who;
-    if (!c || !queries || !out_counts) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", who);
-    const bool k_ok = k >= 1 && k <= VG_MAX_FUSED_K;
-    if (nq >= 1) for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (nq >= 1 && k_ok && (!out_rowids || !out_dist || !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", who);
-    std::vector<uint64_t> keys((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
-    std::vector<uint32_t> labels((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
-    int rc = grouped_batch_keys(c, masked, metric, queries, nq, k, keys.data(), labels.data(), out_counts);
-    if (rc != VG_OK) return rc;
-    vg_keys_to_rows(c, keys.data(), labels.data(), nq, k, out_counts, out_rowids, out_dist, out_labels);
-    return VG_OK;
+    return vg_batch_rows_from_keys(c, grouped_batch_form(masked).who, !c || !queries || !out_counts, nq, k, k >= 1 && k <= VG_MAX_FUSED_K, true,
+                                   out_rowids, out_dist, out_labels, out_counts, [&](uint64_t *keys, uint32_t *labels) {
+        return grouped_batch_keys(c, masked, metric, queries, nq, k, keys, labels, out_counts);
+    });
 }
 
 extern "C" int vg_scan_topk_batch_grouped(vg_corpus *c, int metric, const void *queries, int nq, int k, int64_t *out_rowids,

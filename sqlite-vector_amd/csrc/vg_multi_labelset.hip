@@ -19,14 +19,12 @@
 // Where the sets are searched: a group whose distinct sets hold at most VG_LSET_LDS_MAX labels in all (8192: 32 KiB + the offsets and
 // masks) is staged into LDS by every workgroup and searched there; a larger group is searched in global memory, where the upper
 // levels of every search stay in the cache (DESIGN.md 3.20 has the sizes both were tested at).
-// Shapes without a multi-query form (f16 / bf16, long rows): one single label-set scan per query (vg_scan_labelset.hip) in that same
+// Shapes without a multi-query form (f16 / bf16, long rows): one single label-set scan per query (vg_rowpred.hip) in that same
 // order, the bitmap rebuilt only where the set changes.
 #include "vg_internal.h"
 
 #include "vg_scan_multi.h"
 #include "vg_pick.h"
-
-#include <numeric>
 
 #define VG_LSET_GROUP 32
 #define VG_LSET_LDS_MAX 8192
@@ -125,7 +123,7 @@ static int labelset_bits_step(vg_corpus *c, const void *ctx, int i, bool *skip) 
     const int64_t ni = lsets->offsets[i + 1] - lsets->offsets[i];
     if (ni == 0 && !lsets->exclude) { *skip = true; return VG_OK; }
     const int64_t np = i > 0 ? lsets->offsets[i] - lsets->offsets[i - 1] : -1;
-    if (ni != np || !std::equal(si, si + ni, lsets->flat + lsets->offsets[i - 1])) return vg_labelset_bits_enqueue(c, si, ni, lsets->exclude);
+    if (ni != np || !std::equal(si, si + ni, lsets->flat + lsets->offsets[i - 1])) return vg_pred_bits_enqueue(c, vg_pred_labelset(si, ni, lsets->exclude));
     return VG_OK;
 }
 
@@ -139,8 +137,8 @@ extern "C" int vg_batch_labelset_plan(const vg_corpus *c, int metric, int *out_q
 
 extern "C" int vg_scan_topk_batch_labelset_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
                                                 const int64_t *set_offsets, int exclude, uint64_t *out_keys, int *out_counts) {
-    const VgFusedBatchForm form = {"vg_scan_topk_batch_labelset", pick_multi_labelset,
-                                   {"vg_scan_topk_labelset", vg_pick_scan_masked, false, false, true, false, 0, true}};
+    const VgFusedBatchForm form = {"vg_scan_topk_batch_labelset", pick_multi_labelset, VG_QROWS_MEMBER,
+                                   vg_pred_form("vg_scan_topk_labelset", vg_pred_labelset(nullptr, 0, exclude), vg_result_plain())};
     if (!c || !queries || !out_counts || !set_offsets) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", form.who);
     if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", form.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
@@ -154,42 +152,25 @@ extern "C" int vg_scan_topk_batch_labelset_keys(vg_corpus *c, int metric, const 
     std::vector<std::vector<uint32_t>> sets((size_t)nq);
     for (int i = 0; i < nq; ++i)
         if (!vg_labelset_normalise(form.who, set_labels + set_offsets[i], set_offsets[i + 1] - set_offsets[i], &sets[(size_t)i])) return VG_ERR_INVALID;
-    std::vector<int> order((size_t)nq);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return sets[(size_t)x] < sets[(size_t)y]; });
-    const size_t row_bytes = (size_t)c->dim * c->es;
-    std::vector<uint8_t> sq((size_t)nq * row_bytes);
+    const std::vector<int> order = vg_stable_order(nq, [&](int x, int y) { return sets[(size_t)x] < sets[(size_t)y]; });
     std::vector<uint32_t> flat;
     std::vector<int64_t> offs((size_t)nq + 1, 0);
     for (int i = 0; i < nq; ++i) {
         const std::vector<uint32_t> &s = sets[(size_t)order[(size_t)i]];
-        memcpy(sq.data() + (size_t)i * row_bytes, (const uint8_t *)queries + (size_t)order[(size_t)i] * row_bytes, row_bytes);
         flat.insert(flat.end(), s.begin(), s.end());
         offs[(size_t)i + 1] = (int64_t)flat.size();
     }
     const VgLabelsetBatch ls = {flat.data(), offs.data(), exclude ? 1 : 0};
-    std::vector<uint64_t> skeys((size_t)nq * k);
-    std::vector<int> scounts((size_t)nq, 0);
     const VgMemberForm member = {&ls, labelset_pack_group, labelset_member_step, labelset_bits_step};
-    int rc = vg_fused_batch_run(c, form, metric, sq.data(), nq, k, nullptr, out_keys ? skeys.data() : nullptr, scounts.data(), nullptr, nullptr, &member);
-    if (rc != VG_OK) return rc;
-    for (int i = 0; i < nq; ++i) {
-        const int dst = order[(size_t)i];
-        out_counts[dst] = scounts[(size_t)i];
-        memcpy(out_keys + (size_t)dst * k, skeys.data() + (size_t)i * k, (size_t)scounts[(size_t)i] * sizeof(uint64_t));
-    }
-    return VG_OK;
+    return vg_ordered_batch(c, queries, nq, k, order, out_keys, out_counts, [&](const void *sq, uint64_t *skeys, int *scounts) {
+        return vg_fused_batch_run(c, form, metric, sq, nq, k, nullptr, skeys, scounts, nullptr, nullptr, &member);
+    });
 }
 
 extern "C" int vg_scan_topk_batch_labelset(vg_corpus *c, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
                                            const int64_t *set_offsets, int exclude, int64_t *out_rowids, double *out_dist, int *out_counts) {
-    if (!c || !queries || !out_counts || !set_offsets) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: NULL argument");
-    const bool k_ok = k >= 1 && k <= VG_MAX_FUSED_K;
-    if (nq >= 1) for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (nq >= 1 && k_ok && (!out_rowids || !out_dist)) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_labelset: NULL output");
-    std::vector<uint64_t> keys((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
-    int rc = vg_scan_topk_batch_labelset_keys(c, metric, queries, nq, k, set_labels, set_offsets, exclude, keys.data(), out_counts);
-    if (rc != VG_OK) return rc;
-    vg_keys_to_rows(c, keys.data(), nullptr, nq, k, out_counts, out_rowids, out_dist, nullptr);
-    return VG_OK;
+    return vg_batch_rows_from_keys(c, "vg_scan_topk_batch_labelset", !c || !queries || !out_counts || !set_offsets, nq, k,
+                                   k >= 1 && k <= VG_MAX_FUSED_K, false, out_rowids, out_dist, nullptr, out_counts, [&](uint64_t *keys, uint32_t *) {
+        return vg_scan_topk_batch_labelset_keys(c, metric, queries, nq, k, set_labels, set_offsets, exclude, keys, out_counts);
+    });
 }

@@ -41,23 +41,23 @@ extern "C" int vg_batch_masked_plan(const vg_corpus *c, int metric, int *out_que
 // NQ * (<= 256) * 64 keys of scratch; dev_out_keys: NQ x 64 keys.  Asynchronous on the corpus stream.  One launcher for every form
 // (VgFusedBatchForm, vg_internal.h): the masked batch, and the paged batches of vg_multi_after.hip (dev_floors: NQ keys).
 // A grouped form (vg_multi_grouped.hip): the lists merge through the label-deduping merge and dev_out_keys receives, per query, 64
-// keys followed by their 64 labels (VG_KEYS_BYTES).  A capped form (vg_multi_capped.hip: grouped, with single.per_label set): the
-// cap, clamped to k, travels in ScanArgs.within_cap - which no other top-k instance reads - and the lists merge through the capped
-// batch merge; everything else is the grouped form's.  A label-set form (vg_multi_labelset.hip: labeled, with single.labelset set):
-// ScanArgs.labels is the membership buffer of the pass' group and `member_shift`, the pass' bit offset inside that group, travels in
-// ScanArgs.within_cap; no query labels.  The valued batch (vg_multi_valued.hip) is a label-set form with another pre-pass.
+// keys followed by their 64 labels (VG_KEYS_BYTES).  A capped form (vg_multi_capped.hip): the cap, clamped to k, travels in
+// ScanArgs.within_cap - which no other top-k instance reads - and the lists merge through the capped batch merge; everything else
+// is the grouped form's.  A membership form (VG_QROWS_MEMBER: vg_multi_labelset.hip, vg_multi_valued.hip): ScanArgs.labels is the
+// membership buffer of the pass' group and `member_shift`, the pass' bit offset inside that group, travels in ScanArgs.within_cap.
 static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s,
                                const uint8_t *dev_queries, const uint64_t *dev_floors, const uint32_t *dev_qlabels, int k, uint64_t *dev_cand,
                                uint64_t *dev_out_keys, int member_shift = 0) {
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);
     ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_queries, k);
     a.cand = dev_cand;
-    if (f.single.masked) a.mask = c->d_mask;
+    const VgResult &res = f.single.result;
+    if (f.rows == VG_QROWS_MASK) a.mask = c->d_mask;
     if (f.single.after) a.floor = dev_floors;
-    if (f.single.labeled && !f.single.labelset) { a.labels = c->d_labels; a.qlabels = dev_qlabels; }
-    if (f.single.labelset) { a.labels = c->d_member; a.within_cap = (unsigned long long)member_shift; }
-    if (f.single.grouped) a.labels = c->d_labels;
-    const int cap = std::min(f.single.per_label, k);          // (capped forms: more than k of one label cannot be returned)
+    if (f.rows == VG_QROWS_LABEL) { a.labels = c->d_labels; a.qlabels = dev_qlabels; }
+    if (f.rows == VG_QROWS_MEMBER) { a.labels = c->d_member; a.within_cap = (unsigned long long)member_shift; }
+    if (res.with_labels()) a.labels = c->d_labels;
+    const int cap = res.kind == VG_RESULT_CAPPED ? std::min(res.per_label, k) : 0;   // (more than k of one label cannot be returned)
     if (cap > 0) a.within_cap = (unsigned long long)cap;
     const size_t smem = std::max<size_t>((size_t)NQ * c->nch * 16, (size_t)VG_PUBLISH_LDS_BYTES);
     hipEvent_t *evs = vg_prof_slot(c, VG_EVF_MERGE);          // one slot of the profiling ring per pass
@@ -66,8 +66,8 @@ static int launch_fused_multi(vg_corpus *c, const VgFusedBatchForm &f, int metri
     if (rc != VG_OK) return rc;
     if (evs) hipEventRecord(evs[2], c->stream);
     rc = cap > 0          ? vg_launch_merge_capped_batch(dev_cand, (int)blocks, k, cap, c->d_labels, dev_out_keys, NQ, c->stream)
-         : f.single.grouped ? vg_launch_merge_grouped_batch(dev_cand, (int)blocks, k, c->d_labels, dev_out_keys, NQ, c->stream)
-                            : vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
+         : res.with_labels() ? vg_launch_merge_grouped_batch(dev_cand, (int)blocks, k, c->d_labels, dev_out_keys, NQ, c->stream)
+                             : vg_launch_merge(dev_cand, (int)blocks, k, dev_out_keys, NQ, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
     if (rc != 0) return vg_fail(VG_ERR_HIP, "%s: merge launch failed: %s", f.who, hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipGetLastError());
@@ -86,13 +86,13 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
                               uint32_t *out_labels, const VgMemberForm *member) {
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
     const int slice = std::min(nq_pad, VG_FUSED_SLICE);
-    const bool qlab = f.single.labeled && !f.single.labelset;          // a label per query goes up with the queries
+    const bool qlab = f.rows == VG_QROWS_LABEL, members = f.rows == VG_QROWS_MEMBER, grouped = f.single.result.with_labels();   // qlab: a label per query goes up with the queries
     // (a membership form: the table of every membership group of VG_MEMBER_GROUP queries - its DISTINCT conditions, equal ones are
     //  neighbours - goes up once, in front of everything; the form packs it (VgMemberForm.pack_group).  A pad query is in no mask)
     struct MemberGroup { size_t at; int nd; size_t total; };
     std::vector<MemberGroup> mgroups;
     std::vector<uint32_t> mdata;
-    if (f.single.labelset) {
+    if (members) {
         for (int g0 = 0; g0 < nq; g0 += VG_MEMBER_GROUP) {
             MemberGroup mg{mdata.size(), 0, 0};
             int rcp = member->pack_group(member->ctx, f.who, g0, std::min(nq, g0 + VG_MEMBER_GROUP), &mdata, &mg.nd, &mg.total);
@@ -107,7 +107,7 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
     const size_t fl_off = (size_t)slice * c->stride;
     const size_t lb_off = fl_off + (f.single.after ? (size_t)slice * sizeof(uint64_t) : 0);
     // (a grouped form: a query's 64 keys are followed by their 64 labels, so its pitch in d_bkeys is VG_KEYS_BYTES)
-    const size_t kpitch = f.single.grouped ? VG_KEYS_BYTES / sizeof(uint64_t) : 64;
+    const size_t kpitch = grouped ? VG_KEYS_BYTES / sizeof(uint64_t) : 64;
     const size_t qbytes = lb_off + (qlab ? (size_t)slice * sizeof(uint32_t) : 0), keybytes = (size_t)nq_pad * kpitch * sizeof(uint64_t);
     if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
                                 HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
@@ -123,7 +123,7 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
     std::vector<uint32_t> hl(qlab ? (size_t)nq_pad : 0, VG_LABEL_NONE);
     if (qlab) for (int i = 0; i < nq; ++i) hl[(size_t)i] = qlabels[i];
     int rc = VG_OK;
-    if (f.single.labelset) {                                          // (mdata, like hq, stays where it is until the wait)
+    if (members) {                                                    // (mdata, like hq, stays where it is until the wait)
         hipError_t e = hipMemcpyAsync(c->d_lset, mdata.data(), mdata.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) rc = vg_fail(VG_ERR_HIP, "%s: label-set upload failed: %s", f.who, hipGetErrorString(e));
     }
@@ -137,7 +137,7 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
         if (e != hipSuccess) { rc = vg_fail(VG_ERR_HIP, "%s: query upload failed: %s", f.who, hipGetErrorString(e)); break; }
         for (int g = 0; g < nqs && rc == VG_OK; g += NQ) {
             // (a label-set form: the first pass of a membership group is preceded by the group's pre-pass; a slice is whole groups)
-            if (f.single.labelset && (q0 + g) % VG_MEMBER_GROUP == 0) {
+            if (members && (q0 + g) % VG_MEMBER_GROUP == 0) {
                 const MemberGroup &mg = mgroups[(size_t)((q0 + g) / VG_MEMBER_GROUP)];
                 if ((rc = member->member_enqueue(c, member->ctx, mg.at, mg.nd, mg.total)) != VG_OK) break;
             }
@@ -160,7 +160,7 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
             const uint64_t key = keys[(size_t)i * kpitch + j];
             if (key == VG_KEY_EMPTY) break;
             out_keys[(size_t)i * k + cnt] = key;
-            if (f.single.grouped) out_labels[(size_t)i * k + cnt] = reinterpret_cast<const uint32_t *>(&keys[(size_t)i * kpitch + 64])[j];
+            if (grouped) out_labels[(size_t)i * k + cnt] = reinterpret_cast<const uint32_t *>(&keys[(size_t)i * kpitch + 64])[j];
             ++cnt;
         }
         out_counts[i] = cnt;
@@ -173,23 +173,21 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
 // winners' labels, filled by a grouped form only.
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                        uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member) {
-    if (!c || !queries || !out_counts || (f.single.after && !floors) || (f.single.labeled && !f.single.labelset && !qlabels) ||
-        (f.single.labelset && !member)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
+    const bool grouped = f.single.result.with_labels();
+    if (!c || !queries || !out_counts || (f.single.after && !floors) || (f.rows == VG_QROWS_LABEL && !qlabels) ||
+        (f.rows == VG_QROWS_MEMBER && !member)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", f.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.per_label > 0 ? "capped" : f.single.grouped ? "grouped" : f.single.labeled ? "labeled" : f.single.masked ? "masked" : "paged");
-    if (!out_keys || (f.single.grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.single.noun);
+    if (!out_keys || (grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    if (f.single.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
-    if (f.single.valued && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
-    if (f.single.labeled && !f.single.valued) {              // (a valued form needs labels or values, as its caller says and checked)
-        if (!c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
-        for (int i = 0; i < nq && !f.single.labelset; ++i)
-            if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", f.who, i);
-    }
-    if (f.single.grouped && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
-    if ((f.single.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
+    if (f.rows == VG_QROWS_MASK && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (f.single.needs_values && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
+    if (f.single.needs_labels && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+    for (int i = 0; i < nq && f.rows == VG_QROWS_LABEL; ++i)
+        if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", f.who, i);
+    if ((f.rows == VG_QROWS_MASK && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     HIP_TRY(hipSetDevice(c->device));
     VgShape s{};
     scan_fn_t fn = nullptr;
@@ -198,19 +196,19 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
         const size_t row_bytes = (size_t)c->dim * c->es;
         for (int i = 0; i < nq; ++i) {
             // (a labeled form: the bitmap of a label is built once and serves the run of queries that share it)
-            if (f.single.labeled && !f.single.labelset && (i == 0 || qlabels[i] != qlabels[i - 1])) {
-                int rcb = vg_label_bits_enqueue(c, qlabels[i]);
+            if (f.rows == VG_QROWS_LABEL && (i == 0 || qlabels[i] != qlabels[i - 1])) {
+                int rcb = vg_pred_bits_enqueue(c, vg_pred_label(qlabels[i]));
                 if (rcb != VG_OK) return rcb;
             }
             // (a membership form: the same per run of equal conditions; a condition that allows no row at all - no launch, count 0)
-            if (f.single.labelset) {
+            if (f.rows == VG_QROWS_MEMBER) {
                 bool skip = false;
                 int rcb = member->bits_enqueue(c, member->ctx, i, &skip);
                 if (rcb != VG_OK) return rcb;
                 if (skip) continue;
             }
             int rc = vg_fused_run(c, f.single, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, floors ? floors[i] : 0ull,
-                                  out_keys + (size_t)i * k, &out_counts[i], f.single.grouped ? out_labels + (size_t)i * k : nullptr);
+                                  out_keys + (size_t)i * k, &out_counts[i], grouped ? out_labels + (size_t)i * k : nullptr);
             if (rc != VG_OK) return rc;
         }
         return VG_OK;
@@ -220,17 +218,15 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
 
 extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
                                               int *out_counts) {
-    const VgFusedBatchForm form = {"vg_scan_topk_batch_masked", vg_pick_multi<MultiFamily<VG_MQ_MASKED>>, {"vg_scan_topk_masked", vg_pick_scan_masked, true, false}};
+    const VgFusedBatchForm form = {"vg_scan_topk_batch_masked", vg_pick_multi<MultiFamily<VG_MQ_MASKED>>, VG_QROWS_MASK,
+                                   vg_fused_form("vg_scan_topk_masked", "masked", vg_pick_scan_masked, VG_ROWS_MASK)};
     return vg_fused_batch_run(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts);
 }
 
 extern "C" int vg_scan_topk_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
                                          double *out_dist, int *out_counts) {
-    if (!c || !queries || !out_counts) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: NULL argument");
-    if (nq >= 1 && k >= 1 && k <= VG_MAX_FUSED_K && (!out_rowids || !out_dist)) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_masked: NULL output");
-    std::vector<uint64_t> keys((nq >= 1 && k >= 1 && k <= VG_MAX_FUSED_K) ? (size_t)nq * k : 1);
-    int rc = vg_scan_topk_batch_masked_keys(c, metric, queries, nq, k, keys.data(), out_counts);
-    if (rc != VG_OK) return rc;
-    vg_keys_to_rows(c, keys.data(), nullptr, nq, k, out_counts, out_rowids, out_dist, nullptr);
-    return VG_OK;
+    return vg_batch_rows_from_keys(c, "vg_scan_topk_batch_masked", !c || !queries || !out_counts, nq, k, k >= 1 && k <= VG_MAX_FUSED_K, false,
+                                   out_rowids, out_dist, nullptr, out_counts, [&](uint64_t *keys, uint32_t *) {
+        return vg_scan_topk_batch_masked_keys(c, metric, queries, nq, k, keys, out_counts);
+    });
 }

@@ -11,13 +11,11 @@
 //     dwords a condition; query mask: bit j set when query j of the group asks under the condition;
 //   * vg_value_member_kernel runs once per group, in stream order in front of the group's passes: it reads values[row] once - and
 //     labels[row] when a condition of the group names a label - and writes ONE dword per row into d_member.
-// Shapes without a multi-query form (f16 / bf16, long rows): one single valued scan per query (vg_scan_valued.hip) in that same
+// Shapes without a multi-query form (f16 / bf16, long rows): one single valued scan per query (vg_rowpred.hip) in that same
 // order, the bitmap rebuilt only where the condition changes.
 #include "vg_internal.h"
 
 #include "vg_device.h"
-
-#include <numeric>
 
 #define VG_VALUE_GROUP 32               // queries per membership dword: at most that many distinct conditions in a table
 #define VG_VALUE_COND_DWORDS 8
@@ -93,7 +91,7 @@ static int valued_bits_step(vg_corpus *c, const void *ctx, int i, bool *skip) {
     const VgValuedBatch *v = (const VgValuedBatch *)ctx;
     if (v->los[i] > v->his[i]) { *skip = true; return VG_OK; }
     if (i > 0 && same_cond(v, i, i - 1)) return VG_OK;       // (the query in front was not skipped: its interval is this one)
-    return vg_value_bits_enqueue(c, v->los[i], v->his[i], v->labels ? 1 : 0, v->labels ? v->labels[i] : 0u);
+    return vg_pred_bits_enqueue(c, v->labels ? vg_pred_value_labeled(v->los[i], v->his[i], v->labels[i]) : vg_pred_value(v->los[i], v->his[i]));
 }
 
 extern "C" int vg_batch_valued_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
@@ -102,8 +100,9 @@ extern "C" int vg_batch_valued_plan(const vg_corpus *c, int metric, int *out_que
 
 extern "C" int vg_scan_topk_batch_valued_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, const int64_t *los, const int64_t *his,
                                               const uint32_t *query_labels, uint64_t *out_keys, int *out_counts) {
-    const VgFusedBatchForm form = {"vg_scan_topk_batch_valued", vg_pick_multi_labelset,
-                                   {"vg_scan_topk_valued", vg_pick_scan_masked, false, false, true, false, 0, true, true}};
+    // (the handle must hold values; labels only where the queries name one, which is checked below)
+    const VgFusedBatchForm form = {"vg_scan_topk_batch_valued", vg_pick_multi_labelset, VG_QROWS_MEMBER,
+                                   vg_pred_form("vg_scan_topk_valued", vg_pred_value(0, 0), vg_result_plain())};
     if (!c || !queries || !out_counts || !los || !his) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", form.who);
     if (nq < 1) return vg_fail(VG_ERR_INVALID, "%s: nq must be at least 1", form.who);
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
@@ -118,47 +117,30 @@ extern "C" int vg_scan_topk_batch_valued_keys(vg_corpus *c, int metric, const vo
             if (query_labels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", form.who, i);
     }
     // the queries in (label, lo, hi) order (stable: equal conditions keep caller order)
-    std::vector<int> order((size_t)nq);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+    const std::vector<int> order = vg_stable_order(nq, [&](int x, int y) {
         if (query_labels && query_labels[x] != query_labels[y]) return query_labels[x] < query_labels[y];
         if (los[x] != los[y]) return los[x] < los[y];
         return his[x] < his[y];
     });
-    const size_t row_bytes = (size_t)c->dim * c->es;
-    std::vector<uint8_t> sq((size_t)nq * row_bytes);
     std::vector<int64_t> slo((size_t)nq), shi((size_t)nq);
     std::vector<uint32_t> slab(query_labels ? (size_t)nq : 0);
     for (int i = 0; i < nq; ++i) {
         const int src = order[(size_t)i];
-        memcpy(sq.data() + (size_t)i * row_bytes, (const uint8_t *)queries + (size_t)src * row_bytes, row_bytes);
         slo[(size_t)i] = los[src];
         shi[(size_t)i] = his[src];
         if (query_labels) slab[(size_t)i] = query_labels[src];
     }
     const VgValuedBatch vb = {slo.data(), shi.data(), query_labels ? slab.data() : nullptr};
     const VgMemberForm member = {&vb, valued_pack_group, valued_member_step, valued_bits_step};
-    std::vector<uint64_t> skeys((size_t)nq * k);
-    std::vector<int> scounts((size_t)nq, 0);
-    int rc = vg_fused_batch_run(c, form, metric, sq.data(), nq, k, nullptr, skeys.data(), scounts.data(), nullptr, nullptr, &member);
-    if (rc != VG_OK) return rc;
-    for (int i = 0; i < nq; ++i) {
-        const int dst = order[(size_t)i];
-        out_counts[dst] = scounts[(size_t)i];
-        memcpy(out_keys + (size_t)dst * k, skeys.data() + (size_t)i * k, (size_t)scounts[(size_t)i] * sizeof(uint64_t));
-    }
-    return VG_OK;
+    return vg_ordered_batch(c, queries, nq, k, order, out_keys, out_counts, [&](const void *sq, uint64_t *skeys, int *scounts) {
+        return vg_fused_batch_run(c, form, metric, sq, nq, k, nullptr, skeys, scounts, nullptr, nullptr, &member);
+    });
 }
 
 extern "C" int vg_scan_topk_batch_valued(vg_corpus *c, int metric, const void *queries, int nq, int k, const int64_t *los, const int64_t *his,
                                          const uint32_t *query_labels, int64_t *out_rowids, double *out_dist, int *out_counts) {
-    if (!c || !queries || !out_counts || !los || !his) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_valued: NULL argument");
-    const bool k_ok = k >= 1 && k <= VG_MAX_FUSED_K;
-    if (nq >= 1) for (int i = 0; i < nq; ++i) out_counts[i] = 0;
-    if (nq >= 1 && k_ok && (!out_rowids || !out_dist)) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_valued: NULL output");
-    std::vector<uint64_t> keys((nq >= 1 && k_ok) ? (size_t)nq * k : 1);
-    int rc = vg_scan_topk_batch_valued_keys(c, metric, queries, nq, k, los, his, query_labels, keys.data(), out_counts);
-    if (rc != VG_OK) return rc;
-    vg_keys_to_rows(c, keys.data(), nullptr, nq, k, out_counts, out_rowids, out_dist, nullptr);
-    return VG_OK;
+    return vg_batch_rows_from_keys(c, "vg_scan_topk_batch_valued", !c || !queries || !out_counts || !los || !his, nq, k,
+                                   k >= 1 && k <= VG_MAX_FUSED_K, false, out_rowids, out_dist, nullptr, out_counts, [&](uint64_t *keys, uint32_t *) {
+        return vg_scan_topk_batch_valued_keys(c, metric, queries, nq, k, los, his, query_labels, keys, out_counts);
+    });
 }

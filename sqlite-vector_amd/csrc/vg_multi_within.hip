@@ -19,7 +19,7 @@
 //
 // The labeled batch (vg_scan_within_batch_labeled: each query its own label and its own radius) is the same host code once more: its
 // kernels are the VG_MQ_LABELED | VG_MQ_WITHIN instances, held by vg_multi_within_labeled.hip, its launches set ScanArgs.labels and
-// every query's label travels in its descriptor, its fallback is nq single labeled range scans (vg_scan_within_labeled.hip).  What is
+// every query's label travels in its descriptor, its fallback is nq single labeled range scans (vg_rowpred.hip).  What is
 // its own is the entry point's: the queries are ordered by label (stable) before they are cut into passes, as in vg_multi_labeled.hip
 // - a pass' queries then share as few distinct labels as possible, which is what lets a pass skip the batches of rows that carry none
 // of them - and the held results are put back at the caller's indices.
@@ -28,11 +28,9 @@
 #include "vg_scan_multi.h"
 #include "vg_pick.h"
 
-#include <numeric>
-
-// what differs between the unmasked, the masked and the labeled batch: whose name errors carry, whether the launches read the handle's
-// mask, whether they read its labels (then every query names one)
-struct WbForm { const char *who; bool masked; bool labeled; };
+// what differs between the unmasked, the masked and the labeled batch: whose name errors carry, and whether the launches read the
+// handle's mask or its labels (then every query names one).  No membership form
+struct WbForm { const char *who; VgBatchRows rows; };
 
 // (queries per pass, launch shape, kernel) of the multi-query range scan, unmasked, masked or labeled; 0 queries per pass: the fallback
 // serves the shape.  Every instance of the three tables compiles without scratch or spills: the masked and
@@ -41,9 +39,9 @@ static int mw_plan(const vg_corpus *c, int metric, const WbForm &form, VgShape *
     const int NQ = vg_multi_plan(c, metric, s);
     if (NQ == 0) return 0;
     const int acc = vg_metric_to_acc(metric);
-    scan_fn_t f = form.labeled  ? vg_pick_multi_within_labeled(c->vtype, acc, s->U, NQ)
-                  : form.masked ? vg_pick_multi_within_masked(c->vtype, acc, s->U, NQ)
-                                : vg_pick_multi<MultiFamily<VG_MQ_WITHIN>>(c->vtype, acc, s->U, NQ);
+    scan_fn_t f = form.rows == VG_QROWS_LABEL  ? vg_pick_multi_within_labeled(c->vtype, acc, s->U, NQ)
+                  : form.rows == VG_QROWS_MASK ? vg_pick_multi_within_masked(c->vtype, acc, s->U, NQ)
+                                               : vg_pick_multi<MultiFamily<VG_MQ_WITHIN>>(c->vtype, acc, s->U, NQ);
     if (fn) *fn = f;
     return f ? NQ : 0;
 }
@@ -60,13 +58,13 @@ static int within_batch_plan(const vg_corpus *c, int metric, const WbForm &form,
     return VG_OK;
 }
 extern "C" int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
-    return within_batch_plan(c, metric, WbForm{"vg_within_batch_plan", false, false}, out_queries_per_pass, out_lpr, out_u);
+    return within_batch_plan(c, metric, WbForm{"vg_within_batch_plan", VG_QROWS_ALL}, out_queries_per_pass, out_lpr, out_u);
 }
 extern "C" int vg_within_batch_masked_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
-    return within_batch_plan(c, metric, WbForm{"vg_within_batch_masked_plan", true, false}, out_queries_per_pass, out_lpr, out_u);
+    return within_batch_plan(c, metric, WbForm{"vg_within_batch_masked_plan", VG_QROWS_MASK}, out_queries_per_pass, out_lpr, out_u);
 }
 extern "C" int vg_within_batch_labeled_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u) {
-    return within_batch_plan(c, metric, WbForm{"vg_within_batch_labeled_plan", false, true}, out_queries_per_pass, out_lpr, out_u);
+    return within_batch_plan(c, metric, WbForm{"vg_within_batch_labeled_plan", VG_QROWS_LABEL}, out_queries_per_pass, out_lpr, out_u);
 }
 
 // queries go up in slices of this many (a multiple of every queries-per-pass): staging and key regions do not grow with the batch
@@ -94,8 +92,8 @@ static int ensure_dev(unsigned long long **p, size_t *have, size_t need) {
 static int launch_multi_within(vg_corpus *c, const WbForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_block) {
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);      // the multi-query scan's launch shape
     ScanArgs a = vg_scan_args(c, metric, vg_metric_to_acc(metric), s, dev_block, 0);
-    if (f.masked) a.mask = c->d_mask;
-    if (f.labeled) a.labels = c->d_labels;                     // (the queries' labels are in their descriptors)
+    if (f.rows == VG_QROWS_MASK) a.mask = c->d_mask;
+    if (f.rows == VG_QROWS_LABEL) a.labels = c->d_labels;                     // (the queries' labels are in their descriptors)
     a.store_lds_off = (int)(((size_t)NQ * c->nch * 16 + 255) / 256 * 256);     // the key queues behind the staged queries
     const size_t smem = (size_t)a.store_lds_off + (size_t)NQ * VG_WITHIN_LDS_BYTES;
     hipEvent_t *evs = vg_prof_slot(c, 0);                      // one slot of the profiling ring per pass
@@ -148,7 +146,7 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
             d->out = c->d_wb + (long long)j * pitch;
             d->cap = real ? (unsigned long long)cap : 0ull;
             d->r = real ? vg_within_radius(radii[q0 + j]) : -INFINITY;
-            d->label = (real && f.labeled) ? qlabels[q0 + j] : VG_LABEL_NONE;
+            d->label = (real && f.rows == VG_QROWS_LABEL) ? qlabels[q0 + j] : VG_LABEL_NONE;
         }
         HIP_TRY(hipMemcpyAsync(d_stage, block_of(q0), (size_t)(nqs / NQ) * block_bytes, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(vg_wb_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, c->d_wb, pitch, nqs, (unsigned long long *)nullptr);
@@ -211,7 +209,8 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
 static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *queries, int nq, const double *radii, const uint32_t *qlabels,
                         int64_t limit, int64_t *out_matches, int64_t *out_held) {
     for (int i = 0; i < nq; ++i) { if (out_matches) out_matches[i] = 0; if (out_held) out_held[i] = 0; }      // (every error leaves the counts zeroed)
-    if (!c || !queries || !radii || (f.labeled && !qlabels)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
+    const bool masked = f.rows == VG_QROWS_MASK, labeled = f.rows == VG_QROWS_LABEL;
+    if (!c || !queries || !radii || (labeled && !qlabels)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     c->wb_keys.clear();
     c->wb_matches.clear();
     c->wb_launches = 0;
@@ -219,15 +218,15 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     for (int i = 0; i < nq; ++i)
         if (radii[i] != radii[i]) return vg_fail(VG_ERR_INVALID, "%s: radius %d is NaN", f.who, i);
-    if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
-    if (f.labeled) {
+    if (masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (labeled) {
         if (!c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
         for (int i = 0; i < nq; ++i)
             if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: a query's label is VG_LABEL_NONE, which names no row", f.who);
     }
     c->wb_keys.resize((size_t)nq);
     c->wb_matches.assign((size_t)nq, 0);
-    if (c->n_rows == 0 || (f.masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
+    if (c->n_rows == 0 || (masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
     HIP_TRY(hipSetDevice(c->device));
     VgShape s{};
     scan_fn_t fn = nullptr;
@@ -243,9 +242,9 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
         for (int i = 0; i < nq && rc == VG_OK; ++i) {
             int64_t m = 0, h = 0;
             const void *q = (const uint8_t *)queries + (size_t)i * row_bytes;
-            rc = f.labeled  ? vg_scan_within_labeled(c, metric, q, radii[i], limit, qlabels[i], &m, &h)
-                 : f.masked ? vg_scan_within_masked(c, metric, q, radii[i], limit, &m, &h)
-                            : vg_scan_within(c, metric, q, radii[i], limit, &m, &h);
+            rc = labeled  ? vg_scan_within_labeled(c, metric, q, radii[i], limit, qlabels[i], &m, &h)
+                 : masked ? vg_scan_within_masked(c, metric, q, radii[i], limit, &m, &h)
+                          : vg_scan_within(c, metric, q, radii[i], limit, &m, &h);
             if (rc != VG_OK) break;
             c->wb_keys[(size_t)i] = c->within_keys;
             c->wb_matches[(size_t)i] = m;
@@ -267,31 +266,27 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
 
 extern "C" int vg_scan_within_batch(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                     int64_t *out_matches, int64_t *out_held) {
-    return within_batch(c, WbForm{"vg_scan_within_batch", false, false}, metric, queries, nq, radii, nullptr, limit, out_matches, out_held);
+    return within_batch(c, WbForm{"vg_scan_within_batch", VG_QROWS_ALL}, metric, queries, nq, radii, nullptr, limit, out_matches, out_held);
 }
 
 extern "C" int vg_scan_within_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, const double *radii, int64_t limit,
                                            int64_t *out_matches, int64_t *out_held) {
-    return within_batch(c, WbForm{"vg_scan_within_batch_masked", true, false}, metric, queries, nq, radii, nullptr, limit, out_matches, out_held);
+    return within_batch(c, WbForm{"vg_scan_within_batch_masked", VG_QROWS_MASK}, metric, queries, nq, radii, nullptr, limit, out_matches, out_held);
 }
 
 extern "C" int vg_scan_within_batch_labeled(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *query_labels,
                                             const double *radii, int64_t limit, int64_t *out_matches, int64_t *out_held) {
-    const WbForm form = {"vg_scan_within_batch_labeled", false, true};
+    const WbForm form = {"vg_scan_within_batch_labeled", VG_QROWS_LABEL};
     if (nq < 1 || !c || !queries || !radii || !query_labels)           // (nothing to order: the shared routine zeroes the counts and refuses)
         return within_batch(c, form, metric, queries, nq, radii, query_labels, limit, out_matches, out_held);
     // queries in label order (stable: equal labels keep caller order), their radii with them; everything else - argument checks
     // included - is the shared routine's
-    std::vector<int> order((size_t)nq);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return query_labels[x] < query_labels[y]; });
-    const size_t row_bytes = (size_t)c->dim * c->es;
-    std::vector<uint8_t> sq((size_t)nq * row_bytes);
+    const std::vector<int> order = vg_stable_order(nq, [&](int x, int y) { return query_labels[x] < query_labels[y]; });
+    const std::vector<uint8_t> sq = vg_permute_queries(c, queries, order);
     std::vector<uint32_t> sl((size_t)nq);
     std::vector<double> sr((size_t)nq);
     for (int i = 0; i < nq; ++i) {
         const size_t src = (size_t)order[(size_t)i];
-        memcpy(sq.data() + (size_t)i * row_bytes, (const uint8_t *)queries + src * row_bytes, row_bytes);
         sl[(size_t)i] = query_labels[src];
         sr[(size_t)i] = radii[src];
     }

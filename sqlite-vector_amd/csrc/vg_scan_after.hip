@@ -62,8 +62,10 @@ static int cursor_floor(const vg_corpus *c, const char *who, double after_dist, 
 // ------------------------------------------------------------------------------------------------ the scans
 
 static VgFusedForm after_form(bool masked) {
-    if (masked) return VgFusedForm{"vg_scan_topk_after_masked", vg_pick_scan_after_masked, true, true};
-    return VgFusedForm{"vg_scan_topk_after", vg_pick_scan_after, false, true};
+    VgFusedForm f = masked ? vg_fused_form("vg_scan_topk_after_masked", "masked", vg_pick_scan_after_masked, VG_ROWS_MASK)
+                           : vg_fused_form("vg_scan_topk_after", "paged", vg_pick_scan_after, VG_ROWS_ALL);
+    f.after = true;
+    return f;
 }
 
 int vg_after_floor_run(vg_corpus *c, bool masked, int metric, const void *query, int k, uint64_t floor, uint64_t *out_keys, int *out_count) {

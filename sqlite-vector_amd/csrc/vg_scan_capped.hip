@@ -72,8 +72,8 @@ int vg_launch_merge_capped(const uint64_t *dev_cand, int nlists, int k, int per_
 // ------------------------------------------------------------------------------------------------ the scans
 
 static VgFusedForm capped_form(bool masked, int per_label) {
-    if (masked) return VgFusedForm{"vg_scan_topk_capped_masked", vg_pick_scan_capped_masked, true, false, false, true, per_label};
-    return VgFusedForm{"vg_scan_topk_capped", vg_pick_scan_capped, false, false, false, true, per_label};
+    if (masked) return vg_fused_form("vg_scan_topk_capped_masked", "capped", vg_pick_scan_capped_masked, VG_ROWS_MASK, vg_result_capped(per_label));
+    return vg_fused_form("vg_scan_topk_capped", "capped", vg_pick_scan_capped, VG_ROWS_ALL, vg_result_capped(per_label));
 }
 
 static int capped_keys(vg_corpus *c, bool masked, int metric, const void *query, int k, int per_label, uint64_t *out_keys, uint32_t *out_labels,

@@ -72,8 +72,8 @@ int vg_launch_merge_grouped(const uint64_t *dev_cand, int nlists, int k, const u
 // ------------------------------------------------------------------------------------------------ the scans
 
 static VgFusedForm grouped_form(bool masked) {
-    if (masked) return VgFusedForm{"vg_scan_topk_grouped_masked", vg_pick_scan_grouped_masked, true, false, false, true};
-    return VgFusedForm{"vg_scan_topk_grouped", vg_pick_scan_grouped, false, false, false, true};
+    if (masked) return vg_fused_form("vg_scan_topk_grouped_masked", "grouped", vg_pick_scan_grouped_masked, VG_ROWS_MASK, vg_result_grouped());
+    return vg_fused_form("vg_scan_topk_grouped", "grouped", vg_pick_scan_grouped, VG_ROWS_ALL, vg_result_grouped());
 }
 
 static int grouped_rows(vg_corpus *c, bool masked, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,

@@ -82,11 +82,10 @@ extern "C" int64_t vg_corpus_mask_count(const vg_corpus *c) { return c ? c->mask
 // ------------------------------------------------------------------------------------------------ the scan
 
 // One routine for every fused top-k variant that differs from the masked scan only in its kernel table and a ScanArgs field (3.11 of
-// DESIGN.md): VgFusedForm names the table, whether ScanArgs.mask is set (and a mask required) and whether ScanArgs.floor is (the paged
-// scans of vg_scan_after.hip; the floor key travels in the 8 bytes behind the query, one upload) and whether the scan is grouped (the
-// grouped scans of vg_scan_grouped.hip: ScanArgs.labels, the label-deduping merge, labels in the result) or capped (the capped scans
-// of vg_scan_capped.hip: a grouped form whose per_label is set - the cap in ScanArgs.within_cap, which no top-k kernel reads, and the
-// capped merge).
+// DESIGN.md): VgFusedForm names the table, where ScanArgs.mask comes from (the user's mask, then required, or a row predicate's
+// bitmap), whether ScanArgs.floor is set (the paged scans of vg_scan_after.hip; the floor key travels in the 8 bytes behind the query,
+// one upload) and the result: grouped (vg_scan_grouped.hip: ScanArgs.labels, the label-deduping merge, labels in the result) or capped
+// (vg_scan_capped.hip: the grouped path with the cap in ScanArgs.within_cap, which no top-k kernel reads, and the capped merge).
 // the form's kernel + the plain scan's merge; the k winners land in the pinned c->h_keys (copied behind the merge)
 static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     int acc = vg_metric_to_acc(metric);
@@ -100,11 +99,12 @@ static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     const long long blocks = vg_plain_scan_blocks(c, c->n_rows, s);      // the launch shape of the plain top-k scan
     ScanArgs a = vg_scan_args(c, metric, acc, s, c->d_query, k);
     a.cand = c->d_cand;
-    if (f.masked) a.mask = c->d_mask;
-    if (f.labeled) a.mask = c->d_label_bits;                 // (the bitmap of one label, built on this stream in front of the scan)
+    const bool grouped = f.result.with_labels();
+    if (f.rows == VG_ROWS_MASK) a.mask = c->d_mask;
+    if (f.rows == VG_ROWS_BITMAP) a.mask = c->d_label_bits;  // (a row predicate's bitmap, built on this stream in front of the scan)
     if (f.after) a.floor = reinterpret_cast<const uint64_t *>(c->d_query + c->stride);
-    if (f.grouped) a.labels = c->d_labels;
-    const int cap = std::min(f.per_label, k);               // (capped forms: more than k of one label cannot be returned)
+    if (grouped) a.labels = c->d_labels;
+    const int cap = f.result.kind == VG_RESULT_CAPPED ? std::min(f.result.per_label, k) : 0;   // (more than k of one label cannot be returned)
     if (cap > 0) a.within_cap = (unsigned long long)cap;
     const size_t smem = std::max<size_t>(vg_query_lds_bytes(c, s), (size_t)VG_PUBLISH_LDS_BYTES);
 
@@ -113,12 +113,12 @@ static int launch_fused(vg_corpus *c, const VgFusedForm &f, int metric, int k) {
     if ((rc = vg_launch_scan_kernel(fn, blocks, smem, c->stream, a)) != VG_OK) return rc;
     if (evs) hipEventRecord(evs[2], c->stream);
     int rcm = cap > 0   ? vg_launch_merge_capped(c->d_cand, (int)blocks, k, cap, c->d_labels, c->d_keys, c->stream)
-              : f.grouped ? vg_launch_merge_grouped(c->d_cand, (int)blocks, k, c->d_labels, c->d_keys, c->stream)
+              : grouped ? vg_launch_merge_grouped(c->d_cand, (int)blocks, k, c->d_labels, c->d_keys, c->stream)
                         : vg_launch_merge_one(c->d_cand, (int)blocks, k, c->d_keys, c->stream);
     if (evs) hipEventRecord(evs[3], c->stream);
     if (rcm != 0) return vg_fail(VG_ERR_HIP, "%s: merge launch failed: %s", f.who, hipGetErrorString((hipError_t)rcm));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_keys, c->d_keys, f.grouped ? VG_KEYS_BYTES : VG_WAVE * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->h_keys, c->d_keys, grouped ? VG_KEYS_BYTES : VG_WAVE * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return VG_OK;
 }
@@ -130,13 +130,13 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
     if (!c || !query || !out_count) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
     *out_count = 0;
     if (k < 1) return vg_fail(VG_ERR_INVALID, "%s: k must be at least 1", f.who);
-    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.per_label > 0 ? "capped" : f.grouped ? "grouped" : f.labeled ? "labeled" : f.masked ? "masked" : "paged");
-    if (!out_keys || (f.grouped && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
+    if (k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "%s: k must be in 1..%d (%s scans use the fused list only)", f.who, VG_MAX_FUSED_K, f.noun);
+    if (!out_keys || (f.result.with_labels() && !out_labels)) return vg_fail(VG_ERR_INVALID, "%s: NULL output", f.who);
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
-    if (f.valued && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
-    if (((f.labeled && !f.valued) || f.grouped) && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
-    if ((f.masked && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
+    if (f.rows == VG_ROWS_MASK && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (f.needs_values && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
+    if (f.needs_labels && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+    if ((f.rows == VG_ROWS_MASK && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     if (f.after && floor == VG_EMPTY_KEY) return VG_OK;      // nothing is behind the cursor: no launch
     HIP_TRY(hipSetDevice(c->device));
     c->enqueued = false;                                    // (the pinned key buffer is this scan's landing zone now)
@@ -151,7 +151,7 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
     const uint32_t *h_labels = reinterpret_cast<const uint32_t *>(c->h_keys + VG_WAVE);      // (grouped forms: the labels behind the keys)
     while (cnt < k && c->h_keys[cnt] != VG_EMPTY_KEY) {
         out_keys[cnt] = c->h_keys[cnt];
-        if (f.grouped) out_labels[cnt] = h_labels[cnt];
+        if (f.result.with_labels()) out_labels[cnt] = h_labels[cnt];
         ++cnt;
     }
     *out_count = cnt;
@@ -162,7 +162,7 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
 scan_fn_t vg_pick_scan_masked(int vtype, int acc, int U, bool long_rows) { return vg_pick_scan<ScanFamily<VG_SQ_MASKED, true, true>>(vtype, acc, U, long_rows); }
 
 extern "C" int vg_scan_topk_masked_keys(vg_corpus *c, int metric, const void *query, int k, uint64_t *out_keys, int *out_count) {
-    const VgFusedForm form = {"vg_scan_topk_masked", vg_pick_scan_masked, true, false};
+    const VgFusedForm form = vg_fused_form("vg_scan_topk_masked", "masked", vg_pick_scan_masked, VG_ROWS_MASK);
     return vg_fused_run(c, form, metric, query, k, 0ull, out_keys, out_count);
 }
 

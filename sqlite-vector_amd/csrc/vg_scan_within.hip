@@ -14,7 +14,7 @@
 // result - is here ONCE and serves the batch form (vg_multi_within.hip) too; each form keeps its own held result on the handle.
 // So is the single scan itself (vg_within_run): the masked range scan (vg_scan_within_masked.hip) is this code with its own kernel
 // table and ScanArgs.mask set, and leaves its result where vg_scan_within leaves its own; the labeled range scans
-// (vg_scan_within_labeled.hip) are the masked one over a bitmap of their own making.
+// (vg_rowpred.hip) are the masked one over a bitmap of their own making.
 #include "vg_internal.h"
 
 #include "vg_scan.h"
@@ -108,8 +108,8 @@ static int launch_within(vg_corpus *c, const VgWithinForm &f, int metric, float 
     a.emit = c->d_within;
     a.within_r = r;
     a.within_cap = (unsigned long long)cap;
-    if (f.masked) a.mask = c->d_mask;
-    if (f.labeled) a.mask = c->d_label_bits;                 // (the bitmap of a label or a label set, built on this stream in front of the scan)
+    if (f.rows == VG_ROWS_MASK) a.mask = c->d_mask;
+    if (f.rows == VG_ROWS_BITMAP) a.mask = c->d_label_bits;  // (a row predicate's bitmap, built on this stream in front of the scan)
     a.store_lds_off = (int)((vg_query_lds_bytes(c, s) + 255) / 256 * 256);     // the wavefronts' key queues behind the query
     const size_t smem = (size_t)a.store_lds_off + VG_WITHIN_LDS_BYTES;
 
@@ -133,21 +133,27 @@ static int ensure_within_buffer(vg_corpus *c, int64_t cap) {
     return VG_OK;
 }
 
-// a single range scan, unmasked, masked or labeled (VgWithinForm, vg_internal.h): argument checks, launch, the overflow protocol, the held result
-int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
-                  int64_t *out_held) {
+int vg_within_begin(vg_corpus *c, const char *who, int metric, const void *query, double radius, int64_t *out_matches, int64_t *out_held) {
     if (out_matches) *out_matches = 0;
     if (out_held) *out_held = 0;
-    if (!c || !query) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
+    if (!c || !query) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", who);
     c->within_keys.clear();
     c->within_matches = 0;
     c->within_launches = 0;
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    if (radius != radius) return vg_fail(VG_ERR_INVALID, "%s: the radius is NaN", f.who);
-    if (f.masked && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
-    if (f.valued && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
-    if (f.labeled && !f.valued && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
-    if (c->n_rows == 0 || (f.masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
+    if (radius != radius) return vg_fail(VG_ERR_INVALID, "%s: the radius is NaN", who);
+    return VG_OK;
+}
+
+// a single range scan of any form (VgWithinForm, vg_internal.h): argument checks, launch, the overflow protocol, the held result
+int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
+                  int64_t *out_held) {
+    int rcb = vg_within_begin(c, f.who, metric, query, radius, out_matches, out_held);
+    if (rcb != VG_OK) return rcb;
+    if (f.rows == VG_ROWS_MASK && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
+    if (f.needs_values && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
+    if (f.needs_labels && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+    if (c->n_rows == 0 || (f.rows == VG_ROWS_MASK && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
     HIP_TRY(hipSetDevice(c->device));
     c->enqueued = false;                                     // (the pinned key buffer is this scan's landing zone now)
     const float r = vg_within_radius(radius);
@@ -179,7 +185,7 @@ int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *q
 
 extern "C" int vg_scan_within(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                               int64_t *out_held) {
-    const VgWithinForm form = {"vg_scan_within", vg_pick_scan<ScanFamily<VG_SQ_WITHIN, true, true>>, false};
+    const VgWithinForm form = vg_within_form("vg_scan_within", vg_pick_scan<ScanFamily<VG_SQ_WITHIN, true, true>>, VG_ROWS_ALL);
     return vg_within_run(c, form, metric, query, radius, limit, out_matches, out_held);
 }
 

@@ -13,13 +13,13 @@
 #include "vg_scan.h"
 #include "vg_pick.h"
 
-// the kernel table as a plain function: the labeled range scans (vg_scan_within_labeled.hip) run these kernels over a label bitmap
+// the kernel table as a plain function: the range forms of the row predicates (vg_rowpred.hip) run these kernels over a label bitmap
 scan_fn_t vg_pick_scan_within_masked(int vtype, int acc, int U, bool long_rows) {
     return vg_pick_scan<ScanFamily<VG_SQ_WITHIN | VG_SQ_MASKED, true, true>>(vtype, acc, U, long_rows);
 }
 
 extern "C" int vg_scan_within_masked(vg_corpus *c, int metric, const void *query, double radius, int64_t limit, int64_t *out_matches,
                                      int64_t *out_held) {
-    const VgWithinForm form = {"vg_scan_within_masked", vg_pick_scan_within_masked, true};
+    const VgWithinForm form = vg_within_form("vg_scan_within_masked", vg_pick_scan_within_masked, VG_ROWS_MASK);
     return vg_within_run(c, form, metric, query, radius, limit, out_matches, out_held);
 }
