@@ -34,7 +34,19 @@ extern "C" {
 
 /* same numbering as the reference's enums, distance-cpu.h:36-58 */
 enum { VG_TYPE_F32 = 1, VG_TYPE_F16 = 2, VG_TYPE_BF16 = 3, VG_TYPE_U8 = 4, VG_TYPE_I8 = 5 };
-enum { VG_DIST_L2 = 1, VG_DIST_SQUARED_L2 = 2, VG_DIST_COSINE = 3, VG_DIST_DOT = 4, VG_DIST_L1 = 5 };
+enum { VG_DIST_L2 = 1, VG_DIST_SQUARED_L2 = 2, VG_DIST_COSINE = 3, VG_DIST_DOT = 4, VG_DIST_L1 = 5,
+       VG_DIST_HAMMING = 6 /* not a metric of the reference: see below */ };
+/* Hamming distance (VG_DIST_HAMMING): rows are bit vectors packed 8 dimensions to a byte, served for VG_TYPE_U8 corpora only - a row
+ * of `dim` bytes is 8 * dim bits and the query is `dim` bytes like every uint8 query.  The distance of a row is popcount(q XOR x)
+ * over its `dim` bytes, returned as a float: exact (8 * dim < 2^24 for every supported row length) and always finite; the zero
+ * padding of both sides contributes nothing.  Every entry point that takes a metric serves it - plain, masked, range (the radius
+ * compares against this float), paged, labeled, label-set, valued, grouped and capped scans, single and batch, one corpus or shards -
+ * with the order, counts, VG_KEY_EMPTY padding and rowid mapping of every other metric.  Over any other element type the call is
+ * refused with VG_ERR_UNSUPPORTED ("<entry point>: Hamming distance needs a uint8 corpus") behind the argument checks that return
+ * VG_ERR_INVALID and in front of any launch, counts and outputs zeroed as for the entry point's other refusals.  tie_order =
+ * reference (corpus, shard set, vg_slab_scan_begin) together with it is VG_ERR_UNSUPPORTED: the reference has no such metric and so
+ * no history-dependent order to reproduce.  The batch never takes the matrix cores and the single scan never the nibble filter:
+ * vg_batch_last_path() reports 5 (multi-query scan) or 6 (single scans). */
 enum { VG_QUANT_AUTO = 0, VG_QUANT_U8 = 1, VG_QUANT_S8 = 2 };
 
 enum {

@@ -24,6 +24,7 @@ EXT_PATH = os.path.join(HERE, "vector.so")         # must be named vector.* (ent
 # enums (same numbering as the reference, distance-cpu.h:36-58)
 F32, F16, BF16, U8, I8 = 1, 2, 3, 4, 5
 L2, SQUARED_L2, COSINE, DOT, L1 = 1, 2, 3, 4, 5
+HAMMING = 6                  # not a metric of the reference: differing bits of packed bit vectors, U8 corpora only (pack_bits)
 QUANT_U8, QUANT_S8 = 1, 2
 TIE_POSITION, TIE_REFERENCE = 0, 1
 KEY_EMPTY = 0xFFFFFFFFFFFFFFFF
@@ -335,6 +336,25 @@ def device_count():
 
 def backend_name():
     return lib().vg_backend_name().decode()
+
+
+def pack_bits(x):
+    """rows of bits for a U8 corpus scanned with HAMMING: a 2-D array of bools or numbers [n, d] -> uint8 [n, ceil(d / 8)].  A bit is 1
+    where the entry is true or > 0; the first dimension is the most significant bit of the first byte (np.packbits); tail bits are 0."""
+    x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError("pack_bits: a 2-D array is needed, got %d-D" % x.ndim)
+    bits = x if x.dtype == np.bool_ else x > 0
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="big"))
+
+
+def hamming_reference(rows_u8, q_u8):
+    """popcount(q XOR row) of every row on the host, float32 [n]: what a HAMMING scan returns as distances (spot checks, tests)"""
+    rows = np.asarray(rows_u8)
+    q = np.asarray(q_u8)
+    if rows.dtype != np.uint8 or q.dtype != np.uint8 or rows.ndim != 2 or q.shape != (rows.shape[1],):
+        raise ValueError("hamming_reference: uint8 rows [n, d] and a uint8 query [d] are needed")
+    return np.unpackbits(rows ^ q[None, :], axis=1).sum(axis=1, dtype=np.int64).astype(np.float32)
 
 
 def plan_batch_half_form(stride_bytes, k, nq):

@@ -75,7 +75,7 @@ __device__ inline uint32_t vg_dot4(uint32_t a, uint32_t b, uint32_t c) {
 }
 
 template <int VT, int ACC> struct AccumInt {
-    uint32_t sqx;           // sum q*x  (DOT/COS/L2) | sum |q-x| (L1)       -- exact, modulo 2^32 like the reference
+    uint32_t sqx;           // sum q*x  (DOT/COS/L2) | sum |q-x| (L1) | sum popcount(q^x) (HAM)   -- exact, modulo 2^32 like the reference
     uint32_t sxx;           // sum x*x  (COS/L2)
     struct QStat { uint32_t qq; };
 
@@ -86,6 +86,9 @@ template <int VT, int ACC> struct AccumInt {
             // |q-x| per byte: v_sad_u8; signed bytes are biased by 128 first (|a-b| is shift invariant)
             const uint32_t bias = (VT == T_I8) ? 0x80808080u : 0u;
             sqx = __builtin_amdgcn_sad_u8(q ^ bias, x ^ bias, sqx);
+        } else if (ACC == A_HAM) {
+            // differing bits of 32 dimensions (T_U8 only, vg_pick.h); bit count first: v_bcnt_u32_b32 adds its second operand
+            sqx = (uint32_t)__builtin_popcount(q ^ x) + sqx;
         } else {
             sqx = vg_dot4<VT>(q, x, sqx);
             if (ACC != A_DOT) sxx = vg_dot4<VT>(x, x, sxx);
@@ -122,6 +125,7 @@ template <int VT, int ACC> struct AccumInt {
     __device__ inline float finish(const QStat &qs, int lpr_log2, int root) {
         const uint32_t qx = vg_group_sum(sqx, lpr_log2);
         if (ACC == A_L1) return as_float_signed_like(qx);
+        if (ACC == A_HAM) return (float)qx;                              // at most 8 * dim < 2^24: exact
         if (ACC == A_DOT) return -as_float_signed_like(qx);
         const uint32_t xx = vg_group_sum(sxx, lpr_log2);
         if (ACC == A_L2) {

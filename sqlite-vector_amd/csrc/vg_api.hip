@@ -111,6 +111,7 @@ int vg_metric_to_acc(int metric);
 extern "C" int vg_plan_scan_shape(int vtype, int dim, int metric, int *lanes_per_row, int *chunks_per_lane, int *long_rows) {
     const int acc = vg_metric_to_acc(metric);
     if (vtype < VG_TYPE_F32 || vtype > VG_TYPE_I8 || dim < 1 || acc < 0) return vg_fail(VG_ERR_INVALID, "vg_plan_scan_shape: bad type / dim / metric");
+    if (int rcm = vg_metric_check(vtype, metric, "vg_plan_scan_shape")) return rcm;
     Shape s;
     choose_shape((int)(((long long)dim * vg_elem_size(vtype) + 15) / 16), vtype, acc, &s);
     if (lanes_per_row) *lanes_per_row = 1 << s.lpr_log2;
@@ -145,8 +146,26 @@ int vg_metric_to_acc(int metric) {
         case VG_DIST_COSINE: return A_COS;
         case VG_DIST_DOT: return A_DOT;
         case VG_DIST_L1: return A_L1;
+        case VG_DIST_HAMMING: return A_HAM;
     }
     return -1;
+}
+
+// The one home of "is this metric served over this element type": an unknown metric is VG_ERR_INVALID, Hamming distance over
+// anything but uint8 rows VG_ERR_UNSUPPORTED in the caller's name (A_HAM has uint8 kernels only, vg_pick.h).  Every entry point
+// that takes a metric asks here behind its own argument checks and in front of any launch
+int vg_metric_check(int vtype, int metric, const char *who) {
+    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (metric == VG_DIST_HAMMING && vtype != VG_TYPE_U8) return vg_fail(VG_ERR_UNSUPPORTED, "%s: Hamming distance needs a uint8 corpus", who);
+    return VG_OK;
+}
+// ... and where the caller serves tie_order = reference: the reference has no Hamming distance, hence no history-dependent order
+// of equal distances to reproduce - refused, not answered in position order under another name
+int vg_metric_check_tie(int vtype, int metric, int tie_order, const char *who) {
+    if (int rcm = vg_metric_check(vtype, metric, who)) return rcm;
+    if (metric == VG_DIST_HAMMING && tie_order == VG_TIE_REFERENCE)
+        return vg_fail(VG_ERR_UNSUPPORTED, "%s: Hamming distance is not served with tie_order = reference", who);
+    return VG_OK;
 }
 
 static const char *type_tag(int t) {
@@ -155,7 +174,7 @@ static const char *type_tag(int t) {
     return "?";
 }
 static const char *acc_tag(int a) {
-    switch (a) { case A_L2: return "l2"; case A_COS: return "cos"; case A_DOT: return "dot"; case A_L1: return "l1"; case A_COSN: return "cosn"; }
+    switch (a) { case A_L2: return "l2"; case A_COS: return "cos"; case A_DOT: return "dot"; case A_L1: return "l1"; case A_COSN: return "cosn"; case A_HAM: return "ham"; }
     return "?";
 }
 
@@ -176,7 +195,7 @@ extern "C" const char *vg_scan_kernel_name(vg_corpus *c, int metric) {
     if (!c) return "";
     Shape s;
     int acc = vg_metric_to_acc(metric);
-    if (acc < 0 || !choose_shape(c->nch, c->vtype, acc, &s)) return "";
+    if (acc < 0 || (acc == A_HAM && c->vtype != VG_TYPE_U8) || !choose_shape(c->nch, c->vtype, acc, &s)) return "";
     if (half_cosine_cached(c, acc, s)) acc = A_COSN;
     if (!s.long_rows && vg_scan_filter_name(c, metric, c->kernel_name, sizeof(c->kernel_name))) return c->kernel_name;
     snprintf(c->kernel_name, sizeof(c->kernel_name), "scan%s_%s_%s_u%d_lpr%d%s", s.long_rows ? "_long" : "",
@@ -281,7 +300,8 @@ int vg_launch_scan_kernel(scan_fn_t fn, long long blocks, size_t smem, hipStream
 static int launch_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int k, uint64_t *dev_out_keys,
                        float *dev_out_dist, hipStream_t stream, const ScanPlan &plan) {
     int acc = vg_metric_to_acc(metric);
-    if (acc < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (int rcm = vg_metric_check(c->vtype, metric, "scan launch")) return rcm;
+    if (acc == A_HAM && plan.ref_emit) return vg_fail(VG_ERR_UNSUPPORTED, "scan launch: Hamming distance has no reference tie order");
     const int64_t n_rows = (plan.n_rows >= 0) ? std::min<int64_t>(plan.n_rows, c->n_rows) : c->n_rows;
     if (plan.ref_emit) c->ref_prefix_rows = -1;              // (set by whichever launch below really emits)
     Shape s;
@@ -412,6 +432,7 @@ extern "C" int vg_scan_topk_device(vg_corpus *c, int metric, const void *dev_que
         HIP_TRY(hipMemsetAsync(dev_out_keys, 0xFF, VG_WAVE * sizeof(uint64_t), st));
         return VG_OK;
     }
+    if (int rcm = vg_metric_check(c->vtype, metric, "vg_scan_topk_device")) return rcm;
     return launch_scan(c, metric, (const uint8_t *)dev_query, k, dev_out_keys, nullptr, st);
 }
 
@@ -419,6 +440,7 @@ extern "C" int vg_scan_distances_device(vg_corpus *c, int metric, const void *de
     if (!c || !dev_query || !dev_out_dist) return vg_fail(VG_ERR_INVALID, "vg_scan_distances_device: NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     if (c->n_rows == 0) return VG_OK;
+    if (int rcm = vg_metric_check(c->vtype, metric, "vg_scan_distances_device")) return rcm;
     return launch_scan(c, metric, (const uint8_t *)dev_query, 0, nullptr, dev_out_dist, stream ? (hipStream_t)stream : c->stream);
 }
 
@@ -435,6 +457,7 @@ extern "C" int vg_scan_distances(vg_corpus *c, int metric, const void *query, fl
     if (!c || !query || !out_dist_host) return vg_fail(VG_ERR_INVALID, "vg_scan_distances: NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     if (c->n_rows == 0) return VG_OK;
+    if (int rcm = vg_metric_check(c->vtype, metric, "vg_scan_distances")) return rcm;
     int rc = ensure_dist_buffer(c);
     if (rc != VG_OK) return rc;
     stage_query(c, query);
@@ -453,6 +476,7 @@ extern "C" int vg_scan_distances_resident(vg_corpus *c, int metric, const void *
     if (!c || !query) return vg_fail(VG_ERR_INVALID, "vg_scan_distances_resident: NULL argument");
     HIP_TRY(hipSetDevice(c->device));
     if (c->n_rows == 0) { c->dist_valid_rows = 0; return VG_OK; }
+    if (int rcm = vg_metric_check(c->vtype, metric, "vg_scan_distances_resident")) return rcm;
     int rc = ensure_dist_buffer(c);
     if (rc != VG_OK) return rc;
     stage_query(c, query);
@@ -519,7 +543,7 @@ static int scan_topk_large_k(vg_corpus *c, int metric, const void *query, int k,
 int vg_scan_topk_enqueue_plan(vg_corpus *c, int metric, const void *query, int k, bool ref_emit) {
     if (!c || !query) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_enqueue: NULL argument");
     if (k < 1 || k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_enqueue: k must be in 1..%d", VG_MAX_FUSED_K);
-    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (int rcm = vg_metric_check(c->vtype, metric, "vg_scan_topk_enqueue")) return rcm;
     c->enqueued = false;
     if (c->n_rows == 0) return VG_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -553,7 +577,7 @@ extern "C" int vg_scan_topk_enqueue(vg_corpus *c, int metric, const void *query,
 int vg_scan_topk_enqueue_dev(vg_corpus *c, int metric, const void *query, int k) {
     if (!c || !query) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_enqueue_dev: NULL argument");
     if (k < 1 || k > VG_MAX_FUSED_K) return vg_fail(VG_ERR_UNSUPPORTED, "vg_scan_topk_enqueue_dev: k must be in 1..%d", VG_MAX_FUSED_K);
-    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (int rcm = vg_metric_check(c->vtype, metric, "vg_scan_topk_enqueue_dev")) return rcm;
     HIP_TRY(hipSetDevice(c->device));
     c->enqueued = false;
     if (c->n_rows == 0) {
@@ -584,7 +608,7 @@ extern "C" int vg_scan_topk_keys(vg_corpus *c, int metric, const void *query, in
     *out_count = 0;
     if (k <= 0 || c->n_rows == 0) return VG_OK;
     if (!out_keys) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_keys: NULL output");
-    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (int rcm = vg_metric_check(c->vtype, metric, "vg_scan_topk_keys")) return rcm;
     HIP_TRY(hipSetDevice(c->device));
     if (k > VG_MAX_FUSED_K) return scan_topk_large_k(c, metric, query, k, out_keys, out_count);
     uint64_t keys[VG_WAVE];
@@ -603,6 +627,7 @@ extern "C" int vg_scan_topk(vg_corpus *c, int metric, const void *query, int k, 
     *out_count = 0;
     if (k <= 0 || c->n_rows == 0) return VG_OK;
     if (!out_rowids || !out_dist) return vg_fail(VG_ERR_INVALID, "vg_scan_topk: NULL output");
+    if (int rcm = vg_metric_check_tie(c->vtype, metric, c->tie_order, "vg_scan_topk")) return rcm;
     if (c->tie_order == VG_TIE_REFERENCE) return vg_scan_topk_reference(c, metric, query, k, out_rowids, out_dist, out_count);
     std::vector<uint64_t> keys((size_t)std::min<int64_t>((int64_t)k, c->n_rows));
     int cnt = 0;

@@ -152,7 +152,7 @@ static bool batch_h_eligible(const vg_corpus *c, int metric, int k) {
 static bool batch_i8_eligible(const vg_corpus *c, int metric, int k) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0) return false;
     if (c->vtype != VG_TYPE_U8 && c->vtype != VG_TYPE_I8) return false;
-    if (metric == VG_DIST_L1) return false;
+    if (metric == VG_DIST_L1 || metric == VG_DIST_HAMMING) return false;   // (the kernel's modes: L2 / cosine / dot - a bit count is no matrix product)
     return vg_batch_i8_lds_bytes(c->stride, k) != 0;
 }
 
@@ -697,6 +697,7 @@ extern "C" int vg_scan_topk_batch_keys(vg_corpus *c, int metric, const void *que
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k <= 0 || c->n_rows == 0) return VG_OK;
     if (!out_keys) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch_keys: NULL output");
+    if (int rcm = vg_metric_check(c->vtype, metric, "vg_scan_topk_batch_keys")) return rcm;
     HIP_TRY(hipSetDevice(c->device));
     // A handful of queries over a corpus the filter scans serve: single scans (0.7 ms each at 10M x 384, whatever the type) beat one
     // 128- / 256-query-wide matrix pass (~2.9 ms however few of its query slots are used) up to three queries; they tie at four.
@@ -796,6 +797,7 @@ extern "C" int vg_scan_topk_batch(vg_corpus *c, int metric, const void *queries,
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k <= 0 || c->n_rows == 0) return VG_OK;
     if (!out_rowids || !out_dist) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_batch: NULL output");
+    if (int rcm = vg_metric_check_tie(c->vtype, metric, c->tie_order, "vg_scan_topk_batch")) return rcm;
     if (c->tie_order == VG_TIE_REFERENCE) {
         // The reference's order differs from (distance, position) only where equal distances meet among a query's k + 1 best
         // (vg_scan_topk_reference): the batch runs as it is - matrix cores included - with one more list slot, and only the

@@ -23,7 +23,7 @@ static int fused_multi_plan(const vg_corpus *c, int metric, VgShape *s, scan_fn_
 
 int vg_batch_plan_report(const vg_corpus *c, int metric, vg_pick_multi_fn_t pick, int *out_queries_per_pass, int *out_lpr, int *out_u) {
     if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
-    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (int rcm = vg_metric_check(c->vtype, metric, "batch plan")) return rcm;
     VgShape s{};
     const int NQ = fused_multi_plan(c, metric, &s, nullptr, pick);
     if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the form's single scan has the plain scan's
@@ -187,6 +187,7 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
     if (f.single.needs_labels && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
     for (int i = 0; i < nq && f.rows == VG_QROWS_LABEL; ++i)
         if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", f.who, i);
+    if (int rcm = vg_metric_check(c->vtype, metric, f.who)) return rcm;
     if ((f.rows == VG_QROWS_MASK && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     HIP_TRY(hipSetDevice(c->device));
     VgShape s{};

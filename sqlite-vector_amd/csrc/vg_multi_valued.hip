@@ -116,6 +116,7 @@ extern "C" int vg_scan_topk_batch_valued_keys(vg_corpus *c, int metric, const vo
         for (int i = 0; i < nq; ++i)
             if (query_labels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", form.who, i);
     }
+    if (int rcm = vg_metric_check(c->vtype, metric, form.who)) return rcm;
     // the queries in (label, lo, hi) order (stable: equal conditions keep caller order)
     const std::vector<int> order = vg_stable_order(nq, [&](int x, int y) {
         if (query_labels && query_labels[x] != query_labels[y]) return query_labels[x] < query_labels[y];

@@ -48,7 +48,7 @@ static int mw_plan(const vg_corpus *c, int metric, const WbForm &form, VgShape *
 
 static int within_batch_plan(const vg_corpus *c, int metric, const WbForm &form, int *out_queries_per_pass, int *out_lpr, int *out_u) {
     if (!c) return vg_fail(VG_ERR_INVALID, "corpus is NULL");
-    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (int rcm = vg_metric_check(c->vtype, metric, form.who)) return rcm;
     VgShape s{};
     const int NQ = mw_plan(c, metric, form, &s, nullptr);
     if (NQ == 0) vg_plain_scan_shape(c, metric, &s);          // the fallback's shape: the single range scan's
@@ -224,6 +224,7 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
         for (int i = 0; i < nq; ++i)
             if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: a query's label is VG_LABEL_NONE, which names no row", f.who);
     }
+    if (int rcm = vg_metric_check(c->vtype, metric, f.who)) return rcm;
     c->wb_keys.resize((size_t)nq);
     c->wb_matches.assign((size_t)nq, 0);
     if (c->n_rows == 0 || (masked && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch

@@ -246,7 +246,7 @@ extern "C" int vg_scan_topk_reference(vg_corpus *c, int metric, const void *quer
     *out_count = 0;
     if (k <= 0 || c->n_rows == 0) return VG_OK;
     if (!out_rowids || !out_dist) return vg_fail(VG_ERR_INVALID, "vg_scan_topk_reference: NULL output");
-    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (int rcm = vg_metric_check_tie(c->vtype, metric, VG_TIE_REFERENCE, "vg_scan_topk_reference")) return rcm;
     ++c->ref_stats[0];
     VgShape shape;
     vg_plain_scan_shape(c, metric, &shape);

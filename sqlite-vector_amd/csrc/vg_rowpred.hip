@@ -160,6 +160,7 @@ int vg_pred_topk_keys(vg_corpus *c, const char *who, VgResult result, const VgRo
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
     int rc = vg_pred_refusal(c, who, pred, result.with_labels());
     if (rc != VG_OK) return rc;
+    if ((rc = vg_metric_check(c->vtype, metric, who)) != VG_OK) return rc;
     if (c->n_rows == 0 || vg_pred_allows_nothing(pred)) return VG_OK;          // no row can be returned: no launch
     if ((rc = vg_pred_bits_enqueue(c, pred)) != VG_OK) return rc;
     return vg_fused_run(c, vg_pred_form(who, pred, result), metric, query, k, 0ull, out_keys, out_count, out_labels);
@@ -185,6 +186,7 @@ int vg_pred_within(vg_corpus *c, const char *who, const VgRowPred &pred, int met
     int rc = vg_within_begin(c, who, metric, query, radius, out_matches, out_held);
     if (rc != VG_OK) return rc;
     if ((rc = vg_pred_refusal(c, who, pred, false)) != VG_OK) return rc;
+    if ((rc = vg_metric_check(c->vtype, metric, who)) != VG_OK) return rc;
     if (c->n_rows == 0 || vg_pred_allows_nothing(pred)) return VG_OK;          // no row can match: no launch
     if ((rc = vg_pred_bits_enqueue(c, pred)) != VG_OK) return rc;
     VgWithinForm form = vg_within_form(who, vg_pick_scan_within_masked, VG_ROWS_BITMAP);

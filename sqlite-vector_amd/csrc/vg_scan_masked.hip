@@ -136,6 +136,7 @@ int vg_fused_run(vg_corpus *c, const VgFusedForm &f, int metric, const void *que
     if (f.rows == VG_ROWS_MASK && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
     if (f.needs_values && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
     if (f.needs_labels && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+    if (int rcm = vg_metric_check(c->vtype, metric, f.who)) return rcm;
     if ((f.rows == VG_ROWS_MASK && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
     if (f.after && floor == VG_EMPTY_KEY) return VG_OK;      // nothing is behind the cursor: no launch
     HIP_TRY(hipSetDevice(c->device));

@@ -153,6 +153,7 @@ int vg_within_run(vg_corpus *c, const VgWithinForm &f, int metric, const void *q
     if (f.rows == VG_ROWS_MASK && c->mask_count < 0) return vg_fail(VG_ERR_INVALID, "%s: no row mask set", f.who);
     if (f.needs_values && !c->has_values) return vg_fail(VG_ERR_INVALID, "%s: no values set", f.who);
     if (f.needs_labels && !c->has_labels) return vg_fail(VG_ERR_INVALID, "%s: no labels set", f.who);
+    if (int rcm = vg_metric_check(c->vtype, metric, f.who)) return rcm;
     if (c->n_rows == 0 || (f.rows == VG_ROWS_MASK && c->mask_count == 0)) return VG_OK;      // nothing can match: no launch
     HIP_TRY(hipSetDevice(c->device));
     c->enqueued = false;                                     // (the pinned key buffer is this scan's landing zone now)

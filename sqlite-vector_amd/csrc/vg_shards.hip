@@ -766,6 +766,7 @@ extern "C" int vg_shards_scan_topk(vg_shards *s, int metric, const void *query, 
     if (s->S == 1 && s->gather_mode == 0) return vg_scan_topk(s->sh[0], metric, query, k, out_rowids, out_dist, out_count);
     if (k <= 0 || s->n_rows == 0) return VG_OK;
     if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk: NULL output");
+    if (int rcm = vg_metric_check_tie(s->vtype, metric, s->tie_order, "vg_shards_scan_topk")) return rcm;
     const bool ref = s->tie_order == VG_TIE_REFERENCE;
     if (ref && k > VG_WAVE_KEYS) { ++s->ref_stats[0]; return shards_scan_topk_reference(s, metric, query, k, out_rowids, out_dist, out_count); }
     if (ref) return shards_scan_topk_fused(s, metric, query, k, false, out_rowids, out_dist, out_count);
@@ -796,6 +797,7 @@ extern "C" int vg_shards_scan_topk_batch(vg_shards *s, int metric, const void *q
     for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     if (k <= 0 || s->n_rows == 0) return VG_OK;
     if (!out_rowids || !out_dist) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_batch: NULL output");
+    if (int rcm = vg_metric_check_tie(s->vtype, metric, s->tie_order, "vg_shards_scan_topk_batch")) return rcm;
     const bool ref = s->tie_order == VG_TIE_REFERENCE;      // (one more list slot; only the queries with a tie are answered again, one by one)
     const size_t qbytes = (size_t)s->dim * s->es;
     if (ref && k >= VG_WAVE_KEYS) {                          // no slot to look for a tie with: every query through the single-query form
@@ -1292,7 +1294,7 @@ static const FusedForm kFusedForms[] = {
 // VG_OK: go on; FUSED_ONE_SHARD: the handle is one corpus, whose own entry point answers (and refuses); anything else: refused.
 // `inputs`: the form's input pointers are all there; `outputs`: its output arrays are (the counts: out_counts, nq of them, zeroed here)
 enum { FUSED_ONE_SHARD = -1 };
-static int fused_preamble(int form, const vg_shards *s, bool inputs, int nq, int k, int per_label, bool outputs, int *out_counts) {
+static int fused_preamble(int form, const vg_shards *s, int metric, bool inputs, int nq, int k, int per_label, bool outputs, int *out_counts) {
     const FusedForm &f = kFusedForms[form];
     if (!s || !inputs || !out_counts) return refuse(VG_ERR_INVALID, f.outer, "NULL argument");
     if (s->S == 1) return FUSED_ONE_SHARD;
@@ -1306,6 +1308,9 @@ static int fused_preamble(int form, const vg_shards *s, bool inputs, int nq, int
     if (f.values && !vg_shards_has_values(s)) return refuse(VG_ERR_INVALID, f.inner, "no values set");
     if (f.labels && !vg_shards_has_labels(s)) return refuse(VG_ERR_INVALID, f.inner, "no labels set");
     if (f.by_label && s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, f.outer, "more than 2^32 - 1 rows over all shards");
+    // (an unknown metric stays the shards' own refusal: their entry points give it in front of some of their own argument checks - a
+    //  label set's offsets, a cursor - and behind others, an order this preamble cannot reproduce for every form)
+    if (metric == VG_DIST_HAMMING) return vg_metric_check(s->vtype, metric, f.inner);
     return VG_OK;
 }
 
@@ -1375,7 +1380,7 @@ static int merge_back_by_label(const vg_shards *s, const ShardLists &L, int k, i
 
 extern "C" int vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
                                           int *out_count) {
-    int rc = fused_preamble(F_MASKED, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    int rc = fused_preamble(F_MASKED, s, metric, query, 1, k, 0, out_rowids && out_dist, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_masked(s->sh[0], metric, query, k, out_rowids, out_dist, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1387,7 +1392,7 @@ extern "C" int vg_shards_scan_topk_masked(vg_shards *s, int metric, const void *
 
 extern "C" int vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
                                                 double *out_dist, int *out_counts) {
-    int rc = fused_preamble(F_BATCH_MASKED, s, queries, nq, k, 0, out_rowids && out_dist, out_counts);
+    int rc = fused_preamble(F_BATCH_MASKED, s, metric, queries, nq, k, 0, out_rowids && out_dist, out_counts);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_batch_masked(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_counts);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1399,7 +1404,7 @@ extern "C" int vg_shards_scan_topk_batch_masked(vg_shards *s, int metric, const 
 
 extern "C" int vg_shards_scan_topk_labeled(vg_shards *s, int metric, const void *query, int k, uint32_t label, int64_t *out_rowids,
                                            double *out_dist, int *out_count) {
-    int rc = fused_preamble(F_LABELED, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    int rc = fused_preamble(F_LABELED, s, metric, query, 1, k, 0, out_rowids && out_dist, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_labeled(s->sh[0], metric, query, k, label, out_rowids, out_dist, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1411,7 +1416,7 @@ extern "C" int vg_shards_scan_topk_labeled(vg_shards *s, int metric, const void 
 
 extern "C" int vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
                                                  int64_t *out_rowids, double *out_dist, int *out_counts) {
-    int rc = fused_preamble(F_BATCH_LABELED, s, queries && query_labels, nq, k, 0, out_rowids && out_dist, out_counts);
+    int rc = fused_preamble(F_BATCH_LABELED, s, metric, queries && query_labels, nq, k, 0, out_rowids && out_dist, out_counts);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_batch_labeled(s->sh[0], metric, queries, nq, query_labels, k, out_rowids, out_dist, out_counts);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1425,7 +1430,7 @@ extern "C" int vg_shards_scan_topk_batch_labeled(vg_shards *s, int metric, const
 // (and refuses a bad set itself)
 extern "C" int vg_shards_scan_topk_labelset(vg_shards *s, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels,
                                             int exclude, int64_t *out_rowids, double *out_dist, int *out_count) {
-    int rc = fused_preamble(F_LABELSET, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    int rc = fused_preamble(F_LABELSET, s, metric, query, 1, k, 0, out_rowids && out_dist, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_labelset(s->sh[0], metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1437,7 +1442,7 @@ extern "C" int vg_shards_scan_topk_labelset(vg_shards *s, int metric, const void
 
 extern "C" int vg_shards_scan_topk_batch_labelset(vg_shards *s, int metric, const void *queries, int nq, int k, const uint32_t *set_labels,
                                                   const int64_t *set_offsets, int exclude, int64_t *out_rowids, double *out_dist, int *out_counts) {
-    int rc = fused_preamble(F_BATCH_LABELSET, s, queries && set_offsets, nq, k, 0, out_rowids && out_dist, out_counts);
+    int rc = fused_preamble(F_BATCH_LABELSET, s, metric, queries && set_offsets, nq, k, 0, out_rowids && out_dist, out_counts);
     if (rc == FUSED_ONE_SHARD)
         return vg_scan_topk_batch_labelset(s->sh[0], metric, queries, nq, k, set_labels, set_offsets, exclude, out_rowids, out_dist, out_counts);
     if (rc != VG_OK) return rc;
@@ -1451,7 +1456,7 @@ extern "C" int vg_shards_scan_topk_batch_labelset(vg_shards *s, int metric, cons
 // grouped scans: the k nearest labels, the best row of each
 extern "C" int vg_shards_scan_topk_grouped(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
                                            uint32_t *out_labels, int *out_count) {
-    int rc = fused_preamble(F_GROUPED, s, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
+    int rc = fused_preamble(F_GROUPED, s, metric, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_grouped(s->sh[0], metric, query, k, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1463,7 +1468,7 @@ extern "C" int vg_shards_scan_topk_grouped(vg_shards *s, int metric, const void 
 
 extern "C" int vg_shards_scan_topk_grouped_masked(vg_shards *s, int metric, const void *query, int k, int64_t *out_rowids, double *out_dist,
                                                   uint32_t *out_labels, int *out_count) {
-    int rc = fused_preamble(F_GROUPED_MASKED, s, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
+    int rc = fused_preamble(F_GROUPED_MASKED, s, metric, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_grouped_masked(s->sh[0], metric, query, k, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1475,7 +1480,7 @@ extern "C" int vg_shards_scan_topk_grouped_masked(vg_shards *s, int metric, cons
 
 extern "C" int vg_shards_scan_topk_batch_grouped(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
                                                  double *out_dist, uint32_t *out_labels, int *out_counts) {
-    int rc = fused_preamble(F_BATCH_GROUPED, s, queries, nq, k, 0, out_rowids && out_dist && out_labels, out_counts);
+    int rc = fused_preamble(F_BATCH_GROUPED, s, metric, queries, nq, k, 0, out_rowids && out_dist && out_labels, out_counts);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_batch_grouped(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1487,7 +1492,7 @@ extern "C" int vg_shards_scan_topk_batch_grouped(vg_shards *s, int metric, const
 
 extern "C" int vg_shards_scan_topk_batch_grouped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
                                                         double *out_dist, uint32_t *out_labels, int *out_counts) {
-    int rc = fused_preamble(F_BATCH_GROUPED_MASKED, s, queries, nq, k, 0, out_rowids && out_dist && out_labels, out_counts);
+    int rc = fused_preamble(F_BATCH_GROUPED_MASKED, s, metric, queries, nq, k, 0, out_rowids && out_dist && out_labels, out_counts);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_batch_grouped_masked(s->sh[0], metric, queries, nq, k, out_rowids, out_dist, out_labels, out_counts);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1500,7 +1505,7 @@ extern "C" int vg_shards_scan_topk_batch_grouped_masked(vg_shards *s, int metric
 // capped scans: the k nearest rows, at most per_label of one label
 extern "C" int vg_shards_scan_topk_capped(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t *out_rowids,
                                           double *out_dist, uint32_t *out_labels, int *out_count) {
-    int rc = fused_preamble(F_CAPPED, s, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
+    int rc = fused_preamble(F_CAPPED, s, metric, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_capped(s->sh[0], metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1512,7 +1517,7 @@ extern "C" int vg_shards_scan_topk_capped(vg_shards *s, int metric, const void *
 
 extern "C" int vg_shards_scan_topk_capped_masked(vg_shards *s, int metric, const void *query, int k, int per_label, int64_t *out_rowids,
                                                  double *out_dist, uint32_t *out_labels, int *out_count) {
-    int rc = fused_preamble(F_CAPPED_MASKED, s, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
+    int rc = fused_preamble(F_CAPPED_MASKED, s, metric, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_capped_masked(s->sh[0], metric, query, k, per_label, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1524,7 +1529,7 @@ extern "C" int vg_shards_scan_topk_capped_masked(vg_shards *s, int metric, const
 
 extern "C" int vg_shards_scan_topk_batch_capped(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
                                                 double *out_dist, uint32_t *out_labels, int *out_counts) {
-    int rc = fused_preamble(F_BATCH_CAPPED, s, queries, nq, k, per_label, out_rowids && out_dist && out_labels, out_counts);
+    int rc = fused_preamble(F_BATCH_CAPPED, s, metric, queries, nq, k, per_label, out_rowids && out_dist && out_labels, out_counts);
     if (rc == FUSED_ONE_SHARD)
         return vg_scan_topk_batch_capped(s->sh[0], metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
     if (rc != VG_OK) return rc;
@@ -1537,7 +1542,7 @@ extern "C" int vg_shards_scan_topk_batch_capped(vg_shards *s, int metric, const 
 
 extern "C" int vg_shards_scan_topk_batch_capped_masked(vg_shards *s, int metric, const void *queries, int nq, int k, int per_label, int64_t *out_rowids,
                                                        double *out_dist, uint32_t *out_labels, int *out_counts) {
-    int rc = fused_preamble(F_BATCH_CAPPED_MASKED, s, queries, nq, k, per_label, out_rowids && out_dist && out_labels, out_counts);
+    int rc = fused_preamble(F_BATCH_CAPPED_MASKED, s, metric, queries, nq, k, per_label, out_rowids && out_dist && out_labels, out_counts);
     if (rc == FUSED_ONE_SHARD)
         return vg_scan_topk_batch_capped_masked(s->sh[0], metric, queries, nq, k, per_label, out_rowids, out_dist, out_labels, out_counts);
     if (rc != VG_OK) return rc;
@@ -1550,7 +1555,7 @@ extern "C" int vg_shards_scan_topk_batch_capped_masked(vg_shards *s, int metric,
 
 extern "C" int vg_shards_scan_topk_grouped_labelset(vg_shards *s, int metric, const void *query, int k, const uint32_t *labels, int64_t n_labels,
                                                     int exclude, int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
-    int rc = fused_preamble(F_GROUPED_LABELSET, s, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
+    int rc = fused_preamble(F_GROUPED_LABELSET, s, metric, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
     if (rc == FUSED_ONE_SHARD)
         return vg_scan_topk_grouped_labelset(s->sh[0], metric, query, k, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;
@@ -1566,7 +1571,7 @@ extern "C" int vg_shards_scan_topk_capped_labelset(vg_shards *s, int metric, con
                                                    int *out_count) {
     if (out_count) *out_count = 0;
     if (per_label < 1) return fail(VG_ERR_INVALID, "vg_shards_scan_topk_capped_labelset: per_label must be at least 1");
-    int rc = fused_preamble(F_CAPPED_LABELSET, s, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
+    int rc = fused_preamble(F_CAPPED_LABELSET, s, metric, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
     if (rc == FUSED_ONE_SHARD)
         return vg_scan_topk_capped_labelset(s->sh[0], metric, query, k, per_label, labels, n_labels, exclude, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;
@@ -1580,7 +1585,7 @@ extern "C" int vg_shards_scan_topk_capped_labelset(vg_shards *s, int metric, con
 // value-range scans: an interval means the same on every shard - every shard gets the caller's interval(s), and labels, as they are
 extern "C" int vg_shards_valued_scan_topk(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi, int64_t *out_rowids,
                                           double *out_dist, int *out_count) {
-    int rc = fused_preamble(F_VALUED, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    int rc = fused_preamble(F_VALUED, s, metric, query, 1, k, 0, out_rowids && out_dist, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_valued(s->sh[0], metric, query, k, lo, hi, out_rowids, out_dist, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1592,7 +1597,7 @@ extern "C" int vg_shards_valued_scan_topk(vg_shards *s, int metric, const void *
 
 extern "C" int vg_shards_valued_scan_topk_labeled(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi, uint32_t label,
                                                   int64_t *out_rowids, double *out_dist, int *out_count) {
-    int rc = fused_preamble(F_VALUED_LABELED, s, query, 1, k, 0, out_rowids && out_dist, out_count);
+    int rc = fused_preamble(F_VALUED_LABELED, s, metric, query, 1, k, 0, out_rowids && out_dist, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_valued_labeled(s->sh[0], metric, query, k, lo, hi, label, out_rowids, out_dist, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1605,7 +1610,7 @@ extern "C" int vg_shards_valued_scan_topk_labeled(vg_shards *s, int metric, cons
 extern "C" int vg_shards_valued_scan_topk_batch(vg_shards *s, int metric, const void *queries, int nq, int k, const int64_t *los,
                                                 const int64_t *his, const uint32_t *query_labels, int64_t *out_rowids, double *out_dist,
                                                 int *out_counts) {
-    int rc = fused_preamble(F_BATCH_VALUED, s, queries && los && his, nq, k, 0, out_rowids && out_dist, out_counts);
+    int rc = fused_preamble(F_BATCH_VALUED, s, metric, queries && los && his, nq, k, 0, out_rowids && out_dist, out_counts);
     if (rc == FUSED_ONE_SHARD)
         return vg_scan_topk_batch_valued(s->sh[0], metric, queries, nq, k, los, his, query_labels, out_rowids, out_dist, out_counts);
     if (rc != VG_OK) return rc;
@@ -1619,7 +1624,7 @@ extern "C" int vg_shards_valued_scan_topk_batch(vg_shards *s, int metric, const 
 
 extern "C" int vg_shards_valued_scan_topk_grouped(vg_shards *s, int metric, const void *query, int k, int64_t lo, int64_t hi,
                                                   int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
-    int rc = fused_preamble(F_GROUPED_VALUED, s, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
+    int rc = fused_preamble(F_GROUPED_VALUED, s, metric, query, 1, k, 0, out_rowids && out_dist && out_labels, out_count);
     if (rc == FUSED_ONE_SHARD) return vg_scan_topk_grouped_valued(s->sh[0], metric, query, k, lo, hi, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;
     ShardLists L;
@@ -1633,7 +1638,7 @@ extern "C" int vg_shards_valued_scan_topk_capped(vg_shards *s, int metric, const
                                                  int64_t *out_rowids, double *out_dist, uint32_t *out_labels, int *out_count) {
     if (out_count) *out_count = 0;
     if (per_label < 1) return fail(VG_ERR_INVALID, "vg_shards_valued_scan_topk_capped: per_label must be at least 1");
-    int rc = fused_preamble(F_CAPPED_VALUED, s, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
+    int rc = fused_preamble(F_CAPPED_VALUED, s, metric, query, 1, k, per_label, out_rowids && out_dist && out_labels, out_count);
     if (rc == FUSED_ONE_SHARD)
         return vg_scan_topk_capped_valued(s->sh[0], metric, query, k, per_label, lo, hi, out_rowids, out_dist, out_labels, out_count);
     if (rc != VG_OK) return rc;

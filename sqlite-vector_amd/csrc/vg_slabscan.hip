@@ -117,7 +117,7 @@ extern "C" int vg_slab_scan_begin(int device, int vtype, int dim, int metric, co
     if (!out) return vg_fail(VG_ERR_INVALID, "vg_slab_scan_begin: out is NULL");
     *out = nullptr;
     if (!query || k < 0 || slab_rows < 1) return vg_fail(VG_ERR_INVALID, "vg_slab_scan_begin: query, k >= 0 and slab_rows >= 1 are needed");
-    if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
+    if (int rcm = vg_metric_check_tie(vtype, metric, tie_order, "vg_slab_scan_begin")) return rcm;
     vg_slab_scan *s = new vg_slab_scan();
     s->device = device; s->vtype = vtype; s->dim = dim; s->metric = metric; s->k = k; s->tie_order = tie_order;
     s->slab_rows = slab_rows; s->rowid_base = rowid_base;
