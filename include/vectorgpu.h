@@ -35,7 +35,8 @@ extern "C" {
 /* same numbering as the reference's enums, distance-cpu.h:36-58 */
 enum { VG_TYPE_F32 = 1, VG_TYPE_F16 = 2, VG_TYPE_BF16 = 3, VG_TYPE_U8 = 4, VG_TYPE_I8 = 5 };
 enum { VG_DIST_L2 = 1, VG_DIST_SQUARED_L2 = 2, VG_DIST_COSINE = 3, VG_DIST_DOT = 4, VG_DIST_L1 = 5,
-       VG_DIST_HAMMING = 6 /* not a metric of the reference: see below */ };
+       VG_DIST_HAMMING = 6 /* not a metric of the reference: see below */,
+       VG_DIST_JACCARD = 7 /* Jaccard / Tanimoto distance, not a metric of the reference either: see below */ };
 /* Hamming distance (VG_DIST_HAMMING): rows are bit vectors packed 8 dimensions to a byte, served for VG_TYPE_U8 corpora only - a row
  * of `dim` bytes is 8 * dim bits and the query is `dim` bytes like every uint8 query.  The distance of a row is popcount(q XOR x)
  * over its `dim` bytes, returned as a float: exact (8 * dim < 2^24 for every supported row length) and always finite; the zero
@@ -47,6 +48,20 @@ enum { VG_DIST_L2 = 1, VG_DIST_SQUARED_L2 = 2, VG_DIST_COSINE = 3, VG_DIST_DOT =
  * reference (corpus, shard set, vg_slab_scan_begin) together with it is VG_ERR_UNSUPPORTED: the reference has no such metric and so
  * no history-dependent order to reproduce.  The batch never takes the matrix cores and the single scan never the nibble filter:
  * vg_batch_last_path() reports 5 (multi-query scan) or 6 (single scans). */
+/* Jaccard / Tanimoto distance (VG_DIST_JACCARD): the distance of sparse bit sets of varying weight (fingerprints, tag and shingle
+ * sets), over the same rows as Hamming distance - VG_TYPE_U8 corpora only, `dim` bytes = 8 * dim bits a row, the query `dim` bytes.
+ * With i = popcount(q AND x) and u = popcount(q OR x) over the row's `dim` bytes the distance is the float (float)(u - i) / (float)u:
+ * two exact int-to-float conversions (u <= 8 * dim < 2^24) and ONE correctly rounded IEEE single division - not 1.0f - i / u, which
+ * rounds twice - and 0.0f where u == 0 (query and row both empty).  It is always finite and lies in [0, 1]; the zero padding of
+ * either side contributes nothing to i or u; equal rationals give equal floats (1/2, 2/4, 64/128), so ties are ordered as everywhere:
+ * (distance, scan position).  (Rows of 2^17 bytes and more: a non-zero distance of at most 8 * 2^-23 comes back as 0.0f, the
+ * engine's near-zero rule of every metric; no shorter row can have one.)  Every entry point that takes a metric serves it - plain,
+ * masked, range (the radius compares against this float), paged, labeled, label-set, valued, grouped and capped scans, single and
+ * batch, one corpus or shards, k > 64 - with the order, counts, VG_KEY_EMPTY padding and rowid mapping of every other metric.  The
+ * refusals are Hamming's two in the same positions: over any other element type VG_ERR_UNSUPPORTED ("<entry point>: Jaccard
+ * distance needs a uint8 corpus") behind the argument checks that return VG_ERR_INVALID and in front of any launch, counts and
+ * outputs zeroed; with tie_order = reference (corpus, shard set, vg_slab_scan_begin) VG_ERR_UNSUPPORTED.  The batch never takes the
+ * matrix cores and the single scan never the nibble filter: vg_batch_last_path() reports 5 or 6. */
 enum { VG_QUANT_AUTO = 0, VG_QUANT_U8 = 1, VG_QUANT_S8 = 2 };
 
 enum {

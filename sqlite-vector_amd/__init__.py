@@ -25,6 +25,8 @@ EXT_PATH = os.path.join(HERE, "vector.so")         # must be named vector.* (ent
 F32, F16, BF16, U8, I8 = 1, 2, 3, 4, 5
 L2, SQUARED_L2, COSINE, DOT, L1 = 1, 2, 3, 4, 5
 HAMMING = 6                  # not a metric of the reference: differing bits of packed bit vectors, U8 corpora only (pack_bits)
+JACCARD = 7                  # not a metric of the reference either: 1 - |q AND x| / |q OR x| of packed bit vectors, U8 corpora only
+TANIMOTO = JACCARD           # (the same distance under its other name)
 QUANT_U8, QUANT_S8 = 1, 2
 TIE_POSITION, TIE_REFERENCE = 0, 1
 KEY_EMPTY = 0xFFFFFFFFFFFFFFFF
@@ -339,8 +341,10 @@ def backend_name():
 
 
 def pack_bits(x):
-    """rows of bits for a U8 corpus scanned with HAMMING: a 2-D array of bools or numbers [n, d] -> uint8 [n, ceil(d / 8)].  A bit is 1
-    where the entry is true or > 0; the first dimension is the most significant bit of the first byte (np.packbits); tail bits are 0."""
+    """rows of bits for a U8 corpus scanned with HAMMING or JACCARD (= TANIMOTO): a 2-D array of bools or numbers [n, d] -> uint8
+    [n, ceil(d / 8)].  A bit is 1 where the entry is true or > 0; the first dimension is the most significant bit of the first byte
+    (np.packbits); tail bits are 0, so they add nothing to a Hamming distance nor to the intersection or union of a Jaccard distance.
+    The query of either metric is one such row."""
     x = np.asarray(x)
     if x.ndim != 2:
         raise ValueError("pack_bits: a 2-D array is needed, got %d-D" % x.ndim)
@@ -355,6 +359,20 @@ def hamming_reference(rows_u8, q_u8):
     if rows.dtype != np.uint8 or q.dtype != np.uint8 or rows.ndim != 2 or q.shape != (rows.shape[1],):
         raise ValueError("hamming_reference: uint8 rows [n, d] and a uint8 query [d] are needed")
     return np.unpackbits(rows ^ q[None, :], axis=1).sum(axis=1, dtype=np.int64).astype(np.float32)
+
+
+def jaccard_reference(rows_u8, q_u8):
+    """(u - i) / u with i = popcount(q AND row), u = popcount(q OR row) of every row on the host, float32 [n], 0 where u == 0: what
+    a JACCARD scan returns as distances, bit for bit - one float32 division of two exactly converted integers (spot checks, tests)"""
+    rows = np.asarray(rows_u8)
+    q = np.asarray(q_u8)
+    if rows.dtype != np.uint8 or q.dtype != np.uint8 or rows.ndim != 2 or q.shape != (rows.shape[1],):
+        raise ValueError("jaccard_reference: uint8 rows [n, d] and a uint8 query [d] are needed")
+    i = np.unpackbits(rows & q[None, :], axis=1).sum(axis=1, dtype=np.int64)
+    u = np.unpackbits(rows | q[None, :], axis=1).sum(axis=1, dtype=np.int64)
+    out = np.zeros(rows.shape[0], dtype=np.float32)
+    np.divide((u - i).astype(np.float32), u.astype(np.float32), out=out, where=u > 0)
+    return out
 
 
 def plan_batch_half_form(stride_bytes, k, nq):

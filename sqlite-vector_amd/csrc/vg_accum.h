@@ -75,8 +75,8 @@ __device__ inline uint32_t vg_dot4(uint32_t a, uint32_t b, uint32_t c) {
 }
 
 template <int VT, int ACC> struct AccumInt {
-    uint32_t sqx;           // sum q*x  (DOT/COS/L2) | sum |q-x| (L1) | sum popcount(q^x) (HAM)   -- exact, modulo 2^32 like the reference
-    uint32_t sxx;           // sum x*x  (COS/L2)
+    uint32_t sqx;           // sum q*x  (DOT/COS/L2) | sum |q-x| (L1) | sum popcount(q^x) (HAM, JAC)   -- exact, modulo 2^32 like the reference
+    uint32_t sxx;           // sum x*x  (COS/L2) | sum popcount(q|x) (JAC)
     struct QStat { uint32_t qq; };
 
     __device__ inline void init() { sqx = 0; sxx = 0; }
@@ -89,6 +89,11 @@ template <int VT, int ACC> struct AccumInt {
         } else if (ACC == A_HAM) {
             // differing bits of 32 dimensions (T_U8 only, vg_pick.h); bit count first: v_bcnt_u32_b32 adds its second operand
             sqx = (uint32_t)__builtin_popcount(q ^ x) + sqx;
+        } else if (ACC == A_JAC) {
+            // differing bits and union bits of 32 dimensions (T_U8 only, vg_pick.h): |q OR x| - |q AND x| = |q XOR x|, so the two sums
+            // are the distance's numerator and denominator and no query statistic is kept live through the loop
+            sqx = (uint32_t)__builtin_popcount(q ^ x) + sqx;
+            sxx = (uint32_t)__builtin_popcount(q | x) + sxx;
         } else {
             sqx = vg_dot4<VT>(q, x, sqx);
             if (ACC != A_DOT) sxx = vg_dot4<VT>(x, x, sxx);
@@ -128,6 +133,11 @@ template <int VT, int ACC> struct AccumInt {
         if (ACC == A_HAM) return (float)qx;                              // at most 8 * dim < 2^24: exact
         if (ACC == A_DOT) return -as_float_signed_like(qx);
         const uint32_t xx = vg_group_sum(sxx, lpr_log2);
+        if (ACC == A_JAC) {
+            // (u - i) / u with i = |q AND x|, u = |q OR x| and u - i = |q XOR x|: two exact conversions (u <= 8 * dim < 2^24) and
+            // ONE correctly rounded divide, not 1 - i / u, which rounds twice; two empty sets are at distance 0
+            return xx ? __fdiv_rn((float)qx, (float)xx) : 0.0f;
+        }
         if (ACC == A_L2) {
             // sum (q-x)^2 = qq + xx - 2 qx, exact in modular 32-bit arithmetic
             const uint32_t total = qs.qq + xx - 2u * qx;

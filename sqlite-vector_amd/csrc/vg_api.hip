@@ -147,24 +147,30 @@ int vg_metric_to_acc(int metric) {
         case VG_DIST_DOT: return A_DOT;
         case VG_DIST_L1: return A_L1;
         case VG_DIST_HAMMING: return A_HAM;
+        case VG_DIST_JACCARD: return A_JAC;
     }
     return -1;
 }
 
-// The one home of "is this metric served over this element type": an unknown metric is VG_ERR_INVALID, Hamming distance over
-// anything but uint8 rows VG_ERR_UNSUPPORTED in the caller's name (A_HAM has uint8 kernels only, vg_pick.h).  Every entry point
-// that takes a metric asks here behind its own argument checks and in front of any launch
+// the metrics over packed bit vectors (Hamming, Jaccard): uint8 kernels only, no reference tie order, no nibble filter, no matrix cores
+bool vg_metric_is_bits(int metric) { return metric == VG_DIST_HAMMING || metric == VG_DIST_JACCARD; }
+static const char *bits_metric_name(int metric) { return metric == VG_DIST_JACCARD ? "Jaccard" : "Hamming"; }
+
+// The one home of "is this metric served over this element type": an unknown metric is VG_ERR_INVALID, a bit-vector distance over
+// anything but uint8 rows VG_ERR_UNSUPPORTED in the caller's name (A_HAM and A_JAC have uint8 kernels only, vg_pick.h).  Every entry
+// point that takes a metric asks here behind its own argument checks and in front of any launch
 int vg_metric_check(int vtype, int metric, const char *who) {
     if (vg_metric_to_acc(metric) < 0) return vg_fail(VG_ERR_INVALID, "unknown distance metric %d", metric);
-    if (metric == VG_DIST_HAMMING && vtype != VG_TYPE_U8) return vg_fail(VG_ERR_UNSUPPORTED, "%s: Hamming distance needs a uint8 corpus", who);
+    if (vg_metric_is_bits(metric) && vtype != VG_TYPE_U8)
+        return vg_fail(VG_ERR_UNSUPPORTED, "%s: %s distance needs a uint8 corpus", who, bits_metric_name(metric));
     return VG_OK;
 }
-// ... and where the caller serves tie_order = reference: the reference has no Hamming distance, hence no history-dependent order
+// ... and where the caller serves tie_order = reference: the reference has no bit-vector distance, hence no history-dependent order
 // of equal distances to reproduce - refused, not answered in position order under another name
 int vg_metric_check_tie(int vtype, int metric, int tie_order, const char *who) {
     if (int rcm = vg_metric_check(vtype, metric, who)) return rcm;
-    if (metric == VG_DIST_HAMMING && tie_order == VG_TIE_REFERENCE)
-        return vg_fail(VG_ERR_UNSUPPORTED, "%s: Hamming distance is not served with tie_order = reference", who);
+    if (vg_metric_is_bits(metric) && tie_order == VG_TIE_REFERENCE)
+        return vg_fail(VG_ERR_UNSUPPORTED, "%s: %s distance is not served with tie_order = reference", who, bits_metric_name(metric));
     return VG_OK;
 }
 
@@ -174,7 +180,7 @@ static const char *type_tag(int t) {
     return "?";
 }
 static const char *acc_tag(int a) {
-    switch (a) { case A_L2: return "l2"; case A_COS: return "cos"; case A_DOT: return "dot"; case A_L1: return "l1"; case A_COSN: return "cosn"; case A_HAM: return "ham"; }
+    switch (a) { case A_L2: return "l2"; case A_COS: return "cos"; case A_DOT: return "dot"; case A_L1: return "l1"; case A_COSN: return "cosn"; case A_HAM: return "ham"; case A_JAC: return "jac"; }
     return "?";
 }
 
@@ -195,7 +201,7 @@ extern "C" const char *vg_scan_kernel_name(vg_corpus *c, int metric) {
     if (!c) return "";
     Shape s;
     int acc = vg_metric_to_acc(metric);
-    if (acc < 0 || (acc == A_HAM && c->vtype != VG_TYPE_U8) || !choose_shape(c->nch, c->vtype, acc, &s)) return "";
+    if (acc < 0 || (vg_metric_is_bits(metric) && c->vtype != VG_TYPE_U8) || !choose_shape(c->nch, c->vtype, acc, &s)) return "";
     if (half_cosine_cached(c, acc, s)) acc = A_COSN;
     if (!s.long_rows && vg_scan_filter_name(c, metric, c->kernel_name, sizeof(c->kernel_name))) return c->kernel_name;
     snprintf(c->kernel_name, sizeof(c->kernel_name), "scan%s_%s_%s_u%d_lpr%d%s", s.long_rows ? "_long" : "",
@@ -301,7 +307,8 @@ static int launch_scan(vg_corpus *c, int metric, const uint8_t *dev_query, int k
                        float *dev_out_dist, hipStream_t stream, const ScanPlan &plan) {
     int acc = vg_metric_to_acc(metric);
     if (int rcm = vg_metric_check(c->vtype, metric, "scan launch")) return rcm;
-    if (acc == A_HAM && plan.ref_emit) return vg_fail(VG_ERR_UNSUPPORTED, "scan launch: Hamming distance has no reference tie order");
+    if (vg_metric_is_bits(metric) && plan.ref_emit)
+        return vg_fail(VG_ERR_UNSUPPORTED, "scan launch: %s distance has no reference tie order", bits_metric_name(metric));
     const int64_t n_rows = (plan.n_rows >= 0) ? std::min<int64_t>(plan.n_rows, c->n_rows) : c->n_rows;
     if (plan.ref_emit) c->ref_prefix_rows = -1;              // (set by whichever launch below really emits)
     Shape s;

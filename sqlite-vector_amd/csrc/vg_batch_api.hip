@@ -152,7 +152,7 @@ static bool batch_h_eligible(const vg_corpus *c, int metric, int k) {
 static bool batch_i8_eligible(const vg_corpus *c, int metric, int k) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0) return false;
     if (c->vtype != VG_TYPE_U8 && c->vtype != VG_TYPE_I8) return false;
-    if (metric == VG_DIST_L1 || metric == VG_DIST_HAMMING) return false;   // (the kernel's modes: L2 / cosine / dot - a bit count is no matrix product)
+    if (metric == VG_DIST_L1 || vg_metric_is_bits(metric)) return false;   // (the kernel's modes: L2 / cosine / dot - a bit count is no matrix product)
     return vg_batch_i8_lds_bytes(c->stride, k) != 0;
 }
 

@@ -339,10 +339,11 @@ static inline hipEvent_t *vg_prof_slot(vg_corpus *c, uint8_t flags) {
 
 // ---- internal entry points that cross translation units
 int vg_metric_to_acc(int metric);                                  // vg_api.hip; -1 for an unknown metric
-// vg_api.hip: VG_OK, or the refusal every entry point gives for its metric - unknown: VG_ERR_INVALID; Hamming distance over an
-// element type other than uint8: VG_ERR_UNSUPPORTED, the message in `who`'s name
+bool vg_metric_is_bits(int metric);                                // vg_api.hip: a distance over packed bit vectors (Hamming, Jaccard)
+// vg_api.hip: VG_OK, or the refusal every entry point gives for its metric - unknown: VG_ERR_INVALID; Hamming or Jaccard distance
+// over an element type other than uint8: VG_ERR_UNSUPPORTED, the message in `who`'s name
 int vg_metric_check(int vtype, int metric, const char *who);
-int vg_metric_check_tie(int vtype, int metric, int tie_order, const char *who);   // ... and Hamming under tie_order = reference: VG_ERR_UNSUPPORTED
+int vg_metric_check_tie(int vtype, int metric, int tie_order, const char *who);   // ... and either under tie_order = reference: VG_ERR_UNSUPPORTED
 void vg_collect_timing(vg_corpus *c);                              // vg_api.hip: event times of the last launch
 int vg_ensure_row_norms(vg_corpus *c);                             // vg_api.hip (uses the f16 / bf16 norm kernel of vg_scan.h)
 struct VgShape { int lpr_log2; int U; bool long_rows; };           // launch shape of a scan: lanes per row, chunks per lane

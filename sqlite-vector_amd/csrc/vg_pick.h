@@ -3,7 +3,7 @@
 // One ladder for the single-query kernels (vg_scan.h) and one for the multi-query kernel (vg_scan_multi.h); WHICH kernel template
 // a ladder walks is its family - a struct with templated static getters (a function template cannot be a template argument):
 //     single-query   template <int VT, int ACC, int U> static scan_fn_t fn();         the register-resident kernel
-//                    static const bool has_ham;                                        the table holds the uint8 Hamming instances
+//                    static const bool has_bits;                                       the table holds the uint8 bit-vector instances (Hamming, Jaccard)
 //                    static const bool has_long;                                       rows no shape covers are served ...
 //                    template <int VT, int ACC> static scan_fn_t long_fn();            ... by this kernel (only when has_long)
 //     multi-query    template <int VT, int ACC, int U, int NQ> static scan_fn_t fn();
@@ -12,8 +12,8 @@
 // A getter is instantiated only for the combinations a ladder names, and a kernel only where its getter is: the translation unit
 // that walks a ladder over a family holds that family's kernels, and exactly these -
 //     single-query   all five element types x L2 / cosine / dot / L1 x U in {1, 2, 3, 4, 6, 8}; A_COSN (cached row norms) for
-//                    f16 / bf16 only; the long-row kernel without A_COSN; A_HAM (Hamming distance) for uint8 only, long rows included, not in the EX table
-//     multi-query    f32 / uint8 / int8 x L2 / cosine / dot / L1, A_HAM for uint8 only; U in {1, 2, 3} at 4 queries per pass, U in {4, 6} at 2
+//                    f16 / bf16 only; the long-row kernel without A_COSN; A_HAM / A_JAC (Hamming, Jaccard distance) for uint8 only, long rows included, not in the EX table
+//     multi-query    f32 / uint8 / int8 x L2 / cosine / dot / L1, A_HAM / A_JAC for uint8 only; U in {1, 2, 3} at 4 queries per pass, U in {4, 6} at 2
 // A combination outside the table is nullptr.
 #pragma once
 
@@ -25,7 +25,7 @@
 template <int FORM, bool NT, bool HAS_LONG>
 struct ScanFamily {
     static const bool has_long = HAS_LONG;
-    static const bool has_ham = !(FORM & VG_SQ_EX);      // tie_order = reference refuses Hamming before any launch: no EX instances
+    static const bool has_bits = !(FORM & VG_SQ_EX);     // tie_order = reference refuses Hamming and Jaccard before any launch: no EX instances
     template <int VT, int ACC, int U> static scan_fn_t fn() { return vg_scan_kernel<VT, ACC, U, NT, FORM>; }
     template <int VT, int ACC> static scan_fn_t long_fn() { return vg_scan_long_kernel<VT, ACC, NT, FORM>; }
 };
@@ -58,7 +58,10 @@ static scan_fn_t vg_pick_acc(int acc, int U, bool long_rows) {
                 case A_DOT: return F::template long_fn<VT, A_DOT>();
                 case A_L1: return F::template long_fn<VT, A_L1>();
                 case A_HAM:
-                    if constexpr (VT == T_U8 && F::has_ham) return F::template long_fn<VT, A_HAM>();
+                    if constexpr (VT == T_U8 && F::has_bits) return F::template long_fn<VT, A_HAM>();
+                    return nullptr;
+                case A_JAC:
+                    if constexpr (VT == T_U8 && F::has_bits) return F::template long_fn<VT, A_JAC>();
                     return nullptr;
             }
         }
@@ -73,7 +76,10 @@ static scan_fn_t vg_pick_acc(int acc, int U, bool long_rows) {
             if constexpr (VT == T_F16 || VT == T_BF16) return vg_pick_u<F, VT, A_COSN>(U);
             return nullptr;
         case A_HAM:
-            if constexpr (VT == T_U8 && F::has_ham) return vg_pick_u<F, VT, A_HAM>(U);
+            if constexpr (VT == T_U8 && F::has_bits) return vg_pick_u<F, VT, A_HAM>(U);
+            return nullptr;
+        case A_JAC:
+            if constexpr (VT == T_U8 && F::has_bits) return vg_pick_u<F, VT, A_JAC>(U);
             return nullptr;
     }
     return nullptr;
@@ -118,6 +124,9 @@ static scan_fn_t vg_pick_multi_acc(int acc, int U) {
         case A_L1: return vg_pick_multi_u<F, VT, A_L1, NQ>(U);
         case A_HAM:
             if constexpr (VT == T_U8) return vg_pick_multi_u<F, VT, A_HAM, NQ>(U);
+            return nullptr;
+        case A_JAC:
+            if constexpr (VT == T_U8) return vg_pick_multi_u<F, VT, A_JAC, NQ>(U);
             return nullptr;
     }
     return nullptr;

@@ -1310,7 +1310,7 @@ static int fused_preamble(int form, const vg_shards *s, int metric, bool inputs,
     if (f.by_label && s->n_rows > 0xFFFFFFFFll) return refuse(VG_ERR_UNSUPPORTED, f.outer, "more than 2^32 - 1 rows over all shards");
     // (an unknown metric stays the shards' own refusal: their entry points give it in front of some of their own argument checks - a
     //  label set's offsets, a cursor - and behind others, an order this preamble cannot reproduce for every form)
-    if (metric == VG_DIST_HAMMING) return vg_metric_check(s->vtype, metric, f.inner);
+    if (vg_metric_is_bits(metric)) return vg_metric_check(s->vtype, metric, f.inner);
     return VG_OK;
 }
 
