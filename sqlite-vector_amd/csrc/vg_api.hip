@@ -4,6 +4,7 @@
 // launch, decoding the k winning keys into (rowid, distance).  No distance is ever computed on the host: if
 // the HIP runtime / a gfx950 device is missing every entry point fails with VG_ERR_NO_DEVICE.
 #include "vg_internal.h"
+#include "vg_batch_units.h"          // vg_rownorm_launch
 
 #include "vg_scan.h"
 #include "vg_pick.h"
@@ -647,9 +648,6 @@ extern "C" int vg_scan_topk(vg_corpus *c, int metric, const void *query, int k, 
     *out_count = cnt;
     return VG_OK;
 }
-
-extern "C" int vg_rownorm_launch(const float *dev_rows, long long row0, long long n, long long stride_bytes, float *dev_out,
-                                 hipStream_t stream);
 
 // Row norms, computed once per appended row and kept next to the corpus.  f32 corpora: ||row|| (batched cosine / L2);
 // f16 / bf16 corpora: (float) sum x^2 (single-query cosine, A_COSN).

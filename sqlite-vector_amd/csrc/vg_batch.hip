@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "vg_batch_common.h"
+#include "vg_batch_units.h"
 
 #define VGB_THREADS 256
 #define VGB_WAVES 4

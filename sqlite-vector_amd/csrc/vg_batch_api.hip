@@ -2,48 +2,13 @@
 // statistics the matrix-core kernels need, query staging, launches of vg_batch.hip (f32) / vg_batch_i8.hip (uint8, int8) /
 // vg_batch_h.hip (f16, bf16), slicing of very large batches; shapes none of them serves go through the multi-query scan
 // (vg_multi.hip) or, last, one single-query scan per query.
+// Layout: the derived copies of the corpus (ensure_*), what the four drivers share (batch_mode_root, batch_type_code, unpack_keys,
+// rescan_unjudged; buffer growth, query staging and the profiling slot are vg_internal.h's), the drivers - scan_topk_batch_long /
+// _q8 / _mfma / _multi - and vg_scan_topk_batch_keys, which tries them in that order through run_sliced.
 #include "vg_internal.h"
+#include "vg_batch_units.h"          // the kernel units' host entry points
 
 #include "vg_device.h"
-
-// ---- batched queries: the MFMA path (vg_batch.hip) when the shape allows it, otherwise nq single-query scans
-extern "C" size_t vg_batch_lds_bytes(long long stride_bytes, int k);
-extern "C" int vg_batch_launch(const float *dev_rows, long long n_rows, long long stride_bytes,
-                               const float *dev_queries, int nq_pad, int nq_real, int k, int mode, int root,
-                               const float *dev_xnorm, uint64_t *dev_cand, int npart, int tiles_per_part,
-                               uint64_t *dev_out_keys, hipStream_t stream);
-extern "C" int vg_batch_lists_per_query(long long n_rows, int npart);
-extern "C" int vg_rownorm_launch(const float *dev_rows, long long row0, long long n, long long stride_bytes, float *dev_out,
-                                 hipStream_t stream);
-
-// Row norms, computed once per appended row and kept next to the corpus.  f32 corpora: ||row|| (batched cosine / L2);
-// f16 / bf16 corpora: (float) sum x^2 (single-query cosine, A_COSN).
-// ---- quantized batches on the integer matrix cores (vg_batch_i8.hip)
-extern "C" size_t vg_batch_i8_lds_bytes(long long stride_bytes, int k);
-extern "C" int vg_batch_i8_queries_per_block(long long stride_bytes);
-extern "C" int vg_i8_rowstat_launch(const uint8_t *dev_rows, long long row0, long long n, long long stride, int is_u8,
-                                    uint32_t *dev_stat, uint8_t *dev_flipped, hipStream_t stream);
-extern "C" int vg_batch_i8_launch(const uint8_t *dev_rows_signed, long long n_rows, long long stride_bytes,
-                                  const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int mode, int root, int is_u8,
-                                  const uint32_t *dev_row_stat, uint64_t *dev_cand, int npart,
-                                  int tiles_per_part, uint64_t *dev_out_keys, hipStream_t stream);
-
-// ---- f16 / bf16 batches: matrix-core filter + exact f64 re-evaluation (vg_batch_h.hip)
-extern "C" size_t vg_batch_h_lds_bytes(long long stride_bytes, int k);
-extern "C" int vg_batch_h_queries_per_block(long long stride_bytes);
-extern "C" int vg_batch_h_plan(long long stride_bytes, int k, int nq, int *waves, int *blocks_per_cu);
-extern "C" int vg_batch_h_launch(const uint8_t *dev_rows, int rows_tiled, long long n_rows, long long stride_bytes, int dim, int type_code,
-                                 const uint8_t *dev_xrows, long long xstride_bytes,
-                                 const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int mode, int root,
-                                 const float *dev_row_nn, uint64_t *dev_cand, int npart, int tiles_per_part,
-                                 uint64_t *dev_out_keys, unsigned long long *dev_evals, int waves,
-                                 uint64_t *dev_pairs, uint32_t *dev_pair_counts, int pair_cap, hipStream_t stream);
-extern "C" int vg_batch_h_split(long long stride_bytes, int k);        // vg_batch_h.hip: the split form is on for such rows
-#define VG_BPAIR_CAP 2048               // candidate pairs per filter wavefront and stage (a batch that overflows one falls back to the fused kernel)
-#define VG_BPAIR_CAP_LONG 8192          // ... of the long-row kernel (64 KB per region, 1024 regions: its fallback is one scan per query)
-extern "C" int vg_tile_major_launch(const uint8_t *dev_rows, long long row0, long long n, long long stride, uint8_t *dev_out, hipStream_t stream);
-extern "C" int vg_f32_to_bf16_launch(const uint8_t *dev_rows, long long row0, long long n, long long stride, int dim,
-                                     uint8_t *dev_out, long long ostride, hipStream_t stream);
 
 // f32 corpora with rows of 513 .. 1024 floats have no f32 matrix-core kernel (A does not fit the register file, the tiles not
 // the LDS): they run through the half-precision kernel with a bf16 SHADOW copy as the filter's input and the f32 rows for the
@@ -52,7 +17,6 @@ extern "C" int vg_f32_to_bf16_launch(const uint8_t *dev_rows, long long row0, lo
 // own rule (vg_filter.hip: switched on, >= 3 GB) is about to have - that shadow copy; VG_F32_FILTER=1 / 0 forces it on / off.
 // A selectivity guard like the filter scan's watches the exact evaluations (see scan_topk_batch_mfma).
 long long vg_bf16_shadow_stride(const vg_corpus *c) { return (((long long)c->dim * 2 + 15) / 16) * 16; }
-static long long bf16_shadow_stride(const vg_corpus *c) { return vg_bf16_shadow_stride(c); }
 static bool batch_f32_filter_short_rows(const vg_corpus *c) {
     const int sw = vg_sw(SW_VG_F32_FILTER, -1);
     if (sw >= 0) return sw != 0;
@@ -61,10 +25,10 @@ static bool batch_f32_filter_short_rows(const vg_corpus *c) {
 static bool batch_f32_filter_eligible(const vg_corpus *c, int metric, int k) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_F32 || metric == VG_DIST_L1) return false;
     if (c->dim <= 512 && !batch_f32_filter_short_rows(c)) return false;
-    return vg_batch_h_lds_bytes(bf16_shadow_stride(c), k) != 0;
+    return vg_batch_h_lds_bytes(vg_bf16_shadow_stride(c), k) != 0;
 }
 int vg_ensure_bf16_shadow(vg_corpus *c) {
-    const long long bs = bf16_shadow_stride(c);
+    const long long bs = vg_bf16_shadow_stride(c);
     if (c->bf_cap < c->n_rows) {
         const int64_t cap = std::max<int64_t>(c->cap_rows, c->n_rows);
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -81,31 +45,45 @@ int vg_ensure_bf16_shadow(vg_corpus *c) {
     return VG_OK;
 }
 
-// f32 corpora through the bf16 filter: the shadow copy the BATCH kernel streams is tile-major (vg_f32_to_bf16_tm_kernel) - the
-// row-major bf16 copy above is what the single-query bf16 filter scan reads (VG_SCAN_FILTER_SHADOW=bf16; the default single-query
-// filter streams the int8 copy, so by default only this one exists).  Same + 50 % of the corpus; tm_rows / tm_cap are shared with
-// the f16 / bf16 corpora's tile-major copy (a corpus has one element type).  -1: switched off / no memory (row-major gather).
-extern "C" int vg_f32_to_bf16_tm_launch(const uint8_t *dev_rows, long long row0, long long n, long long stride, int dim,
-                                        uint8_t *dev_out, long long ostride, hipStream_t stream);
-static int ensure_bf16_tile_major(vg_corpus *c) {
+// d_rows_tm, the tile-major copy of the corpus the half-precision batch kernels stream (a corpus has one element type, so one such
+// copy: tm_rows / tm_cap).  Made at the first batch, extended per appended row: reallocated (behind a wait for the corpus stream)
+// when the corpus outgrew it, whole 32-row tiles of `ostride` bytes per row, zeroed; extend(row0, n) enqueues the pass that writes
+// rows [row0, row0 + n) and returns 0 or a hipError_t, `what` names it in the failure's message.
+// -1: switched off / no memory (the kernel gathers from the row-major rows, the K-split kernel hands the batch on)
+template <class Extend> static int ensure_tile_major(vg_corpus *c, long long ostride, const char *what, Extend extend) {
     if (vg_sw(SW_VG_BATCH_TILE_MAJOR, 1) == 0 || c->tm_disabled) return -1;
-    const long long bs = bf16_shadow_stride(c);
     if (c->tm_cap < c->n_rows) {
         const int64_t cap = std::max<int64_t>(c->cap_rows, c->n_rows);
         HIP_TRY(hipStreamSynchronize(c->stream));
         if (c->d_rows_tm) hipFree(c->d_rows_tm);
         c->d_rows_tm = nullptr; c->tm_cap = 0; c->tm_rows = 0;
-        const size_t bytes = (size_t)((cap + 31) / 32 * 32) * bs;                               // whole tiles
+        const size_t bytes = (size_t)((cap + 31) / 32 * 32) * ostride;                          // whole tiles
         if (hipMalloc(&c->d_rows_tm, bytes) != hipSuccess) { (void)hipGetLastError(); c->d_rows_tm = nullptr; c->tm_disabled = true; return -1; }
         HIP_TRY(hipMemsetAsync(c->d_rows_tm, 0, bytes, c->stream));                             // (rows past the end: defined bytes)
         c->tm_cap = cap;
     }
     if (c->tm_rows < c->n_rows) {
-        int rc = vg_f32_to_bf16_tm_launch(c->d_rows, c->tm_rows, c->n_rows - c->tm_rows, c->stride, c->dim, c->d_rows_tm, bs, c->stream);
-        if (rc != 0) return vg_fail(VG_ERR_HIP, "tile-major bf16 shadow pass failed: %s", hipGetErrorString((hipError_t)rc));
+        const int rc = extend((long long)c->tm_rows, (long long)(c->n_rows - c->tm_rows));
+        if (rc != 0) return vg_fail(VG_ERR_HIP, "%s failed: %s", what, hipGetErrorString((hipError_t)rc));
         c->tm_rows = c->n_rows;
     }
     return VG_OK;
+}
+// f32 corpora through the bf16 filter: the shadow copy the BATCH kernel streams is tile-major (vg_f32_to_bf16_tm_kernel) - the
+// row-major bf16 copy above is what the single-query bf16 filter scan reads (VG_SCAN_FILTER_SHADOW=bf16; the default single-query
+// filter streams the int8 copy, so by default only this one exists).  + 50 % of the corpus in HBM
+static int ensure_bf16_tile_major(vg_corpus *c) {
+    const long long bs = vg_bf16_shadow_stride(c);
+    return ensure_tile_major(c, bs, "tile-major bf16 shadow pass", [&](long long row0, long long n) {
+        return vg_f32_to_bf16_tm_launch(c->d_rows, row0, n, c->stride, c->dim, c->d_rows_tm, bs, c->stream);
+    });
+}
+// f16 / bf16 corpora: the rows themselves, tile-major (+ 100 % of the corpus in HBM; without it every LDS-DMA instruction gathers
+// 32-byte runs from 32 rows - vg_batch_i8.hip)
+static int ensure_half_tile_major(vg_corpus *c) {
+    return ensure_tile_major(c, c->stride, "tile-major pass", [&](long long row0, long long n) {
+        return vg_tile_major_launch(c->d_rows, row0, n, c->stride, c->d_rows_tm, c->stream);
+    });
 }
 
 // what the batched bf16 filter streams for an f32 corpus: the tile-major shadow copy, else (switched off / no room) the row-major one
@@ -116,29 +94,6 @@ static int ensure_f32_batch_shadow(vg_corpus *c, const uint8_t **rows, int *tile
     const int rc = vg_ensure_bf16_shadow(c);
     if (rc != VG_OK) return rc;
     *rows = c->d_rows_bf; *tiled = 0;
-    return VG_OK;
-}
-
-// f16 / bf16 corpora: the tile-major copy the matrix-core kernel streams (+ 100 % of the corpus in HBM, made at the first batch and
-// extended per appended row; without it every LDS-DMA instruction gathers 32-byte runs from 32 rows - vg_batch_i8.hip).  A corpus
-// it does not fit next to keeps the row-major gather.
-static int ensure_half_tile_major(vg_corpus *c) {
-    if (vg_sw(SW_VG_BATCH_TILE_MAJOR, 1) == 0 || c->tm_disabled) return -1;
-    if (c->tm_cap < c->n_rows) {
-        const int64_t cap = std::max<int64_t>(c->cap_rows, c->n_rows);
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_rows_tm) hipFree(c->d_rows_tm);
-        c->d_rows_tm = nullptr; c->tm_cap = 0; c->tm_rows = 0;
-        const size_t bytes = (size_t)((cap + 31) / 32 * 32) * c->stride;                        // whole tiles
-        if (hipMalloc(&c->d_rows_tm, bytes) != hipSuccess) { (void)hipGetLastError(); c->d_rows_tm = nullptr; c->tm_disabled = true; return -1; }
-        HIP_TRY(hipMemsetAsync(c->d_rows_tm, 0, bytes, c->stream));                             // (rows past the end: defined bytes)
-        c->tm_cap = cap;
-    }
-    if (c->tm_rows < c->n_rows) {
-        int rc = vg_tile_major_launch(c->d_rows, c->tm_rows, c->n_rows - c->tm_rows, c->stride, c->d_rows_tm, c->stream);
-        if (rc != 0) return vg_fail(VG_ERR_HIP, "tile-major pass failed: %s", hipGetErrorString((hipError_t)rc));
-        c->tm_rows = c->n_rows;
-    }
     return VG_OK;
 }
 
@@ -186,22 +141,38 @@ static int ensure_i8_row_stats(vg_corpus *c) {
     return VG_OK;
 }
 
+// ---- what the drivers below share
+// the kernels' view of a metric (none of them serves L1): mode 0 dot, 1 cosine, 2 L2; root: the result is the square root (L2)
+static void batch_mode_root(int metric, int *mode, int *root) {
+    *mode = metric == VG_DIST_DOT ? 0 : (metric == VG_DIST_COSINE ? 1 : 2);
+    *root = metric == VG_DIST_L2 ? 1 : 0;
+}
+// the element type of the rows the exact evaluation reads: 2 f32 (f32_rows: an f32 corpus behind a bf16 / int8 filter), 1 bf16, 0 f16
+static int batch_type_code(const vg_corpus *c, bool f32_rows) { return f32_rows ? 2 : (c->vtype == VG_TYPE_BF16 ? 1 : 0); }
+// one list of a query - ascending, VG_KEY_EMPTY padded, slots < k - to `out`; the keys it held
+static int unpack_list(const uint64_t *list, int k, uint64_t *out) {
+    int cnt = 0;
+    while (cnt < k && list[cnt] != VG_KEY_EMPTY) { out[cnt] = list[cnt]; ++cnt; }
+    return cnt;
+}
+// nq such lists `src_pitch` keys apart (d_bkeys on the host: 64) -> out_keys at pitch k + out_counts
+static void unpack_keys(const uint64_t *src, size_t src_pitch, int nq, int k, uint64_t *out_keys, int *out_counts) {
+    for (int i = 0; i < nq; ++i) out_counts[i] = unpack_list(src + (size_t)i * src_pitch, k, out_keys + (size_t)i * k);
+}
+// the queries a filter could not judge (Inf / NaN elements, a norm of zero or out of range): a single scan each
+static int rescan_unjudged(vg_corpus *c, int metric, const void *queries, const std::vector<int> &unjudged, int k, uint64_t *out_keys,
+                           int *out_counts) {
+    const size_t row_bytes = (size_t)c->dim * c->es;
+    for (int i : unjudged)
+        VG_TRY(vg_scan_topk_keys(c, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, out_keys + (size_t)i * k, out_counts + i));
+    return VG_OK;
+}
+
 // ---- rows of 1025 .. 3072 elements (f16 / bf16 corpora; f32 corpora through their bf16 shadow copy): vg_batch_hl.hip, the K dimension
 // split over the four wavefronts of a workgroup.  Always the split form (filter kernel -> candidate pairs -> exact evaluation) and always
 // from the tile-major copy; a batch whose pairs overflow a region (data the filter cannot separate, queries with Inf / NaN) is answered by
 // the multi-query scan, and so are the next ones over this corpus.
-extern "C" int vg_batch_hl_serves(long long stride_bytes, int k);
-extern "C" int vg_batch_hl_queries_per_block(long long stride_bytes);
-extern "C" int vg_batch_hl_regions(long long stride_bytes, int nq_pad, int npart);
-extern "C" int vg_batch_hl_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, int dim, int type_code,
-                                  const uint8_t *dev_xrows, long long xstride_bytes,
-                                  const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int mode, int root,
-                                  const float *dev_row_nn, const float *dev_query_nn, uint64_t *dev_cand, int npart,
-                                  uint64_t *dev_out_keys, unsigned long long *dev_evals,
-                                  uint64_t *dev_pairs, uint32_t *dev_pair_counts, int pair_cap, hipStream_t stream);
-extern "C" int vg_batch_hl_query_norms(const uint8_t *dev_queries, long long stride_bytes, int dim, int type_code, int nq_real, int nq_pad,
-                                       float *dev_out, hipStream_t stream);
-static long long batch_long_stride(const vg_corpus *c) { return c->vtype == VG_TYPE_F32 ? bf16_shadow_stride(c) : c->stride; }
+static long long batch_long_stride(const vg_corpus *c) { return c->vtype == VG_TYPE_F32 ? vg_bf16_shadow_stride(c) : c->stride; }
 static bool batch_long_eligible(const vg_corpus *c, int metric, int k) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || vg_sw(SW_VG_BATCH_LONG, 1) == 0 || metric == VG_DIST_L1 || c->tm_disabled) return false;
     if (c->vtype != VG_TYPE_F32 && c->vtype != VG_TYPE_F16 && c->vtype != VG_TYPE_BF16) return false;
@@ -229,54 +200,32 @@ static int scan_topk_batch_long(vg_corpus *c, int metric, const void *queries, i
     const size_t qrows = (size_t)nq_pad * c->stride, qbytes = qrows + (size_t)nq_pad * sizeof(float);      // the query rows, then their norms
     const size_t candbytes = (size_t)nq_pad * vg_batch_lists_per_query(c->n_rows, npart) * 64 * sizeof(uint64_t);
     const size_t keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
-    if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
-                                HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
-    if (c->bcand_bytes < candbytes) { if (c->d_bcand) hipFree(c->d_bcand); c->d_bcand = nullptr; c->bcand_bytes = 0;
-                                      HIP_TRY(hipMalloc(&c->d_bcand, candbytes)); c->bcand_bytes = candbytes; }
-    if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
-                                     HIP_TRY(hipMalloc(&c->d_bkeys, keybytes)); c->bkeys_bytes = keybytes; }
     const int n_regions = vg_batch_hl_regions(fstride, nq_pad, npart);
-    const size_t need = (size_t)n_regions * VG_BPAIR_CAP_LONG * sizeof(uint64_t), needc = ((size_t)n_regions + 1) * sizeof(uint32_t);
-    if (c->bpairs_bytes < need) { if (c->d_bpairs) hipFree(c->d_bpairs); c->d_bpairs = nullptr; c->bpairs_bytes = 0;
-                                  HIP_TRY(hipMalloc(&c->d_bpairs, need)); c->bpairs_bytes = need; }
-    if (c->bpcount_bytes < needc) { if (c->d_bpcounts) hipFree(c->d_bpcounts); c->d_bpcounts = nullptr; c->bpcount_bytes = 0;
-                                    HIP_TRY(hipMalloc(&c->d_bpcounts, needc)); c->bpcount_bytes = needc; }
+    VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, qbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bcand, &c->bcand_bytes, candbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bkeys, &c->bkeys_bytes, keybytes));
+    VG_TRY(vg_dev_reserve(&c->d_bpairs, &c->bpairs_bytes, (size_t)n_regions * VG_BPAIR_CAP_LONG * sizeof(uint64_t)));
+    VG_TRY(vg_dev_reserve(&c->d_bpcounts, &c->bpcount_bytes, ((size_t)n_regions + 1) * sizeof(uint32_t)));
     // the queries go up through a PINNED buffer of the corpus (zero-padded rows of the corpus stride, zero rows up to nq_pad; the
     // per-query norms come back through its tail): a pageable source is staged by the runtime at a fraction of the link's rate, and
     // at 1024 x 6 KB that, a zero-filled vector and a scalar norm loop on the host were 1.35 ms of every batch (profiles/r8l)
-    const size_t row_bytes = (size_t)c->dim * c->es;
-    if (c->h_bq_bytes < qbytes) {
-        if (c->h_bq) hipHostFree(c->h_bq);
-        c->h_bq = nullptr; c->h_bq_bytes = 0;
-        HIP_TRY(hipHostMalloc(&c->h_bq, qbytes));
-        c->h_bq_bytes = qbytes;
-    }
-    if (row_bytes == (size_t)c->stride) memcpy(c->h_bq, queries, (size_t)nq * row_bytes);
-    else
-        for (int i = 0; i < nq; ++i) {
-            memcpy(c->h_bq + (size_t)i * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
-            memset(c->h_bq + (size_t)i * c->stride + row_bytes, 0, (size_t)c->stride - row_bytes);
-        }
-    if (nq_pad > nq) memset(c->h_bq + (size_t)nq * c->stride, 0, (size_t)(nq_pad - nq) * c->stride);
+    VG_TRY(vg_reserve_h_bq(c, qbytes));
+    vg_stage_queries(c->h_bq, queries, nq, nq_pad, (size_t)c->stride, (size_t)c->dim * c->es);
     HIP_TRY(hipMemcpyAsync(c->d_bq, c->h_bq, qrows, hipMemcpyHostToDevice, c->stream));
     // sum q^2 per query, on the device.  A query the filter cannot judge (Inf / NaN elements, a norm of zero or out of range) would
     // send EVERY row down the exact path - in the split form that is a pair per row: its norm comes out as -1, the kernels multiply it as
     // zero and let none of its pairs pass, and it is answered by a single scan below
     float *dev_qnn = reinterpret_cast<float *>((uint8_t *)c->d_bq + qrows);
+    const int type_code = batch_type_code(c, f32);
     {
-        const int rcq = vg_batch_hl_query_norms((const uint8_t *)c->d_bq, c->stride, c->dim, f32 ? 2 : (c->vtype == VG_TYPE_BF16 ? 1 : 0), nq, nq_pad, dev_qnn, c->stream);
+        const int rcq = vg_batch_hl_query_norms((const uint8_t *)c->d_bq, c->stride, c->dim, type_code, nq, nq_pad, dev_qnn, c->stream);
         if (rcq != 0) return vg_fail(VG_ERR_HIP, "query norm pass failed: %s", hipGetErrorString((hipError_t)rcq));
     }
-    hipEvent_t *evs = nullptr;
-    if (c->profiling) {
-        int slot = (int)(c->prof_launches % VG_PROF_RING);
-        evs = &c->ev[(size_t)slot * VG_PROF_EVS];
-        c->ev_flags[(size_t)slot] = 0;
-        ++c->prof_launches;
-        hipEventRecord(evs[0], c->stream);
-    }
-    const int mode = metric == VG_DIST_DOT ? 0 : (metric == VG_DIST_COSINE ? 1 : 2), root = metric == VG_DIST_L2 ? 1 : 0;
-    const int rc = vg_batch_hl_launch(c->d_rows_tm, c->n_rows, fstride, c->dim, f32 ? 2 : (c->vtype == VG_TYPE_BF16 ? 1 : 0), c->d_rows, c->stride,
+    hipEvent_t *evs = vg_prof_slot(c, 0);
+    if (evs) hipEventRecord(evs[0], c->stream);
+    int mode, root;
+    batch_mode_root(metric, &mode, &root);
+    const int rc = vg_batch_hl_launch(c->d_rows_tm, c->n_rows, fstride, c->dim, type_code, c->d_rows, c->stride,
                                       (const uint8_t *)c->d_bq, nq_pad, nq, k, mode, root, c->d_xnorm, dev_qnn,
                                       c->d_bcand, npart, c->d_bkeys, nullptr, c->d_bpairs, c->d_bpcounts, VG_BPAIR_CAP_LONG, c->stream);
     if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
@@ -293,45 +242,13 @@ static int scan_topk_batch_long(vg_corpus *c, int metric, const void *queries, i
     if (overflow != 0) { c->blong_cooldown = 16; return -1; }   // (rows the filter cannot separate / judge: the next batches scan)
     std::vector<int> unjudged;
     for (int i = 0; i < nq; ++i) if (h_qnn[i] < 0.0f) unjudged.push_back(i);
-    for (int i = 0; i < nq; ++i) {
-        int cnt = 0;
-        for (int j = 0; j < k; ++j) {
-            const uint64_t key = keys[(size_t)i * 64 + j];
-            if (key == VG_EMPTY_KEY) break;
-            out_keys[(size_t)i * k + cnt] = key;
-            ++cnt;
-        }
-        out_counts[i] = cnt;
-    }
-    for (int i : unjudged) {
-        const int rc1 = vg_scan_topk_keys(c, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, out_keys + (size_t)i * k, out_counts + i);
-        if (rc1 != VG_OK) return rc1;
-    }
-    return VG_OK;
+    unpack_keys(keys.data(), 64, nq, k, out_keys, out_counts);
+    return rescan_unjudged(c, metric, queries, unjudged, k, out_keys, out_counts);
 }
 
 // ---- f32 corpora, large batches: the INTEGER matrix cores as the filter over the int8 shadow copy (vg_batch_q8.hip) - 64 queries per
 // wavefront, a quarter of the corpus' bytes streamed, the single scan's f32 arithmetic for the pairs that pass.  Default for every batch
 // (round 5: from 257 queries on) over corpora the filter scans' policy covers; VG_BATCH_Q8=0 / 1 forces it off / on.
-extern "C" int vg_batch_q8_serves(long long q8stride_bytes, long long xstride_bytes, int k);
-extern "C" int vg_batch_q8_queries_per_block(void);
-extern "C" int vg_batch_q8_padded_queries(int nq, long long q8stride_bytes);
-extern "C" int vg_batch_q8_max_partitions(void);
-extern "C" int vg_batch_q8_regions(int nq_pad, int npart);
-extern "C" size_t vg_batch_q8_work_bytes(int nq_pad, long long q8stride_bytes, long long xstride_bytes);
-extern "C" size_t vg_batch_q8_work_stat_offset(int nq_pad, long long q8stride_bytes, long long xstride_bytes);
-extern "C" size_t vg_batch_q8_work_perm_offset(int nq_pad, long long q8stride_bytes, long long xstride_bytes);
-extern "C" int vg_batch_q8_max_queries(void);
-extern "C" int vg_q8_rstat_launch(const void *dev_q8stat, const float *dev_xnorm, long long row0, long long n, void *dev_out, int nn_squared, hipStream_t stream);
-extern "C" int vg_batch_q8_launch(const uint8_t *dev_rows_tm, const void *dev_rstat, long long n_rows, long long q8stride, int dim,
-                                  const uint8_t *dev_xrows, long long xstride, const float *dev_xnorm,
-                                  const uint8_t *dev_xqueries, void *dev_qwork, int nq_pad, int nq_real, int k, int mode, int root,
-                                  uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, unsigned long long *dev_evals,
-                                  uint64_t *dev_pairs, uint32_t *dev_pair_counts, int pair_cap, int type_code, hipStream_t stream);
-extern "C" int vg_batch_q8_workgroups_per_cu(long long q8stride_bytes);
-extern "C" size_t vg_batch_q8_pack_bytes(int nq_pad, int k);
-extern "C" int vg_batch_q8_pack_launch(const uint64_t *dev_keys, const void *dev_qwork, int nq_pad, long long q8stride, long long xstride, int k,
-                                       const uint32_t *dev_overflow_flag, const unsigned long long *dev_evals, void *dev_out, hipStream_t stream);
 static long long q8_shadow_stride_of(const vg_corpus *c) { return (((long long)c->dim + 15) / 16) * 16; }
 static bool batch_q8_eligible(const vg_corpus *c, int metric, int k, int nq) {
     const bool served_type = c->vtype == VG_TYPE_F32 || c->vtype == VG_TYPE_F16 || c->vtype == VG_TYPE_BF16;   // (the int8 image of the row, whatever it is stored as)
@@ -396,50 +313,27 @@ static int scan_topk_batch_q8(vg_corpus *c, int metric, const void *queries, int
     const size_t qrows = (size_t)nq_pad * c->stride, qbytes = qrows + vg_batch_q8_work_bytes(nq_pad, qs, c->stride);
     const size_t candbytes = (size_t)nq_pad * std::max(npart, 64) * 64 * sizeof(uint64_t);
     const size_t keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
-    if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
-                                HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
-    if (c->bcand_bytes < candbytes) { if (c->d_bcand) hipFree(c->d_bcand); c->d_bcand = nullptr; c->bcand_bytes = 0;
-                                      HIP_TRY(hipMalloc(&c->d_bcand, candbytes)); c->bcand_bytes = candbytes; }
-    if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
-                                     HIP_TRY(hipMalloc(&c->d_bkeys, keybytes)); c->bkeys_bytes = keybytes; }
     const int n_regions = vg_batch_q8_regions(nq_pad, npart);
-    const size_t need = (size_t)n_regions * VG_BPAIR_CAP * sizeof(uint64_t), needc = ((size_t)n_regions + 1) * sizeof(uint32_t);
-    if (c->bpairs_bytes < need) { if (c->d_bpairs) hipFree(c->d_bpairs); c->d_bpairs = nullptr; c->bpairs_bytes = 0;
-                                  HIP_TRY(hipMalloc(&c->d_bpairs, need)); c->bpairs_bytes = need; }
-    if (c->bpcount_bytes < needc) { if (c->d_bpcounts) hipFree(c->d_bpcounts); c->d_bpcounts = nullptr; c->bpcount_bytes = 0;
-                                    HIP_TRY(hipMalloc(&c->d_bpcounts, needc)); c->bpcount_bytes = needc; }
+    VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, qbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bcand, &c->bcand_bytes, candbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bkeys, &c->bkeys_bytes, keybytes));
+    VG_TRY(vg_dev_reserve(&c->d_bpairs, &c->bpairs_bytes, (size_t)n_regions * VG_BPAIR_CAP * sizeof(uint64_t)));
+    VG_TRY(vg_dev_reserve(&c->d_bpcounts, &c->bpcount_bytes, ((size_t)n_regions + 1) * sizeof(uint32_t)));
     // the f32 queries go up through the corpus' pinned buffer: zero-padded rows of the corpus stride, zero rows up to nq_pad; the queries'
     // statistics (which of them the filter could judge) come back through its tail
     const size_t packbytes = vg_batch_q8_pack_bytes(nq_pad, k);                              // what comes back, packed by the device: one copy
-    const size_t row_bytes = (size_t)c->dim * c->es, statbytes = (packbytes + 15) / 16 * 16;
-    if (c->h_bq_bytes < qrows + statbytes) {
-        if (c->h_bq) hipHostFree(c->h_bq);
-        c->h_bq = nullptr; c->h_bq_bytes = 0;
-        HIP_TRY(hipHostMalloc(&c->h_bq, qrows + statbytes));
-        c->h_bq_bytes = qrows + statbytes;
-    }
-    if (row_bytes == (size_t)c->stride) memcpy(c->h_bq, queries, (size_t)nq * row_bytes);
-    else
-        for (int i = 0; i < nq; ++i) {
-            memcpy(c->h_bq + (size_t)i * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
-            memset(c->h_bq + (size_t)i * c->stride + row_bytes, 0, (size_t)c->stride - row_bytes);
-        }
-    if (nq_pad > nq) memset(c->h_bq + (size_t)nq * c->stride, 0, (size_t)(nq_pad - nq) * c->stride);
+    VG_TRY(vg_reserve_h_bq(c, qrows + (packbytes + 15) / 16 * 16));
+    vg_stage_queries(c->h_bq, queries, nq, nq_pad, (size_t)c->stride, (size_t)c->dim * c->es);
     HIP_TRY(hipMemcpyAsync(c->d_bq, c->h_bq, qrows, hipMemcpyHostToDevice, c->stream));
-    hipEvent_t *evs = nullptr;
-    if (c->profiling) {
-        int slot = (int)(c->prof_launches % VG_PROF_RING);
-        evs = &c->ev[(size_t)slot * VG_PROF_EVS];
-        c->ev_flags[(size_t)slot] = 0;
-        ++c->prof_launches;
-        hipEventRecord(evs[0], c->stream);
-    }
-    const int mode = metric == VG_DIST_DOT ? 0 : (metric == VG_DIST_COSINE ? 1 : 2), root = metric == VG_DIST_L2 ? 1 : 0;
+    hipEvent_t *evs = vg_prof_slot(c, 0);
+    if (evs) hipEventRecord(evs[0], c->stream);
+    int mode, root;
+    batch_mode_root(metric, &mode, &root);
     uint8_t *qwork = (uint8_t *)c->d_bq + qrows;
     const int rc = vg_batch_q8_launch(c->d_rows_q8tm, c->d_q8tm_stat, c->n_rows, qs, c->dim, c->d_rows, c->stride, c->d_xnorm,
                                       (const uint8_t *)c->d_bq, qwork, nq_pad, nq, k, mode, root, c->d_bcand, npart, c->d_bkeys,
                                       c->d_filter_evals + 1, c->d_bpairs, c->d_bpcounts, VG_BPAIR_CAP,
-                                      c->vtype == VG_TYPE_F32 ? 2 : (c->vtype == VG_TYPE_BF16 ? 1 : 0), c->stream);
+                                      batch_type_code(c, c->vtype == VG_TYPE_F32), c->stream);
     if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
     if (rc == -1) { hipStreamSynchronize(c->stream); c->bq8_status = 2; return -1; }
     if (rc != 0) return vg_fail(VG_ERR_HIP, "batched scan launch (int8 filter) failed: %s", hipGetErrorString((hipError_t)rc));
@@ -458,24 +352,13 @@ static int scan_topk_batch_q8(vg_corpus *c, int metric, const void *queries, int
     const uint32_t *h_judged = h_pack + 4 + nq_pad;
     const uint64_t *keys = reinterpret_cast<const uint64_t *>(h_pack + 4 + 2 * (size_t)nq_pad);
     std::vector<int> unjudged;
-    for (int p = 0; p < nq_pad; ++p) {
+    for (int p = 0; p < nq_pad; ++p) {                                  // (the permuted form of unpack_keys: source pitch k)
         const int i = h_perm[p];
         if (i < 0 || i >= nq) continue;                                 // (padding)
         if (h_judged[p] == 0u) { unjudged.push_back(i); continue; }
-        int cnt = 0;
-        for (int j = 0; j < k; ++j) {
-            const uint64_t key = keys[(size_t)p * k + j];
-            if (key == VG_EMPTY_KEY) break;
-            out_keys[(size_t)i * k + cnt] = key;
-            ++cnt;
-        }
-        out_counts[i] = cnt;
+        out_counts[i] = unpack_list(keys + (size_t)p * k, k, out_keys + (size_t)i * k);
     }
-    for (int i : unjudged) {                                            // queries the filter could not judge (Inf / NaN / zero / out of range): a single scan each
-        const int rc1 = vg_scan_topk_keys(c, metric, (const uint8_t *)queries + (size_t)i * row_bytes, k, out_keys + (size_t)i * k, out_counts + i);
-        if (rc1 != VG_OK) return rc1;
-    }
-    return VG_OK;
+    return rescan_unjudged(c, metric, queries, unjudged, k, out_keys, out_counts);
 }
 
 static bool batch_mfma_eligible(const vg_corpus *c, int metric, int k) {
@@ -504,7 +387,7 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
     }
     const bool half = (c->vtype == VG_TYPE_F16 || c->vtype == VG_TYPE_BF16) || f32_filter;
     c->last_batch_half = half;
-    const long long fstride = f32_filter ? bf16_shadow_stride(c) : c->stride;       // row stride of what the matrix core reads
+    const long long fstride = f32_filter ? vg_bf16_shadow_stride(c) : c->stride;    // row stride of what the matrix core reads
     // f16 / bf16 / f32-through-bf16 batches: the kernel comes as one 8-wavefront workgroup per CU or as two of four (vg_batch_h_plan)
     int h_waves = 8, h_bpc = 1;
     const bool h_split = half && vg_batch_h_split(fstride, k) != 0 && !c->bsplit_off;
@@ -529,28 +412,13 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
     const size_t qbytes = (size_t)nq_pad * c->stride;
     const size_t candbytes = (size_t)nq_pad * vg_batch_lists_per_query(c->n_rows, npart) * 64 * sizeof(uint64_t);
     const size_t keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
-    if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
-                                HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
-    if (c->bcand_bytes < candbytes) { if (c->d_bcand) hipFree(c->d_bcand); c->d_bcand = nullptr; c->bcand_bytes = 0;
-                                      HIP_TRY(hipMalloc(&c->d_bcand, candbytes)); c->bcand_bytes = candbytes; }
-    if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
-                                     HIP_TRY(hipMalloc(&c->d_bkeys, keybytes)); c->bkeys_bytes = keybytes; }
+    VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, qbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bcand, &c->bcand_bytes, candbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bkeys, &c->bkeys_bytes, keybytes));
     // queries: zero-padded rows of the corpus stride, zero rows up to nq_pad - through the corpus' pinned buffer (a pageable source is
-    // staged by the runtime at a fraction of the link's rate)
-    const size_t row_bytes = (size_t)c->dim * c->es;
-    if (c->h_bq_bytes < qbytes) {
-        if (c->h_bq) hipHostFree(c->h_bq);
-        c->h_bq = nullptr; c->h_bq_bytes = 0;
-        HIP_TRY(hipHostMalloc(&c->h_bq, qbytes));
-        c->h_bq_bytes = qbytes;
-    }
-    if (row_bytes == (size_t)c->stride) memcpy(c->h_bq, queries, (size_t)nq * row_bytes);
-    else
-        for (int i = 0; i < nq; ++i) {
-            memcpy(c->h_bq + (size_t)i * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
-            memset(c->h_bq + (size_t)i * c->stride + row_bytes, 0, (size_t)c->stride - row_bytes);
-        }
-    if (nq_pad > nq) memset(c->h_bq + (size_t)nq * c->stride, 0, (size_t)(nq_pad - nq) * c->stride);
+    // staged by the runtime at a fraction of the link's rate).  The copy is enqueued FIRST: the passes below run behind it
+    VG_TRY(vg_reserve_h_bq(c, qbytes));
+    vg_stage_queries(c->h_bq, queries, nq, nq_pad, (size_t)c->stride, (size_t)c->dim * c->es);
     HIP_TRY(hipMemcpyAsync(c->d_bq, c->h_bq, qbytes, hipMemcpyHostToDevice, c->stream));
     if (quantized) {
         int rcn = ensure_i8_row_stats(c);
@@ -564,15 +432,10 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
         if (rcn != VG_OK) return rcn;
     }
 
-    hipEvent_t *evs = nullptr;
-    if (c->profiling) {
-        int slot = (int)(c->prof_launches % VG_PROF_RING);
-        evs = &c->ev[(size_t)slot * VG_PROF_EVS];
-        c->ev_flags[(size_t)slot] = 0;
-        ++c->prof_launches;
-        hipEventRecord(evs[0], c->stream);
-    }
-    const int mode = metric == VG_DIST_DOT ? 0 : (metric == VG_DIST_COSINE ? 1 : 2), root = metric == VG_DIST_L2 ? 1 : 0;
+    hipEvent_t *evs = vg_prof_slot(c, 0);
+    if (evs) hipEventRecord(evs[0], c->stream);
+    int mode, root;
+    batch_mode_root(metric, &mode, &root);
     const uint8_t *hrows = f32_filter ? f32_shadow : c->d_rows;         // what the half-precision kernel's matrix core reads
     int hrows_tiled = f32_filter ? f32_shadow_tiled : 0;
     if (half && !f32_filter) {
@@ -592,22 +455,19 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
             if (rce != VG_OK) return rce;
             dev_evals = c->d_filter_evals + 1;
         }
-        // the split form (vg_batch_h.hip, FILTER kind): one region of VG_BPAIR_CAP candidate pairs per filter wavefront + their counts
+        // the split form (vg_batch_h.hip, FILTER kind): one region of VG_BPAIR_CAP candidate pairs per filter wavefront + their counts.
+        // Buffers that do not fit are no error here: no split form, the fused kernel answers
         uint64_t *dev_pairs = nullptr;
         uint32_t *dev_pair_counts = nullptr;
         const int n_regions = G * npart * h_waves;
         if (h_split && !c->bsplit_off) {
-            const size_t need = (size_t)n_regions * VG_BPAIR_CAP * sizeof(uint64_t), needc = ((size_t)n_regions + 1) * sizeof(uint32_t);
-            if (c->bpairs_bytes < need) { if (c->d_bpairs) hipFree(c->d_bpairs); c->d_bpairs = nullptr; c->bpairs_bytes = 0;
-                                          if (hipMalloc(&c->d_bpairs, need) == hipSuccess) c->bpairs_bytes = need; else (void)hipGetLastError(); }
-            if (c->bpcount_bytes < needc) { if (c->d_bpcounts) hipFree(c->d_bpcounts); c->d_bpcounts = nullptr; c->bpcount_bytes = 0;
-                                            if (hipMalloc(&c->d_bpcounts, needc) == hipSuccess) c->bpcount_bytes = needc; else (void)hipGetLastError(); }
-            if (c->bpairs_bytes >= need && c->bpcount_bytes >= needc) { dev_pairs = c->d_bpairs; dev_pair_counts = c->d_bpcounts; }
+            const bool have_pairs = vg_dev_reserve_optional(&c->d_bpairs, &c->bpairs_bytes, (size_t)n_regions * VG_BPAIR_CAP * sizeof(uint64_t));
+            const bool have_counts = vg_dev_reserve_optional(&c->d_bpcounts, &c->bpcount_bytes, ((size_t)n_regions + 1) * sizeof(uint32_t));
+            if (have_pairs && have_counts) { dev_pairs = c->d_bpairs; dev_pair_counts = c->d_bpcounts; }
         }
-        rc = vg_batch_h_launch(hrows, hrows_tiled, c->n_rows, fstride, c->dim,
-                               f32_filter ? 2 : (c->vtype == VG_TYPE_BF16 ? 1 : 0), c->d_rows, c->stride, (const uint8_t *)c->d_bq,
-                               nq_pad, nq, k, mode, root, c->d_xnorm, c->d_bcand, npart, tiles_per_part, c->d_bkeys, dev_evals, h_waves,
-                               dev_pairs, dev_pair_counts, VG_BPAIR_CAP, c->stream);
+        rc = vg_batch_h_launch(hrows, hrows_tiled, c->n_rows, fstride, c->dim, batch_type_code(c, f32_filter), c->d_rows, c->stride,
+                               (const uint8_t *)c->d_bq, nq_pad, nq, k, mode, root, c->d_xnorm, c->d_bcand, npart, tiles_per_part, c->d_bkeys,
+                               dev_evals, h_waves, dev_pairs, dev_pair_counts, VG_BPAIR_CAP, c->stream);
         if (rc == 0 && dev_pairs) {                      // a region ran full (data the filter cannot separate): the fused kernel answers
             HIP_TRY(hipMemcpyAsync(&split_overflow, dev_pair_counts + n_regions, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             split_used = true;
@@ -628,7 +488,7 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
     vg_collect_timing(c);
     if (split_used && split_overflow != 0) {               // the pair buffer ran full somewhere: this batch again through the fused kernel
         c->bsplit_off = true;                              // (and the next ones: such data keeps doing that)
-        return scan_topk_batch_mfma(c, metric, queries, nq, k, out_keys, out_counts);
+        return scan_topk_batch_mfma(c, metric, queries, nq, k, out_keys, out_counts);   // (from the top, staging included: the fused form pads the batch to its own workgroup width)
     }
     if (f32_filter && f32_mfma_serves) {
         // Selectivity guard.  An exact evaluation occupies a whole wavefront (and stalls its workgroup at the tile barrier):
@@ -640,16 +500,7 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
         if ((now - c->bfilter_evals_seen) > pairs / 256 && vg_sw(SW_VG_F32_FILTER, -1) < 0) c->bfilter_cooldown = 64;
         c->bfilter_evals_seen = now;
     }
-    for (int i = 0; i < nq; ++i) {
-        int cnt = 0;
-        for (int j = 0; j < k; ++j) {
-            uint64_t key = keys[(size_t)i * 64 + j];
-            if (key == VG_EMPTY_KEY) break;
-            out_keys[(size_t)i * k + cnt] = key;
-            ++cnt;
-        }
-        out_counts[i] = cnt;
-    }
+    unpack_keys(keys.data(), 64, nq, k, out_keys, out_counts);
     return VG_OK;
 }
 
@@ -659,13 +510,10 @@ static int scan_topk_batch_multi(vg_corpus *c, int metric, const void *queries, 
     if (NQ == 0) return -1;
     const int ngroups = (nq + NQ - 1) / NQ, nq_pad = ngroups * NQ;
     const size_t qbytes = (size_t)nq_pad * c->stride, keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
-    if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
-                                HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
-    if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
-                                     HIP_TRY(hipMalloc(&c->d_bkeys, keybytes)); c->bkeys_bytes = keybytes; }
-    std::vector<uint8_t> hq(qbytes, 0);                       // zero-padded rows of the corpus stride; pad queries are zero
-    const size_t row_bytes = (size_t)c->dim * c->es;
-    for (int i = 0; i < nq; ++i) memcpy(hq.data() + (size_t)i * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
+    VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, qbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bkeys, &c->bkeys_bytes, keybytes));
+    std::vector<uint8_t> hq(qbytes);                          // zero-padded rows of the corpus stride; pad queries are zero (pageable: this path's own)
+    vg_stage_queries(hq.data(), queries, nq, nq_pad, (size_t)c->stride, (size_t)c->dim * c->es);
     HIP_TRY(hipMemcpyAsync(c->d_bq, hq.data(), qbytes, hipMemcpyHostToDevice, c->stream));
     for (int g = 0; g < ngroups; ++g) {
         int rc = vg_launch_scan_multi(c, metric, (const uint8_t *)c->d_bq + (size_t)g * NQ * c->stride, k, c->d_cand,
@@ -676,17 +524,22 @@ static int scan_topk_batch_multi(vg_corpus *c, int metric, const void *queries, 
     std::vector<uint64_t> keys((size_t)nq * 64);
     HIP_TRY(hipMemcpyAsync(keys.data(), c->d_bkeys, (size_t)nq * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < nq; ++i) {
-        int cnt = 0;
-        for (int j = 0; j < k; ++j) {
-            const uint64_t key = keys[(size_t)i * 64 + j];
-            if (key == VG_KEY_EMPTY) break;
-            out_keys[(size_t)i * k + cnt] = key;
-            ++cnt;
-        }
-        out_counts[i] = cnt;
-    }
+    unpack_keys(keys.data(), 64, nq, k, out_keys, out_counts);
     return VG_OK;
+}
+
+// very large batches go through a driver in slices of `slice` queries (the per-(query, partition) candidate lists are nq x ~128 x
+// 512 B), until a slice does not answer VG_OK.  -1: the driver hands the batch on - the counts are zero again for the next path
+typedef int (*batch_driver_t)(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts);
+static int run_sliced(vg_corpus *c, batch_driver_t driver, int slice, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
+                      int *out_counts) {
+    const size_t qbytes = (size_t)c->dim * c->es;
+    int rc = VG_OK;
+    for (int q0 = 0; q0 < nq && rc == VG_OK; q0 += slice)
+        rc = driver(c, metric, (const uint8_t *)queries + (size_t)q0 * qbytes, std::min(slice, nq - q0), k, out_keys + (size_t)q0 * k, out_counts + q0);
+    if (rc == -1)
+        for (int i = 0; i < nq; ++i) out_counts[i] = 0;
+    return rc;
 }
 
 extern "C" int vg_scan_topk_batch_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
@@ -702,48 +555,29 @@ extern "C" int vg_scan_topk_batch_keys(vg_corpus *c, int metric, const void *que
     // A handful of queries over a corpus the filter scans serve: single scans (0.7 ms each at 10M x 384, whatever the type) beat one
     // 128- / 256-query-wide matrix pass (~2.9 ms however few of its query slots are used) up to three queries; they tie at four.
     const bool few = nq <= vg_sw(SW_VG_BATCH_MIN_QUERIES, 4) - 1 && vg_scan_filter_would_serve(c, metric, k);
+    const int slice_sw = vg_sw(SW_VG_BATCH_SLICE, 4096);
+    // A path in its cool-down (a batch overflowed its pair regions) is not tried: the batch counts the cool-down down instead
     // (the int8 filter first: it serves rows up to 1536 elements too; what it hands back - or does not serve - goes on to the K-split bf16 kernel)
-    if (!few && batch_q8_eligible(c, metric, k, nq) && c->bq8_cooldown > 0) --c->bq8_cooldown;
-    else if (!few && batch_q8_eligible(c, metric, k, nq)) {
-        const int slice = std::min(vg_batch_q8_max_queries(), std::max(512, vg_sw(SW_VG_BATCH_SLICE, 4096)));
-        int rc = VG_OK;
-        const size_t qbytes = (size_t)c->dim * c->es;
-        for (int q0 = 0; q0 < nq && rc == VG_OK; q0 += slice) {
-            const int nqs = std::min(slice, nq - q0);
-            rc = scan_topk_batch_q8(c, metric, (const uint8_t *)queries + (size_t)q0 * qbytes, nqs, k, out_keys + (size_t)q0 * k, out_counts + q0);
-        }
+    const bool q8 = !few && batch_q8_eligible(c, metric, k, nq);
+    if (q8 && c->bq8_cooldown > 0) --c->bq8_cooldown;
+    else if (q8) {
+        const int rc = run_sliced(c, scan_topk_batch_q8, std::min(vg_batch_q8_max_queries(), std::max(512, slice_sw)), metric, queries, nq, k, out_keys, out_counts);
         if (rc != -1) { c->last_batch_path = 7; return rc; }
-        for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     }
-    if (!few && batch_long_eligible(c, metric, k) && c->blong_cooldown > 0) --c->blong_cooldown;
-    else if (!few && batch_long_eligible(c, metric, k)) {
-        const int slice = std::max(256, vg_sw(SW_VG_BATCH_SLICE, 4096));
-        int rc = VG_OK;
-        const size_t qbytes = (size_t)c->dim * c->es;
-        for (int q0 = 0; q0 < nq && rc == VG_OK; q0 += slice) {
-            const int nqs = std::min(slice, nq - q0);
-            rc = scan_topk_batch_long(c, metric, (const uint8_t *)queries + (size_t)q0 * qbytes, nqs, k, out_keys + (size_t)q0 * k, out_counts + q0);
-        }
+    const bool lng = !few && batch_long_eligible(c, metric, k);
+    if (lng && c->blong_cooldown > 0) --c->blong_cooldown;
+    else if (lng) {
+        const int rc = run_sliced(c, scan_topk_batch_long, std::max(256, slice_sw), metric, queries, nq, k, out_keys, out_counts);
         if (rc != -1) { c->last_batch_path = 4; return rc; }
-        for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     }
     if (!few && (batch_mfma_eligible(c, metric, k) || batch_i8_eligible(c, metric, k) || batch_h_eligible(c, metric, k) ||
                  batch_f32_filter_eligible(c, metric, k))) {
-        // very large batches go through in slices: the per-(query, partition) candidate lists are nq x ~128 x 512 B
-        const int slice = std::max(256, vg_sw(SW_VG_BATCH_SLICE, 4096));
-        int rc = VG_OK;
-        const size_t qbytes = (size_t)c->dim * c->es;
-        for (int q0 = 0; q0 < nq && rc == VG_OK; q0 += slice) {
-            const int nqs = std::min(slice, nq - q0);
-            rc = scan_topk_batch_mfma(c, metric, (const uint8_t *)queries + (size_t)q0 * qbytes, nqs, k, out_keys + (size_t)q0 * k,
-                                      out_counts + q0);
-        }
+        const int rc = run_sliced(c, scan_topk_batch_mfma, std::max(256, slice_sw), metric, queries, nq, k, out_keys, out_counts);
         if (rc != -1) {
             const bool quantized = (c->vtype == VG_TYPE_U8 || c->vtype == VG_TYPE_I8);
             c->last_batch_path = quantized ? 2 : ((c->vtype != VG_TYPE_F32 || c->last_batch_half) ? 3 : 1);
             return rc;
         }
-        for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     }
     // shapes the matrix-core kernels do not serve (f16 / bf16, L1, k > 32, rows > 512 floats / 1 KiB): the multi-query
     // scan (vg_scan_multi_kernel: 4 - or 2 for f16 / bf16 - queries share every row load of the HBM-bound pass) ...

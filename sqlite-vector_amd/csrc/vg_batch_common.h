@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "vg_batch_dma.h"
+#include "vg_batch_units.h"
 #include "vg_lists.h"
 #include "vg_switches.h"
 
@@ -71,11 +72,7 @@ static inline int vgb_stage_bounds(long long ntiles, long long pre_tiles, long l
     return n;
 }
 
-// ---- the rest of the host side
-// per query: its lists in the candidate buffer -> the final k keys (vg_batch.hip)
-extern "C" int vg_batch_merge_launch(const uint64_t *dev_cand, int nq_pad, int lists_per_query, int npart, int k,
-                                     uint64_t *dev_out_keys, hipStream_t stream);
-
+// ---- the rest of the host side (the merge of a query's lists: vg_batch_merge_launch, vg_batch_units.h)
 // the k-step counts (32 bytes of a row each) the kernels with 64-k-step register files are instantiated for; 0: not served
 static inline int vgb_ksteps(long long stride_bytes) { return (int)((stride_bytes + 31) / 32); }
 static inline int vgb_ntb64(long long stride_bytes) {

@@ -28,6 +28,7 @@
 #include "vg_accum.h"
 #include "vg_batch_common.h"
 #include "vg_batch_h_defs.h"
+#include "vg_batch_units.h"
 
 
 #ifndef VGH_WAVES
@@ -660,12 +661,6 @@ __global__ __launch_bounds__(64 * W, (W == 4 && VGH_HAS_W4(NTB) && KIND != VGH_F
 #ifndef VGH_TU
 #define VGH_TU 0
 #endif
-extern "C" int vgh_launch_real_f16(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);
-extern "C" int vgh_launch_real_bf16(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);
-extern "C" int vgh_launch_real_f32(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);   // -DVGH_TU=3
-extern "C" int vgh_launch_bound_f16(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);    // -DVGH_TU=2
-extern "C" int vgh_launch_bound_bf16(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);   // -DVGH_TU=4
-extern "C" int vgh_launch_bound_f32(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);    // -DVGH_TU=5
 
 template <int VT, int NTB, int MODE, int BOUND, int W>
 static int launch_h(const BatchArgsH &a, int blocks, size_t smem, hipStream_t stream) {
@@ -765,12 +760,6 @@ extern "C" int vgh_launch_exact_f32(const BatchArgsH *a, int ntb, int waves, int
 }
 #endif
 #if VGH_TU == 0
-extern "C" int vgh_launch_filter_f16(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);
-extern "C" int vgh_launch_filter_bf16(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);
-extern "C" int vgh_launch_filter_f32(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream);
-extern "C" int vgh_launch_exact_f16(const BatchArgsH *a, int ntb, int waves, int regions, size_t smem, hipStream_t stream);
-extern "C" int vgh_launch_exact_bf16(const BatchArgsH *a, int ntb, int waves, int regions, size_t smem, hipStream_t stream);
-extern "C" int vgh_launch_exact_f32(const BatchArgsH *a, int ntb, int waves, int regions, size_t smem, hipStream_t stream);
 extern "C" int vgh_launch_real_f16(const BatchArgsH *a, int ntb, int waves, int blocks, size_t smem, hipStream_t stream) {
     return launch_h_ntb<T_F16, VGH_REAL>(*a, ntb, waves, blocks, smem, stream);
 }

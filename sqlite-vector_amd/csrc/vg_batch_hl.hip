@@ -31,6 +31,7 @@
 #include "vg_accum.h"
 #include "vg_batch_common.h"
 #include "vg_batch_h_defs.h"
+#include "vg_batch_units.h"
 
 #define VGHL_WAVES 4
 #define VGHL_QS(NTBP) ((NTBP) <= 24 ? 2 : 1)     // (two sets at 32 k-steps = 256 registers of A: the gate spills, its reloads drain the load ring)
@@ -425,16 +426,6 @@ static int launch_hlx(const BatchArgsH &a, int sets, int blocks, size_t smem, hi
     if (xu <= 12) return launch_hlx_mode<VT, 12>(a, sets, blocks, smem, stream, subs_given);
     return -1;
 }
-
-extern "C" int vghl_bound_f16(const BatchArgsH *a, int ntbp, int blocks, size_t smem, hipStream_t stream);       // -DVGHL_TU=0 (+ the entry point)
-extern "C" int vghl_filter_f16(const BatchArgsH *a, int ntbp, int blocks, size_t smem, hipStream_t stream);      // 1 (+ the exact kernel)
-extern "C" int vghl_bound_bf16(const BatchArgsH *a, int ntbp, int blocks, size_t smem, hipStream_t stream);      // 2
-extern "C" int vghl_filter_bf16(const BatchArgsH *a, int ntbp, int blocks, size_t smem, hipStream_t stream);     // 3
-extern "C" int vghl_bound_f32(const BatchArgsH *a, int ntbp, int blocks, size_t smem, hipStream_t stream);       // 4
-extern "C" int vghl_filter_f32(const BatchArgsH *a, int ntbp, int blocks, size_t smem, hipStream_t stream);      // 5
-extern "C" int vghl_exact_f16(const BatchArgsH *a, int sets, int blocks, size_t smem, hipStream_t stream);
-extern "C" int vghl_exact_bf16(const BatchArgsH *a, int sets, int blocks, size_t smem, hipStream_t stream);
-extern "C" int vghl_exact_f32(const BatchArgsH *a, int sets, int blocks, size_t smem, hipStream_t stream);
 
 #if VGHL_TU == 1
 extern "C" int vghl_filter_f16(const BatchArgsH *a, int ntbp, int blocks, size_t smem, hipStream_t stream) { return launch_hl<T_F16, VGH_FILTER>(*a, ntbp, blocks, smem, stream); }

@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "vg_batch_common.h"
+#include "vg_batch_units.h"
 
 #ifndef VGI_WAVES
 #define VGI_WAVES 8                     // two wavefronts per SIMD
@@ -609,9 +610,6 @@ extern "C" int vg_i8_rowstat_launch(const uint8_t *dev_rows, long long row0, lon
 // The kernel instantiations are split over two translation units compiled from this file (build.py): the real-pass
 // kernels here, the PRE kernels with -DVGI_TU_PRE (vg_batch_i8_pre.o); -DVGI_TU_ALL: both in this one unit (the
 // measurement builds of tools/build_i8_variants.sh).
-extern "C" int vgi_launch_pre(const BatchArgsI8 *a, int ntb, int blocks, size_t smem, hipStream_t stream);
-extern "C" int vgi_launch_real(const BatchArgsI8 *a, int ntb, int blocks, size_t smem, hipStream_t stream);
-
 // LDS bytes of one workgroup: tile buffers (+ the tiles' row sums), the queries' sums and thresholds, the lists
 static size_t vgi_lds(int NTB, int k, int nbuf) {
     const size_t waves = (size_t)VGI_WAVES_OF(NTB);

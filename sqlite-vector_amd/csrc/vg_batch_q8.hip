@@ -36,6 +36,7 @@
 #include "vg_accum.h"
 #include "vg_batch_common.h"
 #include "vg_batch_h_defs.h"
+#include "vg_batch_units.h"
 
 #define VGQ_WAVES 4                     // one wavefront per SIMD; two workgroups per CU
 #define VGQ_QS 2                        // query sets of 32 per wavefront
@@ -1036,14 +1037,6 @@ static int vgq_ntb(long long stride_bytes) {
 static size_t vgq_lds_bytes(int NTB) {
     return (size_t)VGQ_RING_OF(NTB) * NTB * 1024 + (size_t)VGQ_STAT_SLOTS * 1024 + (size_t)VGQ_WAVES * 64 * 16 + (size_t)VGQ_WAVES * 128 * 8 + (size_t)VGQ_WAVES * VGQ_QCAP * 160;
 }
-
-extern "C" int vgh_launch_exact_f32(const BatchArgsH *a, int ntb, int waves, int regions, size_t smem, hipStream_t stream);   // vg_batch_h.hip (-DVGH_TU=8)
-extern "C" int vgh_launch_exact_f16(const BatchArgsH *a, int ntb, int waves, int regions, size_t smem, hipStream_t stream);   // (-DVGH_TU=6)
-extern "C" int vgh_launch_exact_bf16(const BatchArgsH *a, int ntb, int waves, int regions, size_t smem, hipStream_t stream);  // (-DVGH_TU=7)
-// the same kernel with more chunks per lane (rows beyond 4 KiB f32 / 2 KiB f16 - bf16): vg_batch_hl.hip's instantiations
-extern "C" int vghl_exact_regions_f16(const BatchArgsH *a, int waves, int regions, size_t smem, hipStream_t stream);
-extern "C" int vghl_exact_regions_bf16(const BatchArgsH *a, int waves, int regions, size_t smem, hipStream_t stream);
-extern "C" int vghl_exact_regions_f32(const BatchArgsH *a, int waves, int regions, size_t smem, hipStream_t stream);
 
 // does the int8 batch filter serve rows of q8stride_bytes int8 elements (xstride_bytes: the f32 rows) with lists of k?
 extern "C" int vg_batch_q8_serves(long long q8stride_bytes, long long xstride_bytes, int k) {

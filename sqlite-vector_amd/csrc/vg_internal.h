@@ -215,7 +215,53 @@ struct vg_corpus {
     long long pass_rows[3] = {0, 0, 0};
 };
 
-#include "vg_switches.h"            // the environment switches: vg_sw(SW_..., default)
+#define VG_TRY(expr) do { const int rc__ = (expr); if (rc__ != VG_OK) return rc__; } while (0)   // a VG_* code other than VG_OK: return it
+
+// ---- the handle's grow-only work buffers (d_bq, d_bcand, d_bkeys, d_bpairs, d_bpcounts, d_wb ...): *p holds at least `need` bytes
+// and *have says how many.  Large enough: nothing to do; else the old buffer is freed - what it held is NOT carried over - and one of
+// `need` bytes allocated.  After a failed allocation *p is null and *have 0
+template <class T> static inline hipError_t vg_dev_regrow(T **p, size_t *have, size_t need) {
+    if (*have >= need) return hipSuccess;
+    if (*p) hipFree(*p);
+    *p = nullptr; *have = 0;
+    const hipError_t e = hipMalloc(p, need);
+    if (e == hipSuccess) *have = need;
+    else *p = nullptr;
+    return e;
+}
+// ... where the caller cannot go on without the buffer: VG_OK, or VG_ERR_NOMEM / VG_ERR_HIP with the message set
+template <class T> static inline int vg_dev_reserve(T **p, size_t *have, size_t need) {
+    HIP_TRY(vg_dev_regrow(p, have, need));
+    return VG_OK;
+}
+// ... where it can (a form of the kernel that needs no such buffer): false - not available, the HIP error cleared, nothing reported
+template <class T> static inline bool vg_dev_reserve_optional(T **p, size_t *have, size_t need) {
+    if (vg_dev_regrow(p, have, need) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+// h_bq, the pinned buffer the batch drivers stage their queries in (small results come back through its tail): the same rule
+static inline int vg_reserve_h_bq(vg_corpus *c, size_t need) {
+    if (c->h_bq_bytes >= need) return VG_OK;
+    if (c->h_bq) hipHostFree(c->h_bq);
+    c->h_bq = nullptr; c->h_bq_bytes = 0;
+    HIP_TRY(hipHostMalloc(&c->h_bq, need));
+    c->h_bq_bytes = need;
+    return VG_OK;
+}
+// nq queries of row_bytes each, back to back -> dst as nq_pad rows of `stride` bytes, the layout every batch kernel reads at d_bq:
+// a row zero-padded to the stride, rows [nq, nq_pad) zero
+static inline void vg_stage_queries(uint8_t *dst, const void *queries, int nq, int nq_pad, size_t stride, size_t row_bytes) {
+    if (row_bytes == stride) memcpy(dst, queries, (size_t)nq * row_bytes);
+    else
+        for (int i = 0; i < nq; ++i) {
+            memcpy(dst + (size_t)i * stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
+            memset(dst + (size_t)i * stride + row_bytes, 0, stride - row_bytes);
+        }
+    if (nq_pad > nq) memset(dst + (size_t)nq * stride, 0, (size_t)(nq_pad - nq) * stride);
+}
+
+#include "vg_switches.h"           // the environment switches: vg_sw(SW_..., default)
 
 // What one scan launch covers.  n_rows < 0: the whole corpus; a prefix otherwise (the filter scan's plain pre-pass).
 struct ScanPlan {

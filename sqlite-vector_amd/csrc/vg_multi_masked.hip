@@ -109,10 +109,8 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
     // (a grouped form: a query's 64 keys are followed by their 64 labels, so its pitch in d_bkeys is VG_KEYS_BYTES)
     const size_t kpitch = grouped ? VG_KEYS_BYTES / sizeof(uint64_t) : 64;
     const size_t qbytes = lb_off + (qlab ? (size_t)slice * sizeof(uint32_t) : 0), keybytes = (size_t)nq_pad * kpitch * sizeof(uint64_t);
-    if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
-                                HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
-    if (c->bkeys_bytes < keybytes) { if (c->d_bkeys) hipFree(c->d_bkeys); c->d_bkeys = nullptr; c->bkeys_bytes = 0;
-                                     HIP_TRY(hipMalloc(&c->d_bkeys, keybytes)); c->bkeys_bytes = keybytes; }
+    VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, qbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bkeys, &c->bkeys_bytes, keybytes));
     // zero-padded rows of the corpus stride; pad queries are zero.  The whole batch stays on the host until the wait: a slice's copy
     // is ordered behind the passes of the slice in front of it by the stream, its source must not move before it ran
     std::vector<uint8_t> hq((size_t)nq_pad * c->stride, 0);

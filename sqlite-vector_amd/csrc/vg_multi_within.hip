@@ -79,15 +79,6 @@ __global__ void vg_wb_counts_kernel(unsigned long long *regions, long long pitch
     else regions[(long long)i * pitch] = 0ull;
 }
 
-static int ensure_dev(unsigned long long **p, size_t *have, size_t need) {
-    if (*have >= need) return VG_OK;
-    if (*p) hipFree(*p);
-    *p = nullptr; *have = 0;
-    HIP_TRY(hipMalloc(p, need));
-    *have = need;
-    return VG_OK;
-}
-
 // one pass: NQ queries + their descriptors at dev_block.  Asynchronous on the corpus stream.
 static int launch_multi_within(vg_corpus *c, const WbForm &f, int metric, scan_fn_t fn, int NQ, const VgShape &s, const uint8_t *dev_block) {
     const long long blocks = vg_percu_scan_blocks(c, c->n_rows, s);      // the multi-query scan's launch shape
@@ -119,8 +110,7 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
     const int slice = std::min(nq_pad, VG_WB_SLICE);
     const size_t block_bytes = (size_t)NQ * c->stride + (size_t)NQ * sizeof(VgWithinQuery);      // one pass: [NQ queries | NQ descriptors]
     const size_t qbytes = (size_t)(slice / NQ) * block_bytes;
-    if (c->bq_bytes < qbytes) { if (c->d_bq) hipFree(c->d_bq); c->d_bq = nullptr; c->bq_bytes = 0;
-                                HIP_TRY(hipMalloc(&c->d_bq, qbytes)); c->bq_bytes = qbytes; }
+    VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, qbytes));
     if (!c->d_wb_counts) HIP_TRY(hipMalloc(&c->d_wb_counts, (size_t)VG_WB_SLICE * sizeof(unsigned long long)));
     if (!c->h_wb) HIP_TRY(hipHostMalloc(&c->h_wb, (size_t)(VG_WB_SLICE + 8) * sizeof(unsigned long long)));
     // zero-padded rows of the corpus stride; a pad query is zero with no capacity, a radius nothing is below and no label.  The whole batch stays
@@ -138,7 +128,7 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
         int64_t cap = c->wb_cap_init > 0 ? c->wb_cap_init : std::max<int64_t>(VG_WB_MIN_CAP, (int64_t)VG_WITHIN_INITIAL_CAP / nqs);
         cap = std::max<int64_t>(1, std::min<int64_t>(cap, c->n_rows));
         const long long pitch = (long long)cap + 1;
-        int rc = ensure_dev(&c->d_wb, &c->wb_bytes, (size_t)nqs * (size_t)pitch * sizeof(unsigned long long));
+        int rc = vg_dev_reserve(&c->d_wb, &c->wb_bytes, (size_t)nqs * (size_t)pitch * sizeof(unsigned long long));
         if (rc != VG_OK) return rc;
         for (int j = 0; j < nqs; ++j) {
             VgWithinQuery *d = desc_of(q0 + j);
@@ -176,7 +166,7 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
             if (!over) continue;
             size_t words = 0;
             for (int n = 0; n < NQ; ++n) words += (size_t)counts[(size_t)(g + n)] + 1;
-            if ((rc = ensure_dev(&c->d_wb_grow, &c->wb_grow_bytes, words * sizeof(unsigned long long))) != VG_OK) return rc;
+            if ((rc = vg_dev_reserve(&c->d_wb_grow, &c->wb_grow_bytes, words * sizeof(unsigned long long))) != VG_OK) return rc;
             size_t at = 0;
             for (int n = 0; n < NQ; ++n) {
                 VgWithinQuery *d = desc_of(q0 + g + n);
