@@ -1239,7 +1239,8 @@ class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeled
         return bool(lib().vg_batch_h_split_off(self.h))
 
     def last_batch_path(self):
-        """1 f32 matrix-core kernel, 2 int8, 3 half-precision kernel, 4 its long-row form, 5 multi-query scan, 6 one scan per query"""
+        """1 f32 matrix-core kernel, 2 int8, 3 half-precision kernel, 4 its long-row form, 5 multi-query scan, 6 one scan per query,
+        7 int8 matrix-core filter over an f32 / f16 / bf16 corpus, 8 bit vectors (Hamming / Jaccard) on the int8 matrix cores"""
         return lib().vg_batch_last_path(self.h)
 
     def batch_filter_exact_evals(self):

@@ -1,10 +1,10 @@
 // vg_batch_api.hip - host side of the batched scans (vg_scan_topk_batch[_keys]): partition planning, the cached per-row
 // statistics the matrix-core kernels need, query staging, launches of vg_batch.hip (f32) / vg_batch_i8.hip (uint8, int8) /
-// vg_batch_h.hip (f16, bf16), slicing of very large batches; shapes none of them serves go through the multi-query scan
+// vg_batch_h.hip (f16, bf16) / vg_batch_bits.hip (bit vectors), slicing of very large batches; shapes none of them serves go through the multi-query scan
 // (vg_multi.hip) or, last, one single-query scan per query.
 // Layout: the derived copies of the corpus (ensure_*), what the four drivers share (batch_mode_root, batch_type_code, unpack_keys,
 // rescan_unjudged; buffer growth, query staging and the profiling slot are vg_internal.h's), the drivers - scan_topk_batch_long /
-// _q8 / _mfma / _multi - and vg_scan_topk_batch_keys, which tries them in that order through run_sliced.
+// _q8 / _mfma / _bits / _multi - and vg_scan_topk_batch_keys, which tries them in that order through run_sliced.
 #include "vg_internal.h"
 #include "vg_batch_units.h"          // the kernel units' host entry points
 
@@ -504,6 +504,52 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
     return VG_OK;
 }
 
+// ---- packed bit vectors (uint8 corpora, Hamming / Jaccard), batches of VG_BATCH_BITS_MIN_QUERIES queries or more: vg_batch_bits.hip, the
+// integer matrix cores over the rows spread to 0 / 1 bytes on their way into LDS.  The kernel reads c->d_rows itself: no derived copy, no
+// per-row statistic, nothing to keep in step with the rows.  Every distance is the single scan's, bit for bit.
+#define VG_BATCH_BITS_MIN_QUERIES_DEFAULT 64   // (0: never.  Measured, tools/bits_batch_bench.py / DESIGN.md 3.25: at 32 queries over 32-byte rows the multi-query scan still wins)
+static bool batch_bits_eligible(const vg_corpus *c, int metric, int k, int nq) {
+    if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_U8 || !vg_metric_is_bits(metric)) return false;
+    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, VG_BATCH_BITS_MIN_QUERIES_DEFAULT);
+    if (min_q <= 0 || nq < min_q) return false;
+    return vg_batch_bits_lds_bytes(c->stride, k) != 0;                    // k <= 32, rows of up to 128 bytes
+}
+
+static int scan_topk_batch_bits(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts) {
+    const int QPB = vg_batch_bits_queries_per_block();
+    const int nq_pad = ((nq + QPB - 1) / QPB) * QPB;
+    const int G = nq_pad / QPB;
+    // partitions: one workgroup per CU and query group (VG_BATCH_BPC overrides the workgroups per CU, as in scan_topk_batch_mfma), a
+    // multiple of 8 (one per XCD), <= 256
+    int npart = std::max(1, c->cu_count * std::max(1, vg_sw(SW_VG_BATCH_BPC, 1)) / G);
+    if (npart >= 8) npart = (npart / 8) * 8;
+    npart = std::min(npart, 256);
+    npart = (int)std::min<long long>(npart, (c->n_rows + 31) / 32);
+    const size_t qbytes = (size_t)nq_pad * c->stride;
+    const size_t candbytes = (size_t)nq_pad * vg_batch_lists_per_query(c->n_rows, npart) * 64 * sizeof(uint64_t);
+    const size_t keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
+    VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, qbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bcand, &c->bcand_bytes, candbytes));
+    VG_TRY(vg_dev_reserve(&c->d_bkeys, &c->bkeys_bytes, keybytes));
+    // queries: zero-padded rows of the corpus stride, zero rows up to nq_pad - through the corpus' pinned buffer
+    VG_TRY(vg_reserve_h_bq(c, qbytes));
+    vg_stage_queries(c->h_bq, queries, nq, nq_pad, (size_t)c->stride, (size_t)c->dim * c->es);
+    HIP_TRY(hipMemcpyAsync(c->d_bq, c->h_bq, qbytes, hipMemcpyHostToDevice, c->stream));
+    hipEvent_t *evs = vg_prof_slot(c, 0);
+    if (evs) hipEventRecord(evs[0], c->stream);
+    const int rc = vg_batch_bits_launch(c->d_rows, c->n_rows, c->stride, (const uint8_t *)c->d_bq, nq_pad, nq, k,
+                                        metric == VG_DIST_JACCARD ? 1 : 0, c->d_bcand, npart, c->d_bkeys, c->stream);
+    if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
+    if (rc == -1) { hipStreamSynchronize(c->stream); return -1; }
+    if (rc != 0) return vg_fail(VG_ERR_HIP, "batched scan launch (bit vectors) failed: %s", hipGetErrorString((hipError_t)rc));
+    std::vector<uint64_t> keys((size_t)nq * 64);
+    HIP_TRY(hipMemcpyAsync(keys.data(), c->d_bkeys, (size_t)nq * 64 * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    vg_collect_timing(c);
+    unpack_keys(keys.data(), 64, nq, k, out_keys, out_counts);
+    return VG_OK;
+}
+
 // nq queries, NQ per pass of the multi-query scan kernel; all passes are enqueued back to back, one wait at the end
 static int scan_topk_batch_multi(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts) {
     const int NQ = vg_multi_queries_per_pass(c, metric);
@@ -578,6 +624,11 @@ extern "C" int vg_scan_topk_batch_keys(vg_corpus *c, int metric, const void *que
             c->last_batch_path = quantized ? 2 : ((c->vtype != VG_TYPE_F32 || c->last_batch_half) ? 3 : 1);
             return rc;
         }
+    }
+    // bit vectors: the integer matrix cores from VG_BATCH_BITS_MIN_QUERIES queries on (never for a handful: `few` does not apply to them)
+    if (batch_bits_eligible(c, metric, k, nq)) {
+        const int rc = run_sliced(c, scan_topk_batch_bits, std::max(256, slice_sw), metric, queries, nq, k, out_keys, out_counts);
+        if (rc != -1) { c->last_batch_path = 8; return rc; }
     }
     // shapes the matrix-core kernels do not serve (f16 / bf16, L1, k > 32, rows > 512 floats / 1 KiB): the multi-query
     // scan (vg_scan_multi_kernel: 4 - or 2 for f16 / bf16 - queries share every row load of the HBM-bound pass) ...

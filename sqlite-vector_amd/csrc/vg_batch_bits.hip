@@ -1,0 +1,369 @@
+// vg_batch_bits.hip - batched queries over PACKED BIT VECTORS (uint8 rows, VG_DIST_HAMMING / VG_DIST_JACCARD) on the integer matrix
+// cores.  A bit count is a matrix product once the bits are spread to bytes: with i = popcount(q AND x) = the dot product of the two
+// rows seen as 0 / 1 vectors,
+//     Hamming = |q| + |x| - 2 i            Jaccard = (u - i) / u,  u = |q| + |x| - i,  0 when u == 0
+// - exact integers up to the one division the single scan performs too (vg_accum.h, A_HAM / A_JAC), so every pair's distance is the
+// single scan's bit for bit and the lists equal nq separate scans, ties included.  No filter, no re-evaluation stage.
+//
+//   * the work split is vg_batch_i8.hip's: a workgroup = 8 wavefronts x 32 queries = 256 queries x one partition of the corpus,
+//     partitions interleaved over the 8 XCDs, tiles of 32 rows, lists of k <= 32 keys per query in LDS, the barrier-per-tile schedule;
+//   * A (queries) is stationary in registers: a query row of `stride` packed bytes is spread ONCE to 8 * stride bytes of 0 / 1; lane
+//     (x, h) keeps the 16 values of bits [32t + 16h, +16) of query x in areg[t]; NTB = stride / 4 k-steps <= 32 (128 VGPRs).  Signed
+//     bytes 0 / 1: no sign flip, no correction term;
+//   * B (rows) is read from the corpus ITSELF: 32 consecutive row-major rows are 32 * stride contiguous bytes.  No tile-major copy, no
+//     shadow copy, no cached per-row statistic - nothing to patch when rows change.  LPR lanes share a row; each loads 8 packed bytes
+//     of the NEXT tile (one global_load_dwordx2: 4 KB of HBM per tile at 128-byte rows), spreads each 16 bits to a 16-byte chunk -
+//     per output dword: 4 bits out (v_bfe_u32), times 0x00204081 (v_mul_u32_u24: the four copies of the nibble do not overlap, bit j
+//     lands on bit 8j), AND 0x01010101 - and stores it with ds_write_b128 into the other tile buffer, in the i8 kernel's layout
+//     (transposed by 16-byte chunk: chunk column c of the 32 rows at c * 512 + row * 16; one ds_read_b128 feeds one MFMA).  The same
+//     lanes count their bits (v_bcnt) and a butterfly over the LPR lanes leaves |x| of the 32 rows in LDS next to the tile;
+//   * rows past n_rows are not loaded (they spread as zeros) and never offered to a list;
+//   * the gate is an integer margin on the raw accumulator for Hamming (2 i + ng - |x| >= 0, exact) and an integer product test without
+//     a division for Jaccard (it cannot reject a pair whose float distance is below the threshold); survivors get the
+//     exact distance - the expressions of vg_accum.h - and go through vgb_list_insert;
+//   * large corpora: the pre-pass and the staged real passes of vg_batch_common.h.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstdlib>
+#include <type_traits>
+
+#include "vg_batch_common.h"
+#include "vg_batch_units.h"
+
+#define VGBB_WAVES 8
+#define VGBB_QPW 32
+#define VGBB_QPB (VGBB_WAVES * VGBB_QPW)
+#define VGBB_TILE 32
+#define VGBB_MAX_K 32
+#define VGBB_BPIPE 4                    // B-operand register quads in flight
+
+struct BatchArgsBits {
+    const uint8_t *rows;      // the corpus' own row-major rows: `stride` packed bytes each
+    const uint8_t *queries;   // nq_pad x stride packed bytes, zero padded
+    uint64_t *cand;
+    long long n_rows;
+    long long stride;         // bytes per row (multiple of 16, <= 128)
+    int nq_pad, nq_real, npart, k;   // queries [nq_real, nq_pad) are padding
+    int tiles_per_part;
+    long long tile_begin, tile_end;
+    int part_base, npart_total;
+    const uint64_t *init_keys;
+    int seed;                 // staged real passes (vg_batch_common.h): partition 0 starts its lists from init_keys
+};
+
+// bits 0 .. 15 of v -> 16 bytes of 0 / 1, byte j of dword d = bit 4d + j
+__device__ __forceinline__ vgb_i32x4 vgbb_spread16(uint32_t v) {
+    vgb_i32x4 o;
+    o[0] = (int)(__umul24(__builtin_amdgcn_ubfe(v, 0, 4), 0x00204081u) & 0x01010101u);
+    o[1] = (int)(__umul24(__builtin_amdgcn_ubfe(v, 4, 4), 0x00204081u) & 0x01010101u);
+    o[2] = (int)(__umul24(__builtin_amdgcn_ubfe(v, 8, 4), 0x00204081u) & 0x01010101u);
+    o[3] = (int)(__umul24(__builtin_amdgcn_ubfe(v, 12, 4), 0x00204081u) & 0x01010101u);
+    return o;
+}
+
+// NTB = k-steps per row (32 bits = 4 packed bytes each): rows up to 4 * NTB bytes, shorter ones zero-padded in the k dimension
+// JAC = Jaccard (else Hamming); PRE = the pre-pass variant (vg_batch_i8.hip): only the smallest distance of a query in a tile enters
+template <int NTB, bool JAC, bool PRE>
+__global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(BatchArgsBits a) {
+    constexpr int THREADS = 64 * VGBB_WAVES;
+    constexpr int TILE_BYTES = NTB * 1024;                      // 32 rows x 32 NTB spread bytes
+    constexpr int LPR = NTB <= 8 ? 4 : (NTB <= 16 ? 8 : 16);   // lanes that share a row of the packed tile, 8 bytes each
+    constexpr int SPREADERS = VGBB_TILE * LPR;                  // threads that load and spread (whole wavefronts: 128 / 256 / 512)
+    static_assert(NTB % 4 == 0 && NTB >= 2 * VGBB_BPIPE && NTB <= 32 && LPR * 8 >= NTB * 4, "row ladder");
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint8_t *tile0 = smem;                                                               // 2 tile buffers
+    uint32_t *xcnt_lds = reinterpret_cast<uint32_t *>(smem + 2 * TILE_BYTES);            // [2][32]: |x| of a buffer's rows
+    uint32_t *qcnt_lds = xcnt_lds + 2 * VGBB_TILE;                                       // [waves][32]: |q|
+    float *thr_lds = reinterpret_cast<float *>(qcnt_lds + VGBB_QPB);                     // [waves][32]: current k-th best distance
+    uint64_t *lists = reinterpret_cast<uint64_t *>(thr_lds + VGBB_QPB);                  // [waves][32][k]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int x = lane & 31, h = lane >> 5;
+    const int k = a.k;
+
+    const int G = a.nq_pad / VGBB_QPB;
+    const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    const int g = idx % G;
+    const int part = (idx / G) * 8 + xcd;
+    if (part >= a.npart) return;
+    const int q0 = g * VGBB_QPB + wave * VGBB_QPW;
+
+    // ---- A operand: the query's bits [32t + 16h, +16) = half h of its packed dword t, spread; |q| on the way
+    vgb_i32x4 areg[NTB];
+    uint32_t qc_part = 0;
+    {
+        const uint8_t *qrow = a.queries + (long long)(q0 + x) * a.stride;
+        vgb_static_for<0, NTB / 4>([&](auto gc) {
+            constexpr int g4 = decltype(gc)::value;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (16 * g4 < a.stride) v = *reinterpret_cast<const uint4 *>(qrow + 16 * g4);
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            vgb_static_for<0, 4>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                const uint32_t half = h ? (w[j] >> 16) : (w[j] & 0xFFFFu);
+                qc_part += (uint32_t)__builtin_popcount(half);
+                areg[4 * g4 + j] = vgbb_spread16(half);
+            });
+        });
+    }
+    uint32_t *qc_w = qcnt_lds + wave * VGBB_QPW;
+    float *thr_w = thr_lds + wave * VGBB_QPW;
+    uint64_t *wave_lists = lists + (size_t)wave * VGBB_QPW * k;
+    {
+        const uint32_t qc = qc_part + __shfl_xor(qc_part, 32);
+        if (h == 0) {
+            qc_w[x] = qc;
+            // the pre-pass bound is the distance of an actual row, which the first real stage meets again: one ulp up, so that the
+            // strict comparison of the slow path lets a row AT the bound in; padding queries never accept
+            float t = a.init_keys ? nextafterf(vgb_kth_distance(a.init_keys[(long long)(q0 + x) * 64 + (k - 1)]), INFINITY) : INFINITY;
+            if (q0 + x >= a.nq_real) t = -INFINITY;
+            thr_w[x] = t;
+        }
+        const bool seeded = a.seed != 0 && part == 0;               // (keys of rows no later stage meets again)
+        for (int s = lane; s < VGBB_QPW * k; s += 64)
+            wave_lists[s] = seeded ? a.init_keys[(long long)(q0 + s / k) * 64 + s % k] : VG_EMPTY_KEY;
+    }
+    // chunk columns past the row length are never written by the spreading: they read as 0 bits
+    for (int s = tid; s < 2 * TILE_BYTES / 4; s += THREADS) reinterpret_cast<uint32_t *>(tile0)[s] = 0u;
+    __syncthreads();
+
+    // ---- the tile's producer side.  Thread (prow, pj) owns packed bytes [8 pj, +8) of row prow of a tile = chunk columns 4 pj .. 4 pj + 3
+    const long long tile_first = a.tile_begin + (long long)part * a.tiles_per_part;
+    const long long tile_last = min(tile_first + a.tiles_per_part, a.tile_end);
+    const bool spreader = tid < SPREADERS;                          // (wave-uniform)
+    const int prow = tid / LPR, pj = tid % LPR;
+    const bool pcols = spreader && 8 * pj < (int)a.stride;          // the row has such bytes
+    const uint8_t *pbase = a.rows + (long long)prow * a.stride + 8 * pj;
+    const unsigned long long tile_stride = (unsigned long long)a.stride * VGBB_TILE;
+    uint8_t *pdst = tile0 + (pcols ? (4 * pj) * 512 + prow * 16 : 0);
+    auto load_packed = [&](long long tile) __attribute__((always_inline)) -> uint2 {
+        uint2 v = make_uint2(0u, 0u);
+        if (pcols && tile * VGBB_TILE + prow < a.n_rows) v = *reinterpret_cast<const uint2 *>(pbase + (unsigned long long)tile * tile_stride);
+        return v;
+    };
+    // chunk c (0 .. 3) of the thread's 8 bytes into buffer `buf`
+    auto spread_chunk = [&](auto cc, uint2 v, int buf) __attribute__((always_inline)) {
+        constexpr int c = decltype(cc)::value;
+        const uint32_t w = (c < 2) ? v.x : v.y;
+        const vgb_i32x4 o = vgbb_spread16((c & 1) ? (w >> 16) : (w & 0xFFFFu));
+        if (pcols) *reinterpret_cast<vgb_i32x4 *>(pdst + buf * TILE_BYTES + c * 512) = o;
+    };
+    auto store_count = [&](uint2 v, int buf) __attribute__((always_inline)) {
+        if (!spreader) return;
+        uint32_t cnt = (uint32_t)__builtin_popcount(v.x) + (uint32_t)__builtin_popcount(v.y);
+#pragma unroll
+        for (int m = 1; m < LPR; m <<= 1) cnt += __shfl_xor(cnt, m);
+        if (pj == 0) xcnt_lds[buf * VGBB_TILE + prow] = cnt;
+    };
+
+    // ---- the gate.  Register r of lane (x, h) belongs to query qi(r, h) = (r&3) + 8*(r>>2) + 4*h; i = acc[r].
+    //   Hamming  d = |q| + |x| - 2 i < thr  <=>  2 i + ng - |x| >= 0,  ng = ceil(thr) - 1 - |q|: integers, exact
+    //   Jaccard  (S - 2 i) 2^18 <= gt (S - i),  S = |q| + |x|,  gt = ceil(thr 2^18) <= 2^19: integers (v_mul_u32_u24), implied by
+    //            fl((u - i) / u) < thr; a padding query stands in the gate with |q| = 4096 and gt = 0 and never passes
+    // The exact test - (float) distance < thr, the single scan's arithmetic - is the slow path's.
+    vgb_i32x16 ng;                      // Hamming: the margin; Jaccard: |q|
+    vgb_i32x16 gs;                      // Jaccard: gt
+    auto gate_ham = [](uint32_t qc, float thr) __attribute__((always_inline)) -> int {
+        if (thr == -INFINITY) return -(1 << 30);               // padding
+        if (!(thr < 1.0e9f)) return 1 << 30;                   // list not full: everything passes
+        return (int)ceilf(thr) - 1 - (int)qc;
+    };
+    auto gate_jac = [](float thr) __attribute__((always_inline)) -> int {
+        if (thr == -INFINITY) return 0;                        // padding
+        if (!(thr < 2.0f)) return 1 << 19;                     // list not full (a <= b always): everything passes
+        return (int)ceilf(thr * 262144.0f);                    // (a power of two: exact, also for the denormal start threshold above 0)
+    };
+    vgb_static_for<0, 16>([&](auto rc) {
+        constexpr int r = decltype(rc)::value;
+        const int qi = (r & 3) + 8 * (r >> 2) + 4 * h;
+        ng[r] = JAC ? (thr_w[qi] == -INFINITY ? 4096 : (int)qc_w[qi]) : gate_ham(qc_w[qi], thr_w[qi]);
+        gs[r] = JAC ? gate_jac(thr_w[qi]) : 0;
+    });
+    auto passes = [&](int i, int ngr, int gsr, int xx) __attribute__((always_inline)) -> bool {
+        if constexpr (JAC) { const int S = ngr + xx; return ((uint32_t)(S - 2 * i) << 18) <= __umul24((uint32_t)gsr, (uint32_t)(S - i)); }
+        else return 2 * i + ngr - xx >= 0;
+    };
+    auto judge_any = [&](const vgb_i32x16 &acc, int xx) __attribute__((always_inline)) -> bool {
+        if constexpr (JAC) {
+            bool p = false;
+            vgb_static_for<0, 16>([&](auto rc) { constexpr int r = decltype(rc)::value; p |= passes(acc[r], ng[r], gs[r], xx); });
+            return __ballot(p) != 0;
+        } else {
+            int mm = -0x7FFFFFFF;
+            vgb_static_for<0, 16>([&](auto rc) { constexpr int r = decltype(rc)::value; const int m = 2 * acc[r] + ng[r]; mm = mm > m ? mm : m; });
+            return __ballot(mm - xx >= 0) != 0;
+        }
+    };
+    // the slow path of a tile (vg_batch_i8.hip's): which registers hold a passing pair, then - one copy of the code, looping over the
+    // pending registers by run-time index - the exact distance, the list inserts, the refreshed gate
+    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int xx) __attribute__((always_inline)) {
+        const long long row = tile * VGBB_TILE + x;
+        unsigned pend = 0;
+        vgb_static_for<0, 16>([&](auto rc) {
+            constexpr int r = decltype(rc)::value;
+            pend |= __ballot(passes(acc[r], ng[r], gs[r], xx)) ? (1u << r) : 0u;
+        });
+        while (pend) {
+            const int r = __builtin_ctz(pend);
+            pend &= pend - 1;
+            const int q_lo = (r & 3) + 8 * (r >> 2), qi = q_lo + 4 * h;
+            const uint32_t qc = qc_w[qi];
+            float thr_l = thr_w[qi];
+            const uint32_t i = (uint32_t)acc[r];
+            float d;
+            if (JAC) {
+                const uint32_t u = qc + (uint32_t)xx - i;
+                d = u ? __fdiv_rn((float)(u - i), (float)u) : 0.0f;
+            } else {
+                d = (float)(qc + (uint32_t)xx - 2u * i);
+            }
+            d = vg_clamp(d);
+            // strict: rows arrive in scan order, a row that only ties the k-th best has the larger position and loses
+            const bool pass = (row < a.n_rows) && (d < thr_l);
+            unsigned long long m = __ballot(pass);
+            if (!m) continue;
+            if constexpr (PRE) {
+                uint64_t kmin = pass ? vg_make_key(d, (uint32_t)row) : VG_EMPTY_KEY;     // min over the 32 rows of each query
+                kmin = vgb_min64(kmin, vgb_dpp64<VG_DPP_QUAD_PERM(1, 0, 3, 2)>(kmin));
+                kmin = vgb_min64(kmin, vgb_dpp64<VG_DPP_QUAD_PERM(2, 3, 0, 1)>(kmin));
+                kmin = vgb_min64(kmin, vgb_dpp64<VG_DPP_ROW_HALF_MIRROR>(kmin));
+                kmin = vgb_min64(kmin, vgb_dpp64<VG_DPP_ROW_MIRROR>(kmin));
+                kmin = vgb_min64(kmin, (uint64_t)__shfl_xor((unsigned long long)kmin, 16));
+#pragma unroll
+                for (int hh = 0; hh < 2; ++hh) {
+                    const uint64_t c = vg_readlane64(kmin, 32 * hh);
+                    if (c == VG_EMPTY_KEY) continue;
+                    const float nt = vgb_kth_distance(vgb_list_insert(wave_lists + (q_lo + 4 * hh) * k, k, lane, c));
+                    if (h == hh) thr_l = fminf(nt, thr_l);
+                }
+            } else {
+                const uint64_t key = vg_make_key(d, (uint32_t)row);
+                while (m) {
+                    const int src = __ffsll((long long)m) - 1;
+                    m &= m - 1;
+                    const int hh = src >> 5;
+                    const uint64_t c = vg_readlane64(key, src);
+                    const float nt = vgb_kth_distance(vgb_list_insert(wave_lists + (q_lo + 4 * hh) * k, k, lane, c));
+                    if (h == hh) thr_l = fminf(nt, thr_l);
+                }
+            }
+            if (x == 0) thr_w[qi] = thr_l;                                  // (the 32 lanes of a half hold the same value)
+            if (JAC) gs[r] = gate_jac(thr_l);
+            else ng[r] = gate_ham(qc, thr_l);
+        }
+    };
+
+    // ---- BARRIER PER TILE: the k loop of tile t with, in between its MFMAs, the load of tile t+1's packed bytes (top), their spreading
+    // into the other buffer (second half, a chunk every NTB / 8 k-steps) and the rows' bit counts; test; barrier
+    constexpr int BP = VGBB_BPIPE;
+    vgb_i32x4 bq[BP];
+    vgb_i32x16 acc;
+    const uint32_t lds_tile0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)tile0;
+    if (tile_first < tile_last) {
+        const uint2 v0 = load_packed(tile_first);
+        vgb_static_for<0, 4>([&](auto cc) { spread_chunk(cc, v0, 0); });
+        store_count(v0, 0);
+    }
+    __syncthreads();
+    for (long long tile = tile_first; tile < tile_last; ++tile) {
+        const int cur_buf = (int)((tile - tile_first) & 1), next_buf = cur_buf ^ 1;
+        const long long tile_next = min(tile + 1, tile_last - 1);          // (the last iteration spreads its own tile again)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0;
+        const uint32_t baddr = lds_tile0 + (uint32_t)(cur_buf * TILE_BYTES + h * 512 + x * 16);
+        uint2 pk = make_uint2(0u, 0u);
+        vgb_static_for<0, BP>([&](auto tc) { vgb_lds_read128<1024 * decltype(tc)::value>(bq[decltype(tc)::value], baddr); });
+        vgb_static_for<0, NTB>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            constexpr int in_flight_after = (NTB - 1 - t) < (BP - 1) ? (NTB - 1 - t) : (BP - 1);
+            vgb_wait_lds<in_flight_after>(bq[t % BP]);
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(areg[t], bq[t % BP], acc, 0, 0, 0);
+            if constexpr (t + BP < NTB) vgb_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
+            if constexpr (t == 0) pk = load_packed(tile_next);
+            constexpr int S0 = NTB / 2, SD = NTB / 8;
+            if constexpr (t >= S0 && (t - S0) % SD == 0 && (t - S0) / SD < 4)
+                spread_chunk(std::integral_constant<int, (t - S0) / SD>{}, pk, next_buf);
+            if constexpr (t == NTB - 1) store_count(pk, next_buf);
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        const int xx = (int)xcnt_lds[cur_buf * VGBB_TILE + x];
+        if (judge_any(acc, xx)) judge_slow(acc, tile, xx);
+        __syncthreads();
+    }
+
+    for (int s = lane; s < VGBB_QPW * 64; s += 64) {
+        const int qi = s >> 6, slot = s & 63;
+        a.cand[((long long)(q0 + qi) * a.npart_total + a.part_base + part) * 64 + slot] = (slot < k) ? wave_lists[qi * k + slot] : VG_EMPTY_KEY;
+    }
+}
+
+// ---- host side
+// The kernel instantiations are split over two translation units compiled from this file (build.py): the real-pass kernels and the
+// entry points here, the PRE kernels with -DVGBB_TU_PRE.
+// the ladder of row lengths: k-steps the kernels are instantiated for (rows of up to 32 / 64 / 96 / 128 bytes); 0: not served
+static int vgbb_ntb(long long stride_bytes) {
+    if (stride_bytes < 16 || stride_bytes % 16 != 0) return 0;
+    const long long ntb = stride_bytes / 4;
+    return ntb <= 8 ? 8 : (ntb <= 16 ? 16 : (ntb <= 24 ? 24 : (ntb <= 32 ? 32 : 0)));
+}
+
+template <int NTB, bool JAC, bool PRE>
+static int launch_bits(const BatchArgsBits &a, int blocks, size_t smem, hipStream_t stream) {
+    return vgb_launch(vg_batch_bits_kernel<NTB, JAC, PRE>, blocks, 64 * VGBB_WAVES, smem, stream, a);
+}
+template <bool PRE>
+static int launch_bits_ntb(const BatchArgsBits &a, int ntb, int jaccard, int blocks, size_t smem, hipStream_t stream) {
+    switch (ntb) {
+    case 8: return jaccard ? launch_bits<8, true, PRE>(a, blocks, smem, stream) : launch_bits<8, false, PRE>(a, blocks, smem, stream);
+    case 16: return jaccard ? launch_bits<16, true, PRE>(a, blocks, smem, stream) : launch_bits<16, false, PRE>(a, blocks, smem, stream);
+    case 24: return jaccard ? launch_bits<24, true, PRE>(a, blocks, smem, stream) : launch_bits<24, false, PRE>(a, blocks, smem, stream);
+    case 32: return jaccard ? launch_bits<32, true, PRE>(a, blocks, smem, stream) : launch_bits<32, false, PRE>(a, blocks, smem, stream);
+    }
+    return -1;
+}
+#ifdef VGBB_TU_PRE
+extern "C" int vgbb_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream) {
+    return launch_bits_ntb<true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+#else
+extern "C" int vgbb_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream) {
+    return launch_bits_ntb<false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+
+extern "C" int vg_batch_bits_queries_per_block(void) { return VGBB_QPB; }
+
+// LDS bytes of one workgroup: two spread tiles, their rows' bit counts, the queries' bit counts and thresholds, the lists
+// (128-byte rows, k = 32: 65536 + 256 + 1024 + 1024 + 65536 = 133376)
+extern "C" size_t vg_batch_bits_lds_bytes(long long stride_bytes, int k) {
+    const int NTB = vgbb_ntb(stride_bytes);
+    if (!NTB || k < 1 || k > VGBB_MAX_K) return 0;
+    return (size_t)2 * NTB * 1024 + 2 * VGBB_TILE * 4 + VGBB_QPB * 4 + VGBB_QPB * 4 + (size_t)VGBB_QPB * k * 8;
+}
+
+// dev_rows: the corpus' row-major rows; dev_queries: nq_pad x stride packed bytes.  Returns 0, -1 if the shape is not served, a
+// hipError_t otherwise.  dev_cand sized like the f32 kernel's.
+extern "C" int vg_batch_bits_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
+                                    const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
+                                    uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream) {
+    const size_t smem = vg_batch_bits_lds_bytes(stride_bytes, k);
+    if (!smem || nq_pad < VGBB_QPB || nq_pad % VGBB_QPB != 0 || npart < 1 || npart > VG_SEL_MAX_HEADS || n_rows < 1) return -1;
+    BatchArgsBits a;
+    a.rows = dev_rows; a.queries = dev_queries; a.cand = dev_cand;
+    a.n_rows = n_rows; a.stride = stride_bytes; a.nq_pad = nq_pad; a.nq_real = nq_real; a.npart = npart; a.k = k;
+    const int variant = vgbb_ntb(stride_bytes) * 2 + (jaccard ? 1 : 0);       // what the two units' launchers take
+    const int G = nq_pad / VGBB_QPB;
+    const int blocks = G * ((npart + 7) / 8) * 8;
+    const long long ntiles = (n_rows + VGBB_TILE - 1) / VGBB_TILE;
+    // large corpora: the pre-pass hands every query a start threshold, the real pass runs in stages from there (vg_batch_i8.hip)
+    long long pre = 0;
+    {
+        const int denom = vg_sw(SW_VG_BATCH_PREPASS, VGB_PREPASS_DENOM_DEFAULT);
+        if (denom > 0 && ntiles >= 65536) pre = ((ntiles / denom + npart - 1) / npart) * npart;
+    }
+    return vgb_run_staged(a, ntiles, pre, 400, dev_out_keys, stream,
+                          [&](const BatchArgsBits &b) { return vgbb_launch_pre(&b, variant, blocks, smem, stream); },
+                          [&](const BatchArgsBits &b) { return vgbb_launch_real(&b, variant, blocks, smem, stream); });
+}
+#endif   // !VGBB_TU_PRE

@@ -14,6 +14,7 @@
 
 struct BatchArgsH;                      // vg_batch_h_defs.h
 struct BatchArgsI8;                     // vg_batch_i8.hip
+struct BatchArgsBits;                   // vg_batch_bits.hip
 
 extern "C" {
 
@@ -41,6 +42,16 @@ int vg_batch_i8_launch(const uint8_t *dev_rows_signed, long long n_rows, long lo
                        int tiles_per_part, uint64_t *dev_out_keys, hipStream_t stream);
 int vgi_launch_pre(const BatchArgsI8 *a, int ntb, int blocks, size_t smem, hipStream_t stream);     // -DVGI_TU_PRE
 int vgi_launch_real(const BatchArgsI8 *a, int ntb, int blocks, size_t smem, hipStream_t stream);
+
+// ---- vg_batch_bits.hip: packed bit vectors (uint8 rows, Hamming / Jaccard) on the integer matrix cores, the rows spread to 0 / 1 bytes
+// on their way into LDS; `jaccard`: 0 Hamming, 1 Jaccard
+size_t vg_batch_bits_lds_bytes(long long stride_bytes, int k);             // 0: rows / k it does not serve
+int vg_batch_bits_queries_per_block(void);
+int vg_batch_bits_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
+                         const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
+                         uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
+int vgbb_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);  // -DVGBB_TU_PRE; variant = 2 * k-steps + jaccard
+int vgbb_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);
 
 // ---- vg_batch_h.hip: f16 / bf16 rows (and f32 rows through their bf16 shadow copy) - matrix-core filter + exact re-evaluation;
 // the conversion passes behind the derived copies of a corpus

@@ -62,6 +62,7 @@ struct VgSwitchName { const char *name; int lab; };
 static const VgSwitchName vg_switch_names[VGSW_COUNT] = {
     {"VECTORGPU_SHARD_GATHER", 0},
     {"VECTORGPU_SHARD_THREADS", 0},
+    {"VG_BATCH_BITS_MIN_QUERIES", 0},
     {"VG_BATCH_BPC", 1},
     {"VG_BATCH_H_SPLIT", 0},
     {"VG_BATCH_H_WAVES", 0},
