@@ -21,8 +21,8 @@ VEC = os.path.join(HERE, "vector.so")
 # (source, object, extra flags): the two kernel families with the most template instantiations are compiled as several
 # translation units from one source file each (the half-precision batch kernels: 9 + 6 units), so that a from-scratch build is bounded
 # by the total CPU time over the cores (~30 CPU-minutes: ~4 min on 8 cores) instead of by its longest unit
-# vg_batch_bits.hip is integer code - its float math is two conversions and a division per surviving pair - and is compiled with the
-# packed-f32 VALU forms off: the compiler forms none in it either way (tools/kernel_regs.py takes the same flags)
+# vg_batch_bits.hip and vg_batch_bitsl.hip are integer code - their float math is two conversions and a division per surviving pair -
+# and are compiled with the packed-f32 VALU forms off: the compiler forms none in them either way (tools/kernel_regs.py takes the same flags)
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_UNITS = [("vg_api.hip", "vg_api.hip.o", []), ("vg_corpus.hip", "vg_corpus.hip.o", []), ("vg_batch_api.hip", "vg_batch_api.hip.o", []),
              ("vg_select.hip", "vg_select.hip.o", []), ("vg_batch.hip", "vg_batch.hip.o", []), ("vg_quant.hip", "vg_quant.hip.o", []),
@@ -30,6 +30,7 @@ HIP_UNITS = [("vg_api.hip", "vg_api.hip.o", []), ("vg_corpus.hip", "vg_corpus.hi
              ("vg_batch_q8.hip", "vg_batch_q8.o", []),
              ("vg_batch_i8.hip", "vg_batch_i8.hip.o", []), ("vg_batch_i8.hip", "vg_batch_i8_pre.o", ["-DVGI_TU_PRE"]),
              ("vg_batch_bits.hip", "vg_batch_bits.hip.o", NO_PK_F32), ("vg_batch_bits.hip", "vg_batch_bits_pre.o", NO_PK_F32 + ["-DVGBB_TU_PRE"]),
+             ("vg_batch_bitsl.hip", "vg_batch_bitsl.hip.o", NO_PK_F32), ("vg_batch_bitsl.hip", "vg_batch_bitsl_pre.o", NO_PK_F32 + ["-DVGBL_TU_PRE"]),
              ("vg_batch_h.hip", "vg_batch_h.hip.o", []), ("vg_batch_h.hip", "vg_batch_h_bf16.o", ["-DVGH_TU=1"]),
              ("vg_batch_h.hip", "vg_batch_h_bound.o", ["-DVGH_TU=2"]), ("vg_batch_h.hip", "vg_batch_h_f32.o", ["-DVGH_TU=3"]),
              ("vg_batch_h.hip", "vg_batch_h_bound_bf16.o", ["-DVGH_TU=4"]), ("vg_batch_h.hip", "vg_batch_h_bound_f32.o", ["-DVGH_TU=5"]),

@@ -1,6 +1,6 @@
 // vg_batch_api.hip - host side of the batched scans (vg_scan_topk_batch[_keys]): partition planning, the cached per-row
 // statistics the matrix-core kernels need, query staging, launches of vg_batch.hip (f32) / vg_batch_i8.hip (uint8, int8) /
-// vg_batch_h.hip (f16, bf16) / vg_batch_bits.hip (bit vectors), slicing of very large batches; shapes none of them serves go through the multi-query scan
+// vg_batch_h.hip (f16, bf16) / vg_batch_bits.hip, vg_batch_bitsl.hip (bit vectors), slicing of very large batches; shapes none of them serves go through the multi-query scan
 // (vg_multi.hip) or, last, one single-query scan per query.
 // Layout: the derived copies of the corpus (ensure_*), what the four drivers share (batch_mode_root, batch_type_code, unpack_keys,
 // rescan_unjudged; buffer growth, query staging and the profiling slot are vg_internal.h's), the drivers - scan_topk_batch_long /
@@ -504,19 +504,20 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
     return VG_OK;
 }
 
-// ---- packed bit vectors (uint8 corpora, Hamming / Jaccard), batches of VG_BATCH_BITS_MIN_QUERIES queries or more: vg_batch_bits.hip, the
-// integer matrix cores over the rows spread to 0 / 1 bytes on their way into LDS.  The kernel reads c->d_rows itself: no derived copy, no
+// ---- packed bit vectors (uint8 corpora, Hamming / Jaccard), batches of VG_BATCH_BITS_MIN_QUERIES queries or more: vg_batch_bits.hip (rows
+// of up to 128 bytes) and vg_batch_bitsl.hip (up to 512), the integer matrix cores over the rows spread to 0 / 1 bytes on their way into LDS.  The kernel reads c->d_rows itself: no derived copy, no
 // per-row statistic, nothing to keep in step with the rows.  Every distance is the single scan's, bit for bit.
 #define VG_BATCH_BITS_MIN_QUERIES_DEFAULT 64   // (0: never.  Measured, tools/bits_batch_bench.py / DESIGN.md 3.25: at 32 queries over 32-byte rows the multi-query scan still wins)
+#define VG_BATCH_BITS_MIN_QUERIES_LONG_DEFAULT 32   // rows beyond 128 bytes, all four ladder steps (at 16 queries the multi-query scan wins or ties Hamming at every row length, from 32 on the matrix cores win every cell by more than both spreads)
 static bool batch_bits_eligible(const vg_corpus *c, int metric, int k, int nq) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_U8 || !vg_metric_is_bits(metric)) return false;
-    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, VG_BATCH_BITS_MIN_QUERIES_DEFAULT);
+    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, c->stride > 128 ? VG_BATCH_BITS_MIN_QUERIES_LONG_DEFAULT : VG_BATCH_BITS_MIN_QUERIES_DEFAULT);
     if (min_q <= 0 || nq < min_q) return false;
-    return vg_batch_bits_lds_bytes(c->stride, k) != 0;                    // k <= 32, rows of up to 128 bytes
+    return vg_batch_bits_lds_bytes(c->stride, k) != 0;                    // k <= 32, rows of up to 512 bytes (193 - 256 bytes: k <= 29)
 }
 
 static int scan_topk_batch_bits(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts) {
-    const int QPB = vg_batch_bits_queries_per_block();
+    const int QPB = vg_batch_bits_queries_per_block(c->stride);           // 256 / 128 / 64 by row length
     const int nq_pad = ((nq + QPB - 1) / QPB) * QPB;
     const int G = nq_pad / QPB;
     // partitions: one workgroup per CU and query group (VG_BATCH_BPC overrides the workgroups per CU, as in scan_topk_batch_mfma), a

@@ -21,46 +21,23 @@
 //   * the gate is an integer margin on the raw accumulator for Hamming (2 i + ng - |x| >= 0, exact) and an integer product test without
 //     a division for Jaccard (it cannot reject a pair whose float distance is below the threshold); survivors get the
 //     exact distance - the expressions of vg_accum.h - and go through vgb_list_insert;
-//   * large corpora: the pre-pass and the staged real passes of vg_batch_common.h.
+//   * large corpora: the pre-pass and the staged real passes of vg_batch_common.h;
+//   * rows of 129 .. 512 bytes: vg_batch_bitsl.hip, the K dimension split over the wavefronts of a workgroup - the host entry points at
+//     the end of this file hand such strides on.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cstdlib>
 #include <type_traits>
 
+#include "vg_batch_bits_defs.h"
 #include "vg_batch_common.h"
 #include "vg_batch_units.h"
 
 #define VGBB_WAVES 8
 #define VGBB_QPW 32
 #define VGBB_QPB (VGBB_WAVES * VGBB_QPW)
-#define VGBB_TILE 32
-#define VGBB_MAX_K 32
 #define VGBB_BPIPE 4                    // B-operand register quads in flight
-
-struct BatchArgsBits {
-    const uint8_t *rows;      // the corpus' own row-major rows: `stride` packed bytes each
-    const uint8_t *queries;   // nq_pad x stride packed bytes, zero padded
-    uint64_t *cand;
-    long long n_rows;
-    long long stride;         // bytes per row (multiple of 16, <= 128)
-    int nq_pad, nq_real, npart, k;   // queries [nq_real, nq_pad) are padding
-    int tiles_per_part;
-    long long tile_begin, tile_end;
-    int part_base, npart_total;
-    const uint64_t *init_keys;
-    int seed;                 // staged real passes (vg_batch_common.h): partition 0 starts its lists from init_keys
-};
-
-// bits 0 .. 15 of v -> 16 bytes of 0 / 1, byte j of dword d = bit 4d + j
-__device__ __forceinline__ vgb_i32x4 vgbb_spread16(uint32_t v) {
-    vgb_i32x4 o;
-    o[0] = (int)(__umul24(__builtin_amdgcn_ubfe(v, 0, 4), 0x00204081u) & 0x01010101u);
-    o[1] = (int)(__umul24(__builtin_amdgcn_ubfe(v, 4, 4), 0x00204081u) & 0x01010101u);
-    o[2] = (int)(__umul24(__builtin_amdgcn_ubfe(v, 8, 4), 0x00204081u) & 0x01010101u);
-    o[3] = (int)(__umul24(__builtin_amdgcn_ubfe(v, 12, 4), 0x00204081u) & 0x01010101u);
-    return o;
-}
 
 // NTB = k-steps per row (32 bits = 4 packed bytes each): rows up to 4 * NTB bytes, shorter ones zero-padded in the k dimension
 // JAC = Jaccard (else Hamming); PRE = the pre-pass variant (vg_batch_i8.hip): only the smallest distance of a query in a tile enters
@@ -332,11 +309,16 @@ extern "C" int vgbb_launch_real(const BatchArgsBits *a, int variant, int blocks,
     return launch_bits_ntb<false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
 }
 
-extern "C" int vg_batch_bits_queries_per_block(void) { return VGBB_QPB; }
+// queries a workgroup serves: 256, or the long-row form's 128 (rows of up to 256 bytes) / 64 (up to 512)
+extern "C" int vg_batch_bits_queries_per_block(long long stride_bytes) {
+    return stride_bytes > 128 ? vg_batch_bitsl_queries_per_block(stride_bytes) : VGBB_QPB;
+}
 
 // LDS bytes of one workgroup: two spread tiles, their rows' bit counts, the queries' bit counts and thresholds, the lists
-// (128-byte rows, k = 32: 65536 + 256 + 1024 + 1024 + 65536 = 133376)
+// (128-byte rows, k = 32: 65536 + 256 + 1024 + 1024 + 65536 = 133376); rows beyond 128 bytes: the long-row form's answer.  0: not
+// served - the ONE place that decides which rows and k take the matrix cores
 extern "C" size_t vg_batch_bits_lds_bytes(long long stride_bytes, int k) {
+    if (stride_bytes > 128) return vg_batch_bitsl_lds_bytes(stride_bytes, k);
     const int NTB = vgbb_ntb(stride_bytes);
     if (!NTB || k < 1 || k > VGBB_MAX_K) return 0;
     return (size_t)2 * NTB * 1024 + 2 * VGBB_TILE * 4 + VGBB_QPB * 4 + VGBB_QPB * 4 + (size_t)VGBB_QPB * k * 8;
@@ -347,6 +329,8 @@ extern "C" size_t vg_batch_bits_lds_bytes(long long stride_bytes, int k) {
 extern "C" int vg_batch_bits_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
                                     const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
                                     uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream) {
+    if (stride_bytes > 128)
+        return vg_batch_bitsl_launch(dev_rows, n_rows, stride_bytes, dev_queries, nq_pad, nq_real, k, jaccard, dev_cand, npart, dev_out_keys, stream);
     const size_t smem = vg_batch_bits_lds_bytes(stride_bytes, k);
     if (!smem || nq_pad < VGBB_QPB || nq_pad % VGBB_QPB != 0 || npart < 1 || npart > VG_SEL_MAX_HEADS || n_rows < 1) return -1;
     BatchArgsBits a;

@@ -14,7 +14,7 @@
 
 struct BatchArgsH;                      // vg_batch_h_defs.h
 struct BatchArgsI8;                     // vg_batch_i8.hip
-struct BatchArgsBits;                   // vg_batch_bits.hip
+struct BatchArgsBits;                   // vg_batch_bits_defs.h
 
 extern "C" {
 
@@ -46,12 +46,21 @@ int vgi_launch_real(const BatchArgsI8 *a, int ntb, int blocks, size_t smem, hipS
 // ---- vg_batch_bits.hip: packed bit vectors (uint8 rows, Hamming / Jaccard) on the integer matrix cores, the rows spread to 0 / 1 bytes
 // on their way into LDS; `jaccard`: 0 Hamming, 1 Jaccard
 size_t vg_batch_bits_lds_bytes(long long stride_bytes, int k);             // 0: rows / k it does not serve
-int vg_batch_bits_queries_per_block(void);
+int vg_batch_bits_queries_per_block(long long stride_bytes);              // 256; rows beyond 128 bytes: 128 (<= 256 bytes) / 64 (<= 512)
 int vg_batch_bits_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
                          const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
                          uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
 int vgbb_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);  // -DVGBB_TU_PRE; variant = 2 * k-steps + jaccard
 int vgbb_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);
+// ---- vg_batch_bitsl.hip: its long-row form (rows of 129 .. 512 bytes, the K dimension split over the wavefronts of a workgroup), reached
+// through the three entry points above
+size_t vg_batch_bitsl_lds_bytes(long long stride_bytes, int k);
+int vg_batch_bitsl_queries_per_block(long long stride_bytes);
+int vg_batch_bitsl_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
+                          const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
+                          uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
+int vgbl_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);  // -DVGBL_TU_PRE; variant = 2 * (64 K-slices + k-steps per slice) + jaccard
+int vgbl_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);
 
 // ---- vg_batch_h.hip: f16 / bf16 rows (and f32 rows through their bf16 shadow copy) - matrix-core filter + exact re-evaluation;
 // the conversion passes behind the derived copies of a corpus
