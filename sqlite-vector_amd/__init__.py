@@ -302,6 +302,7 @@ def _load():
         "vg_within_batch_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_within_batch_set_initial_capacity": (i32, [vp, i64]),
         "vg_within_batch_last_launches": (i32, [vp]),
+        "vg_within_batch_last_path": (i32, [vp]),
         "vg_shards_within_batch_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_shards_within_batch_set_initial_capacity": (i32, [vp, i64]),
         "vg_shards_within_batch_last_launches": (i32, [vp]),
@@ -1149,6 +1150,11 @@ class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeled
 
     def within_batch_last_launches(self):
         return within_batch_last_launches(self)
+
+    def within_batch_last_path(self):
+        """which path answered the last batch range scan of any form: 5 multi-query range scan, 6 one range scan per query, 8 bit vectors
+        (Hamming / Jaccard) on the int8 matrix cores, 0 no call yet"""
+        return int(lib().vg_within_batch_last_path(self.h))
 
     def scan_topk_batch(self, metric, queries, k):
         queries = np.ascontiguousarray(queries)

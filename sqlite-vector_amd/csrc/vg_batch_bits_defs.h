@@ -25,6 +25,48 @@ struct BatchArgsBits {
     int seed;                 // staged real passes (vg_batch_common.h): partition 0 starts its lists from init_keys
 };
 
+// ---- the range form (vg_batch_bits_within.hip: every row within a radius).  Here, not in that unit, so that a K-split
+// range form for rows beyond 128 bytes can take the gate and the emission as they are.
+struct BatchArgsBitsWithin {
+    const uint8_t *rows;      // as BatchArgsBits
+    const uint8_t *queries;   // nq_pad x stride packed bytes, zero padded
+    const void *desc;         // nq_pad VgWithinQuery (vg_scan_multi.h): region [count | cap keys], cap, radius; a padding query: cap 0, radius -Inf
+    long long n_rows;
+    long long stride;         // bytes per row: 16 .. 128, a multiple of 16
+    int nq_pad, npart;
+    int tiles_per_part;
+};
+
+// A row matches iff d <= r.  Every distance here is finite and >= 0: a radius below zero (-0.0 is not) matches nothing and stands as
+// -Inf, the padding query's; otherwise d <= r <=> d < thr with thr the next float above r (+Inf stays +Inf) - the strict test the
+// top-k kernels' gates were derived for
+__device__ __forceinline__ float vgbb_within_thr(float r) { return (r < 0.0f) ? -INFINITY : nextafterf(r, INFINITY); }
+// the gates of vg_batch_bits.hip (its gate_ham / gate_jac, statement for statement; that kernel keeps its own copies and with them its code)
+//   Hamming  d = |q| + |x| - 2 i < thr  <=>  2 i + ng - |x| >= 0,  ng = ceil(thr) - 1 - |q|
+//   Jaccard  (S - 2 i) 2^18 <= gt (S - i),  S = |q| + |x|,  gt = ceil(thr 2^18) <= 2^19
+__device__ __forceinline__ int vgbb_gate_ham(uint32_t qc, float thr) {
+    if (thr == -INFINITY) return -(1 << 30);               // never matches
+    if (!(thr < 1.0e9f)) return 1 << 30;                   // everything matches
+    return (int)ceilf(thr) - 1 - (int)qc;
+}
+__device__ __forceinline__ int vgbb_gate_jac(float thr) {
+    if (thr == -INFINITY) return 0;                        // never matches (with |q| = 4096 in the gate)
+    if (!(thr < 2.0f)) return 1 << 19;                     // everything matches (a <= b always)
+    return (int)ceilf(thr * 262144.0f);                    // (a power of two: exact, also for the denormal threshold of the radius 0)
+}
+// One accumulator register's matches leave: lanes 0 .. 31 hold rows 0 .. 31 of a tile against one query, lanes 32 .. 63 against another;
+// out / cap are the lane's query's.  Per half: the keys compacted by ballot, ONE atomicAdd on the region's count, vector stores while
+// they fit - the count keeps counting past cap (vg_within_flush's protocol).  All 64 lanes call it.
+__device__ __forceinline__ void vgbb_within_emit(bool pass, uint64_t key, unsigned long long *out, unsigned long long cap, int lane) {
+    const unsigned long long m = __ballot(pass);
+    const uint32_t mh = (lane & 32) ? (uint32_t)(m >> 32) : (uint32_t)m;
+    const uint32_t cnt = (uint32_t)__popc(mh), rank = (uint32_t)__popc(mh & ((1u << (lane & 31)) - 1u));
+    unsigned long long base = 0ull;
+    if ((lane & 31) == 0 && cnt) base = atomicAdd(out, (unsigned long long)cnt);
+    base = __shfl(base, lane & 32);
+    if (pass && base + rank < cap) out[1 + base + rank] = key;
+}
+
 // bits 0 .. 15 of v -> 16 bytes of 0 / 1, byte j of dword d = bit 4d + j
 __device__ __forceinline__ vgb_i32x4 vgbb_spread16(uint32_t v) {
     vgb_i32x4 o;

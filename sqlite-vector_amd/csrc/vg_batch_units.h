@@ -61,6 +61,11 @@ int vg_batch_bitsl_launch(const uint8_t *dev_rows, long long n_rows, long long s
                           uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
 int vgbl_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);  // -DVGBL_TU_PRE; variant = 2 * (64 K-slices + k-steps per slice) + jaccard
 int vgbl_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);
+// ---- vg_batch_bits_within.hip: the range form of vg_batch_bits.hip (rows of up to 128 bytes): every row within a radius, a radius per
+// query.  dev_desc: nq_pad VgWithinQuery descriptors (vg_scan_multi.h); one launch over all rows, keys appended to the queries' regions
+size_t vg_batch_bits_within_lds_bytes(long long stride_bytes);             // 0: rows it does not serve
+int vg_batch_bits_within_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
+                                const uint8_t *dev_queries, const void *dev_desc, int nq_pad, int jaccard, int npart, hipStream_t stream);
 
 // ---- vg_batch_h.hip: f16 / bf16 rows (and f32 rows through their bf16 shadow copy) - matrix-core filter + exact re-evaluation;
 // the conversion passes behind the derived copies of a corpus

@@ -167,6 +167,7 @@ struct vg_corpus {
     size_t wb_bytes = 0, wb_grow_bytes = 0;
     int64_t wb_cap_init = 0;                  // vg_within_batch_set_initial_capacity: keys per query (0: a share of VG_WITHIN_INITIAL_CAP)
     int wb_launches = 0;                      // scan kernel launches of the last vg_scan_within_batch
+    int wb_last_path = 0;                     // vg_within_batch_last_path (vectorgpu_diag.h)
     std::vector<std::vector<uint64_t>> wb_keys;   // per query: the held keys, ascending = (distance, scan position)
     std::vector<int64_t> wb_matches;
     // masked scans (vg_scan_masked.hip): the row mask - bit (p & 63) of word (p >> 6) = the row at scan position p may be returned.  Read

@@ -27,6 +27,7 @@
 
 #include "vg_scan_multi.h"
 #include "vg_pick.h"
+#include "vg_batch_units.h"          // vg_batch_bits_within_launch
 
 // what differs between the unmasked, the masked and the labeled batch: whose name errors carry, and whether the launches read the
 // handle's mask or its labels (then every query names one).  No membership form
@@ -196,6 +197,117 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
     return VG_OK;
 }
 
+// ---- packed bit vectors (uint8 corpora, Hamming / Jaccard), unmasked and unlabeled batches of VG_BATCH_BITS_MIN_QUERIES queries or more over
+// rows of 16 .. 128 bytes: the range form of the matrix-core batch kernel (vg_batch_bits_within.hip).  A launch is one workgroup's 256
+// queries against every row - the corpus is read once per 256 queries, not once per 4 - and a slice is one launch, so the staging
+// area, the gathered counts and the overflow protocol above keep their sizes and their shape at the granularity of a launch.
+#define VG_WITHIN_BITS_MIN_QUERIES_DEFAULT 256    // (0: never.  Measured, tools/bits_within_bench.py / DESIGN.md 3.27: at 64 queries the multi-query range scan still wins or ties cells)
+static bool within_bits_eligible(const vg_corpus *c, int metric, int nq) {
+    if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_U8 || !vg_metric_is_bits(metric)) return false;
+    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, VG_WITHIN_BITS_MIN_QUERIES_DEFAULT);
+    if (min_q <= 0 || nq < min_q) return false;
+    return vg_batch_bits_within_lds_bytes(c->stride) != 0;
+}
+
+// the count word of n descriptors' regions: zeroed (dst == nullptr) or gathered into dst
+__global__ void vg_wb_desc_counts_kernel(const VgWithinQuery *desc, int n, unsigned long long *dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (dst) dst[i] = desc[i].out[0];
+    else desc[i].out[0] = 0ull;
+}
+
+static int batch_within_bits(vg_corpus *c, const char *who, int metric, const void *queries, int nq, const double *radii, int64_t limit) {
+    constexpr int QPB = VG_WB_SLICE;                                  // the workgroup's queries = a launch = a slice
+    const int nslices = (nq + QPB - 1) / QPB;
+    const size_t qbytes = (size_t)QPB * c->stride, block_bytes = qbytes + (size_t)QPB * sizeof(VgWithinQuery);      // [256 queries | 256 descriptors]
+    VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, block_bytes));
+    if (!c->d_wb_counts) HIP_TRY(hipMalloc(&c->d_wb_counts, (size_t)VG_WB_SLICE * sizeof(unsigned long long)));
+    if (!c->h_wb) HIP_TRY(hipHostMalloc(&c->h_wb, (size_t)(VG_WB_SLICE + 8) * sizeof(unsigned long long)));
+    // partitions: one workgroup per CU (VG_BATCH_BPC overrides the workgroups per CU), a multiple of 8 (one per XCD), a tile at least
+    int npart = std::max(1, c->cu_count * std::max(1, vg_sw(SW_VG_BATCH_BPC, 1)));
+    if (npart >= 8) npart = (npart / 8) * 8;
+    npart = (int)std::min<long long>(npart, (c->n_rows + 31) / 32);
+    // zero-padded rows of the corpus stride; a pad query is zero with no capacity and a radius nothing is below
+    std::vector<uint8_t> hq((size_t)nslices * block_bytes, 0);
+    const size_t row_bytes = (size_t)c->dim * c->es;
+    for (int i = 0; i < nq; ++i)
+        memcpy(hq.data() + (size_t)(i / QPB) * block_bytes + (size_t)(i % QPB) * c->stride, (const uint8_t *)queries + (size_t)i * row_bytes, row_bytes);
+    uint8_t *d_stage = (uint8_t *)c->d_bq;
+    const VgWithinQuery *d_desc = reinterpret_cast<const VgWithinQuery *>(d_stage + qbytes);
+    const int jaccard = metric == VG_DIST_JACCARD ? 1 : 0;
+
+    // descriptors up, counts zeroed, the launch, counts back into h_wb[0, nqs): one wait
+    auto run = [&](uint8_t *block, VgWithinQuery *desc, int nqs) -> int {
+        HIP_TRY(hipMemcpyAsync(d_stage, block, block_bytes, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(vg_wb_desc_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, d_desc, nqs, (unsigned long long *)nullptr);
+        hipEvent_t *evs = vg_prof_slot(c, 0);
+        if (evs) hipEventRecord(evs[0], c->stream);
+        const int rc = vg_batch_bits_within_launch(c->d_rows, c->n_rows, c->stride, d_stage, d_desc, QPB, jaccard, npart, c->stream);
+        if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
+        if (rc != 0) {
+            hipStreamSynchronize(c->stream);
+            return vg_fail(VG_ERR_HIP, "%s: range batch launch (bit vectors) failed: %s", who, rc == -1 ? "shape not served" : hipGetErrorString((hipError_t)rc));
+        }
+        ++c->wb_launches;
+        hipLaunchKernelGGL(vg_wb_desc_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, d_desc, nqs, c->d_wb_counts);
+        hipError_t e = hipMemcpyAsync(c->h_wb, c->d_wb_counts, (size_t)nqs * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+        hipError_t e2 = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess || e2 != hipSuccess) return vg_fail(VG_ERR_HIP, "%s: %s", who, hipGetErrorString(e != hipSuccess ? e : e2));
+        return VG_OK;
+    };
+
+    for (int s = 0; s < nslices; ++s) {
+        const int q0 = s * QPB, nqs = std::min(QPB, nq - q0);         // (real queries: the pad queries own no region)
+        uint8_t *block = hq.data() + (size_t)s * block_bytes;
+        VgWithinQuery *desc = reinterpret_cast<VgWithinQuery *>(block + qbytes);
+        // a query's share of the one key budget, never more than the rows there are
+        int64_t cap = c->wb_cap_init > 0 ? c->wb_cap_init : std::max<int64_t>(VG_WB_MIN_CAP, (int64_t)VG_WITHIN_INITIAL_CAP / nqs);
+        cap = std::max<int64_t>(1, std::min<int64_t>(cap, c->n_rows));
+        const long long pitch = (long long)cap + 1;
+        VG_TRY(vg_dev_reserve(&c->d_wb, &c->wb_bytes, (size_t)nqs * (size_t)pitch * sizeof(unsigned long long)));
+        for (int j = 0; j < QPB; ++j) {
+            const bool real = j < nqs;
+            desc[j].out = real ? c->d_wb + (long long)j * pitch : c->d_wb;      // (a pad query never matches: its region is never touched)
+            desc[j].cap = real ? (unsigned long long)cap : 0ull;
+            desc[j].r = real ? vg_within_radius(radii[q0 + j]) : -INFINITY;
+            desc[j].label = VG_LABEL_NONE;
+        }
+        VG_TRY(run(block, desc, nqs));
+        std::vector<int64_t> counts((size_t)nqs);
+        bool over = false;
+        for (int j = 0; j < nqs; ++j) { counts[(size_t)j] = (int64_t)c->h_wb[j]; over = over || counts[(size_t)j] > cap; }
+        // the queries that fit: their keys leave first (nothing below touches d_wb)
+        bool pending = false;
+        for (int j = 0; j < nqs; ++j)
+            if (counts[(size_t)j] <= cap) VG_TRY(collect_keys(c, q0 + j, c->d_wb + (long long)j * pitch + 1, counts[(size_t)j], limit, &pending));
+        if (pending) HIP_TRY(hipStreamSynchronize(c->stream));
+        if (over) {
+            // a launch with a query past its capacity: once more as a whole, counts reset, every region at its counted size
+            size_t words = 0;
+            for (int j = 0; j < nqs; ++j) words += (size_t)std::max<int64_t>(counts[(size_t)j], 1) + 1;
+            VG_TRY(vg_dev_reserve(&c->d_wb_grow, &c->wb_grow_bytes, words * sizeof(unsigned long long)));
+            size_t at = 0;
+            for (int j = 0; j < QPB; ++j) {
+                desc[j].out = c->d_wb_grow + (j < nqs ? at : 0);
+                if (j < nqs) { desc[j].cap = (unsigned long long)std::max<int64_t>(counts[(size_t)j], 1); at += (size_t)desc[j].cap + 1; }
+            }
+            VG_TRY(run(block, desc, nqs));
+            for (int j = 0; j < nqs; ++j)
+                if ((int64_t)c->h_wb[j] != counts[(size_t)j])
+                    return vg_fail(VG_ERR_HIP, "%s: two launches counted %lld and %lld rows for query %d", who, (long long)counts[(size_t)j],
+                                   (long long)c->h_wb[j], q0 + j);
+            pending = false;
+            for (int j = 0; j < nqs; ++j)
+                if (counts[(size_t)j] > cap) VG_TRY(collect_keys(c, q0 + j, desc[j].out + 1, counts[(size_t)j], limit, &pending));
+            if (pending) HIP_TRY(hipStreamSynchronize(c->stream));          // (d_wb_grow serves the next such launch)
+        }
+        for (int j = 0; j < nqs; ++j) vg_within_finish(&c->wb_keys[(size_t)(q0 + j)], c->wb_matches[(size_t)(q0 + j)], limit);
+    }
+    vg_collect_timing(c);
+    return VG_OK;
+}
+
 static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *queries, int nq, const double *radii, const uint32_t *qlabels,
                         int64_t limit, int64_t *out_matches, int64_t *out_held) {
     for (int i = 0; i < nq; ++i) { if (out_matches) out_matches[i] = 0; if (out_held) out_held[i] = 0; }      // (every error leaves the counts zeroed)
@@ -223,7 +335,11 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
     scan_fn_t fn = nullptr;
     const int NQ = mw_plan(c, metric, f, &s, &fn);
     int rc = VG_OK;
-    if (NQ == 0) {                                               // no multi-query form: the single range scans of the same form, one by one
+    c->wb_last_path = 0;
+    if (f.rows == VG_QROWS_ALL && within_bits_eligible(c, metric, nq)) {      // bit vectors, enough queries: the integer matrix cores
+        rc = batch_within_bits(c, f.who, metric, queries, nq, radii, limit);
+        c->wb_last_path = 8;
+    } else if (NQ == 0) {                                        // no multi-query form: the single range scans of the same form, one by one
         const size_t row_bytes = (size_t)c->dim * c->es;
         // (the single range scan keeps its own result apart: what the handle held for it is put back behind the loop)
         std::vector<uint64_t> single_keys;
@@ -244,8 +360,10 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
         c->within_keys.swap(single_keys);
         c->within_matches = single_matches;
         c->within_launches = single_launches;
+        c->wb_last_path = 6;
     } else {
         rc = batch_within_multi(c, f, metric, fn, NQ, s, queries, nq, radii, qlabels, limit);
+        c->wb_last_path = 5;
     }
     if (rc != VG_OK) { c->wb_keys.clear(); c->wb_matches.clear(); return rc; }
     for (int i = 0; i < nq; ++i) {
@@ -327,3 +445,4 @@ extern "C" int vg_within_batch_set_initial_capacity(vg_corpus *c, int64_t keys_p
 }
 
 extern "C" int vg_within_batch_last_launches(const vg_corpus *c) { return c ? c->wb_launches : 0; }
+extern "C" int vg_within_batch_last_path(const vg_corpus *c) { return c ? c->wb_last_path : 0; }
