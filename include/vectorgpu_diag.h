@@ -133,7 +133,8 @@ int vg_shards_within_last_launches(const vg_shards *s);
  * Every pass takes one slot of the profiling ring.
  * vg_within_batch_last_path: which path answered the last batch range scan of any form on this handle - 5 = the multi-query range scan,
  * 6 = one range scan per query, 8 = the integer matrix cores (vg_batch_bits_within.hip: unmasked, unlabeled Hamming / Jaccard batches of
- * VG_BATCH_BITS_MIN_QUERIES queries or more over uint8 rows of 16 .. 128 bytes, a multiple of 16), 0 = no call yet. */
+ * VG_BATCH_BITS_MIN_QUERIES queries or more over uint8 rows of 16 .. 128 bytes, a multiple of 16; vg_batch_bitsl_within.hip: rows of
+ * 144 .. 512 bytes and at least one workgroup's 128 (<= 256 bytes) / 64 queries), 0 = no call yet. */
 int vg_within_batch_last_path(const vg_corpus *c);
 int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 int vg_within_batch_set_initial_capacity(vg_corpus *c, int64_t keys_per_query);

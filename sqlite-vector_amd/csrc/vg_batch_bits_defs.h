@@ -25,15 +25,15 @@ struct BatchArgsBits {
     int seed;                 // staged real passes (vg_batch_common.h): partition 0 starts its lists from init_keys
 };
 
-// ---- the range form (vg_batch_bits_within.hip: every row within a radius).  Here, not in that unit, so that a K-split
-// range form for rows beyond 128 bytes can take the gate and the emission as they are.
+// ---- the range forms (every row within a radius): vg_batch_bits_within.hip (rows of up to 128 bytes) and its K-split
+// sibling vg_batch_bitsl_within.hip (129 .. 512 bytes; 3.28), which share the arguments, the gate and the emission below.
 struct BatchArgsBitsWithin {
     const uint8_t *rows;      // as BatchArgsBits
     const uint8_t *queries;   // nq_pad x stride packed bytes, zero padded
     const void *desc;         // nq_pad VgWithinQuery (vg_scan_multi.h): region [count | cap keys], cap, radius; a padding query: cap 0, radius -Inf
     long long n_rows;
-    long long stride;         // bytes per row: 16 .. 128, a multiple of 16
-    int nq_pad, npart;
+    long long stride;         // bytes per row, a multiple of 16: 16 .. 128 (vg_batch_bits_within.hip), 144 .. 512 (vg_batch_bitsl_within.hip)
+    int nq_pad, npart;        // nq_pad: a multiple of the unit's queries per workgroup (256; the long rows' 128 / 64)
     int tiles_per_part;
 };
 

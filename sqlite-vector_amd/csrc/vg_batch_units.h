@@ -66,6 +66,12 @@ int vgbl_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t sme
 size_t vg_batch_bits_within_lds_bytes(long long stride_bytes);             // 0: rows it does not serve
 int vg_batch_bits_within_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
                                 const uint8_t *dev_queries, const void *dev_desc, int nq_pad, int jaccard, int npart, hipStream_t stream);
+// ---- vg_batch_bitsl_within.hip: the range form of vg_batch_bitsl.hip (rows of 129 .. 512 bytes): the same arguments and answers, nq_pad
+// a multiple of the queries per workgroup - 128 (<= 256 bytes) / 64 (<= 512); one launch over all rows and all query groups
+size_t vg_batch_bitsl_within_lds_bytes(long long stride_bytes);            // 0: rows it does not serve
+int vg_batch_bitsl_within_queries_per_block(long long stride_bytes);       // 0: rows it does not serve
+int vg_batch_bitsl_within_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
+                                 const uint8_t *dev_queries, const void *dev_desc, int nq_pad, int jaccard, int npart, hipStream_t stream);
 
 // ---- vg_batch_h.hip: f16 / bf16 rows (and f32 rows through their bf16 shadow copy) - matrix-core filter + exact re-evaluation;
 // the conversion passes behind the derived copies of a corpus

@@ -27,7 +27,7 @@
 
 #include "vg_scan_multi.h"
 #include "vg_pick.h"
-#include "vg_batch_units.h"          // vg_batch_bits_within_launch
+#include "vg_batch_units.h"          // vg_batch_bits_within_launch, vg_batch_bitsl_within_launch
 
 // what differs between the unmasked, the masked and the labeled batch: whose name errors carry, and whether the launches read the
 // handle's mask or its labels (then every query names one).  No membership form
@@ -197,16 +197,28 @@ static int batch_within_multi(vg_corpus *c, const WbForm &f, int metric, scan_fn
     return VG_OK;
 }
 
-// ---- packed bit vectors (uint8 corpora, Hamming / Jaccard), unmasked and unlabeled batches of VG_BATCH_BITS_MIN_QUERIES queries or more over
-// rows of 16 .. 128 bytes: the range form of the matrix-core batch kernel (vg_batch_bits_within.hip).  A launch is one workgroup's 256
+// ---- packed bit vectors (uint8 corpora, Hamming / Jaccard), unmasked and unlabeled batches of VG_BATCH_BITS_MIN_QUERIES queries or more: the
+// range forms of the matrix-core batch kernels.  Rows of 16 .. 128 bytes (vg_batch_bits_within.hip): a launch is one workgroup's 256
 // queries against every row - the corpus is read once per 256 queries, not once per 4 - and a slice is one launch, so the staging
-// area, the gathered counts and the overflow protocol above keep their sizes and their shape at the granularity of a launch.
+// area, the gathered counts and the overflow protocol above keep their sizes and their shape at the granularity of a launch.  Rows of
+// 129 .. 512 bytes (vg_batch_bitsl_within.hip): a workgroup holds 128 (<= 256 bytes) or 64 queries; a slice is still 256 queries and one
+// launch, of as many query groups as hold a real query - 1 to 2 of 128, 1 to 4 of 64.
 #define VG_WITHIN_BITS_MIN_QUERIES_DEFAULT 256    // (0: never.  Measured, tools/bits_within_bench.py / DESIGN.md 3.27: at 64 queries the multi-query range scan still wins or ties cells)
+// rows beyond 128 bytes, by K-split (0: never; measured).  Whatever the threshold - the switch included -, such a batch
+// needs one full workgroup of real queries: a launch below that floor is more than half padding
+#define VG_WITHIN_BITS_MIN_QUERIES_LONG2_DEFAULT 256   // strides 144 .. 256, 128 queries per workgroup: at 128 queries one (result-bound) cell stayed inside the spreads
+#define VG_WITHIN_BITS_MIN_QUERIES_LONG4_DEFAULT 64    // strides 272 .. 512, 64 queries per workgroup: the floor wins every measured cell
 static bool within_bits_eligible(const vg_corpus *c, int metric, int nq) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_U8 || !vg_metric_is_bits(metric)) return false;
-    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, VG_WITHIN_BITS_MIN_QUERIES_DEFAULT);
-    if (min_q <= 0 || nq < min_q) return false;
-    return vg_batch_bits_within_lds_bytes(c->stride) != 0;
+    if (c->stride <= 128) {
+        const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, VG_WITHIN_BITS_MIN_QUERIES_DEFAULT);
+        if (min_q <= 0 || nq < min_q) return false;
+        return vg_batch_bits_within_lds_bytes(c->stride) != 0;
+    }
+    if (vg_batch_bitsl_within_lds_bytes(c->stride) == 0) return false;
+    const int qpb = vg_batch_bitsl_within_queries_per_block(c->stride);
+    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, qpb == 128 ? VG_WITHIN_BITS_MIN_QUERIES_LONG2_DEFAULT : VG_WITHIN_BITS_MIN_QUERIES_LONG4_DEFAULT);
+    return min_q > 0 && nq >= std::max(min_q, qpb);
 }
 
 // the count word of n descriptors' regions: zeroed (dst == nullptr) or gathered into dst
@@ -218,16 +230,20 @@ __global__ void vg_wb_desc_counts_kernel(const VgWithinQuery *desc, int n, unsig
 }
 
 static int batch_within_bits(vg_corpus *c, const char *who, int metric, const void *queries, int nq, const double *radii, int64_t limit) {
-    constexpr int QPB = VG_WB_SLICE;                                  // the workgroup's queries = a launch = a slice
+    constexpr int QPB = VG_WB_SLICE;                                  // a slice = a launch; rows of up to 128 bytes: = the workgroup's queries
+    const int lqpb = c->stride > 128 ? vg_batch_bitsl_within_queries_per_block(c->stride) : 0;      // the long rows' queries per workgroup
     const int nslices = (nq + QPB - 1) / QPB;
     const size_t qbytes = (size_t)QPB * c->stride, block_bytes = qbytes + (size_t)QPB * sizeof(VgWithinQuery);      // [256 queries | 256 descriptors]
     VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, block_bytes));
     if (!c->d_wb_counts) HIP_TRY(hipMalloc(&c->d_wb_counts, (size_t)VG_WB_SLICE * sizeof(unsigned long long)));
     if (!c->h_wb) HIP_TRY(hipHostMalloc(&c->h_wb, (size_t)(VG_WB_SLICE + 8) * sizeof(unsigned long long)));
-    // partitions: one workgroup per CU (VG_BATCH_BPC overrides the workgroups per CU), a multiple of 8 (one per XCD), a tile at least
-    int npart = std::max(1, c->cu_count * std::max(1, vg_sw(SW_VG_BATCH_BPC, 1)));
-    if (npart >= 8) npart = (npart / 8) * 8;
-    npart = (int)std::min<long long>(npart, (c->n_rows + 31) / 32);
+    // partitions of a launch of G query groups: one workgroup per CU (VG_BATCH_BPC overrides the workgroups per CU) over the groups, a
+    // multiple of 8 (one per XCD), a tile at least
+    auto parts = [&](int G) {
+        int npart = std::max(1, c->cu_count * std::max(1, vg_sw(SW_VG_BATCH_BPC, 1)) / G);
+        if (npart >= 8) npart = (npart / 8) * 8;
+        return (int)std::min<long long>(npart, (c->n_rows + 31) / 32);
+    };
     // zero-padded rows of the corpus stride; a pad query is zero with no capacity and a radius nothing is below
     std::vector<uint8_t> hq((size_t)nslices * block_bytes, 0);
     const size_t row_bytes = (size_t)c->dim * c->es;
@@ -243,7 +259,10 @@ static int batch_within_bits(vg_corpus *c, const char *who, int metric, const vo
         hipLaunchKernelGGL(vg_wb_desc_counts_kernel, dim3(1), dim3(VG_WB_SLICE), 0, c->stream, d_desc, nqs, (unsigned long long *)nullptr);
         hipEvent_t *evs = vg_prof_slot(c, 0);
         if (evs) hipEventRecord(evs[0], c->stream);
-        const int rc = vg_batch_bits_within_launch(c->d_rows, c->n_rows, c->stride, d_stage, d_desc, QPB, jaccard, npart, c->stream);
+        // (long rows: the query groups that hold a real query; the descriptors behind them are padding up to the slice)
+        const int nq_pad = lqpb ? (nqs + lqpb - 1) / lqpb * lqpb : QPB;
+        const int rc = lqpb ? vg_batch_bitsl_within_launch(c->d_rows, c->n_rows, c->stride, d_stage, d_desc, nq_pad, jaccard, parts(nq_pad / lqpb), c->stream)
+                            : vg_batch_bits_within_launch(c->d_rows, c->n_rows, c->stride, d_stage, d_desc, QPB, jaccard, parts(1), c->stream);
         if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
         if (rc != 0) {
             hipStreamSynchronize(c->stream);

@@ -2,7 +2,8 @@
 """Hamming / Jaccard batch RANGE scans: the integer matrix cores (vg_batch_bits_within.hip, path 8) against the multi-query range scan
 (path 5) on ONE handle, in ONE process (10M rows; Hamming over random bytes, Jaccard over the mixed-density rows of tools/jaccard_bench.py):
 
-  row lengths  32 bytes (256 bits) and 128 bytes (1024 bits)
+  row lengths  32 bytes (256 bits) and 128 bytes (1024 bits); --row-bytes 256 / 512: the long-row form (vg_batch_bitsl_within.hip), whose
+               cells below one workgroup of queries (128 up to 256 bytes, 64 beyond) are skipped - such batches keep path 5
   nq           16, 32, 64, 256, 1024
   radii        two per cell, taken from the data: each query's own 20th smallest distance (scan_topk_batch), and the median, over 8 of
                the queries, of the 10 000th smallest distance (scan_distances + a partition on the host) - a query then matches about
@@ -46,7 +47,7 @@ def main():
     out = {"rows": N, "steps": args.steps, "warmup": args.warmup, "cases": {}}
     st = lambda a: {"min_ms": round(float(np.min(a)), 3), "median_ms": round(float(np.median(a)), 3),
                     "max_ms": round(float(np.max(a)), 3), "spread_ms": round(float(np.max(a) - np.min(a)), 3)}
-    wins = {nq: True for nq in args.nq}
+    wins = {}                                                   # per measured nq: every cell won
     for name, metric, make in (("hamming", pkg.HAMMING, lambda rng, n, dim: rng.integers(0, 256, (n, dim), dtype=np.uint8)),
                                ("jaccard", pkg.JACCARD, mixed_rows)):
         for dim in args.row_bytes:
@@ -63,6 +64,8 @@ def main():
                 # a radius per query from its own top-k where the target fits one (k <= 32), else the 8 queries' median for all
                 radius = c.scan_topk_batch(metric, qs, target)[1][:, target - 1].copy() if target <= 32 else float(np.median(kth[:, ti]))
                 for nq in args.nq:
+                    if dim > 128 and nq < (128 if dim <= 256 else 64):      # below one workgroup of queries rows beyond 128 bytes keep path 5
+                        continue
                     qn = np.ascontiguousarray(qs[:nq])
 
                     def run(switch):
@@ -87,12 +90,12 @@ def main():
                     gain = b["multi_query"]["wall"]["median_ms"] - b["matrix_cores"]["wall"]["median_ms"]
                     b["multi_over_matrix_wall"] = round(b["multi_query"]["wall"]["median_ms"] / b["matrix_cores"]["wall"]["median_ms"], 3)
                     b["faster_by_more_than_both_spreads"] = bool(gain > max(b["multi_query"]["wall"]["spread_ms"], b["matrix_cores"]["wall"]["spread_ms"]))
-                    wins[nq] = wins[nq] and b["faster_by_more_than_both_spreads"]
+                    wins[nq] = wins.get(nq, True) and b["faster_by_more_than_both_spreads"]
                     e["about_%d_matches_nq_%d" % (target, nq)] = b
                     print(name, dim, target, nq, b["matrix_cores"]["wall"]["median_ms"], b["multi_query"]["wall"]["median_ms"], file=sys.stderr, flush=True)
             out["cases"]["%s_%d_bytes" % (name, dim)] = e
             c.close()
-    order = sorted(args.nq)
+    order = sorted(wins)
     ok = [nq for i, nq in enumerate(order) if all(wins[m] for m in order[i:])]      # (it and every larger measured batch)
     out["threshold"] = ok[0] if ok else 0
     print(json.dumps(out, indent=1))
