@@ -509,14 +509,31 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
 // per-row statistic, nothing to keep in step with the rows.  Every distance is the single scan's, bit for bit.
 #define VG_BATCH_BITS_MIN_QUERIES_DEFAULT 64   // (0: never.  Measured, tools/bits_batch_bench.py / DESIGN.md 3.25: at 32 queries over 32-byte rows the multi-query scan still wins)
 #define VG_BATCH_BITS_MIN_QUERIES_LONG_DEFAULT 32   // rows beyond 128 bytes, all four ladder steps (at 16 queries the multi-query scan wins or ties Hamming at every row length, from 32 on the matrix cores win every cell by more than both spreads)
-static bool batch_bits_eligible(const vg_corpus *c, int metric, int k, int nq) {
+#define VG_BATCH_BITS_MASKED_MIN_QUERIES_DEFAULT 64   // masked batches (the gathering form, rows of up to 128 bytes).  Measured, tools/bits_batch_masked_bench.py / DESIGN.md 3.29: at 32 queries the multi-query scan still wins a contiguous 10 % mask over 32-byte rows (0.89 against 1.01 ms Hamming), from 64 on the matrix cores win every cell by more than both spreads
+// masked: the batch of vg_scan_topk_batch_masked - a mask with allowed rows, rows of up to 128 bytes, a threshold of its own
+static bool batch_bits_eligible(const vg_corpus *c, int metric, int k, int nq, bool masked = false) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_U8 || !vg_metric_is_bits(metric)) return false;
-    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, c->stride > 128 ? VG_BATCH_BITS_MIN_QUERIES_LONG_DEFAULT : VG_BATCH_BITS_MIN_QUERIES_DEFAULT);
+    if (masked && (c->stride > 128 || c->mask_count <= 0)) return false;
+    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, masked ? VG_BATCH_BITS_MASKED_MIN_QUERIES_DEFAULT
+                                                                 : (c->stride > 128 ? VG_BATCH_BITS_MIN_QUERIES_LONG_DEFAULT : VG_BATCH_BITS_MIN_QUERIES_DEFAULT));
     if (min_q <= 0 || nq < min_q) return false;
-    return vg_batch_bits_lds_bytes(c->stride, k) != 0;                    // k <= 32, rows of up to 512 bytes (193 - 256 bytes: k <= 29)
+    return (masked ? vg_batch_bits_masked_lds_bytes(c->stride, k) : vg_batch_bits_lds_bytes(c->stride, k)) != 0;   // k <= 32, rows of up to 512 bytes (193 - 256 bytes: k <= 29)
 }
 
-static int scan_topk_batch_bits(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts) {
+// the mask of the handle as the list the gathering kernel walks (vg_internal.h: d_mask_pos), built on the corpus stream when the
+// mask changed since the last one was
+static int ensure_mask_positions(vg_corpus *c) {
+    if (c->mask_pos_valid) return VG_OK;
+    const size_t cap = ((size_t)c->mask_count + 31) / 32 * 32;
+    VG_TRY(vg_dev_reserve(&c->d_mask_pos, &c->mask_pos_bytes, (cap + vg_batch_bits_pos_scratch_dwords(c->n_rows)) * sizeof(uint32_t)));
+    const int rc = vg_batch_bits_pos_launch(c->d_mask, c->n_rows, c->d_mask_pos, (long long)cap, c->d_mask_pos + cap, c->stream);
+    if (rc != 0) return vg_fail(VG_ERR_HIP, "mask position list pass failed: %s", hipGetErrorString((hipError_t)rc));
+    c->mask_pos_valid = true;
+    return VG_OK;
+}
+
+// one driver for the plain and the masked batch: the masked one counts tiles of the position list and launches the gathering form
+static int scan_topk_batch_bits_form(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts, bool masked) {
     const int QPB = vg_batch_bits_queries_per_block(c->stride);           // 256 / 128 / 64 by row length
     const int nq_pad = ((nq + QPB - 1) / QPB) * QPB;
     const int G = nq_pad / QPB;
@@ -525,7 +542,7 @@ static int scan_topk_batch_bits(vg_corpus *c, int metric, const void *queries, i
     int npart = std::max(1, c->cu_count * std::max(1, vg_sw(SW_VG_BATCH_BPC, 1)) / G);
     if (npart >= 8) npart = (npart / 8) * 8;
     npart = std::min(npart, 256);
-    npart = (int)std::min<long long>(npart, (c->n_rows + 31) / 32);
+    npart = (int)std::min<long long>(npart, ((masked ? c->mask_count : c->n_rows) + 31) / 32);
     const size_t qbytes = (size_t)nq_pad * c->stride;
     const size_t candbytes = (size_t)nq_pad * vg_batch_lists_per_query(c->n_rows, npart) * 64 * sizeof(uint64_t);
     const size_t keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
@@ -536,10 +553,14 @@ static int scan_topk_batch_bits(vg_corpus *c, int metric, const void *queries, i
     VG_TRY(vg_reserve_h_bq(c, qbytes));
     vg_stage_queries(c->h_bq, queries, nq, nq_pad, (size_t)c->stride, (size_t)c->dim * c->es);
     HIP_TRY(hipMemcpyAsync(c->d_bq, c->h_bq, qbytes, hipMemcpyHostToDevice, c->stream));
+    if (masked) VG_TRY(ensure_mask_positions(c));
     hipEvent_t *evs = vg_prof_slot(c, 0);
     if (evs) hipEventRecord(evs[0], c->stream);
-    const int rc = vg_batch_bits_launch(c->d_rows, c->n_rows, c->stride, (const uint8_t *)c->d_bq, nq_pad, nq, k,
-                                        metric == VG_DIST_JACCARD ? 1 : 0, c->d_bcand, npart, c->d_bkeys, c->stream);
+    const int jaccard = metric == VG_DIST_JACCARD ? 1 : 0;
+    const int rc = masked ? vg_batch_bits_masked_launch(c->d_rows, c->n_rows, c->stride, c->d_mask_pos, c->mask_count, (const uint8_t *)c->d_bq, nq_pad, nq, k,
+                                                        jaccard, c->d_bcand, npart, c->d_bkeys, c->stream)
+                          : vg_batch_bits_launch(c->d_rows, c->n_rows, c->stride, (const uint8_t *)c->d_bq, nq_pad, nq, k,
+                                                 jaccard, c->d_bcand, npart, c->d_bkeys, c->stream);
     if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
     if (rc == -1) { hipStreamSynchronize(c->stream); return -1; }
     if (rc != 0) return vg_fail(VG_ERR_HIP, "batched scan launch (bit vectors) failed: %s", hipGetErrorString((hipError_t)rc));
@@ -549,6 +570,13 @@ static int scan_topk_batch_bits(vg_corpus *c, int metric, const void *queries, i
     vg_collect_timing(c);
     unpack_keys(keys.data(), 64, nq, k, out_keys, out_counts);
     return VG_OK;
+}
+
+static int scan_topk_batch_bits(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts) {
+    return scan_topk_batch_bits_form(c, metric, queries, nq, k, out_keys, out_counts, false);
+}
+static int scan_topk_batch_bits_masked(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts) {
+    return scan_topk_batch_bits_form(c, metric, queries, nq, k, out_keys, out_counts, true);
 }
 
 // nq queries, NQ per pass of the multi-query scan kernel; all passes are enqueued back to back, one wait at the end
@@ -587,6 +615,11 @@ static int run_sliced(vg_corpus *c, batch_driver_t driver, int slice, int metric
     if (rc == -1)
         for (int i = 0; i < nq; ++i) out_counts[i] = 0;
     return rc;
+}
+
+int vg_batch_bits_masked_try(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts) {
+    if (!batch_bits_eligible(c, metric, k, nq, true)) return -1;
+    return run_sliced(c, scan_topk_batch_bits_masked, std::max(256, vg_sw(SW_VG_BATCH_SLICE, 4096)), metric, queries, nq, k, out_keys, out_counts);
 }
 
 extern "C" int vg_scan_topk_batch_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,

@@ -23,7 +23,11 @@
 //     exact distance - the expressions of vg_accum.h - and go through vgb_list_insert;
 //   * large corpora: the pre-pass and the staged real passes of vg_batch_common.h;
 //   * rows of 129 .. 512 bytes: vg_batch_bitsl.hip, the K dimension split over the wavefronts of a workgroup - the host entry points at
-//     the end of this file hand such strides on.
+//     the end of this file hand such strides on;
+//   * MASKED batches (GATHER): the tile loop runs over VIRTUAL tiles - 32 consecutive entries of the mask's position list
+//     (ascending scan positions, padded with 0xFFFFFFFF to whole tiles; built by vgbb_pos_* at the end of this file).  The producer lanes
+//     already compute the address of every row they load: here it is rows + position * stride, the position fetched two tiles ahead, the
+//     row one tile ahead.  Rows the mask excludes are never read; a tile's positions sit in LDS next to its bit counts and make the keys.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -41,8 +45,14 @@
 
 // NTB = k-steps per row (32 bits = 4 packed bytes each): rows up to 4 * NTB bytes, shorter ones zero-padded in the k dimension
 // JAC = Jaccard (else Hamming); PRE = the pre-pass variant (vg_batch_i8.hip): only the smallest distance of a query in a tile enters
-template <int NTB, bool JAC, bool PRE>
-__global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(BatchArgsBits a) {
+#define VGBB_NO_POS 0xFFFFFFFFu          // a padding entry of the position list: no row
+struct BatchArgsBitsGather : BatchArgsBits {
+    const uint32_t *pos;      // GATHER: tile_end * 32 entries - the allowed scan positions, ascending, VGBB_NO_POS behind the last
+};
+
+// GATHER = the masked form: tiles are runs of 32 entries of a.pos, not of 32 consecutive rows
+template <int NTB, bool JAC, bool PRE, bool GATHER>
+__global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::conditional_t<GATHER, BatchArgsBitsGather, BatchArgsBits> a) {
     constexpr int THREADS = 64 * VGBB_WAVES;
     constexpr int TILE_BYTES = NTB * 1024;                      // 32 rows x 32 NTB spread bytes
     constexpr int LPR = NTB <= 8 ? 4 : (NTB <= 16 ? 8 : 16);   // lanes that share a row of the packed tile, 8 bytes each
@@ -51,7 +61,8 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(Batch
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *tile0 = smem;                                                               // 2 tile buffers
     uint32_t *xcnt_lds = reinterpret_cast<uint32_t *>(smem + 2 * TILE_BYTES);            // [2][32]: |x| of a buffer's rows
-    uint32_t *qcnt_lds = xcnt_lds + 2 * VGBB_TILE;                                       // [waves][32]: |q|
+    uint32_t *xpos_lds = xcnt_lds + 2 * VGBB_TILE;                                       // GATHER only - [2][32]: the rows' scan positions
+    uint32_t *qcnt_lds = xcnt_lds + (GATHER ? 4 : 2) * VGBB_TILE;                        // [waves][32]: |q|
     float *thr_lds = reinterpret_cast<float *>(qcnt_lds + VGBB_QPB);                     // [waves][32]: current k-th best distance
     uint64_t *lists = reinterpret_cast<uint64_t *>(thr_lds + VGBB_QPB);                  // [waves][32][k]
 
@@ -120,6 +131,16 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(Batch
         if (pcols && tile * VGBB_TILE + prow < a.n_rows) v = *reinterpret_cast<const uint2 *>(pbase + (unsigned long long)tile * tile_stride);
         return v;
     };
+    // GATHER: the thread's entry of a virtual tile (the LPR lanes of a row read the same dword), and the row behind an entry
+    auto load_pos = [&](long long tile) __attribute__((always_inline)) -> uint32_t {
+        if constexpr (GATHER) return spreader ? a.pos[tile * VGBB_TILE + prow] : VGBB_NO_POS;
+        else return 0u;
+    };
+    auto load_gathered = [&](uint32_t p) __attribute__((always_inline)) -> uint2 {
+        uint2 v = make_uint2(0u, 0u);
+        if (pcols && p != VGBB_NO_POS) v = *reinterpret_cast<const uint2 *>(a.rows + (unsigned long long)p * (unsigned long long)a.stride + 8 * pj);
+        return v;
+    };
     // chunk c (0 .. 3) of the thread's 8 bytes into buffer `buf`
     auto spread_chunk = [&](auto cc, uint2 v, int buf) __attribute__((always_inline)) {
         constexpr int c = decltype(cc)::value;
@@ -127,12 +148,13 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(Batch
         const vgb_i32x4 o = vgbb_spread16((c & 1) ? (w >> 16) : (w & 0xFFFFu));
         if (pcols) *reinterpret_cast<vgb_i32x4 *>(pdst + buf * TILE_BYTES + c * 512) = o;
     };
-    auto store_count = [&](uint2 v, int buf) __attribute__((always_inline)) {
+    auto store_count = [&](uint2 v, int buf, uint32_t p) __attribute__((always_inline)) {
         if (!spreader) return;
         uint32_t cnt = (uint32_t)__builtin_popcount(v.x) + (uint32_t)__builtin_popcount(v.y);
 #pragma unroll
         for (int m = 1; m < LPR; m <<= 1) cnt += __shfl_xor(cnt, m);
         if (pj == 0) xcnt_lds[buf * VGBB_TILE + prow] = cnt;
+        if constexpr (GATHER) { if (pj == 0) xpos_lds[buf * VGBB_TILE + prow] = p; }
     };
 
     // ---- the gate.  Register r of lane (x, h) belongs to query qi(r, h) = (r&3) + 8*(r>>2) + 4*h; i = acc[r].
@@ -175,8 +197,8 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(Batch
     };
     // the slow path of a tile (vg_batch_i8.hip's): which registers hold a passing pair, then - one copy of the code, looping over the
     // pending registers by run-time index - the exact distance, the list inserts, the refreshed gate
-    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int xx) __attribute__((always_inline)) {
-        const long long row = tile * VGBB_TILE + x;
+    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int buf, int xx) __attribute__((always_inline)) {
+        const long long row = GATHER ? (long long)xpos_lds[buf * VGBB_TILE + x] : tile * VGBB_TILE + x;
         unsigned pend = 0;
         vgb_static_for<0, 16>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
@@ -198,7 +220,7 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(Batch
             }
             d = vg_clamp(d);
             // strict: rows arrive in scan order, a row that only ties the k-th best has the larger position and loses
-            const bool pass = (row < a.n_rows) && (d < thr_l);
+            const bool pass = (GATHER ? row != (long long)VGBB_NO_POS : row < a.n_rows) && (d < thr_l);
             unsigned long long m = __ballot(pass);
             if (!m) continue;
             if constexpr (PRE) {
@@ -238,10 +260,13 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(Batch
     vgb_i32x4 bq[BP];
     vgb_i32x16 acc;
     const uint32_t lds_tile0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)tile0;
+    uint32_t pos_next = VGBB_NO_POS, pos_next2 = VGBB_NO_POS;          // GATHER: the thread's entries of tiles t + 1 and t + 2 (clamped like tile_next)
     if (tile_first < tile_last) {
-        const uint2 v0 = load_packed(tile_first);
+        const uint32_t p0 = load_pos(tile_first);
+        if constexpr (GATHER) pos_next = load_pos(min(tile_first + 1, tile_last - 1));
+        const uint2 v0 = GATHER ? load_gathered(p0) : load_packed(tile_first);
         vgb_static_for<0, 4>([&](auto cc) { spread_chunk(cc, v0, 0); });
-        store_count(v0, 0);
+        store_count(v0, 0, p0);
     }
     __syncthreads();
     for (long long tile = tile_first; tile < tile_last; ++tile) {
@@ -258,15 +283,19 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(Batch
             vgb_wait_lds<in_flight_after>(bq[t % BP]);
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(areg[t], bq[t % BP], acc, 0, 0, 0);
             if constexpr (t + BP < NTB) vgb_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
-            if constexpr (t == 0) pk = load_packed(tile_next);
+            if constexpr (t == 0) {
+                if constexpr (GATHER) { pk = load_gathered(pos_next); pos_next2 = load_pos(min(tile + 2, tile_last - 1)); }
+                else pk = load_packed(tile_next);
+            }
             constexpr int S0 = NTB / 2, SD = NTB / 8;
             if constexpr (t >= S0 && (t - S0) % SD == 0 && (t - S0) / SD < 4)
                 spread_chunk(std::integral_constant<int, (t - S0) / SD>{}, pk, next_buf);
-            if constexpr (t == NTB - 1) store_count(pk, next_buf);
+            if constexpr (t == NTB - 1) store_count(pk, next_buf, pos_next);
             __builtin_amdgcn_sched_barrier(0);
         });
         const int xx = (int)xcnt_lds[cur_buf * VGBB_TILE + x];
-        if (judge_any(acc, xx)) judge_slow(acc, tile, xx);
+        if (judge_any(acc, xx)) judge_slow(acc, tile, cur_buf, xx);
+        if constexpr (GATHER) pos_next = pos_next2;
         __syncthreads();
     }
 
@@ -276,9 +305,11 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(Batch
     }
 }
 
+
 // ---- host side
-// The kernel instantiations are split over two translation units compiled from this file (build.py): the real-pass kernels and the
-// entry points here, the PRE kernels with -DVGBB_TU_PRE.
+// The kernel instantiations are split over four translation units compiled from this file (build.py): the real-pass kernels and the
+// entry points here, the PRE kernels with -DVGBB_TU_PRE; the masked form's real-pass kernels, its position-list kernels and its entry
+// points with -DVGBB_TU_GATHER, its PRE kernels with -DVGBB_TU_GATHER_PRE.
 // the ladder of row lengths: k-steps the kernels are instantiated for (rows of up to 32 / 64 / 96 / 128 bytes); 0: not served
 static int vgbb_ntb(long long stride_bytes) {
     if (stride_bytes < 16 || stride_bytes % 16 != 0) return 0;
@@ -286,27 +317,134 @@ static int vgbb_ntb(long long stride_bytes) {
     return ntb <= 8 ? 8 : (ntb <= 16 ? 16 : (ntb <= 24 ? 24 : (ntb <= 32 ? 32 : 0)));
 }
 
-template <int NTB, bool JAC, bool PRE>
-static int launch_bits(const BatchArgsBits &a, int blocks, size_t smem, hipStream_t stream) {
-    return vgb_launch(vg_batch_bits_kernel<NTB, JAC, PRE>, blocks, 64 * VGBB_WAVES, smem, stream, a);
+template <int NTB, bool JAC, bool PRE, bool GATHER, typename Args>
+static int launch_bits(const Args &a, int blocks, size_t smem, hipStream_t stream) {
+    return vgb_launch(vg_batch_bits_kernel<NTB, JAC, PRE, GATHER>, blocks, 64 * VGBB_WAVES, smem, stream, a);
 }
-template <bool PRE>
-static int launch_bits_ntb(const BatchArgsBits &a, int ntb, int jaccard, int blocks, size_t smem, hipStream_t stream) {
+template <bool PRE, bool GATHER, typename Args>
+static int launch_bits_ntb(const Args &a, int ntb, int jaccard, int blocks, size_t smem, hipStream_t stream) {
     switch (ntb) {
-    case 8: return jaccard ? launch_bits<8, true, PRE>(a, blocks, smem, stream) : launch_bits<8, false, PRE>(a, blocks, smem, stream);
-    case 16: return jaccard ? launch_bits<16, true, PRE>(a, blocks, smem, stream) : launch_bits<16, false, PRE>(a, blocks, smem, stream);
-    case 24: return jaccard ? launch_bits<24, true, PRE>(a, blocks, smem, stream) : launch_bits<24, false, PRE>(a, blocks, smem, stream);
-    case 32: return jaccard ? launch_bits<32, true, PRE>(a, blocks, smem, stream) : launch_bits<32, false, PRE>(a, blocks, smem, stream);
+    case 8: return jaccard ? launch_bits<8, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bits<8, false, PRE, GATHER>(a, blocks, smem, stream);
+    case 16: return jaccard ? launch_bits<16, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bits<16, false, PRE, GATHER>(a, blocks, smem, stream);
+    case 24: return jaccard ? launch_bits<24, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bits<24, false, PRE, GATHER>(a, blocks, smem, stream);
+    case 32: return jaccard ? launch_bits<32, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bits<32, false, PRE, GATHER>(a, blocks, smem, stream);
     }
     return -1;
 }
-#ifdef VGBB_TU_PRE
+#if defined(VGBB_TU_PRE)
 extern "C" int vgbb_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream) {
-    return launch_bits_ntb<true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+    return launch_bits_ntb<true, false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+#elif defined(VGBB_TU_GATHER_PRE)
+extern "C" int vgbb_launch_gather_pre(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream) {
+    return launch_bits_ntb<true, true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+#elif defined(VGBB_TU_GATHER)
+extern "C" int vgbb_launch_gather_real(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream) {
+    return launch_bits_ntb<false, true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+
+// ---- the position list of a row mask (bit p & 63 of word p >> 6: the row at scan position p is allowed): the allowed positions,
+// ascending, then VGBB_NO_POS up to a multiple of 32.  Two launches over blocks of VGBB_POS_WORDS mask words, a word per thread: the
+// blocks' popcount sums; then every block adds up the sums in front of it, scans its own words and writes its positions.
+#define VGBB_POS_WORDS 256
+// word w of the mask with the bits from n_rows on cleared (what lies behind the last row is not relied on); words past the mask: 0
+__device__ __forceinline__ uint64_t vgbb_mask_word(const uint64_t *mask, long long w, long long n_rows) {
+    const long long left = n_rows - w * 64;
+    if (left <= 0) return 0ull;
+    const uint64_t m = mask[w];
+    return left < 64 ? (m & ((1ull << left) - 1ull)) : m;
+}
+__device__ __forceinline__ uint32_t vgbb_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int m = 32; m; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__global__ __launch_bounds__(VGBB_POS_WORDS) void vgbb_pos_sums_kernel(const uint64_t *mask, long long n_rows, uint32_t *sums) {
+    __shared__ uint32_t wsum[VGBB_POS_WORDS / 64];
+    const int tid = threadIdx.x;
+    const uint32_t c = vgbb_wave_sum((uint32_t)__popcll(vgbb_mask_word(mask, (long long)blockIdx.x * VGBB_POS_WORDS + tid, n_rows)));
+    if ((tid & 63) == 0) wsum[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) sums[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+// pos: `cap` entries = the mask's count rounded up to 32 (nothing is written at or past cap, whatever the mask holds)
+__global__ __launch_bounds__(VGBB_POS_WORDS) void vgbb_pos_write_kernel(const uint64_t *mask, long long n_rows, const uint32_t *sums, uint32_t *pos,
+                                                                        long long cap) {
+    __shared__ uint32_t wfront[VGBB_POS_WORDS / 64], wown[VGBB_POS_WORDS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t front = 0;
+    for (unsigned b = (unsigned)tid; b < blockIdx.x; b += VGBB_POS_WORDS) front += sums[b];
+    front = vgbb_wave_sum(front);
+    const long long w = (long long)blockIdx.x * VGBB_POS_WORDS + tid;
+    uint64_t m = vgbb_mask_word(mask, w, n_rows);
+    const uint32_t c = (uint32_t)__popcll(m);
+    uint32_t inc = c;                                           // inclusive scan over the wavefront's words
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 0) wfront[wave] = front;
+    if (lane == 63) wown[wave] = inc;
+    __syncthreads();
+    long long at = (long long)wfront[0] + wfront[1] + wfront[2] + wfront[3] + (inc - c);
+    for (int i = 0; i < wave; ++i) at += wown[i];
+    const uint32_t p0 = (uint32_t)(w * 64);
+    while (m) {
+        const int bit = __builtin_ctzll(m);
+        m &= m - 1;
+        if (at < cap) pos[at] = p0 + (uint32_t)bit;
+        ++at;
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid < 32) {              // the last virtual tile's padding
+        const long long total = (long long)wfront[0] + wfront[1] + wfront[2] + wfront[3] + wown[0] + wown[1] + wown[2] + wown[3];
+        if (total + tid < ((total + 31) & ~31ll) && total + tid < cap) pos[total + tid] = VGBB_NO_POS;
+    }
+}
+// dwords of scratch (the blocks' sums) vg_batch_bits_pos_launch needs behind the list
+extern "C" size_t vg_batch_bits_pos_scratch_dwords(long long n_rows) { return (size_t)(((n_rows + 63) / 64 + VGBB_POS_WORDS - 1) / VGBB_POS_WORDS); }
+// dev_mask: ceil(n_rows / 64) words; dev_pos: `cap` entries (the mask's count rounded up to 32); 0 or a hipError_t
+extern "C" int vg_batch_bits_pos_launch(const uint64_t *dev_mask, long long n_rows, uint32_t *dev_pos, long long cap, uint32_t *dev_sums, hipStream_t stream) {
+    const unsigned blocks = (unsigned)vg_batch_bits_pos_scratch_dwords(n_rows);
+    if (blocks == 0) return 0;
+    hipLaunchKernelGGL(vgbb_pos_sums_kernel, dim3(blocks), dim3(VGBB_POS_WORDS), 0, stream, dev_mask, n_rows, dev_sums);
+    hipLaunchKernelGGL(vgbb_pos_write_kernel, dim3(blocks), dim3(VGBB_POS_WORDS), 0, stream, dev_mask, n_rows, (const uint32_t *)dev_sums, dev_pos, cap);
+    return (int)hipGetLastError();
+}
+
+// the masked form's LDS: vg_batch_bits_lds_bytes + the two tiles' positions (128-byte rows, k = 32: 133632); rows of up to 128 bytes only
+extern "C" size_t vg_batch_bits_masked_lds_bytes(long long stride_bytes, int k) {
+    const size_t plain = stride_bytes > 128 ? 0 : vg_batch_bits_lds_bytes(stride_bytes, k);
+    return plain ? plain + 2 * VGBB_TILE * 4 : 0;
+}
+
+// vg_batch_bits_launch over the n_pos rows of a position list (dev_pos: n_pos rounded up to 32 entries, vg_batch_bits_pos_launch's):
+// tiles, partitions, the pre-pass and the stages count VIRTUAL tiles.  The keys carry the rows' real scan positions.
+extern "C" int vg_batch_bits_masked_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_pos, long long n_pos,
+                                           const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
+                                           uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream) {
+    const size_t smem = vg_batch_bits_masked_lds_bytes(stride_bytes, k);
+    const long long ntiles = (n_pos + VGBB_TILE - 1) / VGBB_TILE;
+    if (!smem || nq_pad < VGBB_QPB || nq_pad % VGBB_QPB != 0 || npart < 1 || npart > VG_SEL_MAX_HEADS || npart > ntiles || n_pos < 1 || n_pos > n_rows) return -1;
+    BatchArgsBitsGather a;
+    a.rows = dev_rows; a.queries = dev_queries; a.cand = dev_cand; a.pos = dev_pos;
+    a.n_rows = n_rows; a.stride = stride_bytes; a.nq_pad = nq_pad; a.nq_real = nq_real; a.npart = npart; a.k = k;
+    const int variant = vgbb_ntb(stride_bytes) * 2 + (jaccard ? 1 : 0);
+    const int G = nq_pad / VGBB_QPB;
+    const int blocks = G * ((npart + 7) / 8) * 8;
+    long long pre = 0;
+    {
+        const int denom = vg_sw(SW_VG_BATCH_PREPASS, VGB_PREPASS_DENOM_DEFAULT);
+        if (denom > 0 && ntiles >= 65536) pre = ((ntiles / denom + npart - 1) / npart) * npart;
+    }
+    return vgb_run_staged(a, ntiles, pre, 400, dev_out_keys, stream,
+                          [&](const BatchArgsBitsGather &b) { return vgbb_launch_gather_pre(&b, variant, blocks, smem, stream); },
+                          [&](const BatchArgsBitsGather &b) { return vgbb_launch_gather_real(&b, variant, blocks, smem, stream); });
 }
 #else
 extern "C" int vgbb_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream) {
-    return launch_bits_ntb<false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+    return launch_bits_ntb<false, false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
 }
 
 // queries a workgroup serves: 256, or the long-row form's 128 (rows of up to 256 bytes) / 64 (up to 512)
@@ -350,4 +488,4 @@ extern "C" int vg_batch_bits_launch(const uint8_t *dev_rows, long long n_rows, l
                           [&](const BatchArgsBits &b) { return vgbb_launch_pre(&b, variant, blocks, smem, stream); },
                           [&](const BatchArgsBits &b) { return vgbb_launch_real(&b, variant, blocks, smem, stream); });
 }
-#endif   // !VGBB_TU_PRE
+#endif

@@ -15,6 +15,7 @@
 struct BatchArgsH;                      // vg_batch_h_defs.h
 struct BatchArgsI8;                     // vg_batch_i8.hip
 struct BatchArgsBits;                   // vg_batch_bits_defs.h
+struct BatchArgsBitsGather;             // vg_batch_bits.hip
 
 extern "C" {
 
@@ -52,6 +53,16 @@ int vg_batch_bits_launch(const uint8_t *dev_rows, long long n_rows, long long st
                          uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
 int vgbb_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);  // -DVGBB_TU_PRE; variant = 2 * k-steps + jaccard
 int vgbb_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);
+// its masked form (-DVGBB_TU_GATHER: real pass, position list, entry points; -DVGBB_TU_GATHER_PRE): rows of up to 128 bytes, gathered
+// through the list of a row mask's allowed positions - ascending, padded with 0xFFFFFFFF to a multiple of 32 entries
+size_t vg_batch_bits_masked_lds_bytes(long long stride_bytes, int k);      // 0: rows / k it does not serve
+size_t vg_batch_bits_pos_scratch_dwords(long long n_rows);                 // dev_sums of vg_batch_bits_pos_launch
+int vg_batch_bits_pos_launch(const uint64_t *dev_mask, long long n_rows, uint32_t *dev_pos, long long cap, uint32_t *dev_sums, hipStream_t stream);
+int vg_batch_bits_masked_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_pos, long long n_pos,
+                                const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
+                                uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
+int vgbb_launch_gather_pre(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream);
+int vgbb_launch_gather_real(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream);
 // ---- vg_batch_bitsl.hip: its long-row form (rows of 129 .. 512 bytes, the K dimension split over the wavefronts of a workgroup), reached
 // through the three entry points above
 size_t vg_batch_bitsl_lds_bytes(long long stride_bytes, int k);

@@ -176,6 +176,13 @@ struct vg_corpus {
     int64_t mask_cap_words = 0;
     std::vector<uint64_t> mask_host;          // the same words on the host (vg_corpus_clone copies them)
     int64_t mask_count = -1;                  // rows allowed; -1: no mask
+    // the mask as a list (vg_batch_bits.hip, GATHER): the allowed scan positions, ascending, padded with 0xFFFFFFFF to a multiple of 32
+    // (+ the build's scratch behind them).  Built by the first matrix-core masked batch behind a mask, 4 bytes per allowed row;
+    // mask_pos_valid is cleared wherever d_mask changes or the mask is dropped (vg_mask_upload, vg_drop_mask)
+    uint32_t *d_mask_pos = nullptr;
+    size_t mask_pos_bytes = 0;
+    bool mask_pos_valid = false;
+    int last_batch_masked_path = 0;           // vg_batch_masked_last_path (vectorgpu_diag.h)
     // labeled scans (vg_rowpred.hip, vg_multi_labeled.hip): a uint32 per scan position in device memory (VG_LABEL_NONE: the row
     // matches no query).  Read by the labeled scans only; lifetime rule for rule the mask's (vg_drop_labels).  d_label_bits: the bitmap
     // "rows the query may see" a row predicate's scan builds for itself (vg_pred_bits_enqueue) - scratch, never the user's mask
@@ -317,7 +324,7 @@ static inline int64_t vg_pair_position(unsigned long long pair) { return (int64_
 static inline void vg_drop_within_results(vg_corpus *c) {           // (held range-scan results name positions of the rows as they were)
     c->within_keys.clear(); c->within_matches = 0; c->wb_keys.clear(); c->wb_matches.clear();
 }
-static inline void vg_drop_mask(vg_corpus *c) { c->mask_count = -1; c->mask_host.clear(); }   // (the device words stay allocated for the next mask)
+static inline void vg_drop_mask(vg_corpus *c) { c->mask_count = -1; c->mask_host.clear(); c->mask_pos_valid = false; }   // (the device words stay allocated for the next mask)
 int vg_mask_upload(vg_corpus *c);             // vg_scan_masked.hip: mask_host -> d_mask
 static inline void vg_drop_labels(vg_corpus *c) { c->has_labels = false; }   // (the device dwords stay allocated for the next labels)
 static inline void vg_drop_values(vg_corpus *c) { c->has_values = false; }   // (the same: the device values stay allocated)
@@ -590,6 +597,9 @@ bool vg_scan_filter_policy(const vg_corpus *c);      // vg_filter.hip: filter sw
 int vg_ensure_filter_counters(vg_corpus *c);         // vg_filter.hip: d_filter_evals[2] + pinned mirror
 bool vg_scan_filter_name(vg_corpus *c, int metric, char *out, size_t out_len);   // vg_filter.hip: kernel name when the filter serves the scan
 bool vg_batch_keys_are_scan_exact(const vg_corpus *c, int metric, int k);   // vg_batch_api.hip: a batch's floats are the single scan's
+// vg_batch_api.hip: a masked bit-vector batch on the matrix cores, behind vg_scan_topk_batch_masked_keys' checks (a mask with allowed
+// rows is set, out_counts are zero); -1: not served / handed on - the multi-query scan answers, the counts are zero again
+int vg_batch_bits_masked_try(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts);
 long long vg_bf16_shadow_stride(const vg_corpus *c);               // vg_batch_api.hip: row stride of the bf16 shadow copy of an f32 corpus
 int vg_ensure_bf16_shadow(vg_corpus *c);                           // vg_batch_api.hip: build / extend it (corpus stream)
 int vg_ensure_q8_shadow(vg_corpus *c);                             // vg_filter.hip: the int8 shadow copy + per-row (scale, residual norm)

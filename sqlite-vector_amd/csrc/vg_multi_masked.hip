@@ -166,11 +166,12 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
     return VG_OK;
 }
 
-// packed keys (distance image << 32 | position local to this corpus), ascending, nq x k: the form a multi-shard caller merges.
-// Slots behind out_counts[i] are not written.  `floors`: a key per query, read by an after form only.  `out_labels` (nq x k): the
-// winners' labels, filled by a grouped form only.
-int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
-                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member) {
+// vg_fused_batch_run's two halves, for a caller with a path of its own in between (vg_scan_topk_batch_masked_keys below).  fused_batch_check: the
+// argument checks; the counts are zero behind it; *nothing: the answer is complete as it stands (an empty mask, no rows) - no launch.
+static int fused_batch_check(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                             uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member,
+                             bool *nothing) {
+    *nothing = false;
     const bool grouped = f.single.result.with_labels();
     if (!c || !queries || !out_counts || (f.single.after && !floors) || (f.rows == VG_QROWS_LABEL && !qlabels) ||
         (f.rows == VG_QROWS_MEMBER && !member)) return vg_fail(VG_ERR_INVALID, "%s: NULL argument", f.who);
@@ -186,11 +187,19 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
     for (int i = 0; i < nq && f.rows == VG_QROWS_LABEL; ++i)
         if (qlabels[i] == VG_LABEL_NONE) return vg_fail(VG_ERR_INVALID, "%s: query %d: VG_LABEL_NONE names no row", f.who, i);
     if (int rcm = vg_metric_check(c->vtype, metric, f.who)) return rcm;
-    if ((f.rows == VG_QROWS_MASK && c->mask_count == 0) || c->n_rows == 0) return VG_OK;      // an empty mask: no launch
+    if ((f.rows == VG_QROWS_MASK && c->mask_count == 0) || c->n_rows == 0) { *nothing = true; return VG_OK; }      // an empty mask: no launch
     HIP_TRY(hipSetDevice(c->device));
+    return VG_OK;
+}
+// fused_batch_scan: the batch behind its checks - the multi-query scan (*path = 5) or the form's single scans (6)
+static int fused_batch_scan(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                            uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member,
+                            int *path) {
+    const bool grouped = f.single.result.with_labels();
     VgShape s{};
     scan_fn_t fn = nullptr;
     const int NQ = fused_multi_plan(c, metric, &s, &fn, f.pick);
+    *path = NQ == 0 ? 6 : 5;
     if (NQ == 0) {                                               // no multi-query form: the single scans of the form, one by one
         const size_t row_bytes = (size_t)c->dim * c->es;
         for (int i = 0; i < nq; ++i) {
@@ -215,12 +224,35 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
     return fused_batch_multi(c, f, metric, fn, NQ, s, queries, nq, floors, qlabels, k, out_keys, out_counts, out_labels, member);
 }
 
+// packed keys (distance image << 32 | position local to this corpus), ascending, nq x k: the form a multi-shard caller merges.
+// Slots behind out_counts[i] are not written.  `floors`: a key per query, read by an after form only.  `out_labels` (nq x k): the
+// winners' labels, filled by a grouped form only.
+int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                       uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member) {
+    bool nothing = false;
+    int path = 0;
+    const int rc = fused_batch_check(c, f, metric, queries, nq, k, floors, out_keys, out_counts, qlabels, out_labels, member, &nothing);
+    if (rc != VG_OK || nothing) return rc;
+    return fused_batch_scan(c, f, metric, queries, nq, k, floors, out_keys, out_counts, qlabels, out_labels, member, &path);
+}
+
+// The plain masked batch: behind the checks, bit-vector batches the matrix cores serve go through the position list of the mask
+// (vg_batch_bits_masked_try, vg_batch_api.hip; -1: not such a batch, or handed on) - everything else, as before, through the scans
 extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
                                               int *out_counts) {
     const VgFusedBatchForm form = {"vg_scan_topk_batch_masked", vg_pick_multi<MultiFamily<VG_MQ_MASKED>>, VG_QROWS_MASK,
                                    vg_fused_form("vg_scan_topk_masked", "masked", vg_pick_scan_masked, VG_ROWS_MASK)};
-    return vg_fused_batch_run(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts);
+    bool nothing = false;
+    int rc = fused_batch_check(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts, nullptr, nullptr, nullptr, &nothing);
+    if (rc != VG_OK || nothing) return rc;
+    rc = vg_batch_bits_masked_try(c, metric, queries, nq, k, out_keys, out_counts);
+    if (rc != -1) { c->last_batch_masked_path = 8; return rc; }
+    int path = 0;
+    rc = fused_batch_scan(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts, nullptr, nullptr, nullptr, &path);
+    c->last_batch_masked_path = path;
+    return rc;
 }
+extern "C" int vg_batch_masked_last_path(const vg_corpus *c) { return c ? c->last_batch_masked_path : 0; }
 
 extern "C" int vg_scan_topk_batch_masked(vg_corpus *c, int metric, const void *queries, int nq, int k, int64_t *out_rowids,
                                          double *out_dist, int *out_counts) {

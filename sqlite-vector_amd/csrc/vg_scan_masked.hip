@@ -21,6 +21,7 @@
 // mask_host (ceil(n_rows / 64) words, tail bits clear) -> d_mask; the scan that follows runs on the same stream
 int vg_mask_upload(vg_corpus *c) {
     HIP_TRY(hipSetDevice(c->device));
+    c->mask_pos_valid = false;                               // (the position list of the words as they were)
     const int64_t words = (int64_t)c->mask_host.size();
     if (words == 0) return VG_OK;
     if (c->mask_cap_words < words) {
