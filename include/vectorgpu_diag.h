@@ -138,8 +138,8 @@ int vg_shards_within_last_launches(const vg_shards *s);
 int vg_within_batch_last_path(const vg_corpus *c);
 /* vg_batch_masked_last_path: which path answered the last vg_scan_topk_batch_masked[_keys] on this handle, in the numbering above -
  * 5 = the multi-query scan, 6 = one masked scan per query, 8 = the integer matrix cores gathering the allowed rows through the mask's
- * position list (vg_batch_bits.hip: Hamming / Jaccard batches of VG_BATCH_BITS_MIN_QUERIES queries or more over uint8 rows of
- * 16 .. 128 bytes, a multiple of 16, k <= 32), 0 = no call yet.  A call that returns before any launch (an error, an empty mask, no
+ * position list (Hamming / Jaccard batches of VG_BATCH_BITS_MIN_QUERIES queries or more over uint8 rows of a multiple of 16 bytes, k <= 32 -
+ * vg_batch_bits.hip: rows of 16 .. 128 bytes; vg_batch_bitsl.hip: 144 .. 512 bytes, k <= 28 at 208 .. 256), 0 = no call yet.  A call that returns before any launch (an error, an empty mask, no
  * rows) leaves it as it was. */
 int vg_batch_masked_last_path(const vg_corpus *c);
 int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);

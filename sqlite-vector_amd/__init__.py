@@ -1100,7 +1100,7 @@ class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeled
 
     def batch_masked_last_path(self):
         """which path answered the last scan_topk_batch_masked: 5 multi-query scan, 6 one masked scan per query, 8 bit vectors
-        (Hamming / Jaccard) on the int8 matrix cores through the mask's position list, 0 no call yet"""
+        (Hamming / Jaccard, rows of up to 512 bytes) on the int8 matrix cores through the mask's position list, 0 no call yet"""
         return int(lib().vg_batch_masked_last_path(self.h))
 
     def scan_within_masked(self, metric, query, radius, limit=None):

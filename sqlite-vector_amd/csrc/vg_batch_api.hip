@@ -510,14 +510,20 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
 #define VG_BATCH_BITS_MIN_QUERIES_DEFAULT 64   // (0: never.  Measured, tools/bits_batch_bench.py / DESIGN.md 3.25: at 32 queries over 32-byte rows the multi-query scan still wins)
 #define VG_BATCH_BITS_MIN_QUERIES_LONG_DEFAULT 32   // rows beyond 128 bytes, all four ladder steps (at 16 queries the multi-query scan wins or ties Hamming at every row length, from 32 on the matrix cores win every cell by more than both spreads)
 #define VG_BATCH_BITS_MASKED_MIN_QUERIES_DEFAULT 64   // masked batches (the gathering form, rows of up to 128 bytes).  Measured, tools/bits_batch_masked_bench.py / DESIGN.md 3.29: at 32 queries the multi-query scan still wins a contiguous 10 % mask over 32-byte rows (0.89 against 1.01 ms Hamming), from 64 on the matrix cores win every cell by more than both spreads
-// masked: the batch of vg_scan_topk_batch_masked - a mask with allowed rows, rows of up to 128 bytes, a threshold of its own
+// masked batches over rows beyond 128 bytes (vg_batch_bitsl.hip's gathering form), per ladder step.  Measured, tools/bits_batch_masked_bench.py
+// --row-bytes 192 256 384 512 / DESIGN.md 3.30: at 16 queries the multi-query scan wins or ties the full mask at 192 / 256 / 384 bytes (Hamming
+// at 256: 2.12 against 3.10 ms) and 512-byte rows win every cell (the closest: Hamming, full mask, 3.50 against 3.91 ms); from 32 on the matrix
+// cores win every cell of every step by more than both spreads
+#define VG_BATCH_BITS_MASKED_MIN_QUERIES_LONG_DEFAULT(stride) ((stride) > 384 ? 16 : 32)
+// masked: the batch of vg_scan_topk_batch_masked - a mask with allowed rows, thresholds of its own
 static bool batch_bits_eligible(const vg_corpus *c, int metric, int k, int nq, bool masked = false) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_U8 || !vg_metric_is_bits(metric)) return false;
-    if (masked && (c->stride > 128 || c->mask_count <= 0)) return false;
-    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, masked ? VG_BATCH_BITS_MASKED_MIN_QUERIES_DEFAULT
-                                                                 : (c->stride > 128 ? VG_BATCH_BITS_MIN_QUERIES_LONG_DEFAULT : VG_BATCH_BITS_MIN_QUERIES_DEFAULT));
+    if (masked && c->mask_count <= 0) return false;
+    const bool long_rows = c->stride > 128;
+    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, masked ? (long_rows ? VG_BATCH_BITS_MASKED_MIN_QUERIES_LONG_DEFAULT(c->stride) : VG_BATCH_BITS_MASKED_MIN_QUERIES_DEFAULT)
+                                                                 : (long_rows ? VG_BATCH_BITS_MIN_QUERIES_LONG_DEFAULT : VG_BATCH_BITS_MIN_QUERIES_DEFAULT));
     if (min_q <= 0 || nq < min_q) return false;
-    return (masked ? vg_batch_bits_masked_lds_bytes(c->stride, k) : vg_batch_bits_lds_bytes(c->stride, k)) != 0;   // k <= 32, rows of up to 512 bytes (193 - 256 bytes: k <= 29)
+    return (masked ? vg_batch_bits_masked_lds_bytes(c->stride, k) : vg_batch_bits_lds_bytes(c->stride, k)) != 0;   // k <= 32, rows of up to 512 bytes (193 - 256 bytes: k <= 29, masked k <= 28)
 }
 
 // the mask of the handle as the list the gathering kernel walks (vg_internal.h: d_mask_pos), built on the corpus stream when the

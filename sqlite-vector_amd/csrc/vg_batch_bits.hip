@@ -45,12 +45,7 @@
 
 // NTB = k-steps per row (32 bits = 4 packed bytes each): rows up to 4 * NTB bytes, shorter ones zero-padded in the k dimension
 // JAC = Jaccard (else Hamming); PRE = the pre-pass variant (vg_batch_i8.hip): only the smallest distance of a query in a tile enters
-#define VGBB_NO_POS 0xFFFFFFFFu          // a padding entry of the position list: no row
-struct BatchArgsBitsGather : BatchArgsBits {
-    const uint32_t *pos;      // GATHER: tile_end * 32 entries - the allowed scan positions, ascending, VGBB_NO_POS behind the last
-};
-
-// GATHER = the masked form: tiles are runs of 32 entries of a.pos, not of 32 consecutive rows
+// GATHER = the masked form (BatchArgsBitsGather, VGBB_NO_POS: vg_batch_bits_defs.h): tiles are runs of 32 entries of a.pos, not of 32 consecutive rows
 template <int NTB, bool JAC, bool PRE, bool GATHER>
 __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::conditional_t<GATHER, BatchArgsBitsGather, BatchArgsBits> a) {
     constexpr int THREADS = 64 * VGBB_WAVES;
@@ -413,9 +408,11 @@ extern "C" int vg_batch_bits_pos_launch(const uint64_t *dev_mask, long long n_ro
     return (int)hipGetLastError();
 }
 
-// the masked form's LDS: vg_batch_bits_lds_bytes + the two tiles' positions (128-byte rows, k = 32: 133632); rows of up to 128 bytes only
+// the masked form's LDS: vg_batch_bits_lds_bytes + the two tiles' positions (128-byte rows, k = 32: 133632); rows beyond 128 bytes: the
+// long-row form's answer
 extern "C" size_t vg_batch_bits_masked_lds_bytes(long long stride_bytes, int k) {
-    const size_t plain = stride_bytes > 128 ? 0 : vg_batch_bits_lds_bytes(stride_bytes, k);
+    if (stride_bytes > 128) return vg_batch_bitsl_masked_lds_bytes(stride_bytes, k);
+    const size_t plain = vg_batch_bits_lds_bytes(stride_bytes, k);
     return plain ? plain + 2 * VGBB_TILE * 4 : 0;
 }
 
@@ -424,9 +421,13 @@ extern "C" size_t vg_batch_bits_masked_lds_bytes(long long stride_bytes, int k) 
 extern "C" int vg_batch_bits_masked_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_pos, long long n_pos,
                                            const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
                                            uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream) {
+    if (stride_bytes > 128)
+        return vg_batch_bitsl_masked_launch(dev_rows, n_rows, stride_bytes, dev_pos, n_pos, dev_queries, nq_pad, nq_real, k, jaccard, dev_cand, npart,
+                                            dev_out_keys, stream);
     const size_t smem = vg_batch_bits_masked_lds_bytes(stride_bytes, k);
     const long long ntiles = (n_pos + VGBB_TILE - 1) / VGBB_TILE;
-    if (!smem || nq_pad < VGBB_QPB || nq_pad % VGBB_QPB != 0 || npart < 1 || npart > VG_SEL_MAX_HEADS || npart > ntiles || n_pos < 1 || n_pos > n_rows) return -1;
+    const int QPB = vg_batch_bits_queries_per_block(stride_bytes);
+    if (!smem || nq_pad < QPB || nq_pad % QPB != 0 || npart < 1 || npart > VG_SEL_MAX_HEADS || npart > ntiles || n_pos < 1 || n_pos > n_rows) return -1;
     BatchArgsBitsGather a;
     a.rows = dev_rows; a.queries = dev_queries; a.cand = dev_cand; a.pos = dev_pos;
     a.n_rows = n_rows; a.stride = stride_bytes; a.nq_pad = nq_pad; a.nq_real = nq_real; a.npart = npart; a.k = k;

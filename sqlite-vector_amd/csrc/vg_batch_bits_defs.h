@@ -25,6 +25,12 @@ struct BatchArgsBits {
     int seed;                 // staged real passes (vg_batch_common.h): partition 0 starts its lists from init_keys
 };
 
+// the masked (GATHER) forms of both units: tiles are runs of 32 entries of the mask's position list, not of 32 consecutive rows
+#define VGBB_NO_POS 0xFFFFFFFFu          // a padding entry of the position list: no row
+struct BatchArgsBitsGather : BatchArgsBits {
+    const uint32_t *pos;      // GATHER: tile_end * 32 entries - the allowed scan positions, ascending, VGBB_NO_POS behind the last
+};
+
 // ---- the range forms (every row within a radius): vg_batch_bits_within.hip (rows of up to 128 bytes) and its K-split
 // sibling vg_batch_bitsl_within.hip (129 .. 512 bytes; 3.28), which share the arguments, the gate and the emission below.
 struct BatchArgsBitsWithin {

@@ -16,7 +16,12 @@
 //   * KS = 2 has two tile buffers (2 x 48 / 64 KiB): the next tile is spread between the MFMAs of the current one, as in the short form.
 //     KS = 4 has ONE (96 / 128 KiB of the 160): the next tile's packed bytes are loaded at the top of the k loop, kept in registers (6 /
 //     8 VGPRs) and spread after the exchange.  Barriers per tile: after the k loop, after the partials are written, after they are
-//     read (the buffer is free again); the one-buffer form has a fourth behind its spreading.
+//     read (the buffer is free again); the one-buffer form has a fourth behind its spreading;
+//   * MASKED batches (GATHER): the tile loop runs over VIRTUAL tiles - 32 consecutive entries of the mask's position list
+//     (vg_batch_bits.hip builds it).  Thread (prow, pj) fetches entry prow of the tile TWO ahead into a register and, one tile ahead, its
+//     units of the row at rows + position * stride: 16 lanes read 128 contiguous bytes of one row.  A tile's positions lie in LDS next
+//     to its bit counts; the lead takes both into registers before the tile's third barrier - past it the other wavefronts already
+//     write the next tile's - and makes the keys from them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -32,9 +37,9 @@
 
 // KS = K-slices (wavefronts that share 32 queries), NTBW = k-steps (32 bits each) per slice: rows up to 4 KS NTBW bytes, shorter ones
 // zero-padded in the k dimension; JAC = Jaccard (else Hamming); PRE = the pre-pass variant: only the smallest distance of a query in a
-// tile enters
-template <int KS, int NTBW, bool JAC, bool PRE>
-__global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(BatchArgsBits a) {
+// tile enters; GATHER = the masked form: tiles are runs of 32 entries of a.pos, not of 32 consecutive rows
+template <int KS, int NTBW, bool JAC, bool PRE, bool GATHER>
+__global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(std::conditional_t<GATHER, BatchArgsBitsGather, BatchArgsBits> a) {
     constexpr int THREADS = 64 * VGBL_WAVES;
     constexpr int QG = VGBL_WAVES / KS, QPB = QG * 32;
     constexpr int NTB = KS * NTBW;                              // k-steps of a whole row
@@ -47,7 +52,8 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *tile0 = smem;                                                               // NBUF tile buffers
     uint32_t *xcnt_lds = reinterpret_cast<uint32_t *>(smem + NBUF * TILE_BYTES);         // [NBUF][32][4]: |x| of a buffer's rows, by quarter
-    uint32_t *qpart_lds = xcnt_lds + NBUF * VGBB_TILE * 4;                               // [waves][32]: |q| of a wavefront's slice
+    uint32_t *xpos_lds = xcnt_lds + NBUF * VGBB_TILE * 4;                                // GATHER only - [NBUF][32]: the rows' scan positions
+    uint32_t *qpart_lds = xpos_lds + (GATHER ? NBUF * VGBB_TILE : 0);                    // [waves][32]: |q| of a wavefront's slice
     uint32_t *qcnt_lds = qpart_lds + VGBL_WAVES * 32;                                    // [QG][32]: |q|
     float *thr_lds = reinterpret_cast<float *>(qcnt_lds + QPB);                          // [QG][32]: current k-th best distance
     uint64_t *lists = reinterpret_cast<uint64_t *>(thr_lds + QPB);                       // [QG][32][k]
@@ -127,6 +133,20 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
                 pk[u] = *reinterpret_cast<const uint2 *>(pbase + (unsigned long long)tile * tile_stride + 128 * u);
         });
     };
+    // GATHER: the thread's entry of a virtual tile (16 consecutive lanes read 16 consecutive dwords; the 16 threads of a row the same
+    // one), and the row behind an entry - a padding entry loads nothing and spreads zeros
+    auto load_pos = [&](long long tile) __attribute__((always_inline)) -> uint32_t {
+        if constexpr (GATHER) return a.pos[tile * VGBB_TILE + prow];
+        else return 0u;
+    };
+    auto load_gathered = [&](uint32_t p) __attribute__((always_inline)) {
+        const uint8_t *src = a.rows + (unsigned long long)p * (unsigned long long)a.stride + 8 * pj;
+        vgb_static_for<0, UPT>([&](auto uc) {
+            constexpr int u = decltype(uc)::value;
+            pk[u] = make_uint2(0u, 0u);
+            if (p != VGBB_NO_POS && 8 * (pj + 16 * u) < (int)a.stride) pk[u] = *reinterpret_cast<const uint2 *>(src + 128 * u);
+        });
+    };
     // chunk ci (0 .. NCH - 1: unit ci / 4, its 16 bits ci % 4) into buffer `buf`
     auto spread_chunk = [&](auto cc, int buf) __attribute__((always_inline)) {
         constexpr int u = decltype(cc)::value / 4, c = decltype(cc)::value % 4;
@@ -134,12 +154,13 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
         const vgb_i32x4 o = vgbb_spread16((c & 1) ? (w >> 16) : (w & 0xFFFFu));
         if (8 * (pj + 16 * u) < (int)a.stride) *reinterpret_cast<vgb_i32x4 *>(pdst + buf * TILE_BYTES + (64 * u + c) * 512) = o;
     };
-    auto store_count = [&](int buf) __attribute__((always_inline)) {
+    auto store_count = [&](int buf, uint32_t p) __attribute__((always_inline)) {
         uint32_t cnt = 0;
         vgb_static_for<0, UPT>([&](auto uc) { constexpr int u = decltype(uc)::value; cnt += (uint32_t)__builtin_popcount(pk[u].x) + (uint32_t)__builtin_popcount(pk[u].y); });
         cnt += __shfl_xor(cnt, 16);
         cnt += __shfl_xor(cnt, 32);
         if (lane < 16) xcnt_lds[(buf * VGBB_TILE + prow) * 4 + (wave >> 1)] = cnt;
+        if constexpr (GATHER) { if (pj == 0) xpos_lds[buf * VGBB_TILE + prow] = p; }
     };
 
     // ---- the gate (vg_batch_bits.hip's; the lead's).  Register r of lane (x, h) belongs to query qi(r, h) = (r&3) + 8*(r>>2) + 4*h; i = acc[r].
@@ -184,8 +205,10 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
     };
     // the slow path of a tile: which registers hold a passing pair, then - one copy of the code, looping over the pending registers by
     // run-time index - the exact distance, the list inserts, the refreshed gate
-    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int xx) __attribute__((always_inline)) {
-        const long long row = tile * VGBB_TILE + x;
+    // (GATHER: the row's scan position xp comes in a register, like xx - the lead fetched both before the tile's third barrier, behind
+    // which the other wavefronts write the next tile's counts and positions)
+    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int xx, uint32_t xp) __attribute__((always_inline)) {
+        const long long row = GATHER ? (long long)xp : tile * VGBB_TILE + x;
         unsigned pend = 0;
         vgb_static_for<0, 16>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
@@ -207,7 +230,7 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
             }
             d = vg_clamp(d);
             // strict: rows arrive in scan order, a row that only ties the k-th best has the larger position and loses
-            const bool pass = (row < a.n_rows) && (d < thr_l);
+            const bool pass = (GATHER ? xp != VGBB_NO_POS : row < a.n_rows) && (d < thr_l);
             unsigned long long m = __ballot(pass);
             if (!m) continue;
             if constexpr (PRE) {
@@ -250,10 +273,13 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
     vgb_i32x4 bq[BP];
     vgb_i32x16 acc;
     const uint32_t lds_tile0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)tile0;
+    uint32_t pos_next = VGBB_NO_POS, pos_next2 = VGBB_NO_POS;          // GATHER: the thread's entries of tiles t + 1 and t + 2 (clamped like tile_next)
     if (tile_first < tile_last) {
-        load_packed(tile_first);
+        const uint32_t p0 = load_pos(tile_first);
+        if constexpr (GATHER) { pos_next = load_pos(min(tile_first + 1, tile_last - 1)); load_gathered(p0); }
+        else load_packed(tile_first);
         vgb_static_for<0, NCH>([&](auto cc) { spread_chunk(cc, 0); });
-        store_count(0);
+        store_count(0, p0);
     }
     __syncthreads();
     for (long long tile = tile_first; tile < tile_last; ++tile) {
@@ -269,10 +295,13 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
             vgb_wait_lds<in_flight_after>(bq[t % BP]);
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(areg[t], bq[t % BP], acc, 0, 0, 0);
             if constexpr (t + BP < NTBW) vgb_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
-            if constexpr (t == 0) load_packed(tile_next);
+            if constexpr (t == 0) {
+                if constexpr (GATHER) { load_gathered(pos_next); pos_next2 = load_pos(min(tile + 2, tile_last - 1)); }
+                else load_packed(tile_next);
+            }
             if constexpr (NBUF == 2 && t >= S0 && (t - S0) % SD == 0 && (t - S0) / SD < NCH)
                 spread_chunk(std::integral_constant<int, (t - S0) / SD>{}, next_buf);
-            if constexpr (NBUF == 2 && t == NTBW - 1) store_count(next_buf);
+            if constexpr (NBUF == 2 && t == NTBW - 1) store_count(next_buf, pos_next);
             __builtin_amdgcn_sched_barrier(0);
         });
         __syncthreads();                                                    // the tile is consumed (two buffers: and the next one complete)
@@ -286,6 +315,7 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
             });
         __syncthreads();
         int xx = 0;
+        uint32_t xp = VGBB_NO_POS;
         if (lead) {
             vgb_static_for<0, 4 * (KS - 1)>([&](auto jc) {
                 constexpr int s = decltype(jc)::value / 4, j = decltype(jc)::value % 4;
@@ -294,14 +324,16 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
             });
             const uint4 xc = reinterpret_cast<const uint4 *>(xcnt_lds)[cur_buf * VGBB_TILE + x];
             xx = (int)(xc.x + xc.y + xc.z + xc.w);
+            if constexpr (GATHER) xp = xpos_lds[cur_buf * VGBB_TILE + x];
         }
         __syncthreads();                                                    // the exchange is read: the buffer may be spread into again
-        if (lead && judge_any(acc, xx)) judge_slow(acc, tile, xx);
+        if (lead && judge_any(acc, xx)) judge_slow(acc, tile, xx, xp);
         if constexpr (NBUF == 1) {
             vgb_static_for<0, NCH>([&](auto cc) { spread_chunk(cc, 0); });
-            store_count(0);
+            store_count(0, pos_next);
             __syncthreads();
         }
+        if constexpr (GATHER) pos_next = pos_next2;
     }
 
     if (lead)
@@ -312,8 +344,8 @@ __global__ __launch_bounds__(64 * VGBL_WAVES, 1) void vg_batch_bitsl_kernel(Batc
 }
 
 // ---- host side
-// Two translation units are compiled from this file (build.py): the real-pass kernels and the entry points here, the PRE kernels with
-// -DVGBL_TU_PRE.
+// Four translation units are compiled from this file (build.py): the real-pass kernels and the entry points here, the PRE kernels with
+// -DVGBL_TU_PRE; the masked form's real-pass kernels and its entry points with -DVGBL_TU_GATHER, its PRE kernels with -DVGBL_TU_GATHER_PRE.
 // the ladder of row lengths: rows of up to 192 / 256 bytes run as KS = 2 with 24 / 32 k-steps per slice, up to 384 / 512 as KS = 4;
 // 64 KS + NTBW, 0: not served
 static int vgbl_step(long long stride_bytes) {
@@ -321,27 +353,72 @@ static int vgbl_step(long long stride_bytes) {
     return stride_bytes <= 192 ? 2 * 64 + 24 : (stride_bytes <= 256 ? 2 * 64 + 32 : (stride_bytes <= 384 ? 4 * 64 + 24 : 4 * 64 + 32));
 }
 
-template <int KS, int NTBW, bool JAC, bool PRE>
-static int launch_bitsl(const BatchArgsBits &a, int blocks, size_t smem, hipStream_t stream) {
-    return vgb_launch(vg_batch_bitsl_kernel<KS, NTBW, JAC, PRE>, blocks, 64 * VGBL_WAVES, smem, stream, a);
+template <int KS, int NTBW, bool JAC, bool PRE, bool GATHER, typename Args>
+static int launch_bitsl(const Args &a, int blocks, size_t smem, hipStream_t stream) {
+    return vgb_launch(vg_batch_bitsl_kernel<KS, NTBW, JAC, PRE, GATHER>, blocks, 64 * VGBL_WAVES, smem, stream, a);
 }
-template <bool PRE>
-static int launch_bitsl_step(const BatchArgsBits &a, int step, int jaccard, int blocks, size_t smem, hipStream_t stream) {
+template <bool PRE, bool GATHER, typename Args>
+static int launch_bitsl_step(const Args &a, int step, int jaccard, int blocks, size_t smem, hipStream_t stream) {
     switch (step) {
-    case 2 * 64 + 24: return jaccard ? launch_bitsl<2, 24, true, PRE>(a, blocks, smem, stream) : launch_bitsl<2, 24, false, PRE>(a, blocks, smem, stream);
-    case 2 * 64 + 32: return jaccard ? launch_bitsl<2, 32, true, PRE>(a, blocks, smem, stream) : launch_bitsl<2, 32, false, PRE>(a, blocks, smem, stream);
-    case 4 * 64 + 24: return jaccard ? launch_bitsl<4, 24, true, PRE>(a, blocks, smem, stream) : launch_bitsl<4, 24, false, PRE>(a, blocks, smem, stream);
-    case 4 * 64 + 32: return jaccard ? launch_bitsl<4, 32, true, PRE>(a, blocks, smem, stream) : launch_bitsl<4, 32, false, PRE>(a, blocks, smem, stream);
+    case 2 * 64 + 24: return jaccard ? launch_bitsl<2, 24, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bitsl<2, 24, false, PRE, GATHER>(a, blocks, smem, stream);
+    case 2 * 64 + 32: return jaccard ? launch_bitsl<2, 32, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bitsl<2, 32, false, PRE, GATHER>(a, blocks, smem, stream);
+    case 4 * 64 + 24: return jaccard ? launch_bitsl<4, 24, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bitsl<4, 24, false, PRE, GATHER>(a, blocks, smem, stream);
+    case 4 * 64 + 32: return jaccard ? launch_bitsl<4, 32, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bitsl<4, 32, false, PRE, GATHER>(a, blocks, smem, stream);
     }
     return -1;
 }
-#ifdef VGBL_TU_PRE
+#if defined(VGBL_TU_PRE)
 extern "C" int vgbl_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream) {
-    return launch_bitsl_step<true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+    return launch_bitsl_step<true, false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+#elif defined(VGBL_TU_GATHER_PRE)
+extern "C" int vgbl_launch_gather_pre(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream) {
+    return launch_bitsl_step<true, true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+#elif defined(VGBL_TU_GATHER)
+extern "C" int vgbl_launch_gather_real(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream) {
+    return launch_bitsl_step<false, true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+
+// the masked form's LDS: vg_batch_bitsl_lds_bytes + the positions of each tile buffer's rows (NBUF x 128 bytes)
+//   <= 192 bytes  134 400 at k = 32
+//   <= 256       131 072 + 3 328 + 1024 k = 163 072 at k = 28: k = 29 .. 32 are handed on (the unmasked form fills the LDS exactly at 29)
+//   <= 384       116 864 at k = 32
+//   <= 512       149 632 at k = 32
+extern "C" size_t vg_batch_bitsl_masked_lds_bytes(long long stride_bytes, int k) {
+    const size_t plain = vg_batch_bitsl_lds_bytes(stride_bytes, k);
+    if (!plain) return 0;
+    const size_t bytes = plain + ((vgbl_step(stride_bytes) >> 6) == 2 ? 2 : 1) * VGBB_TILE * 4;
+    return bytes <= VGBB_LDS_LIMIT ? bytes : 0;
+}
+
+// vg_batch_bits_masked_launch's arguments and answers (vg_batch_bits.hip hands rows beyond 128 bytes on to here): tiles, partitions,
+// the pre-pass and the stages count VIRTUAL tiles of the position list; the keys carry the rows' real scan positions
+extern "C" int vg_batch_bitsl_masked_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_pos, long long n_pos,
+                                            const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
+                                            uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream) {
+    const size_t smem = vg_batch_bitsl_masked_lds_bytes(stride_bytes, k);
+    const int QPB = vg_batch_bitsl_queries_per_block(stride_bytes);
+    const long long ntiles = (n_pos + VGBB_TILE - 1) / VGBB_TILE;
+    if (!smem || nq_pad < QPB || nq_pad % QPB != 0 || npart < 1 || npart > VG_SEL_MAX_HEADS || npart > ntiles || n_pos < 1 || n_pos > n_rows) return -1;
+    BatchArgsBitsGather a;
+    a.rows = dev_rows; a.queries = dev_queries; a.cand = dev_cand; a.pos = dev_pos;
+    a.n_rows = n_rows; a.stride = stride_bytes; a.nq_pad = nq_pad; a.nq_real = nq_real; a.npart = npart; a.k = k;
+    const int variant = vgbl_step(stride_bytes) * 2 + (jaccard ? 1 : 0);
+    const int G = nq_pad / QPB;
+    const int blocks = G * ((npart + 7) / 8) * 8;
+    long long pre = 0;
+    {
+        const int denom = vg_sw(SW_VG_BATCH_PREPASS, VGB_PREPASS_DENOM_DEFAULT);
+        if (denom > 0 && ntiles >= 65536) pre = ((ntiles / denom + npart - 1) / npart) * npart;
+    }
+    return vgb_run_staged(a, ntiles, pre, 400, dev_out_keys, stream,
+                          [&](const BatchArgsBitsGather &b) { return vgbl_launch_gather_pre(&b, variant, blocks, smem, stream); },
+                          [&](const BatchArgsBitsGather &b) { return vgbl_launch_gather_real(&b, variant, blocks, smem, stream); });
 }
 #else
 extern "C" int vgbl_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream) {
-    return launch_bitsl_step<false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+    return launch_bitsl_step<false, false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
 }
 
 extern "C" int vg_batch_bitsl_queries_per_block(long long stride_bytes) {
@@ -387,4 +464,4 @@ extern "C" int vg_batch_bitsl_launch(const uint8_t *dev_rows, long long n_rows, 
                           [&](const BatchArgsBits &b) { return vgbl_launch_pre(&b, variant, blocks, smem, stream); },
                           [&](const BatchArgsBits &b) { return vgbl_launch_real(&b, variant, blocks, smem, stream); });
 }
-#endif   // !VGBL_TU_PRE
+#endif

@@ -15,7 +15,7 @@
 struct BatchArgsH;                      // vg_batch_h_defs.h
 struct BatchArgsI8;                     // vg_batch_i8.hip
 struct BatchArgsBits;                   // vg_batch_bits_defs.h
-struct BatchArgsBitsGather;             // vg_batch_bits.hip
+struct BatchArgsBitsGather;             // vg_batch_bits_defs.h
 
 extern "C" {
 
@@ -53,8 +53,9 @@ int vg_batch_bits_launch(const uint8_t *dev_rows, long long n_rows, long long st
                          uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
 int vgbb_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);  // -DVGBB_TU_PRE; variant = 2 * k-steps + jaccard
 int vgbb_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);
-// its masked form (-DVGBB_TU_GATHER: real pass, position list, entry points; -DVGBB_TU_GATHER_PRE): rows of up to 128 bytes, gathered
-// through the list of a row mask's allowed positions - ascending, padded with 0xFFFFFFFF to a multiple of 32 entries
+// its masked form (-DVGBB_TU_GATHER: real pass, position list, entry points; -DVGBB_TU_GATHER_PRE): rows gathered through the list of a
+// row mask's allowed positions - ascending, padded with 0xFFFFFFFF to a multiple of 32 entries; rows beyond 128 bytes (up to 512) are
+// handed on to vg_batch_bitsl.hip's masked form
 size_t vg_batch_bits_masked_lds_bytes(long long stride_bytes, int k);      // 0: rows / k it does not serve
 size_t vg_batch_bits_pos_scratch_dwords(long long n_rows);                 // dev_sums of vg_batch_bits_pos_launch
 int vg_batch_bits_pos_launch(const uint64_t *dev_mask, long long n_rows, uint32_t *dev_pos, long long cap, uint32_t *dev_sums, hipStream_t stream);
@@ -72,6 +73,14 @@ int vg_batch_bitsl_launch(const uint8_t *dev_rows, long long n_rows, long long s
                           uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
 int vgbl_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);  // -DVGBL_TU_PRE; variant = 2 * (64 K-slices + k-steps per slice) + jaccard
 int vgbl_launch_real(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream);
+// its masked form (-DVGBL_TU_GATHER: real pass and entry points; -DVGBL_TU_GATHER_PRE), reached through vg_batch_bits_masked_lds_bytes /
+// vg_batch_bits_masked_launch: the same position list; rows of 193 .. 256 bytes: k <= 28
+size_t vg_batch_bitsl_masked_lds_bytes(long long stride_bytes, int k);     // 0: rows / k it does not serve
+int vg_batch_bitsl_masked_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_pos, long long n_pos,
+                                 const uint8_t *dev_queries, int nq_pad, int nq_real, int k, int jaccard,
+                                 uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
+int vgbl_launch_gather_pre(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream);
+int vgbl_launch_gather_real(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream);
 // ---- vg_batch_bits_within.hip: the range form of vg_batch_bits.hip (rows of up to 128 bytes): every row within a radius, a radius per
 // query.  dev_desc: nq_pad VgWithinQuery descriptors (vg_scan_multi.h); one launch over all rows, keys appended to the queries' regions
 size_t vg_batch_bits_within_lds_bytes(long long stride_bytes);             // 0: rows it does not serve

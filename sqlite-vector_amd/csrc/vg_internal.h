@@ -176,7 +176,7 @@ struct vg_corpus {
     int64_t mask_cap_words = 0;
     std::vector<uint64_t> mask_host;          // the same words on the host (vg_corpus_clone copies them)
     int64_t mask_count = -1;                  // rows allowed; -1: no mask
-    // the mask as a list (vg_batch_bits.hip, GATHER): the allowed scan positions, ascending, padded with 0xFFFFFFFF to a multiple of 32
+    // the mask as a list (vg_batch_bits.hip and vg_batch_bitsl.hip, GATHER: rows of up to 512 bytes): the allowed scan positions, ascending, padded with 0xFFFFFFFF to a multiple of 32
     // (+ the build's scratch behind them).  Built by the first matrix-core masked batch behind a mask, 4 bytes per allowed row;
     // mask_pos_valid is cleared wherever d_mask changes or the mask is dropped (vg_mask_upload, vg_drop_mask)
     uint32_t *d_mask_pos = nullptr;

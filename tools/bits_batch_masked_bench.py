@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Masked Hamming / Jaccard batches: the gathering matrix-core form (vg_batch_bits.hip GATHER, batch_masked_last_path() == 8) against the
+"""Masked Hamming / Jaccard batches: the gathering matrix-core form (vg_batch_bits.hip / vg_batch_bitsl.hip GATHER, batch_masked_last_path() == 8) against the
 masked multi-query scan (path 5) on ONE handle, in ONE process (10M rows, k = 20; Hamming over random bytes, Jaccard over the
 mixed-density rows of tools/jaccard_bench.py):
 
-  row lengths  32 bytes (256 bits) and 128 bytes (1024 bits)
+  row lengths  32 bytes (256 bits) and 128 bytes (1024 bits); --row-bytes 256 512 [192 384]: the long-row form's ladder steps
   nq           16, 32, 64, 256, 1024
   masks        100 %, a random 10 %, a random 1 %, and 10 % as one contiguous run of rows
   The two paths ALTERNATE step by step on the same build: VG_BATCH_BITS_MIN_QUERIES=2 takes the matrix cores, =0 switches them off - the
@@ -14,9 +14,11 @@ mixed-density rows of tools/jaccard_bench.py):
   `position_list_ms`: what the first matrix-core batch behind a set_mask takes longer than the median one (16 queries; the build of
   the position list), median of 5.
   `threshold`: the smallest measured nq from which on (it and every larger one) the matrix cores are faster in EVERY measured cell by
-  more than both paths' min-to-max spreads; 0 (switched off) when none qualifies.
+  more than both paths' min-to-max spreads; 0 (switched off) when none qualifies.  `threshold_by_row_bytes`: the same rule over the
+  cells of one row length - the long-row form ships a default per ladder step.
 
     python tools/bits_batch_masked_bench.py [--rows 10000000] [--steps 20] [--warmup 3] > profiles/bits_batch_masked_bench_10M_u8_k20.json
+    python tools/bits_batch_masked_bench.py --row-bytes 192 256 384 512 > profiles/bits_batch_masked_long_bench_10M_u8_k20.json
 """
 import argparse
 import json
@@ -62,6 +64,7 @@ def main():
     st = lambda a, nd: {"min_ms": round(float(np.min(a)), nd), "median_ms": round(float(np.median(a)), nd),
                         "max_ms": round(float(np.max(a)), nd), "spread_ms": round(float(np.max(a) - np.min(a)), nd)}
     wins = {nq: True for nq in args.nq}
+    wins_dim = {dim: {nq: True for nq in args.nq} for dim in args.row_bytes}
     makers = {"hamming": (pkg.HAMMING, lambda rng, n, dim: rng.integers(0, 256, (n, dim), dtype=np.uint8)), "jaccard": (pkg.JACCARD, mixed_rows)}
     for name in args.metrics:
         metric, make = makers[name]
@@ -105,6 +108,7 @@ def main():
                     b["multi_over_matrix_wall"] = round(b["multi_query"]["wall"]["median_ms"] / b["matrix_cores"]["wall"]["median_ms"], 3)
                     b["faster_by_more_than_both_spreads"] = bool(gain > max(b["multi_query"]["wall"]["spread_ms"], b["matrix_cores"]["wall"]["spread_ms"]))
                     wins[nq] = wins[nq] and b["faster_by_more_than_both_spreads"]
+                    wins_dim[dim][nq] = wins_dim[dim][nq] and b["faster_by_more_than_both_spreads"]
                     e["nq_%d" % nq] = b
                 # the one-off cost of the position list: the first matrix-core batch behind set_mask against the median one
                 q16 = np.ascontiguousarray(qs[:16])
@@ -117,8 +121,9 @@ def main():
                 out["cases"]["%s_%d_bytes_%s" % (name, dim, kind)] = e
                 print("%s %d bytes, mask %s: done" % (name, dim, kind), file=sys.stderr, flush=True)
             c.close()
-    ok = [nq for i, nq in enumerate(sorted(args.nq)) if all(wins[m] for m in sorted(args.nq)[i:])]      # (it and every larger measured batch)
-    out["threshold"] = ok[0] if ok else 0
+    first_ok = lambda w: next((nq for i, nq in enumerate(sorted(args.nq)) if all(w[m] for m in sorted(args.nq)[i:])), 0)      # (it and every larger measured batch)
+    out["threshold"] = first_ok(wins)
+    out["threshold_by_row_bytes"] = {str(dim): first_ok(wins_dim[dim]) for dim in args.row_bytes}
     print(json.dumps(out, indent=1))
 
 
