@@ -134,7 +134,9 @@ int vg_shards_within_last_launches(const vg_shards *s);
  * vg_within_batch_last_path: which path answered the last batch range scan of any form on this handle - 5 = the multi-query range scan,
  * 6 = one range scan per query, 8 = the integer matrix cores (vg_batch_bits_within.hip: unmasked, unlabeled Hamming / Jaccard batches of
  * VG_BATCH_BITS_MIN_QUERIES queries or more over uint8 rows of 16 .. 128 bytes, a multiple of 16; vg_batch_bitsl_within.hip: rows of
- * 144 .. 512 bytes and at least one workgroup's 128 (<= 256 bytes) / 64 queries), 0 = no call yet. */
+ * 144 .. 512 bytes and at least one workgroup's 128 (<= 256 bytes) / 64 queries; and MASKED such batches (vg_scan_within_batch_masked)
+ * of max(VG_BATCH_BITS_MIN_QUERIES, 128) queries or more over rows of 16 .. 128 bytes under a mask with allowed rows: the gathering form
+ * of vg_batch_bits_within.hip - masked batches over longer rows keep 5), 0 = no call yet. */
 int vg_within_batch_last_path(const vg_corpus *c);
 /* vg_batch_masked_last_path: which path answered the last vg_scan_topk_batch_masked[_keys] on this handle, in the numbering above -
  * 5 = the multi-query scan, 6 = one masked scan per query, 8 = the integer matrix cores gathering the allowed rows through the mask's

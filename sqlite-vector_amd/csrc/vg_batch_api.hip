@@ -526,9 +526,9 @@ static bool batch_bits_eligible(const vg_corpus *c, int metric, int k, int nq, b
     return (masked ? vg_batch_bits_masked_lds_bytes(c->stride, k) : vg_batch_bits_lds_bytes(c->stride, k)) != 0;   // k <= 32, rows of up to 512 bytes (193 - 256 bytes: k <= 29, masked k <= 28)
 }
 
-// the mask of the handle as the list the gathering kernel walks (vg_internal.h: d_mask_pos), built on the corpus stream when the
+// the mask of the handle as the list the gathering kernels walk (vg_internal.h: d_mask_pos), built on the corpus stream when the
 // mask changed since the last one was
-static int ensure_mask_positions(vg_corpus *c) {
+int vg_ensure_mask_positions(vg_corpus *c) {
     if (c->mask_pos_valid) return VG_OK;
     const size_t cap = ((size_t)c->mask_count + 31) / 32 * 32;
     VG_TRY(vg_dev_reserve(&c->d_mask_pos, &c->mask_pos_bytes, (cap + vg_batch_bits_pos_scratch_dwords(c->n_rows)) * sizeof(uint32_t)));
@@ -559,7 +559,7 @@ static int scan_topk_batch_bits_form(vg_corpus *c, int metric, const void *queri
     VG_TRY(vg_reserve_h_bq(c, qbytes));
     vg_stage_queries(c->h_bq, queries, nq, nq_pad, (size_t)c->stride, (size_t)c->dim * c->es);
     HIP_TRY(hipMemcpyAsync(c->d_bq, c->h_bq, qbytes, hipMemcpyHostToDevice, c->stream));
-    if (masked) VG_TRY(ensure_mask_positions(c));
+    if (masked) VG_TRY(vg_ensure_mask_positions(c));
     hipEvent_t *evs = vg_prof_slot(c, 0);
     if (evs) hipEventRecord(evs[0], c->stream);
     const int jaccard = metric == VG_DIST_JACCARD ? 1 : 0;

@@ -42,6 +42,12 @@ struct BatchArgsBitsWithin {
     int nq_pad, npart;        // nq_pad: a multiple of the unit's queries per workgroup (256; the long rows' 128 / 64)
     int tiles_per_part;
 };
+// the masked (GATHER) range form of vg_batch_bits_within.hip: tiles are runs of 32 entries of the mask's position list;
+// tiles_per_part and npart then count tiles of the LIST, n_rows stays the corpus' (no entry names a row at or past it)
+struct BatchArgsBitsWithinGather : BatchArgsBitsWithin {
+    const uint32_t *pos;      // n_tiles * 32 entries - the allowed scan positions, ascending, VGBB_NO_POS behind the last
+    long long n_tiles;        // ceil(allowed rows / 32)
+};
 
 // A row matches iff d <= r.  Every distance here is finite and >= 0: a radius below zero (-0.0 is not) matches nothing and stands as
 // -Inf, the padding query's; otherwise d <= r <=> d < thr with thr the next float above r (+Inf stays +Inf) - the strict test the

@@ -15,7 +15,11 @@
 //     pair the float test accepts, its survivors are decided by fl((u - i) / u) <= r;
 //   * emission (vgbb_within_emit): per accumulator register with a match the keys are compacted by ballot, ONE atomicAdd per (query, tile)
 //     reserves their place in the query's region and vector stores write them while they fit; the count keeps counting past the capacity
-//     - that is how the host learns the size it needs (vg_multi_within.hip).  Order inside a region is free: the host sorts.
+//     - that is how the host learns the size it needs (vg_multi_within.hip).  Order inside a region is free: the host sorts;
+//   * MASKED batches (GATHER; a unit of its own, -DVGBW_TU_GATHER): the tile loop of vg_batch_bits.hip's masked form - a
+//     tile is 32 consecutive entries of the mask's position list (ascending scan positions, 0xFFFFFFFF behind the last), the entry fetched
+//     two tiles ahead, the row at rows + position * stride one tile ahead.  Rows the mask excludes are never read; a tile's positions sit
+//     in LDS next to its bit counts, under the same two-buffer scheme, and make the keys; a padding entry has a distance and never a key.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -33,8 +37,9 @@
 
 // NTB = k-steps per row (32 bits = 4 packed bytes each): rows up to 4 * NTB bytes, shorter ones zero-padded in the k dimension
 // JAC = Jaccard (else Hamming)
-template <int NTB, bool JAC>
-__global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kernel(BatchArgsBitsWithin a) {
+// GATHER = the masked form (BatchArgsBitsWithinGather, VGBB_NO_POS: vg_batch_bits_defs.h): tiles are runs of 32 entries of a.pos, not of 32 consecutive rows
+template <int NTB, bool JAC, bool GATHER>
+__global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kernel(std::conditional_t<GATHER, BatchArgsBitsWithinGather, BatchArgsBitsWithin> a) {
     constexpr int THREADS = 64 * VGBB_WAVES;
     constexpr int TILE_BYTES = NTB * 1024;                      // 32 rows x 32 NTB spread bytes
     constexpr int LPR = NTB <= 8 ? 4 : (NTB <= 16 ? 8 : 16);   // lanes that share a row of the packed tile, 8 bytes each
@@ -43,7 +48,8 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kerne
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint8_t *tile0 = smem;                                                               // 2 tile buffers
     uint32_t *xcnt_lds = reinterpret_cast<uint32_t *>(smem + 2 * TILE_BYTES);            // [2][32]: |x| of a buffer's rows
-    uint32_t *qcnt_lds = xcnt_lds + 2 * VGBB_TILE;                                       // [waves][32]: |q|
+    uint32_t *xpos_lds = xcnt_lds + 2 * VGBB_TILE;                                       // GATHER only - [2][32]: the rows' scan positions
+    uint32_t *qcnt_lds = xcnt_lds + (GATHER ? 4 : 2) * VGBB_TILE;                        // [waves][32]: |q|
     float *rad_lds = reinterpret_cast<float *>(qcnt_lds + VGBB_QPB);                     // [waves][32]: the radius (-Inf: matches nothing)
     unsigned long long *out_lds = reinterpret_cast<unsigned long long *>(rad_lds + VGBB_QPB);      // [waves][32]: the region [count | cap keys]
     unsigned long long *cap_lds = out_lds + VGBB_QPB;                                    // [waves][32]: its capacity
@@ -96,7 +102,10 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kerne
     __syncthreads();
 
     // ---- the tile's producer side.  Thread (prow, pj) owns packed bytes [8 pj, +8) of row prow of a tile = chunk columns 4 pj .. 4 pj + 3
-    const long long ntiles = (a.n_rows + VGBB_TILE - 1) / VGBB_TILE;
+    const long long ntiles = [&]() __attribute__((always_inline)) -> long long {
+        if constexpr (GATHER) return a.n_tiles;                     // tiles of the position list
+        else return (a.n_rows + VGBB_TILE - 1) / VGBB_TILE;
+    }();
     const long long tile_first = (long long)part * a.tiles_per_part;
     const long long tile_last = min(tile_first + a.tiles_per_part, ntiles);
     const bool spreader = tid < SPREADERS;                          // (wave-uniform)
@@ -110,6 +119,18 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kerne
         if (pcols && tile * VGBB_TILE + prow < a.n_rows) v = *reinterpret_cast<const uint2 *>(pbase + (unsigned long long)tile * tile_stride);
         return v;
     };
+    // GATHER: the thread's entry of a tile of the list (the LPR lanes of a row read the same dword; tile < ntiles: inside the list), and the
+    // row behind an entry - a padding entry loads nothing and spreads as zeros
+    auto load_pos = [&](long long tile) __attribute__((always_inline)) -> uint32_t {
+        if constexpr (GATHER) return spreader ? a.pos[tile * VGBB_TILE + prow] : VGBB_NO_POS;
+        else return 0u;
+    };
+    auto load_gathered = [&](uint32_t p) __attribute__((always_inline)) -> uint2 {
+        uint2 v = make_uint2(0u, 0u);
+        if (pcols && p != VGBB_NO_POS && (long long)p < a.n_rows)
+            v = *reinterpret_cast<const uint2 *>(a.rows + (unsigned long long)p * (unsigned long long)a.stride + 8 * pj);
+        return v;
+    };
     // chunk c (0 .. 3) of the thread's 8 bytes into buffer `buf`
     auto spread_chunk = [&](auto cc, uint2 v, int buf) __attribute__((always_inline)) {
         constexpr int c = decltype(cc)::value;
@@ -117,12 +138,13 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kerne
         const vgb_i32x4 o = vgbb_spread16((c & 1) ? (w >> 16) : (w & 0xFFFFu));
         if (pcols) *reinterpret_cast<vgb_i32x4 *>(pdst + buf * TILE_BYTES + c * 512) = o;
     };
-    auto store_count = [&](uint2 v, int buf) __attribute__((always_inline)) {
+    auto store_count = [&](uint2 v, int buf, uint32_t p) __attribute__((always_inline)) {
         if (!spreader) return;
         uint32_t cnt = (uint32_t)__builtin_popcount(v.x) + (uint32_t)__builtin_popcount(v.y);
 #pragma unroll
         for (int m = 1; m < LPR; m <<= 1) cnt += __shfl_xor(cnt, m);
         if (pj == 0) xcnt_lds[buf * VGBB_TILE + prow] = cnt;
+        if constexpr (GATHER) { if (pj == 0) xpos_lds[buf * VGBB_TILE + prow] = p; }
     };
 
     // ---- the gate.  Register r of lane (x, h) belongs to query qi(r, h) = (r&3) + 8*(r>>2) + 4*h; i = acc[r].  Constants of the launch:
@@ -153,8 +175,8 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kerne
     };
     // the slow path of a tile: which registers hold a passing pair, then - one copy of the code, looping over the pending registers by
     // run-time index - the exact distance, the exact test against the radius, the keys' way out
-    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int xx) __attribute__((always_inline)) {
-        const long long row = tile * VGBB_TILE + x;
+    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int buf, int xx) __attribute__((always_inline)) {
+        const long long row = GATHER ? (long long)xpos_lds[buf * VGBB_TILE + x] : tile * VGBB_TILE + x;
         unsigned pend = 0;
         vgb_static_for<0, 16>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
@@ -174,8 +196,9 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kerne
                 d = (float)(qc + (uint32_t)xx - 2u * i);
             }
             d = vg_clamp(d);
-            // (rows at or past n_rows spread as zeros: they have a distance, and never a key.  -Inf in rad_w: nothing is <= it)
-            const bool pass = (row < a.n_rows) && (d <= rad_w[qi]);
+            // (rows at or past n_rows - GATHER: padding entries - spread as zeros: they have a distance, and never a key.  -Inf in rad_w:
+            // nothing is <= it)
+            const bool pass = (GATHER ? row != (long long)VGBB_NO_POS : row < a.n_rows) && (d <= rad_w[qi]);
             vgbb_within_emit(pass, vg_make_key(d, (uint32_t)row), reinterpret_cast<unsigned long long *>((uintptr_t)out_w[qi]), cap_w[qi], lane);
         }
     };
@@ -186,10 +209,13 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kerne
     vgb_i32x4 bq[BP];
     vgb_i32x16 acc;
     const uint32_t lds_tile0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)tile0;
+    uint32_t pos_next = VGBB_NO_POS, pos_next2 = VGBB_NO_POS;          // GATHER: the thread's entries of tiles t + 1 and t + 2 (clamped like tile_next)
     if (tile_first < tile_last) {
-        const uint2 v0 = load_packed(tile_first);
+        const uint32_t p0 = load_pos(tile_first);
+        if constexpr (GATHER) pos_next = load_pos(min(tile_first + 1, tile_last - 1));
+        const uint2 v0 = GATHER ? load_gathered(p0) : load_packed(tile_first);
         vgb_static_for<0, 4>([&](auto cc) { spread_chunk(cc, v0, 0); });
-        store_count(v0, 0);
+        store_count(v0, 0, p0);
     }
     __syncthreads();
     for (long long tile = tile_first; tile < tile_last; ++tile) {
@@ -206,15 +232,21 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_within_kerne
             vgb_wait_lds<in_flight_after>(bq[t % BP]);
             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(areg[t], bq[t % BP], acc, 0, 0, 0);
             if constexpr (t + BP < NTB) vgb_lds_read128<1024 * (t + BP)>(bq[t % BP], baddr);
-            if constexpr (t == 0) pk = load_packed(tile_next);
+            if constexpr (t == 0) {
+                if constexpr (GATHER) { pk = load_gathered(pos_next); pos_next2 = load_pos(min(tile + 2, tile_last - 1)); }
+                else pk = load_packed(tile_next);
+            }
             constexpr int S0 = NTB / 2, SD = NTB / 8;
             if constexpr (t >= S0 && (t - S0) % SD == 0 && (t - S0) / SD < 4)
                 spread_chunk(std::integral_constant<int, (t - S0) / SD>{}, pk, next_buf);
-            if constexpr (t == NTB - 1) store_count(pk, next_buf);
+            if constexpr (t == NTB - 1) store_count(pk, next_buf, pos_next);
             __builtin_amdgcn_sched_barrier(0);
         });
         const int xx = (int)xcnt_lds[cur_buf * VGBB_TILE + x];
-        if (judge_any(acc, xx)) judge_slow(acc, tile, xx);
+        // (the judge reads cur_buf's counts and positions; this iteration's producers wrote next_buf's only, and write cur_buf's again
+        // only behind the barrier below)
+        if (judge_any(acc, xx)) judge_slow(acc, tile, cur_buf, xx);
+        if constexpr (GATHER) pos_next = pos_next2;
         __syncthreads();
     }
 }
@@ -227,6 +259,46 @@ static int vgbw_ntb(long long stride_bytes) {
     return ntb <= 8 ? 8 : (ntb <= 16 ? 16 : (ntb <= 24 ? 24 : 32));
 }
 
+// The kernel instantiations are split over two translation units compiled from this file (build.py): the unmasked kernels and their
+// entry points here, the masked form's kernels and entry points with -DVGBW_TU_GATHER.
+template <int NTB, bool GATHER, typename Args>
+static int launch_within(const Args &a, int jaccard, int blocks, size_t smem, hipStream_t stream) {
+    return jaccard ? vgb_launch(vg_batch_bits_within_kernel<NTB, true, GATHER>, blocks, 64 * VGBB_WAVES, smem, stream, a)
+                   : vgb_launch(vg_batch_bits_within_kernel<NTB, false, GATHER>, blocks, 64 * VGBB_WAVES, smem, stream, a);
+}
+template <bool GATHER, typename Args>
+static int launch_within_ntb(const Args &a, int jaccard, int blocks, size_t smem, hipStream_t stream) {
+    switch (vgbw_ntb(a.stride)) {
+    case 8: return launch_within<8, GATHER>(a, jaccard, blocks, smem, stream);
+    case 16: return launch_within<16, GATHER>(a, jaccard, blocks, smem, stream);
+    case 24: return launch_within<24, GATHER>(a, jaccard, blocks, smem, stream);
+    case 32: return launch_within<32, GATHER>(a, jaccard, blocks, smem, stream);
+    }
+    return -1;
+}
+
+#if defined(VGBW_TU_GATHER)
+// the masked form's LDS: vg_batch_bits_within_lds_bytes + the two tiles' positions (128-byte rows: 72192)
+extern "C" size_t vg_batch_bits_within_masked_lds_bytes(long long stride_bytes) {
+    const size_t plain = vg_batch_bits_within_lds_bytes(stride_bytes);
+    return plain ? plain + 2 * VGBB_TILE * 4 : 0;
+}
+
+// vg_batch_bits_within_launch over the n_pos rows of a position list (dev_pos: n_pos rounded up to 32 entries, vg_batch_bits_pos_launch's):
+// tiles and partitions count tiles of the LIST.  The keys carry the rows' real scan positions.
+extern "C" int vg_batch_bits_within_masked_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_pos, long long n_pos,
+                                                  const uint8_t *dev_queries, const void *dev_desc, int nq_pad, int jaccard, int npart, hipStream_t stream) {
+    const size_t smem = vg_batch_bits_within_masked_lds_bytes(stride_bytes);
+    const long long ntiles = (n_pos + VGBB_TILE - 1) / VGBB_TILE;
+    if (!smem || nq_pad < VGBB_QPB || nq_pad % VGBB_QPB != 0 || npart < 1 || npart > ntiles || n_pos < 1 || n_pos > n_rows || !dev_pos) return -1;
+    BatchArgsBitsWithinGather a;
+    a.rows = dev_rows; a.queries = dev_queries; a.desc = dev_desc; a.pos = dev_pos;
+    a.n_rows = n_rows; a.stride = stride_bytes; a.nq_pad = nq_pad; a.npart = npart; a.n_tiles = ntiles;
+    a.tiles_per_part = (int)((ntiles + npart - 1) / npart);
+    const int G = nq_pad / VGBB_QPB;
+    return launch_within_ntb<true>(a, jaccard, G * ((npart + 7) / 8) * 8, smem, stream);
+}
+#else
 // LDS bytes of one workgroup: two spread tiles, their rows' bit counts, per query |q|, radius, region, capacity
 // (128-byte rows: 65536 + 256 + 1024 + 1024 + 2048 + 2048 = 71936).  0: rows it does not serve
 extern "C" size_t vg_batch_bits_within_lds_bytes(long long stride_bytes) {
@@ -234,12 +306,6 @@ extern "C" size_t vg_batch_bits_within_lds_bytes(long long stride_bytes) {
     if (!NTB) return 0;
     const size_t bytes = (size_t)2 * NTB * 1024 + 2 * VGBB_TILE * 4 + VGBB_QPB * 4 + VGBB_QPB * 4 + (size_t)VGBB_QPB * 8 * 2;
     return bytes <= VGBB_LDS_LIMIT ? bytes : 0;
-}
-
-template <int NTB>
-static int launch_within(const BatchArgsBitsWithin &a, int jaccard, int blocks, size_t smem, hipStream_t stream) {
-    return jaccard ? vgb_launch(vg_batch_bits_within_kernel<NTB, true>, blocks, 64 * VGBB_WAVES, smem, stream, a)
-                   : vgb_launch(vg_batch_bits_within_kernel<NTB, false>, blocks, 64 * VGBB_WAVES, smem, stream, a);
 }
 
 // dev_rows: the corpus' row-major rows; dev_queries: nq_pad x stride packed bytes; dev_desc: nq_pad VgWithinQuery.  One launch over all
@@ -254,12 +320,6 @@ extern "C" int vg_batch_bits_within_launch(const uint8_t *dev_rows, long long n_
     a.n_rows = n_rows; a.stride = stride_bytes; a.nq_pad = nq_pad; a.npart = npart;
     a.tiles_per_part = (int)((ntiles + npart - 1) / npart);
     const int G = nq_pad / VGBB_QPB;
-    const int blocks = G * ((npart + 7) / 8) * 8;
-    switch (vgbw_ntb(stride_bytes)) {
-    case 8: return launch_within<8>(a, jaccard, blocks, smem, stream);
-    case 16: return launch_within<16>(a, jaccard, blocks, smem, stream);
-    case 24: return launch_within<24>(a, jaccard, blocks, smem, stream);
-    case 32: return launch_within<32>(a, jaccard, blocks, smem, stream);
-    }
-    return -1;
+    return launch_within_ntb<false>(a, jaccard, G * ((npart + 7) / 8) * 8, smem, stream);
 }
+#endif

@@ -86,6 +86,11 @@ int vgbl_launch_gather_real(const BatchArgsBitsGather *a, int variant, int block
 size_t vg_batch_bits_within_lds_bytes(long long stride_bytes);             // 0: rows it does not serve
 int vg_batch_bits_within_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes,
                                 const uint8_t *dev_queries, const void *dev_desc, int nq_pad, int jaccard, int npart, hipStream_t stream);
+// its masked form (-DVGBW_TU_GATHER, a unit of its own: DESIGN.md 3.31): rows gathered through vg_batch_bits_pos_launch's list of the
+// n_pos allowed positions; tiles and partitions count tiles of the list (npart <= ceil(n_pos / 32)); keys carry the real scan positions
+size_t vg_batch_bits_within_masked_lds_bytes(long long stride_bytes);      // 0: rows it does not serve
+int vg_batch_bits_within_masked_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_pos, long long n_pos,
+                                       const uint8_t *dev_queries, const void *dev_desc, int nq_pad, int jaccard, int npart, hipStream_t stream);
 // ---- vg_batch_bitsl_within.hip: the range form of vg_batch_bitsl.hip (rows of 129 .. 512 bytes): the same arguments and answers, nq_pad
 // a multiple of the queries per workgroup - 128 (<= 256 bytes) / 64 (<= 512); one launch over all rows and all query groups
 size_t vg_batch_bitsl_within_lds_bytes(long long stride_bytes);            // 0: rows it does not serve

@@ -600,6 +600,9 @@ bool vg_batch_keys_are_scan_exact(const vg_corpus *c, int metric, int k);   // v
 // vg_batch_api.hip: a masked bit-vector batch on the matrix cores, behind vg_scan_topk_batch_masked_keys' checks (a mask with allowed
 // rows is set, out_counts are zero); -1: not served / handed on - the multi-query scan answers, the counts are zero again
 int vg_batch_bits_masked_try(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts);
+// vg_batch_api.hip: the handle's mask (mask_count > 0) as the list the gathering kernels walk (d_mask_pos), built on the corpus stream
+// when the mask changed since the last one was; the masked top-k batch and the masked range batch (vg_multi_within.hip) share it
+int vg_ensure_mask_positions(vg_corpus *c);
 long long vg_bf16_shadow_stride(const vg_corpus *c);               // vg_batch_api.hip: row stride of the bf16 shadow copy of an f32 corpus
 int vg_ensure_bf16_shadow(vg_corpus *c);                           // vg_batch_api.hip: build / extend it (corpus stream)
 int vg_ensure_q8_shadow(vg_corpus *c);                             // vg_filter.hip: the int8 shadow copy + per-row (scale, residual norm)

@@ -15,7 +15,8 @@
 //
 // The masked batch (vg_scan_within_batch_masked) is the same host code: its kernels are the VG_MQ_WITHIN | VG_MQ_MASKED instances, held by
 // vg_multi_within_masked.hip, its launches set ScanArgs.mask, its fallback is nq single MASKED range scans - nothing else differs, and
-// it leaves its held results where the unmasked batch leaves its own.
+// it leaves its held results where the unmasked batch leaves its own.  (Bit vectors of up to 128 bytes, 128 queries or more: the
+// gathering matrix-core form below instead, within_bits_masked_eligible.)
 //
 // The labeled batch (vg_scan_within_batch_labeled: each query its own label and its own radius) is the same host code once more: its
 // kernels are the VG_MQ_LABELED | VG_MQ_WITHIN instances, held by vg_multi_within_labeled.hip, its launches set ScanArgs.labels and
@@ -27,7 +28,7 @@
 
 #include "vg_scan_multi.h"
 #include "vg_pick.h"
-#include "vg_batch_units.h"          // vg_batch_bits_within_launch, vg_batch_bitsl_within_launch
+#include "vg_batch_units.h"          // vg_batch_bits_within_launch, vg_batch_bits_within_masked_launch, vg_batch_bitsl_within_launch
 
 // what differs between the unmasked, the masked and the labeled batch: whose name errors carry, and whether the launches read the
 // handle's mask or its labels (then every query names one).  No membership form
@@ -220,6 +221,19 @@ static bool within_bits_eligible(const vg_corpus *c, int metric, int nq) {
     const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, qpb == 128 ? VG_WITHIN_BITS_MIN_QUERIES_LONG2_DEFAULT : VG_WITHIN_BITS_MIN_QUERIES_LONG4_DEFAULT);
     return min_q > 0 && nq >= std::max(min_q, qpb);
 }
+// MASKED batches (vg_scan_within_batch_masked) over rows of up to 128 bytes: the gathering form of vg_batch_bits_within.hip,
+// which walks the list of the mask's allowed positions (vg_ensure_mask_positions) and never reads an excluded row.  Whatever the
+// threshold - the switch included -, such a batch needs half a workgroup of real queries: a launch is one workgroup of 256 query slots
+// and below 128 of them it is mostly padding.  Rows beyond 128 bytes keep the masked multi-query range scan.
+#define VG_WITHIN_BITS_MASKED_MIN_QUERIES_DEFAULT 128   // (0: never.  Measured, tools/bits_within_masked_bench.py / DESIGN.md 3.31: at 128 queries - the floor - the matrix cores win all 16 cells by more than both spreads, the closest a contiguous 10 % mask over 32-byte Hamming rows, 2.32 against 3.35 ms)
+#define VG_WITHIN_BITS_MASKED_FLOOR 128
+static bool within_bits_masked_eligible(const vg_corpus *c, int metric, int nq) {
+    if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_U8 || !vg_metric_is_bits(metric)) return false;
+    if (c->mask_count <= 0 || c->stride > 128) return false;
+    const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, VG_WITHIN_BITS_MASKED_MIN_QUERIES_DEFAULT);
+    if (min_q <= 0 || nq < std::max(min_q, VG_WITHIN_BITS_MASKED_FLOOR)) return false;
+    return vg_batch_bits_within_masked_lds_bytes(c->stride) != 0;
+}
 
 // the count word of n descriptors' regions: zeroed (dst == nullptr) or gathered into dst
 __global__ void vg_wb_desc_counts_kernel(const VgWithinQuery *desc, int n, unsigned long long *dst) {
@@ -229,7 +243,8 @@ __global__ void vg_wb_desc_counts_kernel(const VgWithinQuery *desc, int n, unsig
     else desc[i].out[0] = 0ull;
 }
 
-static int batch_within_bits(vg_corpus *c, const char *who, int metric, const void *queries, int nq, const double *radii, int64_t limit) {
+// masked: the batch of vg_scan_within_batch_masked over rows of up to 128 bytes - tiles and partitions count the mask's position list
+static int batch_within_bits(vg_corpus *c, const char *who, int metric, const void *queries, int nq, const double *radii, int64_t limit, bool masked) {
     constexpr int QPB = VG_WB_SLICE;                                  // a slice = a launch; rows of up to 128 bytes: = the workgroup's queries
     const int lqpb = c->stride > 128 ? vg_batch_bitsl_within_queries_per_block(c->stride) : 0;      // the long rows' queries per workgroup
     const int nslices = (nq + QPB - 1) / QPB;
@@ -242,8 +257,9 @@ static int batch_within_bits(vg_corpus *c, const char *who, int metric, const vo
     auto parts = [&](int G) {
         int npart = std::max(1, c->cu_count * std::max(1, vg_sw(SW_VG_BATCH_BPC, 1)) / G);
         if (npart >= 8) npart = (npart / 8) * 8;
-        return (int)std::min<long long>(npart, (c->n_rows + 31) / 32);
+        return (int)std::min<long long>(npart, ((masked ? c->mask_count : c->n_rows) + 31) / 32);
     };
+    if (masked) VG_TRY(vg_ensure_mask_positions(c));
     // zero-padded rows of the corpus stride; a pad query is zero with no capacity and a radius nothing is below
     std::vector<uint8_t> hq((size_t)nslices * block_bytes, 0);
     const size_t row_bytes = (size_t)c->dim * c->es;
@@ -261,8 +277,10 @@ static int batch_within_bits(vg_corpus *c, const char *who, int metric, const vo
         if (evs) hipEventRecord(evs[0], c->stream);
         // (long rows: the query groups that hold a real query; the descriptors behind them are padding up to the slice)
         const int nq_pad = lqpb ? (nqs + lqpb - 1) / lqpb * lqpb : QPB;
-        const int rc = lqpb ? vg_batch_bitsl_within_launch(c->d_rows, c->n_rows, c->stride, d_stage, d_desc, nq_pad, jaccard, parts(nq_pad / lqpb), c->stream)
-                            : vg_batch_bits_within_launch(c->d_rows, c->n_rows, c->stride, d_stage, d_desc, QPB, jaccard, parts(1), c->stream);
+        const int rc = masked ? vg_batch_bits_within_masked_launch(c->d_rows, c->n_rows, c->stride, c->d_mask_pos, c->mask_count, d_stage, d_desc, QPB, jaccard,
+                                                                   parts(1), c->stream)
+                       : lqpb ? vg_batch_bitsl_within_launch(c->d_rows, c->n_rows, c->stride, d_stage, d_desc, nq_pad, jaccard, parts(nq_pad / lqpb), c->stream)
+                              : vg_batch_bits_within_launch(c->d_rows, c->n_rows, c->stride, d_stage, d_desc, QPB, jaccard, parts(1), c->stream);
         if (evs) { hipEventRecord(evs[2], c->stream); hipEventRecord(evs[3], c->stream); }
         if (rc != 0) {
             hipStreamSynchronize(c->stream);
@@ -356,7 +374,10 @@ static int within_batch(vg_corpus *c, const WbForm &f, int metric, const void *q
     int rc = VG_OK;
     c->wb_last_path = 0;
     if (f.rows == VG_QROWS_ALL && within_bits_eligible(c, metric, nq)) {      // bit vectors, enough queries: the integer matrix cores
-        rc = batch_within_bits(c, f.who, metric, queries, nq, radii, limit);
+        rc = batch_within_bits(c, f.who, metric, queries, nq, radii, limit, false);
+        c->wb_last_path = 8;
+    } else if (masked && within_bits_masked_eligible(c, metric, nq)) {        // ... under a mask: their gathering form (rows of up to 128 bytes)
+        rc = batch_within_bits(c, f.who, metric, queries, nq, radii, limit, true);
         c->wb_last_path = 8;
     } else if (NQ == 0) {                                        // no multi-query form: the single range scans of the same form, one by one
         const size_t row_bytes = (size_t)c->dim * c->es;

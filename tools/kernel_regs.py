@@ -6,7 +6,8 @@ Every other argument goes to the compile: the batch units exist only under their
 vg_batch_i8.hip -DVGI_TU_PRE, vg_batch_h.hip -DVGH_TU=1..8, vg_batch_hl.hip -DVGHL_TU=0..5, and vg_batch_bits.hip / vg_batch_bitsl.hip
 are built with -Xclang -target-feature -Xclang -packed-fp32-ops [-DVGBB_TU_PRE / -DVGBL_TU_PRE; the masked forms -DVGBB_TU_GATHER /
 -DVGBB_TU_GATHER_PRE / -DVGBL_TU_GATHER / -DVGBL_TU_GATHER_PRE], their range forms
-vg_batch_bits_within.hip / vg_batch_bitsl_within.hip with the same two -Xclang pairs and no unit flag.
+vg_batch_bits_within.hip / vg_batch_bitsl_within.hip with the same two -Xclang pairs and no unit flag, the masked range form
+(the 8 GATHER instances of vg_batch_bits_within.hip) with -DVGBW_TU_GATHER.
 --digest: one line per kernel - VGPRs, SGPRs, spilled VGPRs / SGPRs, scratch, static LDS and a hash of the kernel's instruction text
 (comments stripped, local label numbers and mangled symbol names blanked), then the demangled name: two revisions of a unit whose
 lines agree generate the same code."""
