@@ -144,6 +144,11 @@ int vg_within_batch_last_path(const vg_corpus *c);
  * vg_batch_bits.hip: rows of 16 .. 128 bytes; vg_batch_bitsl.hip: 144 .. 512 bytes, k <= 28 at 208 .. 256), 0 = no call yet.  A call that returns before any launch (an error, an empty mask, no
  * rows) leaves it as it was. */
 int vg_batch_masked_last_path(const vg_corpus *c);
+/* vg_batch_labeled_last_path: the same for the last vg_scan_topk_batch_labeled[_keys] on this handle - 5 = the multi-query scan, 6 = one
+ * labeled scan per query, 8 = the integer matrix cores with the label test in front of their gate (vg_batch_bits.hip, the labeled form:
+ * Hamming / Jaccard batches of VG_BATCH_BITS_MIN_QUERIES queries or more over uint8 rows of 16 .. 128 bytes, a multiple of 16, k <= 32;
+ * longer rows keep 5), 0 = no call yet.  A call that returns before any launch (an error, no rows) leaves it as it was. */
+int vg_batch_labeled_last_path(const vg_corpus *c);
 int vg_within_batch_plan(const vg_corpus *c, int metric, int *out_queries_per_pass, int *out_lpr, int *out_u);
 int vg_within_batch_set_initial_capacity(vg_corpus *c, int64_t keys_per_query);
 int vg_within_batch_last_launches(const vg_corpus *c);

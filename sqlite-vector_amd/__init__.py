@@ -211,6 +211,7 @@ def _load():
         "vg_shards_scan_topk_batch_masked": (i32, [vp, i32, vp, i32, i32, vp, vp, vp]),
         "vg_batch_masked_plan": (i32, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "vg_batch_masked_last_path": (i32, [vp]),
+        "vg_batch_labeled_last_path": (i32, [vp]),
         # labeled scans: a uint32 label per row on the handle, each query names one
         "vg_corpus_set_labels": (i32, [vp, vp, i64]),
         "vg_corpus_clear_labels": (i32, [vp]),
@@ -1102,6 +1103,11 @@ class Corpus(_PagedScans, _LabeledOps, _GroupedOps, _LabelsetOps, _WithinLabeled
         """which path answered the last scan_topk_batch_masked: 5 multi-query scan, 6 one masked scan per query, 8 bit vectors
         (Hamming / Jaccard, rows of up to 512 bytes) on the int8 matrix cores through the mask's position list, 0 no call yet"""
         return int(lib().vg_batch_masked_last_path(self.h))
+
+    def batch_labeled_last_path(self):
+        """which path answered the last scan_topk_batch_labeled: 5 multi-query scan, 6 one labeled scan per query, 8 bit vectors
+        (Hamming / Jaccard, rows of up to 128 bytes) on the int8 matrix cores with the label test in their gate, 0 no call yet"""
+        return int(lib().vg_batch_labeled_last_path(self.h))
 
     def scan_within_masked(self, metric, query, radius, limit=None):
         """scan_within among the ALLOWED rows: (rowids, distances, matches); it holds its result where scan_within does"""

@@ -31,6 +31,7 @@ HIP_UNITS = [("vg_api.hip", "vg_api.hip.o", []), ("vg_corpus.hip", "vg_corpus.hi
              ("vg_batch_i8.hip", "vg_batch_i8.hip.o", []), ("vg_batch_i8.hip", "vg_batch_i8_pre.o", ["-DVGI_TU_PRE"]),
              ("vg_batch_bits.hip", "vg_batch_bits.hip.o", NO_PK_F32), ("vg_batch_bits.hip", "vg_batch_bits_pre.o", NO_PK_F32 + ["-DVGBB_TU_PRE"]),
              ("vg_batch_bits.hip", "vg_batch_bits_gather.o", NO_PK_F32 + ["-DVGBB_TU_GATHER"]), ("vg_batch_bits.hip", "vg_batch_bits_gather_pre.o", NO_PK_F32 + ["-DVGBB_TU_GATHER_PRE"]),
+             ("vg_batch_bits.hip", "vg_batch_bits_labeled.o", NO_PK_F32 + ["-DVGBB_TU_LABELED"]), ("vg_batch_bits.hip", "vg_batch_bits_labeled_pre.o", NO_PK_F32 + ["-DVGBB_TU_LABELED_PRE"]),
              ("vg_batch_bits_within.hip", "vg_batch_bits_within.hip.o", NO_PK_F32), ("vg_batch_bits_within.hip", "vg_batch_bits_within_gather.o", NO_PK_F32 + ["-DVGBW_TU_GATHER"]),
              ("vg_batch_bitsl_within.hip", "vg_batch_bitsl_within.hip.o", NO_PK_F32),
              ("vg_batch_bitsl.hip", "vg_batch_bitsl.hip.o", NO_PK_F32), ("vg_batch_bitsl.hip", "vg_batch_bitsl_pre.o", NO_PK_F32 + ["-DVGBL_TU_PRE"]),

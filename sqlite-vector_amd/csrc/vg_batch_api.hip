@@ -515,9 +515,21 @@ static int scan_topk_batch_mfma(vg_corpus *c, int metric, const void *queries, i
 // at 256: 2.12 against 3.10 ms) and 512-byte rows win every cell (the closest: Hamming, full mask, 3.50 against 3.91 ms); from 32 on the matrix
 // cores win every cell of every step by more than both spreads
 #define VG_BATCH_BITS_MASKED_MIN_QUERIES_LONG_DEFAULT(stride) ((stride) > 384 ? 16 : 32)
-// masked: the batch of vg_scan_topk_batch_masked - a mask with allowed rows, thresholds of its own
-static bool batch_bits_eligible(const vg_corpus *c, int metric, int k, int nq, bool masked = false) {
+// labeled batches (the labeled form, rows of up to 128 bytes).  Measured, tools/bits_batch_labeled_bench.py / DESIGN.md 3.32: at 64 queries
+// the labeled multi-query scan still wins or ties 36 of 48 cells (every cell with 4096 tenants or with the labels in runs; the widest: 32-byte
+// Hamming rows, 256 tenants in runs, all queries one label, 1.38 against 3.24 ms); from 256 on the matrix cores win every cell by more
+// than both spreads
+#define VG_BATCH_BITS_LABELED_MIN_QUERIES_DEFAULT 256
+static_assert(VG_LABEL_NONE == 0xFFFFFFFFu, "the kernels' 'no label' (VGBB_NO_LABEL, vg_batch_bits_defs.h) is the interface's");
+// masked: the batch of vg_scan_topk_batch_masked - a mask with allowed rows, thresholds of its own; labeled: the batch of
+// vg_scan_topk_batch_labeled - labels set, rows of up to 128 bytes, a threshold of its own
+static bool batch_bits_eligible(const vg_corpus *c, int metric, int k, int nq, bool masked = false, bool labeled = false) {
     if (vg_sw(SW_VG_BATCH_MFMA, 1) == 0 || c->vtype != VG_TYPE_U8 || !vg_metric_is_bits(metric)) return false;
+    if (labeled) {
+        if (!c->has_labels || c->stride > 128 || c->stride % 16 != 0) return false;
+        const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, VG_BATCH_BITS_LABELED_MIN_QUERIES_DEFAULT);
+        return min_q > 0 && nq >= min_q && vg_batch_bits_labeled_lds_bytes(c->stride, k) != 0;     // k <= 32
+    }
     if (masked && c->mask_count <= 0) return false;
     const bool long_rows = c->stride > 128;
     const int min_q = vg_sw(SW_VG_BATCH_BITS_MIN_QUERIES, masked ? (long_rows ? VG_BATCH_BITS_MASKED_MIN_QUERIES_LONG_DEFAULT(c->stride) : VG_BATCH_BITS_MASKED_MIN_QUERIES_DEFAULT)
@@ -538,8 +550,11 @@ int vg_ensure_mask_positions(vg_corpus *c) {
     return VG_OK;
 }
 
-// one driver for the plain and the masked batch: the masked one counts tiles of the position list and launches the gathering form
-static int scan_topk_batch_bits_form(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts, bool masked) {
+// one driver for the plain, the masked and the labeled batch: the masked one counts tiles of the position list and launches the gathering
+// form; the labeled one (qlabels: a label per query of the slice) stages the labels behind the queries - VG_LABEL_NONE for the padding
+// queries - and launches the labeled form over the handle's row labels
+static int scan_topk_batch_bits_form(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts, bool masked,
+                                     const uint32_t *qlabels = nullptr) {
     const int QPB = vg_batch_bits_queries_per_block(c->stride);           // 256 / 128 / 64 by row length
     const int nq_pad = ((nq + QPB - 1) / QPB) * QPB;
     const int G = nq_pad / QPB;
@@ -549,7 +564,8 @@ static int scan_topk_batch_bits_form(vg_corpus *c, int metric, const void *queri
     if (npart >= 8) npart = (npart / 8) * 8;
     npart = std::min(npart, 256);
     npart = (int)std::min<long long>(npart, ((masked ? c->mask_count : c->n_rows) + 31) / 32);
-    const size_t qbytes = (size_t)nq_pad * c->stride;
+    const size_t lb_off = (size_t)nq_pad * c->stride;                     // (a multiple of 16: the labels behind the queries are aligned)
+    const size_t qbytes = lb_off + (qlabels ? (size_t)nq_pad * sizeof(uint32_t) : 0);
     const size_t candbytes = (size_t)nq_pad * vg_batch_lists_per_query(c->n_rows, npart) * 64 * sizeof(uint64_t);
     const size_t keybytes = (size_t)nq_pad * 64 * sizeof(uint64_t);
     VG_TRY(vg_dev_reserve(&c->d_bq, &c->bq_bytes, qbytes));
@@ -558,12 +574,19 @@ static int scan_topk_batch_bits_form(vg_corpus *c, int metric, const void *queri
     // queries: zero-padded rows of the corpus stride, zero rows up to nq_pad - through the corpus' pinned buffer
     VG_TRY(vg_reserve_h_bq(c, qbytes));
     vg_stage_queries(c->h_bq, queries, nq, nq_pad, (size_t)c->stride, (size_t)c->dim * c->es);
+    if (qlabels) {
+        uint32_t *hl = reinterpret_cast<uint32_t *>(c->h_bq + lb_off);
+        for (int i = 0; i < nq_pad; ++i) hl[i] = i < nq ? qlabels[i] : VG_LABEL_NONE;
+    }
     HIP_TRY(hipMemcpyAsync(c->d_bq, c->h_bq, qbytes, hipMemcpyHostToDevice, c->stream));
     if (masked) VG_TRY(vg_ensure_mask_positions(c));
     hipEvent_t *evs = vg_prof_slot(c, 0);
     if (evs) hipEventRecord(evs[0], c->stream);
     const int jaccard = metric == VG_DIST_JACCARD ? 1 : 0;
-    const int rc = masked ? vg_batch_bits_masked_launch(c->d_rows, c->n_rows, c->stride, c->d_mask_pos, c->mask_count, (const uint8_t *)c->d_bq, nq_pad, nq, k,
+    const int rc = qlabels ? vg_batch_bits_labeled_launch(c->d_rows, c->n_rows, c->stride, c->d_labels, (const uint8_t *)c->d_bq,
+                                                          reinterpret_cast<const uint32_t *>((const uint8_t *)c->d_bq + lb_off), nq_pad, nq, k, jaccard,
+                                                          c->d_bcand, npart, c->d_bkeys, c->stream)
+                   : masked ? vg_batch_bits_masked_launch(c->d_rows, c->n_rows, c->stride, c->d_mask_pos, c->mask_count, (const uint8_t *)c->d_bq, nq_pad, nq, k,
                                                         jaccard, c->d_bcand, npart, c->d_bkeys, c->stream)
                           : vg_batch_bits_launch(c->d_rows, c->n_rows, c->stride, (const uint8_t *)c->d_bq, nq_pad, nq, k,
                                                  jaccard, c->d_bcand, npart, c->d_bkeys, c->stream);
@@ -612,7 +635,7 @@ static int scan_topk_batch_multi(vg_corpus *c, int metric, const void *queries, 
 // very large batches go through a driver in slices of `slice` queries (the per-(query, partition) candidate lists are nq x ~128 x
 // 512 B), until a slice does not answer VG_OK.  -1: the driver hands the batch on - the counts are zero again for the next path
 typedef int (*batch_driver_t)(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts);
-static int run_sliced(vg_corpus *c, batch_driver_t driver, int slice, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
+template <class Driver = batch_driver_t> static int run_sliced(vg_corpus *c, Driver driver, int slice, int metric, const void *queries, int nq, int k, uint64_t *out_keys,
                       int *out_counts) {
     const size_t qbytes = (size_t)c->dim * c->es;
     int rc = VG_OK;
@@ -626,6 +649,15 @@ static int run_sliced(vg_corpus *c, batch_driver_t driver, int slice, int metric
 int vg_batch_bits_masked_try(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts) {
     if (!batch_bits_eligible(c, metric, k, nq, true)) return -1;
     return run_sliced(c, scan_topk_batch_bits_masked, std::max(256, vg_sw(SW_VG_BATCH_SLICE, 4096)), metric, queries, nq, k, out_keys, out_counts);
+}
+
+// (the driver is a closure here: a slice finds its labels by where its counts start in the batch's)
+int vg_batch_bits_labeled_try(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *qlabels, int k, uint64_t *out_keys, int *out_counts) {
+    if (!batch_bits_eligible(c, metric, k, nq, false, true)) return -1;
+    auto driver = [&](vg_corpus *cc, int m, const void *sq, int snq, int sk, uint64_t *skeys, int *scounts) {
+        return scan_topk_batch_bits_form(cc, m, sq, snq, sk, skeys, scounts, false, qlabels + (scounts - out_counts));
+    };
+    return run_sliced(c, driver, std::max(256, vg_sw(SW_VG_BATCH_SLICE, 4096)), metric, queries, nq, k, out_keys, out_counts);
 }
 
 extern "C" int vg_scan_topk_batch_keys(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys,

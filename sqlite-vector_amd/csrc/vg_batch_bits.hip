@@ -28,6 +28,10 @@
 //     (ascending scan positions, padded with 0xFFFFFFFF to whole tiles; built by vgbb_pos_* at the end of this file).  The producer lanes
 //     already compute the address of every row they load: here it is rows + position * stride, the position fetched two tiles ahead, the
 //     row one tile ahead.  Rows the mask excludes are never read; a tile's positions sit in LDS next to its bit counts and make the keys.
+//   * LABELED batches: every query asks for the rows of ITS label.  All pairs are multiplied as before; the label of a
+//     tile's rows travels with their bit counts (one dword per row, loaded one tile ahead by the row's first producer lane), the 16 query
+//     labels of a lane sit in registers next to its gate values, and the equality test stands IN FRONT of the gate: a row of another
+//     label never reaches the slow path, whatever its distance.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -46,8 +50,12 @@
 // NTB = k-steps per row (32 bits = 4 packed bytes each): rows up to 4 * NTB bytes, shorter ones zero-padded in the k dimension
 // JAC = Jaccard (else Hamming); PRE = the pre-pass variant (vg_batch_i8.hip): only the smallest distance of a query in a tile enters
 // GATHER = the masked form (BatchArgsBitsGather, VGBB_NO_POS: vg_batch_bits_defs.h): tiles are runs of 32 entries of a.pos, not of 32 consecutive rows
-template <int NTB, bool JAC, bool PRE, bool GATHER>
-__global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::conditional_t<GATHER, BatchArgsBitsGather, BatchArgsBits> a) {
+// LABELED = the labeled form (BatchArgsBitsLabeled, VGBB_NO_LABEL): a pair counts only where the row carries the query's label
+template <bool GATHER, bool LABELED>
+using vgbb_args_t = std::conditional_t<LABELED, BatchArgsBitsLabeled, std::conditional_t<GATHER, BatchArgsBitsGather, BatchArgsBits>>;
+template <int NTB, bool JAC, bool PRE, bool GATHER, bool LABELED = false>
+__global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(vgbb_args_t<GATHER, LABELED> a) {
+    static_assert(!(GATHER && LABELED), "the labeled form walks consecutive rows: it is not combined with the gathering one");
     constexpr int THREADS = 64 * VGBB_WAVES;
     constexpr int TILE_BYTES = NTB * 1024;                      // 32 rows x 32 NTB spread bytes
     constexpr int LPR = NTB <= 8 ? 4 : (NTB <= 16 ? 8 : 16);   // lanes that share a row of the packed tile, 8 bytes each
@@ -57,7 +65,8 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
     uint8_t *tile0 = smem;                                                               // 2 tile buffers
     uint32_t *xcnt_lds = reinterpret_cast<uint32_t *>(smem + 2 * TILE_BYTES);            // [2][32]: |x| of a buffer's rows
     uint32_t *xpos_lds = xcnt_lds + 2 * VGBB_TILE;                                       // GATHER only - [2][32]: the rows' scan positions
-    uint32_t *qcnt_lds = xcnt_lds + (GATHER ? 4 : 2) * VGBB_TILE;                        // [waves][32]: |q|
+    uint32_t *xlab_lds = xcnt_lds + 2 * VGBB_TILE;                                       // LABELED only - [2][32]: the rows' labels (the same dwords)
+    uint32_t *qcnt_lds = xcnt_lds + (GATHER || LABELED ? 4 : 2) * VGBB_TILE;             // [waves][32]: |q|
     float *thr_lds = reinterpret_cast<float *>(qcnt_lds + VGBB_QPB);                     // [waves][32]: current k-th best distance
     uint64_t *lists = reinterpret_cast<uint64_t *>(thr_lds + VGBB_QPB);                  // [waves][32][k]
 
@@ -136,6 +145,11 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
         if (pcols && p != VGBB_NO_POS) v = *reinterpret_cast<const uint2 *>(a.rows + (unsigned long long)p * (unsigned long long)a.stride + 8 * pj);
         return v;
     };
+    // LABELED: the label of row prow of a tile, fetched by the row's first producer lane alone; a row at or past n_rows carries none
+    auto load_label = [&](long long tile) __attribute__((always_inline)) -> uint32_t {
+        if constexpr (LABELED) return (spreader && pj == 0 && tile * VGBB_TILE + prow < a.n_rows) ? a.labels[tile * VGBB_TILE + prow] : VGBB_NO_LABEL;
+        else return 0u;
+    };
     // chunk c (0 .. 3) of the thread's 8 bytes into buffer `buf`
     auto spread_chunk = [&](auto cc, uint2 v, int buf) __attribute__((always_inline)) {
         constexpr int c = decltype(cc)::value;
@@ -143,13 +157,14 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
         const vgb_i32x4 o = vgbb_spread16((c & 1) ? (w >> 16) : (w & 0xFFFFu));
         if (pcols) *reinterpret_cast<vgb_i32x4 *>(pdst + buf * TILE_BYTES + c * 512) = o;
     };
-    auto store_count = [&](uint2 v, int buf, uint32_t p) __attribute__((always_inline)) {
+    auto store_count = [&](uint2 v, int buf, uint32_t p, uint32_t lab) __attribute__((always_inline)) {
         if (!spreader) return;
         uint32_t cnt = (uint32_t)__builtin_popcount(v.x) + (uint32_t)__builtin_popcount(v.y);
 #pragma unroll
         for (int m = 1; m < LPR; m <<= 1) cnt += __shfl_xor(cnt, m);
         if (pj == 0) xcnt_lds[buf * VGBB_TILE + prow] = cnt;
         if constexpr (GATHER) { if (pj == 0) xpos_lds[buf * VGBB_TILE + prow] = p; }
+        if constexpr (LABELED) { if (pj == 0) xlab_lds[buf * VGBB_TILE + prow] = lab; }
     };
 
     // ---- the gate.  Register r of lane (x, h) belongs to query qi(r, h) = (r&3) + 8*(r>>2) + 4*h; i = acc[r].
@@ -157,8 +172,14 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
     //   Jaccard  (S - 2 i) 2^18 <= gt (S - i),  S = |q| + |x|,  gt = ceil(thr 2^18) <= 2^19: integers (v_mul_u32_u24), implied by
     //            fl((u - i) / u) < thr; a padding query stands in the gate with |q| = 4096 and gt = 0 and never passes
     // The exact test - (float) distance < thr, the single scan's arithmetic - is the slow path's.
+    // LABELED: the pair stands in the gate only where ok_r = (qlab[r] == the row's label) and the row has one.  A list holds rows of its
+    // query's label only, so its threshold is the k-th best among those: without the test in the gate every closer row of another tenant
+    // would enter the slow path.  Hamming: a pair that is not ok takes the padding query's margin -(1 << 30) into the max (2 i + ng of an
+    // ok pair of a real query lies above it, and the subtraction of |x| cannot wrap).  A padding query carries VGBB_NO_LABEL, a row
+    // without a label too: the row's own test keeps the two apart, and the padding query's threshold (-Inf) passes nothing either way.
     vgb_i32x16 ng;                      // Hamming: the margin; Jaccard: |q|
     vgb_i32x16 gs;                      // Jaccard: gt
+    uint32_t qlab[LABELED ? 16 : 1];    // LABELED: the label of query qi(r, h)
     auto gate_ham = [](uint32_t qc, float thr) __attribute__((always_inline)) -> int {
         if (thr == -INFINITY) return -(1 << 30);               // padding
         if (!(thr < 1.0e9f)) return 1 << 30;                   // list not full: everything passes
@@ -174,13 +195,36 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
         const int qi = (r & 3) + 8 * (r >> 2) + 4 * h;
         ng[r] = JAC ? (thr_w[qi] == -INFINITY ? 4096 : (int)qc_w[qi]) : gate_ham(qc_w[qi], thr_w[qi]);
         gs[r] = JAC ? gate_jac(thr_w[qi]) : 0;
+        if constexpr (LABELED) qlab[r] = a.qlabels[q0 + qi];
     });
     auto passes = [&](int i, int ngr, int gsr, int xx) __attribute__((always_inline)) -> bool {
         if constexpr (JAC) { const int S = ngr + xx; return ((uint32_t)(S - 2 * i) << 18) <= __umul24((uint32_t)gsr, (uint32_t)(S - i)); }
         else return 2 * i + ngr - xx >= 0;
     };
-    auto judge_any = [&](const vgb_i32x16 &acc, int xx) __attribute__((always_inline)) -> bool {
-        if constexpr (JAC) {
+    // LABELED, Jaccard: `passes` of a pair of equal labels; any other pair stands with the left side 2^32 - 1, above every right side
+    // (gt (S - i) <= 2^19 * 5120) - a select on a value, like Hamming's, so that no comparison result has to outlive its statement
+    auto passes_lab = [&](int i, int ngr, int gsr, int xx, uint32_t ql, uint32_t xlab) __attribute__((always_inline)) -> bool {
+        const int S = ngr + xx;
+        const uint32_t lhs = (ql == xlab) ? ((uint32_t)(S - 2 * i) << 18) : 0xFFFFFFFFu;
+        return lhs <= __umul24((uint32_t)gsr, (uint32_t)(S - i));
+    };
+    auto judge_any = [&](const vgb_i32x16 &acc, int xx, uint32_t xlab) __attribute__((always_inline)) -> bool {
+        if constexpr (LABELED) {
+            const bool labeled_row = xlab != VGBB_NO_LABEL;
+            if constexpr (JAC) {
+                bool p = false;
+                vgb_static_for<0, 16>([&](auto rc) { constexpr int r = decltype(rc)::value; p |= passes_lab(acc[r], ng[r], gs[r], xx, qlab[r], xlab); });
+                return __ballot(p && labeled_row) != 0;
+            } else {
+                int mm = -(1 << 30);
+                vgb_static_for<0, 16>([&](auto rc) {
+                    constexpr int r = decltype(rc)::value;
+                    const int m = (qlab[r] == xlab) ? 2 * acc[r] + ng[r] : -(1 << 30);
+                    mm = mm > m ? mm : m;
+                });
+                return __ballot(labeled_row && mm - xx >= 0) != 0;
+            }
+        } else if constexpr (JAC) {
             bool p = false;
             vgb_static_for<0, 16>([&](auto rc) { constexpr int r = decltype(rc)::value; p |= passes(acc[r], ng[r], gs[r], xx); });
             return __ballot(p) != 0;
@@ -192,12 +236,20 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
     };
     // the slow path of a tile (vg_batch_i8.hip's): which registers hold a passing pair, then - one copy of the code, looping over the
     // pending registers by run-time index - the exact distance, the list inserts, the refreshed gate
-    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int buf, int xx) __attribute__((always_inline)) {
+    // (LABELED: `mine`, bit r = the lane's row carries the label of the query of register r - the predicate of the gate, kept per lane
+    //  for the exact test below, where r is a run-time index)
+    auto judge_slow = [&](const vgb_i32x16 &acc, long long tile, int buf, int xx, uint32_t xlab) __attribute__((always_inline)) {
         const long long row = GATHER ? (long long)xpos_lds[buf * VGBB_TILE + x] : tile * VGBB_TILE + x;
-        unsigned pend = 0;
+        unsigned pend = 0, mine = 0;
         vgb_static_for<0, 16>([&](auto rc) {
             constexpr int r = decltype(rc)::value;
-            pend |= __ballot(passes(acc[r], ng[r], gs[r], xx)) ? (1u << r) : 0u;
+            if constexpr (LABELED) {
+                const unsigned ok = (qlab[r] == xlab && xlab != VGBB_NO_LABEL) ? (1u << r) : 0u;
+                mine |= ok;
+                pend |= __ballot(ok != 0u && passes(acc[r], ng[r], gs[r], xx)) ? (1u << r) : 0u;
+            } else {
+                pend |= __ballot(passes(acc[r], ng[r], gs[r], xx)) ? (1u << r) : 0u;
+            }
         });
         while (pend) {
             const int r = __builtin_ctz(pend);
@@ -215,7 +267,7 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
             }
             d = vg_clamp(d);
             // strict: rows arrive in scan order, a row that only ties the k-th best has the larger position and loses
-            const bool pass = (GATHER ? row != (long long)VGBB_NO_POS : row < a.n_rows) && (d < thr_l);
+            const bool pass = (GATHER ? row != (long long)VGBB_NO_POS : row < a.n_rows) && (!LABELED || ((mine >> r) & 1u)) && (d < thr_l);
             unsigned long long m = __ballot(pass);
             if (!m) continue;
             if constexpr (PRE) {
@@ -256,12 +308,13 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
     vgb_i32x16 acc;
     const uint32_t lds_tile0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)tile0;
     uint32_t pos_next = VGBB_NO_POS, pos_next2 = VGBB_NO_POS;          // GATHER: the thread's entries of tiles t + 1 and t + 2 (clamped like tile_next)
+    uint32_t lab_next = VGBB_NO_LABEL;                                  // LABELED: the label of the thread's row of tile t + 1
     if (tile_first < tile_last) {
         const uint32_t p0 = load_pos(tile_first);
         if constexpr (GATHER) pos_next = load_pos(min(tile_first + 1, tile_last - 1));
         const uint2 v0 = GATHER ? load_gathered(p0) : load_packed(tile_first);
         vgb_static_for<0, 4>([&](auto cc) { spread_chunk(cc, v0, 0); });
-        store_count(v0, 0, p0);
+        store_count(v0, 0, p0, load_label(tile_first));
     }
     __syncthreads();
     for (long long tile = tile_first; tile < tile_last; ++tile) {
@@ -281,15 +334,17 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
             if constexpr (t == 0) {
                 if constexpr (GATHER) { pk = load_gathered(pos_next); pos_next2 = load_pos(min(tile + 2, tile_last - 1)); }
                 else pk = load_packed(tile_next);
+                if constexpr (LABELED) lab_next = load_label(tile_next);
             }
             constexpr int S0 = NTB / 2, SD = NTB / 8;
             if constexpr (t >= S0 && (t - S0) % SD == 0 && (t - S0) / SD < 4)
                 spread_chunk(std::integral_constant<int, (t - S0) / SD>{}, pk, next_buf);
-            if constexpr (t == NTB - 1) store_count(pk, next_buf, pos_next);
+            if constexpr (t == NTB - 1) store_count(pk, next_buf, pos_next, lab_next);
             __builtin_amdgcn_sched_barrier(0);
         });
         const int xx = (int)xcnt_lds[cur_buf * VGBB_TILE + x];
-        if (judge_any(acc, xx)) judge_slow(acc, tile, cur_buf, xx);
+        const uint32_t xlab = LABELED ? xlab_lds[cur_buf * VGBB_TILE + x] : 0u;
+        if (judge_any(acc, xx, xlab)) judge_slow(acc, tile, cur_buf, xx, xlab);
         if constexpr (GATHER) pos_next = pos_next2;
         __syncthreads();
     }
@@ -302,9 +357,10 @@ __global__ __launch_bounds__(64 * VGBB_WAVES, 1) void vg_batch_bits_kernel(std::
 
 
 // ---- host side
-// The kernel instantiations are split over four translation units compiled from this file (build.py): the real-pass kernels and the
+// The kernel instantiations are split over six translation units compiled from this file (build.py): the real-pass kernels and the
 // entry points here, the PRE kernels with -DVGBB_TU_PRE; the masked form's real-pass kernels, its position-list kernels and its entry
-// points with -DVGBB_TU_GATHER, its PRE kernels with -DVGBB_TU_GATHER_PRE.
+// points with -DVGBB_TU_GATHER, its PRE kernels with -DVGBB_TU_GATHER_PRE; the labeled form's real-pass kernels and entry points with
+// -DVGBB_TU_LABELED, its PRE kernels with -DVGBB_TU_LABELED_PRE.
 // the ladder of row lengths: k-steps the kernels are instantiated for (rows of up to 32 / 64 / 96 / 128 bytes); 0: not served
 static int vgbb_ntb(long long stride_bytes) {
     if (stride_bytes < 16 || stride_bytes % 16 != 0) return 0;
@@ -312,21 +368,62 @@ static int vgbb_ntb(long long stride_bytes) {
     return ntb <= 8 ? 8 : (ntb <= 16 ? 16 : (ntb <= 24 ? 24 : (ntb <= 32 ? 32 : 0)));
 }
 
-template <int NTB, bool JAC, bool PRE, bool GATHER, typename Args>
+template <int NTB, bool JAC, bool PRE, bool GATHER, bool LABELED, typename Args>
 static int launch_bits(const Args &a, int blocks, size_t smem, hipStream_t stream) {
-    return vgb_launch(vg_batch_bits_kernel<NTB, JAC, PRE, GATHER>, blocks, 64 * VGBB_WAVES, smem, stream, a);
+    return vgb_launch(vg_batch_bits_kernel<NTB, JAC, PRE, GATHER, LABELED>, blocks, 64 * VGBB_WAVES, smem, stream, a);
 }
-template <bool PRE, bool GATHER, typename Args>
+template <bool PRE, bool GATHER, bool LABELED = false, typename Args>
 static int launch_bits_ntb(const Args &a, int ntb, int jaccard, int blocks, size_t smem, hipStream_t stream) {
     switch (ntb) {
-    case 8: return jaccard ? launch_bits<8, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bits<8, false, PRE, GATHER>(a, blocks, smem, stream);
-    case 16: return jaccard ? launch_bits<16, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bits<16, false, PRE, GATHER>(a, blocks, smem, stream);
-    case 24: return jaccard ? launch_bits<24, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bits<24, false, PRE, GATHER>(a, blocks, smem, stream);
-    case 32: return jaccard ? launch_bits<32, true, PRE, GATHER>(a, blocks, smem, stream) : launch_bits<32, false, PRE, GATHER>(a, blocks, smem, stream);
+    case 8: return jaccard ? launch_bits<8, true, PRE, GATHER, LABELED>(a, blocks, smem, stream) : launch_bits<8, false, PRE, GATHER, LABELED>(a, blocks, smem, stream);
+    case 16: return jaccard ? launch_bits<16, true, PRE, GATHER, LABELED>(a, blocks, smem, stream) : launch_bits<16, false, PRE, GATHER, LABELED>(a, blocks, smem, stream);
+    case 24: return jaccard ? launch_bits<24, true, PRE, GATHER, LABELED>(a, blocks, smem, stream) : launch_bits<24, false, PRE, GATHER, LABELED>(a, blocks, smem, stream);
+    case 32: return jaccard ? launch_bits<32, true, PRE, GATHER, LABELED>(a, blocks, smem, stream) : launch_bits<32, false, PRE, GATHER, LABELED>(a, blocks, smem, stream);
     }
     return -1;
 }
-#if defined(VGBB_TU_PRE)
+#if defined(VGBB_TU_LABELED_PRE)
+extern "C" int vgbb_launch_labeled_pre(const BatchArgsBitsLabeled *a, int variant, int blocks, size_t smem, hipStream_t stream) {
+    return launch_bits_ntb<true, false, true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+#elif defined(VGBB_TU_LABELED)
+extern "C" int vgbb_launch_labeled_real(const BatchArgsBitsLabeled *a, int variant, int blocks, size_t smem, hipStream_t stream) {
+    return launch_bits_ntb<false, false, true>(*a, variant >> 1, variant & 1, blocks, smem, stream);
+}
+
+// the labeled form's LDS: vg_batch_bits_lds_bytes + the two tiles' labels (128-byte rows, k = 32: 133632).  Rows of up to 128 bytes only:
+// longer ones have no labeled form (the multi-query scan answers)
+extern "C" size_t vg_batch_bits_labeled_lds_bytes(long long stride_bytes, int k) {
+    if (stride_bytes > 128) return 0;
+    const size_t plain = vg_batch_bits_lds_bytes(stride_bytes, k);
+    return plain ? plain + 2 * VGBB_TILE * 4 : 0;
+}
+
+// vg_batch_bits_launch with a label per row (dev_labels: n_rows dwords) and per query (dev_qlabels: nq_pad dwords, VGBB_NO_LABEL for the
+// padding queries): tiles, partitions, the pre-pass and the stages are the plain form's
+extern "C" int vg_batch_bits_labeled_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_labels,
+                                            const uint8_t *dev_queries, const uint32_t *dev_qlabels, int nq_pad, int nq_real, int k, int jaccard,
+                                            uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream) {
+    const size_t smem = vg_batch_bits_labeled_lds_bytes(stride_bytes, k);
+    const long long ntiles = (n_rows + VGBB_TILE - 1) / VGBB_TILE;
+    if (!smem || !dev_labels || !dev_qlabels || nq_pad < VGBB_QPB || nq_pad % VGBB_QPB != 0 || npart < 1 || npart > VG_SEL_MAX_HEADS ||
+        npart > ntiles || n_rows < 1) return -1;
+    BatchArgsBitsLabeled a;
+    a.rows = dev_rows; a.queries = dev_queries; a.cand = dev_cand; a.labels = dev_labels; a.qlabels = dev_qlabels;
+    a.n_rows = n_rows; a.stride = stride_bytes; a.nq_pad = nq_pad; a.nq_real = nq_real; a.npart = npart; a.k = k;
+    const int variant = vgbb_ntb(stride_bytes) * 2 + (jaccard ? 1 : 0);
+    const int G = nq_pad / VGBB_QPB;
+    const int blocks = G * ((npart + 7) / 8) * 8;
+    long long pre = 0;
+    {
+        const int denom = vg_sw(SW_VG_BATCH_PREPASS, VGB_PREPASS_DENOM_DEFAULT);
+        if (denom > 0 && ntiles >= 65536) pre = ((ntiles / denom + npart - 1) / npart) * npart;
+    }
+    return vgb_run_staged(a, ntiles, pre, 400, dev_out_keys, stream,
+                          [&](const BatchArgsBitsLabeled &b) { return vgbb_launch_labeled_pre(&b, variant, blocks, smem, stream); },
+                          [&](const BatchArgsBitsLabeled &b) { return vgbb_launch_labeled_real(&b, variant, blocks, smem, stream); });
+}
+#elif defined(VGBB_TU_PRE)
 extern "C" int vgbb_launch_pre(const BatchArgsBits *a, int variant, int blocks, size_t smem, hipStream_t stream) {
     return launch_bits_ntb<true, false>(*a, variant >> 1, variant & 1, blocks, smem, stream);
 }

@@ -31,6 +31,14 @@ struct BatchArgsBitsGather : BatchArgsBits {
     const uint32_t *pos;      // GATHER: tile_end * 32 entries - the allowed scan positions, ascending, VGBB_NO_POS behind the last
 };
 
+// the labeled (LABELED) form of vg_batch_bits.hip: every query asks for the rows of ITS label only; tiles stay runs of
+// 32 consecutive rows
+#define VGBB_NO_LABEL 0xFFFFFFFFu        // = VG_LABEL_NONE (vectorgpu.h; vg_batch_api.hip asserts the value): a row no query matches, a padding query
+struct BatchArgsBitsLabeled : BatchArgsBits {
+    const uint32_t *labels;   // LABELED: n_rows dwords - the label of the row at each scan position
+    const uint32_t *qlabels;  // LABELED: nq_pad dwords - the queries' labels, VGBB_NO_LABEL for the padding queries
+};
+
 // ---- the range forms (every row within a radius): vg_batch_bits_within.hip (rows of up to 128 bytes) and its K-split
 // sibling vg_batch_bitsl_within.hip (129 .. 512 bytes; 3.28), which share the arguments, the gate and the emission below.
 struct BatchArgsBitsWithin {

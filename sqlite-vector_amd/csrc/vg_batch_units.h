@@ -16,6 +16,7 @@ struct BatchArgsH;                      // vg_batch_h_defs.h
 struct BatchArgsI8;                     // vg_batch_i8.hip
 struct BatchArgsBits;                   // vg_batch_bits_defs.h
 struct BatchArgsBitsGather;             // vg_batch_bits_defs.h
+struct BatchArgsBitsLabeled;            // vg_batch_bits_defs.h
 
 extern "C" {
 
@@ -64,6 +65,15 @@ int vg_batch_bits_masked_launch(const uint8_t *dev_rows, long long n_rows, long 
                                 uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
 int vgbb_launch_gather_pre(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream);
 int vgbb_launch_gather_real(const BatchArgsBitsGather *a, int variant, int blocks, size_t smem, hipStream_t stream);
+// its labeled form (-DVGBB_TU_LABELED: real pass and entry points; -DVGBB_TU_LABELED_PRE), rows of up to 128 bytes only: dev_labels holds
+// a label per scan position (n_rows dwords), dev_qlabels one per query (nq_pad dwords, 0xFFFFFFFF for the padding queries); a query's
+// list takes rows of its own label only
+size_t vg_batch_bits_labeled_lds_bytes(long long stride_bytes, int k);     // 0: rows / k it does not serve
+int vg_batch_bits_labeled_launch(const uint8_t *dev_rows, long long n_rows, long long stride_bytes, const uint32_t *dev_labels,
+                                 const uint8_t *dev_queries, const uint32_t *dev_qlabels, int nq_pad, int nq_real, int k, int jaccard,
+                                 uint64_t *dev_cand, int npart, uint64_t *dev_out_keys, hipStream_t stream);
+int vgbb_launch_labeled_pre(const BatchArgsBitsLabeled *a, int variant, int blocks, size_t smem, hipStream_t stream);
+int vgbb_launch_labeled_real(const BatchArgsBitsLabeled *a, int variant, int blocks, size_t smem, hipStream_t stream);
 // ---- vg_batch_bitsl.hip: its long-row form (rows of 129 .. 512 bytes, the K dimension split over the wavefronts of a workgroup), reached
 // through the three entry points above
 size_t vg_batch_bitsl_lds_bytes(long long stride_bytes, int k);

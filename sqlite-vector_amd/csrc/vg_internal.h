@@ -183,6 +183,7 @@ struct vg_corpus {
     size_t mask_pos_bytes = 0;
     bool mask_pos_valid = false;
     int last_batch_masked_path = 0;           // vg_batch_masked_last_path (vectorgpu_diag.h)
+    int last_batch_labeled_path = 0;          // vg_batch_labeled_last_path (vectorgpu_diag.h)
     // labeled scans (vg_rowpred.hip, vg_multi_labeled.hip): a uint32 per scan position in device memory (VG_LABEL_NONE: the row
     // matches no query).  Read by the labeled scans only; lifetime rule for rule the mask's (vg_drop_labels).  d_label_bits: the bitmap
     // "rows the query may see" a row predicate's scan builds for itself (vg_pred_bits_enqueue) - scratch, never the user's mask
@@ -483,6 +484,12 @@ int vg_launch_merge_capped(const uint64_t *dev_cand, int nlists, int k, int per_
 int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                        uint64_t *out_keys, int *out_counts, const uint32_t *qlabels = nullptr, uint32_t *out_labels = nullptr,
                        const VgMemberForm *member = nullptr);
+// its two halves (vg_multi_masked.hip), for a batch with a path of its own in between: the argument checks and refusals (the counts are
+// zero behind them; *nothing: the answer is complete as it stands, no launch), then the scans (*path: 5 multi-query, 6 single scans)
+int vg_fused_batch_check(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                         uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member, bool *nothing);
+int vg_fused_batch_scan(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+                        uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member, int *path);
 // vg_scan_masked.hip: the winners' keys as rows - query i's counts[i] keys at keys + i * k become (rowid, distance[, label]) at
 // out_* + i * k.  labels / out_labels: both or neither; a single scan is nq = 1
 void vg_keys_to_rows(const vg_corpus *c, const uint64_t *keys, const uint32_t *labels, int nq, int k, const int *counts, int64_t *out_rowids,
@@ -600,6 +607,9 @@ bool vg_batch_keys_are_scan_exact(const vg_corpus *c, int metric, int k);   // v
 // vg_batch_api.hip: a masked bit-vector batch on the matrix cores, behind vg_scan_topk_batch_masked_keys' checks (a mask with allowed
 // rows is set, out_counts are zero); -1: not served / handed on - the multi-query scan answers, the counts are zero again
 int vg_batch_bits_masked_try(vg_corpus *c, int metric, const void *queries, int nq, int k, uint64_t *out_keys, int *out_counts);
+// vg_batch_api.hip: a labeled bit-vector batch on the matrix cores (rows of up to 128 bytes), behind vg_scan_topk_batch_labeled_keys'
+// checks (labels are set, no query label is VG_LABEL_NONE, out_counts are zero); -1: not such a batch, the multi-query scan answers
+int vg_batch_bits_labeled_try(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *qlabels, int k, uint64_t *out_keys, int *out_counts);
 // vg_batch_api.hip: the handle's mask (mask_count > 0) as the list the gathering kernels walk (d_mask_pos), built on the corpus stream
 // when the mask changed since the last one was; the masked top-k batch and the masked range batch (vg_multi_within.hip) share it
 int vg_ensure_mask_positions(vg_corpus *c);

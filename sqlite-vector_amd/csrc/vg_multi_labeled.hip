@@ -8,6 +8,7 @@
 // distinct labels as possible, which is what lets a pass skip the batches of rows that carry none of them - and the results are
 // scattered back to caller order.  A pad query of a ragged last pass carries VG_LABEL_NONE and matches nothing.  Shapes without a
 // multi-query form (f16 / bf16, long rows): one single labeled scan per query (vg_rowpred.hip), one bitmap per distinct label.
+// Hamming / Jaccard batches over rows of up to 128 bytes go to the integer matrix cores in front of all that.
 #include "vg_internal.h"
 
 #include "vg_scan_multi.h"
@@ -29,12 +30,23 @@ extern "C" int vg_scan_topk_batch_labeled_keys(vg_corpus *c, int metric, const v
     const std::vector<int> order = vg_stable_order(nq, [&](int x, int y) { return query_labels[x] < query_labels[y]; });
     std::vector<uint32_t> sl((size_t)nq);
     for (int i = 0; i < nq; ++i) sl[(size_t)i] = query_labels[order[(size_t)i]];
+    // Inside the ordered run: the shared routine's checks and refusals first, then - bit-vector batches the matrix cores serve
+    // (vg_batch_bits_labeled_try, vg_batch_api.hip: the labeled form of vg_batch_bits.hip, rows of up to 128 bytes; -1: not such a
+    // batch) - that form, and everything else, as before, through the scans
     return vg_ordered_batch(c, queries, nq, k, order, out_keys, out_counts, [&](const void *sq, uint64_t *skeys, int *scounts) {
-        int rc = vg_fused_batch_run(c, form, metric, sq, nq, k, nullptr, skeys, scounts, sl.data());
+        bool nothing = false;
+        int rc = vg_fused_batch_check(c, form, metric, sq, nq, k, nullptr, skeys, scounts, sl.data(), nullptr, nullptr, &nothing);
+        if (rc == VG_OK && !nothing) {
+            int path = 8;
+            rc = vg_batch_bits_labeled_try(c, metric, sq, nq, sl.data(), k, skeys, scounts);
+            if (rc == -1) rc = vg_fused_batch_scan(c, form, metric, sq, nq, k, nullptr, skeys, scounts, sl.data(), nullptr, nullptr, &path);
+            c->last_batch_labeled_path = path;
+        }
         for (int i = 0; i < nq; ++i) out_counts[i] = 0;
         return rc;
     });
 }
+extern "C" int vg_batch_labeled_last_path(const vg_corpus *c) { return c ? c->last_batch_labeled_path : 0; }
 
 extern "C" int vg_scan_topk_batch_labeled(vg_corpus *c, int metric, const void *queries, int nq, const uint32_t *query_labels, int k,
                                           int64_t *out_rowids, double *out_dist, int *out_counts) {

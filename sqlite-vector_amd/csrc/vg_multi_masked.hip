@@ -166,9 +166,10 @@ static int fused_batch_multi(vg_corpus *c, const VgFusedBatchForm &f, int metric
     return VG_OK;
 }
 
-// vg_fused_batch_run's two halves, for a caller with a path of its own in between (vg_scan_topk_batch_masked_keys below).  fused_batch_check: the
+// vg_fused_batch_run's two halves, for a caller with a path of its own in between (vg_scan_topk_batch_masked_keys below, the labeled batch
+// of vg_multi_labeled.hip).  vg_fused_batch_check: the
 // argument checks; the counts are zero behind it; *nothing: the answer is complete as it stands (an empty mask, no rows) - no launch.
-static int fused_batch_check(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+int vg_fused_batch_check(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                              uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member,
                              bool *nothing) {
     *nothing = false;
@@ -191,8 +192,8 @@ static int fused_batch_check(vg_corpus *c, const VgFusedBatchForm &f, int metric
     HIP_TRY(hipSetDevice(c->device));
     return VG_OK;
 }
-// fused_batch_scan: the batch behind its checks - the multi-query scan (*path = 5) or the form's single scans (6)
-static int fused_batch_scan(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
+// vg_fused_batch_scan: the batch behind its checks - the multi-query scan (*path = 5) or the form's single scans (6)
+int vg_fused_batch_scan(vg_corpus *c, const VgFusedBatchForm &f, int metric, const void *queries, int nq, int k, const uint64_t *floors,
                             uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member,
                             int *path) {
     const bool grouped = f.single.result.with_labels();
@@ -231,9 +232,9 @@ int vg_fused_batch_run(vg_corpus *c, const VgFusedBatchForm &f, int metric, cons
                        uint64_t *out_keys, int *out_counts, const uint32_t *qlabels, uint32_t *out_labels, const VgMemberForm *member) {
     bool nothing = false;
     int path = 0;
-    const int rc = fused_batch_check(c, f, metric, queries, nq, k, floors, out_keys, out_counts, qlabels, out_labels, member, &nothing);
+    const int rc = vg_fused_batch_check(c, f, metric, queries, nq, k, floors, out_keys, out_counts, qlabels, out_labels, member, &nothing);
     if (rc != VG_OK || nothing) return rc;
-    return fused_batch_scan(c, f, metric, queries, nq, k, floors, out_keys, out_counts, qlabels, out_labels, member, &path);
+    return vg_fused_batch_scan(c, f, metric, queries, nq, k, floors, out_keys, out_counts, qlabels, out_labels, member, &path);
 }
 
 // The plain masked batch: behind the checks, bit-vector batches the matrix cores serve go through the position list of the mask
@@ -243,12 +244,12 @@ extern "C" int vg_scan_topk_batch_masked_keys(vg_corpus *c, int metric, const vo
     const VgFusedBatchForm form = {"vg_scan_topk_batch_masked", vg_pick_multi<MultiFamily<VG_MQ_MASKED>>, VG_QROWS_MASK,
                                    vg_fused_form("vg_scan_topk_masked", "masked", vg_pick_scan_masked, VG_ROWS_MASK)};
     bool nothing = false;
-    int rc = fused_batch_check(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts, nullptr, nullptr, nullptr, &nothing);
+    int rc = vg_fused_batch_check(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts, nullptr, nullptr, nullptr, &nothing);
     if (rc != VG_OK || nothing) return rc;
     rc = vg_batch_bits_masked_try(c, metric, queries, nq, k, out_keys, out_counts);
     if (rc != -1) { c->last_batch_masked_path = 8; return rc; }
     int path = 0;
-    rc = fused_batch_scan(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts, nullptr, nullptr, nullptr, &path);
+    rc = vg_fused_batch_scan(c, form, metric, queries, nq, k, nullptr, out_keys, out_counts, nullptr, nullptr, nullptr, &path);
     c->last_batch_masked_path = path;
     return rc;
 }

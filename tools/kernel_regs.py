@@ -5,7 +5,8 @@ prints name, VGPRs, spilled VGPRs, scratch bytes; without --all only kernels tha
 Every other argument goes to the compile: the batch units exist only under their unit flags (HIP_UNITS in build.py), for instance
 vg_batch_i8.hip -DVGI_TU_PRE, vg_batch_h.hip -DVGH_TU=1..8, vg_batch_hl.hip -DVGHL_TU=0..5, and vg_batch_bits.hip / vg_batch_bitsl.hip
 are built with -Xclang -target-feature -Xclang -packed-fp32-ops [-DVGBB_TU_PRE / -DVGBL_TU_PRE; the masked forms -DVGBB_TU_GATHER /
--DVGBB_TU_GATHER_PRE / -DVGBL_TU_GATHER / -DVGBL_TU_GATHER_PRE], their range forms
+-DVGBB_TU_GATHER_PRE / -DVGBL_TU_GATHER / -DVGBL_TU_GATHER_PRE; the labeled form of vg_batch_bits.hip -DVGBB_TU_LABELED /
+-DVGBB_TU_LABELED_PRE], their range forms
 vg_batch_bits_within.hip / vg_batch_bitsl_within.hip with the same two -Xclang pairs and no unit flag, the masked range form
 (the 8 GATHER instances of vg_batch_bits_within.hip) with -DVGBW_TU_GATHER.
 --digest: one line per kernel - VGPRs, SGPRs, spilled VGPRs / SGPRs, scratch, static LDS and a hash of the kernel's instruction text
